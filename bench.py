@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — train images/sec of the ConvAE hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,6 +16,10 @@ all-reduced inside libcae_hip (RCCL, two buckets, second stream, captured in the
 
 `value` times the hot path itself (the engine's epoch loop, K steps).  `train_api` (N = 1) is SURVEY §8(d)'s metric to the
 letter: ConvAEModel.train() on the same data, 20 epochs, a test pass every 10, images/s of its epoch loop.
+
+`--dump-outputs DIR` (rank 0) writes what the last timed step hands its caller, as DIR/<name>.npy: `loss` (float64) and the
+trained model state under its state_dict names (`encoder.*`, `decoder.*`, float32; num_batches_tracked left out).  Data,
+weights and shuffle are seeded, so two builds run with the same arguments can be compared file by file.
 
 Prints ONE JSON line on rank 0.
 """
@@ -172,6 +176,16 @@ def roofline_from_profile(recs, steps, trace_us=None):
             "algorithmic_bytes_per_launch": nbytes, "share_of_step": us_sum / total}, table, corrected_step
 
 
+def dump_outputs(out_dir, loss, state):
+    """DIR/loss.npy and DIR/<encoder|decoder>.<state_dict key>.npy"""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float64))
+    for side, sd in zip(("encoder", "decoder"), state):
+        for k, v in sd.items():
+            if v.is_floating_point():
+                np.save(os.path.join(out_dir, f"{side}.{k}.npy"), v.numpy().astype(np.float32))
+
+
 def main():
     # stdout carries exactly ONE line (the JSON): libraries that print banners to fd 1 (RCCL does under
     # NCCL_DEBUG=VERSION) are diverted to stderr for the whole run
@@ -189,6 +203,8 @@ def main():
     ap.add_argument("--dp-host-allreduce", action="store_true",
                     help="data-parallel runs: torch.distributed all-reduce between two library calls instead of the in-library RCCL path")
     ap.add_argument("--launch-order", default=None, help="write the per-step launch sequence [label, algorithmic bytes] here")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and the trained model state as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -226,6 +242,8 @@ def main():
     steps_per_epoch = N_TRAIN // global_batch
     dp_graph = None
     dp_times = {}
+    # loss slot of the last step run: the engine's epoch loops restart at slot 0 every steps_per_epoch steps
+    last_slot = [None]
 
     if dist is None:
         def run(nsteps):
@@ -275,7 +293,7 @@ def main():
 
             def run(nsteps):
                 for k in range(nsteps):
-                    dp.train_step(0, perm, (k % steps_per_epoch) * global_batch + lo, hi - lo, global_batch)
+                    last_slot[0] = dp.train_step(0, perm, (k % steps_per_epoch) * global_batch + lo, hi - lo, global_batch)
 
     def barrier():
         if dist is not None:
@@ -303,6 +321,18 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:      # before the profiling steps below move the model on
+        slot = last_slot[0] if last_slot[0] is not None else (args.steps - 1) % steps_per_epoch
+        if dist is not None and native:
+            loss = eng.dp_read_losses(slot, 1)[0]      # a collective: every rank takes part
+        else:
+            loss = eng._read_losses(slot, 1)[0]
+            if dist is not None:                       # each rank's slot holds its share of the global-batch mean
+                lt = torch.tensor([loss], dtype=torch.float64, device=device)
+                dist.all_reduce(lt)
+                loss = float(lt.item())
+        if rank == 0:
+            dump_outputs(args.dump_outputs, loss, eng.export_state())
     eng._read_losses(0, min(steps_per_epoch, eng.loss_slots))  # drain loss slots (outside the timed region)
 
     result = None

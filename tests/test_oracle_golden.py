@@ -10,7 +10,14 @@ import torch
 from helpers import GOLDEN, MODEL_CASES, GoldenCase, projections, subsample
 from oracle import cae_oracle as orc
 
-torch.set_num_threads(1)
+
+@pytest.fixture(autouse=True)
+def _one_thread():
+    """the golden vectors were summed on one thread; tests in other modules change the process-wide count"""
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    yield
+    torch.set_num_threads(n)
 
 
 def _model(case, prefix="init/"):

@@ -6,7 +6,14 @@ import torch
 
 from unet_helpers import TRAIN_CASES, UNET_CASES, UnetCase, unet_oracle
 
-torch.set_num_threads(1)
+
+@pytest.fixture(autouse=True)
+def _one_thread():
+    """the golden vectors were summed on one thread; tests in other modules change the process-wide count"""
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    yield
+    torch.set_num_threads(n)
 
 
 @pytest.mark.parametrize("name", UNET_CASES)
