@@ -11,63 +11,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CaeError, LayerSpecC, TensorInfoC, check
-
-TRAIN, TEST = 0, 1
-
-
-def _spec_layers(spec):
-    """accept a ModelSpec-like object or its JSON dict; return two lists of plain dicts"""
-    if hasattr(spec, "save"):
-        spec = spec.save()
-    return spec["input_layers"], spec["output_layers"]
+from ._engine_base import TEST, TRAIN, SpecPlan, _spec_layers, _to_c, require_gpu  # noqa: F401  (public names)
+from ._lib import CaeError, check
 
 
-def _to_c(layers):
-    arr = (LayerSpecC * len(layers))()
-    for i, l in enumerate(layers):
-        k = l["kernel_size"]
-        (kh, kw) = (int(k[0]), int(k[1])) if isinstance(k, (list, tuple)) else (int(k), int(k))
-        (ic, ih, iw) = l["input_dimensions"]
-        (oc, oh, ow) = l["output_dimensions"]
-        arr[i] = LayerSpecC(ic, ih, iw, oc, oh, ow, kh, kw, int(l["stride"]), int(l.get("output_padding", 0)))
-    return arr
-
-
-class EnginePlan:
+class EnginePlan(SpecPlan):
     """Geometry-only view of an engine (no GPU needed): tensor table, arena and workspace sizes."""
 
-    def __init__(self, spec, fc_size, latent_size, max_batch):
-        self.lib = _lib.load()
-        (enc, dec) = _spec_layers(spec)
-        self.enc_layers, self.dec_layers = enc, dec
-        self.fc_size, self.latent_size, self.max_batch = int(fc_size), int(latent_size), int(max_batch)
-        handle = C.c_void_p()
-        check(self.lib.cae_engine_create(_to_c(enc), len(enc), _to_c(dec), len(dec), self.fc_size,
-                                         self.latent_size, self.max_batch, C.byref(handle)))
-        self.handle = handle
-        self.n_param = int(self.lib.cae_param_count(handle))
-        self.n_buffer = int(self.lib.cae_buffer_count(handle))
-        self.workspace_bytes = int(self.lib.cae_workspace_bytes(handle))
-        self.tensors = OrderedDict()
-        info = TensorInfoC()
-        for i in range(self.lib.cae_tensor_count(handle)):
-            check(self.lib.cae_tensor_info(handle, i, C.byref(info)))
-            shape = tuple(int(info.shape[d]) for d in range(info.ndim))
-            self.tensors[info.name.decode()] = (int(info.arena), int(info.offset), int(info.numel), shape)
-        self.in_shape = tuple(enc[0]["input_dimensions"])
-        self.out_shape = tuple(dec[-1]["output_dimensions"])
-
-    def close(self):
-        if getattr(self, "handle", None) is not None and self.handle.value:
-            self.lib.cae_engine_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    PREFIX = "cae_"
 
     def bn_prefixes(self):
         """state_dict prefixes ("enc/encoder_cnn.1") of the BatchNorm layers, in order"""
@@ -77,25 +28,9 @@ class EnginePlan:
 class HipEngine(EnginePlan):
 
     def __init__(self, spec, fc_size, latent_size, max_batch, device=None, graph=True, specialised=True):
-        if not torch.cuda.is_available():
-            raise CaeError("cae_tools_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
-                           "there is no CPU fallback")
+        require_gpu()
         super().__init__(spec, fc_size, latent_size, max_batch)
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
-        with torch.cuda.device(self.device):
-            self.stream = torch.cuda.Stream()
-        f32 = dict(dtype=torch.float32, device=self.device)
-        self.params = torch.zeros(self.n_param, **f32)
-        self.grads = torch.zeros(self.n_param, **f32)
-        self.exp_avg = torch.zeros(self.n_param, **f32)
-        self.exp_avg_sq = torch.zeros(self.n_param, **f32)
-        self.buffers = torch.zeros(max(self.n_buffer, 4), **f32)
-        self.workspace = torch.zeros(self.workspace_bytes + 256, dtype=torch.uint8, device=self.device)
-        ws_ptr = (self.workspace.data_ptr() + 255) // 256 * 256
-        check(self.lib.cae_bind(self.handle, self.params.data_ptr(), self.grads.data_ptr(),
-                                self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.buffers.data_ptr(),
-                                ws_ptr, self.workspace_bytes))
-        check(self.lib.cae_set_stream(self.handle, self.stream.cuda_stream))
+        self._bind(device, grads=True, buffers=True)
         check(self.lib.cae_set_graph_mode(self.handle, 1 if graph else 0))
         check(self.lib.cae_set_kernel_mode(self.handle, int(specialised) if isinstance(specialised, int) and not isinstance(specialised, bool) else (1 if specialised else 0)))
         torch.cuda.synchronize(self.device)
@@ -108,54 +43,15 @@ class HipEngine(EnginePlan):
         self._cursor = None     # host shadow of the device cursor (batch_start, loss_slot); None = unknown
 
     # ---- parameters ------------------------------------------------------------------------
-    def _arena(self, arena):
-        return self.params if arena == 0 else self.buffers
-
-    def view(self, name):
-        """torch view (device) of a named tensor, e.g. 'dec/decoder_conv.0.weight'"""
-        (arena, off, numel, shape) = self.tensors[name]
-        return self._arena(arena)[off:off + numel].view(shape)
-
     def grad_view(self, name):
         (arena, off, numel, shape) = self.tensors[name]
         assert arena == 0
         return self.grads[off:off + numel].view(shape)
 
-    def load_state(self, enc_state, dec_state):
-        """copy reference-format state dicts (encoder.weights / decoder.weights) into the arenas"""
-        self.sync()
-        nbt = None
-        for prefix, sd in (("enc/", enc_state), ("dec/", dec_state)):
-            for k, v in sd.items():
-                if k.endswith("num_batches_tracked"):
-                    nbt = int(np.asarray(v)) if nbt is None else nbt
-                    continue
-                name = prefix + k
-                if name not in self.tensors:
-                    raise CaeError(f"unexpected tensor '{k}' for this model geometry")
-                t = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).to(torch.float32)
-                dst = self.view(name)
-                if tuple(t.shape) != tuple(dst.shape):
-                    raise CaeError(f"shape mismatch for '{k}': {tuple(t.shape)} vs {tuple(dst.shape)}")
-                dst.copy_(t.to(self.device))
-        missing = [n for n in self.tensors if (n[4:] not in (enc_state if n.startswith("enc/") else dec_state))]
-        if missing:
-            raise CaeError(f"state dict is missing {missing[:3]}...")
-        if nbt is not None:
-            self.num_batches_tracked = nbt
-        torch.cuda.synchronize(self.device)
-
     def export_state(self):
         """(encoder_state, decoder_state) as CPU tensors under the reference's state_dict keys and
         order, including num_batches_tracked"""
-        self.sync()
-        enc, dec = OrderedDict(), OrderedDict()
-        for name in self.tensors:
-            side = enc if name.startswith("enc/") else dec
-            side[name[4:]] = self.view(name).detach().cpu().clone()
-            if name.endswith(".running_var"):
-                side[name[4:-len("running_var")] + "num_batches_tracked"] = torch.tensor(
-                    self.num_batches_tracked, dtype=torch.int64)
+        (enc, dec) = super().export_state()
         # state_dict order of nn.BatchNorm2d: weight, bias, running_mean, running_var, num_batches_tracked
         return self._ordered(enc), self._ordered(dec)
 
@@ -500,21 +396,7 @@ class HipEngine(EnginePlan):
 
     def score(self, x):
         """eval-mode forward of an explicit batch (B,C,H,W) fp32 CUDA tensor -> (B,C,H,W)"""
-        if x.dtype != torch.float32 or not x.is_cuda:
-            raise CaeError("score() needs an fp32 CUDA tensor")
-        self._same_device(x, "score() input")
-        x = x.contiguous()
-        out = torch.empty((x.shape[0],) + tuple(self.out_shape), dtype=torch.float32, device=self.device)
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        done = 0
-        while done < x.shape[0]:
-            n = min(self.max_batch, x.shape[0] - done)
-            check(self.lib.cae_score(self.handle, x[done:done + n].data_ptr(), n, out[done:done + n].data_ptr()))
-            done += n
-        torch.cuda.current_stream(self.device).wait_stream(self.stream)
-        x.record_stream(self.stream)
-        out.record_stream(self.stream)
-        return out
+        return self._module_forward(self.lib.cae_score, x, self.out_shape, "score")
 
     def _module_forward(self, fn, x, row_shape, what):
         if x.dtype != torch.float32 or not x.is_cuda:
@@ -522,12 +404,7 @@ class HipEngine(EnginePlan):
         self._same_device(x, f"{what}() input")
         x = x.contiguous()
         out = torch.empty((x.shape[0],) + tuple(row_shape), dtype=torch.float32, device=self.device)
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        done = 0
-        while done < x.shape[0]:
-            n = min(self.max_batch, x.shape[0] - done)
-            check(fn(self.handle, x[done:done + n].data_ptr(), n, out[done:done + n].data_ptr()))
-            done += n
+        self._chunked(fn, x, out)
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
         x.record_stream(self.stream)
         out.record_stream(self.stream)
@@ -544,9 +421,6 @@ class HipEngine(EnginePlan):
         if z.dim() != 2 or z.shape[1] != self.latent_size:
             raise CaeError(f"decode() expects (batch, {self.latent_size}), got {tuple(z.shape)}")
         return self._module_forward(self.lib.cae_decode, z, self.out_shape, "decode")
-
-    def sync(self):
-        check(self.lib.cae_sync(self.handle))
 
     # ---- measurement -----------------------------------------------------------------------
     def profile_begin(self):

@@ -2,17 +2,19 @@
 (src/cae_tools/models/base_model.py): model id (:33,56-61), io-spec accessors (:35-54),
 evaluate (:69-100), apply (:102-152), dump_metrics (:154-157), save/load of input_spec.json /
 output_spec.json (:162-180).  Scoring, denormalisation and the metric reductions run on the GPU
-through libcae_hip; only per-case sums and the final fp64 predictions cross PCIe."""
+through libcae_hip; only per-case sums and the final fp64 predictions cross PCIe.
+EngineModel is what the four engine-backed models (ConvAE, UNET, VarAE, Linear) share on top of that."""
 import json
 import os
+import time
 import uuid
 
-import numpy as np
 import torch
 
 from ..data.arrays import DataArray
 from .ds_dataset import DSDataset
 from .model_metric import DeviceModelMetric, ModelMetric  # noqa: F401
+from .model_sizer import ModelSpec, create_model_spec
 
 
 def _make_data_array(like_ds, data, dims):
@@ -21,6 +23,14 @@ def _make_data_array(like_ds, data, dims):
         import xarray as xr
         return xr.DataArray(data, dims=dims)
     return DataArray(data, dims=dims)
+
+
+def _index_batches(n, batch_size):
+    """the sample order a reference DataLoader(dataset, batch_size, shuffle=True) produces: drawn
+    from torch's global generator exactly as RandomSampler does, so the same seed gives the same
+    batches (conv_ae_model.py:291-292, 315-325)"""
+    loader = torch.utils.data.DataLoader(torch.arange(n), batch_size=batch_size, shuffle=True)
+    return torch.cat([b for b in loader]).to(torch.int32).numpy()
 
 
 class BaseModel:
@@ -143,3 +153,168 @@ class BaseModel:
 
     def get_parameters(self):
         pass  # implement in sub-class
+
+
+class EngineModel(BaseModel):
+    """What the libcae_hip-backed models share: host weight containers mirrored by one engine, the model folder, and the
+    parts of train() around the epoch loop.  This base implements the spec-driven encoder / decoder models; a sub-class
+    supplies MODEL_TYPE (its model-database type), PARAM_KEYS (parameters.json entries load() restores), _modules() and
+    _make_engine(max_batch)."""
+
+    MODEL_TYPE = None
+    PARAM_KEYS = ()
+    OPTIONAL_PARAM_KEYS = ("conv_kernel_size", "conv_stride", "conv_input_layer_count", "conv_output_layer_count")
+
+    def _modules(self):
+        """fresh host weight containers for the current spec / shapes"""
+        raise NotImplementedError
+
+    def _make_engine(self, max_batch):
+        raise NotImplementedError
+
+    def _weight_files(self):
+        """model-folder file name -> host container, in save order"""
+        return {"encoder.weights": self.encoder, "decoder.weights": self.decoder}
+
+    def _spec_record(self):
+        """the spec as stored in spec.json and the model database"""
+        return self.spec.save()
+
+    # ---- engine ----------------------------------------------------------------------------
+    def _load_engine(self, eng):
+        """host state -> a new engine"""
+        eng.load_state(self.encoder.state_dict(), self.decoder.state_dict())
+
+    def _pull_weights(self):
+        """device arenas -> the host containers (state_dict source for save())"""
+        if self._engine is not None:
+            (enc, dec) = self._engine.export_state()
+            self.encoder.load_state_dict(enc)
+            self.decoder.load_state_dict(dec)
+
+    def _get_engine(self, max_batch):
+        """the engine, re-created (weights carried over) when it cannot take max_batch rows"""
+        if self._engine is None or self._engine.max_batch < max_batch:
+            if self._engine is not None:
+                self._pull_weights()
+            eng = self._make_engine(max_batch)
+            self._load_engine(eng)
+            self._engine = eng
+        return self._engine
+
+    def _score_device(self, x):
+        return self._get_engine(max(1, min(int(self.batch_size), int(x.shape[0])))).score(x)
+
+    def score(self, batches, save_arr):
+        """eval-mode forward of a list of (B,C,H,W) batches into save_arr"""
+        ctr = 0
+        for batch in batches:
+            x = torch.as_tensor(batch, dtype=torch.float32)
+            y = self._score_device(x.cuda() if not x.is_cuda else x).cpu().numpy()
+            save_arr[ctr:ctr + y.shape[0], :, :, :] = y
+            ctr += self.batch_size
+
+    # ---- persistence -----------------------------------------------------------------------
+    def save(self, to_folder):
+        os.makedirs(to_folder, exist_ok=True)
+        self._pull_weights()
+        for fname, module in self._weight_files().items():
+            torch.save(module.state_dict(), os.path.join(to_folder, fname))
+        spec = self._spec_record()
+        text_files = {"normalisation.weights": json.dumps(self.normalisation_parameters),
+                      "parameters.json": json.dumps(self.get_parameters())}
+        if spec:    # LinearModel has none
+            text_files["spec.json"] = json.dumps(spec)
+        text_files.update({"history.json": json.dumps(self.history), "summary.txt": self.summary()})
+        for fname, text in text_files.items():
+            with open(os.path.join(to_folder, fname), "w") as f:
+                f.write(text)
+        super().save(to_folder)
+
+    def _load_modules(self, from_folder):
+        with open(os.path.join(from_folder, "spec.json")) as f:
+            self.spec = ModelSpec()
+            self.spec.load(json.loads(f.read()))
+        self._modules()
+
+    def load(self, from_folder):
+        with open(os.path.join(from_folder, "normalisation.weights")) as f:
+            self.normalisation_parameters = json.loads(f.read())
+        with open(os.path.join(from_folder, "parameters.json")) as f:
+            p = json.loads(f.read())
+        if "model_id" in p:
+            self.set_model_id(p["model_id"])
+        self.input_shape, self.output_shape = tuple(p["input_shape"]), tuple(p["output_shape"])
+        for key in self.PARAM_KEYS:
+            setattr(self, key, p[key])
+        for key in self.OPTIONAL_PARAM_KEYS:
+            setattr(self, key, p.get(key, None))
+        with open(os.path.join(from_folder, "history.json")) as f:
+            self.history = json.loads(f.read())
+        self._load_modules(from_folder)
+        for fname, module in self._weight_files().items():
+            module.load_state_dict(self.torch_load(os.path.join(from_folder, fname)))
+        self._engine = None
+        super().load(from_folder)
+
+    # ---- training --------------------------------------------------------------------------
+    def _progress(self, message):
+        """a progress line of train()'s set-up; only UNET prints them"""
+
+    def _build(self):
+        """spec and host containers for a model trained from scratch (kept when training continues)"""
+        if not self.spec:
+            (input_chan, input_y, input_x) = self.input_shape
+            (output_chan, output_y, output_x) = self.output_shape
+            self.spec = create_model_spec(input_size=(input_y, input_x), input_channels=input_chan,
+                                          output_size=(output_y, output_x), output_channels=output_chan,
+                                          kernel_size=self.conv_kernel_size, stride=self.conv_stride,
+                                          input_layer_count=self.conv_input_layer_count,
+                                          output_layer_count=self.conv_output_layer_count)
+        if not self.encoder or not self.decoder:
+            self._modules()
+
+    def _train_prologue(self, input_variables, output_variable, training_ds, testing_ds, mask_variable_name=None):
+        """both data sets (normalisation from the training set), specs, shapes, the model, and the frozen shuffles drawn
+        in the reference's order (training loader first): (train_ds, test_ds, train_perm, test_perm)"""
+        self._progress("initiating train method")
+        train_ds = DSDataset(training_ds, input_variables, output_variable, normalise_in=self.normalise_input,
+                             normalise_out=self.normalise_output, mask_variable_name=mask_variable_name)
+        self._progress("loaded train_ds to train method")
+        self.normalisation_parameters = train_ds.get_normalisation_parameters()
+        self.set_input_spec(train_ds.get_input_spec())
+        self.set_output_spec(train_ds.get_output_spec())
+        test_ds = DSDataset(testing_ds, input_variables, output_variable, normalise_in=self.normalise_input,
+                            normalise_out=self.normalise_output, mask_variable_name=mask_variable_name)
+        test_ds.set_normalisation_parameters(self.normalisation_parameters)
+        self.input_shape = tuple(train_ds.get_input_shape())
+        self.output_shape = tuple(train_ds.get_output_shape())
+        self._progress("finished loading train_ds and test_ds from DSDataset")
+        self._build()
+        train_perm = _index_batches(len(train_ds), self.batch_size)
+        test_perm = _index_batches(len(test_ds), self.batch_size)
+        self._progress("finished train_loarder and test_loader")
+        return train_ds, test_ds, train_perm, test_perm
+
+    def _train_epilogue(self, start, train_ds, test_ds, train_loss, test_loss, input_variables, output_variable, model_path,
+                        training_paths, testing_paths, lead=True):
+        """after the epoch loop: history, database records, save (or pull the weights to the host) and the metrics of
+        both data sets.  Only the lead rank of a data-parallel run prints, saves and records; every rank evaluates."""
+        self.history["nr_epochs"] += self.nr_epochs
+        if lead:
+            print("elapsed:" + str(time.time() - start))
+        if self.db and lead:
+            self.db.add_training_result(self.get_model_id(), self.MODEL_TYPE, output_variable, input_variables,
+                                        self.summary(), model_path, training_paths, train_loss, testing_paths, test_loss,
+                                        self.get_parameters(), self._spec_record())
+        if model_path and lead:
+            self.save(model_path)
+        else:
+            self._pull_weights()
+        metrics = {"test": self.evaluate(test_ds), "train": self.evaluate(train_ds)}
+        if lead:
+            self.dump_metrics("Test Metrics", metrics["test"])
+            self.dump_metrics("Train Metrics", metrics["train"])
+        if self.db and lead:
+            self.db.add_evaluation_result(self.get_model_id(), training_paths, testing_paths, metrics)
+        return metrics

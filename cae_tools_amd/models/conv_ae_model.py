@@ -10,8 +10,6 @@ implements the intended behaviour: DSDataset's 4-tuples are accepted, train() ta
 mask_variable_name the CLI passes (ignored by the 'conv' method: its loss is plain MSE), and the
 evaluation mask covers every output pixel.
 """
-import json
-import os
 import time
 
 import numpy as np
@@ -19,23 +17,18 @@ import torch
 
 from .. import dp as _dp
 from .. import engine as _eng
-from .base_model import BaseModel
-from .model_sizer import create_model_spec, ModelSpec
-from .ds_dataset import DSDataset
+from .base_model import EngineModel
+from .ds_dataset import DSDataset  # noqa: F401  (this module's public name since before EngineModel built the data sets)
 from .encoder import Encoder
 from .decoder import Decoder
 from ..utils.model_database import ModelDatabase
 
 
-def _index_batches(n, batch_size):
-    """the sample order a reference DataLoader(dataset, batch_size, shuffle=True) produces: drawn
-    from torch's global generator exactly as RandomSampler does, so the same seed gives the same
-    batches (conv_ae_model.py:291-292, 315-325)"""
-    loader = torch.utils.data.DataLoader(torch.arange(n), batch_size=batch_size, shuffle=True)
-    return torch.cat([b for b in loader]).to(torch.int32).numpy()
+class ConvAEModel(EngineModel):
 
-
-class ConvAEModel(BaseModel):
+    MODEL_TYPE = "ConvAE"
+    PARAM_KEYS = ("batch_size", "test_interval", "encoded_dim_size", "fc_size", "lr", "weight_decay", "normalise_input",
+                  "normalise_output")
 
     def __init__(self, normalise_input=True, normalise_output=True, batch_size=10,
                  nr_epochs=500, test_interval=10, encoded_dim_size=32, fc_size=128,
@@ -91,84 +84,29 @@ class ConvAEModel(BaseModel):
             "model_id": self.get_model_id(),
         }
 
-    def _pull_weights(self):
-        """device arenas -> the host Encoder/Decoder containers (state_dict source for save())"""
-        if self._engine is not None:
-            (enc, dec) = self._engine.export_state()
-            self.encoder.load_state_dict(enc)
-            self.decoder.load_state_dict(dec)
-
-    def save(self, to_folder):
-        os.makedirs(to_folder, exist_ok=True)
-        self._pull_weights()
-        torch.save(self.encoder.state_dict(), os.path.join(to_folder, "encoder.weights"))
-        torch.save(self.decoder.state_dict(), os.path.join(to_folder, "decoder.weights"))
-        text_files = {
-            "normalisation.weights": json.dumps(self.normalisation_parameters),
-            "parameters.json": json.dumps(self.get_parameters()),
-            "spec.json": json.dumps(self.spec.save()),
-            "history.json": json.dumps(self.history),
-            "summary.txt": self.summary(),
-        }
-        for fname, text in text_files.items():
-            with open(os.path.join(to_folder, fname), "w") as f:
-                f.write(text)
-        super().save(to_folder)
-
-    def load(self, from_folder):
-        with open(os.path.join(from_folder, "normalisation.weights")) as f:
-            self.normalisation_parameters = json.loads(f.read())
-        with open(os.path.join(from_folder, "parameters.json")) as f:
-            p = json.loads(f.read())
-        if "model_id" in p:
-            self.set_model_id(p["model_id"])
-        self.input_shape = tuple(p["input_shape"])
-        self.output_shape = tuple(p["output_shape"])
-        for key in ("batch_size", "test_interval", "encoded_dim_size", "fc_size", "lr", "weight_decay",
-                    "normalise_input", "normalise_output"):
-            setattr(self, key, p[key])
-        for key in ("conv_kernel_size", "conv_stride", "conv_input_layer_count", "conv_output_layer_count"):
-            setattr(self, key, p.get(key, None))
-        with open(os.path.join(from_folder, "history.json")) as f:
-            self.history = json.loads(f.read())
-        with open(os.path.join(from_folder, "spec.json")) as f:
-            self.spec = ModelSpec()
-            self.spec.load(json.loads(f.read()))
+    def _modules(self):
         self.encoder = Encoder(self.spec.get_input_layers(), encoded_space_dim=self.encoded_dim_size, fc_size=self.fc_size)
         self.decoder = Decoder(self.spec.get_output_layers(), encoded_space_dim=self.encoded_dim_size, fc_size=self.fc_size)
-        self.encoder.load_state_dict(self.torch_load(os.path.join(from_folder, "encoder.weights")))
-        self.decoder.load_state_dict(self.torch_load(os.path.join(from_folder, "decoder.weights")))
+
+    def load(self, from_folder):
+        super().load(from_folder)
         self.encoder.eval()
         self.decoder.eval()
-        self._engine = None
-        super().load(from_folder)
 
     # ---- engine ----------------------------------------------------------------------------
-    def _get_engine(self, max_batch):
-        if self._engine is None or self._engine.max_batch < max_batch:
-            if self._engine is not None:
-                self._pull_weights()
-            eng = _eng.HipEngine(self.spec, self.fc_size, self.encoded_dim_size, max_batch=max_batch)
-            eng.load_state(self.encoder.state_dict(), self.decoder.state_dict())
-            self.encoder.attach(eng)
-            self.decoder.attach(eng)
-            self._engine = eng
-        return self._engine
+    def _make_engine(self, max_batch):
+        return _eng.HipEngine(self.spec, self.fc_size, self.encoded_dim_size, max_batch=max_batch)
+
+    def _load_engine(self, eng):
+        super()._load_engine(eng)
+        self.encoder.attach(eng)
+        self.decoder.attach(eng)
 
     def _score_device(self, x):
         # an engine that exists is used as it is (score() walks the array in chunks of its max_batch)
-        eng = self._engine if self._engine is not None else self._get_engine(max(1, min(int(self.batch_size), int(x.shape[0]))))
-        return eng.score(x)
-
-    def score(self, batches, save_arr):
-        """eval-mode forward of a list of (B,C,H,W) batches into save_arr (:223-239)"""
-        ctr = 0
-        for batch in batches:
-            x = torch.as_tensor(batch, dtype=torch.float32)
-            x = x.cuda() if not x.is_cuda else x
-            y = self._score_device(x).cpu().numpy()
-            save_arr[ctr:ctr + y.shape[0], :, :, :] = y
-            ctr += self.batch_size
+        if self._engine is not None:
+            return self._engine.score(x)
+        return super()._score_device(x)
 
     # ---- training --------------------------------------------------------------------------
     def train(self, input_variables, output_variable, training_ds, testing_ds, model_path="", training_paths="",
@@ -179,33 +117,8 @@ class ConvAEModel(BaseModel):
         # a rank of a torch.distributed.run launch works on ITS GPU from the first allocation on (the data sets below
         # are uploaded to the current device, the engine is created on it)
         dist = _dp.ensure_process_group()
-        train_ds = DSDataset(training_ds, input_variables, output_variable,
-                             normalise_in=self.normalise_input, normalise_out=self.normalise_output)
-        self.normalisation_parameters = train_ds.get_normalisation_parameters()
-        self.set_input_spec(train_ds.get_input_spec())
-        self.set_output_spec(train_ds.get_output_spec())
-        test_ds = DSDataset(testing_ds, input_variables, output_variable,
-                            normalise_in=self.normalise_input, normalise_out=self.normalise_output)
-        test_ds.set_normalisation_parameters(self.normalisation_parameters)
-        self.input_shape = tuple(train_ds.get_input_shape())
-        self.output_shape = tuple(train_ds.get_output_shape())
-        (input_chan, input_y, input_x) = self.input_shape
-        (output_chan, output_y, output_x) = self.output_shape
-
-        if not self.spec:
-            self.spec = create_model_spec(input_size=(input_y, input_x), input_channels=input_chan,
-                                          output_size=(output_y, output_x), output_channels=output_chan,
-                                          kernel_size=self.conv_kernel_size, stride=self.conv_stride,
-                                          input_layer_count=self.conv_input_layer_count,
-                                          output_layer_count=self.conv_output_layer_count)
-        if not self.encoder:
-            self.encoder = Encoder(self.spec.get_input_layers(), encoded_space_dim=self.encoded_dim_size, fc_size=self.fc_size)
-        if not self.decoder:
-            self.decoder = Decoder(self.spec.get_output_layers(), encoded_space_dim=self.encoded_dim_size, fc_size=self.fc_size)
-
-        # frozen shuffles, drawn in the reference's order: training loader first, then test loader
-        train_perm = _index_batches(len(train_ds), self.batch_size)
-        test_perm = _index_batches(len(test_ds), self.batch_size)
+        (train_ds, test_ds, train_perm, test_perm) = self._train_prologue(input_variables, output_variable, training_ds,
+                                                                          testing_ds)
 
         # Data parallel (build-only; the reference selects ONE device at :294-297 and moves the modules there at :312-313):
         # under a torch.distributed.run launch every rank holds the model and both data sets, takes its rows of each frozen
@@ -264,27 +177,8 @@ class ConvAEModel(BaseModel):
         if par is not None:
             par.broadcast_buffers(0)
 
-        elapsed = time.time() - start
-        self.history["nr_epochs"] = self.history["nr_epochs"] + self.nr_epochs
-        if lead:
-            print("elapsed:" + str(elapsed))
-
-        if self.db and lead:     # :343-345
-            self.db.add_training_result(self.get_model_id(), "ConvAE", output_variable, input_variables, self.summary(),
-                                        model_path, training_paths, train_loss, testing_paths, test_loss,
-                                        self.get_parameters(), self.spec.save())
-        if model_path and lead:
-            self.save(model_path)
-        else:
-            self._pull_weights()
-
-        metrics = {"test": self.evaluate(test_ds), "train": self.evaluate(train_ds)}
-        if lead:
-            self.dump_metrics("Test Metrics", metrics["test"])
-            self.dump_metrics("Train Metrics", metrics["train"])
-        if self.db and lead:     # :358-359
-            self.db.add_evaluation_result(self.get_model_id(), training_paths, testing_paths, metrics)
-        return metrics
+        return self._train_epilogue(start, train_ds, test_ds, train_loss, test_loss, input_variables, output_variable,
+                                    model_path, training_paths, testing_paths, lead=lead)
 
     def summary(self):
         if not self.spec:

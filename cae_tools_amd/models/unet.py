@@ -15,8 +15,6 @@ What differs from the reference, on purpose:
   * with mask_variable_name=None and a one-channel input the reference's all-ones mask has the input's shape
     (ds_dataset.py:152-156); it is materialised here so that torch.sum(mask) counts what the reference counts.
 """
-import json
-import os
 import time
 
 import numpy as np
@@ -25,10 +23,8 @@ import torch
 from .. import unet_engine as _ue
 from ..utils.model_database import ModelDatabase
 from ._params import ParamBag, add_batchnorm, default_layer_init
-from .base_model import BaseModel
-from .conv_ae_model import _index_batches
-from .ds_dataset import DSDataset
-from .model_sizer import ModelSpec, create_model_spec
+from .base_model import EngineModel
+from .model_sizer import ModelSpec
 
 
 def _drawn(shape, n_bias):
@@ -139,7 +135,11 @@ def unet_layer_spec(input_channels, output_channels, size, channels, kernel_size
     return ModelSpec(enc, dec)
 
 
-class UNET(BaseModel):
+class UNET(EngineModel):
+
+    MODEL_TYPE = "UNET"
+    PARAM_KEYS = ("batch_size", "test_interval", "encoded_dim_size", "fc_size", "lr", "weight_decay", "normalise_input",
+                  "normalise_output")
 
     def __init__(self, normalise_input=True, normalise_output=True, batch_size=10, nr_epochs=500, test_interval=10,
                  encoded_dim_size=32, fc_size=128, lr=0.001, weight_decay=1e-5, dropout_rate=0.1, use_gpu=True,
@@ -204,111 +204,20 @@ class UNET(BaseModel):
                 + f"\tLatent Vector:\n\t\tsize={self.encoded_dim_size}\n" + fc
                 + "".join(str(l) for l in self.spec.output_layers))
 
-    def _pull_weights(self):
-        if self._engine is not None:
-            (enc, dec) = self._engine.export_state()
-            self.encoder.load_state_dict(enc)
-            self.decoder.load_state_dict(dec)
-
-    def save(self, to_folder):
-        os.makedirs(to_folder, exist_ok=True)
-        self._pull_weights()
-        torch.save(self.encoder.state_dict(), os.path.join(to_folder, "encoder.weights"))
-        torch.save(self.decoder.state_dict(), os.path.join(to_folder, "decoder.weights"))
-        for fname, text in {"normalisation.weights": json.dumps(self.normalisation_parameters),
-                            "parameters.json": json.dumps(self.get_parameters()),
-                            "spec.json": json.dumps(self.spec.save()),
-                            "history.json": json.dumps(self.history),
-                            "summary.txt": self.summary()}.items():
-            with open(os.path.join(to_folder, fname), "w") as f:
-                f.write(text)
-        super().save(to_folder)
-
-    def load(self, from_folder):
-        with open(os.path.join(from_folder, "normalisation.weights")) as f:
-            self.normalisation_parameters = json.loads(f.read())
-        with open(os.path.join(from_folder, "parameters.json")) as f:
-            p = json.loads(f.read())
-        if "model_id" in p:
-            self.set_model_id(p["model_id"])
-        self.input_shape = tuple(p["input_shape"])
-        self.output_shape = tuple(p["output_shape"])
-        for key in ("batch_size", "test_interval", "encoded_dim_size", "fc_size", "lr", "weight_decay", "normalise_input",
-                    "normalise_output"):
-            setattr(self, key, p[key])
-        for key in ("conv_kernel_size", "conv_stride", "conv_input_layer_count", "conv_output_layer_count"):
-            setattr(self, key, p.get(key, None))
-        with open(os.path.join(from_folder, "history.json")) as f:
-            self.history = json.loads(f.read())
-        with open(os.path.join(from_folder, "spec.json")) as f:
-            self.spec = ModelSpec()
-            self.spec.load(json.loads(f.read()))
+    def _modules(self):
         self.encoder = Encoder(self.spec.get_input_layers(), encoded_space_dim=self.encoded_dim_size, fc_size=self.fc_size,
                                dropout_rate=self.dropout_rate)
         self.decoder = Decoder(self.spec.get_output_layers(), encoded_space_dim=self.encoded_dim_size, fc_size=self.fc_size,
                                dropout_rate=self.dropout_rate)
-        self.encoder.load_state_dict(self.torch_load(os.path.join(from_folder, "encoder.weights")))
-        self.decoder.load_state_dict(self.torch_load(os.path.join(from_folder, "decoder.weights")))
-        self._engine = None
-        super().load(from_folder)
 
-    # ---- engine ----------------------------------------------------------------------------------------
-    def _get_engine(self, max_batch):
-        if self._engine is None or self._engine.max_batch < max_batch:
-            if self._engine is not None:
-                self._pull_weights()
-            eng = _ue.UnetEngine(self.spec, self.fc_size, self.encoded_dim_size, max_batch=max_batch)
-            eng.load_state(self.encoder.state_dict(), self.decoder.state_dict())
-            self._engine = eng
-        return self._engine
-
-    def _score_device(self, x):
-        eng = self._get_engine(max(1, min(int(self.batch_size), int(x.shape[0]))))
-        return eng.score(x)
-
-    def score(self, batches, save_arr):
-        """eval-mode forward of a list of (B,C,H,W) batches into save_arr (:373-382)"""
-        ctr = 0
-        for batch in batches:
-            x = torch.as_tensor(batch, dtype=torch.float32)
-            y = self._score_device(x.cuda() if not x.is_cuda else x).cpu().numpy()
-            save_arr[ctr:ctr + y.shape[0], :, :, :] = y
-            ctr += self.batch_size
+    def _make_engine(self, max_batch):
+        return _ue.UnetEngine(self.spec, self.fc_size, self.encoded_dim_size, max_batch=max_batch)
 
     # ---- training --------------------------------------------------------------------------------------
     def train(self, input_variables, output_variable, training_ds, testing_ds, model_path="", training_paths="",
               testing_paths="", mask_variable_name=None):
-        print("initiating train method")
-        train_ds = DSDataset(training_ds, input_variables, output_variable, normalise_in=self.normalise_input,
-                             normalise_out=self.normalise_output, mask_variable_name=mask_variable_name)
-        print("loaded train_ds to train method")
-        self.set_input_spec(train_ds.get_input_spec())
-        self.set_output_spec(train_ds.get_output_spec())
-        self.normalisation_parameters = train_ds.get_normalisation_parameters()
-        test_ds = DSDataset(testing_ds, input_variables, output_variable, normalise_in=self.normalise_input,
-                            normalise_out=self.normalise_output, mask_variable_name=mask_variable_name)
-        test_ds.set_normalisation_parameters(self.normalisation_parameters)
-        self.input_shape = tuple(train_ds.get_input_shape())
-        self.output_shape = tuple(train_ds.get_output_shape())
-        (input_chan, input_y, input_x) = self.input_shape
-        (output_chan, output_y, output_x) = self.output_shape
-        print("finished loading train_ds and test_ds from DSDataset")
-        if not self.spec:
-            self.spec = create_model_spec(input_size=(input_y, input_x), input_channels=input_chan,
-                                          output_size=(output_y, output_x), output_channels=output_chan,
-                                          kernel_size=self.conv_kernel_size, stride=self.conv_stride,
-                                          input_layer_count=self.conv_input_layer_count,
-                                          output_layer_count=self.conv_output_layer_count)
-        if not self.encoder:
-            self.encoder = Encoder(self.spec.get_input_layers(), encoded_space_dim=self.encoded_dim_size,
-                                   fc_size=self.fc_size, dropout_rate=self.dropout_rate)
-        if not self.decoder:
-            self.decoder = Decoder(self.spec.get_output_layers(), encoded_space_dim=self.encoded_dim_size,
-                                   fc_size=self.fc_size, dropout_rate=self.dropout_rate)
-        # frozen shuffles in the reference's order (:440-441, both loaders shuffle)
-        train_perm = _index_batches(len(train_ds), self.batch_size)
-        test_perm = _index_batches(len(test_ds), self.batch_size)
-        print("finished train_loarder and test_loader")
+        (train_ds, test_ds, train_perm, test_perm) = self._train_prologue(input_variables, output_variable, training_ds,
+                                                                          testing_ds, mask_variable_name)
         print(f"Running on device: {torch.device('cuda')}")
         start = time.time()
 
@@ -343,24 +252,11 @@ class UNET(BaseModel):
                     print(f"learn rate: {self.lr:.6f}")
         except KeyboardInterrupt:
             print("Training interrupted. Performing cleanup...")
-        elapsed = time.time() - start
-        self.history["nr_epochs"] += self.nr_epochs
-        print("elapsed:" + str(elapsed))
+        return self._train_epilogue(start, train_ds, test_ds, train_loss, test_loss, input_variables, output_variable,
+                                    model_path, training_paths, testing_paths)
 
-        if self.db:
-            self.db.add_training_result(self.get_model_id(), "UNET", output_variable, input_variables, self.summary(),
-                                        model_path, training_paths, train_loss, testing_paths, test_loss,
-                                        self.get_parameters(), self.spec.save())
-        if model_path:
-            self.save(model_path)
-        else:
-            self._pull_weights()
-        metrics = {"test": self.evaluate(test_ds), "train": self.evaluate(train_ds)}
-        self.dump_metrics("Test Metrics", metrics["test"])
-        self.dump_metrics("Train Metrics", metrics["train"])
-        if self.db:
-            self.db.add_evaluation_result(self.get_model_id(), training_paths, testing_paths, metrics)
-        return metrics
+    def _progress(self, message):
+        print(message)
 
     def _loss_mask(self, ds):
         """(N, 1|C, H, W) fp32 mask for the loss, or None for all ones counted over the output's channels"""
