@@ -6,7 +6,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,6 +26,7 @@
 #include "dp_comm.h"
 #include "kernels_ctbwd.h"   // argument struct only: the kernel lives in ctbwd.hip
 #include "trunk_api.h"
+#include "engine_host.h"
 
 // The benchmark geometry's template kernels, instantiated HERE so that their code sits next to the non-template kernels of
 // the same step (implicit instantiations are emitted at the end of the 3 MB text section, 2 MB away): see DESIGN.md §4.
@@ -40,38 +40,20 @@ template __global__ void k_s2_bwd_rows<8, 2, 4, 3, 3, 4, 2, 1>(S2Rows);
 }  // namespace cae
 
 using namespace cae;
+using namespace cae_internal;
 
 namespace cae_internal {
 int ctbwd_launch(const void* args, size_t bytes, unsigned gx, unsigned gy, unsigned gz, size_t lds, hipStream_t s);   // ctbwd.hip
 }
 
 namespace {
-
 thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
 }  // namespace
 
-// shared with unet_engine.hip: sets the message cae_last_error() returns for the calling thread
+// engine_host.h: the message cae_last_error() returns for the calling thread
 void cae_detail_set_error(const char* msg) { g_err = msg; }
 
 namespace {
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess)                                                                      \
-            return fail(CAE_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
 
 constexpr float kBnEps = 1e-5f;      // nn.BatchNorm2d default (encoder.py:45, decoder.py:47)
 constexpr float kBnMomentum = 0.1f;  // nn.BatchNorm2d default
@@ -106,8 +88,7 @@ struct cae_engine {
     FcLayer fc[4];  // encoder_lin.0, encoder_lin.2, decoder_lin.0, decoder_lin.2
     int fc_size = 0, latent = 0, max_batch = 0;
     int in_c = 0, in_h = 0, in_w = 0, out_c = 0, out_h = 0, out_w = 0;
-    std::vector<cae_tensor_info_t> tensors;
-    int64_t n_param = 0, n_buf = 0;
+    TensorTable tab;
     int n_bn = 0;
     std::vector<int64_t> bn_stat_off;   // per BN: byte offset of its [C][4] double sums
     std::vector<int64_t> bn_saved_off;  // per BN: byte offset of its [C][2] float mean/invstd
@@ -180,32 +161,6 @@ struct cae_engine {
 };
 
 namespace {
-
-void add_tensor(cae_engine* e, const std::string& name, int arena, std::vector<int64_t> shape, int64_t* off_out) {
-    cae_tensor_info_t t;
-    memset(&t, 0, sizeof t);
-    snprintf(t.name, sizeof t.name, "%s", name.c_str());
-    t.arena = arena;
-    t.ndim = (int)shape.size();
-    t.numel = 1;
-    for (size_t i = 0; i < shape.size(); i++) {
-        t.shape[i] = shape[i];
-        t.numel *= shape[i];
-    }
-    int64_t& top = arena == 0 ? e->n_param : e->n_buf;
-    top = align_up(top, 4);  // 16-byte aligned tensors
-    t.offset = top;
-    top += t.numel;
-    *off_out = t.offset;
-    e->tensors.push_back(t);
-}
-
-int64_t carve(int64_t& top, int64_t bytes) {
-    top = align_up(top, 256);
-    int64_t o = top;
-    top += bytes;
-    return o;
-}
 
 // ---- descriptor helpers -----------------------------------------------------------------------
 
@@ -379,10 +334,6 @@ bool s2_shape_ok(const ConvLayer& L) {
     S2_SHAPES(CHK)
 #undef CHK
     return false;
-}
-int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
 }
 
 bool s2_eligible(const cae_engine* e, const ConvLayer& L) { return e->use_s2 && L.sh_w >= 0 && s2_shape_ok(L); }
@@ -905,7 +856,7 @@ bool dp_single_collective(const cae_engine* e, const StepArgs& a) { return !dp_o
 
 int dp_first_bucket(cae_engine* e, const StepArgs& a) {
     if (!a.dp || dp_single_collective(e, a)) return CAE_OK;
-    const int64_t lo = e->bucket_split, hi = e->n_param;
+    const int64_t lo = e->bucket_split, hi = e->tab.n_param;
     const bool overlap = dp_overlap(e, a);
     hipStream_t on = overlap ? e->comm_stream : e->stream;
     if (overlap) {
@@ -925,7 +876,7 @@ int dp_first_bucket(cae_engine* e, const StepArgs& a) {
 // after the last backward kernel: second bucket, join, Adam from the reduced fp32 gradients
 int dp_finish_step(cae_engine* e, const StepArgs& a) {
     hipStream_t s = e->stream;
-    const int64_t lo = 0, hi = dp_single_collective(e, a) ? e->n_param : e->bucket_split;
+    const int64_t lo = 0, hi = dp_single_collective(e, a) ? e->tab.n_param : e->bucket_split;
     {
         ProfScope _p(e, "dp_narrow_bucket1", 0, 12.0 * (hi - lo));
         hipLaunchKernelGGL(k_narrow_range, dim3(grid1(hi - lo > 0 ? hi - lo : 1)), dim3(256), 0, s, (long long)lo, (long long)hi,
@@ -938,8 +889,8 @@ int dp_finish_step(cae_engine* e, const StepArgs& a) {
     if (int rc = dp_allreduce_grads(e, lo, hi, s)) return rc;
     StepTail none;
     memset(&none, 0, sizeof none);
-    ProfScope _p(e, "adam", 0, 28.0 * e->n_param);
-    hipLaunchKernelGGL(k_adam, dim3(grid1(e->n_param)), dim3(256), 0, s, (long long)e->n_param, e->params,
+    ProfScope _p(e, "adam", 0, 28.0 * e->tab.n_param);
+    hipLaunchKernelGGL(k_adam, dim3(grid1(e->tab.n_param)), dim3(256), 0, s, (long long)e->tab.n_param, e->params,
                        (const float*)e->grads, e->m, e->v, e->hp, (const StepState*)e->state(), e->shard_segs(), none, 0,
                        std::log(e->hp.beta1), std::log(e->hp.beta2), AdamConv0{});
     return CAE_OK;
@@ -1758,10 +1709,10 @@ int launch_one(cae_engine* e, int op, const StepArgs& a) {
         rc = launch_backward(e, af);
         if (rc) return rc;
         if (op == OP_TRAIN) {
-            ProfScope _p(e, "adam", 0, 32.0 * e->n_param);
+            ProfScope _p(e, "adam", 0, 32.0 * e->tab.n_param);
             AdamConv0 c0 = e->c0_pending;
             StepTail tl = step_tail_of(e, a.inc(), 1);
-            int nreg = grid1(e->n_param), grid = nreg;
+            int nreg = grid1(e->tab.n_param), grid = nreg;
             if (c0.on) {
                 // that layer's BatchNorm table (the first of the swept range) is read by this launch: the next step's
                 // k_head_fwd clears it
@@ -1771,11 +1722,11 @@ int launch_one(cae_engine* e, int op, const StepArgs& a) {
                 c0.n_regular = nreg;
                 grid = nreg + c0.nw;
             }
-            hipLaunchKernelGGL(k_adam, dim3(grid), dim3(256), 0, s, (long long)e->n_param, e->params,
+            hipLaunchKernelGGL(k_adam, dim3(grid), dim3(256), 0, s, (long long)e->tab.n_param, e->params,
                                (const float*)nullptr, e->m, e->v, e->hp, (const StepState*)e->state(), e->shard_segs(),
                                tl, 0, std::log(e->hp.beta1), std::log(e->hp.beta2), c0);
         } else {
-            hipLaunchKernelGGL(k_acc_to_f32, dim3(grid1(e->n_param)), dim3(256), 0, s, (long long)e->n_param, e->grads,
+            hipLaunchKernelGGL(k_acc_to_f32, dim3(grid1(e->tab.n_param)), dim3(256), 0, s, (long long)e->tab.n_param, e->grads,
                                e->shard_segs(), step_tail_of(e, a.inc(), 1));
         }
     } else if (op == OP_EVAL) {
@@ -1786,7 +1737,7 @@ int launch_one(cae_engine* e, int op, const StepArgs& a) {
         StepTail none;
         memset(&none, 0, sizeof none);
         // forward_backward already counted this optimiser step (its first kernel bumps adam_step)
-        hipLaunchKernelGGL(k_adam, dim3(grid1(e->n_param)), dim3(256), 0, s, (long long)e->n_param, e->params,
+        hipLaunchKernelGGL(k_adam, dim3(grid1(e->tab.n_param)), dim3(256), 0, s, (long long)e->tab.n_param, e->params,
                            (const float*)e->grads, e->m, e->v, e->hp, (const StepState*)e->state(), e->shard_segs(),
                            none, 0, std::log(e->hp.beta1), std::log(e->hp.beta2), AdamConv0{});
     }
@@ -1908,12 +1859,12 @@ static int engine_create_impl(const cae_layer_spec* enc, int n_enc, const cae_la
         L.bn_index = bn++;
         const std::string c = "enc/encoder_cnn." + std::to_string(3 * i);
         const std::string b = "enc/encoder_cnn." + std::to_string(3 * i + 1);
-        add_tensor(e, c + ".weight", 0, {L.cout, L.cin, L.kh, L.kw}, &L.w_off);
-        add_tensor(e, c + ".bias", 0, {L.cout}, &L.b_off);
-        add_tensor(e, b + ".weight", 0, {L.cout}, &L.gamma_off);
-        add_tensor(e, b + ".bias", 0, {L.cout}, &L.beta_off);
-        add_tensor(e, b + ".running_mean", 1, {L.cout}, &L.rm_off);
-        add_tensor(e, b + ".running_var", 1, {L.cout}, &L.rv_off);
+        L.w_off = e->tab.add(c + ".weight", 0, {L.cout, L.cin, L.kh, L.kw});
+        L.b_off = e->tab.add(c + ".bias", 0, {L.cout});
+        L.gamma_off = e->tab.add(b + ".weight", 0, {L.cout});
+        L.beta_off = e->tab.add(b + ".bias", 0, {L.cout});
+        L.rm_off = e->tab.add(b + ".running_mean", 1, {L.cout});
+        L.rv_off = e->tab.add(b + ".running_var", 1, {L.cout});
         e->enc.push_back(L);
     }
     const ConvLayer& EL = e->enc.back();
@@ -1930,31 +1881,17 @@ static int engine_create_impl(const cae_layer_spec* enc, int n_enc, const cae_la
         if (i == 1 && variational) {
             // two named tensors per half, ONE (2 * latent, fc) matrix and ONE (2 * latent) bias vector in the arena: the table
             // lists mu.weight, mu.bias, logvar.weight, logvar.bias (the 'var' model's state_dict order) with those offsets
-            int64_t& top = e->n_param;
-            top = align_up(top, 4);
-            F.w_off = top;
-            top += (int64_t)heads * F.nin;
-            top = align_up(top, 4);
-            F.b_off = top;
-            top += heads;
-            const char* hn[2] = {"enc/encoder_mu", "enc/encoder_logvar"};
-            for (int h = 0; h < 2; h++)
-                for (int part = 0; part < 2; part++) {
-                    cae_tensor_info_t t;
-                    memset(&t, 0, sizeof t);
-                    snprintf(t.name, sizeof t.name, "%s.%s", hn[h], part == 0 ? "weight" : "bias");
-                    t.arena = 0;
-                    t.ndim = part == 0 ? 2 : 1;
-                    t.shape[0] = latent_size;
-                    if (part == 0) t.shape[1] = F.nin;
-                    t.numel = part == 0 ? (int64_t)latent_size * F.nin : latent_size;
-                    t.offset = part == 0 ? F.w_off + (int64_t)h * latent_size * F.nin : F.b_off + (int64_t)h * latent_size;
-                    e->tensors.push_back(t);
-                }
+            F.w_off = e->tab.reserve(0, (int64_t)heads * F.nin);
+            F.b_off = e->tab.reserve(0, heads);
+            const std::string hn[2] = {"enc/encoder_mu", "enc/encoder_logvar"};
+            for (int h = 0; h < 2; h++) {
+                e->tab.list(hn[h] + ".weight", 0, {latent_size, F.nin}, F.w_off + (int64_t)h * latent_size * F.nin);
+                e->tab.list(hn[h] + ".bias", 0, {latent_size}, F.b_off + (int64_t)h * latent_size);
+            }
             continue;
         }
-        add_tensor(e, std::string(fnames[i]) + ".weight", 0, {F.nout, F.nin}, &F.w_off);
-        add_tensor(e, std::string(fnames[i]) + ".bias", 0, {F.nout}, &F.b_off);
+        F.w_off = e->tab.add(std::string(fnames[i]) + ".weight", 0, {F.nout, F.nin});
+        F.b_off = e->tab.add(std::string(fnames[i]) + ".bias", 0, {F.nout});
     }
     for (int i = 0; i < n_dec; i++) {
         const cae_layer_spec& s = dec[i];
@@ -1967,18 +1904,17 @@ static int engine_create_impl(const cae_layer_spec* enc, int n_enc, const cae_la
         L.bn_index = L.has_bn ? bn++ : -1;
         const std::string c = "dec/decoder_conv." + std::to_string(3 * i);
         const std::string b = "dec/decoder_conv." + std::to_string(3 * i + 1);
-        add_tensor(e, c + ".weight", 0, {L.cin, L.cout, L.kh, L.kw}, &L.w_off);
-        add_tensor(e, c + ".bias", 0, {L.cout}, &L.b_off);
+        L.w_off = e->tab.add(c + ".weight", 0, {L.cin, L.cout, L.kh, L.kw});
+        L.b_off = e->tab.add(c + ".bias", 0, {L.cout});
         if (L.has_bn) {
-            add_tensor(e, b + ".weight", 0, {L.cout}, &L.gamma_off);
-            add_tensor(e, b + ".bias", 0, {L.cout}, &L.beta_off);
-            add_tensor(e, b + ".running_mean", 1, {L.cout}, &L.rm_off);
-            add_tensor(e, b + ".running_var", 1, {L.cout}, &L.rv_off);
+            L.gamma_off = e->tab.add(b + ".weight", 0, {L.cout});
+            L.beta_off = e->tab.add(b + ".bias", 0, {L.cout});
+            L.rm_off = e->tab.add(b + ".running_mean", 1, {L.cout});
+            L.rv_off = e->tab.add(b + ".running_var", 1, {L.cout});
         }
         e->dec.push_back(L);
     }
-    e->n_param = align_up(e->n_param, 4);
-    e->n_buf = align_up(e->n_buf, 4);
+    e->tab.close();
     e->n_bn = bn;
     // data parallelism: bucket boundary and the SyncBN collective order (forward: producers in layer order; backward: the
     // table of a layer's INPUT BatchNorm after that layer's input-gradient kernel) - see launch_forward / launch_backward
@@ -2023,51 +1959,50 @@ static int engine_create_impl(const cae_layer_spec* enc, int n_enc, const cae_la
     }
 
     // ---- workspace carve
-    int64_t top = 0;
-    e->off_state = carve(top, sizeof(StepState));
-    e->off_losses = carve(top, (int64_t)kLossSlots * kStatShards * sizeof(double));
-    e->off_scan = carve(top, 1024 * 3 * sizeof(double));
+    Carver carve{256};
+    e->off_state = carve(sizeof(StepState));
+    e->off_losses = carve((int64_t)kLossSlots * kStatShards * sizeof(double));
+    e->off_scan = carve(1024 * 3 * sizeof(double));
     e->bn_stat_off.resize(bn);
     e->bn_saved_off.resize(bn);
     e->bn_channels.resize(bn);
-    e->off_zero_begin = align_up(top, 256);
+    e->off_zero_begin = carve.top;
     auto reg_bn = [&](const ConvLayer& L) {
         if (!L.has_bn) return;
         e->bn_channels[L.bn_index] = L.cout;
-        e->bn_stat_off[L.bn_index] = carve(top, (int64_t)kStatShards * L.cout * 4 * sizeof(double));
+        e->bn_stat_off[L.bn_index] = carve((int64_t)kStatShards * L.cout * 4 * sizeof(double));
         if (L.cout > e->max_channels) e->max_channels = L.cout;
     };
     for (auto& L : e->enc) reg_bn(L);
     for (auto& L : e->dec) reg_bn(L);
-    e->off_gradacc = carve(top, e->n_param * (int64_t)sizeof(double));
-    e->off_sgacc = carve(top, (int64_t)kStatShards * (e->segs.n > 0 ? e->segs.n : 4) * (int64_t)sizeof(double));
-    e->off_zero_end = align_up(top, 256);
-    top = e->off_zero_end;
-    for (auto& L : e->enc) e->bn_saved_off[L.bn_index] = carve(top, (int64_t)L.cout * 2 * sizeof(float));
+    e->off_gradacc = carve(e->tab.n_param * (int64_t)sizeof(double));
+    e->off_sgacc = carve((int64_t)kStatShards * (e->segs.n > 0 ? e->segs.n : 4) * (int64_t)sizeof(double));
+    e->off_zero_end = carve.top;
+    for (auto& L : e->enc) e->bn_saved_off[L.bn_index] = carve((int64_t)L.cout * 2 * sizeof(float));
     for (auto& L : e->dec)
-        if (L.has_bn) e->bn_saved_off[L.bn_index] = carve(top, (int64_t)L.cout * 2 * sizeof(float));
+        if (L.has_bn) e->bn_saved_off[L.bn_index] = carve((int64_t)L.cout * 2 * sizeof(float));
     const int64_t mb = max_batch;
     for (auto& L : e->enc) {
-        L.act_off = carve(top, mb * L.out_elems() * 4);
-        L.grad_off = carve(top, mb * L.out_elems() * 4);
+        L.act_off = carve(mb * L.out_elems() * 4);
+        L.grad_off = carve(mb * L.out_elems() * 4);
     }
     for (int i = 0; i < 4; i++) {
-        e->fc[i].act_off = carve(top, mb * e->fc[i].nout * 4);
-        e->fc[i].grad_off = carve(top, mb * e->fc[i].nout * 4);
+        e->fc[i].act_off = carve(mb * e->fc[i].nout * 4);
+        e->fc[i].grad_off = carve(mb * e->fc[i].nout * 4);
     }
     for (auto& L : e->dec) {
         if (!L.has_bn) continue;
-        L.act_off = carve(top, mb * L.out_elems() * 4);
-        L.grad_off = carve(top, mb * L.out_elems() * 4);
+        L.act_off = carve(mb * L.out_elems() * 4);
+        L.grad_off = carve(mb * L.out_elems() * 4);
     }
-    e->off_glast = carve(top, mb * e->dec.back().out_elems() * 4);
-    e->off_xbatch = carve(top, (mb * e->enc[0].in_elems() + e->enc[0].cout) * 4);   // + the layer's gamma before the update
+    e->off_glast = carve(mb * e->dec.back().out_elems() * 4);
+    e->off_xbatch = carve((mb * e->enc[0].in_elems() + e->enc[0].cout) * 4);   // + the layer's gamma before the update
     if (variational) {
-        e->off_vz = carve(top, mb * latent_size * 4);
-        e->off_vgz = carve(top, mb * latent_size * 4);
-        e->off_zlast = carve(top, mb * e->dec.back().out_elems() * 4);
+        e->off_vz = carve(mb * latent_size * 4);
+        e->off_vgz = carve(mb * latent_size * 4);
+        e->off_zlast = carve(mb * e->dec.back().out_elems() * 4);
     }
-    e->ws_need = align_up(top, 256);
+    e->ws_need = carve.top;
     for (auto& L : e->enc)
         if (L.cin > e->max_channels) e->max_channels = L.cin;
     for (auto& L : e->dec)
@@ -2087,13 +2022,11 @@ void cae_engine_destroy(cae_engine* e) {
     delete e;
 }
 
-int64_t cae_param_count(const cae_engine* e) { return e ? e->n_param : 0; }
-int64_t cae_buffer_count(const cae_engine* e) { return e ? e->n_buf : 0; }
-int cae_tensor_count(const cae_engine* e) { return e ? (int)e->tensors.size() : 0; }
+int64_t cae_param_count(const cae_engine* e) { return e ? e->tab.n_param : 0; }
+int64_t cae_buffer_count(const cae_engine* e) { return e ? e->tab.n_buf : 0; }
+int cae_tensor_count(const cae_engine* e) { return e ? e->tab.count() : 0; }
 int cae_tensor_info(const cae_engine* e, int index, cae_tensor_info_t* out) {
-    if (!e || !out || index < 0 || index >= (int)e->tensors.size()) return fail(CAE_ERR_ARG, "tensor index out of range");
-    *out = e->tensors[index];
-    return CAE_OK;
+    return e ? e->tab.info(index, out) : fail(CAE_ERR_ARG, "tensor index out of range");
 }
 int64_t cae_workspace_bytes(const cae_engine* e) { return e ? e->ws_need : 0; }
 int cae_loss_slots(const cae_engine*) { return kLossSlots; }
@@ -2260,7 +2193,7 @@ namespace {
 // plain launches for data-parallel steps (dp_graph_ok = false); wrong VALUES fail the init.
 int dp_self_test(cae_engine* e) {
     hipStream_t s = e->stream;
-    const int64_t n = e->n_param, mid = e->bucket_split;
+    const int64_t n = e->tab.n_param, mid = e->bucket_split;
     auto body = [&]() -> int {
         HIP_TRY(hipEventRecord(e->ev_fork, s));
         HIP_TRY(hipStreamWaitEvent(e->comm_stream, e->ev_fork, 0));
@@ -2334,10 +2267,10 @@ int cae_dp_init(cae_engine* e, int world, int rank, const void* id128_host) {
     // main stream), on the gradient arena as scratch - its contents mean nothing between steps
     if (int rc = dp_self_test(e)) return rc;
     // the whole arena in one collective (the structure without overlap): its size class too is met outside any capture first
-    if (int rc = dp_allreduce_grads(e, 0, e->n_param, e->stream)) return rc;
+    if (int rc = dp_allreduce_grads(e, 0, e->tab.n_param, e->stream)) return rc;
     for (int c : e->bn_channels) {
         const size_t nd = (size_t)kStatShards * c * 4;
-        if ((int64_t)nd * 2 > e->n_param) continue;
+        if ((int64_t)nd * 2 > e->tab.n_param) continue;
         NCCL_TRY(rccl().AllReduce(e->grads, e->grads, nd, RcclApi::kFloat64, RcclApi::kSum, e->dp_comm, e->stream));
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -2368,11 +2301,11 @@ int cae_dp_broadcast_state(cae_engine* e, int root, int what) {
         if (n > 0) NCCL_TRY(rccl().Broadcast(p, p, (size_t)n, RcclApi::kFloat32, root, e->dp_comm, s));
         return CAE_OK;
     };
-    if (what & 1) if (int rc = bc(e->params, e->n_param)) return rc;
-    if (what & 2) if (int rc = bc(e->bufs, e->n_buf)) return rc;
+    if (what & 1) if (int rc = bc(e->params, e->tab.n_param)) return rc;
+    if (what & 2) if (int rc = bc(e->bufs, e->tab.n_buf)) return rc;
     if (what & 4) {
-        if (int rc = bc(e->m, e->n_param)) return rc;
-        if (int rc = bc(e->v, e->n_param)) return rc;
+        if (int rc = bc(e->m, e->tab.n_param)) return rc;
+        if (int rc = bc(e->v, e->tab.n_param)) return rc;
     }
     HIP_TRY(hipStreamSynchronize(s));
     return CAE_OK;
@@ -2568,7 +2501,7 @@ int64_t cae_debug_read(cae_engine* e, const char* what, int index, void* host_ou
         esz = 8;
     } else if (w == "grad_acc") {
         src = e->gradacc();
-        n = e->n_param;
+        n = e->tab.n_param;
         esz = 8;
     } else if (w == "bn_stats") {
         if (index < 0 || index >= e->n_bn) return fail(CAE_ERR_ARG, "bn index out of range");
@@ -2783,7 +2716,7 @@ int trunk_backward(cae_engine* e, const float* x, int batch) {
 
 int trunk_adam(cae_engine* e) {
     if (!e || !e->ws) return fail(CAE_ERR_STATE, "trunk_adam: not a bound engine");
-    hipLaunchKernelGGL(k_adam, dim3(grid1(e->n_param)), dim3(256), 0, e->stream, (long long)e->n_param, e->params,
+    hipLaunchKernelGGL(k_adam, dim3(grid1(e->tab.n_param)), dim3(256), 0, e->stream, (long long)e->tab.n_param, e->params,
                        (const float*)nullptr, e->m, e->v, e->hp, (const StepState*)e->state(), e->shard_segs(),
                        step_tail_of(e, 0, 0), 0, std::log(e->hp.beta1), std::log(e->hp.beta2), AdamConv0{});
     HIP_TRY(hipGetLastError());
@@ -2792,10 +2725,10 @@ int trunk_adam(cae_engine* e) {
 
 int trunk_gradients(cae_engine* e, float* out, double scale) {
     if (!e || !e->ws || !out) return fail(CAE_ERR_STATE, "trunk_gradients: bad argument");
-    hipLaunchKernelGGL(k_acc_to_f32, dim3(grid1(e->n_param)), dim3(256), 0, e->stream, (long long)e->n_param, out, e->shard_segs(),
+    hipLaunchKernelGGL(k_acc_to_f32, dim3(grid1(e->tab.n_param)), dim3(256), 0, e->stream, (long long)e->tab.n_param, out, e->shard_segs(),
                        step_tail_of(e, 0, 0));
     if (scale != 1.0)
-        hipLaunchKernelGGL(k_scale_f32, dim3(grid1(e->n_param)), dim3(256), 0, e->stream, out, (long long)e->n_param, (float)scale);
+        hipLaunchKernelGGL(k_scale_f32, dim3(grid1(e->tab.n_param)), dim3(256), 0, e->stream, out, (long long)e->tab.n_param, (float)scale);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
@@ -2804,7 +2737,7 @@ int trunk_adam_from(cae_engine* e, const float* grads) {
     if (!e || !e->ws || !grads) return fail(CAE_ERR_STATE, "trunk_adam_from: bad argument");
     StepTail none;
     memset(&none, 0, sizeof none);
-    hipLaunchKernelGGL(k_adam, dim3(grid1(e->n_param)), dim3(256), 0, e->stream, (long long)e->n_param, e->params, grads, e->m, e->v,
+    hipLaunchKernelGGL(k_adam, dim3(grid1(e->tab.n_param)), dim3(256), 0, e->stream, (long long)e->tab.n_param, e->params, grads, e->m, e->v,
                        e->hp, (const StepState*)e->state(), e->shard_segs(), none, 0, std::log(e->hp.beta1), std::log(e->hp.beta2),
                        AdamConv0{});
     HIP_TRY(hipGetLastError());

@@ -10,9 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <algorithm>
 #include <map>
@@ -20,6 +18,7 @@
 #include <vector>
 
 #include "cae_unet.h"
+#include "engine_host.h"
 #include "kernels_unet.h"
 #include "kernels_unet_mfma.h"
 #include "kernels_unet_lin.h"
@@ -35,32 +34,13 @@ namespace ugemm {
 #include "kernels_gemm.h"
 }  // namespace ugemm
 
-void cae_detail_set_error(const char* msg);   // engine.hip: message returned by cae_last_error()
-
 using namespace unet;
+using namespace cae_internal;
 
 namespace {
 
-int ufail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    cae_detail_set_error(buf);
-    return code;
-}
-
-#define UHIP_TRY(expr)                                                                                          \
-    do {                                                                                                        \
-        hipError_t _e = (expr);                                                                                 \
-        if (_e != hipSuccess)                                                                                   \
-            return ufail(CAE_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
 constexpr float kEps = 1e-5f;       // nn.BatchNorm default
 constexpr float kMomentum = 0.1f;   // nn.BatchNorm default
-constexpr int kLossSlots = 4096;
 
 // dropout sites (oracle/unet_oracle.py)
 constexpr uint32_t SITE_ENC_CONV = 0, SITE_ENC_FC0 = 100, SITE_ENC_FC1 = 101, SITE_DEC_FC0 = 102, SITE_DEC_FC1 = 103,
@@ -98,41 +78,27 @@ struct Fc {
     int64_t gh = 0, ga = 0;          // grad wrt raw output (in place of ga after activation backward), grad wrt a
 };
 
-struct DataSet {
-    const float* x = nullptr;
-    const float* t = nullptr;
-    const float* m = nullptr;
-    int mc = 0;
-    int64_t n = 0;
-};
-
 }  // namespace
 
-struct unet_engine {
+struct unet_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets, loss slots: engine_host.h)
     std::vector<ConvLayer> enc, dec;
     Fc fc[4];                        // enc_lin.0, enc_lin.4, dec_lin.0, dec_lin.4
-    int fc_size = 0, latent = 0, max_batch = 0;
+    int fc_size = 0, latent = 0;
     int in_c = 0, in_h = 0, in_w = 0, out_c = 0, out_h = 0, out_w = 0;
-    std::vector<cae_tensor_info_t> tensors;
-    int64_t n_params = 0, n_buffers = 0;
+    TensorTable tab;
     // workspace
-    int64_t ws_bytes = 0;
-    int64_t off_gacc = 0, off_dsum = 0, n_dsum = 0, off_losses = 0, off_ls = 0, off_f32 = 0, off_gscratch = 0, gscratch_bytes = 0;
+    int64_t off_gacc = 0, off_dsum = 0, n_dsum = 0, off_ls = 0, off_f32 = 0, off_gscratch = 0, gscratch_bytes = 0;
     int64_t off_thinpart = 0, thinpart_bytes = 0;   // weight-gradient partial tiles: per workgroup (kernels_unet_thin.h), per K slice (tile engine)
     int64_t off_linpart = 0, linpart_bytes = 0;   // K-slice partial tiles of the big Linear layers (kernels_unet_lin.h)
     bool fc_f32[4] = {false, false, false, false};   // this backward stored fc[k]'s weight gradient as fp32 (F32Ranges)
     bool fc_f32_dirty[4] = {false, false, false, false};   // ... and nothing has cleared those accumulator slots since
     int64_t xb = 0, y = 0, coef = 0;
-    char* ws = nullptr;
     float *params = nullptr, *m = nullptr, *v = nullptr, *buffers = nullptr;
-    hipStream_t stream = nullptr;
     Hyper hyper{1e-3, 0.9, 0.999, 1e-8, 1e-5};
     double dropout = 0.1, lambda_p = 1.0;
     uint32_t seed = 0;
-    int64_t step = 0;
     int specialised = 1;
     bool gacc_clean = false;   // the fp64 gradient accumulator is all zero (k_adamw clears what it consumes) but for fc_f32_dirty
-    DataSet ds[2];
 
     float* f(int64_t off) const { return reinterpret_cast<float*>(ws + off_f32) + off; }
     double* dsum(int64_t off) const { return reinterpret_cast<double*>(ws + off_dsum) + off; }
@@ -143,39 +109,12 @@ struct unet_engine {
 
 namespace {
 
-int64_t add_tensor(unet_engine* e, const std::string& name, int arena, std::vector<int64_t> shape) {
-    cae_tensor_info_t t;
-    memset(&t, 0, sizeof t);
-    snprintf(t.name, sizeof t.name, "%s", name.c_str());
-    t.arena = arena;
-    t.ndim = (int)shape.size();
-    int64_t n = 1;
-    for (size_t i = 0; i < shape.size(); i++) {
-        t.shape[i] = shape[i];
-        n *= shape[i];
-    }
-    int64_t& top = arena == 0 ? e->n_params : e->n_buffers;
-    top = (top + 3) & ~int64_t(3);
-    t.offset = top;
-    t.numel = n;
-    top += n;
-    e->tensors.push_back(t);
-    return t.offset;
-}
-
 void add_bn(unet_engine* e, const std::string& key, int C, Bn& bn) {
     bn.C = C;
-    bn.gamma = add_tensor(e, key + ".weight", 0, {C});
-    bn.beta = add_tensor(e, key + ".bias", 0, {C});
-    bn.rmean = add_tensor(e, key + ".running_mean", 1, {C});
-    bn.rvar = add_tensor(e, key + ".running_var", 1, {C});
-}
-
-int blocks_for(long long n, int cap = 8192) {
-    long long b = (n + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > cap) b = cap;
-    return (int)b;
+    bn.gamma = e->tab.add(key + ".weight", 0, {C});
+    bn.beta = e->tab.add(key + ".bias", 0, {C});
+    bn.rmean = e->tab.add(key + ".running_mean", 1, {C});
+    bn.rvar = e->tab.add(key + ".running_var", 1, {C});
 }
 
 Drop make_drop(const unet_engine* e, uint32_t site, bool train) {
@@ -192,12 +131,12 @@ Drop make_drop(const unet_engine* e, uint32_t site, bool train) {
 
 // ---- conv dispatch --------------------------------------------------------------------------------
 void conv_down(unet_engine* e, const Geom& g, const float* L, const float* w, const float* bias, float* S) {
-    static const int thin_off = getenv("CAE_UNET_THIN") ? atoi(getenv("CAE_UNET_THIN")) == 0 : 0;   // env: A/B measurements only
+    static const int thin_off = env_int("CAE_UNET_THIN", 1) == 0;   // env: A/B measurements only
     if (e->specialised && !thin_off && thin_geom(g)) {   // the image-end layers: kernels_unet_thin.h
         thin_down_launch(g, L, w, bias, S, e->stream);
         return;
     }
-    static const int patch_off = getenv("CAE_UNET_PATCH") ? atoi(getenv("CAE_UNET_PATCH")) == 0 : 0;   // env: A/B measurements only
+    static const int patch_off = env_int("CAE_UNET_PATCH", 1) == 0;   // env: A/B measurements only
     if (e->specialised && !patch_off && patch_geom(g)) {   // the wide layers: kernels_unet_patch.h
         pdown_launch(g, L, w, bias, S, e->stream);
         return;
@@ -212,7 +151,7 @@ void conv_down(unet_engine* e, const Geom& g, const float* L, const float* w, co
 
 // wp: the layer's repacked weights (pack_up_weights below) or nullptr when the layer does not run the tile engine
 void conv_up(unet_engine* e, const Geom& g, const float* S, const float* w, const float* wp, const float* bias, float* L) {
-    static const int thin_off = getenv("CAE_UNET_THIN") ? atoi(getenv("CAE_UNET_THIN")) == 0 : 0;   // env: A/B measurements only
+    static const int thin_off = env_int("CAE_UNET_THIN", 1) == 0;   // env: A/B measurements only
     if (e->specialised && !thin_off && wp && thin_up_geom(g)) {   // ... 128 columns wide: the row walk of kernels_unet_thin.h
         thin_up_launch(g, S, wp, bias, L, e->stream);
         return;
@@ -227,7 +166,7 @@ void conv_up(unet_engine* e, const Geom& g, const float* S, const float* w, cons
         }
         return;
     }
-    static const int patch_off = getenv("CAE_UNET_PATCH") ? atoi(getenv("CAE_UNET_PATCH")) == 0 : 0;   // env: A/B measurements only
+    static const int patch_off = env_int("CAE_UNET_PATCH", 1) == 0;   // env: A/B measurements only
     if (e->specialised && !patch_off && wp && g.Cl > 4 && pup_geom(g)) {   // the wide layers: kernels_unet_patch.h
         pup_launch(g, S, wp, bias, L, e->stream);
         return;
@@ -241,19 +180,19 @@ void conv_up(unet_engine* e, const Geom& g, const float* S, const float* w, cons
 }
 
 void conv_wgrad(unet_engine* e, const Geom& g, const float* S, const float* L, double* acc) {
-    static const int thin_off = getenv("CAE_UNET_THIN") ? atoi(getenv("CAE_UNET_THIN")) == 0 : 0;   // env: A/B measurements only
+    static const int thin_off = env_int("CAE_UNET_THIN", 1) == 0;   // env: A/B measurements only
     if (e->specialised && !thin_off && thin_geom(g)) {   // the image-end layers: kernels_unet_thin.h
         float* part = thin_wgrad_part_bytes(g) <= (size_t)e->thinpart_bytes ? reinterpret_cast<float*>(e->ws + e->off_thinpart) : nullptr;
         thin_wgrad_launch(g, S, L, acc, part, e->stream);
         return;
     }
-    static const int patch_off = getenv("CAE_UNET_PATCH") ? atoi(getenv("CAE_UNET_PATCH")) == 0 : 0;   // env: A/B measurements only
+    static const int patch_off = env_int("CAE_UNET_PATCH", 1) == 0;   // env: A/B measurements only
     if (e->specialised && !patch_off && pwgrad_geom(g) && pwgrad_part_bytes(g) <= (size_t)e->thinpart_bytes) {   // kernels_unet_patch.h
         pwgrad_launch(g, S, L, acc, reinterpret_cast<float*>(e->ws + e->off_thinpart), e->stream);
         return;
     }
     if (e->specialised && mfma_wgrad_eligible(g)) {
-        static const int part_off = getenv("CAE_UNET_WGPART") ? atoi(getenv("CAE_UNET_WGPART")) == 0 : 0;   // env: A/B measurements only
+        static const int part_off = env_int("CAE_UNET_WGPART", 1) == 0;   // env: A/B measurements only
         const size_t need = mfma_wgrad_part_bytes(g);
         float* part = (!part_off && need && need <= (size_t)e->thinpart_bytes) ? reinterpret_cast<float*>(e->ws + e->off_thinpart) : nullptr;
         mfma_wgrad_launch(g, S, L, acc, part, e->stream);
@@ -269,7 +208,7 @@ void conv_wgrad(unet_engine* e, const Geom& g, const float* S, const float* L, d
 // kernels that end in a workgroup-wide sum + atomics: fewer, longer workgroups (the sum's two barriers and the atomics are a
 // fixed 2-3 us; at 128 chunks a workgroup of the 128 x 128 maps had four loop trips of work in front of them)
 dim3 red_grid(int B, int C, int HW) {
-    static const int target = getenv("CAE_UNET_REDWGS") ? atoi(getenv("CAE_UNET_REDWGS")) : 1280;   // env: tuning runs only
+    static const int target = env_int("CAE_UNET_REDWGS", 1280);   // env: tuning runs only
     int chunks = (int)(((long long)B * HW + 256 * 4 - 1) / (256 * 4));
     const int want = std::max(4, target / std::max(1, C));     // about `target` workgroups over the C channels
     if (chunks > want) chunks = want;
@@ -333,7 +272,7 @@ ugemm::cae::GemmArgs gemm16_args(int M, int N, int K) {
 // the big layers on kernels_unet_lin.h: batch <= 64, 16-byte rows, room for the K slices' partial tiles
 bool lin_big(const unet_engine* e, const Fc& L, int B) {
     if (!e->specialised || small_fc(L) || B > 64 || (L.nin & 3) || (L.nout & 3)) return false;
-    static const int off = getenv("CAE_UNET_LIN") ? atoi(getenv("CAE_UNET_LIN")) == 0 : 0;   // env: A/B measurements only
+    static const int off = env_int("CAE_UNET_LIN", 1) == 0;   // env: A/B measurements only
     if (off) return false;
     const long long need = (long long)std::max((L.nin + 127) / 128 * (long long)L.nout, (L.nout + 127) / 128 * (long long)L.nin) * B * 4;
     return need <= e->linpart_bytes;
@@ -473,7 +412,7 @@ void pack_up_weights(unet_engine* e, bool train) {
 // x: (B, in_c, in_h, in_w) contiguous.  Leaves the raw last-layer output in dec.back().u
 int forward(unet_engine* e, const float* x, int B, bool train) {
     const int n = (int)e->enc.size();
-    if (train) UHIP_TRY(hipMemsetAsync(e->dsum(0), 0, (size_t)e->n_dsum * sizeof(double), e->stream));
+    if (train) HIP_TRY(hipMemsetAsync(e->dsum(0), 0, (size_t)e->n_dsum * sizeof(double), e->stream));
     pack_up_weights(e, train);
     const float* cur = x;
     for (int i = 0; i < n; i++) {
@@ -500,7 +439,7 @@ int forward(unet_engine* e, const float* x, int B, bool train) {
             if (train) bn_stats(e, L.bn, e->f(L.h), L.nout, B, 1);
             bn_act(e, L.bn, e->f(L.h), L.nout, B, 1, train, d, nullptr, e->f(L.a));
         } else {
-            hipLaunchKernelGGL(k_relu_drop, dim3(blocks_for((long long)B * L.nout)), dim3(256), 0, e->stream, e->f(L.h),
+            hipLaunchKernelGGL(k_relu_drop, dim3(blocks_for((long long)B * L.nout, 8192)), dim3(256), 0, e->stream, e->f(L.h),
                                (long long)B * L.nout, d, e->f(L.a));
         }
         cur = e->f(L.a);
@@ -525,7 +464,7 @@ int forward(unet_engine* e, const float* x, int B, bool train) {
         bn_act(e, L.bn, nullptr, 0, B, HW, train, d, nullptr, e->f(L.din_next), ZCat{e->f(L.u), e->f(L.att), skip, C});
         cur = e->f(L.din_next);
     }
-    UHIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
 
@@ -543,21 +482,20 @@ int loss_forward(unet_engine* e, int which, const int32_t* perm, int64_t start, 
     const ConvLayer& L = e->dec.back();
     const int C = e->out_c, HW = e->out_h * e->out_w;
     double* ls = reinterpret_cast<double*>(e->ws + e->off_ls);
-    UHIP_TRY(hipMemsetAsync(ls, 0, (size_t)B * C * 8 * sizeof(double), e->stream));
+    HIP_TRY(hipMemsetAsync(ls, 0, (size_t)B * C * 8 * sizeof(double), e->stream));
     const LossSrc src = loss_src(e, which, perm, start);
     // (seven workgroup-wide fp64 sums end every workgroup: about 768 of them, each a long slice of its plane)
-    static const int ls_wgs = getenv("CAE_UNET_LSWGS") ? atoi(getenv("CAE_UNET_LSWGS")) : 768;   // env: tuning runs only
+    static const int ls_wgs = env_int("CAE_UNET_LSWGS", 768);   // env: tuning runs only
     int chunks = std::max(1, std::min(32, ls_wgs / std::max(1, B * C)));
     chunks = std::min(chunks, (HW + 1023) / 1024);
     hipLaunchKernelGGL(k_loss_sums, dim3(chunks, B * C), dim3(256), 0, e->stream, e->f(L.u), 1, src, C, HW, ls);
-    double* out2 = reinterpret_cast<double*>(e->ws + e->off_losses) + 2 * (size_t)slot;
     hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(256), 0, e->stream, ls, B, C, src.Cm, src.mask ? 1 : 0, e->lambda_p,
-                       out2, want_grad ? e->f(e->coef) : nullptr);
+                       e->losses(slot), want_grad ? e->f(e->coef) : nullptr);
     if (want_grad) {
         // ... and, in the same pass, the last layer's bias gradient (its sum over the batch and the map); backward() clears the
         // accumulator before anything else adds to it, so the clear is issued here, ahead of this launch
         if (!e->gacc_clean) {
-            UHIP_TRY(hipMemsetAsync(e->gacc(0), 0, (size_t)e->n_params * sizeof(double), e->stream));
+            HIP_TRY(hipMemsetAsync(e->gacc(0), 0, (size_t)e->tab.n_param * sizeof(double), e->stream));
             for (int k = 0; k < 4; k++) e->fc_f32_dirty[k] = false;
             e->gacc_clean = true;
         }
@@ -566,7 +504,7 @@ int loss_forward(unet_engine* e, int which, const int32_t* perm, int64_t start, 
         hipLaunchKernelGGL(k_loss_grad, dim3(std::max(1, chunks), B * C), dim3(256), 0, e->stream, e->f(L.u), src, B, C, HW, e->f(e->coef),
                            e->f(L.gu), e->gacc(L.b));
     }
-    UHIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
 
@@ -574,7 +512,7 @@ int loss_forward(unet_engine* e, int which, const int32_t* perm, int64_t start, 
 int backward(unet_engine* e, const float* x, int B) {
     const int n = (int)e->enc.size(), nd = (int)e->dec.size();
     if (!e->gacc_clean) {
-        UHIP_TRY(hipMemsetAsync(e->gacc(0), 0, (size_t)e->n_params * sizeof(double), e->stream));
+        HIP_TRY(hipMemsetAsync(e->gacc(0), 0, (size_t)e->tab.n_param * sizeof(double), e->stream));
         for (int k = 0; k < 4; k++) e->fc_f32_dirty[k] = false;
     }
     e->gacc_clean = false;
@@ -622,7 +560,7 @@ int backward(unet_engine* e, const float* x, int B) {
         if (L.has_bn) {
             bn_backward(e, L.bn, gin, L.nout, nullptr, 0, e->f(L.h), L.nout, B, 1, d, e->f(L.gh));
         } else {
-            hipLaunchKernelGGL(k_relu_drop_bwd, dim3(blocks_for((long long)B * L.nout)), dim3(256), 0, e->stream, e->f(L.gh), gin,
+            hipLaunchKernelGGL(k_relu_drop_bwd, dim3(blocks_for((long long)B * L.nout, 8192)), dim3(256), 0, e->stream, e->f(L.gh), gin,
                                e->f(L.h), (long long)B * L.nout, d);
         }
         const float* in = k == 0 ? (make_drop(e, SITE_ENC_CONV + n - 1, true).on ? e->f(e->enc[n - 1].a) : e->f(e->enc[n - 1].s))
@@ -656,19 +594,7 @@ int backward(unet_engine* e, const float* x, int B) {
             gin = e->f(e->enc[i - 1].ga);
         }
     }
-    UHIP_TRY(hipGetLastError());
-    return CAE_OK;
-}
-
-int check_batch(unet_engine* e, int which, const int32_t* perm, int64_t start, int batch, int slot) {
-    if (!e || !e->ws) return ufail(CAE_ERR_STATE, "unet: engine is not bound");
-    if (which < 0 || which > 1 || !e->ds[which].x) return ufail(CAE_ERR_STATE, "unet: data set %d is not set", which);
-    if (batch < 1 || batch > e->max_batch) return ufail(CAE_ERR_ARG, "unet: batch %d outside 1..%d", batch, e->max_batch);
-    if (start < 0 || start + batch > e->ds[which].n)
-        return ufail(CAE_ERR_ARG, "unet: samples %lld..%lld outside the data set (%lld)", (long long)start,
-                     (long long)(start + batch), (long long)e->ds[which].n);
-    if (slot < 0 || slot >= kLossSlots) return ufail(CAE_ERR_ARG, "unet: loss slot %d outside 0..%d", slot, kLossSlots - 1);
-    (void)perm;
+    HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
 
@@ -676,7 +602,7 @@ int gather_x(unet_engine* e, int which, const int32_t* perm, int64_t start, int 
     const long long E = (long long)e->in_c * e->in_h * e->in_w;
     hipLaunchKernelGGL(k_gather, dim3(blocks_for((long long)B * E, 65536)), dim3(256), 0, e->stream, e->ds[which].x, perm,
                        (long long)start, B, E, e->f(e->xb));
-    UHIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
 
@@ -685,7 +611,7 @@ AdamwConsts adamw_consts(const unet_engine* e) {
     const double bc1 = 1.0 - pow(h.beta1, (double)e->step), bc2 = 1.0 - pow(h.beta2, (double)e->step);
     return AdamwConsts{(float)(h.lr / bc1), (float)sqrt(bc2), (float)(1.0 - h.lr * h.wd), (float)h.beta1, (float)h.beta2, (float)h.eps};
 }
-int adamw_blocks(const unet_engine* e) { return blocks_for((e->n_params + 3) / 4, 2048); }
+int adamw_blocks(const unet_engine* e) { return blocks_for((e->tab.n_param + 3) / 4, 2048); }
 
 F32Ranges f32_ranges(const unet_engine* e) {
     F32Ranges fr;
@@ -697,22 +623,22 @@ F32Ranges f32_ranges(const unet_engine* e) {
 
 int train_or_fb(unet_engine* e, int which, const int32_t* perm, int64_t start, int batch, int slot, float* grads_out,
                 double grad_scale = 1.0) {
-    int rc = check_batch(e, which, perm, start, batch, slot);
+    int rc = check_batch(e, "unet", which, start, batch, slot, true);
     if (rc) return rc;
     if ((rc = gather_x(e, which, perm, start, batch))) return rc;
     if ((rc = forward(e, e->f(e->xb), batch, true))) return rc;
     if ((rc = loss_forward(e, which, perm, start, batch, slot, true))) return rc;
     if ((rc = backward(e, e->f(e->xb), batch))) return rc;
     if (grads_out) {
-        hipLaunchKernelGGL(k_acc_to_f32, dim3(blocks_for(e->n_params, 65536)), dim3(256), 0, e->stream, (long long)e->n_params,
+        hipLaunchKernelGGL(k_acc_to_f32, dim3(blocks_for(e->tab.n_param, 65536)), dim3(256), 0, e->stream, (long long)e->tab.n_param,
                            e->gacc(0), grads_out, grad_scale, f32_ranges(e));
     } else {
         e->step += 1;
-        hipLaunchKernelGGL(k_adamw, dim3(adamw_blocks(e)), dim3(256), 0, e->stream, (long long)e->n_params, e->params, e->gacc(0), e->m,
+        hipLaunchKernelGGL(k_adamw, dim3(adamw_blocks(e)), dim3(256), 0, e->stream, (long long)e->tab.n_param, e->params, e->gacc(0), e->m,
                            e->v, adamw_consts(e), f32_ranges(e));
         e->gacc_clean = true;
     }
-    UHIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
 
@@ -723,16 +649,16 @@ extern "C" {
 int unet_engine_create(const cae_layer_spec* enc, int n_enc, const cae_layer_spec* dec, int n_dec, int fc_size,
                        int latent_size, int max_batch, unet_engine** out) {
     if (!enc || !dec || !out || n_enc < 1 || n_dec < 1 || fc_size < 1 || latent_size < 1 || max_batch < 1)
-        return ufail(CAE_ERR_ARG, "unet_engine_create: bad argument");
+        return fail(CAE_ERR_ARG, "unet_engine_create: bad argument");
     if (n_enc != n_dec)
-        return ufail(CAE_ERR_ARG, "unet_engine_create: the UNET decoder needs one layer per encoder layer (%d vs %d): every "
-                                  "decoder layer but the last takes one skip connection (unet.py:141-145,157-161)", n_enc, n_dec);
+        return fail(CAE_ERR_ARG, "unet_engine_create: the UNET decoder needs one layer per encoder layer (%d vs %d): every "
+                                 "decoder layer but the last takes one skip connection (unet.py:141-145,157-161)", n_enc, n_dec);
     unet_engine* e = new unet_engine();
     e->fc_size = fc_size;
     e->latent = latent_size;
     e->max_batch = max_batch;
     auto bad = [&](const char* msg, int i) {
-        const int rc = ufail(CAE_ERR_ARG, "unet_engine_create: layer %d: %s", i, msg);
+        const int rc = fail(CAE_ERR_ARG, "unet_engine_create: layer %d: %s", i, msg);
         delete e;
         return rc;
     };
@@ -778,15 +704,15 @@ int unet_engine_create(const cae_layer_spec* enc, int n_enc, const cae_layer_spe
     for (int i = 0; i < n_enc; i++) {
         ConvLayer& L = e->enc[i];
         const std::string c = "enc/encoder_cnn." + std::to_string(4 * i), b = "enc/encoder_cnn." + std::to_string(4 * i + 1);
-        L.w = add_tensor(e, c + ".weight", 0, {L.g.Cs, L.g.Cl, L.g.kh, L.g.kw});
-        L.b = add_tensor(e, c + ".bias", 0, {L.g.Cs});
+        L.w = e->tab.add(c + ".weight", 0, {L.g.Cs, L.g.Cl, L.g.kh, L.g.kw});
+        L.b = e->tab.add(c + ".bias", 0, {L.g.Cs});
         add_bn(e, b, L.g.Cs, L.bn);
     }
     auto add_fc = [&](Fc& L, const std::string& key, int nin, int nout) {
         L.nin = nin;
         L.nout = nout;
-        L.w = add_tensor(e, key + ".weight", 0, {nout, nin});
-        L.b = add_tensor(e, key + ".bias", 0, {nout});
+        L.w = e->tab.add(key + ".weight", 0, {nout, nin});
+        L.b = e->tab.add(key + ".bias", 0, {nout});
     };
     add_fc(e->fc[0], "enc/encoder_lin.0", F, fc_size);
     e->fc[0].has_bn = true;
@@ -800,18 +726,17 @@ int unet_engine_create(const cae_layer_spec* enc, int n_enc, const cae_layer_spe
         ConvLayer& L = e->dec[j];
         if (!L.has_skip) continue;
         const std::string a = "dec/attention_layers." + std::to_string(j);
-        L.w1 = add_tensor(e, a + ".fc1.weight", 0, {L.R, L.g.Cl, 1, 1});
-        L.w2 = add_tensor(e, a + ".fc2.weight", 0, {L.g.Cl, L.R, 1, 1});
+        L.w1 = e->tab.add(a + ".fc1.weight", 0, {L.R, L.g.Cl, 1, 1});
+        L.w2 = e->tab.add(a + ".fc2.weight", 0, {L.g.Cl, L.R, 1, 1});
     }
     for (int j = 0; j < n_dec; j++) {
         ConvLayer& L = e->dec[j];
         const std::string c = "dec/decoder_conv." + std::to_string(4 * j), b = "dec/decoder_conv." + std::to_string(4 * j + 1);
-        L.w = add_tensor(e, c + ".weight", 0, {L.g.Cs, L.g.Cl, L.g.kh, L.g.kw});
-        L.b = add_tensor(e, c + ".bias", 0, {L.g.Cl});
+        L.w = e->tab.add(c + ".weight", 0, {L.g.Cs, L.g.Cl, L.g.kh, L.g.kw});
+        L.b = e->tab.add(c + ".bias", 0, {L.g.Cl});
         if (L.has_bn) add_bn(e, b, 2 * L.g.Cl, L.bn);
     }
-    e->n_params = (e->n_params + 3) & ~int64_t(3);
-    e->n_buffers = (e->n_buffers + 3) & ~int64_t(3);
+    e->tab.close();
     // ---- workspace -------------------------------------------------------------------------------------
     const int64_t B = max_batch;
     int64_t nd = 0;   // doubles: BN sums
@@ -827,12 +752,7 @@ int unet_engine_create(const cae_layer_spec* enc, int n_enc, const cae_layer_spe
     for (auto& L : e->dec)
         if (L.has_bn) carve_bn(L.bn);
     e->n_dsum = nd;
-    int64_t nf = 0;   // floats
-    auto F32 = [&](int64_t n) {
-        const int64_t off = nf;
-        nf += (n + 63) & ~int64_t(63);
-        return off;
-    };
+    Carver F32{64};   // the fp32 sub-arena (float offsets)
     auto carve_saved = [&](Bn& bn) { bn.saved = F32(2 * bn.C); };
     e->xb = F32(B * e->in_c * e->in_h * e->in_w);
     for (auto& L : e->enc) {
@@ -866,15 +786,11 @@ int unet_engine_create(const cae_layer_spec* enc, int n_enc, const cae_layer_spe
     };
     for (auto& L : e->dec) carve_packed(L);
     for (size_t i = 1; i < e->enc.size(); i++) carve_packed(e->enc[i]);
-    int64_t off = 0;
-    auto bytes = [&](int64_t n) {
-        const int64_t o = off;
-        off += (n + 255) & ~int64_t(255);
-        return o;
-    };
-    e->off_gacc = bytes(e->n_params * 8);
+    Carver bytes{256};
+    e->off_gacc = bytes(e->tab.n_param * 8);
     e->off_dsum = bytes(nd * 8);
-    e->off_losses = bytes((int64_t)kLossSlots * 2 * 8);
+    e->per_slot = 2;   // (mse, pearson loss)
+    e->off_losses = bytes((int64_t)kStepLossSlots * e->per_slot * 8);
     e->off_ls = bytes(B * e->out_c * 8 * 8);
     int64_t gs = 0;   // split-K scratch of the Linear GEMMs: rows x batch doubles, kept zero between uses
     for (int k = 0; k < 4; k++) gs = std::max<int64_t>(gs, (int64_t)std::max(e->fc[k].nin, e->fc[k].nout) * B);
@@ -900,49 +816,40 @@ int unet_engine_create(const cae_layer_spec* enc, int n_enc, const cae_layer_spe
     for (auto& L : e->dec) thin_need(L);
     e->off_thinpart = bytes(tp);
     e->thinpart_bytes = tp;
-    e->off_f32 = bytes(nf * 4);
-    e->ws_bytes = off;
+    e->off_f32 = bytes(F32.top * 4);
+    e->ws_bytes = bytes.top;
     *out = e;
     return CAE_OK;
 }
 
 void unet_engine_destroy(unet_engine* e) { delete e; }
 
-int64_t unet_param_count(const unet_engine* e) { return e ? e->n_params : 0; }
-int64_t unet_buffer_count(const unet_engine* e) { return e ? e->n_buffers : 0; }
-int unet_tensor_count(const unet_engine* e) { return e ? (int)e->tensors.size() : 0; }
+int64_t unet_param_count(const unet_engine* e) { return e ? e->tab.n_param : 0; }
+int64_t unet_buffer_count(const unet_engine* e) { return e ? e->tab.n_buf : 0; }
+int unet_tensor_count(const unet_engine* e) { return e ? e->tab.count() : 0; }
 int unet_tensor_info(const unet_engine* e, int index, cae_tensor_info_t* out) {
-    if (!e || !out || index < 0 || index >= (int)e->tensors.size()) return ufail(CAE_ERR_ARG, "unet_tensor_info: bad argument");
-    *out = e->tensors[index];
-    return CAE_OK;
+    return e ? e->tab.info(index, out) : fail(CAE_ERR_ARG, "unet_tensor_info: null engine");
 }
 int64_t unet_workspace_bytes(const unet_engine* e) { return e ? e->ws_bytes : 0; }
 
 int unet_bind(unet_engine* e, float* params, float* m, float* v, float* buffers, void* workspace, int64_t workspace_bytes) {
-    if (!e || !params || !m || !v || !buffers || !workspace) return ufail(CAE_ERR_ARG, "unet_bind: null pointer");
-    if (workspace_bytes < e->ws_bytes) return ufail(CAE_ERR_ARG, "unet_bind: workspace of %lld bytes, need %lld",
-                                                     (long long)workspace_bytes, (long long)e->ws_bytes);
-    if ((uintptr_t)workspace & 255) return ufail(CAE_ERR_ARG, "unet_bind: workspace must be 256-byte aligned");
-    e->params = params, e->m = m, e->v = v, e->buffers = buffers, e->ws = (char*)workspace;
+    if (int rc = bind_workspace(e, "unet", params && m && v && buffers, workspace, workspace_bytes)) return rc;
+    e->params = params, e->m = m, e->v = v, e->buffers = buffers;
     return CAE_OK;
 }
 
-int unet_set_stream(unet_engine* e, void* hip_stream) {
-    if (!e) return ufail(CAE_ERR_ARG, "unet_set_stream: null engine");
-    e->stream = (hipStream_t)hip_stream;
-    return CAE_OK;
-}
+int unet_set_stream(unet_engine* e, void* hip_stream) { return set_stream(e, "unet", hip_stream); }
 
 int unet_set_kernel_mode(unet_engine* e, int specialised) {
-    if (!e) return ufail(CAE_ERR_ARG, "unet_set_kernel_mode: null engine");
+    if (!e) return fail(CAE_ERR_ARG, "unet_set_kernel_mode: null engine");
     e->specialised = specialised ? 1 : 0;
     return CAE_OK;
 }
 
 int unet_set_hyper(unet_engine* e, double lr, double beta1, double beta2, double eps, double weight_decay, double dropout_rate,
                    double lambda_pearson, uint32_t dropout_seed) {
-    if (!e) return ufail(CAE_ERR_ARG, "unet_set_hyper: null engine");
-    if (!(dropout_rate >= 0.0 && dropout_rate < 1.0)) return ufail(CAE_ERR_ARG, "unet_set_hyper: dropout_rate must be in [0, 1)");
+    if (!e) return fail(CAE_ERR_ARG, "unet_set_hyper: null engine");
+    if (!(dropout_rate >= 0.0 && dropout_rate < 1.0)) return fail(CAE_ERR_ARG, "unet_set_hyper: dropout_rate must be in [0, 1)");
     e->hyper = Hyper{lr, beta1, beta2, eps, weight_decay};
     e->dropout = dropout_rate;
     e->lambda_p = lambda_pearson;
@@ -950,85 +857,61 @@ int unet_set_hyper(unet_engine* e, double lr, double beta1, double beta2, double
     return CAE_OK;
 }
 
-int unet_set_step(unet_engine* e, int64_t step) {
-    if (!e || step < 0) return ufail(CAE_ERR_ARG, "unet_set_step: bad argument");
-    e->step = step;
-    return CAE_OK;
-}
+int unet_set_step(unet_engine* e, int64_t step) { return set_step(e, "unet", step); }
 
 int unet_set_dataset(unet_engine* e, int which, const float* x, const float* target, const float* mask, int mask_channels,
                      int64_t n) {
-    if (!e || which < 0 || which > 1 || !x || n < 1) return ufail(CAE_ERR_ARG, "unet_set_dataset: bad argument");
-    if (mask && mask_channels != 1 && mask_channels != e->out_c)
-        return ufail(CAE_ERR_ARG, "unet_set_dataset: mask has %d channels, expected 1 or %d", mask_channels, e->out_c);
-    e->ds[which] = DataSet{x, target, mask, mask_channels, n};
-    return CAE_OK;
+    if (e && mask && mask_channels != 1 && mask_channels != e->out_c)
+        return fail(CAE_ERR_ARG, "unet_set_dataset: mask has %d channels, expected 1 or %d", mask_channels, e->out_c);
+    return set_dataset(e, "unet", which, DataSet{x, target, mask, mask_channels, n});
 }
 
 int unet_train_step(unet_engine* e, int which, const int32_t* perm, int64_t start, int batch, int loss_slot) {
-    if (e && !e->ds[which & 1].t) return ufail(CAE_ERR_STATE, "unet_train_step: data set has no target");
     return train_or_fb(e, which, perm, start, batch, loss_slot, nullptr);
 }
 
 int unet_forward_backward(unet_engine* e, int which, const int32_t* perm, int64_t start, int batch, int loss_slot,
                           float* grads, double grad_scale) {
-    if (!grads) return ufail(CAE_ERR_ARG, "unet_forward_backward: null gradient buffer");
-    if (e && !e->ds[which & 1].t) return ufail(CAE_ERR_STATE, "unet_forward_backward: data set has no target");
+    if (!grads) return fail(CAE_ERR_ARG, "unet_forward_backward: null gradient buffer");
     return train_or_fb(e, which, perm, start, batch, loss_slot, grads, grad_scale);
 }
 
 int unet_apply_gradients(unet_engine* e, const float* grads) {
-    if (!e || !e->ws || !grads) return ufail(CAE_ERR_ARG, "unet_apply_gradients: bad argument");
-    hipLaunchKernelGGL(k_f32_to_acc, dim3(blocks_for(e->n_params, 65536)), dim3(256), 0, e->stream, (long long)e->n_params, grads,
+    if (!e || !e->ws || !grads) return fail(CAE_ERR_ARG, "unet_apply_gradients: bad argument");
+    hipLaunchKernelGGL(k_f32_to_acc, dim3(blocks_for(e->tab.n_param, 65536)), dim3(256), 0, e->stream, (long long)e->tab.n_param, grads,
                        e->gacc(0));
     e->step += 1;
-    hipLaunchKernelGGL(k_adamw, dim3(adamw_blocks(e)), dim3(256), 0, e->stream, (long long)e->n_params, e->params, e->gacc(0), e->m,
+    hipLaunchKernelGGL(k_adamw, dim3(adamw_blocks(e)), dim3(256), 0, e->stream, (long long)e->tab.n_param, e->params, e->gacc(0), e->m,
                        e->v, adamw_consts(e), F32Ranges{{0, 0, 0, 0}, {0, 0, 0, 0}, 0});
     e->gacc_clean = true;
     for (int k = 0; k < 4; k++) e->fc_f32[k] = e->fc_f32_dirty[k] = false;   // every slot was rewritten as fp64 and cleared
-    UHIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
 
 int unet_eval_step(unet_engine* e, int which, const int32_t* perm, int64_t start, int batch, int loss_slot) {
-    int rc = check_batch(e, which, perm, start, batch, loss_slot);
+    int rc = check_batch(e, "unet", which, start, batch, loss_slot, true);
     if (rc) return rc;
-    if (!e->ds[which].t) return ufail(CAE_ERR_STATE, "unet_eval_step: data set has no target");
     if ((rc = gather_x(e, which, perm, start, batch))) return rc;
     if ((rc = forward(e, e->f(e->xb), batch, false))) return rc;
     return loss_forward(e, which, perm, start, batch, loss_slot, false);
 }
 
 int unet_score(unet_engine* e, const float* x, int batch, float* y) {
-    if (!e || !e->ws) return ufail(CAE_ERR_STATE, "unet_score: engine is not bound");
-    if (!x || !y || batch < 1 || batch > e->max_batch) return ufail(CAE_ERR_ARG, "unet_score: bad argument");
-    int rc = forward(e, x, batch, false);
-    if (rc) return rc;
+    int rc = check_score(e, "unet", x, batch, y);
+    if (rc || (rc = forward(e, x, batch, false))) return rc;
     const long long n = (long long)batch * e->out_c * e->out_h * e->out_w;
     hipLaunchKernelGGL(k_sigmoid, dim3(blocks_for(n, 65536)), dim3(256), 0, e->stream, e->f(e->dec.back().u), n, y);
-    UHIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
 
-int unet_loss_slots(const unet_engine* e) { return e ? kLossSlots : 0; }
-
-int unet_read_losses(unet_engine* e, int first_slot, int count, double* out) {
-    if (!e || !e->ws || !out || first_slot < 0 || count < 0 || first_slot + count > kLossSlots)
-        return ufail(CAE_ERR_ARG, "unet_read_losses: bad argument");
-    UHIP_TRY(hipMemcpyAsync(out, reinterpret_cast<double*>(e->ws + e->off_losses) + 2 * (size_t)first_slot,
-                            (size_t)count * 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    UHIP_TRY(hipStreamSynchronize(e->stream));
-    return CAE_OK;
-}
-
-int unet_sync(unet_engine* e) {
-    if (!e) return ufail(CAE_ERR_ARG, "unet_sync: null engine");
-    UHIP_TRY(hipStreamSynchronize(e->stream));
-    return CAE_OK;
-}
+int unet_loss_slots(const unet_engine* e) { return e ? kStepLossSlots : 0; }
+int unet_read_losses(unet_engine* e, int first_slot, int count, double* out) { return read_losses(e, "unet", first_slot, count, out); }
+int unet_sync(unet_engine* e) { return sync(e, "unet"); }
 
 int unet_debug_read(unet_engine* e, const char* what, float* out, int64_t count) {
-    if (!e || !e->ws || !what || !out || count < 1) return ufail(CAE_ERR_ARG, "unet_debug_read: bad argument");
+    if (!e || !e->ws || !what || !out || count < 1) return fail(CAE_ERR_ARG, "unet_debug_read: bad argument");
     std::map<std::string, int64_t> table;
     for (size_t i = 0; i < e->enc.size(); i++) {
         const std::string k = std::to_string(i);
@@ -1044,9 +927,9 @@ int unet_debug_read(unet_engine* e, const char* what, float* out, int64_t count)
     }
     for (int k = 0; k < 4; k++) table["fc_h" + std::to_string(k)] = e->fc[k].h, table["fc_a" + std::to_string(k)] = e->fc[k].a;
     auto it = table.find(what);
-    if (it == table.end()) return ufail(CAE_ERR_ARG, "unet_debug_read: unknown tensor '%s'", what);
-    UHIP_TRY(hipMemcpyAsync(out, e->f(it->second), (size_t)count * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    UHIP_TRY(hipStreamSynchronize(e->stream));
+    if (it == table.end()) return fail(CAE_ERR_ARG, "unet_debug_read: unknown tensor '%s'", what);
+    HIP_TRY(hipMemcpyAsync(out, e->f(it->second), (size_t)count * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return CAE_OK;
 }
 

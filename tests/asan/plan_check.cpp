@@ -1,9 +1,11 @@
 // CPU-only exercise of the host side of libcae_hip under AddressSanitizer: plan creation / tensor tables / error paths /
-// destruction of the ConvAE engine (plain and trunk mode through the var engine) and the UNET engine.  No GPU call is made.
+// destruction of the ConvAE engine (plain and trunk mode through the var engine), the UNET engine and the Linear engine.
+// No GPU call is made.
 #include <cstdio>
 #include <cstring>
 #include <vector>
 #include "cae_hip.h"
+#include "cae_linear.h"
 #include "cae_vae.h"
 #include "cae_unet.h"
 
@@ -84,6 +86,23 @@ int main() {
         }
         auto small = dec_layers(3, 5, 64, 4);   // 128x128 output: MS-SSIM needs >= 176
         expect(vae_engine_create(enc.data(), 2, small.data(), 5, 16, 4, 4, &v) != 0, "too small an output for MS-SSIM is refused");
+        // the Linear engine: sizes, an unbound step, bad arguments
+        lin_engine* l = nullptr;
+        expect(lin_engine_create(8, 32, 5, &l) == 0, "lin_engine_create");
+        if (l) {
+            double loss[2];
+            float dummy[4];
+            expect(lin_param_count(l) == 32 * 8 + 32, "lin_param_count");
+            expect(lin_workspace_bytes(l) > 0 && lin_loss_slots(l) == 4096, "Linear sizes");
+            expect(lin_train_step(l, 0, nullptr, 0, 5, 0) != 0, "a step on an unbound Linear engine is refused");
+            expect(lin_score(l, dummy, 1, dummy) != 0, "scoring on an unbound Linear engine is refused");
+            expect(lin_read_losses(l, 4095, 2, loss) != 0, "loss slots out of range are refused");
+            expect(lin_set_dataset(l, 2, dummy, dummy, 4) != 0 && lin_set_dataset(l, 0, nullptr, dummy, 4) != 0, "bad data sets are refused");
+            expect(lin_set_step(l, -1) != 0, "a negative step is refused");
+            expect(lin_bind(l, dummy, dummy, nullptr, dummy, 1 << 30) != 0, "a null arena is refused");
+            lin_engine_destroy(l);
+        }
+        expect(lin_engine_create(0, 32, 5, &l) != 0 && lin_engine_create(1 << 20, 1 << 20, 5, &l) != 0, "bad Linear sizes are refused");
     }
     printf(failures ? "%d checks failed\n" : "host-side plan checks clean (%d)\n", failures);
     return failures ? 1 : 0;

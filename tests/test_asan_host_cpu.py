@@ -1,7 +1,7 @@
 """The host side of libcae_hip under AddressSanitizer + LeakSanitizer (SURVEY.md §5 "sanitizers"): tools/asan_host_check.sh builds
 every .hip source with -fsanitize=address (device code compiled as usual, never launched: GPU ASAN is not available on this
 pool) and runs tests/asan/plan_check.cpp on the CPU - engine plans, tensor tables, error paths and destruction of the ConvAE
-engine, the var engine (trunk mode) and the UNET engine.  The build takes ~4 minutes, so the test runs only when asked for:
+engine, the var engine (trunk mode), the UNET engine and the Linear engine.  The build takes ~4 minutes, so the test runs only when asked for:
 CAE_ASAN=1 python -m pytest tests/test_asan_host_cpu.py  (last run: clean)."""
 import os
 import subprocess

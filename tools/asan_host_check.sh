@@ -3,7 +3,7 @@
 # this pool, so the device code is compiled as usual and never launched): every .hip source is compiled with
 # -fsanitize=address -fno-gpu-sanitize into cae_tools_amd/csrc/_obj_asan/, linked with tests/asan/plan_check.cpp, and the
 # executable - engine plans, tensor tables, error paths, destruction, for the ConvAE engine, the var engine (a trunk-mode
-# ConvAE engine inside) and the UNET engine - runs on the CPU.  ~4 minutes (engine.hip is one translation unit).
+# ConvAE engine inside), the UNET engine and the Linear engine - runs on the CPU.  ~4 minutes (engine.hip is one translation unit).
 #     bash tools/asan_host_check.sh
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
