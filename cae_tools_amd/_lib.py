@@ -114,6 +114,7 @@ SIGNATURES = {
     "unet_read_losses": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "unet_sync": (C.c_int, [_P]),
     "unet_debug_read": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
+    "unet_debug_plan": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p, C.c_int64]),
     # ---- include/cae_vae.h ----
     "vae_engine_create": (C.c_int, [C.POINTER(LayerSpecC), C.c_int, C.POINTER(LayerSpecC), C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.POINTER(C.c_void_p)]),

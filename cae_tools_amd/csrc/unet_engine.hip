@@ -1,7 +1,8 @@
 // unet_engine.hip — host side of the UNET path: tensor table, workspace carving, launch sequence and the
 // extern "C" ABI declared in include/cae_unet.h.
 //
-// Which kernels a layer runs (conv_down / conv_up / conv_wgrad / lin_fwd / lin_bwd below decide, in this order):
+// Which kernels a layer runs (choose_down / choose_up / choose_wgrad / choose_lin below decide, in this order; unet_debug_plan
+// reports their answers):
 //   4x4 / s2 / p1 layers with <= 4 channels on the large side (the image end)   kernels_unet_thin.h   (patch in LDS, weights in registers)
 //   ... with maps 16 / 32 / 64 / 128 wide and channel counts multiples of 4 / 8   kernels_unet_patch.h  (patch in LDS, weight tiles in LDS)
 //   any other 4x4 / s2 / p1 layer                                                 kernels_unet_mfma.h   (im2col tile engine)
@@ -130,20 +131,58 @@ Drop make_drop(const unet_engine* e, uint32_t site, bool train) {
 }
 
 // ---- conv dispatch --------------------------------------------------------------------------------
-void conv_down(unet_engine* e, const Geom& g, const float* L, const float* w, const float* bias, float* S) {
-    static const int thin_off = env_int("CAE_UNET_THIN", 1) == 0;   // env: A/B measurements only
-    if (e->specialised && !thin_off && thin_geom(g)) {   // the image-end layers: kernels_unet_thin.h
-        thin_down_launch(g, L, w, bias, S, e->stream);
-        return;
-    }
+// The choosers below are the whole decision: the launch code switches on what they return and unet_debug_plan reports it.
+enum DownK { DOWN_THIN, DOWN_PATCH, DOWN_MFMA, DOWN_GENERIC };
+enum UpK { UP_THIN, UP_THIN_CL, UP_PATCH, UP_MFMA, UP_GENERIC };
+// *_ATOMIC: the same kernel family with fp64 atomics from every workgroup instead of partial tiles folded in order
+enum WgradK { WG_THIN, WG_THIN_ATOMIC, WG_PATCH, WG_MFMA, WG_MFMA_ATOMIC, WG_GENERIC };
+enum LinK { LIN_BIG, LIN_GEMM16, LIN_TILE, LIN_GENERIC };
+
+const char* const kDownName[] = {"thin", "patch", "mfma", "generic"};
+const char* const kUpName[] = {"thin", "up_thin", "patch", "mfma", "generic"};
+const char* const kWgradName[] = {"thin", "thin_atomic", "patch", "mfma", "mfma_atomic", "generic"};
+const char* const kLinName[] = {"lin_big", "gemm16", "tile", "generic"};
+
+DownK choose_down(const unet_engine* e, const Geom& g) {
+    static const int thin_off = env_int("CAE_UNET_THIN", 1) == 0;     // env: A/B measurements only
     static const int patch_off = env_int("CAE_UNET_PATCH", 1) == 0;   // env: A/B measurements only
-    if (e->specialised && !patch_off && patch_geom(g)) {   // the wide layers: kernels_unet_patch.h
-        pdown_launch(g, L, w, bias, S, e->stream);
-        return;
+    if (e->specialised && !thin_off && thin_geom(g)) return DOWN_THIN;       // the image-end layers: kernels_unet_thin.h
+    if (e->specialised && !patch_off && patch_geom(g)) return DOWN_PATCH;    // the wide layers: kernels_unet_patch.h
+    if (e->specialised && mfma_down_eligible(g)) return DOWN_MFMA;
+    return DOWN_GENERIC;
+}
+
+// has_wp: the layer has repacked weights (pack_up_weights below); the thin, patch and tile-engine kernels read only those
+UpK choose_up(const unet_engine* e, const Geom& g, bool has_wp) {
+    static const int thin_off = env_int("CAE_UNET_THIN", 1) == 0;     // env: A/B measurements only
+    static const int patch_off = env_int("CAE_UNET_PATCH", 1) == 0;   // env: A/B measurements only
+    if (e->specialised && !thin_off && has_wp && thin_up_geom(g)) return UP_THIN;   // ... 128 columns wide: kernels_unet_thin.h
+    if (e->specialised && mfma_geom(g) && g.Cl <= 4) return UP_THIN_CL;   // a handful of output channels: streaming, not a GEMM
+    if (e->specialised && !patch_off && has_wp && g.Cl > 4 && pup_geom(g)) return UP_PATCH;   // the wide layers
+    if (e->specialised && has_wp && mfma_up_eligible(g)) return UP_MFMA;
+    return UP_GENERIC;
+}
+
+WgradK choose_wgrad(const unet_engine* e, const Geom& g) {
+    static const int thin_off = env_int("CAE_UNET_THIN", 1) == 0;     // env: A/B measurements only
+    static const int patch_off = env_int("CAE_UNET_PATCH", 1) == 0;   // env: A/B measurements only
+    static const int part_off = env_int("CAE_UNET_WGPART", 1) == 0;   // env: A/B measurements only
+    if (e->specialised && !thin_off && thin_geom(g))   // the image-end layers: kernels_unet_thin.h
+        return thin_wgrad_part_bytes(g) <= (size_t)e->thinpart_bytes ? WG_THIN : WG_THIN_ATOMIC;
+    if (e->specialised && !patch_off && pwgrad_geom(g) && pwgrad_part_bytes(g) <= (size_t)e->thinpart_bytes) return WG_PATCH;
+    if (e->specialised && mfma_wgrad_eligible(g)) {
+        const size_t need = mfma_wgrad_part_bytes(g);
+        return (!part_off && need && need <= (size_t)e->thinpart_bytes) ? WG_MFMA : WG_MFMA_ATOMIC;
     }
-    if (e->specialised && mfma_down_eligible(g)) {
-        mfma_down_launch(g, L, w, bias, S, e->stream);
-        return;
+    return WG_GENERIC;
+}
+
+void conv_down(unet_engine* e, const Geom& g, const float* L, const float* w, const float* bias, float* S) {
+    switch (choose_down(e, g)) {
+        case DOWN_THIN: thin_down_launch(g, L, w, bias, S, e->stream); return;
+        case DOWN_PATCH: pdown_launch(g, L, w, bias, S, e->stream); return;
+        case DOWN_MFMA: mfma_down_launch(g, L, w, bias, S, e->stream); return;
+        case DOWN_GENERIC: break;
     }
     const long long total = (long long)g.B * g.Cs * g.Hs * g.Ws;
     hipLaunchKernelGGL(k_down, dim3(blocks_for(total, 65536)), dim3(256), 0, e->stream, g, L, w, bias, S);
@@ -151,52 +190,35 @@ void conv_down(unet_engine* e, const Geom& g, const float* L, const float* w, co
 
 // wp: the layer's repacked weights (pack_up_weights below) or nullptr when the layer does not run the tile engine
 void conv_up(unet_engine* e, const Geom& g, const float* S, const float* w, const float* wp, const float* bias, float* L) {
-    static const int thin_off = env_int("CAE_UNET_THIN", 1) == 0;   // env: A/B measurements only
-    if (e->specialised && !thin_off && wp && thin_up_geom(g)) {   // ... 128 columns wide: the row walk of kernels_unet_thin.h
-        thin_up_launch(g, S, wp, bias, L, e->stream);
-        return;
-    }
-    if (e->specialised && mfma_geom(g) && g.Cl <= 4) {   // a handful of output channels: streaming kernel, not a GEMM
-        const int blocks = blocks_for((long long)g.B * g.Hs * g.Ws, 65536);
-        switch (g.Cl) {
-            case 1: hipLaunchKernelGGL(k_up_thin<1>, dim3(blocks), dim3(256), 0, e->stream, g, S, w, bias, L); break;
-            case 2: hipLaunchKernelGGL(k_up_thin<2>, dim3(blocks), dim3(256), 0, e->stream, g, S, w, bias, L); break;
-            case 3: hipLaunchKernelGGL(k_up_thin<3>, dim3(blocks), dim3(256), 0, e->stream, g, S, w, bias, L); break;
-            default: hipLaunchKernelGGL(k_up_thin<4>, dim3(blocks), dim3(256), 0, e->stream, g, S, w, bias, L); break;
+    switch (choose_up(e, g, wp != nullptr)) {
+        case UP_THIN: thin_up_launch(g, S, wp, bias, L, e->stream); return;
+        case UP_THIN_CL: {
+            const int blocks = blocks_for((long long)g.B * g.Hs * g.Ws, 65536);
+            switch (g.Cl) {
+                case 1: hipLaunchKernelGGL(k_up_thin<1>, dim3(blocks), dim3(256), 0, e->stream, g, S, w, bias, L); break;
+                case 2: hipLaunchKernelGGL(k_up_thin<2>, dim3(blocks), dim3(256), 0, e->stream, g, S, w, bias, L); break;
+                case 3: hipLaunchKernelGGL(k_up_thin<3>, dim3(blocks), dim3(256), 0, e->stream, g, S, w, bias, L); break;
+                default: hipLaunchKernelGGL(k_up_thin<4>, dim3(blocks), dim3(256), 0, e->stream, g, S, w, bias, L); break;
+            }
+            return;
         }
-        return;
-    }
-    static const int patch_off = env_int("CAE_UNET_PATCH", 1) == 0;   // env: A/B measurements only
-    if (e->specialised && !patch_off && wp && g.Cl > 4 && pup_geom(g)) {   // the wide layers: kernels_unet_patch.h
-        pup_launch(g, S, wp, bias, L, e->stream);
-        return;
-    }
-    if (e->specialised && wp && mfma_up_eligible(g)) {
-        mfma_up_launch(g, S, wp, bias, L, e->stream);
-        return;
+        case UP_PATCH: pup_launch(g, S, wp, bias, L, e->stream); return;
+        case UP_MFMA: mfma_up_launch(g, S, wp, bias, L, e->stream); return;
+        case UP_GENERIC: break;
     }
     const long long total = (long long)g.B * g.Cl * g.Hl * g.Wl;
     hipLaunchKernelGGL(k_up, dim3(blocks_for(total, 65536)), dim3(256), 0, e->stream, g, S, w, bias, L);
 }
 
 void conv_wgrad(unet_engine* e, const Geom& g, const float* S, const float* L, double* acc) {
-    static const int thin_off = env_int("CAE_UNET_THIN", 1) == 0;   // env: A/B measurements only
-    if (e->specialised && !thin_off && thin_geom(g)) {   // the image-end layers: kernels_unet_thin.h
-        float* part = thin_wgrad_part_bytes(g) <= (size_t)e->thinpart_bytes ? reinterpret_cast<float*>(e->ws + e->off_thinpart) : nullptr;
-        thin_wgrad_launch(g, S, L, acc, part, e->stream);
-        return;
-    }
-    static const int patch_off = env_int("CAE_UNET_PATCH", 1) == 0;   // env: A/B measurements only
-    if (e->specialised && !patch_off && pwgrad_geom(g) && pwgrad_part_bytes(g) <= (size_t)e->thinpart_bytes) {   // kernels_unet_patch.h
-        pwgrad_launch(g, S, L, acc, reinterpret_cast<float*>(e->ws + e->off_thinpart), e->stream);
-        return;
-    }
-    if (e->specialised && mfma_wgrad_eligible(g)) {
-        static const int part_off = env_int("CAE_UNET_WGPART", 1) == 0;   // env: A/B measurements only
-        const size_t need = mfma_wgrad_part_bytes(g);
-        float* part = (!part_off && need && need <= (size_t)e->thinpart_bytes) ? reinterpret_cast<float*>(e->ws + e->off_thinpart) : nullptr;
-        mfma_wgrad_launch(g, S, L, acc, part, e->stream);
-        return;
+    float* part = reinterpret_cast<float*>(e->ws + e->off_thinpart);
+    switch (choose_wgrad(e, g)) {
+        case WG_THIN: thin_wgrad_launch(g, S, L, acc, part, e->stream); return;
+        case WG_THIN_ATOMIC: thin_wgrad_launch(g, S, L, acc, nullptr, e->stream); return;
+        case WG_PATCH: pwgrad_launch(g, S, L, acc, part, e->stream); return;
+        case WG_MFMA: mfma_wgrad_launch(g, S, L, acc, part, e->stream); return;
+        case WG_MFMA_ATOMIC: mfma_wgrad_launch(g, S, L, acc, nullptr, e->stream); return;
+        case WG_GENERIC: break;
     }
     const long long per = (long long)g.B * g.Hs * g.Ws;
     int split = (int)((per + 256 * 16 - 1) / (256 * 16));
@@ -301,26 +323,36 @@ void lin_gemm(unet_engine* e, bool nt, const float* X, long long x_ld, const flo
                            Y, (long long)N);
 }
 
+// (forward and backward of a Linear layer take the same family)
+LinK choose_lin(const unet_engine* e, const Fc& L, int B) {
+    if (lin_big(e, L, B)) return LIN_BIG;
+    if (e->specialised && small_fc(L)) return LIN_GEMM16;
+    if (e->specialised) return LIN_TILE;
+    return LIN_GENERIC;
+}
+
 void lin_fwd(unet_engine* e, const Fc& L, int B, const float* in, float* out) {
-    if (lin_big(e, L, B)) {   // out[b][o] = bias[o] + sum_i in[b][i] W[o][i]
-        lin_gemm(e, true, in, L.nin, e->P(L.w), L.nin, e->P(L.b), out, B, L.nout, L.nin);
-        return;
-    }
-    if (e->specialised && small_fc(L)) {   // out[b][o] = bias[o] + sum_i in[b][i] W[o][i]
-        ugemm::cae::GemmArgs ga = gemm16_args(B, L.nout, L.nin);
-        ga.A = in, ga.sa_m = L.nin, ga.sa_k = 1;
-        ga.B = e->P(L.w), ga.sb_k = 1, ga.sb_n = L.nin;           // B[k][n] = W[n][k]
-        ga.C = out, ga.sc_m = L.nout, ga.sc_n = 1;
-        ga.epi = ugemm::cae::GE_STORE;
-        ga.bias = e->P(L.b);
-        const int tiles = ((B + 15) / 16) * ((L.nout + 15) / 16);
-        hipLaunchKernelGGL(ugemm::cae::k_gemm16, dim3(tiles), dim3(256), gemm16_lds(), e->stream, ga);
-        return;
-    }
-    if (e->specialised) {   // out[b][o] = bias[o] + sum_i in[b][i] W[o][i]
-        GemmDesc d{L.nout, B, L.nin, e->P(L.w), L.nin, 1, in, 1, L.nin, e->P(L.b), out, nullptr, 1, L.nout, 0};
-        gemm_launch(d, reinterpret_cast<double*>(e->ws + e->off_gscratch), e->stream);
-        return;
+    switch (choose_lin(e, L, B)) {
+        case LIN_BIG:   // out[b][o] = bias[o] + sum_i in[b][i] W[o][i]
+            lin_gemm(e, true, in, L.nin, e->P(L.w), L.nin, e->P(L.b), out, B, L.nout, L.nin);
+            return;
+        case LIN_GEMM16: {   // out[b][o] = bias[o] + sum_i in[b][i] W[o][i]
+            ugemm::cae::GemmArgs ga = gemm16_args(B, L.nout, L.nin);
+            ga.A = in, ga.sa_m = L.nin, ga.sa_k = 1;
+            ga.B = e->P(L.w), ga.sb_k = 1, ga.sb_n = L.nin;           // B[k][n] = W[n][k]
+            ga.C = out, ga.sc_m = L.nout, ga.sc_n = 1;
+            ga.epi = ugemm::cae::GE_STORE;
+            ga.bias = e->P(L.b);
+            const int tiles = ((B + 15) / 16) * ((L.nout + 15) / 16);
+            hipLaunchKernelGGL(ugemm::cae::k_gemm16, dim3(tiles), dim3(256), gemm16_lds(), e->stream, ga);
+            return;
+        }
+        case LIN_TILE: {   // out[b][o] = bias[o] + sum_i in[b][i] W[o][i]
+            GemmDesc d{L.nout, B, L.nin, e->P(L.w), L.nin, 1, in, 1, L.nin, e->P(L.b), out, nullptr, 1, L.nout, 0};
+            gemm_launch(d, reinterpret_cast<double*>(e->ws + e->off_gscratch), e->stream);
+            return;
+        }
+        case LIN_GENERIC: break;
     }
     hipLaunchKernelGGL(k_lin_fwd, dim3(L.nout, (B + 7) / 8), dim3(256), 0, e->stream, B, L.nin, L.nout, in, e->P(L.w),
                        e->P(L.b), out);
@@ -328,60 +360,64 @@ void lin_fwd(unet_engine* e, const Fc& L, int B, const float* in, float* out) {
 
 void lin_bwd(unet_engine* e, const Fc& L, int B, const float* in, const float* gout, float* gin) {
     const int fk = (int)(&L - e->fc);
-    const bool big = lin_big(e, L, B);
+    const LinK k = choose_lin(e, L, B);
+    const bool big = k == LIN_BIG;
     if (!big && e->fc_f32_dirty[fk]) {   // an earlier step left fp32 gradients in these fp64 slots
         (void)hipMemsetAsync(e->gacc(L.w), 0, (size_t)L.nin * L.nout * sizeof(double), e->stream);
         e->fc_f32_dirty[fk] = false;
     }
     e->fc_f32[fk] = big;
-    if (big) {
-        // dW[o][i] = sum_b gout[b][o] in[b][i] as fp32 in the first half of the weight's accumulator slots (F32Ranges),
-        // db[o] = sum_b gout[b][o];  gin[b][i] = sum_o gout[b][o] W[o][i]
-        e->fc_f32_dirty[fk] = true;
-        const int B8 = (B + 7) & ~7;
-        const size_t lds = (size_t)2 * B8 * kLinPN * sizeof(float);
-        static bool raised = false;   // above the 64 KiB a kernel gets without asking (batch > 56)
-        if (lds > 65536 && !raised) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lin_outer), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * kLinPN * 4);
-            raised = true;
-        }
-        hipLaunchKernelGGL(k_lin_outer, dim3((L.nin + 127) / 128, (L.nout + 127) / 128), dim3(256), lds, e->stream, gout, (long long)L.nout, in,
-                           (long long)L.nin, B, L.nout, L.nin, reinterpret_cast<float*>(e->gacc(L.w)), e->gacc(L.b));
-        if (gin) lin_gemm(e, false, gout, L.nout, e->P(L.w), L.nin, nullptr, gin, B, L.nin, L.nout);
-        return;
-    }
-    if (e->specialised && small_fc(L)) {
-        // dW[o][i] = sum_b gout[b][o] in[b][i], db[o] = sum_b gout[b][o] (a ones column), K = the whole batch in one tile: plain
-        // fp64 stores into the (zeroed) accumulator, one writer per element; beside it gin[b][i] = sum_o gout[b][o] W[o][i]
-        ugemm::cae::GemmArgs gw = gemm16_args(L.nout, L.nin + 1, B);
-        gw.A = gout, gw.sa_m = 1, gw.sa_k = L.nout;
-        gw.B = in, gw.sb_k = L.nin, gw.sb_n = 1;
-        gw.epi = ugemm::cae::GE_ACC64;
-        gw.accW = e->gacc(L.w), gw.accB = e->gacc(L.b), gw.ones_col = 1;
-        const int tiles_w = ((gw.M + 15) / 16) * ((gw.N + 15) / 16);
-        if (!gin) {
-            hipLaunchKernelGGL(ugemm::cae::k_gemm16, dim3(tiles_w), dim3(256), gemm16_lds(), e->stream, gw);
+    switch (k) {
+        case LIN_BIG: {
+            // dW[o][i] = sum_b gout[b][o] in[b][i] as fp32 in the first half of the weight's accumulator slots (F32Ranges),
+            // db[o] = sum_b gout[b][o];  gin[b][i] = sum_o gout[b][o] W[o][i]
+            e->fc_f32_dirty[fk] = true;
+            const int B8 = (B + 7) & ~7;
+            const size_t lds = (size_t)2 * B8 * kLinPN * sizeof(float);
+            static bool raised = false;   // above the 64 KiB a kernel gets without asking (batch > 56)
+            if (lds > 65536 && !raised) {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lin_outer), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * kLinPN * 4);
+                raised = true;
+            }
+            hipLaunchKernelGGL(k_lin_outer, dim3((L.nin + 127) / 128, (L.nout + 127) / 128), dim3(256), lds, e->stream, gout, (long long)L.nout, in,
+                               (long long)L.nin, B, L.nout, L.nin, reinterpret_cast<float*>(e->gacc(L.w)), e->gacc(L.b));
+            if (gin) lin_gemm(e, false, gout, L.nout, e->P(L.w), L.nin, nullptr, gin, B, L.nin, L.nout);
             return;
         }
-        ugemm::cae::GemmArgs gd = gemm16_args(B, L.nin, L.nout);
-        gd.A = gout, gd.sa_m = L.nout, gd.sa_k = 1;
-        gd.B = e->P(L.w), gd.sb_k = L.nin, gd.sb_n = 1;           // B[k = o][n = i] = W[o][i]
-        gd.C = gin, gd.sc_m = L.nin, gd.sc_n = 1;
-        gd.epi = ugemm::cae::GE_STORE;
-        const int tiles_d = ((gd.M + 15) / 16) * ((gd.N + 15) / 16);
-        hipLaunchKernelGGL(ugemm::cae::k_gemm16_pair, dim3(tiles_w + tiles_d), dim3(256), gemm16_lds(), e->stream, gw, gd, tiles_w, 0);
-        return;
-    }
-    if (e->specialised) {
-        // dW[o][i] += sum_b gout[b][o] in[b][i];  db[o] += sum_b gout[b][o];  gin[b][i] = sum_o gout[b][o] W[o][i]
-        GemmDesc w{L.nout, L.nin, B, gout, 1, L.nout, in, L.nin, 1, nullptr, nullptr, e->gacc(L.w), L.nin, 1, 2};
-        gemm_launch(w, nullptr, e->stream);
-        hipLaunchKernelGGL(k_col_sums, dim3((L.nout + 255) / 256), dim3(256), 0, e->stream, B, L.nout, gout, e->gacc(L.b));
-        if (gin) {
-            GemmDesc d{L.nin, B, L.nout, e->P(L.w), 1, L.nin, gout, 1, L.nout, nullptr, gin, nullptr, 1, L.nin, 0};
-            gemm_launch(d, reinterpret_cast<double*>(e->ws + e->off_gscratch), e->stream);
+        case LIN_GEMM16: {
+            // dW[o][i] = sum_b gout[b][o] in[b][i], db[o] = sum_b gout[b][o] (a ones column), K = the whole batch in one tile: plain
+            // fp64 stores into the (zeroed) accumulator, one writer per element; beside it gin[b][i] = sum_o gout[b][o] W[o][i]
+            ugemm::cae::GemmArgs gw = gemm16_args(L.nout, L.nin + 1, B);
+            gw.A = gout, gw.sa_m = 1, gw.sa_k = L.nout;
+            gw.B = in, gw.sb_k = L.nin, gw.sb_n = 1;
+            gw.epi = ugemm::cae::GE_ACC64;
+            gw.accW = e->gacc(L.w), gw.accB = e->gacc(L.b), gw.ones_col = 1;
+            const int tiles_w = ((gw.M + 15) / 16) * ((gw.N + 15) / 16);
+            if (!gin) {
+                hipLaunchKernelGGL(ugemm::cae::k_gemm16, dim3(tiles_w), dim3(256), gemm16_lds(), e->stream, gw);
+                return;
+            }
+            ugemm::cae::GemmArgs gd = gemm16_args(B, L.nin, L.nout);
+            gd.A = gout, gd.sa_m = L.nout, gd.sa_k = 1;
+            gd.B = e->P(L.w), gd.sb_k = L.nin, gd.sb_n = 1;           // B[k = o][n = i] = W[o][i]
+            gd.C = gin, gd.sc_m = L.nin, gd.sc_n = 1;
+            gd.epi = ugemm::cae::GE_STORE;
+            const int tiles_d = ((gd.M + 15) / 16) * ((gd.N + 15) / 16);
+            hipLaunchKernelGGL(ugemm::cae::k_gemm16_pair, dim3(tiles_w + tiles_d), dim3(256), gemm16_lds(), e->stream, gw, gd, tiles_w, 0);
+            return;
         }
-        return;
+        case LIN_TILE: {
+            // dW[o][i] += sum_b gout[b][o] in[b][i];  db[o] += sum_b gout[b][o];  gin[b][i] = sum_o gout[b][o] W[o][i]
+            GemmDesc w{L.nout, L.nin, B, gout, 1, L.nout, in, L.nin, 1, nullptr, nullptr, e->gacc(L.w), L.nin, 1, 2};
+            gemm_launch(w, nullptr, e->stream);
+            hipLaunchKernelGGL(k_col_sums, dim3((L.nout + 255) / 256), dim3(256), 0, e->stream, B, L.nout, gout, e->gacc(L.b));
+            if (gin) {
+                GemmDesc d{L.nin, B, L.nout, e->P(L.w), 1, L.nin, gout, 1, L.nout, nullptr, gin, nullptr, 1, L.nin, 0};
+                gemm_launch(d, reinterpret_cast<double*>(e->ws + e->off_gscratch), e->stream);
+            }
+            return;
+        }
+        case LIN_GENERIC: break;
     }
     hipLaunchKernelGGL(k_lin_wgrad, dim3(blocks_for((long long)L.nout * L.nin, 65536)), dim3(256), 0, e->stream, B, L.nin,
                        L.nout, gout, in, e->gacc(L.w), e->gacc(L.b));
@@ -390,22 +426,36 @@ void lin_bwd(unet_engine* e, const Fc& L, int B, const float* in, const float* g
                            L.nout, gout, e->P(L.w), gin);
 }
 
-// the weights of every layer that runs OpUp (decoder forward; encoder input gradients when training), repacked in one launch
-void pack_up_weights(unet_engine* e, bool train) {
-    if (!e->specialised) return;
-    PackSet ps;
-    memset(&ps, 0, sizeof ps);
-    auto add = [&](const ConvLayer& L) {
-        if (L.wp < 0 || ps.n == 8) return;
-        ps.thin[ps.n] = L.g.Cl <= 4;                           // (the image-end layer: k_thin_up's order)
-        ps.Cs[ps.n] = L.g.Cs, ps.Cl[ps.n] = L.g.Cl, ps.w[ps.n] = e->P(L.w), ps.wp[ps.n] = e->f(L.wp);
-        ps.begin[ps.n + 1] = ps.begin[ps.n] + (long long)16 * L.g.Cs * L.g.Cl;
-        ps.n++;
-    };
-    for (auto& L : e->dec) add(L);
+// the layers whose weights pack_up_weights repacks: every layer with a repack buffer that runs OpUp in this mode (decoder
+// forward; encoder input gradients when training), in launch order
+std::vector<const ConvLayer*> pack_list(const unet_engine* e, bool train) {
+    std::vector<const ConvLayer*> v;
+    if (!e->specialised) return v;
+    for (auto& L : e->dec)
+        if (L.wp >= 0) v.push_back(&L);
     if (train)
-        for (size_t i = 1; i < e->enc.size(); i++) add(e->enc[i]);
-    if (ps.n) hipLaunchKernelGGL(k_pack_up_weights, dim3(blocks_for(ps.begin[ps.n], 2048)), dim3(256), 0, e->stream, ps);
+        for (size_t i = 1; i < e->enc.size(); i++)
+            if (e->enc[i].wp >= 0) v.push_back(&e->enc[i]);
+    return v;
+}
+constexpr int kPackPer = (int)(sizeof(PackSet::Cs) / sizeof(int));   // entries one k_pack_up_weights launch takes
+int pack_launches(size_t entries) { return (int)((entries + kPackPer - 1) / kPackPer); }
+
+// ... repacked in one launch per kPackPer of them (one launch up to cfg3's seven)
+void pack_up_weights(unet_engine* e, bool train) {
+    const std::vector<const ConvLayer*> layers = pack_list(e, train);
+    for (size_t first = 0; first < layers.size(); first += kPackPer) {
+        PackSet ps;
+        memset(&ps, 0, sizeof ps);
+        for (size_t k = first; k < layers.size() && ps.n < kPackPer; k++) {
+            const ConvLayer& L = *layers[k];
+            ps.thin[ps.n] = L.g.Cl <= 4;                           // (the image-end layer: k_thin_up's order)
+            ps.Cs[ps.n] = L.g.Cs, ps.Cl[ps.n] = L.g.Cl, ps.w[ps.n] = e->P(L.w), ps.wp[ps.n] = e->f(L.wp);
+            ps.begin[ps.n + 1] = ps.begin[ps.n] + (long long)16 * L.g.Cs * L.g.Cl;
+            ps.n++;
+        }
+        hipLaunchKernelGGL(k_pack_up_weights, dim3(blocks_for(ps.begin[ps.n], 2048)), dim3(256), 0, e->stream, ps);
+    }
 }
 
 // ---- forward ----------------------------------------------------------------------------------------
@@ -930,6 +980,49 @@ int unet_debug_read(unet_engine* e, const char* what, float* out, int64_t count)
     if (it == table.end()) return fail(CAE_ERR_ARG, "unet_debug_read: unknown tensor '%s'", what);
     HIP_TRY(hipMemcpyAsync(out, e->f(it->second), (size_t)count * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return CAE_OK;
+}
+
+int unet_debug_plan(const unet_engine* e, int batch, int train, char* out, int64_t out_bytes) {
+    if (!e || !out || out_bytes < 1) return fail(CAE_ERR_ARG, "unet_debug_plan: bad argument");
+    if (batch < 1 || batch > e->max_batch)
+        return fail(CAE_ERR_ARG, "unet_debug_plan: batch %d outside 1 .. %d", batch, e->max_batch);
+    const std::vector<const ConvLayer*> packed = pack_list(e, train != 0);
+    auto in_pack = [&](const ConvLayer& L) { return (int)(std::find(packed.begin(), packed.end(), &L) != packed.end()); };
+    auto geom = [&](const ConvLayer& L) {
+        Geom g = L.g;
+        g.B = batch;
+        return g;
+    };
+    std::string s;
+    char line[256];
+    // the calls forward() and backward() make: an encoder layer runs OpDown forward, its weight gradient and (but the first)
+    // OpUp for its input gradient; a decoder layer runs OpUp forward, its weight gradient and OpDown for its input gradient
+    for (size_t i = 0; i < e->enc.size(); i++) {
+        const ConvLayer& L = e->enc[i];
+        const Geom g = geom(L);
+        snprintf(line, sizeof line, "enc%zu down=%s up=%s wgrad=%s wp=%d packed=%d\n", i, kDownName[choose_down(e, g)],
+                 train && i > 0 ? kUpName[choose_up(e, g, L.wp >= 0)] : "-", train ? kWgradName[choose_wgrad(e, g)] : "-",
+                 (int)(L.wp >= 0), in_pack(L));
+        s += line;
+    }
+    for (int k = 0; k < 4; k++) {
+        const char* fam = kLinName[choose_lin(e, e->fc[k], batch)];
+        snprintf(line, sizeof line, "fc%d fwd=%s bwd=%s\n", k, fam, train ? fam : "-");
+        s += line;
+    }
+    for (size_t j = 0; j < e->dec.size(); j++) {
+        const ConvLayer& L = e->dec[j];
+        const Geom g = geom(L);
+        snprintf(line, sizeof line, "dec%zu down=%s up=%s wgrad=%s wp=%d packed=%d\n", j, train ? kDownName[choose_down(e, g)] : "-",
+                 kUpName[choose_up(e, g, L.wp >= 0)], train ? kWgradName[choose_wgrad(e, g)] : "-", (int)(L.wp >= 0), in_pack(L));
+        s += line;
+    }
+    snprintf(line, sizeof line, "pack entries=%zu launches=%d\n", packed.size(), pack_launches(packed.size()));
+    s += line;
+    if ((int64_t)s.size() + 1 > out_bytes)
+        return fail(CAE_ERR_ARG, "unet_debug_plan: the report needs %zu bytes, got %lld", s.size() + 1, (long long)out_bytes);
+    memcpy(out, s.c_str(), s.size() + 1);
     return CAE_OK;
 }
 

@@ -2,6 +2,8 @@
 
 As in engine.py, torch is a container: flat CUDA tensors for the parameter / AdamW / running-statistics
 arenas and the workspace, and a stream.  Every FLOP runs in the HIP kernels."""
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -14,6 +16,22 @@ class UnetPlan(SpecPlan):
 
     PREFIX = "unet_"
 
+    def set_kernel_mode(self, specialised):
+        """True (the default): the shape-specialised kernels where a layer is eligible; False: the shape-generic ones"""
+        check(self.lib.unet_set_kernel_mode(self.handle, 1 if specialised else 0))
+
+    def kernel_plan(self, batch, train):
+        """the kernel families a step at this batch runs (unet_debug_plan, include/cae_unet.h), no GPU needed:
+        {"enc0": {"down": "thin", "up": "-", "wgrad": "thin", "wp": "0", "packed": "0"}, ..., "fc0": {"fwd": ..., "bwd": ...},
+        ..., "dec0": {...}, "pack": {"entries": "7", "launches": "1"}}"""
+        buf = C.create_string_buffer(1 << 16)
+        check(self.lib.unet_debug_plan(self.handle, int(batch), 1 if train else 0, buf, len(buf)))
+        plan = {}
+        for line in buf.value.decode().splitlines():
+            (name, *fields) = line.split()
+            plan[name] = dict(f.split("=", 1) for f in fields)
+        return plan
+
 
 class UnetEngine(SteppedEngine, UnetPlan):
 
@@ -23,7 +41,7 @@ class UnetEngine(SteppedEngine, UnetPlan):
         require_gpu()
         super().__init__(spec, fc_size, latent_size, max_batch)
         self._bind(device, buffers=True)
-        check(self.lib.unet_set_kernel_mode(self.handle, 1 if specialised else 0))
+        self.set_kernel_mode(specialised)
         torch.cuda.synchronize(self.device)
         self._start()
 

@@ -84,6 +84,13 @@ int unet_read_losses(unet_engine* e, int first_slot, int count, double* out_host
 int unet_sync(unet_engine* e);
 /* blocking debug read of an internal activation ("enc_z0", "enc_s0", "dec_u1", "dec_cat0", "att0", "y" ...) */
 int unet_debug_read(unet_engine* e, const char* what, float* out_host, int64_t count);
+/* the kernel plan of a step at this batch (train 1: training step, 0: eval / score), from the choosers the launch code
+ * switches on; no bound workspace or GPU needed.  One line per layer, in order enc0.., fc0..fc3, dec0..:
+ *   "enc<i> down=<family> up=<family> wgrad=<family> wp=<0|1> packed=<0|1>"   (dec<j> likewise; "-": not run in this mode)
+ *   "fc<k> fwd=<family> bwd=<family>"
+ * then "pack entries=<n> launches=<m>".  wp: the layer has a repack buffer; packed: its weights are repacked before the
+ * step.  Writes a NUL-terminated string of at most out_bytes bytes. */
+int unet_debug_plan(const unet_engine* e, int batch, int train, char* out_host, int64_t out_bytes);
 
 #ifdef __cplusplus
 }

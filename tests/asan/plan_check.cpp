@@ -1,5 +1,6 @@
 // CPU-only exercise of the host side of libcae_hip under AddressSanitizer: plan creation / tensor tables / error paths /
-// destruction of the ConvAE engine (plain and trunk mode through the var engine), the UNET engine and the Linear engine.
+// destruction of the ConvAE engine (plain and trunk mode through the var engine), the UNET engine (with its kernel plan) and the
+// Linear engine.
 // No GPU call is made.
 #include <cstdio>
 #include <cstring>
@@ -32,6 +33,22 @@ static std::vector<cae_layer_spec> dec_layers(int h, int n, int c0, int last_k) 
         s = (s - 1) * 2 + k;
     }
     return v;
+}
+
+// a UNET of k4 s2 p1 layers: encoder in_c -> channels[0] -> ..., decoder back up to out_c with the skip concat
+static void unet_layers(int in_c, int out_c, int size, const std::vector<int>& ch, std::vector<cae_layer_spec>& enc,
+                        std::vector<cae_layer_spec>& dec) {
+    const int n = (int)ch.size();
+    std::vector<int> c{in_c}, s{size};
+    for (int i = 0; i < n; i++) {
+        c.push_back(ch[i]);
+        s.push_back(s.back() / 2);
+        enc.push_back(cae_layer_spec{c[i], s[i], s[i], c[i + 1], s[i + 1], s[i + 1], 4, 4, 2, 1});
+    }
+    for (int j = 0; j < n; j++) {
+        const int src = n - j, dst = n - j - 1;
+        dec.push_back(cae_layer_spec{j == 0 ? c[src] : 2 * c[src], s[src], s[src], j < n - 1 ? c[dst] : out_c, s[dst], s[dst], 4, 4, 2, 1});
+    }
 }
 
 int main() {
@@ -102,6 +119,23 @@ int main() {
             expect(lin_bind(l, dummy, dummy, nullptr, dummy, 1 << 30) != 0, "a null arena is refused");
             lin_engine_destroy(l);
         }
+        // a six-level UNET (64 px down to a 1x1 bottleneck): more repacked layers than one repack launch takes; its kernel plan
+        std::vector<cae_layer_spec> uenc, udec;
+        unet_layers(1, 1, 64, {8, 8, 16, 16, 16, 16}, uenc, udec);
+        unet_engine* u = nullptr;
+        expect(unet_engine_create(uenc.data(), 6, udec.data(), 6, 16, 4, 4, &u) == 0, "unet_engine_create (6 levels)");
+        if (u) {
+            char plan[4096];
+            expect(unet_debug_plan(u, 4, 1, plan, sizeof plan) == 0 && strstr(plan, "pack entries=10 launches=2"), "unet_debug_plan");
+            expect(unet_debug_plan(u, 4, 0, plan, sizeof plan) == 0 && strstr(plan, "dec5 "), "unet_debug_plan (eval)");
+            expect(unet_debug_plan(u, 5, 1, plan, sizeof plan) != 0, "a plan beyond max_batch is refused");
+            expect(unet_debug_plan(u, 4, 1, plan, 16) != 0, "too small a plan buffer is refused");
+            expect(unet_train_step(u, 0, nullptr, 0, 4, 0) != 0, "a step on an unbound UNET engine is refused");
+            unet_engine_destroy(u);
+        }
+        udec[5].out_c = 2;
+        udec[4].out_c = 4;   // a skip concat that does not match
+        expect(unet_engine_create(uenc.data(), 6, udec.data(), 6, 16, 4, 4, &u) != 0, "a broken UNET is refused");
         expect(lin_engine_create(0, 32, 5, &l) != 0 && lin_engine_create(1 << 20, 1 << 20, 5, &l) != 0, "bad Linear sizes are refused");
     }
     printf(failures ? "%d checks failed\n" : "host-side plan checks clean (%d)\n", failures);

@@ -16,7 +16,7 @@ and BatchNorm buffers after the AdamW steps.  Train-mode cases use dropout_rate 
 masks come from torch's global generator and cannot be matched by any other implementation); the dropout > 0
 case stores EVAL-mode results only.
 
-    python tests/golden/make_golden_unet.py
+    python tests/golden/make_golden_unet.py [case ...]
 """
 import ast
 import json
@@ -96,11 +96,20 @@ CASES = {
     # dropout 0.1 model: eval-mode only
     "u_drop_eval_b3": dict(spec=unet_spec(3, 3, (16, 16), [8, 16]), fc=12, latent=5, batch=3, seed=35, mask="b1hw",
                            dropout=0.1, eval_only=True),
+    # six levels down to a 1x1 bottleneck (attention with one hidden unit at every gate): ten layers with repacked weights,
+    # more than one repack launch takes.  Eight channels throughout and compact inputs keep the file small.  (Seed: with
+    # 36, 38 or 39 the reference's own fp32 gradients of a bias in front of an attention gate are 0.5-7 % of the tensor
+    # from the fp64 answer, more than any implementation can be held to; with 37 at most 1e-4)
+    "u_deep6_b4": dict(spec=unet_spec(1, 1, (64, 64), [8, 8, 8, 8, 8, 8]), fc=16, latent=4, batch=4, seed=37,
+                       mask="b1hw", compact=True),
 }
 LR, WD, LAMBDA_P, NSTEPS = 1e-3, 1e-5, 1.0, 3
+# compact cases: inputs and targets on a 1/256 grid (exact in fp32, a quarter of the entropy) and no separate copy of the
+# first batch (x0 / t0 / m0 are step0/x, t, m: tests/unet_helpers.py)
+GRID = 256
 
 
-def make_batch(rng, spec, b, mask_kind):
+def make_batch(rng, spec, b, mask_kind, compact=False):
     (ic, ih, iw) = spec["input_layers"][0]["input_dimensions"]
     (oc, oh, ow) = spec["output_layers"][-1]["output_dimensions"]
     x = rng.random((b, ic, ih, iw), dtype=np.float32)
@@ -110,6 +119,8 @@ def make_batch(rng, spec, b, mask_kind):
         for c in range(oc):
             t[i, c] = 0.5 + 0.4 * np.sin(3 * yy * rng.random() + 2 * xx * rng.random() + rng.random())
     t = (t + 0.05 * rng.standard_normal(t.shape)).clip(0, 1).astype(np.float32)
+    if compact:
+        (x, t) = ((np.round(a * GRID) / GRID).astype(np.float32) for a in (x, t))
     if mask_kind == "ones":
         m = np.ones((b, oc, oh, ow), dtype=np.float32)
     elif mask_kind == "b1hw":
@@ -136,10 +147,12 @@ def run_case(name, cfg):
     state_to_np("init/enc/", enc, out)
     state_to_np("init/dec/", dec, out)
     rng = np.random.default_rng(cfg["seed"])
-    batches = [make_batch(rng, spec_json, cfg["batch"] if i % 2 == 0 else max(cfg["batch"] - 1, 2), cfg["mask"])
+    compact = cfg.get("compact", False)
+    batches = [make_batch(rng, spec_json, cfg["batch"] if i % 2 == 0 else max(cfg["batch"] - 1, 2), cfg["mask"], compact)
                for i in range(NSTEPS)]
     (x0, t0, m0) = (torch.from_numpy(a) for a in batches[0])
-    out["x0"], out["t0"], out["m0"] = batches[0]
+    if not compact:
+        out["x0"], out["t0"], out["m0"] = batches[0]
 
     def forward(x):
         (z, skip) = enc(x)
@@ -197,5 +210,6 @@ def run_case(name, cfg):
 
 
 if __name__ == "__main__":
-    for (name, cfg) in CASES.items():
-        run_case(name, cfg)
+    names = sys.argv[1:] or list(CASES)     # e.g. `make_golden_unet.py u_deep6_b4`: that case alone
+    for name in names:
+        run_case(name, CASES[name])

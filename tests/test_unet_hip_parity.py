@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from unet_helpers import hip_relu_decisions, TRAIN_CASES, UNET_CASES, UnetCase, unet_oracle
+from unet_helpers import DEEP_CASES, MEDIUM_CASES, hip_relu_decisions, TRAIN_CASES, UNET_CASES, UnetCase, unet_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -178,25 +178,21 @@ def test_ragged_epoch_matches_oracle_batch_by_batch():
     np.testing.assert_allclose(np.array(got), np.array(want), rtol=3e-5)
 
 
-@pytest.mark.parametrize("size,chans,fc,latent,B", [(64, [32, 64, 96], 24, 6, 5), (128, [16, 32, 64, 72], 20, 5, 3)],
-                         ids=["64px_32-64-96", "128px_16-32-64-72"])
-def test_mfma_path_at_medium_size_against_oracle_and_generic_kernels(size, chans, fc, latent, B):
-    """wide layers, odd batch, dropout on: the specialised kernels (image-end layers from an LDS patch with the weights in
-    registers, wide layers from a patch with weight tiles, the im2col tile engine for what those do not take, the Linear
-    kernels) against the CPU oracle and the generic kernels.  64 px, 32 / 64 / 96 channels: full tiles, a 64-row tile and a
-    partly filled 128-row tile, maps 32 / 16 / 8 wide.  128 px, 16 / 32 / 64 / 72 channels: maps 64 ... 8 wide, a 16-channel
-    image-end layer, channel counts the patch kernels take (32, 64) next to ones they leave to the tile engine (72)"""
+def _against_oracle_and_generic_kernels(in_c, out_c, size, chans, fc, latent, B):
+    """one training forward + backward (dropout on) and a scoring pass, specialised and generic kernels, against the fp32
+    and fp64 CPU oracles"""
     from cae_tools_amd.models.unet import Decoder, Encoder, unet_layer_spec
     from cae_tools_amd.unet_engine import UnetEngine
     from oracle import unet_oracle as uo
-    spec = unet_layer_spec(3, 3, (size, size), chans)
+    (h, w) = size
+    spec = unet_layer_spec(in_c, out_c, size, chans)
     torch.manual_seed(123)
     enc = Encoder(spec.get_input_layers(), latent, fc)
     dec = Decoder(spec.get_output_layers(), latent, fc)
     g = torch.Generator().manual_seed(9)
-    x = torch.rand((B, 3, size, size), generator=g)
-    t = torch.rand((B, 3, size, size), generator=g)
-    m = (torch.rand((B, 1, size, size), generator=g) < 0.85).float()
+    x = torch.rand((B, in_c, h, w), generator=g)
+    t = torch.rand((B, out_c, h, w), generator=g)
+    m = (torch.rand((B, 1, h, w), generator=g) < 0.85).float()
     to64 = lambda sd: {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
     res = {}
     for specialised in (True, False):
@@ -242,9 +238,32 @@ def test_mfma_path_at_medium_size_against_oracle_and_generic_kernels(size, chans
     np.testing.assert_allclose(res[True][2], o.eval_forward(x).numpy(), rtol=0, atol=2e-5)
 
 
+@pytest.mark.parametrize("size,chans,fc,latent,B", [(c[2][0],) + c[3:] for c in MEDIUM_CASES.values()], ids=list(MEDIUM_CASES))
+def test_mfma_path_at_medium_size_against_oracle_and_generic_kernels(size, chans, fc, latent, B):
+    """wide layers, odd batch, dropout on: the specialised kernels (image-end layers from an LDS patch with the weights in
+    registers, wide layers from a patch with weight tiles, the im2col tile engine for what those do not take, the Linear
+    kernels) against the CPU oracle and the generic kernels.  64 px, 32 / 64 / 96 channels: full tiles, a 64-row tile and a
+    partly filled 128-row tile, maps 32 / 16 / 8 wide.  128 px, 16 / 32 / 64 / 72 channels: maps 64 ... 8 wide, a 16-channel
+    image-end layer, channel counts the patch kernels take (32, 64) next to ones they leave to the tile engine (72)"""
+    _against_oracle_and_generic_kernels(3, 3, (size, size), chans, fc, latent, B)
+
+
+@pytest.mark.parametrize("name", list(DEEP_CASES))
+def test_deep_unets_against_oracle_and_generic_kernels(name):
+    """deeper and wider-spread UNETs than the cases above, the same checks.  5 levels at 256 px: nine layers with repacked
+    weights (two repack launches), the encoder's input gradients on the tile engine and the patch kernels, the thin OpUp at
+    the image end.  6 levels at 64 px down to a 1x1 bottleneck: ten repacked layers, attention with one hidden unit,
+    weight gradients on the tile engine with fp64 atomics and on the generic kernel (maps 2 and 1 wide).  512 px: the tile
+    engine on 256-wide image-end maps, k_up_thin<3> at the output, eight repacked layers (one launch, full).  20x28 with a
+    34-channel 5x7 bottleneck: the Linear tile engine (1190 inputs) and the generic OpUp in specialised mode"""
+    (in_c, out_c, size, chans, fc, latent, B) = DEEP_CASES[name]
+    _against_oracle_and_generic_kernels(in_c, out_c, size, chans, fc, latent, B)
+
+
 def test_benchmark_geometry_full_size_against_oracle():
-    """BASELINE cfg3 layers (3x256x256, channels 32/64/128/256, fc128/latent32) at batch 5: every MFMA tile shape, the
-    split-K paths, the thin-layer kernels and the 65536-wide Linear layers at their real sizes against the CPU oracle
+    """BASELINE cfg3 layers (3x256x256, channels 32/64/128/256, fc128/latent32) at batch 5: the patch kernels on every wide
+    layer, their split-K weight gradients, the thin-layer kernels and the 65536-wide Linear layers at their real sizes against
+    the CPU oracle (the im2col tile engine takes none of these layers: tests/test_unet_plan_cpu.py)
     (not batch 2: BatchNorm1d over two samples maps every feature to +-1 and amplifies fp32 rounding without bound)"""
     from cae_tools_amd.models.unet import Decoder, Encoder, unet_layer_spec
     from cae_tools_amd.unet_engine import UnetEngine

@@ -11,13 +11,36 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 UNET_CASES = sorted(os.path.basename(p)[5:-5] for p in glob.glob(os.path.join(GOLDEN, "unet_*.json")))
 TRAIN_CASES = [c for c in UNET_CASES if "eval" not in c]
 
+# the UNET geometries tests/test_unet_hip_parity.py runs against the oracle and the generic kernels, beside the golden
+# cases; tests/test_unet_plan_cpu.py checks which kernel families each reaches.  id -> (in_ch, out_ch, (h, w), channels,
+# fc, latent, batch)
+MEDIUM_CASES = {
+    "64px_32-64-96": (3, 3, (64, 64), [32, 64, 96], 24, 6, 5),
+    "128px_16-32-64-72": (3, 3, (128, 128), [16, 32, 64, 72], 20, 5, 3),
+}
+DEEP_CASES = {
+    # five levels: nine layers with repacked weights (two repack launches)
+    "5lvl_256px_16-256": (3, 3, (256, 256), [16, 32, 64, 128, 256], 24, 6, 4),
+    # six levels to a 1x1 bottleneck: attention with one hidden unit, BatchNorm over the batch alone at the bottom, ten
+    # repacked layers
+    "6lvl_64px_1x1": (1, 1, (64, 64), [8, 8, 16, 16, 16, 16], 16, 4, 6),
+    # 512 px: 256-wide image-end maps (too wide for the thin kernels), eight repacked layers (one launch, exactly full)
+    "512px_8-8-16-16-32": (3, 3, (512, 512), [8, 8, 16, 16, 32], 20, 5, 3),
+    # a 5x7 bottleneck of 34 channels: Linear layers of 1190 inputs (not a multiple of 4: the Linear tile engine), 34-channel
+    # layers the tile engine's OpUp does not take (no repacked weights: the generic transposed convolution)
+    "20x28_34ch": (2, 2, (20, 28), [16, 34], 12, 5, 5),
+}
+
 
 class UnetCase:
 
     def __init__(self, name):
         with open(os.path.join(GOLDEN, f"unet_{name}.json")) as f:
             self.meta = json.load(f)
-        self.z = np.load(os.path.join(GOLDEN, f"unet_{name}.npz"))
+        self.z = dict(np.load(os.path.join(GOLDEN, f"unet_{name}.npz")))
+        if "x0" not in self.z:   # compact cases (make_golden_unet.py) store the first batch once, as step 0's
+            for (k, src) in (("x0", "step0/x"), ("t0", "step0/t"), ("m0", "step0/m")):
+                self.z[k] = self.z[src]
         self.name = name
 
     def state(self, prefix, which):
