@@ -338,22 +338,62 @@ bool s2_shape_ok(const ConvLayer& L) {
 
 bool s2_eligible(const cae_engine* e, const ConvLayer& L) { return e->use_s2 && L.sh_w >= 0 && s2_shape_ok(L); }
 
+// ---- kernel choice of the decoder's conv-transposes ---------------------------------------------------------------------
+// The choosers below (choose_s2_fwd / choose_s2_bwd / choose_rows_* / choose_last here, choose_dec_fwd / choose_dec_bwd after
+// the fused head and tail) are the whole decision: the launch code switches on what they return and cae_debug_plan reports it.
+
+// k_s2_fwd family.  tw: the tile width template argument.
+enum S2FwdK {
+    S2F_CS,     // small maps, many weights: k_s2_fwd_cs (output channels split over the waves)
+    S2F_QUAD,   // small maps: k_s2_fwd (one quad per thread)
+    S2F_WIDE    // k_s2_fwd2 (2x2 quads per thread)
+};
+struct S2FwdPick { S2FwdK k; int tw; };
+
+S2FwdPick choose_s2_fwd(const ConvLayer& L, int B, int epi) {
+    static const int cs_on = env_int("CAE_S2_CS", 1);   // env: A/B measurements only
+    // each thread of k_s2_fwd2 covers 2x2 quads; lanes run along the row
+    const int px = ((L.wout + 1) / 2 + 1) / 2, py = ((L.hout + 1) / 2 + 1) / 2;   // thread columns / rows per image
+    if ((long long)B * px * py < 100000) {
+        // small maps: 4x4 outputs per thread would leave most SIMDs without a wave; one quad per thread
+        const int qx = (L.wout + 1) / 2;
+        const int tw = qx > 32 ? 64 : 32;
+        // intermediate layers with many weights: output channels split over the waves
+        if (L.cin * L.cout * L.kh * L.kw > 80 && (256 / L.cout) % 64 == 0 && cs_on && (epi == S2_RAW_STATS || epi == S2_RAW))
+            return {S2F_CS, tw};
+        return {S2F_QUAD, tw};
+    }
+    return {S2F_WIDE, px > 32 ? 64 : (px > 16 ? 32 : 16)};
+}
+
+// k_s2_bwd family.  tw: tile width (k_s2_bwd2); ct: input channels per thread (k_s2_bwd_split, k_s2_bwd).
+enum S2BwdK {
+    S2B_DIRECT,   // at most 72 weights: k_s2_bwd2 (one input pixel per thread, no LDS staging)
+    S2B_SPLIT,    // 8 input channels, at most 72 weights per wave: k_s2_bwd_split (channels split over the 4 waves)
+    S2B_GENERAL   // k_s2_bwd
+};
+struct S2BwdPick { S2BwdK k; int tw, ct; };
+
+S2BwdPick choose_s2_bwd(const ConvLayer& L) {
+    const int nw = L.cin * L.cout * L.kh * L.kw;
+    if (nw <= 72) return {S2B_DIRECT, L.win > 32 ? 64 : 32, 0};
+    if (L.cin == 8 && nw / 4 <= 72) return {S2B_SPLIT, 32, 2};
+    return {S2B_GENERAL, 32, (L.cin % 2 == 0 && L.cin != 6) ? 2 : 3};
+}
+
+// false: this instantiation has no kernel for the pick (the chooser and the `if constexpr` guards below disagree)
 template <int CIN, int COUT, int KH, int KW>
-void s2_fwd_launch(S2Fwd a, hipStream_t s) {
+bool s2_fwd_launch(S2Fwd a, S2FwdPick p, hipStream_t s) {
     // grid caps measured on MI355X at batch 64 (workgroups walk the remaining tiles): more workgroups
     // only add fp64-atomic traffic at the end of the kernel
     static const int capf = env_int("CAE_CAP_F", 1024), capf2 = env_int("CAE_CAP_F2", 512);   // env: tuning only
-    // each thread covers 2x2 quads; lanes run along the row
-    const int px = ((a.OW + 1) / 2 + 1) / 2, py = ((a.OH + 1) / 2 + 1) / 2;   // thread columns / rows per image
-    if ((long long)a.B * px * py < 100000) {
-        // small maps: 4x4 outputs per thread would leave most SIMDs without a wave; one quad per thread
-        const int qx = (a.OW + 1) / 2, qy = (a.OH + 1) / 2;
-        if constexpr (CIN * COUT * KH * KW > 80 && (256 / COUT) % 64 == 0) {
-            // intermediate layers with many weights: output channels split over the waves (k_s2_fwd_cs)
-            static const int cs_on = env_int("CAE_S2_CS", 1);   // env: A/B measurements only
-            if (cs_on && (a.epi == S2_RAW_STATS || a.epi == S2_RAW)) {
+    const int px = ((a.OW + 1) / 2 + 1) / 2, py = ((a.OH + 1) / 2 + 1) / 2;   // thread columns / rows per image (k_s2_fwd2)
+    const int qx = (a.OW + 1) / 2, qy = (a.OH + 1) / 2;                       // quad columns / rows (k_s2_fwd, k_s2_fwd_cs)
+    switch (p.k) {
+        case S2F_CS:
+            if constexpr (CIN * COUT * KH * KW > 80 && (256 / COUT) % 64 == 0) {
                 constexpr int PIX = 256 / COUT;
-                if (qx > 32) {
+                if (p.tw == 64) {
                     a.tiles_x = (qx + 63) / 64;
                     a.tiles_y = (qy + PIX / 64 - 1) / (PIX / 64);
                     a.total_tiles = a.B * a.tiles_x * a.tiles_y;
@@ -364,93 +404,115 @@ void s2_fwd_launch(S2Fwd a, hipStream_t s) {
                     a.total_tiles = a.B * a.tiles_x * a.tiles_y;
                     hipLaunchKernelGGL((k_s2_fwd_cs<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < capf ? a.total_tiles : capf), dim3(256), 0, s, a);
                 }
-                return;
+                return true;
             }
-        }
-        if (qx > 32) {
-            a.tiles_x = (qx + 63) / 64;
-            a.tiles_y = (qy + 3) / 4;
-            a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-            hipLaunchKernelGGL((k_s2_fwd<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < capf ? a.total_tiles : capf), dim3(256), 0, s, a);
-        } else {
-            a.tiles_x = (qx + 31) / 32;
-            a.tiles_y = (qy + 7) / 8;
-            a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-            hipLaunchKernelGGL((k_s2_fwd<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < capf ? a.total_tiles : capf), dim3(256), 0, s, a);
-        }
-        return;
+            return false;
+        case S2F_QUAD:
+            if (p.tw == 64) {
+                a.tiles_x = (qx + 63) / 64;
+                a.tiles_y = (qy + 3) / 4;
+                a.total_tiles = a.B * a.tiles_x * a.tiles_y;
+                hipLaunchKernelGGL((k_s2_fwd<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < capf ? a.total_tiles : capf), dim3(256), 0, s, a);
+            } else {
+                a.tiles_x = (qx + 31) / 32;
+                a.tiles_y = (qy + 7) / 8;
+                a.total_tiles = a.B * a.tiles_x * a.tiles_y;
+                hipLaunchKernelGGL((k_s2_fwd<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < capf ? a.total_tiles : capf), dim3(256), 0, s, a);
+            }
+            return true;
+        case S2F_WIDE:
+            if (p.tw == 64) {
+                a.tiles_x = (px + 63) / 64;
+                a.tiles_y = (py + 3) / 4;
+                a.total_tiles = a.B * a.tiles_x * a.tiles_y;
+                hipLaunchKernelGGL((k_s2_fwd2<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < capf2 ? a.total_tiles : capf2), dim3(256), 0, s, a);
+            } else if (p.tw == 32) {
+                a.tiles_x = (px + 31) / 32;
+                a.tiles_y = (py + 7) / 8;
+                a.total_tiles = a.B * a.tiles_x * a.tiles_y;
+                hipLaunchKernelGGL((k_s2_fwd2<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < capf2 ? a.total_tiles : capf2), dim3(256), 0, s, a);
+            } else {
+                a.tiles_x = (px + 15) / 16;
+                a.tiles_y = (py + 15) / 16;
+                a.total_tiles = a.B * a.tiles_x * a.tiles_y;
+                hipLaunchKernelGGL((k_s2_fwd2<CIN, COUT, KH, KW, 16>), dim3(a.total_tiles < capf2 ? a.total_tiles : capf2), dim3(256), 0, s, a);
+            }
+            return true;
     }
-    if (px > 32) {
-        a.tiles_x = (px + 63) / 64;
-        a.tiles_y = (py + 3) / 4;
-        a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-        hipLaunchKernelGGL((k_s2_fwd2<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < capf2 ? a.total_tiles : capf2), dim3(256), 0, s, a);
-    } else if (px > 16) {
-        a.tiles_x = (px + 31) / 32;
-        a.tiles_y = (py + 7) / 8;
-        a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-        hipLaunchKernelGGL((k_s2_fwd2<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < capf2 ? a.total_tiles : capf2), dim3(256), 0, s, a);
-    } else {
-        a.tiles_x = (px + 15) / 16;
-        a.tiles_y = (py + 15) / 16;
-        a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-        hipLaunchKernelGGL((k_s2_fwd2<CIN, COUT, KH, KW, 16>), dim3(a.total_tiles < capf2 ? a.total_tiles : capf2), dim3(256), 0, s, a);
-    }
+    return false;
 }
 
-void s2_fwd_dispatch(const ConvLayer& L, const S2Fwd& a, hipStream_t s) {
+// false: nothing launched (a shape outside S2_SHAPES x S2_KERNELS, or a pick the shape has no kernel for)
+bool s2_fwd_dispatch(const ConvLayer& L, const S2Fwd& a, hipStream_t s) {
+    const S2FwdPick p = choose_s2_fwd(L, a.B, a.epi);
 #define ONE(CI, CO, KH_, KW_) \
-    if (L.cin == CI && L.cout == CO && L.kh == KH_ && L.kw == KW_) return s2_fwd_launch<CI, CO, KH_, KW_>(a, s);
+    if (L.cin == CI && L.cout == CO && L.kh == KH_ && L.kw == KW_) return s2_fwd_launch<CI, CO, KH_, KW_>(a, p, s);
 #define PAIR(CI, CO) S2_KERNELS(ONE, CI, CO)
     S2_SHAPES(PAIR)
 #undef PAIR
 #undef ONE
+    return false;
 }
 
 template <int CIN, int COUT, int KH, int KW>
-void s2_bwd_launch(S2Bwd a, hipStream_t s) {
+bool s2_bwd_launch(S2Bwd a, S2BwdPick p, hipStream_t s) {   // false: as s2_fwd_launch
     // 512 workgroups: each ends with Cin*Cout*kh*kw + 2*Cin fp64 atomics, and those dominate beyond that
     // (measured per step at batch 64: 1536 -> 286 us, 512 -> 274 us)
     static const int cap2 = env_int("CAE_CAP_B2", 512), caps = env_int("CAE_CAP_BS", 512);
-    if constexpr (CIN * COUT * KH * KW <= 72) {
-        // direct variant: one input pixel per thread, no LDS staging
-        if (a.W > 32) {
-            a.tiles_x = (a.W + 63) / 64;
-            a.tiles_y = (a.H + 3) / 4;
-            a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-            hipLaunchKernelGGL((k_s2_bwd2<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < cap2 ? a.total_tiles : cap2), dim3(256), 0, s, a);
-        } else {
-            a.tiles_x = (a.W + 31) / 32;
-            a.tiles_y = (a.H + 7) / 8;
-            a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-            hipLaunchKernelGGL((k_s2_bwd2<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < cap2 ? a.total_tiles : cap2), dim3(256), 0, s, a);
-        }
-    } else if constexpr (CIN == 8 && CIN * COUT * KH * KW / 4 <= 72) {
-        // channels split over the 4 waves: 2 per thread, 64 pixels (32 x 2) per workgroup pass
-        a.tiles_x = (a.W + 31) / 32;
-        a.tiles_y = (a.H + 1) / 2;
-        a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-        hipLaunchKernelGGL((k_s2_bwd_split<CIN, 2, COUT, KH, KW, 32>), dim3(a.total_tiles < caps ? a.total_tiles : caps), dim3(256), 0, s, a);
-    } else {
-        constexpr int CT = (CIN % 2 == 0 && CIN != 6) ? 2 : 3;   // input channels per thread
-        constexpr int CG = CIN / CT;                              // ci-groups per workgroup
-        constexpr int PIX = 256 / CG;                             // pixels per tile
-        constexpr int TPX = 32, TPY = PIX / 32;
-        a.tiles_x = (a.W + TPX - 1) / TPX;
-        a.tiles_y = (a.H + TPY - 1) / TPY;
-        a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-        const int grid = a.total_tiles < 1024 ? a.total_tiles : 1024;
-        hipLaunchKernelGGL((k_s2_bwd<CIN, CT, COUT, KH, KW, TPX, TPY>), dim3(grid), dim3(256), 0, s, a);
+    switch (p.k) {
+        case S2B_DIRECT:
+            if constexpr (CIN * COUT * KH * KW <= 72) {
+                if (p.tw == 64) {
+                    a.tiles_x = (a.W + 63) / 64;
+                    a.tiles_y = (a.H + 3) / 4;
+                    a.total_tiles = a.B * a.tiles_x * a.tiles_y;
+                    hipLaunchKernelGGL((k_s2_bwd2<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < cap2 ? a.total_tiles : cap2), dim3(256), 0, s, a);
+                } else {
+                    a.tiles_x = (a.W + 31) / 32;
+                    a.tiles_y = (a.H + 7) / 8;
+                    a.total_tiles = a.B * a.tiles_x * a.tiles_y;
+                    hipLaunchKernelGGL((k_s2_bwd2<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < cap2 ? a.total_tiles : cap2), dim3(256), 0, s, a);
+                }
+                return true;
+            }
+            return false;
+        case S2B_SPLIT:
+            if constexpr (CIN * COUT * KH * KW > 72 && CIN == 8 && CIN * COUT * KH * KW / 4 <= 72) {
+                // 2 channels per thread, 64 pixels (32 x 2) per workgroup pass
+                a.tiles_x = (a.W + 31) / 32;
+                a.tiles_y = (a.H + 1) / 2;
+                a.total_tiles = a.B * a.tiles_x * a.tiles_y;
+                hipLaunchKernelGGL((k_s2_bwd_split<CIN, 2, COUT, KH, KW, 32>), dim3(a.total_tiles < caps ? a.total_tiles : caps), dim3(256), 0, s, a);
+                return true;
+            }
+            return false;
+        case S2B_GENERAL:
+            if constexpr (CIN * COUT * KH * KW > 72 && !(CIN == 8 && CIN * COUT * KH * KW / 4 <= 72)) {
+                constexpr int CT = (CIN % 2 == 0 && CIN != 6) ? 2 : 3;   // input channels per thread
+                constexpr int CG = CIN / CT;                              // ci-groups per workgroup
+                constexpr int PIX = 256 / CG;                             // pixels per tile
+                constexpr int TPX = 32, TPY = PIX / 32;
+                a.tiles_x = (a.W + TPX - 1) / TPX;
+                a.tiles_y = (a.H + TPY - 1) / TPY;
+                a.total_tiles = a.B * a.tiles_x * a.tiles_y;
+                const int grid = a.total_tiles < 1024 ? a.total_tiles : 1024;
+                hipLaunchKernelGGL((k_s2_bwd<CIN, CT, COUT, KH, KW, TPX, TPY>), dim3(grid), dim3(256), 0, s, a);
+                return true;
+            }
+            return false;
     }
+    return false;
 }
 
-void s2_bwd_dispatch(const ConvLayer& L, const S2Bwd& a, hipStream_t s) {
+bool s2_bwd_dispatch(const ConvLayer& L, const S2Bwd& a, hipStream_t s) {   // false: as s2_fwd_dispatch
+    const S2BwdPick p = choose_s2_bwd(L);
 #define ONE(CI, CO, KH_, KW_) \
-    if (L.cin == CI && L.cout == CO && L.kh == KH_ && L.kw == KW_) return s2_bwd_launch<CI, CO, KH_, KW_>(a, s);
+    if (L.cin == CI && L.cout == CO && L.kh == KH_ && L.kw == KW_) return s2_bwd_launch<CI, CO, KH_, KW_>(a, p, s);
 #define PAIR(CI, CO) S2_KERNELS(ONE, CI, CO)
     S2_SHAPES(PAIR)
 #undef PAIR
 #undef ONE
+    return false;
 }
 
 // ---- row-streaming backward of the thin middle layers (kernels_rows.h) ---------------------------------------------------
@@ -476,18 +538,35 @@ bool rows_bwd_ok(const cae_engine* e, const ConvLayer& L) {
     return (L.cin == 4 && L.cout == 2) || (L.cin == 8 && L.cout == 4);
 }
 
-void rows_bwd_launch(const ConvLayer& L, S2Rows a, hipStream_t s) {
+// the variant of the row-streaming kernels: quad rows per band (HB), load depth (D, backward), lane width of an image (32: two
+// images per wave, 64: one)
+struct RowsPick { int hb, d, lw; };
+
+int rows_lw(const ConvLayer& L) { return (L.wout + 1) / 2 <= 32 ? 32 : 64; }
+
+RowsPick choose_rows_bwd(const ConvLayer& L) {
     static const int hb42 = env_int("CAE_ROWS_HB42", 2), hb84 = env_int("CAE_ROWS_HB84", 4);   // env: tuning only
-    a.QH = (L.hout + 1) / 2;
-    const int lw = (L.wout + 1) / 2 <= 32 ? 32 : 64;
     // short bands with every row's loads issued up front (a wave pays the memory latency once) against tall bands that load one
     // row ahead (less re-reading at the band edges, but a round trip per row: a wave is alone on its SIMD)
+    const bool tall = L.cin == 4 ? hb42 == 4 : hb84 == 4;
+    return tall ? RowsPick{4, 1, rows_lw(L)} : RowsPick{2, 3, rows_lw(L)};
+}
+
+RowsPick choose_rows_fwd(const ConvLayer& L) {
+    static const int hb42 = env_int("CAE_ROWS_FHB42", 2), hb84 = env_int("CAE_ROWS_FHB84", 1);   // env: tuning only
+    if (L.cin == 4) return RowsPick{hb42 == 4 ? 4 : 2, 0, rows_lw(L)};
+    return RowsPick{hb84 == 2 ? 2 : 1, 0, rows_lw(L)};
+}
+
+void rows_bwd_launch(const ConvLayer& L, S2Rows a, hipStream_t s) {
+    const RowsPick p = choose_rows_bwd(L);
+    a.QH = (L.hout + 1) / 2;
     if (L.cin == 4) {
-        if (hb42 == 4) rows_go<4, 4, 2, 4, 1>(a, lw, s);
-        else rows_go<4, 4, 2, 2, 3>(a, lw, s);
+        if (p.hb == 4) rows_go<4, 4, 2, 4, 1>(a, p.lw, s);
+        else rows_go<4, 4, 2, 2, 3>(a, p.lw, s);
     } else {
-        if (hb84 == 4) rows_go<8, 2, 4, 4, 1>(a, lw, s);
-        else rows_go<8, 2, 4, 2, 3>(a, lw, s);
+        if (p.hb == 4) rows_go<8, 2, 4, 4, 1>(a, p.lw, s);
+        else rows_go<8, 2, 4, 2, 3>(a, p.lw, s);
     }
 }
 
@@ -503,15 +582,14 @@ void rows_fwd_go(S2FwdRows a, int lw, hipStream_t s) {
 }
 
 void rows_fwd_launch(const ConvLayer& L, S2FwdRows a, hipStream_t s) {
-    static const int hb42 = env_int("CAE_ROWS_FHB42", 2), hb84 = env_int("CAE_ROWS_FHB84", 1);   // env: tuning only
+    const RowsPick p = choose_rows_fwd(L);
     a.QH = (L.hout + 1) / 2;
-    const int lw = (L.wout + 1) / 2 <= 32 ? 32 : 64;
     if (L.cin == 4) {
-        if (hb42 == 4) rows_fwd_go<4, 2, 4>(a, lw, s);
-        else rows_fwd_go<4, 2, 2>(a, lw, s);
+        if (p.hb == 4) rows_fwd_go<4, 2, 4>(a, p.lw, s);
+        else rows_fwd_go<4, 2, 2>(a, p.lw, s);
     } else {
-        if (hb84 == 2) rows_fwd_go<8, 4, 2>(a, lw, s);
-        else rows_fwd_go<8, 4, 1>(a, lw, s);
+        if (p.hb == 2) rows_fwd_go<8, 4, 2>(a, p.lw, s);
+        else rows_fwd_go<8, 4, 1>(a, p.lw, s);
     }
 }
 
@@ -521,43 +599,60 @@ bool last_fused_ok(const cae_engine* e, const ConvLayer& L) {
     return enabled && s2_eligible(e, L) && L.cin * L.cout * L.kh * L.kw <= 72 && L.sh_b >= 0;
 }
 
+// the variant of k_s2_last_fused: quad rows per band (HB), 16-byte target loads (one strip, width a multiple of 4), BatchNorm on
+// its input (a producer with BatchNorm)
+struct LastPick { int hb; bool vec4, bn; };
+
+int last_strips(const ConvLayer& L) {
+    const int qw = (L.wout + 1) / 2;
+    const int wmax = L.win > qw - 1 ? L.win : qw - 1;
+    return (wmax + kLastStripPx - 1) / kLastStripPx;
+}
+
+LastPick choose_last(const ConvLayer& L, bool bn_in) {
+    static const int hb_env = env_int("CAE_LAST_HB", 0);   // env: tuning only
+    // a wave walks a band of HB quad rows (+1 recomputed): taller bands recompute less, shorter ones give more waves
+    // (measured at the benchmark geometry: 2048 waves of 4+1 rows, two per SIMD, beat 1024 of 8+1: 20.4 against 21.8 us;
+    // and at batch 128 / 512, where 8+1 rows used to be chosen: 244.2 against 246.8 and 601.6 against 607.6 us per step -
+    // the 8-row variant's register arrays end up in scratch)
+    int hb = hb_env ? hb_env : 4;
+    if (hb != 8) hb = 4;
+    return LastPick{hb, last_strips(L) == 1 && (L.wout & 3) == 0, bn_in};
+}
+
 template <int CIN, int COUT, int KH, int KW, int HB>
-void last_fused_go(const S2Last& a, hipStream_t s) {
+void last_fused_go(const S2Last& a, LastPick p, hipStream_t s) {
     const dim3 grid((a.total + 3) / 4);
-    const bool vec4 = a.strips == 1 && (a.OW & 3) == 0, bn = a.bn_in.mode != BN_NONE;
-    if (vec4 && bn) hipLaunchKernelGGL((k_s2_last_fused<CIN, COUT, KH, KW, HB, true, true>), grid, dim3(256), 0, s, a);
-    else if (bn) hipLaunchKernelGGL((k_s2_last_fused<CIN, COUT, KH, KW, HB, false, true>), grid, dim3(256), 0, s, a);
+    if (p.vec4 && p.bn) hipLaunchKernelGGL((k_s2_last_fused<CIN, COUT, KH, KW, HB, true, true>), grid, dim3(256), 0, s, a);
+    else if (p.bn) hipLaunchKernelGGL((k_s2_last_fused<CIN, COUT, KH, KW, HB, false, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_s2_last_fused<CIN, COUT, KH, KW, HB, false, false>), grid, dim3(256), 0, s, a);
 }
 
 template <int CIN, int COUT, int KH, int KW>
-void last_fused_launch(S2Last a, hipStream_t s) {
+bool last_fused_launch(S2Last a, LastPick p, hipStream_t s) {   // false: as s2_fwd_launch
     if constexpr (CIN * COUT * KH * KW <= 72) {
-        static const int hb_env = env_int("CAE_LAST_HB", 0);   // env: tuning only
         a.QH = (a.OH + 1) / 2;
         a.QW = (a.OW + 1) / 2;
         const int wmax = a.W > a.QW - 1 ? a.W : a.QW - 1, hmax = a.H > a.QH - 1 ? a.H : a.QH - 1;
-        a.strips = (wmax + kLastStripPx - 1) / kLastStripPx;
-        // a wave walks a band of HB quad rows (+1 recomputed): taller bands recompute less, shorter ones give more waves
-        // (measured at the benchmark geometry: 2048 waves of 4+1 rows, two per SIMD, beat 1024 of 8+1: 20.4 against 21.8 us;
-        // and at batch 128 / 512, where 8+1 rows used to be chosen: 244.2 against 246.8 and 601.6 against 607.6 us per step -
-        // the 8-row variant's register arrays end up in scratch)
-        int hb = hb_env ? hb_env : 4;
-        if (hb != 8) hb = 4;
-        a.bands = (hmax + hb - 1) / hb;
+        a.strips = (wmax + kLastStripPx - 1) / kLastStripPx;   // = last_strips(L)
+        a.bands = (hmax + p.hb - 1) / p.hb;
         a.total = a.B * a.strips * a.bands;
-        if (hb == 8) last_fused_go<CIN, COUT, KH, KW, 8>(a, s);
-        else last_fused_go<CIN, COUT, KH, KW, 4>(a, s);
+        if (p.hb == 8) last_fused_go<CIN, COUT, KH, KW, 8>(a, p, s);
+        else last_fused_go<CIN, COUT, KH, KW, 4>(a, p, s);
+        return true;
     }
+    return false;
 }
 
-void last_fused_dispatch(const ConvLayer& L, const S2Last& a, hipStream_t s) {
+bool last_fused_dispatch(const ConvLayer& L, const S2Last& a, hipStream_t s) {   // false: as s2_fwd_dispatch
+    const LastPick p = choose_last(L, a.bn_in.mode != BN_NONE);
 #define ONE(CI, CO, KH_, KW_) \
-    if (L.cin == CI && L.cout == CO && L.kh == KH_ && L.kw == KW_) return last_fused_launch<CI, CO, KH_, KW_>(a, s);
+    if (L.cin == CI && L.cout == CO && L.kh == KH_ && L.kw == KW_) return last_fused_launch<CI, CO, KH_, KW_>(a, p, s);
 #define PAIR(CI, CO) S2_KERNELS(ONE, CI, CO)
     S2_SHAPES(PAIR)
 #undef PAIR
 #undef ONE
+    return false;
 }
 
 template <class K>
@@ -570,16 +665,16 @@ void head_lds_attr(K kernel, size_t bytes) {
 }
 
 // ---- LDS-staged implicit-GEMM forward of a channel-rich stride-2 ConvTranspose2d (kernels_ctlds.h) ---------------------
-// false: the layer does not fit this kernel (odd channel counts, kernels other than 3/4 taps, an image + weight slice
-// larger than LDS); the caller then runs the gather kernel k_ig_fwd_s2.
+// ct_fwd_plan false: the layer does not fit this kernel (odd channel counts, kernels other than 3/4 taps, an image + weight
+// slice larger than LDS); the layer then runs the gather kernel k_ig_fwd_s2.
 template <int KH, int KW>
 void ct_fwd_go(const CtFwd& c, dim3 grid, int threads, size_t lds, hipStream_t s) {
     head_lds_attr(k_ct_fwd_lds<KH, KW>, lds);
     hipLaunchKernelGGL((k_ct_fwd_lds<KH, KW>), grid, dim3(threads), lds, s, c);
 }
 
-bool ct_fwd_launch(cae_engine* e, const StepArgs& a, const ConvLayer& L, int layer, const float* in, const BnDesc& bn_in,
-                   float* out, double* stats) {
+// Fills c's geometry and split; false: the layer does not fit (see above).
+bool ct_fwd_plan(const cae_engine* e, int batch, const ConvLayer& L, int layer, CtFwd& c, int& waves, size_t& lds) {
     static const int enabled = env_int("CAE_CTLDS", -1);       // env: A/B measurements only - layer mask (-1: by batch size, below)
     static const int mf_target = env_int("CAE_CT_MF", 24);     // env: tuning only - MFMAs per wave before K is split further
     // Against the gather kernel it replaces (k_ig_fwd_s2) the LDS-staged one has a third of the instructions and wins from
@@ -589,9 +684,8 @@ bool ct_fwd_launch(cae_engine* e, const StepArgs& a, const ConvLayer& L, int lay
     // forward's sit within the full-size test's 2e-4 (test_full_size_gpu.py): parity first, the LDS-staged kernels run.
     const int mask = e->gather_fwd ? 0 : (enabled >= 0 ? enabled : 0x7fffffff);
     if (!(layer < 31 && ((mask >> layer) & 1)) || L.cin % 4 || L.kh < 3 || L.kw < 3) return false;
-    CtFwd c;
     memset(&c, 0, sizeof c);
-    c.B = a.batch; c.Cin = L.cin; c.H = L.hin; c.W = L.win; c.Cout = L.cout; c.OH = L.hout; c.OW = L.wout;
+    c.B = batch; c.Cin = L.cin; c.H = L.hin; c.W = L.win; c.Cout = L.cout; c.OH = L.hout; c.OW = L.wout;
     c.QH = (L.hout + 1) / 2; c.QW = (L.wout + 1) / 2;
     c.PW = c.QW + 1;
     c.plane = ((c.QH + 1) * c.PW) | 1;
@@ -605,9 +699,18 @@ bool ct_fwd_launch(cae_engine* e, const StepArgs& a, const ConvLayer& L, int lay
     if (rt > 4) rt = 4;
     c.ks = ks; c.rt = rt;
     c.tg = (c.tiles + rt - 1) / rt;
-    const int waves = rt * ks;
-    const size_t lds = ct_fwd_lds_bytes(L.cin, c.plane, L.kh, L.kw, waves, ks);
-    if (lds > 150 * 1024 || c.plane >= kDivSmallMaxD || (long long)L.cin * c.plane >= kDivSmallMaxN) return false;
+    waves = rt * ks;
+    lds = ct_fwd_lds_bytes(L.cin, c.plane, L.kh, L.kw, waves, ks);
+    return !(lds > 150 * 1024 || c.plane >= kDivSmallMaxD || (long long)L.cin * c.plane >= kDivSmallMaxN);
+}
+
+// the layer's forward on k_ct_fwd_lds: only where ct_fwd_plan holds (choose_dec_fwd)
+void ct_fwd_launch(cae_engine* e, const StepArgs& a, const ConvLayer& L, int layer, const float* in, const BnDesc& bn_in,
+                   float* out, double* stats) {
+    CtFwd c;
+    int waves = 0;
+    size_t lds = 0;
+    (void)ct_fwd_plan(e, a.batch, L, layer, c, waves, lds);
     c.in = in; c.bn_in = bn_in; c.w = e->params + L.w_off; c.bias = e->params + L.b_off; c.out = out; c.stats = stats;
     {
         static const int dbg = env_int("CAE_HEAD_DBG", 0), dbg_layer = env_int("CAE_DBG_LAYER", 2);   // tools/ct_phases.py
@@ -619,7 +722,26 @@ bool ct_fwd_launch(cae_engine* e, const StepArgs& a, const ConvLayer& L, int lay
     else if (L.kh == 4 && L.kw == 4) ct_fwd_go<4, 4>(c, grid, 64 * waves, lds, e->stream);
     else if (L.kh == 3 && L.kw == 4) ct_fwd_go<3, 4>(c, grid, 64 * waves, lds, e->stream);
     else ct_fwd_go<4, 3>(c, grid, 64 * waves, lds, e->stream);
-    return true;
+}
+
+// ---- LDS-staged backward of a channel-rich stride-2 ConvTranspose2d (kernels_ctbwd.h, the kernel in ctbwd.hip) -----------
+// The layers of cae_set_kernel_mode's mask with 3x3 kernels at stride 2, whole 16-channel blocks, images that fit the staging
+// registers / LDS, and few enough images per accumulator address.  False: the gather pair k_ig_bwd_pair.
+struct CtBwdPlan { int imgs, groups, wstr; size_t lds; };
+
+bool ct_bwd_plan(const cae_engine* e, int B, const ConvLayer& L, int l, CtBwdPlan& p) {
+    if (!(l < 31 && ((e->ctbwd_mask >> l) & 1) && L.kh == 3 && L.kw == 3 && L.stride == 2 && L.cin % 16 == 0 && L.cout % 4 == 0 &&
+          L.hout >= 2 * L.hin + 1 && L.wout >= 2 * L.win + 1))
+        return false;
+    const int HW = L.hin * L.win, OHW = L.hout * L.wout, N = L.cout * 9;
+    const int budget = std::min((4 * kCtbG4 * kCtbThreads) / (L.cout * OHW), (4 * kCtbA4 * kCtbThreads) / (16 * HW));
+    int imgs = (int)(((int64_t)L.cin * N * B + 149999) / 150000);
+    imgs = std::max(1, std::min(std::min(imgs, budget), B));
+    p.imgs = imgs;
+    p.groups = (B + imgs - 1) / imgs;
+    p.wstr = N | 1;
+    p.lds = ct_bwd_lds_bytes(L.cin, L.cout, imgs, HW, OHW, p.wstr);
+    return budget >= 1 && 16 * N <= 4 * kCtbW4 * kCtbThreads && p.lds <= 152 * 1024 && (int64_t)L.cin * N * p.groups <= 400000;
 }
 
 // ---- fused head / tail (kernels_head.h) ----------------------------------------------------------
@@ -820,6 +942,63 @@ bool tail_plan(const cae_engine* e, const StepArgs& a, TailArgs& t, size_t& lds_
     // weight-gradient shares: M = nout, N = nin + 1, K = 16 rows
     for (int i = 0; i < 3; i++) t.sp_w[i] = stage_split(((e->fc[2 - i].nout + 15) / 16) * ((e->fc[2 - i].nin + 16) / 16), 16);
     return true;
+}
+
+// ---- kernel choice of a decoder layer (see choose_s2_fwd above) ---------------------------------------------------------
+enum DecFwdK {
+    DF_FUSED_LAST,   // training step's last layer: nothing here, k_s2_last_fused runs forward, loss and backward in launch_backward
+    DF_ROWS,         // k_s2_fwd_rows
+    DF_S2,           // the k_s2_fwd family (choose_s2_fwd)
+    DF_CT_LDS,       // k_ct_fwd_lds
+    DF_IG,           // k_ig_fwd_s2
+    DF_UP            // k_up (shape-generic)
+};
+enum DecBwdK {
+    DB_FUSED_LAST,   // k_s2_last_fused
+    DB_ROWS,         // k_s2_bwd_rows
+    DB_S2,           // the k_s2_bwd family (choose_s2_bwd)
+    DB_CT_LDS,       // k_ct_bwd_lds (ctbwd.hip)
+    DB_IG,           // k_ig_bwd_pair
+    DB_GENERIC       // k_wgrad + k_down (shape-generic)
+};
+
+// the k_s2_fwd epilogue of decoder layer L (layer l) in a step
+int s2_fwd_epi(const cae_engine* e, int l, bool train, bool external_loss) {
+    if (l + 1 < (int)e->dec.size()) return train ? S2_RAW_STATS : S2_RAW;
+    if (external_loss) return S2_RAW;
+    return train ? S2_SIGMSE : S2_SIGOUT;
+}
+
+// the thin middle layers behind a BatchNorm'd producer: the row-streaming kernels (forward and backward) where they fit
+bool rows_ok(const cae_engine* e, const ConvLayer& L, int l) {
+    return l + 1 < (int)e->dec.size() && l > 0 && e->dec[l - 1].has_bn && rows_bwd_ok(e, L);
+}
+
+DecFwdK choose_dec_fwd(const cae_engine* e, const ConvLayer& L, int l, int B, bool train, bool external_loss) {
+    static const int fwd_rows = env_int("CAE_ROWS_FWD", 1);   // env: A/B measurements only
+    const bool last = l + 1 == (int)e->dec.size();
+    if (last && train && !external_loss && last_fused_ok(e, L)) return DF_FUSED_LAST;
+    if (rows_ok(e, L, l) && fwd_rows) return DF_ROWS;
+    if (s2_eligible(e, L)) return DF_S2;
+    if (e->use_s2 && !last && L.stride == 2 && L.kh <= 4 && L.kw <= 4) {
+        CtFwd c;
+        int waves = 0;
+        size_t lds = 0;
+        return ct_fwd_plan(e, B, L, l, c, waves, lds) ? DF_CT_LDS : DF_IG;
+    }
+    return DF_UP;
+}
+
+DecBwdK choose_dec_bwd(const cae_engine* e, const ConvLayer& L, int l, int B, bool external_loss) {
+    const bool last = l + 1 == (int)e->dec.size();
+    if (last && !external_loss && last_fused_ok(e, L)) return DB_FUSED_LAST;
+    if (rows_ok(e, L, l)) return DB_ROWS;
+    if (s2_eligible(e, L)) return DB_S2;
+    if (e->use_s2) {
+        CtBwdPlan p;
+        return ct_bwd_plan(e, B, L, l, p) ? DB_CT_LDS : DB_IG;
+    }
+    return DB_GENERIC;
 }
 
 // ---- data-parallel gradient exchange (cae_dp_train_step) -------------------------------------------
@@ -1050,25 +1229,23 @@ int launch_forward(cae_engine* e, const StepArgs& a) {
         if (last && a.external_loss) {   // raw output for a loss computed outside the trunk: no sigmoid, no statistics
             ep = epi_plain(e->fptr(e->off_zlast));
         }
-        if (last && a.train && !a.external_loss && last_fused_ok(e, L)) continue;   // forward, loss and backward of this layer: one launch, in launch_backward
-        if (!last && l > 0 && e->dec[l - 1].has_bn && rows_bwd_ok(e, L)) {
-            static const int fwd_rows = env_int("CAE_ROWS_FWD", 1);   // env: A/B measurements only
-            if (fwd_rows) {
-                S2FwdRows f;
-                memset(&f, 0, sizeof f);
-                f.B = B; f.H = L.hin; f.W = L.win; f.OH = L.hout; f.OW = L.wout;
-                f.in = small.p; f.bn_in = bns;
-                f.w = e->params + L.w_off; f.bias = e->params + L.b_off;
-                f.out = ep.out;
-                f.stats = a.train ? ep.stats : nullptr;
-                ProfScope _p(e, a.train ? "s2_convt_fwd" : "s2_convt_eval", (int)l, f4((double)B * (L.in_elems() + L.out_elems())));
-                rows_fwd_launch(L, f, s);
-                if (a.train)
-                    if (int rc = sync_bn_table(e, a, L.bn_index)) return rc;
-                continue;
-            }
+        const DecFwdK fk = choose_dec_fwd(e, L, (int)l, B, a.train, a.external_loss);
+        if (fk == DF_FUSED_LAST) continue;   // forward, loss and backward of this layer: one launch, in launch_backward
+        if (fk == DF_ROWS) {
+            S2FwdRows f;
+            memset(&f, 0, sizeof f);
+            f.B = B; f.H = L.hin; f.W = L.win; f.OH = L.hout; f.OW = L.wout;
+            f.in = small.p; f.bn_in = bns;
+            f.w = e->params + L.w_off; f.bias = e->params + L.b_off;
+            f.out = ep.out;
+            f.stats = a.train ? ep.stats : nullptr;
+            ProfScope _p(e, a.train ? "s2_convt_fwd" : "s2_convt_eval", (int)l, f4((double)B * (L.in_elems() + L.out_elems())));
+            rows_fwd_launch(L, f, s);
+            if (a.train)
+                if (int rc = sync_bn_table(e, a, L.bn_index)) return rc;
+            continue;
         }
-        if (s2_eligible(e, L)) {
+        if (fk == DF_S2) {
             S2Fwd f;
             memset(&f, 0, sizeof f);
             f.B = B; f.H = L.hin; f.W = L.win; f.OH = L.hout; f.OW = L.wout;
@@ -1097,17 +1274,19 @@ int launch_forward(cae_engine* e, const StepArgs& a) {
             }
             ProfScope _p(e, last ? (a.train ? "s2_convt_last_fwd_loss" : "s2_convt_last_eval") : (a.train ? "s2_convt_fwd" : "s2_convt_eval"), (int)l,
                          f4((double)B * (L.in_elems() + L.out_elems() * (last && (a.train || a.want_loss) ? 2.0 : 1.0))));
-            s2_fwd_dispatch(L, f, s);
+            if (!s2_fwd_dispatch(L, f, s))
+                return fail(CAE_ERR_STATE, "decoder layer %d: no k_s2_fwd kernel for the chosen variant", (int)l);
             if (a.train && !last)
                 if (int rc = sync_bn_table(e, a, L.bn_index)) return rc;
             continue;
         }
-        if (e->use_s2 && !last && L.stride == 2 && L.kh <= 4 && L.kw <= 4) {
-            if (ct_fwd_launch(e, a, L, (int)l, small.p, bns, ep.out, a.train ? ep.stats : nullptr)) {
-                if (a.train)
-                    if (int rc = sync_bn_table(e, a, L.bn_index)) return rc;
-                continue;
-            }
+        if (fk == DF_CT_LDS) {
+            ct_fwd_launch(e, a, L, (int)l, small.p, bns, ep.out, a.train ? ep.stats : nullptr);
+            if (a.train)
+                if (int rc = sync_bn_table(e, a, L.bn_index)) return rc;
+            continue;
+        }
+        if (fk == DF_IG) {
             IgFwd f;
             memset(&f, 0, sizeof f);
             f.B = B; f.Cin = L.cin; f.H = L.hin; f.W = L.win; f.Cout = L.cout; f.OH = L.hout; f.OW = L.wout;
@@ -1156,6 +1335,7 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
     for (int l = (int)e->dec.size() - 1; l >= 0; l--) {
         const ConvLayer& L = e->dec[l];
         const bool last = l + 1 == (int)e->dec.size();
+        const DecBwdK bk = choose_dec_bwd(e, L, l, B, a.external_loss);
         ConvGeom g{B, L.cin, L.hin, L.win, L.cout, L.hout, L.wout, L.kh, L.kw, L.stride};
         // gradient wrt this layer's raw output
         Src gy;
@@ -1177,7 +1357,7 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
             ain = src_plain(e->fptr(P.act_off), L.cin, L.hin, L.win);
             bna = bn_of(e, P, BN_SAVED, 0, 0);
         }
-        if (last && !a.external_loss && last_fused_ok(e, L)) {
+        if (bk == DB_FUSED_LAST) {
             S2Last f;
             memset(&f, 0, sizeof f);
             f.B = B; f.H = L.hin; f.W = L.win; f.OH = L.hout; f.OW = L.wout;
@@ -1209,12 +1389,13 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
                 f.dbg = dbg == 4 ? reinterpret_cast<long long*>(e->ws + e->off_scan) : nullptr;
             }
             ProfScope _p(e, "s2_convt_last_fused", l, f4((double)B * (L.in_elems() * 2.0 + L.out_elems())));
-            last_fused_dispatch(L, f, s);
+            if (!last_fused_dispatch(L, f, s))
+                return fail(CAE_ERR_STATE, "decoder layer %d: no k_s2_last_fused kernel for the chosen variant", (int)l);
             if (l > 0)
                 if (int rc = sync_bn_table(e, a, e->dec[l - 1].bn_index)) return rc;
             continue;
         }
-        if (!last && l > 0 && e->dec[l - 1].has_bn && rows_bwd_ok(e, L)) {
+        if (bk == DB_ROWS) {
             const ConvLayer& P = e->dec[l - 1];
             S2Rows f;
             memset(&f, 0, sizeof f);
@@ -1240,7 +1421,7 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
             if (int rc = sync_bn_table(e, a, P.bn_index)) return rc;
             continue;
         }
-        if (s2_eligible(e, L)) {
+        if (bk == DB_S2) {
             S2Bwd f;
             memset(&f, 0, sizeof f);
             f.B = B; f.H = L.hin; f.W = L.win; f.OH = L.hout; f.OW = L.wout;
@@ -1268,82 +1449,75 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
             }
             ProfScope _p(e, "s2_convt_bwd", l,
                          f4((double)B * (L.out_elems() * (last ? 1.0 : 2.0) + L.in_elems() * 2.0)));
-            s2_bwd_dispatch(L, f, s);
+            if (!s2_bwd_dispatch(L, f, s))
+                return fail(CAE_ERR_STATE, "decoder layer %d: no k_s2_bwd kernel for the chosen variant", (int)l);
             if (l > 0)
                 if (int rc = sync_bn_table(e, a, e->dec[l - 1].bn_index)) return rc;
             continue;
         }
-        if (e->use_s2) {
-            // LDS-staged backward (kernels_ctbwd.h): 3x3 kernels at stride 2, whole 16-channel blocks, images that fit the
-            // staging registers / LDS, and few enough images per accumulator address; otherwise the gather pair below
-            if (l < 31 && ((e->ctbwd_mask >> l) & 1) && L.kh == 3 && L.kw == 3 && L.stride == 2 && L.cin % 16 == 0 && L.cout % 4 == 0 &&
-                L.hout >= 2 * L.hin + 1 && L.wout >= 2 * L.win + 1) {
-                const int HW = L.hin * L.win, OHW = L.hout * L.wout, N = L.cout * 9;
-                int budget = std::min((4 * kCtbG4 * kCtbThreads) / (L.cout * OHW), (4 * kCtbA4 * kCtbThreads) / (16 * HW));
-                int imgs = (int)(((int64_t)L.cin * N * B + 149999) / 150000);
-                imgs = std::max(1, std::min(std::min(imgs, budget), B));
-                const int groups = (B + imgs - 1) / imgs;
-                const int wstr = N | 1;
-                const size_t lds = ct_bwd_lds_bytes(L.cin, L.cout, imgs, HW, OHW, wstr);
-                if (budget >= 1 && 16 * N <= 4 * kCtbW4 * kCtbThreads && lds <= 152 * 1024 &&
-                    (int64_t)L.cin * N * groups <= 400000) {
-                    CtBwd c;
-                    memset(&c, 0, sizeof c);
-                    c.B = B; c.Cin = L.cin; c.H = L.hin; c.W = L.win; c.Cout = L.cout; c.OH = L.hout; c.OW = L.wout;
-                    c.imgs = imgs; c.wstr = wstr;
-                    c.g = gy.p; c.yout = gy.q; c.bn_out = bng;
-                    c.ain = ain.p; c.bn_in = bna;
-                    c.w = e->params + L.w_off;
-                    if (L.sh_w >= 0) {
-                        c.wacc = e->sgacc() + L.sh_w;
-                        c.wacc_stride = e->segs.n;
-                    } else {
-                        c.wacc = acc + L.w_off;
-                    }
-                    if (l == 0) {
-                        c.gin = e->fptr(e->fc[3].grad_off);
-                    } else {
-                        const ConvLayer& P = e->dec[l - 1];
-                        c.gin = e->fptr(P.grad_off);
-                        c.stats_prev = e->bn_stats(P.bn_index);
-                    }
-                    if (L.has_bn) {
-                        c.bg.stats = e->bn_stats(L.bn_index);
-                        c.bg.gamma_acc = acc + L.gamma_off;
-                        c.bg.beta_acc = acc + L.beta_off;
-                        c.bg.C = L.cout;
-                        c.bg.scale = 1.0 / a.world;
-                    }
-                    {
-                        static const int dbg = env_int("CAE_HEAD_DBG", 0), dbg_layer = env_int("CAE_DBG_LAYER", 2);   // tools/last_phases.py ctb
-                        c.dbg = dbg == 6 && l == dbg_layer ? reinterpret_cast<long long*>(e->ws + e->off_scan) : nullptr;
-                    }
-                    ProfScope _p(e, "ct_convt_bwd", l,
-                                 f4((double)B * (L.out_elems() * (last ? 1.0 : 2.0) + L.in_elems() * (l == 0 ? 1.0 : 2.0))));
-                    static const int wg_target = env_int("CAE_CTBWD_WGS", 256);   // env: tuning only
-                    static const int band_env = env_int("CAE_CTBWD_BANDS", 1);   // env: A/B measurements only
-                    int parts = std::max(1, std::min(8, wg_target / (groups * (L.cin / 16))));
-                    size_t lds_launch = lds;
-                    if (band_env && imgs == 1 && parts > 1) {
-                        // one image per workgroup and workgroups to spare: bands of input rows instead of workgroups that
-                        // stage the same image (where the band's pieces fit the band kernel's staging registers)
-                        const int hb = (L.hin + parts - 1) / parts, bands = (L.hin + hb - 1) / hb;
-                        const int gstr = (2 * hb + 1) * L.wout, astr = hb * L.win;
-                        if (bands > 1 && L.cout * gstr <= 8 * kCtbThreads && 16 * astr <= 2 * kCtbThreads) {
-                            c.bands = bands;
-                            c.hb = hb;
-                            parts = bands;
-                            lds_launch = (32 * (size_t)kCtbWaves + 4 * (size_t)(L.cin + L.cout) + (size_t)L.cout * gstr + 4 + 16 * (size_t)astr + 4 +
-                                          16 * (size_t)wstr + 3 * (size_t)astr + (size_t)kCtbWaves * 16 * 17 + 8) * sizeof(float);
-                        }
-                    }
-                    if (cae_internal::ctbwd_launch(&c, sizeof c, (unsigned)groups, (unsigned)(L.cin / 16), (unsigned)parts, lds_launch, s))
-                        return fail(CAE_ERR_ARG, "k_ct_bwd_lds: argument layout mismatch");
-                    if (l > 0)
-                        if (int rc = sync_bn_table(e, a, e->dec[l - 1].bn_index)) return rc;
-                    continue;
+        if (bk == DB_CT_LDS) {
+            CtBwdPlan cp;
+            (void)ct_bwd_plan(e, B, L, l, cp);
+            const int HW = L.hin * L.win, OHW = L.hout * L.wout;
+            const int imgs = cp.imgs, groups = cp.groups, wstr = cp.wstr;
+            const size_t lds = cp.lds;
+            CtBwd c;
+            memset(&c, 0, sizeof c);
+            c.B = B; c.Cin = L.cin; c.H = L.hin; c.W = L.win; c.Cout = L.cout; c.OH = L.hout; c.OW = L.wout;
+            c.imgs = imgs; c.wstr = wstr;
+            c.g = gy.p; c.yout = gy.q; c.bn_out = bng;
+            c.ain = ain.p; c.bn_in = bna;
+            c.w = e->params + L.w_off;
+            if (L.sh_w >= 0) {
+                c.wacc = e->sgacc() + L.sh_w;
+                c.wacc_stride = e->segs.n;
+            } else {
+                c.wacc = acc + L.w_off;
+            }
+            if (l == 0) {
+                c.gin = e->fptr(e->fc[3].grad_off);
+            } else {
+                const ConvLayer& P = e->dec[l - 1];
+                c.gin = e->fptr(P.grad_off);
+                c.stats_prev = e->bn_stats(P.bn_index);
+            }
+            if (L.has_bn) {
+                c.bg.stats = e->bn_stats(L.bn_index);
+                c.bg.gamma_acc = acc + L.gamma_off;
+                c.bg.beta_acc = acc + L.beta_off;
+                c.bg.C = L.cout;
+                c.bg.scale = 1.0 / a.world;
+            }
+            {
+                static const int dbg = env_int("CAE_HEAD_DBG", 0), dbg_layer = env_int("CAE_DBG_LAYER", 2);   // tools/last_phases.py ctb
+                c.dbg = dbg == 6 && l == dbg_layer ? reinterpret_cast<long long*>(e->ws + e->off_scan) : nullptr;
+            }
+            ProfScope _p(e, "ct_convt_bwd", l,
+                         f4((double)B * (L.out_elems() * (last ? 1.0 : 2.0) + L.in_elems() * (l == 0 ? 1.0 : 2.0))));
+            static const int wg_target = env_int("CAE_CTBWD_WGS", 256);   // env: tuning only
+            static const int band_env = env_int("CAE_CTBWD_BANDS", 1);   // env: A/B measurements only
+            int parts = std::max(1, std::min(8, wg_target / (groups * (L.cin / 16))));
+            size_t lds_launch = lds;
+            if (band_env && imgs == 1 && parts > 1) {
+                // one image per workgroup and workgroups to spare: bands of input rows instead of workgroups that
+                // stage the same image (where the band's pieces fit the band kernel's staging registers)
+                const int hb = (L.hin + parts - 1) / parts, bands = (L.hin + hb - 1) / hb;
+                const int gstr = (2 * hb + 1) * L.wout, astr = hb * L.win;
+                if (bands > 1 && L.cout * gstr <= 8 * kCtbThreads && 16 * astr <= 2 * kCtbThreads) {
+                    c.bands = bands;
+                    c.hb = hb;
+                    parts = bands;
+                    lds_launch = (32 * (size_t)kCtbWaves + 4 * (size_t)(L.cin + L.cout) + (size_t)L.cout * gstr + 4 + 16 * (size_t)astr + 4 +
+                                  16 * (size_t)wstr + 3 * (size_t)astr + (size_t)kCtbWaves * 16 * 17 + 8) * sizeof(float);
                 }
             }
+            if (cae_internal::ctbwd_launch(&c, sizeof c, (unsigned)groups, (unsigned)(L.cin / 16), (unsigned)parts, lds_launch, s))
+                return fail(CAE_ERR_ARG, "k_ct_bwd_lds: argument layout mismatch");
+            if (l > 0)
+                if (int rc = sync_bn_table(e, a, e->dec[l - 1].bn_index)) return rc;
+            continue;
+        }
+        if (bk == DB_IG) {
             IgWgrad fw;
             memset(&fw, 0, sizeof fw);
             fw.B = B; fw.Cin = L.cin; fw.H = L.hin; fw.W = L.win; fw.Cout = L.cout; fw.OH = L.hout; fw.OW = L.wout;
@@ -2577,6 +2751,84 @@ int cae_profile_end(cae_engine* e, cae_profile_rec* out, int capacity) {
     }
     e->prof.clear();
     return n;
+}
+
+int cae_debug_plan(const cae_engine* e, int batch, int train, char* out, int64_t out_bytes) {
+    if (!e || !out || out_bytes < 1) return fail(CAE_ERR_ARG, "cae_debug_plan: bad argument");
+    if (batch < 1 || batch > e->max_batch) return fail(CAE_ERR_ARG, "cae_debug_plan: batch %d outside 1 .. %d", batch, e->max_batch);
+    // the step of a single device without SyncBN; the trunk of the var engine hands its last layer's raw output to a loss outside
+    const bool tr = train != 0, ext = e->variational;
+    const StepArgs a{0, nullptr, batch, batch, batch, tr, true, nullptr, nullptr, false};
+    std::string s;
+    char line[256];
+    {
+        HeadArgs h;
+        size_t lds = 0;
+        snprintf(line, sizeof line, "head fwd=%s\n", head_plan(e, a, h, lds) ? "fused" : "layers");
+        s += line;
+    }
+    static const char* const kEpiName[] = {"raw_stats", "sigmse", "sigout", "raw"};   // S2Epi
+    for (int l = 0; l < (int)e->dec.size(); l++) {
+        const ConvLayer& L = e->dec[l];
+        const int ci = L.cin, co = L.cout, kh = L.kh, kw = L.kw;
+        char f[128], b[128];
+        switch (choose_dec_fwd(e, L, l, batch, tr, ext)) {
+            case DF_FUSED_LAST: {
+                const LastPick p = choose_last(L, l > 0 && e->dec[l - 1].has_bn);
+                snprintf(f, sizeof f, "last_fused<%d,%d,%d,%d> hb=%d vec4=%d bn=%d", ci, co, kh, kw, p.hb, (int)p.vec4, (int)p.bn);
+                break;
+            }
+            case DF_ROWS: {
+                const RowsPick p = choose_rows_fwd(L);
+                snprintf(f, sizeof f, "s2_fwd_rows<%d,%d,%d,%d>", ci, co, p.hb, 64 / p.lw);
+                break;
+            }
+            case DF_S2: {
+                const int epi = s2_fwd_epi(e, l, tr, ext);
+                const S2FwdPick p = choose_s2_fwd(L, batch, epi);
+                const char* fam = p.k == S2F_CS ? "s2_fwd_cs" : (p.k == S2F_QUAD ? "s2_fwd" : "s2_fwd2");
+                snprintf(f, sizeof f, "%s<%d,%d,%d,%d,%d> epi=%s", fam, ci, co, kh, kw, p.tw, kEpiName[epi]);
+                break;
+            }
+            case DF_CT_LDS: snprintf(f, sizeof f, "ct_fwd_lds<%d,%d>", kh, kw); break;
+            case DF_IG: snprintf(f, sizeof f, "ig_fwd_s2"); break;
+            case DF_UP: snprintf(f, sizeof f, "up"); break;
+        }
+        if (!tr) {
+            snprintf(b, sizeof b, "-");
+        } else {
+            switch (choose_dec_bwd(e, L, l, batch, ext)) {
+                case DB_FUSED_LAST: snprintf(b, sizeof b, "(fused)"); break;
+                case DB_ROWS: {
+                    const RowsPick p = choose_rows_bwd(L);
+                    snprintf(b, sizeof b, "s2_bwd_rows<%d,%d,%d,3,3,%d,%d,%d>", ci, ci == 4 ? 4 : 2, co, p.hb, 64 / p.lw, p.d);
+                    break;
+                }
+                case DB_S2: {
+                    const S2BwdPick p = choose_s2_bwd(L);
+                    if (p.k == S2B_DIRECT) snprintf(b, sizeof b, "s2_bwd2<%d,%d,%d,%d,%d>", ci, co, kh, kw, p.tw);
+                    else if (p.k == S2B_SPLIT) snprintf(b, sizeof b, "s2_bwd_split<%d,%d,%d,%d,%d,%d>", ci, p.ct, co, kh, kw, p.tw);
+                    else snprintf(b, sizeof b, "s2_bwd<%d,%d,%d,%d,%d>", ci, p.ct, co, kh, kw);
+                    break;
+                }
+                case DB_CT_LDS: snprintf(b, sizeof b, "ct_bwd_lds"); break;
+                case DB_IG: snprintf(b, sizeof b, "ig_bwd_pair"); break;
+                case DB_GENERIC: snprintf(b, sizeof b, "wgrad+down"); break;
+            }
+        }
+        snprintf(line, sizeof line, "dec%d fwd=%s bwd=%s\n", l, f, b);
+        s += line;
+    }
+    {
+        TailArgs t;
+        size_t lds = 0;
+        snprintf(line, sizeof line, "tail bwd=%s\n", !tr ? "-" : (tail_plan(e, a, t, lds) ? "fused" : "layers"));
+        s += line;
+    }
+    if ((int64_t)s.size() + 1 > out_bytes)
+        return fail(CAE_ERR_ARG, "cae_debug_plan: the report needs %zu bytes, got %lld", s.size() + 1, (long long)out_bytes);
+    memcpy(out, s.c_str(), s.size() + 1);
+    return CAE_OK;
 }
 
 // ---- loader -------------------------------------------------------------------------------------

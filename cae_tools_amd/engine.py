@@ -24,6 +24,23 @@ class EnginePlan(SpecPlan):
         """state_dict prefixes ("enc/encoder_cnn.1") of the BatchNorm layers, in order"""
         return [n[: -len(".running_mean")] for n in self.tensors if n.endswith(".running_mean")]
 
+    def set_kernel_mode(self, mode):
+        """cae_set_kernel_mode: 0 shape-generic kernels, 1 specialised (the default), bit 1 the LDS-staged backward on every
+        eligible layer, bit 2 the gather forward on the channel-rich decoder layers"""
+        check(self.lib.cae_set_kernel_mode(self.handle, int(mode)))
+
+    def kernel_plan(self, batch, train):
+        """the kernels a step at this batch runs (cae_debug_plan, include/cae_hip.h), no GPU needed:
+        {"head": {"fwd": "fused"}, "dec0": {"fwd": "ct_fwd_lds<3,3>", "bwd": "ig_bwd_pair"}, ...,
+        "dec4": {"fwd": "last_fused<2,1,4,4>", "hb": "4", "vec4": "1", "bn": "1", "bwd": "(fused)"}, "tail": {"bwd": "fused"}}"""
+        buf = C.create_string_buffer(1 << 16)
+        check(self.lib.cae_debug_plan(self.handle, int(batch), 1 if train else 0, buf, len(buf)))
+        plan = {}
+        for line in buf.value.decode().splitlines():
+            (name, *fields) = line.split()
+            plan[name] = dict(f.split("=", 1) for f in fields)
+        return plan
+
 
 class HipEngine(EnginePlan):
 

@@ -227,6 +227,12 @@ int cae_graph_count(const cae_engine* e);
  * `index` ignored, count doubles).  Returns the number of elements copied or a negative status. */
 int64_t cae_debug_read(cae_engine* e, const char* what, int index, void* host_out, int64_t capacity_elems);
 
+/* Which kernels a step at `batch` runs (the choosers the launch code switches on), without a GPU: a NUL-terminated report
+ * in out_host, one line per decoder layer ("dec3 fwd=s2_fwd_cs<8,4,3,4,32> epi=raw_stats bwd=s2_bwd<8,2,4,3,4>") between
+ * "head fwd=fused|layers" and "tail bwd=fused|layers|-".  train = 0: the eval forward (bwd=-).  Follows cae_set_kernel_mode;
+ * reports the single-device step without SyncBN.  Fails for a batch outside 1 .. max_batch or too short a buffer. */
+int cae_debug_plan(const cae_engine* e, int batch, int train, char* out_host, int64_t out_bytes);
+
 /* ---- measurement ------------------------------------------------------------------------- */
 
 /* Per-launch timing for bench.py's roofline figure.  Between begin and end every kernel launch

@@ -76,6 +76,14 @@ int main() {
             expect(cae_workspace_bytes(e) > 0 && cae_param_count(e) >= total, "sizes");
             expect(cae_train_step(e, 0, nullptr, 64) != 0, "a step on an unbound engine is refused");
             expect(cae_set_cursor(e, 0, 0) != 0, "cursor on an unbound engine is refused");
+            char plan[4096];
+            expect(cae_debug_plan(e, 64, 1, plan, sizeof plan) == 0 && strstr(plan, "dec5 fwd=last_fused<2,1,4,4> hb=4 vec4=1 bn=1 bwd=(fused)"),
+                   "cae_debug_plan");
+            expect(cae_debug_plan(e, 64, 0, plan, sizeof plan) == 0 && strstr(plan, "tail bwd=-"), "cae_debug_plan (eval)");
+            expect(cae_set_kernel_mode(e, 0) == 0 && cae_debug_plan(e, 8, 1, plan, sizeof plan) == 0 && strstr(plan, "dec5 fwd=up bwd=wgrad+down"),
+                   "cae_debug_plan (generic kernels)");
+            expect(cae_debug_plan(e, 65, 1, plan, sizeof plan) != 0, "a plan beyond max_batch is refused");
+            expect(cae_debug_plan(e, 64, 1, plan, 16) != 0, "too small a plan buffer is refused");
             cae_engine_destroy(e);
         }
         // broken geometry: messages, no leak

@@ -8,6 +8,7 @@ drives them with a short loop equivalent to the reference step
 and stores inputs + expected outputs as data.  No reference source is stored.
 
     python tests/golden/make_golden.py            # rewrites tests/golden/*.npz|*.json
+    python tests/golden/make_golden.py NAME ...   # only these model cases (the other files stay as they are)
 
 The reference has no golden vectors or numeric assertions of its own,
 so these files are the parity pin.  Everything that needs a random number takes it
@@ -100,6 +101,10 @@ CASES = {
     # explicit layer counts (conv_input_layer_count / conv_output_layer_count)
     "counts_b3": dict(in_size=(32, 32), in_ch=1, out_size=(64, 64), out_ch=1, fc=40, latent=10,
                       batch=3, seed=17, in_layers=1, out_layers=2, full_output=True),
+    # 2-channel, non-square output: the last layer is 4->2 with (3, 4) taps, 96 weights (more than the 72 a training step
+    # fuses), so its forward, loss and backward run as separate stride-2 kernels
+    "ch2_63x64_b3": dict(in_size=(16, 16), in_ch=1, out_size=(63, 64), out_ch=2, fc=16, latent=4,
+                         batch=3, seed=19, full_output=True),
 }
 
 # a hand-written layer definition file (--layer-definitions-path) with output_padding
@@ -358,6 +363,14 @@ def dataset_case():
 
 
 def main():
+    only = sys.argv[1:]
+    if only:
+        unknown = set(only) - set(CASES)
+        if unknown:
+            sys.exit(f"unknown case(s): {sorted(unknown)}")
+        for name in only:
+            run_case(name, CASES[name])
+        return
     for name, cfg in CASES.items():
         run_case(name, cfg)
     hs = ModelSpec()

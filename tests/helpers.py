@@ -10,7 +10,7 @@ import numpy as np
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 MODEL_CASES = ["cfg1_b3", "cfg2_b4", "circle2_b2", "tidal_b3", "odd_k5_b5", "s3_b4", "counts_b3",
-               "handspec_b4"]
+               "handspec_b4", "ch2_63x64_b3"]
 
 
 def projections(arr, seed, nproj=8):
