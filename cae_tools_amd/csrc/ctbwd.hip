@@ -1,6 +1,7 @@
 // ctbwd.hip - the LDS-staged backward kernel of the channel-rich decoder layers (kernels_ctbwd.h) in a code object of its own.
-// It is an opt-in (cae_set_kernel_mode bit 1 / CAE_CTBWD), and compiled into engine.hip's code object its mere presence moved
-// the default path's kernels and cost 1.2 us per step (178.9 against 177.7: measured with and without it, twice each).
+// It runs where cae_create's rule or cae_set_kernel_mode bit 1 puts it.  Compiled into engine.hip's code object, its mere
+// presence moved the default path's kernels and cost 1.2 us per step (178.9 against 177.7: measured with and without it,
+// twice each).
 // The shared device helpers come from the same headers, wrapped in a namespace of this file so that their kernels' host
 // stubs do not collide with engine.hip's.
 #include <hip/hip_runtime.h>

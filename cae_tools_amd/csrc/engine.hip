@@ -97,7 +97,7 @@ struct cae_engine {
 
     // workspace carve (byte offsets)
     int64_t off_state = 0, off_losses = 0, off_zero_begin = 0, off_gradacc = 0, off_zero_end = 0;
-    int64_t off_glast = 0, off_scan = 0, off_sgacc = 0;
+    int64_t off_glast = 0, off_sgacc = 0;
     ShardSegs segs{};                      // sharded gradient accumulators (thin stride-2 layers)
     int64_t ws_need = 0;
 
@@ -119,7 +119,7 @@ struct cae_engine {
     cae_internal::TrunkHooks hooks{nullptr, nullptr, nullptr};
     bool gather_fwd = false;   // cae_set_kernel_mode bit 2: channel-rich decoder layers' forward on the gather kernel k_ig_fwd_s2
     int ctbwd_mask = 0;  // bit l: decoder layer l's backward runs the LDS-staged kernel (kernels_ctbwd.h) where eligible
-    int ctbwd_auto = 0;  // ... the mask chosen at creation (CAE_CTBWD, or the rule in cae_create): its layers have sharded accumulators
+    int ctbwd_auto = 0;  // ... the mask chosen at creation (the rule in cae_create): its layers have sharded accumulators
     int64_t off_xbatch = 0;     // the current batch's inputs, contiguous (written by k_head_fwd, read by k_adam's fused conv-0 weight gradient)
     bool x_published = false;   // this step's k_head_fwd wrote them
     AdamConv0 c0_pending{};     // filled by launch_backward when the conv-0 weight gradient is left to k_adam
@@ -351,7 +351,6 @@ enum S2FwdK {
 struct S2FwdPick { S2FwdK k; int tw; };
 
 S2FwdPick choose_s2_fwd(const ConvLayer& L, int B, int epi) {
-    static const int cs_on = env_int("CAE_S2_CS", 1);   // env: A/B measurements only
     // each thread of k_s2_fwd2 covers 2x2 quads; lanes run along the row
     const int px = ((L.wout + 1) / 2 + 1) / 2, py = ((L.hout + 1) / 2 + 1) / 2;   // thread columns / rows per image
     if ((long long)B * px * py < 100000) {
@@ -359,7 +358,7 @@ S2FwdPick choose_s2_fwd(const ConvLayer& L, int B, int epi) {
         const int qx = (L.wout + 1) / 2;
         const int tw = qx > 32 ? 64 : 32;
         // intermediate layers with many weights: output channels split over the waves
-        if (L.cin * L.cout * L.kh * L.kw > 80 && (256 / L.cout) % 64 == 0 && cs_on && (epi == S2_RAW_STATS || epi == S2_RAW))
+        if (L.cin * L.cout * L.kh * L.kw > 80 && (256 / L.cout) % 64 == 0 && (epi == S2_RAW_STATS || epi == S2_RAW))
             return {S2F_CS, tw};
         return {S2F_QUAD, tw};
     }
@@ -381,12 +380,16 @@ S2BwdPick choose_s2_bwd(const ConvLayer& L) {
     return {S2B_GENERAL, 32, (L.cin % 2 == 0 && L.cin != 6) ? 2 : 3};
 }
 
+// grid caps of the k_s2_fwd family (k_s2_fwd / k_s2_fwd_cs, k_s2_fwd2), measured on MI355X at batch 64 (workgroups walk the
+// remaining tiles): more workgroups only add fp64-atomic traffic at the end of the kernel
+constexpr int kS2FwdCap = 1024, kS2Fwd2Cap = 512;
+// ... and of k_s2_bwd2 / k_s2_bwd_split: each workgroup ends with Cin*Cout*kh*kw + 2*Cin fp64 atomics, and those dominate
+// beyond 512 (measured per step at batch 64: 1536 -> 286 us, 512 -> 274 us)
+constexpr int kS2BwdCap = 512;
+
 // false: this instantiation has no kernel for the pick (the chooser and the `if constexpr` guards below disagree)
 template <int CIN, int COUT, int KH, int KW>
 bool s2_fwd_launch(S2Fwd a, S2FwdPick p, hipStream_t s) {
-    // grid caps measured on MI355X at batch 64 (workgroups walk the remaining tiles): more workgroups
-    // only add fp64-atomic traffic at the end of the kernel
-    static const int capf = env_int("CAE_CAP_F", 1024), capf2 = env_int("CAE_CAP_F2", 512);   // env: tuning only
     const int px = ((a.OW + 1) / 2 + 1) / 2, py = ((a.OH + 1) / 2 + 1) / 2;   // thread columns / rows per image (k_s2_fwd2)
     const int qx = (a.OW + 1) / 2, qy = (a.OH + 1) / 2;                       // quad columns / rows (k_s2_fwd, k_s2_fwd_cs)
     switch (p.k) {
@@ -397,12 +400,12 @@ bool s2_fwd_launch(S2Fwd a, S2FwdPick p, hipStream_t s) {
                     a.tiles_x = (qx + 63) / 64;
                     a.tiles_y = (qy + PIX / 64 - 1) / (PIX / 64);
                     a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-                    hipLaunchKernelGGL((k_s2_fwd_cs<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < capf ? a.total_tiles : capf), dim3(256), 0, s, a);
+                    hipLaunchKernelGGL((k_s2_fwd_cs<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < kS2FwdCap ? a.total_tiles : kS2FwdCap), dim3(256), 0, s, a);
                 } else {
                     a.tiles_x = (qx + 31) / 32;
                     a.tiles_y = (qy + PIX / 32 - 1) / (PIX / 32);
                     a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-                    hipLaunchKernelGGL((k_s2_fwd_cs<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < capf ? a.total_tiles : capf), dim3(256), 0, s, a);
+                    hipLaunchKernelGGL((k_s2_fwd_cs<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < kS2FwdCap ? a.total_tiles : kS2FwdCap), dim3(256), 0, s, a);
                 }
                 return true;
             }
@@ -412,12 +415,12 @@ bool s2_fwd_launch(S2Fwd a, S2FwdPick p, hipStream_t s) {
                 a.tiles_x = (qx + 63) / 64;
                 a.tiles_y = (qy + 3) / 4;
                 a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-                hipLaunchKernelGGL((k_s2_fwd<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < capf ? a.total_tiles : capf), dim3(256), 0, s, a);
+                hipLaunchKernelGGL((k_s2_fwd<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < kS2FwdCap ? a.total_tiles : kS2FwdCap), dim3(256), 0, s, a);
             } else {
                 a.tiles_x = (qx + 31) / 32;
                 a.tiles_y = (qy + 7) / 8;
                 a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-                hipLaunchKernelGGL((k_s2_fwd<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < capf ? a.total_tiles : capf), dim3(256), 0, s, a);
+                hipLaunchKernelGGL((k_s2_fwd<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < kS2FwdCap ? a.total_tiles : kS2FwdCap), dim3(256), 0, s, a);
             }
             return true;
         case S2F_WIDE:
@@ -425,17 +428,17 @@ bool s2_fwd_launch(S2Fwd a, S2FwdPick p, hipStream_t s) {
                 a.tiles_x = (px + 63) / 64;
                 a.tiles_y = (py + 3) / 4;
                 a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-                hipLaunchKernelGGL((k_s2_fwd2<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < capf2 ? a.total_tiles : capf2), dim3(256), 0, s, a);
+                hipLaunchKernelGGL((k_s2_fwd2<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < kS2Fwd2Cap ? a.total_tiles : kS2Fwd2Cap), dim3(256), 0, s, a);
             } else if (p.tw == 32) {
                 a.tiles_x = (px + 31) / 32;
                 a.tiles_y = (py + 7) / 8;
                 a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-                hipLaunchKernelGGL((k_s2_fwd2<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < capf2 ? a.total_tiles : capf2), dim3(256), 0, s, a);
+                hipLaunchKernelGGL((k_s2_fwd2<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < kS2Fwd2Cap ? a.total_tiles : kS2Fwd2Cap), dim3(256), 0, s, a);
             } else {
                 a.tiles_x = (px + 15) / 16;
                 a.tiles_y = (py + 15) / 16;
                 a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-                hipLaunchKernelGGL((k_s2_fwd2<CIN, COUT, KH, KW, 16>), dim3(a.total_tiles < capf2 ? a.total_tiles : capf2), dim3(256), 0, s, a);
+                hipLaunchKernelGGL((k_s2_fwd2<CIN, COUT, KH, KW, 16>), dim3(a.total_tiles < kS2Fwd2Cap ? a.total_tiles : kS2Fwd2Cap), dim3(256), 0, s, a);
             }
             return true;
     }
@@ -456,9 +459,6 @@ bool s2_fwd_dispatch(const ConvLayer& L, const S2Fwd& a, hipStream_t s) {
 
 template <int CIN, int COUT, int KH, int KW>
 bool s2_bwd_launch(S2Bwd a, S2BwdPick p, hipStream_t s) {   // false: as s2_fwd_launch
-    // 512 workgroups: each ends with Cin*Cout*kh*kw + 2*Cin fp64 atomics, and those dominate beyond that
-    // (measured per step at batch 64: 1536 -> 286 us, 512 -> 274 us)
-    static const int cap2 = env_int("CAE_CAP_B2", 512), caps = env_int("CAE_CAP_BS", 512);
     switch (p.k) {
         case S2B_DIRECT:
             if constexpr (CIN * COUT * KH * KW <= 72) {
@@ -466,12 +466,12 @@ bool s2_bwd_launch(S2Bwd a, S2BwdPick p, hipStream_t s) {   // false: as s2_fwd_
                     a.tiles_x = (a.W + 63) / 64;
                     a.tiles_y = (a.H + 3) / 4;
                     a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-                    hipLaunchKernelGGL((k_s2_bwd2<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < cap2 ? a.total_tiles : cap2), dim3(256), 0, s, a);
+                    hipLaunchKernelGGL((k_s2_bwd2<CIN, COUT, KH, KW, 64>), dim3(a.total_tiles < kS2BwdCap ? a.total_tiles : kS2BwdCap), dim3(256), 0, s, a);
                 } else {
                     a.tiles_x = (a.W + 31) / 32;
                     a.tiles_y = (a.H + 7) / 8;
                     a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-                    hipLaunchKernelGGL((k_s2_bwd2<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < cap2 ? a.total_tiles : cap2), dim3(256), 0, s, a);
+                    hipLaunchKernelGGL((k_s2_bwd2<CIN, COUT, KH, KW, 32>), dim3(a.total_tiles < kS2BwdCap ? a.total_tiles : kS2BwdCap), dim3(256), 0, s, a);
                 }
                 return true;
             }
@@ -482,7 +482,7 @@ bool s2_bwd_launch(S2Bwd a, S2BwdPick p, hipStream_t s) {   // false: as s2_fwd_
                 a.tiles_x = (a.W + 31) / 32;
                 a.tiles_y = (a.H + 1) / 2;
                 a.total_tiles = a.B * a.tiles_x * a.tiles_y;
-                hipLaunchKernelGGL((k_s2_bwd_split<CIN, 2, COUT, KH, KW, 32>), dim3(a.total_tiles < caps ? a.total_tiles : caps), dim3(256), 0, s, a);
+                hipLaunchKernelGGL((k_s2_bwd_split<CIN, 2, COUT, KH, KW, 32>), dim3(a.total_tiles < kS2BwdCap ? a.total_tiles : kS2BwdCap), dim3(256), 0, s, a);
                 return true;
             }
             return false;
@@ -530,8 +530,7 @@ void rows_go(S2Rows a, int lw, hipStream_t s) {
 }
 
 bool rows_bwd_ok(const cae_engine* e, const ConvLayer& L) {
-    static const int enabled = env_int("CAE_ROWS", 1);            // env: A/B measurements only
-    if (!enabled || !s2_eligible(e, L) || L.kh != 3 || L.kw != 3 || !L.has_bn) return false;
+    if (!s2_eligible(e, L) || L.kh != 3 || L.kw != 3 || !L.has_bn) return false;
     const int qw = (L.wout + 1) / 2;
     const int lw = qw <= 32 ? 32 : 64;
     if (qw > 64 || L.win > lw - 1) return false;      // a lane per quad column; the last lane of an image owns no pixel
@@ -545,29 +544,18 @@ struct RowsPick { int hb, d, lw; };
 int rows_lw(const ConvLayer& L) { return (L.wout + 1) / 2 <= 32 ? 32 : 64; }
 
 RowsPick choose_rows_bwd(const ConvLayer& L) {
-    static const int hb42 = env_int("CAE_ROWS_HB42", 2), hb84 = env_int("CAE_ROWS_HB84", 4);   // env: tuning only
-    // short bands with every row's loads issued up front (a wave pays the memory latency once) against tall bands that load one
-    // row ahead (less re-reading at the band edges, but a round trip per row: a wave is alone on its SIMD)
-    const bool tall = L.cin == 4 ? hb42 == 4 : hb84 == 4;
-    return tall ? RowsPick{4, 1, rows_lw(L)} : RowsPick{2, 3, rows_lw(L)};
+    // 4 -> 2: short bands with every row's loads issued up front (a wave pays the memory latency once); 8 -> 4: tall bands that
+    // load one row ahead (less re-reading at the band edges, but a round trip per row: a wave is alone on its SIMD)
+    return L.cin == 4 ? RowsPick{2, 3, rows_lw(L)} : RowsPick{4, 1, rows_lw(L)};
 }
 
-RowsPick choose_rows_fwd(const ConvLayer& L) {
-    static const int hb42 = env_int("CAE_ROWS_FHB42", 2), hb84 = env_int("CAE_ROWS_FHB84", 1);   // env: tuning only
-    if (L.cin == 4) return RowsPick{hb42 == 4 ? 4 : 2, 0, rows_lw(L)};
-    return RowsPick{hb84 == 2 ? 2 : 1, 0, rows_lw(L)};
-}
+RowsPick choose_rows_fwd(const ConvLayer& L) { return RowsPick{L.cin == 4 ? 2 : 1, 0, rows_lw(L)}; }
 
 void rows_bwd_launch(const ConvLayer& L, S2Rows a, hipStream_t s) {
     const RowsPick p = choose_rows_bwd(L);
     a.QH = (L.hout + 1) / 2;
-    if (L.cin == 4) {
-        if (p.hb == 4) rows_go<4, 4, 2, 4, 1>(a, p.lw, s);
-        else rows_go<4, 4, 2, 2, 3>(a, p.lw, s);
-    } else {
-        if (p.hb == 4) rows_go<8, 2, 4, 4, 1>(a, p.lw, s);
-        else rows_go<8, 2, 4, 2, 3>(a, p.lw, s);
-    }
+    if (L.cin == 4) rows_go<4, 4, 2, 2, 3>(a, p.lw, s);
+    else rows_go<8, 2, 4, 4, 1>(a, p.lw, s);
 }
 
 template <int CIN, int COUT, int HB>
@@ -584,24 +572,24 @@ void rows_fwd_go(S2FwdRows a, int lw, hipStream_t s) {
 void rows_fwd_launch(const ConvLayer& L, S2FwdRows a, hipStream_t s) {
     const RowsPick p = choose_rows_fwd(L);
     a.QH = (L.hout + 1) / 2;
-    if (L.cin == 4) {
-        if (p.hb == 4) rows_fwd_go<4, 2, 4>(a, p.lw, s);
-        else rows_fwd_go<4, 2, 2>(a, p.lw, s);
-    } else {
-        if (p.hb == 2) rows_fwd_go<8, 4, 2>(a, p.lw, s);
-        else rows_fwd_go<8, 4, 1>(a, p.lw, s);
-    }
+    if (L.cin == 4) rows_fwd_go<4, 2, 2>(a, p.lw, s);
+    else rows_fwd_go<8, 4, 1>(a, p.lw, s);
 }
 
 // ---- last decoder layer of a training step as one launch (kernels_last.h): forward + sigmoid + MSE + backward ---------
 bool last_fused_ok(const cae_engine* e, const ConvLayer& L) {
-    static const int enabled = env_int("CAE_LAST_FUSED", 1);   // env: A/B measurements only
-    return enabled && s2_eligible(e, L) && L.cin * L.cout * L.kh * L.kw <= 72 && L.sh_b >= 0;
+    return s2_eligible(e, L) && L.cin * L.cout * L.kh * L.kw <= 72 && L.sh_b >= 0;
 }
 
-// the variant of k_s2_last_fused: quad rows per band (HB), 16-byte target loads (one strip, width a multiple of 4), BatchNorm on
-// its input (a producer with BatchNorm)
-struct LastPick { int hb; bool vec4, bn; };
+// k_s2_last_fused: a wave walks a band of kLastHB quad rows (+1 recomputed): taller bands recompute less, shorter ones give more
+// waves (measured at the benchmark geometry: 2048 waves of 4+1 rows, two per SIMD, beat 1024 of 8+1: 20.4 against 21.8 us;
+// and at batch 128 / 512, where 8+1 rows used to be chosen: 244.2 against 246.8 and 601.6 against 607.6 us per step - the
+// 8-row variant's register arrays end up in scratch)
+constexpr int kLastHB = 4;
+
+// the variant of k_s2_last_fused: 16-byte target loads (one strip, width a multiple of 4), BatchNorm on its input (a producer
+// with BatchNorm)
+struct LastPick { bool vec4, bn; };
 
 int last_strips(const ConvLayer& L) {
     const int qw = (L.wout + 1) / 2;
@@ -609,24 +597,7 @@ int last_strips(const ConvLayer& L) {
     return (wmax + kLastStripPx - 1) / kLastStripPx;
 }
 
-LastPick choose_last(const ConvLayer& L, bool bn_in) {
-    static const int hb_env = env_int("CAE_LAST_HB", 0);   // env: tuning only
-    // a wave walks a band of HB quad rows (+1 recomputed): taller bands recompute less, shorter ones give more waves
-    // (measured at the benchmark geometry: 2048 waves of 4+1 rows, two per SIMD, beat 1024 of 8+1: 20.4 against 21.8 us;
-    // and at batch 128 / 512, where 8+1 rows used to be chosen: 244.2 against 246.8 and 601.6 against 607.6 us per step -
-    // the 8-row variant's register arrays end up in scratch)
-    int hb = hb_env ? hb_env : 4;
-    if (hb != 8) hb = 4;
-    return LastPick{hb, last_strips(L) == 1 && (L.wout & 3) == 0, bn_in};
-}
-
-template <int CIN, int COUT, int KH, int KW, int HB>
-void last_fused_go(const S2Last& a, LastPick p, hipStream_t s) {
-    const dim3 grid((a.total + 3) / 4);
-    if (p.vec4 && p.bn) hipLaunchKernelGGL((k_s2_last_fused<CIN, COUT, KH, KW, HB, true, true>), grid, dim3(256), 0, s, a);
-    else if (p.bn) hipLaunchKernelGGL((k_s2_last_fused<CIN, COUT, KH, KW, HB, false, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_s2_last_fused<CIN, COUT, KH, KW, HB, false, false>), grid, dim3(256), 0, s, a);
-}
+LastPick choose_last(const ConvLayer& L, bool bn_in) { return LastPick{last_strips(L) == 1 && (L.wout & 3) == 0, bn_in}; }
 
 template <int CIN, int COUT, int KH, int KW>
 bool last_fused_launch(S2Last a, LastPick p, hipStream_t s) {   // false: as s2_fwd_launch
@@ -635,10 +606,12 @@ bool last_fused_launch(S2Last a, LastPick p, hipStream_t s) {   // false: as s2_
         a.QW = (a.OW + 1) / 2;
         const int wmax = a.W > a.QW - 1 ? a.W : a.QW - 1, hmax = a.H > a.QH - 1 ? a.H : a.QH - 1;
         a.strips = (wmax + kLastStripPx - 1) / kLastStripPx;   // = last_strips(L)
-        a.bands = (hmax + p.hb - 1) / p.hb;
+        a.bands = (hmax + kLastHB - 1) / kLastHB;
         a.total = a.B * a.strips * a.bands;
-        if (p.hb == 8) last_fused_go<CIN, COUT, KH, KW, 8>(a, p, s);
-        else last_fused_go<CIN, COUT, KH, KW, 4>(a, p, s);
+        const dim3 grid((a.total + 3) / 4);
+        if (p.vec4 && p.bn) hipLaunchKernelGGL((k_s2_last_fused<CIN, COUT, KH, KW, kLastHB, true, true>), grid, dim3(256), 0, s, a);
+        else if (p.bn) hipLaunchKernelGGL((k_s2_last_fused<CIN, COUT, KH, KW, kLastHB, false, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_s2_last_fused<CIN, COUT, KH, KW, kLastHB, false, false>), grid, dim3(256), 0, s, a);
         return true;
     }
     return false;
@@ -673,17 +646,17 @@ void ct_fwd_go(const CtFwd& c, dim3 grid, int threads, size_t lds, hipStream_t s
     hipLaunchKernelGGL((k_ct_fwd_lds<KH, KW>), grid, dim3(threads), lds, s, c);
 }
 
+// MFMAs per wave before K is split further
+constexpr int kCtFwdMfmas = 24;
+
 // Fills c's geometry and split; false: the layer does not fit (see above).
 bool ct_fwd_plan(const cae_engine* e, int batch, const ConvLayer& L, int layer, CtFwd& c, int& waves, size_t& lds) {
-    static const int enabled = env_int("CAE_CTLDS", -1);       // env: A/B measurements only - layer mask (-1: by batch size, below)
-    static const int mf_target = env_int("CAE_CT_MF", 24);     // env: tuning only - MFMAs per wave before K is split further
     // Against the gather kernel it replaces (k_ig_fwd_s2) the LDS-staged one has a third of the instructions and wins from
     // batch 128 up (239.9 / 342.1 / 590.8 against 243.6 / 349.5 / 598.3 us per step at 128 / 256 / 512); at the benchmark's 64
     // both take 8-11 us per launch, all of it latency, and the step is 0.8 us shorter with the gather kernels (167.7 against
     // 168.5, four alternating runs) - but their gradients at that size sit 6.8e-4 from the oracle's where the LDS-staged
     // forward's sit within the full-size test's 2e-4 (test_full_size_gpu.py): parity first, the LDS-staged kernels run.
-    const int mask = e->gather_fwd ? 0 : (enabled >= 0 ? enabled : 0x7fffffff);
-    if (!(layer < 31 && ((mask >> layer) & 1)) || L.cin % 4 || L.kh < 3 || L.kw < 3) return false;
+    if (e->gather_fwd || layer >= 31 || L.cin % 4 || L.kh < 3 || L.kw < 3) return false;
     memset(&c, 0, sizeof c);
     c.B = batch; c.Cin = L.cin; c.H = L.hin; c.W = L.win; c.Cout = L.cout; c.OH = L.hout; c.OW = L.wout;
     c.QH = (L.hout + 1) / 2; c.QW = (L.wout + 1) / 2;
@@ -693,7 +666,7 @@ bool ct_fwd_plan(const cae_engine* e, int batch, const ConvLayer& L, int layer, 
     const int taps = ((L.kh + 1) / 2 + L.kh / 2) * ((L.kw + 1) / 2 + L.kw / 2);   // sum of n_p over the four parities = kh * kw
     const int mf = L.cin * taps / 4;
     int ks = 1;
-    while (ks < 8 && mf / ks > mf_target && L.cin % (ks * 2 * 4) == 0) ks *= 2;
+    while (ks < 8 && mf / ks > kCtFwdMfmas && L.cin % (ks * 2 * 4) == 0) ks *= 2;
     int rt = 8 / ks;
     if (rt > c.tiles) rt = c.tiles;
     if (rt > 4) rt = 4;
@@ -712,10 +685,6 @@ void ct_fwd_launch(cae_engine* e, const StepArgs& a, const ConvLayer& L, int lay
     size_t lds = 0;
     (void)ct_fwd_plan(e, a.batch, L, layer, c, waves, lds);
     c.in = in; c.bn_in = bn_in; c.w = e->params + L.w_off; c.bias = e->params + L.b_off; c.out = out; c.stats = stats;
-    {
-        static const int dbg = env_int("CAE_HEAD_DBG", 0), dbg_layer = env_int("CAE_DBG_LAYER", 2);   // tools/ct_phases.py
-        c.dbg = dbg == 3 && layer == dbg_layer && a.train ? reinterpret_cast<long long*>(e->ws + e->off_scan) : nullptr;
-    }
     dim3 grid((unsigned)(a.batch * c.tg), (unsigned)((L.cout + 15) / 16));
     ProfScope _p(e, a.train ? "ct_convt_fwd" : "ct_convt_eval", layer, f4((double)a.batch * (L.in_elems() + L.out_elems())));
     if (L.kh == 3 && L.kw == 3) ct_fwd_go<3, 3>(c, grid, 64 * waves, lds, e->stream);
@@ -749,8 +718,7 @@ bool ct_bwd_plan(const cae_engine* e, int B, const ConvLayer& L, int l, CtBwdPla
 // Fills the descriptor shared by k_head_fwd and k_tail_bwd and lays out their LDS.  Returns false when the model or
 // the batch does not fit (the caller then runs the per-layer launches).
 bool head_plan(const cae_engine* e, const StepArgs& a, HeadArgs& h, size_t& lds_bytes) {
-    static const int enabled = env_int("CAE_HEAD", 1);   // env: A/B measurements only
-    if (!enabled || !e->use_s2 || a.syncing() || e->variational || (int)e->enc.size() > kHeadMaxEnc) return false;
+    if (!e->use_s2 || a.syncing() || e->variational || (int)e->enc.size() > kHeadMaxEnc) return false;
     memset(&h, 0, sizeof h);
     h.B = a.batch;
     h.n_enc = (int)e->enc.size();
@@ -758,10 +726,9 @@ bool head_plan(const cae_engine* e, const StepArgs& a, HeadArgs& h, size_t& lds_
     h.momentum = kBnMomentum;
     h.eps = kBnEps;
     h.st = e->state();
-    // (1 since the end of round 2: 168.2 against 169.7 us per step with 4 - more workgroups recompute the encoder, each holds
-    // a quarter of the last Linear layer's weights and finishes its strip sooner; 8: 186.9)
-    static const int tpw = env_int("CAE_HEAD_TPW", 1);   // env: tuning only - Linear-3 column tiles per workgroup
-    h.tiles_per_wg = tpw < 1 ? 1 : tpw;
+    // Linear-3 column tiles per workgroup (1 since the end of round 2: 168.2 against 169.7 us per step with 4 - more workgroups
+    // recompute the encoder, each holds a quarter of the last Linear layer's weights and finishes its strip sooner; 8: 186.9)
+    h.tiles_per_wg = 1;
     double* acc = e->gradacc();
     int64_t top = 0;
     auto take = [&](int64_t floats) {
@@ -880,8 +847,7 @@ bool head_plan(const cae_engine* e, const StepArgs& a, HeadArgs& h, size_t& lds_
 
 // k_tail_bwd (kernels_head.h): Linear 2..0 backward in one launch.  False: run the per-layer pair launches.
 bool tail_plan(const cae_engine* e, const StepArgs& a, TailArgs& t, size_t& lds_bytes) {
-    static const int enabled = env_int("CAE_TAIL", 1);   // env: A/B measurements only
-    if (!enabled || !e->use_s2 || a.syncing() || e->variational) return false;
+    if (!e->use_s2 || a.syncing() || e->variational) return false;
     memset(&t, 0, sizeof t);
     const ConvLayer& P = e->enc.back();
     double* acc = e->gradacc();
@@ -975,10 +941,9 @@ bool rows_ok(const cae_engine* e, const ConvLayer& L, int l) {
 }
 
 DecFwdK choose_dec_fwd(const cae_engine* e, const ConvLayer& L, int l, int B, bool train, bool external_loss) {
-    static const int fwd_rows = env_int("CAE_ROWS_FWD", 1);   // env: A/B measurements only
     const bool last = l + 1 == (int)e->dec.size();
     if (last && train && !external_loss && last_fused_ok(e, L)) return DF_FUSED_LAST;
-    if (rows_ok(e, L, l) && fwd_rows) return DF_ROWS;
+    if (rows_ok(e, L, l)) return DF_ROWS;
     if (s2_eligible(e, L)) return DF_S2;
     if (e->use_s2 && !last && L.stride == 2 && L.kh <= 4 && L.kw <= 4) {
         CtFwd c;
@@ -1023,11 +988,8 @@ int dp_allreduce_grads(cae_engine* e, int64_t lo, int64_t hi, hipStream_t on) {
     return CAE_OK;
 }
 
-// first bucket on the second stream (cae_dp_set_overlap; the env variable, read once, overrides it for measurements)
-bool dp_overlap(const cae_engine* e, const StepArgs& a) {
-    static const int forced = env_int("CAE_DP_OVERLAP", -1);
-    return (forced >= 0 ? forced != 0 : e->dp_overlap) && !a.dp_sync;
-}
+// first bucket on the second stream (cae_dp_set_overlap)
+bool dp_overlap(const cae_engine* e, const StepArgs& a) { return e->dp_overlap && !a.dp_sync; }
 
 // Without the overlap (and without SyncBN) there is nothing to gain from two buckets: ONE narrowing launch and ONE all-reduce
 // of the whole gradient arena after backward - one collective latency per step instead of two.
@@ -1089,8 +1051,6 @@ int launch_forward(cae_engine* e, const StepArgs& a) {
         head.perm = a.x_direct ? nullptr : a.perm;
         head.use_cursor = a.x_direct ? 0 : 1;
         head.bump_adam = a.train ? 1 : 0;
-        static const int dbg = env_int("CAE_HEAD_DBG", 0);   // tools/head_phases.py: stamps land in fc[3]'s gradient buffer
-        head.dbg = dbg && !a.train ? reinterpret_cast<long long*>(e->fptr(e->fc[3].grad_off)) : nullptr;
         const int T = (e->fc[3].nout + 15) / 16;
         double bytes = 0;
         for (auto& L : e->enc) bytes += f4((double)B * (L.in_elems() + L.out_elems()));
@@ -1293,16 +1253,11 @@ int launch_forward(cae_engine* e, const StepArgs& a) {
             f.KH = L.kh; f.KW = L.kw; f.QH = (L.hout + 1) / 2; f.QW = (L.wout + 1) / 2;
             f.in = small.p; f.bn_in = bns; f.w = e->params + L.w_off; f.bias = e->params + L.b_off;
             f.out = ep.out; f.stats = a.train ? ep.stats : nullptr;
-            {
-                static const int dbg = env_int("CAE_HEAD_DBG", 0);   // tools/head_phases.py ig: stamps of the LAST such layer
-                f.dbg = dbg == 1 && a.train ? reinterpret_cast<long long*>(e->ws + e->off_scan) : nullptr;
-            }
             const int mtiles = (B * f.QH * f.QW + 15) / 16;
             f.ksplit = L.cin >= 48 ? 4 : (L.cin >= 24 ? 2 : 1);
             // at most ~1024 workgroups over the 4 parities: every workgroup ends with up to 32 fp64 atomics
             {
-                const int waves_m = 4 / f.ksplit;
-                static const int target = env_int("CAE_IG_FWD_WGS", 1024);   // env: tuning only
+                const int waves_m = 4 / f.ksplit, target = 1024;
                 int tpw = (mtiles * 4 + waves_m * target - 1) / (waves_m * target);
                 f.tiles_per_wave = tpw < 1 ? 1 : (tpw > 8 ? 8 : tpw);
             }
@@ -1384,10 +1339,6 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
                 f.gin = e->fptr(P.grad_off);
                 f.stats_in = e->bn_stats(P.bn_index);
             }
-            {
-                static const int dbg = env_int("CAE_HEAD_DBG", 0);   // tools/last_phases.py
-                f.dbg = dbg == 4 ? reinterpret_cast<long long*>(e->ws + e->off_scan) : nullptr;
-            }
             ProfScope _p(e, "s2_convt_last_fused", l, f4((double)B * (L.in_elems() * 2.0 + L.out_elems())));
             if (!last_fused_dispatch(L, f, s))
                 return fail(CAE_ERR_STATE, "decoder layer %d: no k_s2_last_fused kernel for the chosen variant", (int)l);
@@ -1412,10 +1363,6 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
             f.bg.beta_acc = acc + L.beta_off;
             f.bg.C = L.cout;
             f.bg.scale = 1.0 / a.world;
-            {
-                static const int dbg = env_int("CAE_HEAD_DBG", 0), dbg_layer = env_int("CAE_DBG_LAYER", 4);   // tools/last_phases.py rows
-                f.dbg = dbg == 5 && l == dbg_layer ? reinterpret_cast<long long*>(e->ws + e->off_scan) : nullptr;
-            }
             ProfScope _p(e, "s2_convt_bwd", l, f4((double)B * (L.out_elems() * 2.0 + L.in_elems() * 2.0)));
             rows_bwd_launch(L, f, s);
             if (int rc = sync_bn_table(e, a, P.bn_index)) return rc;
@@ -1488,17 +1435,12 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
                 c.bg.C = L.cout;
                 c.bg.scale = 1.0 / a.world;
             }
-            {
-                static const int dbg = env_int("CAE_HEAD_DBG", 0), dbg_layer = env_int("CAE_DBG_LAYER", 2);   // tools/last_phases.py ctb
-                c.dbg = dbg == 6 && l == dbg_layer ? reinterpret_cast<long long*>(e->ws + e->off_scan) : nullptr;
-            }
             ProfScope _p(e, "ct_convt_bwd", l,
                          f4((double)B * (L.out_elems() * (last ? 1.0 : 2.0) + L.in_elems() * (l == 0 ? 1.0 : 2.0))));
-            static const int wg_target = env_int("CAE_CTBWD_WGS", 256);   // env: tuning only
-            static const int band_env = env_int("CAE_CTBWD_BANDS", 1);   // env: A/B measurements only
-            int parts = std::max(1, std::min(8, wg_target / (groups * (L.cin / 16))));
+            // ~256 workgroups
+            int parts = std::max(1, std::min(8, 256 / (groups * (L.cin / 16))));
             size_t lds_launch = lds;
-            if (band_env && imgs == 1 && parts > 1) {
+            if (imgs == 1 && parts > 1) {
                 // one image per workgroup and workgroups to spare: bands of input rows instead of workgroups that
                 // stage the same image (where the band's pieces fit the band kernel's staging registers)
                 const int hb = (L.hin + parts - 1) / parts, bands = (L.hin + hb - 1) / hb;
@@ -1533,8 +1475,7 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
             }
             const int wtiles = ((L.cin + 15) / 16) * ((L.cout * L.kh * L.kw + 15) / 16);
             const int steps = (B * L.hin * L.win + 3) / 4;
-            static const int wgrad_target = env_int("CAE_IG_WGRAD_WGS", 2048);   // env: tuning only
-            int chunks = wgrad_target / wtiles;
+            int chunks = 2048 / wtiles;   // ~2048 weight-gradient workgroups
             if (chunks < 1) chunks = 1;
             int per = (steps + chunks - 1) / chunks;
             per = (per + 31) / 32 * 32;
@@ -1558,8 +1499,7 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
             const int mtiles = (B * L.hin * L.win + 15) / 16;
             const int ksteps = (L.cout * L.kh * L.kw + 3) / 4;
             fd.ksplit = ksteps > 24 ? 4 : (ksteps > 12 ? 2 : 1);   // <= 12 k-steps (one load batch) per wave where possible
-            static const int tpw_env = env_int("CAE_IG_DGRAD_TPW", 0);   // env: tuning only
-            fd.tiles_per_wave = tpw_env > 0 ? tpw_env : (mtiles >= 8192 ? 2 : 1);
+            fd.tiles_per_wave = mtiles >= 8192 ? 2 : 1;
             const int per_block = (4 / fd.ksplit) * fd.tiles_per_wave;
             const int d_gx = (mtiles + per_block - 1) / per_block, d_gy = (L.cin + 15) / 16;
             const size_t lds_d = (128 + 1024) * sizeof(float) + (size_t)(L.cin + L.cout + 1) * sizeof(float4) +
@@ -1567,10 +1507,6 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
             const size_t lds_w = 1024 * sizeof(float) + (size_t)(L.cin + L.cout + 1) * sizeof(float4);
             ProfScope _p(e, "ig_convt_bwd_pair", l,
                          f4((double)B * (L.out_elems() * (last ? 1.0 : 2.0) + L.in_elems() * (l == 0 ? 1.0 : 2.0))));
-            {
-                static const int dbg = env_int("CAE_HEAD_DBG", 0);   // tools/head_phases.py igb: stamps of decoder layer 2's pair
-                fw.dbg = fd.dbg = dbg == 2 && l == 2 ? reinterpret_cast<long long*>(e->ws + e->off_scan) : nullptr;
-            }
             // XCD-aware order (kernels_igemm.h): d_group input-gradient blocks cover the positions of one weight-gradient chunk
             int d_group = (per * 4) / (per_block * 16);
             if (d_group < 1) d_group = 1;
@@ -1639,8 +1575,6 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
                 for (int j = 0; j < 3; j++)
                     bytes += f4((double)B * (3.0 * e->fc[j].nin + 2.0 * e->fc[j].nout) + (double)e->fc[j].nin * e->fc[j].nout) +
                              8.0 * e->fc[j].nin * e->fc[j].nout;
-                static const int dbg = env_int("CAE_HEAD_DBG", 0);
-                tail.dbg = dbg ? reinterpret_cast<long long*>(e->fptr(e->fc[3].grad_off)) : nullptr;   // Linear 3's gradient is dead by now
                 head_lds_attr(k_tail_bwd, tail_lds);
                 ProfScope _p(e, "tail_bwd", 0, bytes);
                 hipLaunchKernelGGL(k_tail_bwd, dim3((B + 15) / 16, 4), dim3(kHeadThreads), tail_lds, s, tail);
@@ -1699,8 +1633,7 @@ int launch_backward(cae_engine* e, const StepArgs& a) {
                     ProfScope _p(e, "linear_bwd_pair_mfma", i,
                                  f4((double)B * (3.0 * F.nin + 2.0 * F.nout) + (double)F.nin * F.nout) + 8.0 * F.nin * F.nout);
                     // the input gradient's contraction runs over nout: long for the last decoder Linear (576 at cfg2): burst variant
-                    static const int burst_on = env_int("CAE_GEMM_BURST", 1);   // env: A/B measurements only
-                    const bool burst = burst_on && gd.epi != GE_BN_MASK && gd.sa_k == 1 && gd.sb_n == 1 && gd.K % 4 == 0 && gd.K >= 128 &&
+                    const bool burst = gd.epi != GE_BN_MASK && gd.sa_k == 1 && gd.sb_n == 1 && gd.K % 4 == 0 && gd.K >= 128 &&
                                        (gd.K / 4 + 3) / 4 <= kBurstSteps && gd.sa_m % 4 == 0;
                     if (burst && gemm16_burst_lds(gd.K) > lds) lds = gemm16_burst_lds(gd.K);
                     hipLaunchKernelGGL(k_gemm16_pair, dim3(tiles_w + tiles_d), dim3(256), lds, s, gw, gd, tiles_w, burst ? 1 : 0);
@@ -1874,9 +1807,8 @@ int launch_one(cae_engine* e, int op, const StepArgs& a) {
     } else if (op == OP_TRAIN || op == OP_FWDBWD) {
         // the accumulators were zeroed by the previous step's last kernel (k_adam / k_acc_to_f32) or by
         // the caller's zero-filled workspace on the very first step
-        static const int fuse_c0 = env_int("CAE_ADAM_CONV0", 1);   // env: A/B measurements only
         StepArgs af = a;
-        af.adam_follows = op == OP_TRAIN && fuse_c0 != 0;
+        af.adam_follows = op == OP_TRAIN;
         memset(&e->c0_pending, 0, sizeof e->c0_pending);
         int rc = launch_forward(e, af);
         if (rc) return rc;
@@ -2111,10 +2043,8 @@ static int engine_create_impl(const cae_layer_spec* enc, int n_enc, const cae_la
             // Which layers take it by default: one block of 16 input channels (no staging repeated per block) and few enough
             // weights that the optimiser's eight shard reads per weight stay cheap - at the benchmark geometry the 16 -> 8
             // layer: 169.6 against 171.5 us per step; the 32 -> 16 and 64 -> 32 layers lose (172.9 / 175.7 on their own).
-            static const int ctb_env = env_int("CAE_CTBWD", -1);   // env: bit l = decoder layer l on the LDS-staged backward kernel
-            const bool ctb_shape = l < 31 && L.transposed && L.stride == 2 && L.kh == 3 && L.kw == 3 && L.cin % 16 == 0 &&
-                                   L.cout % 4 == 0;
-            const bool ctb = ctb_shape && (ctb_env >= 0 ? ((ctb_env >> l) & 1) != 0 : (L.cin == 16 && L.cin * L.cout * 9 <= 2048));
+            const bool ctb = l < 31 && L.transposed && L.stride == 2 && L.kh == 3 && L.kw == 3 && L.cin % 16 == 0 && L.cout % 4 == 0 &&
+                             L.cin == 16 && L.cin * L.cout * 9 <= 2048;
             if (l == 0) e->ctbwd_auto = 0;
             if (ctb) e->ctbwd_auto |= 1 << l;
             e->ctbwd_mask = e->ctbwd_auto;
@@ -2136,7 +2066,7 @@ static int engine_create_impl(const cae_layer_spec* enc, int n_enc, const cae_la
     Carver carve{256};
     e->off_state = carve(sizeof(StepState));
     e->off_losses = carve((int64_t)kLossSlots * kStatShards * sizeof(double));
-    e->off_scan = carve(1024 * 3 * sizeof(double));
+    carve(1024 * 3 * sizeof(double));   // unused (held diagnostics once): the layout behind it stays as it was
     e->bn_stat_off.resize(bn);
     e->bn_saved_off.resize(bn);
     e->bn_channels.resize(bn);
@@ -2244,8 +2174,7 @@ int cae_set_capture_only(cae_engine* e, int enabled) {
 
 int cae_set_kernel_mode(cae_engine* e, int specialised) {
     if (!e) return fail(CAE_ERR_ARG, "null engine");
-    static const int force_env = env_int("CAE_CTBWD_FORCE", -1);   // env: A/B measurements only - run-time mask (unsharded where not chosen at creation)
-    const int ctb = (specialised & 2) ? 0x7fffffff : (force_env >= 0 ? force_env : e->ctbwd_auto);   // bit 1: every eligible layer
+    const int ctb = (specialised & 2) ? 0x7fffffff : e->ctbwd_auto;   // bit 1: every eligible layer
     const bool gather = (specialised & 4) != 0;
     if (e->use_s2 != ((specialised & 1) != 0) || ctb != e->ctbwd_mask || gather != e->gather_fwd) e->drop_graphs();
     e->use_s2 = (specialised & 1) != 0;
@@ -2393,8 +2322,7 @@ int dp_self_test(cae_engine* e) {
     fill();
     if (int rc = body()) return rc;
     if (int rc = check((double)e->dp_world, "plain")) return rc;
-    static const int want_graph = env_int("CAE_DP_GRAPH", 1);   // env: 0 keeps RCCL calls out of captured graphs
-    e->dp_graph_ok = want_graph != 0 && s != nullptr;
+    e->dp_graph_ok = s != nullptr;
     if (!e->dp_graph_ok) return CAE_OK;
     fill();
     HIP_TRY(hipStreamSynchronize(s));
@@ -2669,10 +2597,6 @@ int64_t cae_debug_read(cae_engine* e, const char* what, int index, void* host_ou
         if (index < 0 || index > 3) return fail(CAE_ERR_ARG, "fc index out of range");
         src = e->ws + e->fc[index].grad_off;
         n = mb * e->fc[index].nout;
-    } else if (w == "scan") {   // the loader's scratch: where tools/head_phases.py's decoder-kernel stamps land
-        src = e->ws + e->off_scan;
-        n = 1024 * 3;
-        esz = 8;
     } else if (w == "grad_acc") {
         src = e->gradacc();
         n = e->tab.n_param;
@@ -2775,7 +2699,7 @@ int cae_debug_plan(const cae_engine* e, int batch, int train, char* out, int64_t
         switch (choose_dec_fwd(e, L, l, batch, tr, ext)) {
             case DF_FUSED_LAST: {
                 const LastPick p = choose_last(L, l > 0 && e->dec[l - 1].has_bn);
-                snprintf(f, sizeof f, "last_fused<%d,%d,%d,%d> hb=%d vec4=%d bn=%d", ci, co, kh, kw, p.hb, (int)p.vec4, (int)p.bn);
+                snprintf(f, sizeof f, "last_fused<%d,%d,%d,%d> hb=%d vec4=%d bn=%d", ci, co, kh, kw, kLastHB, (int)p.vec4, (int)p.bn);
                 break;
             }
             case DF_ROWS: {

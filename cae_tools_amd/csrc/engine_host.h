@@ -42,12 +42,6 @@ inline int fail(int code, const char* fmt, ...) {
 // workgroups of 256 threads for n elements: at least 1, at most cap (the grid-stride kernels walk the rest)
 inline int blocks_for(long long n, int cap) { return (int)std::max(1ll, std::min((n + 255) / 256, (long long)cap)); }
 
-// an integer switch from the environment; unset or empty: dflt
-inline int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
 // The tensor table: every named tensor of the model in the reference's state_dict order, with its offset in the parameter
 // (arena 0) or buffer (arena 1) arena.  Tensors are 16-byte aligned.
 struct TensorTable {

@@ -38,7 +38,6 @@ struct CtBwd {
     double* wacc;          // (Cin, Cout*9) fp64 accumulator, or its sharded side table (shard stride wacc_stride doubles)
     long long wacc_stride; // 0: not sharded
     BnGradOut bg;
-    long long* dbg;
 };
 
 constexpr int kCtbThreads = 512;
@@ -89,8 +88,6 @@ __device__ __forceinline__ void ct_bwd_body(const CtBwd& a) {
     int* pos_a = pos_g + P;                                            // [P] offset of (img, pos) inside araw (channel 0)
     int* pos_o = pos_a + P;                                            // [P] offset of (img, pos) inside gin (image b0, channel 0)
     float* tiles = reinterpret_cast<float*>(pos_o + P);                // [waves][16 positions][17]
-#define CTB_STAMP(i) do { if (a.dbg && threadIdx.x == 0 && (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x < 384) a.dbg[((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8 + (i)] = wall_clock64(); } while (0)
-    CTB_STAMP(0);
     const bool designated = blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0;
     const bool bwd = a.bn_out.mode == BN_BWD, act = a.bn_in.mode != BN_NONE;
     const float inv_hw = 1.0f / (float)(nrow * a.W), inv_w = 1.0f / (float)a.W, inv_gstr = 1.0f / (float)gstr,
@@ -155,7 +152,6 @@ __device__ __forceinline__ void ct_bwd_body(const CtBwd& a) {
     for (int u = 0; u < NA; u++) asm volatile("" : "+v"(av[u]));
 #pragma unroll
     for (int u = 0; u < kCtbW4; u++) asm volatile("" : "+v"(wr[u]));
-    CTB_STAMP(1);
 
     bn_consts(a.bn_out, cout4, false);
     bn_consts(a.bn_in, cin4, false, 64);
@@ -197,7 +193,6 @@ __device__ __forceinline__ void ct_bwd_body(const CtBwd& a) {
         pos_o[p] = im * a.Cin * HW + y0 * a.W + pi;
     }
     __syncthreads();
-    CTB_STAMP(2);
     // the gradient maps: BatchNorm-backward once per element
 #pragma unroll
     for (int u = 0; u < NG; u++) {
@@ -229,7 +224,6 @@ __device__ __forceinline__ void ct_bwd_body(const CtBwd& a) {
         }
     }
     __syncthreads();
-    CTB_STAMP(3);
 
     // ---- tasks ----
     const int mtiles = (P + 15) >> 4;                         // input-gradient tasks: one tile of 16 positions each
@@ -362,7 +356,6 @@ __device__ __forceinline__ void ct_bwd_body(const CtBwd& a) {
             }
         }
     }
-    CTB_STAMP(4);
     // ---- the producer's BatchNorm-backward sums ----
     if (a.stats_prev) {
         // the 16 lanes of a row hold the same four channels: DPP row sums, then one LDS atomic per channel and wave
@@ -388,8 +381,6 @@ __device__ __forceinline__ void ct_bwd_body(const CtBwd& a) {
             acc_add<ACC_GRAD>(&a.stats_prev[((size_t)shard * a.Cin + c) * 4 + 2 + (tid & 1)], t);
         }
     }
-    CTB_STAMP(5);
-#undef CTB_STAMP
 }
 
 __global__ void __launch_bounds__(kCtbThreads) k_ct_bwd_lds(CtBwd a) {

@@ -33,7 +33,6 @@ struct CtFwd {
     const float* bias;
     float* out;
     double* stats;   // [shards][Cout][4] or nullptr (eval)
-    long long* dbg;  // diagnostics (tools/ct_phases.py): 8 wall-clock stamps per workgroup (first 384), or nullptr
 };
 
 template <int KH, int KW>
@@ -67,10 +66,8 @@ __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
     constexpr int NP00 = NJ0 * NI0, NP01 = NJ0 * NI1, NP10 = NJ1 * NI0, NP11 = NJ1 * NI1;
     static_assert(KH >= 2 && KH <= 4 && KW >= 2 && KW <= 4, "stride-2 kernels of 2..4 taps per axis");
 
-#define CT_STAMP(i) do { if (a.dbg && threadIdx.x == 0 && blockIdx.y * gridDim.x + blockIdx.x < 384) a.dbg[(blockIdx.y * gridDim.x + blockIdx.x) * 8 + (i)] = wall_clock64(); } while (0)
     kernarg_warm<sizeof(CtFwd)>();
     extern __shared__ double lds_d[];
-    CT_STAMP(0);
     double* lstat = lds_d;                                          // [16 channels][2]
     float4* cin4 = reinterpret_cast<float4*>(lstat + 32);           // [Cin]
     float* wl = reinterpret_cast<float*>(cin4 + a.Cin);             // [Cin][16][KKp]
@@ -176,7 +173,6 @@ __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
         for (int idx = tid; idx < n4; idx += nthr) reinterpret_cast<float4*>(img)[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
-    CT_STAMP(1);
     {   // the image: BatchNorm + ReLU once per element, scattered into the zero border
         const float inv_hw = 1.0f / (float)HW, inv_w = 1.0f / (float)a.W;
         const bool bn = a.bn_in.mode != BN_NONE;
@@ -206,7 +202,6 @@ __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
         }
     }
     __syncthreads();
-    CT_STAMP(2);
 
     const int wv = tid >> 6, lane = tid & 63;
     const int r = lane & 15, q = lane >> 4;
@@ -254,7 +249,6 @@ __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
             }
         }
     }
-    CT_STAMP(3);
     // The bias is waited for HERE, once, outside the predicated stores below.  Left to its first use - inside a predicated
     // block, which the lanes that skip it leave with the load still formally pending - the compiler repeats the wait in every
     // one of the sixteen blocks, and from the second on that wait is for the previous block's STORE to complete (the memory
@@ -290,7 +284,6 @@ __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
             pw[(12 + jj) * 64] = acc11[jj];
         }
         __syncthreads();
-        CT_STAMP(4);
         const int rpw = 16 / a.ks;
         const float* pt = part + (tl * a.ks) * 1024 + lane;
         for (int rl = 0; rl < rpw; rl++) {
@@ -300,7 +293,6 @@ __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
             emit(reg, v);
         }
     } else {
-        CT_STAMP(4);
 #pragma unroll
         for (int jj = 0; jj < 4; jj++) {
             emit(0 + jj, acc00[jj]);
@@ -309,7 +301,6 @@ __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
             emit(12 + jj, acc11[jj]);
         }
     }
-    CT_STAMP(5);
     if (a.stats) {
         // a lane's fp32 sums cover at most 16 values; from there on fp64: lanes r, r+16, r+32, r+48 hold the same channel
         // (fold), waves meet in LDS, then one fp64 atomic per value and workgroup
@@ -329,8 +320,6 @@ __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
             }
         }
     }
-    CT_STAMP(6);
-#undef CT_STAMP
 }
 
 inline size_t ct_fwd_lds_bytes(int Cin, int plane, int KH, int KW, int waves, int ks) {

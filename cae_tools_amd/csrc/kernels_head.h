@@ -13,7 +13,7 @@
 //                input-gradient chain for its rows as far as its task needs, then adds its rows' share of one weight
 //                gradient, or (task 0) writes the masked gradient for the encoder and its BatchNorm sums.
 //
-// Measured rules these follow (tools/head_phases.py prints per-phase wall-clock stamps of both kernels): every global read
+// Measured rules these follow (per-phase timings in DESIGN.md): every global read
 // is issued in one burst at kernel start; weights travel as coalesced 16-byte loads and reach the MFMA operand layout through
 // LDS (gathering them from global memory in that layout costs 16 cache lines per wave instruction); a phase on one CU is
 // bound by latency and instruction issue, not FLOPs, so work is spread over workgroups where no batch-wide sum forbids it.
@@ -93,7 +93,6 @@ struct HeadArgs {
     float* xbatch;      // head, training: the first workgroup leaves the staged input batch here, contiguous (k_adam's fused conv-0 weight gradient)
     double* clear0;     // ... and clears these clear0_n doubles (the first encoder layer's BatchNorm sum table, which k_adam then leaves alone)
     int clear0_n;
-    long long* dbg;     // diagnostics (tools/head_phases.py): per workgroup 16 wall-clock stamps, or nullptr
 };
 
 // C[m][n] = sum_k A(m,k) * B(k,n) over the 16x16 tiles (tm0.., tn0..) x (TM, TN), k in [0,K): the workgroup's 16 waves
@@ -279,10 +278,6 @@ __device__ __forceinline__ void head_stage_inputs(const HeadArgs& a, float* lds,
     __syncthreads();
 }
 
-__device__ __forceinline__ void head_stamp(const HeadArgs& a, int phase) {
-    if (a.dbg && threadIdx.x == 0) a.dbg[(blockIdx.y * gridDim.x + blockIdx.x) * 16 + phase] = wall_clock64();
-}
-
 // The encoder for the whole batch, in LDS: raw outputs at o_y, BatchNorm constants {mean, gamma*invstd, beta, invstd} at
 // o_c.  `publish`: this workgroup writes the raw outputs, saved and running statistics to global memory.
 __device__ __forceinline__ void head_encoder(const HeadArgs& a, float* lds, bool publish) {
@@ -422,7 +417,6 @@ __device__ __forceinline__ void head_encoder(const HeadArgs& a, float* lds, bool
                     }
             }
         }
-        if (l < 2) head_stamp(a, 9 + 3 * l);
         __syncthreads();
         float4* kout = reinterpret_cast<float4*>(lds + L.o_c);
         // a row of 16 lanes per channel: each lane takes one wave's partial sums, the row adds them up with DPP (one thread
@@ -460,7 +454,6 @@ __device__ __forceinline__ void head_encoder(const HeadArgs& a, float* lds, bool
         if (publish && a.train)
             for (int i = tid; i < npos * L.cout; i += kHeadThreads) L.y[i] = yout[i];
         __syncthreads();
-        if (l < 2) head_stamp(a, 10 + 3 * l);
     }
 }
 
@@ -475,7 +468,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_head_fwd(HeadArgs a) {
     // no kernel of the forward/backward pass reads adam_step, so bumping it here cannot race
     if (first && tid == 0 && a.bump_adam) const_cast<StepState*>(a.st)->adam_step += 1;
 
-    head_stamp(a, 0);
     // The cursor first: the input batch hangs off it (head_stage_inputs).  Read through an index the compiler cannot see is
     // zero: a load it knows to be wave-uniform is moved to a scalar register at once, i.e. waited for here, with nothing
     // else in flight yet.
@@ -541,7 +533,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_head_fwd(HeadArgs a) {
 #pragma unroll
     for (int j = 0; j < kHeadEarly; j++) wreg[j] = load_piece(j);
     for (int i = tid; i < 32 * a.ld_h + 32; i += kHeadThreads) lds[a.o_h[0] + i] = 0.f;   // both panels (adjacent), padding and guard included
-    head_stamp(a, 1);
     head_stage_inputs(a, lds, bs);
     // (the LAST workgroup: the first one already publishes the encoder's outputs and statistics)
     if (blockIdx.x == gridDim.x - 1 && blockIdx.y == gridDim.y - 1) {   // uniform per workgroup
@@ -555,7 +546,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_head_fwd(HeadArgs a) {
         }
         for (int i = tid; i < a.clear0_n; i += kHeadThreads) a.clear0[i] = 0.0;
     }
-    head_stamp(a, 2);
     head_encoder(a, lds, first);
     f32x4 wlate[kHeadW4 - kHeadEarly];
     const bool late = a.w_total4 > kHeadEarly * kHeadThreads;   // uniform
@@ -563,7 +553,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_head_fwd(HeadArgs a) {
 #pragma unroll
         for (int j = kHeadEarly; j < kHeadW4; j++) wlate[j - kHeadEarly] = load_piece(j);
     }
-    head_stamp(a, 3);
 
     const int row0 = blockIdx.x * 16;
     const int rows = min(16, a.B - row0);
@@ -587,7 +576,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_head_fwd(HeadArgs a) {
 #pragma unroll
     for (int j = 0; j < kHeadEarly; j++) store_piece(j, wreg[j]);
     __syncthreads();
-    head_stamp(a, 4);
     const bool store_h = blockIdx.y == 0 && a.train;
     auto run_fc = [&](auto I) {
         constexpr int i = decltype(I)::value;
@@ -613,7 +601,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_head_fwd(HeadArgs a) {
                          });
         hin = ho;
         hout = hi;
-        head_stamp(a, 5 + i);
     };
     run_fc(std::integral_constant<int, 0>{});
     if (late) {   // their LDS rows are not read before the barriers of the next stage
@@ -653,7 +640,6 @@ struct TailArgs {
     int w4[3];              // float4s of W0, W1, W2
     StageSplit sp_d[3];     // chain stages producing g1, g0, gx
     StageSplit sp_w[3];     // dW2, dW1, dW0
-    long long* dbg;         // diagnostics (tools/head_phases.py): 16 wall-clock stamps per workgroup, or nullptr
 };
 
 // one row-major block [rows][4 * n4row] as coalesced 16-byte loads, at most two per thread
@@ -681,8 +667,6 @@ __device__ __forceinline__ void tail_put(const TailRegs& r, float* dst, int tota
     }
 }
 
-#define TAIL_STAMP(i) do { if (a.dbg && threadIdx.x == 0) a.dbg[(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = wall_clock64(); } while (0)
-
 // dW[o][i] += sum over this workgroup's rows of g[b][o] * in(b, i); column nin of `in` is the constant 1 (bias gradient)
 template <class FIN>
 __device__ __forceinline__ void tail_wgrad(const float* g, int ldg, int nin, int nout, StageSplit sp, float* part, FIN in,
@@ -708,7 +692,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_tail_bwd(TailArgs a) {
     const int row0 = blockIdx.x * 16, rows = min(16, a.B - row0);
     const HeadFc F0 = a.fc[0], F1 = a.fc[1], F2 = a.fc[2];
 
-    TAIL_STAMP(0);
     // one burst of coalesced loads: this row group's g2; h1 / h0 / y rows, parked in the panel whose masked result they gate
     // (or, for the task whose weight gradient multiplies them, simply kept there); the weights of the links this task walks
     const int g4 = rows * (F2.nout >> 2), h14 = rows * (F1.nout >> 2), h04 = rows * (F0.nout >> 2), y4 = rows * (F0.nin >> 2);
@@ -727,7 +710,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_tail_bwd(TailArgs a) {
         kc[tid] = make_float4(mean, a.gamma[tid] * invstd, a.beta[tid], invstd);
     }
     __syncthreads();
-    TAIL_STAMP(1);
     float* g2 = lds + a.o_g2;
     float* g1 = lds + a.o_g1;
     float* g0 = lds + a.o_g0;
@@ -741,7 +723,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_tail_bwd(TailArgs a) {
     if (want_h0) tail_put(rh0, g0, h04, F0.nout >> 2, ld0);
     if (want_y) tail_put(ry, ys, y4, F0.nin >> 2, F0.nin);
     __syncthreads();
-    TAIL_STAMP(2);
 
     if (need1)
     {   // g1[b][i] = relu'(h1) sum_o g2[b][o] W2[o][i]      (decoder.py:31-35 backwards)
@@ -754,7 +735,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_tail_bwd(TailArgs a) {
                                    g1[m * ld1 + n] = v;
                                });
     }
-    TAIL_STAMP(3);
     if (need2) {   // g0[b][i] = relu'(h0) sum_o g1[b][o] W1[o][i]      (encoder.py:54-58 backwards)
         tail_put(rw1, Wb, a.w4[1], F1.nin >> 2, a.ldw[1]);
         __syncthreads();
@@ -767,7 +747,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_tail_bwd(TailArgs a) {
                                    g0[m * ld0 + n] = v;
                                });
     }
-    TAIL_STAMP(4);
     if (need3) {   // gx[b][i] = bnrelu'(y) sum_o g0[b][o] W0[o][i] -> global, and a dense LDS copy for the BatchNorm sums
         tail_put(rw0, Wb, a.w4[0], F0.nin >> 2, a.ldw[0]);
         __syncthreads();
@@ -785,7 +764,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_tail_bwd(TailArgs a) {
                                    gl[(size_t)m * nin + n] = gm;
                                    gxs[m * nin + n] = gm;
                                });
-        TAIL_STAMP(5);
         // this row group's share of dbeta = sum g and dgamma = sum g * xhat per channel (fp64, fixed order): up to 16 channels
         // at a time, 16 / channels waves each
         double* red = reinterpret_cast<double*>(lds + a.o_red);
@@ -832,7 +810,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_tail_bwd(TailArgs a) {
             }
             __syncthreads();
         }
-        TAIL_STAMP(6);
     }
     // this row group's share of one weight gradient; the multiplier rows are already in LDS
     if (task == 3) {
@@ -849,7 +826,6 @@ __global__ void __launch_bounds__(kHeadThreads) k_tail_bwd(TailArgs a) {
                    },
                    F0.w_acc, F0.b_acc);
     }
-    TAIL_STAMP(7);
 }
 
 }  // namespace cae

@@ -42,21 +42,17 @@ struct IgFwd {
     const float* bias;
     float* out;
     double* stats;  // [shards][Cout][4] or nullptr (eval)
-    long long* dbg; // diagnostics (tools/head_phases.py ig): 8 wall-clock stamps per workgroup of parity 0, or nullptr
 };
 
 // grid (ceil(Mtiles / (4*tiles_per_wave)), 4 parities, ceil(Cout/16)), block 256
 __global__ void __launch_bounds__(256) k_ig_fwd_s2(IgFwd a) {
-#define IG_STAMP(i) do { if (a.dbg && threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) a.dbg[blockIdx.x * 8 + (i)] = wall_clock64(); } while (0)
     extern __shared__ double lds_d[];
-    IG_STAMP(0);
     double* lstat = lds_d;                           // [16 channels][2], fp64: see the statistics epilogue
     float* part = reinterpret_cast<float*>(lds_d + 32);   // [4 waves][256] split-K partial tiles
     float4* cin4 = reinterpret_cast<float4*>(part + 1024);
     bn_consts(a.bn_in, cin4, blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0);
     if (threadIdx.x < 32) lstat[threadIdx.x] = 0.0;
     __syncthreads();
-    IG_STAMP(1);
 
     const int py = blockIdx.y >> 1, px = blockIdx.y & 1;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -96,7 +92,7 @@ __global__ void __launch_bounds__(256) k_ig_fwd_s2(IgFwd a) {
         const int iy = qm - j, ix = qn - i;
         a_ok = a_ok && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
         // Lean operand fetch: this phase is bound by instruction issue (16 waves per CU run ~700 instructions each around
-        // 16 MFMAs: tools/head_phases.py ig), so a load is `wave-uniform channel base + loop-invariant 32-bit lane offset`
+        // 16 MFMAs: DESIGN.md), so a load is `wave-uniform channel base + loop-invariant 32-bit lane offset`
         // (one instruction, no 64-bit lane arithmetic), issued unconditionally from an in-range address, and invalid lanes /
         // channels are zeroed by one select after the BatchNorm transform.
         const unsigned a_off = a_ok ? (unsigned)((b * a.Cin) * HW + iy * a.W + ix) : 0u;
@@ -169,7 +165,6 @@ __global__ void __launch_bounds__(256) k_ig_fwd_s2(IgFwd a) {
 #pragma unroll
             for (int u = 0; u < 8; u++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
         }
-        IG_STAMP(2);
         if (KS > 1) {   // combine the K slices of this M-tile in the slice-0 wave
             __syncthreads();
 #pragma unroll
@@ -205,7 +200,6 @@ __global__ void __launch_bounds__(256) k_ig_fwd_s2(IgFwd a) {
             }
         }
     }
-    IG_STAMP(3);
     if (a.stats) {
         // A lane's fp32 sums cover 4 * tiles_per_wave values; from there on fp64 (as k_ct_fwd_lds does).  Until round 3 the
         // fold over lane groups and waves ran in fp32 (64 * tiles_per_wave values per channel and workgroup): var = E[y^2] -
@@ -227,7 +221,6 @@ __global__ void __launch_bounds__(256) k_ig_fwd_s2(IgFwd a) {
                 acc_add<ACC_STAT>(&a.stats[((size_t)shard * a.Cout + c) * 4 + (threadIdx.x & 1)], lstat[threadIdx.x]);
             }
         }
-        IG_STAMP(4);
 }
 }
 
@@ -244,15 +237,12 @@ struct IgDgrad {
     const float* yprev;    // raw output of the producer (mask) or nullptr: plain store
     BnDesc bn_prev;        // BN_SAVED of the producer or BN_NONE
     double* stats_prev;    // [shards][Cin][4] slots 2,3
-    long long* dbg;        // diagnostics: 4 stamps per workgroup at dbg[(512 + bx) * 4 ..], or nullptr
 };
 
 // grid (ceil(Mtiles / (4*tiles_per_wave)), ceil(Cin/16)), block 256; LDS: see host
 constexpr int kIgdSteps = 9;
 
 __device__ __forceinline__ void ig_dgrad_body(const IgDgrad& a, const int bx, const int by, double* lds_d) {
-#define IGD_STAMP(i) do { if (a.dbg && threadIdx.x == 0 && by == 0 && bx < 256) a.dbg[(512 + bx) * 4 + (i)] = wall_clock64(); } while (0)
-    IGD_STAMP(0);
     const int K = a.Cout * a.KH * a.KW;
     float* lstat = reinterpret_cast<float*>(lds_d);               // [4 waves][16][2]: one writer per slot, folded in wave order
     float* part = lstat + 128;                                    // [4][256] split-K partial tiles
@@ -268,7 +258,6 @@ __device__ __forceinline__ void ig_dgrad_body(const IgDgrad& a, const int bx, co
     }
     if (threadIdx.x < 128) lstat[threadIdx.x] = 0.f;
     __syncthreads();
-    IGD_STAMP(1);
 
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = lane & 15, q = lane >> 4;
@@ -370,7 +359,6 @@ __device__ __forceinline__ void ig_dgrad_body(const IgDgrad& a, const int bx, co
 #pragma unroll
             for (int u = 0; u < kIgdSteps; u++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
         }
-        IGD_STAMP(2);
         // the epilogue inputs are waited for here, once, outside the predicated stores below (left to their first use inside
         // a predicated block, the wait is repeated per block and, the memory counter retiring in order, becomes a wait for
         // the previous block's store to complete: four store round trips one after the other)
@@ -435,7 +423,6 @@ __device__ __forceinline__ void ig_dgrad_body(const IgDgrad& a, const int bx, co
             }
         }
     }
-    IGD_STAMP(3);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -449,14 +436,11 @@ struct IgWgrad {
     BnDesc bn_out;         // BN_BWD or BN_NONE
     double* wacc;          // (Cin, Cout*KH*KW) fp64 accumulator
     BnGradOut bg;
-    long long* dbg;        // diagnostics: 4 stamps per workgroup at dbg[(by * tiles + bx) * 4 ..] for the first 512, or nullptr
 };
 
 // grid (Mtiles*Ntiles, K chunks), block 256: the 4 waves split the chunk, LDS combine, fp64 atomics
 __device__ __forceinline__ void ig_wgrad_body(const IgWgrad& a, const int bx, const int by, double* lds_d) {
-#define IGW_STAMP(i) do { if (a.dbg && threadIdx.x == 0 && wslot < 512) a.dbg[wslot * 4 + (i)] = wall_clock64(); } while (0)
     const int wslot = by * (((a.Cin + 15) >> 4) * ((a.Cout * a.KH * a.KW + 15) >> 4)) + bx;
-    IGW_STAMP(0);
     float* part = reinterpret_cast<float*>(lds_d);            // [4][256]
     float4* cin4 = reinterpret_cast<float4*>(part + 1024);    // [Cin]
     float4* cout4 = cin4 + a.Cin;                             // [Cout]
@@ -474,7 +458,6 @@ __device__ __forceinline__ void ig_wgrad_body(const IgWgrad& a, const int bx, co
         }
     }
     __syncthreads();
-    IGW_STAMP(1);
 
     const int khw = a.KH * a.KW;
     const int N = a.Cout * khw;
@@ -539,16 +522,12 @@ __device__ __forceinline__ void ig_wgrad_body(const IgWgrad& a, const int bx, co
 #pragma unroll
         for (int u = 0; u < 8; u++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
     }
-    IGW_STAMP(2);
 #pragma unroll
     for (int j = 0; j < 4; j++) part[wv * 256 + j * 64 + lane] = acc[j];
     __syncthreads();
     if (wv != 0) return;
     const int cn = tn * 16 + r;
-    if (cn >= N) {
-        IGW_STAMP(3);
-        return;
-    }
+    if (cn >= N) return;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const int cm = tm * 16 + q * 4 + j;
@@ -556,7 +535,6 @@ __device__ __forceinline__ void ig_wgrad_body(const IgWgrad& a, const int bx, co
         const float v = part[j * 64 + lane] + part[256 + j * 64 + lane] + part[512 + j * 64 + lane] + part[768 + j * 64 + lane];
         acc_add<ACC_GRAD>(&a.wacc[(size_t)cm * N + cn], (double)v);
     }
-    IGW_STAMP(3);
 }
 
 __global__ void __launch_bounds__(256) k_ig_dgrad(IgDgrad a) {

@@ -60,7 +60,6 @@ struct S2Last {
     int acc_stride;
     float* gin;              // (B, CIN, H, W) gradient wrt the producer's raw output side (masked by its ReLU)
     double* stats_in;        // producer's [kStatShards][CIN][4] sums (slots 2, 3) or nullptr
-    long long* dbg;          // diagnostics (tools/last_phases.py): 8 wall-clock stamps per workgroup (first 384), or nullptr
 };
 
 constexpr int kLastStripPx = 127;   // pixel columns a strip owns (it computes 128 quad columns)
@@ -116,10 +115,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     __shared__ __attribute__((aligned(16))) float wscr[4 * kWsumScratch];
     __shared__ float xch[4 * CIN * 2 * 64];      // first-row shares of the four bands of a workgroup
 
-#define LF_STAMP(i) do { if (a.dbg && threadIdx.x == 0 && blockIdx.x < 384) a.dbg[blockIdx.x * 8 + (i)] = wall_clock64(); } while (0)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    LF_STAMP(0);
     const unsigned HW = a.H * a.W, OHW = a.OH * a.OW;
 
     // ---- this wave's band
@@ -236,7 +233,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
     }
-    LF_STAMP(1);
 #pragma unroll
     for (int i = 0; i < NACC; i++) wk[i] = uniform_f(wk[i]);
 #pragma unroll
@@ -272,7 +268,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
         }
     }
 
-    LF_STAMP(2);
     float dw[NACC];
 #pragma unroll
     for (int i = 0; i < NACC; i++) dw[i] = 0.f;
@@ -456,7 +451,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
             }
             }
             if constexpr (r == 0) {
-                LF_STAMP(3);
                 // every wave, working or not: the first row's j = 1 shares go up one band through LDS
 #pragma unroll
                 for (int ci = 0; ci < CIN; ci++) {
@@ -493,7 +487,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
         }
     }
 
-    LF_STAMP(4);
     // ---- reductions: wave (through LDS), workgroup (LDS), then one fp64 atomic per value
     {
         float red[NRED];
@@ -535,11 +528,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
             else acc_add<ACC_GRAD>(&a.bias_acc[(size_t)shard * a.acc_stride + co], s);
         }
     }
-    LF_STAMP(5);
     // keeps the permutation value's register its own to the end: were it reused, every write to it would wait for the
     // load that may be pending on it (and, the counter being in order, for the BatchNorm sums and weights ahead of it)
     asm volatile("" :: "v"(perm_val_v));
-#undef LF_STAMP
 }
 
 }  // namespace cae

@@ -35,7 +35,6 @@ struct S2Rows {
     double* wacc;            // sharded [kStatShards][wacc_stride]
     int wacc_stride;
     BnGradOut bg;            // this layer's BatchNorm parameter gradients (published by workgroup 0)
-    long long* dbg;          // diagnostics (tools/last_phases.py rows): 8 wall-clock stamps per workgroup (first 384), or nullptr
 };
 
 // CT input channels per wave (CS = CIN / CT channel groups = waves sharing a band), IMGS images side by side in a wave
@@ -58,10 +57,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     // BatchNorm constants; read back as wave-wide broadcasts where they are used)
     __shared__ __attribute__((aligned(16))) float wl[CIN * COUT * 12];
 
-#define RW_STAMP(i) do { if (a.dbg && threadIdx.x == 0 && blockIdx.x < 384) a.dbg[blockIdx.x * 8 + (i)] = wall_clock64(); } while (0)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    RW_STAMP(0);
     const int cgrp = wv % CS, bsel = wv / CS;            // channel group, band inside the workgroup
     const int c0 = cgrp * CT;
     const int sub = lane / LW, n = lane - sub * LW;      // image inside the wave, quad column = pixel column
@@ -151,7 +148,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
         load_g(R);
     });
     __builtin_amdgcn_sched_barrier(0);
-    RW_STAMP(1);
     {   // the constants, now that the rows are on their way
         sa += dpp_d<0xB1>(sa); sb += dpp_d<0xB1>(sb);
         sa += dpp_d<0x4E>(sa); sb += dpp_d<0x4E>(sb);
@@ -185,7 +181,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
         }
     }
     __syncthreads();         // wl is complete
-    RW_STAMP(2);
 
     float dw[NACC];
 #pragma unroll
@@ -299,7 +294,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
                 actP[c][1] = actN[c][1];
             }
         }
-        if constexpr (r == 0) RW_STAMP(3);
         if constexpr (r == 0 && NB > 1) {
             // bands of one workgroup: the first row's j = 1 shares go up one band through LDS
 #pragma unroll
@@ -327,7 +321,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
         }
     }
 
-    RW_STAMP(4);
     // ---- reductions: wave (through LDS), workgroup (LDS; channel groups keep their own sums), then one fp64 atomic per value
     {
         float red[NRED];
@@ -354,8 +347,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
             acc_add<ACC_GRAD>(&a.stats_in[((size_t)shard * CIN + gsel * CT + (jj >> 1)) * 4 + 2 + (jj & 1)], s);
         }
     }
-    RW_STAMP(5);
-#undef RW_STAMP
 }
 
 }  // namespace cae

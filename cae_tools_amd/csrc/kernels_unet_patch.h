@@ -493,8 +493,7 @@ inline int pwgrad_tpw(const Geom& g) {
     const int rows = g.Cs >= 128 ? 128 : 64;
     const long long tiles_out = (long long)(g.Cl / 8) * ((g.Cs + rows - 1) / rows);
     const int total = g.B * pwgrad_shape(g).tiles;
-    static const int target = getenv("CAE_PWGRAD_WGS") ? atoi(getenv("CAE_PWGRAD_WGS")) : 512;   // env: tuning runs only
-    long long want = (target + tiles_out - 1) / tiles_out;    // slices to aim at: two resident workgroups per CU
+    long long want = (512 + tiles_out - 1) / tiles_out;    // slices to aim at (512 workgroups): two resident workgroups per CU
     if (want < 1) want = 1;
     int tpw = (int)((total + want - 1) / want);
     if (tpw < 2) tpw = 2;

@@ -217,12 +217,7 @@ __global__ void __launch_bounds__(256) k_thin_fold(const float* __restrict__ par
     }
 }
 
-inline int thin_wgrad_tpw(const Geom& g) {
-    static const int tpw_env = getenv("CAE_THIN_TPW") ? atoi(getenv("CAE_THIN_TPW")) : 0;   // env: tuning runs only
-    const int tiles = thin_shape(g).tiles;
-    const int tpw = tpw_env > 0 ? tpw_env : 8;
-    return tpw > tiles ? tiles : tpw;
-}
+inline int thin_wgrad_tpw(const Geom& g) { return std::min(8, thin_shape(g).tiles); }
 inline int thin_wgrad_groups(const Geom& g) {
     const int tpw = thin_wgrad_tpw(g);
     return (thin_shape(g).tiles + tpw - 1) / tpw;
@@ -343,12 +338,7 @@ __global__ void __launch_bounds__(256) k_thin_down(Geom g, const float* __restri
     }
 }
 
-inline int thin_down_tpw(const Geom& g) {
-    static const int tpw_env = getenv("CAE_THIN_DOWN_TPW") ? atoi(getenv("CAE_THIN_DOWN_TPW")) : 0;   // env: tuning runs only
-    const int tiles = thin_shape(g).tiles;
-    const int tpw = tpw_env > 0 ? tpw_env : 8;
-    return tpw > tiles ? tiles : tpw;
-}
+inline int thin_down_tpw(const Geom& g) { return std::min(8, thin_shape(g).tiles); }
 template <int RBN>
 inline void thin_down_launch_cl(const Geom& g, const float* L, const float* w, const float* bias, float* S, hipStream_t s) {
     const ThinShape sh = thin_shape(g);
@@ -458,20 +448,14 @@ inline bool thin_up_geom(const Geom& g) {
 }
 // wq: the layer's weights in k_thin_up's order (k_pack_up_weights, thin entry)
 inline void thin_up_launch(const Geom& g, const float* S, const float* wq, const float* bias, float* L, hipStream_t s) {
-    static const int t_env = getenv("CAE_THIN_UP_T") ? atoi(getenv("CAE_THIN_UP_T")) : 2;   // env: tuning runs only
-    const int T = (t_env == 4 && g.Hs % 4 == 0) ? 4 : 2;
-    const int waves = g.B * (g.Hs / T);
+    const int waves = g.B * (g.Hs / 2);
     const dim3 grid((waves + 3) / 4);
-#define THIN_UP_CASE(CL_)                                                                                       \
-    if (T == 4) hipLaunchKernelGGL((k_thin_up<CL_, 4>), grid, dim3(256), 0, s, g, S, wq, bias, L);              \
-    else hipLaunchKernelGGL((k_thin_up<CL_, 2>), grid, dim3(256), 0, s, g, S, wq, bias, L)
     switch (g.Cl) {
-        case 1: THIN_UP_CASE(1); break;
-        case 2: THIN_UP_CASE(2); break;
-        case 3: THIN_UP_CASE(3); break;
-        default: THIN_UP_CASE(4); break;
+        case 1: hipLaunchKernelGGL((k_thin_up<1, 2>), grid, dim3(256), 0, s, g, S, wq, bias, L); break;
+        case 2: hipLaunchKernelGGL((k_thin_up<2, 2>), grid, dim3(256), 0, s, g, S, wq, bias, L); break;
+        case 3: hipLaunchKernelGGL((k_thin_up<3, 2>), grid, dim3(256), 0, s, g, S, wq, bias, L); break;
+        default: hipLaunchKernelGGL((k_thin_up<4, 2>), grid, dim3(256), 0, s, g, S, wq, bias, L); break;
     }
-#undef THIN_UP_CASE
 }
 
 }  // namespace

@@ -144,35 +144,28 @@ const char* const kWgradName[] = {"thin", "thin_atomic", "patch", "mfma", "mfma_
 const char* const kLinName[] = {"lin_big", "gemm16", "tile", "generic"};
 
 DownK choose_down(const unet_engine* e, const Geom& g) {
-    static const int thin_off = env_int("CAE_UNET_THIN", 1) == 0;     // env: A/B measurements only
-    static const int patch_off = env_int("CAE_UNET_PATCH", 1) == 0;   // env: A/B measurements only
-    if (e->specialised && !thin_off && thin_geom(g)) return DOWN_THIN;       // the image-end layers: kernels_unet_thin.h
-    if (e->specialised && !patch_off && patch_geom(g)) return DOWN_PATCH;    // the wide layers: kernels_unet_patch.h
+    if (e->specialised && thin_geom(g)) return DOWN_THIN;       // the image-end layers: kernels_unet_thin.h
+    if (e->specialised && patch_geom(g)) return DOWN_PATCH;     // the wide layers: kernels_unet_patch.h
     if (e->specialised && mfma_down_eligible(g)) return DOWN_MFMA;
     return DOWN_GENERIC;
 }
 
 // has_wp: the layer has repacked weights (pack_up_weights below); the thin, patch and tile-engine kernels read only those
 UpK choose_up(const unet_engine* e, const Geom& g, bool has_wp) {
-    static const int thin_off = env_int("CAE_UNET_THIN", 1) == 0;     // env: A/B measurements only
-    static const int patch_off = env_int("CAE_UNET_PATCH", 1) == 0;   // env: A/B measurements only
-    if (e->specialised && !thin_off && has_wp && thin_up_geom(g)) return UP_THIN;   // ... 128 columns wide: kernels_unet_thin.h
+    if (e->specialised && has_wp && thin_up_geom(g)) return UP_THIN;   // ... 128 columns wide: kernels_unet_thin.h
     if (e->specialised && mfma_geom(g) && g.Cl <= 4) return UP_THIN_CL;   // a handful of output channels: streaming, not a GEMM
-    if (e->specialised && !patch_off && has_wp && g.Cl > 4 && pup_geom(g)) return UP_PATCH;   // the wide layers
+    if (e->specialised && has_wp && g.Cl > 4 && pup_geom(g)) return UP_PATCH;   // the wide layers
     if (e->specialised && has_wp && mfma_up_eligible(g)) return UP_MFMA;
     return UP_GENERIC;
 }
 
 WgradK choose_wgrad(const unet_engine* e, const Geom& g) {
-    static const int thin_off = env_int("CAE_UNET_THIN", 1) == 0;     // env: A/B measurements only
-    static const int patch_off = env_int("CAE_UNET_PATCH", 1) == 0;   // env: A/B measurements only
-    static const int part_off = env_int("CAE_UNET_WGPART", 1) == 0;   // env: A/B measurements only
-    if (e->specialised && !thin_off && thin_geom(g))   // the image-end layers: kernels_unet_thin.h
+    if (e->specialised && thin_geom(g))   // the image-end layers: kernels_unet_thin.h
         return thin_wgrad_part_bytes(g) <= (size_t)e->thinpart_bytes ? WG_THIN : WG_THIN_ATOMIC;
-    if (e->specialised && !patch_off && pwgrad_geom(g) && pwgrad_part_bytes(g) <= (size_t)e->thinpart_bytes) return WG_PATCH;
+    if (e->specialised && pwgrad_geom(g) && pwgrad_part_bytes(g) <= (size_t)e->thinpart_bytes) return WG_PATCH;
     if (e->specialised && mfma_wgrad_eligible(g)) {
         const size_t need = mfma_wgrad_part_bytes(g);
-        return (!part_off && need && need <= (size_t)e->thinpart_bytes) ? WG_MFMA : WG_MFMA_ATOMIC;
+        return (need && need <= (size_t)e->thinpart_bytes) ? WG_MFMA : WG_MFMA_ATOMIC;
     }
     return WG_GENERIC;
 }
@@ -229,10 +222,11 @@ void conv_wgrad(unet_engine* e, const Geom& g, const float* S, const float* L, d
 
 // kernels that end in a workgroup-wide sum + atomics: fewer, longer workgroups (the sum's two barriers and the atomics are a
 // fixed 2-3 us; at 128 chunks a workgroup of the 128 x 128 maps had four loop trips of work in front of them)
+constexpr int kRedWgs = 1280;
+
 dim3 red_grid(int B, int C, int HW) {
-    static const int target = env_int("CAE_UNET_REDWGS", 1280);   // env: tuning runs only
     int chunks = (int)(((long long)B * HW + 256 * 4 - 1) / (256 * 4));
-    const int want = std::max(4, target / std::max(1, C));     // about `target` workgroups over the C channels
+    const int want = std::max(4, kRedWgs / std::max(1, C));     // about kRedWgs workgroups over the C channels
     if (chunks > want) chunks = want;
     if (chunks < 1) chunks = 1;
     return dim3(chunks, C);
@@ -294,8 +288,6 @@ ugemm::cae::GemmArgs gemm16_args(int M, int N, int K) {
 // the big layers on kernels_unet_lin.h: batch <= 64, 16-byte rows, room for the K slices' partial tiles
 bool lin_big(const unet_engine* e, const Fc& L, int B) {
     if (!e->specialised || small_fc(L) || B > 64 || (L.nin & 3) || (L.nout & 3)) return false;
-    static const int off = env_int("CAE_UNET_LIN", 1) == 0;   // env: A/B measurements only
-    if (off) return false;
     const long long need = (long long)std::max((L.nin + 127) / 128 * (long long)L.nout, (L.nout + 127) / 128 * (long long)L.nin) * B * 4;
     return need <= e->linpart_bytes;
 }
@@ -535,8 +527,7 @@ int loss_forward(unet_engine* e, int which, const int32_t* perm, int64_t start, 
     HIP_TRY(hipMemsetAsync(ls, 0, (size_t)B * C * 8 * sizeof(double), e->stream));
     const LossSrc src = loss_src(e, which, perm, start);
     // (seven workgroup-wide fp64 sums end every workgroup: about 768 of them, each a long slice of its plane)
-    static const int ls_wgs = env_int("CAE_UNET_LSWGS", 768);   // env: tuning runs only
-    int chunks = std::max(1, std::min(32, ls_wgs / std::max(1, B * C)));
+    int chunks = std::max(1, std::min(32, 768 / std::max(1, B * C)));
     chunks = std::min(chunks, (HW + 1023) / 1024);
     hipLaunchKernelGGL(k_loss_sums, dim3(chunks, B * C), dim3(256), 0, e->stream, e->f(L.u), 1, src, C, HW, ls);
     hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(256), 0, e->stream, ls, B, C, src.Cm, src.mask ? 1 : 0, e->lambda_p,

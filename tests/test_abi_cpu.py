@@ -2,6 +2,7 @@
 and its geometry-only entry points agree with the reference-generated fixtures.  No compute calls."""
 import os
 import re
+import struct
 
 import numpy as np
 import pytest
@@ -11,6 +12,26 @@ from cae_tools_amd import _lib
 from cae_tools_amd.engine import EnginePlan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _undefined_dynamic_symbols(path):
+    """Names of the undefined symbols in an ELF64 little-endian shared object's .dynsym (what `nm -D --undefined-only` lists)."""
+    with open(path, "rb") as f:
+        elf = f.read()
+    assert elf[:6] == b"\x7fELF\x02\x01", path
+    shoff, = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", elf, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", elf, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for (_, sh_type, _, _, offset, size, link, _, _, entsize) in sections:
+        if sh_type != 11:   # SHT_DYNSYM
+            continue
+        stroff = sections[link][4]
+        for at in range(offset + entsize, offset + size, entsize):   # entry 0 is the null symbol
+            st_name, _, _, st_shndx = struct.unpack_from("<IBBH", elf, at)
+            if st_shndx == 0:   # SHN_UNDEF
+                names.add(elf[stroff + st_name:elf.index(b"\0", stroff + st_name)].decode().split("@")[0])
+    return names
 
 
 def test_library_exports_every_declared_symbol():
@@ -27,6 +48,10 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"libcae_hip.so does not export {name}"
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
     assert lib.cae_abi_version() == 1
+    # what the library computes depends on its arguments alone, never on the environment
+    undefined = _undefined_dynamic_symbols(_lib.LIB_PATH)
+    assert "hipLaunchKernel" in undefined, sorted(undefined)   # the table was read
+    assert "getenv" not in undefined
 
 
 @pytest.mark.parametrize("name", MODEL_CASES)
