@@ -110,6 +110,9 @@ SIGNATURES = {
     "unet_forward_backward": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_double]),
     "unet_apply_gradients": (C.c_int, [_P, _P]),
     "unet_eval_step": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int]),
+    "unet_forward_backward_sync": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                             ALLREDUCE_FN, _P]),
+    "unet_eval_step_sync": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, ALLREDUCE_FN, _P]),
     "unet_score": (C.c_int, [_P, _P, C.c_int, _P]),
     "unet_loss_slots": (C.c_int, [_P]),
     "unet_read_losses": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_double)]),

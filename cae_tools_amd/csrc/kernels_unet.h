@@ -71,10 +71,12 @@ struct Drop {
     uint32_t thr;   // keep iff hash >= thr
     float scale;    // 1 / (1 - p)
     int on;
+    unsigned long long base;   // added to every element index: a data-parallel shard's first row x the site's elements per sample
 };
 
 __device__ __forceinline__ float drop_factor(const Drop& d, unsigned long long idx) {
     if (!d.on) return 1.f;
+    idx += d.base;
     const uint32_t hi = pcg(d.key + (uint32_t)(idx >> 32));
     const uint32_t r = pcg((uint32_t)idx ^ hi);
     return r >= d.thr ? d.scale : 0.f;
@@ -469,7 +471,8 @@ __global__ void __launch_bounds__(256) k_bn_bwd_reduce(const float* __restrict__
 }
 
 // backward, pass 2 from the operands of pass 1: dz = gamma*invstd*(g - sum_g/N - xhat*sum_gx/N) with g formed as there;
-// block x == 0 also adds dgamma = sum g*xhat, dbeta = sum g to the gradient accumulator.  grid (chunks, C)
+// block x == 0 also adds dgamma = sum g*xhat, dbeta = sum g to the gradient accumulator (acc_gamma nullptr: k_bn_grad_local
+// did, before the sums were all-reduced).  grid (chunks, C)
 __global__ void __launch_bounds__(256) k_bn_bwd_apply2(const float* __restrict__ gA, long long gAbs, const float* __restrict__ gB,
                                                        long long gBbs, const float* __restrict__ z, long long zbs, int B, int C,
                                                        int HW, const float* __restrict__ saved, const float* __restrict__ gamma,
@@ -481,7 +484,7 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply2(const float* __restrict__
     const float ga = gamma[c], be = beta[c];
     const float k1 = ga * invstd, sc = invstd * ga;
     const float m1 = (float)(sums[2 * c] / N), m2 = (float)(sums[2 * c + 1] / N);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (acc_gamma && blockIdx.x == 0 && threadIdx.x == 0) {
         acc_gamma[c] += sums[2 * c + 1];
         acc_beta[c] += sums[2 * c];
     }
@@ -527,7 +530,7 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply2_planes(const float* __res
     const float ga = gamma[c], be = beta[c];
     const float k1 = ga * invstd, sc = invstd * ga;
     const float m1 = (float)(sums[2 * c] / N), m2 = (float)(sums[2 * c + 1] / N);
-    if (b == 0 && threadIdx.x == 0) {
+    if (acc_gamma && b == 0 && threadIdx.x == 0) {
         acc_gamma[c] += sums[2 * c + 1];
         acc_beta[c] += sums[2 * c];
     }
@@ -560,6 +563,17 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply2_planes(const float* __res
     if (gated) {
         const double t = block_sum(s, red);
         if (threadIdx.x == 0) da[(size_t)b * zc.Ch + c] = (float)t;
+    }
+}
+
+// a data-parallel shard's own dgamma = sum g*xhat, dbeta = sum g, taken from the pass-1 sums before they are all-reduced (the
+// caller's SUM over the ranks' gradients then gives the global ones).  grid (ceil(C / 256))
+__global__ void __launch_bounds__(256) k_bn_grad_local(const double* __restrict__ sums, int C, double* __restrict__ acc_gamma,
+                                                       double* __restrict__ acc_beta) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < C) {
+        acc_gamma[c] += sums[2 * c + 1];
+        acc_beta[c] += sums[2 * c];
     }
 }
 
@@ -896,53 +910,90 @@ __global__ void __launch_bounds__(256) k_loss_sums(const float* __restrict__ u, 
     }
 }
 
-// one block: loss values out2 = {mse, 1 - mean r} and the gradient coefficients coef[bc] = {k0, k1, k2, k3}:
-//   dL/dp = m*(k0 + k1*t + k2*p) + k3*m^2*(p - t)
+// Pearson r of one (b, c) plane from its sums s[0..5] (k_loss_sums) and, when coef4 is given, its gradient coefficients
+// {k0, k1, k2, k3}:  dL/dp = m*(k0 + k1*t + k2*p) + k3*m^2*(p - t);  kappa = -lambda / (number of planes), k3 = 2 / sum m
+__device__ __forceinline__ double loss_plane(const double* s, double kappa, double k3, float* coef4) {
+    const double n = s[0], np = n + 1e-8;
+    const double mup = s[1] / np, mut = s[2] / np;
+    const double vp = (s[3] - 2 * mup * s[1] + mup * mup * n) / np + 1e-8;
+    const double vt = (s[4] - 2 * mut * s[2] + mut * mut * n) / np + 1e-8;
+    const double sp = sqrt(vp), st = sqrt(vt);
+    const double A = s[5] - mup * s[2] - mut * s[1] + mup * mut * n;
+    const double r = A / (sp * st) / n;
+    if (coef4) {
+        const double q = 1.0 / (sp * st * n);
+        const double Sp = s[1] - mup * n, St = s[2] - mut * n;   // sum m (p - mup), sum m (t - mut)
+        const double e1 = q;
+        const double e2 = -q * A / (vp * np);
+        const double e0 = q * (-mut - St / np) + e2 * (-mup - Sp / np);
+        coef4[0] = (float)(kappa * e0);
+        coef4[1] = (float)(kappa * e1);
+        coef4[2] = (float)(kappa * e2);
+        coef4[3] = (float)k3;
+    }
+    return r;
+}
+
+// the batch totals {sum m, sum (m (p - t))^2} of the per-plane sums (torch.sum(mask) counts the mask tensor as stored)
+__device__ __forceinline__ void loss_totals(const double* __restrict__ ls, int B, int C, int Cm, int has_mask, double& mtot,
+                                            double& sq) {
+    mtot = 0, sq = 0;
+    for (int bc = threadIdx.x; bc < B * C; bc += 256) {
+        const double* s = ls + (size_t)bc * 8;
+        const int c = bc % C;
+        if (!has_mask || Cm == C || c == 0) mtot += s[0];
+        sq += s[6];
+    }
+}
+
+// one block: loss values out2 = {mse, 1 - mean r} and the gradient coefficients coef[bc] (loss_plane)
 __global__ void __launch_bounds__(256) k_loss_finalize(const double* __restrict__ ls, int B, int C, int Cm, int has_mask,
                                                        double lambda_p, double* __restrict__ out2,
                                                        float* __restrict__ coef) {
     __shared__ double red[4];
     const int n_bc = B * C;
-    double mtot = 0, sq = 0, rsum = 0;
-    for (int bc = threadIdx.x; bc < n_bc; bc += 256) {
-        const double* s = ls + (size_t)bc * 8;
-        const int c = bc % C;
-        if (!has_mask || Cm == C || c == 0) mtot += s[0];   // torch.sum(mask) counts the mask tensor as stored
-        sq += s[6];
-    }
+    double mtot, sq, rsum = 0;
+    loss_totals(ls, B, C, Cm, has_mask, mtot, sq);
     mtot = block_sum(mtot, red);
     __shared__ double sh_m;
     if (threadIdx.x == 0) sh_m = mtot;
     __syncthreads();
     mtot = sh_m;
     sq = block_sum(sq, red);
-    for (int bc = threadIdx.x; bc < n_bc; bc += 256) {
-        const double* s = ls + (size_t)bc * 8;
-        const double n = s[0], np = n + 1e-8;
-        const double mup = s[1] / np, mut = s[2] / np;
-        const double vp = (s[3] - 2 * mup * s[1] + mup * mup * n) / np + 1e-8;
-        const double vt = (s[4] - 2 * mut * s[2] + mut * mut * n) / np + 1e-8;
-        const double sp = sqrt(vp), st = sqrt(vt);
-        const double A = s[5] - mup * s[2] - mut * s[1] + mup * mut * n;
-        const double r = A / (sp * st) / n;
-        rsum += r;
-        if (coef) {
-            const double kappa = -lambda_p / (double)n_bc;
-            const double q = 1.0 / (sp * st * n);
-            const double Sp = s[1] - mup * n, St = s[2] - mut * n;   // sum m (p - mup), sum m (t - mut)
-            const double e1 = q;
-            const double e2 = -q * A / (vp * np);
-            const double e0 = q * (-mut - St / np) + e2 * (-mup - Sp / np);
-            coef[4 * bc + 0] = (float)(kappa * e0);
-            coef[4 * bc + 1] = (float)(kappa * e1);
-            coef[4 * bc + 2] = (float)(kappa * e2);
-            coef[4 * bc + 3] = (float)(2.0 / mtot);
-        }
-    }
+    for (int bc = threadIdx.x; bc < n_bc; bc += 256)
+        rsum += loss_plane(ls + (size_t)bc * 8, -lambda_p / (double)n_bc, 2.0 / mtot, coef ? coef + 4 * bc : nullptr);
     rsum = block_sum(rsum, red);
     if (threadIdx.x == 0) {
         out2[0] = sq / mtot;
         out2[1] = 1.0 - rsum / (double)n_bc;
+    }
+}
+
+// k_loss_finalize split for a data-parallel shard.  Reduce: tot = {sum m, sum (m (p - t))^2, sum r} over this shard's planes
+// (B = 0: zeros), for the caller to sum over the ranks.  one block
+__global__ void __launch_bounds__(256) k_loss_reduce(const double* __restrict__ ls, int B, int C, int Cm, int has_mask,
+                                                     double* __restrict__ tot) {
+    __shared__ double red[4];
+    double mtot, sq, rsum = 0;
+    loss_totals(ls, B, C, Cm, has_mask, mtot, sq);
+    for (int bc = threadIdx.x; bc < B * C; bc += 256) rsum += loss_plane(ls + (size_t)bc * 8, 0.0, 0.0, nullptr);
+    mtot = block_sum(mtot, red);
+    sq = block_sum(sq, red);
+    rsum = block_sum(rsum, red);
+    if (threadIdx.x == 0) tot[0] = mtot, tot[1] = sq, tot[2] = rsum;
+}
+
+// ... finalize from the all-reduced totals and the global plane count n_bc: the loss values (the same on every rank) and this
+// shard's coefficients (coef nullptr: not wanted).  r and the per-plane terms are the plane's own; only the totals are global.
+// one block
+__global__ void __launch_bounds__(256) k_loss_finalize_global(const double* __restrict__ ls, int B, int C,
+                                                              const double* __restrict__ tot, double n_bc, double lambda_p,
+                                                              double* __restrict__ out2, float* __restrict__ coef) {
+    if (coef)
+        for (int bc = threadIdx.x; bc < B * C; bc += 256) loss_plane(ls + (size_t)bc * 8, -lambda_p / n_bc, 2.0 / tot[0], coef + 4 * bc);
+    if (threadIdx.x == 0) {
+        out2[0] = tot[1] / tot[0];
+        out2[1] = 1.0 - tot[2] / n_bc;
     }
 }
 

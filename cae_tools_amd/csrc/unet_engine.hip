@@ -100,6 +100,14 @@ struct unet_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets,
     uint32_t seed = 0;
     int specialised = 1;
     bool gacc_clean = false;   // the fp64 gradient accumulator is all zero (k_adamw clears what it consumes) but for fc_f32_dirty
+    int64_t off_ltot = 0;      // dsum offset of the loss totals {sum mask, sum squared error, sum r} of a data-parallel shard
+    // the data-parallel shard of the current unet_*_sync call (ShardScope); a plain step leaves them at their defaults
+    int64_t row0 = 0;          // the shard's first row in the global batch: dropout hashes global element indices
+    int stat_batch = 0;        // rows behind the BatchNorm statistics (the global batch under SyncBN); 0: the local batch
+    int loss_batch = 0;        // rows behind the loss means (the global batch); 0: the local batch
+    cae_allreduce_fn sync_fn = nullptr;   // sums a table over the ranks (nullptr: no data parallelism)
+    void* sync_user = nullptr;
+    bool sync_bn = false;      // BatchNorm sum tables go through sync_fn too
 
     float* f(int64_t off) const { return reinterpret_cast<float*>(ws + off_f32) + off; }
     double* dsum(int64_t off) const { return reinterpret_cast<double*>(ws + off_dsum) + off; }
@@ -118,10 +126,12 @@ void add_bn(unet_engine* e, const std::string& key, int C, Bn& bn) {
     bn.rvar = e->tab.add(key + ".running_var", 1, {C});
 }
 
-Drop make_drop(const unet_engine* e, uint32_t site, bool train) {
-    Drop d{0, 0, 1.f, 0};
+// per_sample: the site's elements per sample (a shard's masks are those of its rows in the global batch)
+Drop make_drop(const unet_engine* e, uint32_t site, bool train, int64_t per_sample) {
+    Drop d{0, 0, 1.f, 0, 0};
     if (!train || e->dropout <= 0.0) return d;
     d.on = 1;
+    d.base = (unsigned long long)(e->row0 * per_sample);
     const uint32_t k = pcg(e->seed + 0x9E3779B9u * site);
     d.key = pcg(k ^ (uint32_t)(e->step & 0xFFFFFFFF));
     double t = e->dropout * 4294967296.0;
@@ -251,24 +261,47 @@ void bn_stats(unet_engine* e, const Bn& bn, const float* x, long long bs, int B,
 
 const ZCat kNoCat{nullptr, nullptr, nullptr, 0};
 
+// values per channel behind a BatchNorm's statistics
+double bn_count(const unet_engine* e, int B, int HW) { return (double)(e->stat_batch ? e->stat_batch : B) * HW; }
+
+// a completed sum table (`count` doubles) to the caller's all-reduce, when this is a data-parallel call that sums it
+int sync_table(unet_engine* e, double* table, int64_t count, bool bn = true) {
+    if (!e->sync_fn || (bn && !e->sync_bn)) return CAE_OK;
+    if (e->sync_fn(e->sync_user, table, count) != 0) return fail(CAE_ERR_STATE, "unet: the all-reduce callback failed");
+    return CAE_OK;
+}
+
 // skip_sums: where the sums of the ReLU output go (the skip half of a decoder layer's BatchNorm statistics), or nullptr
 void bn_act(unet_engine* e, const Bn& bn, const float* z, long long zbs, int B, int HW, bool train, Drop d, float* s_out,
             float* a_out, const ZCat& zc = kNoCat, double* skip_sums = nullptr) {
     // (with sums to leave, fewer and longer workgroups: red_grid)
     hipLaunchKernelGGL(k_bn_act, skip_sums ? red_grid(B, bn.C, HW) : ew_grid(B, bn.C, HW), dim3(256), 0, e->stream, z, zbs, B, bn.C, HW,
-                       e->f(bn.saved), e->Bf(bn.rmean), e->Bf(bn.rvar), kEps, train ? 2 : 1, e->dsum(bn.sums), (double)B * HW, kMomentum,
+                       e->f(bn.saved), e->Bf(bn.rmean), e->Bf(bn.rvar), kEps, train ? 2 : 1, e->dsum(bn.sums), bn_count(e, B, HW), kMomentum,
                        e->P(bn.gamma), e->P(bn.beta), d, s_out, a_out, zc, skip_sums);
 }
 
-void bn_backward(unet_engine* e, const Bn& bn, const float* gA, long long gAbs, const float* gB, long long gBbs,
-                 const float* z, long long zbs, int B, int HW, Drop d, float* g_io, const ZCat& zc = kNoCat) {
+// between the two passes of a BatchNorm backward: the accumulators pass 2 adds dgamma / dbeta to.  Under SyncBN the pass-1
+// sums are all-reduced here; this shard's dgamma / dbeta are taken from them before (k_bn_grad_local) and pass 2 adds none.
+int bn_bwd_between(unet_engine* e, const Bn& bn, double*& acc_gamma, double*& acc_beta) {
+    acc_gamma = e->gacc(bn.gamma), acc_beta = e->gacc(bn.beta);
+    if (!(e->sync_fn && e->sync_bn)) return CAE_OK;
+    hipLaunchKernelGGL(k_bn_grad_local, dim3((bn.C + 255) / 256), dim3(256), 0, e->stream, e->dsum(bn.bsums), bn.C, acc_gamma, acc_beta);
+    acc_gamma = acc_beta = nullptr;
+    return sync_table(e, e->dsum(bn.bsums), 2 * bn.C);
+}
+
+int bn_backward(unet_engine* e, const Bn& bn, const float* gA, long long gAbs, const float* gB, long long gBbs,
+                const float* z, long long zbs, int B, int HW, Drop d, float* g_io, const ZCat& zc = kNoCat) {
     // pass 1 only sums; pass 2 forms the masked gradient again from gA / gB / z and writes dz (g_io may alias neither input:
     // the callers pass distinct buffers)
     hipLaunchKernelGGL(k_bn_bwd_reduce, red_grid(B, bn.C, HW), dim3(256), 0, e->stream, gA, gAbs, gB, gBbs, z, zbs, B, bn.C,
                        HW, e->f(bn.saved), e->P(bn.gamma), e->P(bn.beta), d, (float*)nullptr, e->dsum(bn.bsums), zc);
+    double *acc_gamma, *acc_beta;
+    if (int rc = bn_bwd_between(e, bn, acc_gamma, acc_beta)) return rc;
     hipLaunchKernelGGL(k_bn_bwd_apply2, ew_grid(B, bn.C, HW), dim3(256), 0, e->stream, gA, gAbs, gB, gBbs, z, zbs, B, bn.C, HW,
-                       e->f(bn.saved), e->P(bn.gamma), e->P(bn.beta), d, e->dsum(bn.bsums), (double)B * HW, e->gacc(bn.gamma),
-                       e->gacc(bn.beta), g_io, zc);
+                       e->f(bn.saved), e->P(bn.gamma), e->P(bn.beta), d, e->dsum(bn.bsums), bn_count(e, B, HW), acc_gamma,
+                       acc_beta, g_io, zc);
+    return CAE_OK;
 }
 
 // small Linear layers: the whole weight matrix is a few 16x16 tiles' worth (see the include of kernels_gemm.h above)
@@ -463,8 +496,11 @@ int forward(unet_engine* e, const float* x, int B, bool train) {
         g.B = B;
         const int HW = g.Hs * g.Ws;
         conv_down(e, g, cur, e->P(L.w), e->P(L.b), e->f(L.z));
-        if (train) bn_stats(e, L.bn, e->f(L.z), (long long)g.Cs * HW, B, HW);
-        const Drop d = make_drop(e, SITE_ENC_CONV + i, train);
+        if (train) {
+            bn_stats(e, L.bn, e->f(L.z), (long long)g.Cs * HW, B, HW);
+            if (int rc = sync_table(e, e->dsum(L.bn.sums), 2 * L.bn.C)) return rc;
+        }
+        const Drop d = make_drop(e, SITE_ENC_CONV + i, train, (int64_t)g.Cs * HW);
         // the skip is the ReLU output; the next layer sees it through the dropout (unet.py:105-107)
         // (a skip's sums are the second half of its decoder layer's BatchNorm statistics: dec[n - 2 - i], channels Cs ..)
         double* skip_sums = (train && i < n - 1) ? e->dsum(e->dec[n - 2 - i].bn.sums) + 2 * g.Cs : nullptr;
@@ -476,9 +512,12 @@ int forward(unet_engine* e, const float* x, int B, bool train) {
     for (int k = 0; k < 4; k++) {
         Fc& L = e->fc[k];
         lin_fwd(e, L, B, cur, e->f(L.h));
-        const Drop d = make_drop(e, sites[k], train);
+        const Drop d = make_drop(e, sites[k], train, L.nout);
         if (L.has_bn) {
-            if (train) bn_stats(e, L.bn, e->f(L.h), L.nout, B, 1);
+            if (train) {
+                bn_stats(e, L.bn, e->f(L.h), L.nout, B, 1);
+                if (int rc = sync_table(e, e->dsum(L.bn.sums), 2 * L.bn.C)) return rc;
+            }
             bn_act(e, L.bn, e->f(L.h), L.nout, B, 1, train, d, nullptr, e->f(L.a));
         } else {
             hipLaunchKernelGGL(k_relu_drop, dim3(blocks_for((long long)B * L.nout, 8192)), dim3(256), 0, e->stream, e->f(L.h),
@@ -502,7 +541,10 @@ int forward(unet_engine* e, const float* x, int B, bool train) {
         hipLaunchKernelGGL(k_pool, dim3(B * C), dim3(256), 0, e->stream, e->f(L.u), HW, e->f(L.pool), train ? psum : nullptr);
         hipLaunchKernelGGL(k_att_fwd, dim3(B), dim3(256), (size_t)(2 * C + 2 * L.R) * sizeof(float), e->stream, e->f(L.pool),
                            C, L.R, e->P(L.w1), e->P(L.w2), e->f(L.att), e->f(L.hid), psum, train ? e->dsum(L.bn.sums) : nullptr);
-        const Drop d = make_drop(e, SITE_DEC_CONV + j, train);
+        // (both halves of the concatenated tensor's sums are in by now: the skip's came with the encoder's bn_act)
+        if (train)
+            if (int rc = sync_table(e, e->dsum(L.bn.sums), 2 * L.bn.C)) return rc;
+        const Drop d = make_drop(e, SITE_DEC_CONV + j, train, (int64_t)2 * C * HW);
         bn_act(e, L.bn, nullptr, 0, B, HW, train, d, nullptr, e->f(L.din_next), ZCat{e->f(L.u), e->f(L.att), skip, C});
         cur = e->f(L.din_next);
     }
@@ -529,9 +571,17 @@ int loss_forward(unet_engine* e, int which, const int32_t* perm, int64_t start, 
     // (seven workgroup-wide fp64 sums end every workgroup: about 768 of them, each a long slice of its plane)
     int chunks = std::max(1, std::min(32, 768 / std::max(1, B * C)));
     chunks = std::min(chunks, (HW + 1023) / 1024);
-    hipLaunchKernelGGL(k_loss_sums, dim3(chunks, B * C), dim3(256), 0, e->stream, e->f(L.u), 1, src, C, HW, ls);
-    hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(256), 0, e->stream, ls, B, C, src.Cm, src.mask ? 1 : 0, e->lambda_p,
-                       e->losses(slot), want_grad ? e->f(e->coef) : nullptr);
+    if (B > 0) hipLaunchKernelGGL(k_loss_sums, dim3(chunks, B * C), dim3(256), 0, e->stream, e->f(L.u), 1, src, C, HW, ls);
+    if (e->sync_fn) {   // a data-parallel shard: the mask count, squared error and Pearson sum are totals over the ranks
+        double* tot = e->dsum(e->off_ltot);
+        hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(256), 0, e->stream, ls, B, C, src.Cm, src.mask ? 1 : 0, tot);
+        if (int rc = sync_table(e, tot, 3, false)) return rc;
+        hipLaunchKernelGGL(k_loss_finalize_global, dim3(1), dim3(256), 0, e->stream, ls, B, C, tot, (double)e->loss_batch * C,
+                           e->lambda_p, e->losses(slot), want_grad ? e->f(e->coef) : nullptr);
+    } else {
+        hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(256), 0, e->stream, ls, B, C, src.Cm, src.mask ? 1 : 0, e->lambda_p,
+                           e->losses(slot), want_grad ? e->f(e->coef) : nullptr);
+    }
     if (want_grad) {
         // ... and, in the same pass, the last layer's bias gradient (its sum over the batch and the map); backward() clears the
         // accumulator before anything else adds to it, so the clear is issued here, ahead of this launch
@@ -575,15 +625,17 @@ int backward(unet_engine* e, const float* x, int B) {
         // (b, c) plane, writes dz and - for the gated half - the gate's gradient da[b][c] = sum dz * u in the same pass.  The first
         // half of gcat goes on through the attention gate to u, the second half into the encoder skip (read in place later)
         {
-            const Drop dd = make_drop(e, SITE_DEC_CONV + (j - 1), true);
+            const Drop dd = make_drop(e, SITE_DEC_CONV + (j - 1), true, (int64_t)2 * Cp * HWp);
             const ZCat zc{e->f(Pv.u), e->f(Pv.att), e->f(e->enc[n - 2 - (j - 1)].s), Cp};
             const Bn& bn = Pv.bn;
             hipLaunchKernelGGL(k_bn_bwd_reduce, red_grid(B, bn.C, HWp), dim3(256), 0, e->stream, e->f(L.gdin), (long long)2 * Cp * HWp,
                                (const float*)nullptr, 0LL, (const float*)nullptr, 0LL, B, bn.C, HWp, e->f(bn.saved), e->P(bn.gamma),
                                e->P(bn.beta), dd, (float*)nullptr, e->dsum(bn.bsums), zc);
+            double *acc_gamma, *acc_beta;
+            if (int rc = bn_bwd_between(e, bn, acc_gamma, acc_beta)) return rc;
             hipLaunchKernelGGL(k_bn_bwd_apply2_planes, dim3(1, bn.C, B), dim3(256), 0, e->stream, e->f(L.gdin), (long long)2 * Cp * HWp,
-                               bn.C, HWp, e->f(bn.saved), e->P(bn.gamma), e->P(bn.beta), dd, e->dsum(bn.bsums), (double)B * HWp,
-                               e->gacc(bn.gamma), e->gacc(bn.beta), e->f(Pv.gcat), zc, e->f(Pv.da));
+                               bn.C, HWp, e->f(bn.saved), e->P(bn.gamma), e->P(bn.beta), dd, e->dsum(bn.bsums), bn_count(e, B, HWp),
+                               acc_gamma, acc_beta, e->f(Pv.gcat), zc, e->f(Pv.da));
         }
         hipLaunchKernelGGL(k_att_bwd, dim3(B), dim3(256), (size_t)(3 * Cp + 4 * Pv.R) * sizeof(float), e->stream,
                            e->f(Pv.pool), e->f(Pv.att), e->f(Pv.hid), e->f(Pv.da), Cp, Pv.R, e->P(Pv.w1), e->P(Pv.w2),
@@ -597,14 +649,14 @@ int backward(unet_engine* e, const float* x, int B) {
     const float* gin = e->f(e->dec[0].gdin);   // grad wrt fc[3].a  (B, nout3)
     for (int k = 3; k >= 0; k--) {
         Fc& L = e->fc[k];
-        const Drop d = make_drop(e, sites[k], true);
+        const Drop d = make_drop(e, sites[k], true, L.nout);
         if (L.has_bn) {
-            bn_backward(e, L.bn, gin, L.nout, nullptr, 0, e->f(L.h), L.nout, B, 1, d, e->f(L.gh));
+            if (int rc = bn_backward(e, L.bn, gin, L.nout, nullptr, 0, e->f(L.h), L.nout, B, 1, d, e->f(L.gh))) return rc;
         } else {
             hipLaunchKernelGGL(k_relu_drop_bwd, dim3(blocks_for((long long)B * L.nout, 8192)), dim3(256), 0, e->stream, e->f(L.gh), gin,
                                e->f(L.h), (long long)B * L.nout, d);
         }
-        const float* in = k == 0 ? (make_drop(e, SITE_ENC_CONV + n - 1, true).on ? e->f(e->enc[n - 1].a) : e->f(e->enc[n - 1].s))
+        const float* in = k == 0 ? (make_drop(e, SITE_ENC_CONV + n - 1, true, 0).on ? e->f(e->enc[n - 1].a) : e->f(e->enc[n - 1].s))
                                  : e->f(e->fc[k - 1].a);
         lin_bwd(e, L, B, in, e->f(L.gh), e->f(L.ga));
         gin = e->f(L.ga);
@@ -623,9 +675,10 @@ int backward(unet_engine* e, const float* x, int B) {
             gskip = e->f(D.gcat) + (size_t)C * HW;
             gskip_bs = (long long)2 * C * HW;
         }
-        bn_backward(e, L.bn, gin, (long long)C * HW, gskip, gskip_bs, e->f(L.z), (long long)C * HW, B, HW,
-                    make_drop(e, SITE_ENC_CONV + i, true), e->f(L.gz));
-        const float* in = i == 0 ? x : (make_drop(e, SITE_ENC_CONV + i - 1, true).on ? e->f(e->enc[i - 1].a) : e->f(e->enc[i - 1].s));
+        if (int rc = bn_backward(e, L.bn, gin, (long long)C * HW, gskip, gskip_bs, e->f(L.z), (long long)C * HW, B, HW,
+                                 make_drop(e, SITE_ENC_CONV + i, true, (int64_t)C * HW), e->f(L.gz)))
+            return rc;
+        const float* in = i == 0 ? x : (make_drop(e, SITE_ENC_CONV + i - 1, true, 0).on ? e->f(e->enc[i - 1].a) : e->f(e->enc[i - 1].s));
         // Conv2d: S = output, L = input
         conv_wgrad(e, g, e->f(L.gz), in, e->gacc(L.w));
         // no bias gradient: this bias is added right before a BatchNorm, whose backward makes every channel of dz sum
@@ -662,10 +715,10 @@ F32Ranges f32_ranges(const unet_engine* e) {
     return fr;
 }
 
+// (batch checked by the caller)
 int train_or_fb(unet_engine* e, int which, const int32_t* perm, int64_t start, int batch, int slot, float* grads_out,
                 double grad_scale = 1.0) {
-    int rc = check_batch(e, "unet", which, start, batch, slot, true);
-    if (rc) return rc;
+    int rc;
     if ((rc = gather_x(e, which, perm, start, batch))) return rc;
     if ((rc = forward(e, e->f(e->xb), batch, true))) return rc;
     if ((rc = loss_forward(e, which, perm, start, batch, slot, true))) return rc;
@@ -678,6 +731,67 @@ int train_or_fb(unet_engine* e, int which, const int32_t* perm, int64_t start, i
         hipLaunchKernelGGL(k_adamw, dim3(adamw_blocks(e)), dim3(256), 0, e->stream, (long long)e->tab.n_param, e->params, e->gacc(0), e->m,
                            e->v, adamw_consts(e), f32_ranges(e));
         e->gacc_clean = true;
+    }
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+// ---- data-parallel shards (unet_forward_backward_sync / unet_eval_step_sync) ----------------------------------------
+// The shard's place in the global batch and the all-reduce callback, for the duration of one call
+struct ShardScope {
+    unet_engine* e;
+    ShardScope(unet_engine* e_, int row0, int global_batch, bool sync_bn, cae_allreduce_fn fn, void* user) : e(e_) {
+        e->row0 = row0, e->stat_batch = sync_bn ? global_batch : 0, e->loss_batch = global_batch;
+        e->sync_fn = fn, e->sync_user = user, e->sync_bn = sync_bn;
+    }
+    ~ShardScope() {
+        e->row0 = 0, e->stat_batch = e->loss_batch = 0;
+        e->sync_fn = nullptr, e->sync_user = nullptr, e->sync_bn = false;
+    }
+};
+
+// the checks of check_batch for a shard, which may be empty (batch 0: global batch < world, or the tail of a partial batch)
+int check_shard(const unet_engine* e, const char* who, int which, int64_t start, int batch, int row0, int global_batch,
+                int world, int slot, cae_allreduce_fn fn) {
+    if (!fn || world < 0 || global_batch < 1 || batch < 0 || row0 < 0 || (int64_t)row0 + batch > global_batch)
+        return fail(CAE_ERR_ARG, "%s: bad argument (batch %d at row %d of %d, world %d)", who, batch, row0, global_batch, world);
+    if (batch > 0) return check_batch(e, who, which, start, batch, slot, true);
+    if (!e->ws) return fail(CAE_ERR_STATE, "%s: engine is not bound", who);
+    if (which < 0 || which > 1 || !e->ds[which].x || !e->ds[which].t) return fail(CAE_ERR_STATE, "%s: data set %d is not set", who, which);
+    if (slot < 0 || slot >= kStepLossSlots) return fail(CAE_ERR_ARG, "%s: loss slot %d outside 0..%d", who, slot, kStepLossSlots - 1);
+    return CAE_OK;
+}
+
+// An empty shard's step: no activations and no launch over the batch, but the same tables - zero here - go to the all-reduce in
+// the order forward(), loss_forward() and backward() pass them on the other ranks, the running statistics advance from the global
+// sums as theirs do (SyncBN; per-rank statistics have nothing to advance from), and the loss slot and the (zero) gradient are written.
+int empty_shard_step(unet_engine* e, int which, int slot, float* grads_out) {
+    const bool train = grads_out != nullptr;
+    const int n = (int)e->enc.size(), nd = (int)e->dec.size();
+    const Drop off{0, 0, 1.f, 0, 0};
+    auto fwd_table = [&](const Bn& bn, int HW) -> int {
+        if (int rc = sync_table(e, e->dsum(bn.sums), 2 * bn.C)) return rc;
+        if (e->sync_bn) bn_act(e, bn, nullptr, 0, 0, HW, true, off, nullptr, nullptr);
+        return CAE_OK;
+    };
+    if (train) {
+        HIP_TRY(hipMemsetAsync(e->dsum(0), 0, (size_t)e->n_dsum * sizeof(double), e->stream));
+        for (auto& L : e->enc)
+            if (int rc = fwd_table(L.bn, L.g.Hs * L.g.Ws)) return rc;
+        for (int k : {0, 2})
+            if (int rc = fwd_table(e->fc[k].bn, 1)) return rc;
+        for (int j = 0; j < nd - 1; j++)
+            if (int rc = fwd_table(e->dec[j].bn, e->dec[j].g.Hl * e->dec[j].g.Wl)) return rc;
+    }
+    if (int rc = loss_forward(e, which, nullptr, 0, 0, slot, false)) return rc;
+    if (train) {
+        for (int j = nd - 1; j >= 1; j--)
+            if (int rc = sync_table(e, e->dsum(e->dec[j - 1].bn.bsums), 2 * e->dec[j - 1].bn.C)) return rc;
+        for (int k : {2, 0})
+            if (int rc = sync_table(e, e->dsum(e->fc[k].bn.bsums), 2 * e->fc[k].bn.C)) return rc;
+        for (int i = n - 1; i >= 0; i--)
+            if (int rc = sync_table(e, e->dsum(e->enc[i].bn.bsums), 2 * e->enc[i].bn.C)) return rc;
+        HIP_TRY(hipMemsetAsync(grads_out, 0, (size_t)e->tab.n_param * sizeof(float), e->stream));
     }
     HIP_TRY(hipGetLastError());
     return CAE_OK;
@@ -792,6 +906,8 @@ int unet_engine_create(const cae_layer_spec* enc, int n_enc, const cae_layer_spe
     carve_bn(e->fc[2].bn);
     for (auto& L : e->dec)
         if (L.has_bn) carve_bn(L.bn);
+    e->off_ltot = nd;
+    nd += 4;
     e->n_dsum = nd;
     Carver F32{64};   // the fp32 sub-arena (float offsets)
     auto carve_saved = [&](Bn& bn) { bn.saved = F32(2 * bn.C); };
@@ -908,13 +1024,25 @@ int unet_set_dataset(unet_engine* e, int which, const float* x, const float* tar
 }
 
 int unet_train_step(unet_engine* e, int which, const int32_t* perm, int64_t start, int batch, int loss_slot) {
+    if (int rc = check_batch(e, "unet", which, start, batch, loss_slot, true)) return rc;
     return train_or_fb(e, which, perm, start, batch, loss_slot, nullptr);
 }
 
 int unet_forward_backward(unet_engine* e, int which, const int32_t* perm, int64_t start, int batch, int loss_slot,
                           float* grads, double grad_scale) {
     if (!grads) return fail(CAE_ERR_ARG, "unet_forward_backward: null gradient buffer");
+    if (int rc = check_batch(e, "unet", which, start, batch, loss_slot, true)) return rc;
     return train_or_fb(e, which, perm, start, batch, loss_slot, grads, grad_scale);
+}
+
+int unet_forward_backward_sync(unet_engine* e, int which, const int32_t* perm, int64_t start, int batch, int row0,
+                               int global_batch, int world, int loss_slot, float* grads, cae_allreduce_fn fn, void* user) {
+    if (!e || !grads) return fail(CAE_ERR_ARG, "unet_forward_backward_sync: bad argument");
+    if (int rc = check_shard(e, "unet_forward_backward_sync", which, start, batch, row0, global_batch, world, loss_slot, fn))
+        return rc;
+    ShardScope scope(e, row0, global_batch, world > 0, fn, user);
+    if (batch == 0) return empty_shard_step(e, which, loss_slot, grads);
+    return train_or_fb(e, which, perm, start, batch, loss_slot, grads, 1.0);
 }
 
 int unet_apply_gradients(unet_engine* e, const float* grads) {
@@ -933,6 +1061,18 @@ int unet_apply_gradients(unet_engine* e, const float* grads) {
 int unet_eval_step(unet_engine* e, int which, const int32_t* perm, int64_t start, int batch, int loss_slot) {
     int rc = check_batch(e, "unet", which, start, batch, loss_slot, true);
     if (rc) return rc;
+    if ((rc = gather_x(e, which, perm, start, batch))) return rc;
+    if ((rc = forward(e, e->f(e->xb), batch, false))) return rc;
+    return loss_forward(e, which, perm, start, batch, loss_slot, false);
+}
+
+int unet_eval_step_sync(unet_engine* e, int which, const int32_t* perm, int64_t start, int batch, int row0, int global_batch,
+                        int loss_slot, cae_allreduce_fn fn, void* user) {
+    if (!e) return fail(CAE_ERR_ARG, "unet_eval_step_sync: null engine");
+    int rc = check_shard(e, "unet_eval_step_sync", which, start, batch, row0, global_batch, 0, loss_slot, fn);
+    if (rc) return rc;
+    ShardScope scope(e, row0, global_batch, false, fn, user);
+    if (batch == 0) return empty_shard_step(e, which, loss_slot, nullptr);
     if ((rc = gather_x(e, which, perm, start, batch))) return rc;
     if ((rc = forward(e, e->f(e->xb), batch, false))) return rc;
     return loss_forward(e, which, perm, start, batch, loss_slot, false);

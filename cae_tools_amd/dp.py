@@ -17,7 +17,9 @@ Two engine protocols:
   set_cursor / claim_slots / dp_train_steps / dp_eval_steps / dp_read_losses / dp_broadcast.
 * half-steps (UnetEngine / VaeEngine / LinearEngine behind GradientHalfSteps, and the CPU stand-ins of the gloo
   tests): .grads, .forward_backward(which, perm, start, size, global_batch), .adam_step(); the all-reduce is
-  torch.distributed's.
+  torch.distributed's.  run_batches additionally drives .forward_backward_sync(which, perm, start, size, row0,
+  global_batch, bn_world, allreduce) / .eval_step_sync(which, perm, start, size, row0, global_batch, allreduce), which
+  return a loss slot, and .read_losses(first, count) / .loss_slots (the UNET engine's global-batch entry points).
 """
 import contextlib
 
@@ -124,9 +126,9 @@ class DataParallel:
     def run_batches(self, which, perm, n, global_batch, train=True):
         """One pass over perm[0:n] in GLOBAL batches of `global_batch` (the last one partial, drop_last=False as in
         conv_ae_model.py:291-292); this rank runs rows shard_bounds(size, world, rank) of each.  Returns the per-batch
-        mean losses over the global batches, identical on every rank.  Native engines only."""
+        mean losses over the global batches, identical on every rank."""
         if not self.native:
-            raise TypeError("run_batches drives the in-library data-parallel path (HipEngine)")
+            return self._run_half_steps(which, perm, n, global_batch, train)
         eng = self.engine
         (full, rem) = divmod(int(n), int(global_batch))
         nb = full + (1 if rem else 0)
@@ -156,13 +158,46 @@ class DataParallel:
             steps(hi - lo, rem, 1)         # hi == lo (an empty shard) still takes part in the collectives
         return eng.dp_read_losses(first, nb)
 
+    def _run_half_steps(self, which, perm, n, global_batch, train):
+        """run_batches over the sync half-steps: every shard (an empty one included) goes through the engine's global-batch
+        entry points, whose tables this rank's all-reduce sums, so the losses are the global batch's; training then
+        all-reduces the gradient and steps the optimiser.  sync_bn=False keeps BatchNorm statistics per rank (bn_world 0);
+        the loss denominators and the dropout masks are the global batch's either way."""
+        eng = self.engine
+
+        def allreduce(t):
+            self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
+
+        out, pending = [], []
+        for b0 in range(0, int(n), int(global_batch)):
+            gb = min(int(global_batch), int(n) - b0)
+            (lo, hi) = shard_bounds(gb, self.world, self.rank)
+            if train:
+                slot = eng.forward_backward_sync(which, perm, b0 + lo, hi - lo, lo, gb, self.world if self.sync_bn else 0,
+                                                 allreduce)
+                with self._stream_ctx():
+                    allreduce(eng.grads)
+                eng.adam_step()
+            else:
+                slot = eng.eval_step_sync(which, perm, b0 + lo, hi - lo, lo, gb, allreduce)
+            pending.append(slot)
+            if slot == eng.loss_slots - 1:     # the slots wrap next: read what they hold
+                out.extend(eng.read_losses(pending[0], len(pending)))
+                pending = []
+        if pending:
+            out.extend(eng.read_losses(pending[0], len(pending)))
+        return out
+
 
 class GradientHalfSteps:
     """UnetEngine / VaeEngine / LinearEngine behind the three-member interface DataParallel drives: a persistent flat
     gradient buffer, forward_backward into it with the local/global weight applied in the kernel that narrows the fp64
     accumulator (grad_scale of *_forward_backward), and the optimiser half-step (*_apply_gradients) after the all-reduce.
-    BatchNorm statistics stay per rank.  The UNET's masked MSE divides by the LOCAL mask count, so with unequal mask
-    coverage across ranks the reduced gradient weights shards by sample count rather than by valid-pixel count."""
+    With forward_backward, BatchNorm statistics stay per rank and the UNET's masked MSE divides by the LOCAL mask count
+    (with unequal mask coverage the reduced gradient weights shards by sample count, not by valid-pixel count).  The UNET's
+    forward_backward_sync / eval_step_sync (what DataParallel.run_batches drives) are the single-device arithmetic at the
+    global batch instead: global loss denominators, dropout masks of the global rows and, with SyncBN, BatchNorm
+    statistics over the global batch."""
 
     def __init__(self, engine):
         self.engine = engine
@@ -172,11 +207,33 @@ class GradientHalfSteps:
         self.buffers = getattr(engine, "buffers", None)
         self._slot = 0
 
-    def forward_backward(self, which, perm, start, size, global_batch):
+    @property
+    def loss_slots(self):
+        return self.engine.loss_slots
+
+    def _next_slot(self):
         slot = self._slot
         self._slot = (slot + 1) % self.engine.loss_slots
+        return slot
+
+    def forward_backward(self, which, perm, start, size, global_batch):
+        slot = self._next_slot()
         self.engine.forward_backward(which, perm, start, size, slot=slot, global_batch=global_batch, out=self.grads)
         return slot
+
+    def forward_backward_sync(self, which, perm, start, size, row0, global_batch, bn_world, allreduce):
+        slot = self._next_slot()
+        self.engine.forward_backward_sync(which, perm, start, size, row0, global_batch, bn_world, allreduce, out=self.grads,
+                                          slot=slot)
+        return slot
+
+    def eval_step_sync(self, which, perm, start, size, row0, global_batch, allreduce):
+        slot = self._next_slot()
+        self.engine.eval_step_sync(which, perm, start, size, row0, global_batch, allreduce, slot=slot)
+        return slot
+
+    def read_losses(self, first, count):
+        return self.engine.read_losses(first, count)
 
     def adam_step(self):
         self.engine.apply_gradients(self.grads)

@@ -20,6 +20,7 @@ import time
 import numpy as np
 import torch
 
+from .. import dp as _dp
 from .. import unet_engine as _ue
 from ..utils.model_database import ModelDatabase
 from ._params import ParamBag, add_batchnorm, default_layer_init
@@ -172,6 +173,11 @@ class UNET(EngineModel):
         self.dropout_seed = dropout_seed
         self._engine = None
         self._steps_done = 0
+        self.timing = None      # set by train(): seconds and images of the epoch loop, and the world size
+        # under a torch.distributed.run launch (one process per GPU) batch_size stays the GLOBAL batch; sync_bn=True computes
+        # BatchNorm statistics over it (N ranks reproduce the single-device step), False keeps per-rank statistics
+        self.sync_bn = True
+        self._lead = True       # this process prints (rank 0 of a data-parallel run)
 
     # ---- persistence ---------------------------------------------------------------------------------
     def get_parameters(self):
@@ -216,12 +222,24 @@ class UNET(EngineModel):
     # ---- training --------------------------------------------------------------------------------------
     def train(self, input_variables, output_variable, training_ds, testing_ds, model_path="", training_paths="",
               testing_paths="", mask_variable_name=None):
+        # Data parallel (build-only; the reference trains on one device): under a torch.distributed.run launch every rank
+        # holds the model and both data sets and takes its rows of each frozen GLOBAL batch (dp.shard_bounds); the engine's
+        # sync entry points sum the BatchNorm, loss and gradient tables over the ranks, so that a step is the single-device
+        # step at batch_size.  Rank 0 prints and saves.
+        dist = _dp.ensure_process_group()
+        (world, rank) = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
+        self._lead = lead = rank == 0
         (train_ds, test_ds, train_perm, test_perm) = self._train_prologue(input_variables, output_variable, training_ds,
                                                                           testing_ds, mask_variable_name)
-        print(f"Running on device: {torch.device('cuda')}")
+        if dist is not None:    # one frozen shuffle for everybody: rank 0's draw
+            box = [train_perm, test_perm]
+            dist.broadcast_object_list(box, src=0)
+            (train_perm, test_perm) = box
+        if lead:
+            print(f"Running on device: {torch.device('cuda')}")
         start = time.time()
 
-        eng = self._get_engine(int(self.batch_size))
+        eng = self._get_engine(-(-int(self.batch_size) // world))   # a rank's share of a global batch
         eng.set_hyper(lr=self.lr, weight_decay=self.weight_decay, dropout_rate=self.dropout_rate,
                       lambda_pearson=self.lambda_pearson, seed=self.dropout_seed)
         eng.reset_optimizer()       # AdamW is re-created on every train() (:457)
@@ -231,32 +249,61 @@ class UNET(EngineModel):
             eng.set_dataset(which, ds.device_inputs(), ds.device_outputs(), self._loss_mask(ds))
         train_idx = eng.upload_perm(train_perm)
         test_idx = eng.upload_perm(test_perm)
-        print(f"finished batching in {time.time() - t0:.2f} seconds")
+        if lead:
+            print(f"finished batching in {time.time() - t0:.2f} seconds")
+        par = None
+        if dist is not None:
+            par = _dp.DataParallel(_dp.GradientHalfSteps(eng), dist, sync_bn=self.sync_bn)
+            par.broadcast_parameters(0)     # rank 0's initial (or loaded) weights, running statistics and moments everywhere
+
+        def one_pass(which, idx, n, train):
+            if par is None:
+                return eng.run_batches(which, idx, n, self.batch_size, train=train)
+            if not train and not self.sync_bn:
+                par.broadcast_buffers(0)    # every rank scores with the same running statistics
+            return par.run_batches(which, idx, n, self.batch_size, train=train)
 
         train_loss = test_loss = 0.0
+        eng.sync()
+        loop_start = time.perf_counter()
         try:
             for epoch in range(self.nr_epochs):
                 e0 = time.time()
-                losses = eng.run_batches(_ue.TRAIN, train_idx, len(train_ds), self.batch_size, train=True)
-                print(f"time used for training one epoch: {time.time() - e0:.2f}")
+                losses = one_pass(_ue.TRAIN, train_idx, len(train_ds), True)
+                if lead:
+                    print(f"time used for training one epoch: {time.time() - e0:.2f}")
                 train_loss = float(np.mean([l[0] for l in losses]))
                 train_pearson_loss = float(np.mean([l[1] for l in losses]))
                 if epoch % self.test_interval == 0:
-                    tl = eng.run_batches(_ue.TEST, test_idx, len(test_ds), self.batch_size, train=False)
+                    tl = one_pass(_ue.TEST, test_idx, len(test_ds), False)
                     test_loss = float(np.mean([l[0] for l in tl]))
                     test_pearson_loss = float(np.mean([l[1] for l in tl]))
                     self.history["train_loss"].append(train_loss)
                     self.history["test_loss"].append(test_loss)
-                    print(f"epoch: {epoch}, train_mse: {train_loss:.6f}, train_pearson_loss: {train_pearson_loss:.4f}, "
-                          f"test_mse: {test_loss:.6f}, test_pearson_loss: {test_pearson_loss:.4f}")
-                    print(f"learn rate: {self.lr:.6f}")
+                    if lead:
+                        print(f"epoch: {epoch}, train_mse: {train_loss:.6f}, train_pearson_loss: {train_pearson_loss:.4f}, "
+                              f"test_mse: {test_loss:.6f}, test_pearson_loss: {test_pearson_loss:.4f}")
+                        print(f"learn rate: {self.lr:.6f}")
         except KeyboardInterrupt:
             print("Training interrupted. Performing cleanup...")
+        eng.sync()
+        self.timing = {"epoch_loop_seconds": time.perf_counter() - loop_start, "train_images": len(train_ds) * self.nr_epochs,
+                       "epochs": self.nr_epochs, "world": world}
+        if par is not None and not self.sync_bn:
+            par.broadcast_buffers(0)
         return self._train_epilogue(start, train_ds, test_ds, train_loss, test_loss, input_variables, output_variable,
-                                    model_path, training_paths, testing_paths)
+                                    model_path, training_paths, testing_paths, lead=lead)
+
+    def _score_device(self, x):
+        # an engine that exists is used as it is (score() walks the array in chunks of its max_batch): a data-parallel
+        # rank's engine holds a share of the batch and is not re-created for scoring
+        if self._engine is not None:
+            return self._engine.score(x)
+        return super()._score_device(x)
 
     def _progress(self, message):
-        print(message)
+        if self._lead:
+            print(message)
 
     def _loss_mask(self, ds):
         """(N, 1|C, H, W) fp32 mask for the loss, or None for all ones counted over the output's channels"""

@@ -3,10 +3,14 @@
 'unet' with skip connections, batch 32).  Not the round's headline bench (bench.py is); prints one JSON line.
 
     python tools/bench_unet.py [--steps 20] [--warmup 3] [--batch 32] [--channels 32,64,128,256] [--generic] [--cpu]
+                               [--force-dp]
 
 Layer definitions are hand-written (k4 s2 p1: the auto-sizer cannot produce a skip-compatible spec, SURVEY.md §8a);
 synthetic data, torch.manual_seed(0) default initialisation, dropout 0.1, AdamW.  FLOPs are the algorithmic
 conv / conv-transpose / linear MACs x 2 x 3 (forward, input gradient, weight gradient); MFMA fp32 peak 157.3 TF.
+
+--force-dp: the data-parallel step of a one-rank RCCL group (unet_forward_backward_sync with SyncBN, its table all-reduces,
+the gradient all-reduce, unet_apply_gradients), i.e. what the data-parallel path adds to a step on one GPU.
 """
 import argparse
 import json
@@ -46,6 +50,7 @@ def main():
     ap.add_argument("--channels", default="32,64,128,256")
     ap.add_argument("--generic", action="store_true", help="shape-generic kernels instead of the MFMA ones")
     ap.add_argument("--cpu", action="store_true", help="also time the CPU oracle (one step)")
+    ap.add_argument("--force-dp", action="store_true", help="the data-parallel step over a one-rank group")
     args = ap.parse_args()
     chans = [int(c) for c in args.channels.split(",")]
     spec = unet_layer_spec(3, 3, (args.size, args.size), chans)
@@ -67,6 +72,28 @@ def main():
     def run(k):
         for s in range(k):
             eng.train_step(0, perm, (s % 2) * B, B, slot=s % 64)
+
+    if args.force_dp:
+        import socket
+        import torch.distributed as dist
+        from cae_tools_amd.dp import GradientHalfSteps
+        with socket.socket() as sk:
+            sk.bind(("127.0.0.1", 0))
+            os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(sk.getsockname()[1]))
+        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda:0"))
+        half = GradientHalfSteps(eng)
+        tables = []
+
+        def allreduce(t):
+            tables.append(t.numel())
+            dist.all_reduce(t)
+
+        def run(k):     # noqa: F811  (the data-parallel step instead of the fused one)
+            for s in range(k):
+                half.forward_backward_sync(0, perm, (s % 2) * B, B, 0, B, 1, allreduce)
+                with torch.cuda.stream(eng.stream):
+                    dist.all_reduce(half.grads)
+                half.adam_step()
     run(args.warmup)
     eng.sync()
     t0 = time.perf_counter()
@@ -82,7 +109,11 @@ def main():
            "algorithmic_gflop_per_step": flops / 1e9,
            "roofline": {"bound": "mfma", "achieved": flops / dt / 1e12, "peak": 157.3, "unit": "TFLOP/s",
                         "frac": flops / dt / 1e12 / 157.3, "traffic": None},
-           "losses_last": eng.read_losses((args.steps - 1) % 64, 1)[0]}
+           "losses_last": eng.read_losses((args.steps - 1) % 64 if not args.force_dp else (args.warmup + args.steps - 1) % eng.loss_slots, 1)[0]}
+    if args.force_dp:
+        per_step = len(tables) // (args.warmup + args.steps)
+        out["config"]["data_parallel"] = {"world": 1, "sync_bn": True, "table_allreduces_per_step": per_step,
+                                          "gradient_allreduce_bytes": 4 * eng.n_param}
     if args.cpu:
         from oracle import unet_oracle as uo
         torch.set_num_threads(16)
@@ -95,6 +126,8 @@ def main():
         out["cpu_baseline"] = {"value": B / cdt, "unit": "images/s", "cores": 16, "kind": "port",
                                "sample": "1 training step at batch %d after 1 warm-up, dropout 0, torch CPU" % B}
     print(json.dumps(out))
+    if args.force_dp:
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
