@@ -143,6 +143,10 @@ SIGNATURES = {
     "vae_loss_slots": (C.c_int, [_P]),
     "vae_read_losses": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "vae_sync": (C.c_int, [_P]),
+    "vae_forward_backward_sync": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                            ALLREDUCE_FN, _P]),
+    "vae_eval_step_sync": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, ALLREDUCE_FN, _P]),
+    "vae_debug_read": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
     # ---- include/cae_linear.h ----
     "lin_engine_create": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "lin_engine_destroy": (None, [_P]),

@@ -282,6 +282,7 @@ struct StepArgs {
     cae_allreduce_fn sync_fn = nullptr;
     void* sync_user = nullptr;
     int world = 1;
+    bool ordered = false;  // trunk mode: every sync_fn call is checked against sync_order, as the dp_sync collectives are
     int nsteps = 1;        // consecutive steps of the same batch size in one captured graph
     // data-parallel step inside the library (cae_dp_train_step): gradient buckets all-reduced by RCCL on the second stream;
     // dp_sync additionally all-reduces every BatchNorm sum table in-stream (SyncBN) instead of calling sync_fn
@@ -316,6 +317,11 @@ int sync_bn_table(cae_engine* e, const StepArgs& a, int bn_index) {
         NCCL_TRY(rccl().AllReduce(e->bn_stats(bn_index), e->bn_stats(bn_index), (size_t)n, RcclApi::kFloat64, RcclApi::kSum,
                                   e->dp_comm, e->stream));
         return CAE_OK;
+    }
+    if (a.ordered) {
+        if (e->sync_pos >= e->sync_order.size() || e->sync_order[e->sync_pos] != bn_index)
+            return fail(CAE_ERR_STATE, "SyncBN: table %d passed out of order (position %zu)", bn_index, e->sync_pos);
+        e->sync_pos++;
     }
     if (a.sync_fn(a.sync_user, e->bn_stats(bn_index), n) != 0)
         return fail(CAE_ERR_STATE, "the all-reduce callback failed for BatchNorm table %d", bn_index);
@@ -2861,31 +2867,90 @@ void trunk_set_hooks(cae_engine* e, const TrunkHooks& hooks) { e->hooks = hooks;
 float* trunk_raw_output(cae_engine* e) { return e->fptr(e->off_zlast); }
 float* trunk_output_gradient(cae_engine* e) { return e->fptr(e->off_glast); }
 double* trunk_output_bias_acc(cae_engine* e) { return e->gradacc() + e->dec.back().b_off; }
+float* trunk_latent(cae_engine* e) { return e->fptr(e->off_vz); }
 
-static StepArgs trunk_args(const float* x, int batch, bool train) {
+// sync.fn with sync.world >= 1: every launch that completes a BatchNorm sum table is followed by the callback (SyncBN over
+// sync.global_batch rows: the means, variances and running-statistics updates use the global count, and the BatchNorm parameter
+// gradients are each rank's 1/world share of the global sums).  No callback or world 0: per-rank statistics, today's launches.
+// The kernels that fold a BatchNorm table's production and consumption into one launch do not run here with a callback: the
+// fused k_head_fwd / k_tail_bwd (which recompute statistics inside one launch) never in trunk mode (head_plan / tail_plan refuse
+// a variational engine), k_conv_bwd_pair and the AdamConv0 fold never while syncing().  So a SyncBN trunk step takes the
+// per-layer path: every table is produced by one launch, handed to the callback, and only then read by the next.
+static StepArgs trunk_args(const float* x, int batch, bool train, const TrunkSync& sync) {
     StepArgs a{0, nullptr, batch, batch, batch, train, false, x, nullptr, false};
+    if (sync.fn && sync.world >= 1) {
+        a.sync_fn = sync.fn;
+        a.sync_user = sync.user;
+        a.world = sync.world;
+        a.global_batch = a.bn_batch = sync.global_batch;
+        a.ordered = true;
+    }
     return a;
 }
 
-int trunk_forward(cae_engine* e, const float* x, int batch, bool train, bool external_loss, float* yhat) {
+// The forward (fwd) or backward half of an EMPTY shard's training step under SyncBN: no launch reads rows, but the callbacks of
+// the other ranks are made in the same order (sync_order: the forward tables, then the backward ones) with this rank's zero
+// tables, and after each one k_bn_empty_shard does what the other ranks' consumers do with it - the running statistics advance
+// from the forward sums, dgamma / dbeta take this rank's share of the backward sums - so that the ranks stay identical.
+static int trunk_empty_shard(cae_engine* e, const StepArgs& a, bool fwd) {
+    if (!a.syncing()) return CAE_OK;
+    size_t n_fwd = e->enc.size();
+    for (auto& L : e->dec) n_fwd += L.has_bn ? 1 : 0;
+    const size_t lo = fwd ? 0 : n_fwd, hi = fwd ? n_fwd : e->sync_order.size();
+    for (size_t k = lo; k < hi; k++) {
+        const int bn = e->sync_order[k];
+        const ConvLayer* P = nullptr;
+        for (auto& L : e->enc) P = L.bn_index == bn ? &L : P;
+        for (auto& L : e->dec) P = L.has_bn && L.bn_index == bn ? &L : P;
+        if (int rc = sync_bn_table(e, a, bn)) return rc;
+        BnDesc d = bn_none();
+        BnGradOut bg;
+        memset(&bg, 0, sizeof bg);
+        if (fwd) {
+            d = bn_of(e, *P, BN_BATCH, (double)a.bn_batch * P->hout * P->wout, 1);
+        } else {
+            bg.stats = e->bn_stats(bn);
+            bg.gamma_acc = e->gradacc() + P->gamma_off;
+            bg.beta_acc = e->gradacc() + P->beta_off;
+            bg.C = P->cout;
+            bg.scale = 1.0 / a.world;
+        }
+        hipLaunchKernelGGL(k_bn_empty_shard, dim3(1), dim3(256), (size_t)P->cout * sizeof(float4), e->stream, d, bg);
+    }
+    return CAE_OK;
+}
+
+int trunk_forward(cae_engine* e, const float* x, int batch, bool train, bool external_loss, float* yhat, const TrunkSync& sync) {
     if (!e || !e->ws || !e->variational) return fail(CAE_ERR_STATE, "trunk_forward: not a bound trunk engine");
-    if (!x || batch < 1 || batch > e->max_batch) return fail(CAE_ERR_ARG, "trunk_forward: batch %d outside [1, %d]", batch, e->max_batch);
-    StepArgs a = trunk_args(x, batch, train);
+    const int min_batch = train && sync.fn ? 0 : 1;   // (an empty shard takes part in a data-parallel training step)
+    if ((batch > 0 && !x) || batch < min_batch || batch > e->max_batch)
+        return fail(CAE_ERR_ARG, "trunk_forward: batch %d outside [%d, %d]", batch, min_batch, e->max_batch);
+    StepArgs a = trunk_args(x, batch, train, sync);
     a.external_loss = external_loss;
     a.yhat = yhat;
-    if (train)   // (see launch_one: every training forward starts from a clean first BatchNorm table; the others are cleared by
-                 // the step tail of the optimiser / gradient hand-over launch)
+    if (train) {   // (see launch_one: every training forward starts from a clean first BatchNorm table; the others are cleared by
+                   // the step tail of the optimiser / gradient hand-over launch)
         memset(&e->c0_pending, 0, sizeof e->c0_pending);
-    if (int rc = launch_forward(e, a)) return rc;
+        e->sync_pos = 0;
+    }
+    if (batch == 0) {   // the empty shard: the optimiser step the first kernel would count, the first table's clear, the tables
+        hipLaunchKernelGGL(k_bump_adam, dim3(1), dim3(1), 0, e->stream, e->state());
+        HIP_TRY(hipMemsetAsync(e->bn_stats(e->enc[0].bn_index), 0, (size_t)kStatShards * e->enc[0].cout * 4 * sizeof(double), e->stream));
+        if (int rc = trunk_empty_shard(e, a, true)) return rc;
+    } else if (int rc = launch_forward(e, a)) {
+        return rc;
+    }
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
 
-int trunk_backward(cae_engine* e, const float* x, int batch) {
+int trunk_backward(cae_engine* e, const float* x, int batch, const TrunkSync& sync) {
     if (!e || !e->ws || !e->variational) return fail(CAE_ERR_STATE, "trunk_backward: not a bound trunk engine");
-    StepArgs a = trunk_args(x, batch, true);
+    StepArgs a = trunk_args(x, batch, true, sync);
     a.external_loss = true;
-    if (int rc = launch_backward(e, a)) return rc;
+    if (int rc = batch == 0 ? trunk_empty_shard(e, a, false) : launch_backward(e, a)) return rc;
+    if (a.ordered && e->sync_pos != e->sync_order.size())
+        return fail(CAE_ERR_STATE, "SyncBN: %zu of %zu tables passed to the callback", e->sync_pos, e->sync_order.size());
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }

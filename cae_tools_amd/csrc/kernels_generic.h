@@ -1097,6 +1097,25 @@ __global__ void k_scale_f64(double* __restrict__ p, long long n, double f) {
 // the optimiser step counter for the data-parallel path, where Adam runs as its own op
 __global__ void k_bump_adam(StepState* st) { st->adam_step += 1; }
 
+// What a rank whose data-parallel shard is empty does with one all-reduced BatchNorm table of a SyncBN step, where the other
+// ranks' kernels read it (one workgroup, dynamic LDS of C float4).  d (BN_BATCH, update): the running statistics advance from
+// the global sums as the designated consumer block does (bn_batch_finish); bg.stats: dgamma / dbeta take this rank's share
+// bg.scale of the global sums, as BnGradOut does in the weight-gradient kernels.
+__global__ void __launch_bounds__(256) k_bn_empty_shard(BnDesc d, BnGradOut bg) {
+    extern __shared__ float4 consts[];
+    bn_consts(d, consts, true);
+    if (!bg.stats) return;
+    for (int c = threadIdx.x; c < bg.C; c += blockDim.x) {
+        double sb = 0.0, sg = 0.0;
+        for (int sh = 0; sh < kStatShards; sh++) {
+            sb += bg.stats[((size_t)sh * bg.C + c) * 4 + 2];
+            sg += bg.stats[((size_t)sh * bg.C + c) * 4 + 3];
+        }
+        bg.beta_acc[c] = sb * bg.scale;
+        bg.gamma_acc[c] = sg * bg.scale;
+    }
+}
+
 __global__ void k_set_state(StepState* st, long long batch_start, int loss_slot, int set_cursor, int adam_step,
                             int set_adam) {
     if (set_cursor) {

@@ -54,9 +54,10 @@ __device__ __forceinline__ float normal_hash(uint32_t key, uint32_t idx) {
 }
 
 // heads: (B, 2 * L) rows [mu | logvar] - the two heads are ONE Linear layer of the trunk (trunk_api.h).  i = b * L + j is the
-// element's index in the (B, L) latent array (what the noise hash and the oracle count in).
+// element's index in the (B, L) latent array; the noise hash counts in the GLOBAL batch's array, (row0 + b) * L + j, so that a
+// data-parallel shard holding rows row0.. of it draws the eps of those rows (row0 0: a whole batch, what the oracle counts in).
 // z = mu + eps * exp(logvar / 2) (train) or mu (eval); kl_out += -0.5 * sum(1 + lv - mu^2 - exp(lv)).  one block per launch chunk
-__global__ void __launch_bounds__(256) k_reparam(const float* __restrict__ heads, int B, int L, uint32_t key, int train,
+__global__ void __launch_bounds__(256) k_reparam(const float* __restrict__ heads, int B, int L, int row0, uint32_t key, int train,
                                                  float* __restrict__ z, float* __restrict__ eps, double* __restrict__ kl_out) {
     __shared__ double red[4];
     double s = 0;
@@ -65,7 +66,7 @@ __global__ void __launch_bounds__(256) k_reparam(const float* __restrict__ heads
         const int b = i / L, j = i - b * L;
         const float m = heads[(size_t)b * 2 * L + j], l = heads[(size_t)b * 2 * L + L + j];
         float e = 0.f;
-        if (train) e = normal_hash(key, (uint32_t)i);
+        if (train) e = normal_hash(key, (uint32_t)((row0 + b) * L + j));
         eps[i] = e;
         z[i] = m + e * expf(0.5f * l);
         s += (double)(1.f + l - m * m - expf(l));
@@ -75,11 +76,12 @@ __global__ void __launch_bounds__(256) k_reparam(const float* __restrict__ heads
 }
 
 // dmu = dz + lambda_kl * mu / n;  dlv = dz * eps * 0.5 * exp(lv/2) + lambda_kl * 0.5 * (exp(lv) - 1) / n;  rows [dmu | dlv]
+// (n_kl: the n of the KL mean, B * L on a single device, the global batch's under data parallelism)
 __global__ void __launch_bounds__(256) k_reparam_bwd(const float* __restrict__ dz, const float* __restrict__ heads,
-                                                     const float* __restrict__ eps, int B, int L, float lambda_kl,
+                                                     const float* __restrict__ eps, int B, int L, float lambda_kl, int n_kl,
                                                      float* __restrict__ dheads) {
     const int n = B * L;
-    const float k = lambda_kl / (float)n;
+    const float k = lambda_kl / (float)n_kl;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const int b = i / L, j = i - b * L;
         const size_t o = (size_t)b * 2 * L + j;
@@ -518,13 +520,16 @@ __global__ void __launch_bounds__(256) k_ssim_combine(float* __restrict__ g1, co
     }
 }
 
-// per (b,c): f_s = relu(mean), M = prod f_s^w_s, loss += (1 - M)/BC; kappa[bc][s] = -lambda_ssim/BC * w_s * M / f_s / N_s
+// per (b,c): f_s = relu(mean), M = prod f_s^w_s, loss += (1 - M)/loss_div; kappa[bc][s] = -lambda_ssim/BC_g * w_s * M / f_s / N_s
 // sums: [scale][BC][2]; nvalid.v[s] = (H_s-10)*(W_s-10), a kernel argument (no per-step host-to-device copy).  one block
+// BC_g: the (b, c) planes of the mean (BC on a single device, the global batch's under data parallelism, where loss_div 1 leaves
+// the raw sum for the all-reduce); loss_div BC: the mean
 struct ScaleCounts {
     int v[kScales];
 };
-__global__ void __launch_bounds__(256) k_msssim_finalize(const double* __restrict__ sums, int BC, ScaleCounts nvalid,
-                                                         float lambda_ssim, double* __restrict__ loss_out, float* __restrict__ kappa) {
+__global__ void __launch_bounds__(256) k_msssim_finalize(const double* __restrict__ sums, int BC, int BC_g, double loss_div,
+                                                         ScaleCounts nvalid, float lambda_ssim, double* __restrict__ loss_out,
+                                                         float* __restrict__ kappa) {
     __shared__ double red[4];
     double acc = 0;
     for (int bc = threadIdx.x; bc < BC; bc += 256) {
@@ -537,10 +542,10 @@ __global__ void __launch_bounds__(256) k_msssim_finalize(const double* __restric
         acc += 1.0 - M;
         for (int s = 0; s < kScales; s++)
             kappa[bc * kScales + s] =
-                f[s] > 0.0 ? (float)(-(double)lambda_ssim / BC * c_ms_weights[s] * M / f[s] / (double)nvalid.v[s]) : 0.f;
+                f[s] > 0.0 ? (float)(-(double)lambda_ssim / BC_g * c_ms_weights[s] * M / f[s] / (double)nvalid.v[s]) : 0.f;
     }
     const double t = block_sum(acc, red);
-    if (threadIdx.x == 0) *loss_out = t / (double)BC;
+    if (threadIdx.x == 0) *loss_out = t / loss_div;
 }
 
 // gradient of the scale's term with respect to its input x: G(q) = kappa * [ (G^T A)(q) + 2 x(q) (G^T Bm)(q) + y(q) (G^T Cm)(q) ]
@@ -611,16 +616,17 @@ __global__ void __launch_bounds__(256) k_sigmoid_gather(const float* __restrict_
     }
 }
 
-// du = scale * (lambda_mse * 2 (y - t) / n + gssim) * y (1 - y);  mse_out += sum (y-t)^2 / n
-// (scale: the data-parallel weight local / global batch of this rank's gradient, 1 on a single device)
+// du = scale * (lambda_mse * 2 (y - t) / n_g + gssim) * y (1 - y);  mse_out += sum (y-t)^2 / mse_div
+// (scale: the data-parallel weight local / global batch of this rank's gradient, 1 on a single device; n_g: the n of the mean,
+// n itself but for a data-parallel shard of a global batch, whose mse_div 1 leaves the raw sum for the all-reduce)
 // du_sum (single-channel outputs): += sum du = the last layer's bias gradient, in the pass that writes du
 __global__ void __launch_bounds__(256) k_vae_loss_grad(const float* __restrict__ y, const float* __restrict__ t,
-                                                       const float* __restrict__ gssim, long long n, float lambda_mse, float scale,
-                                                       float* __restrict__ du, double* __restrict__ mse_out,
-                                                       double* __restrict__ du_sum) {
+                                                       const float* __restrict__ gssim, long long n, long long n_g, double mse_div,
+                                                       float lambda_mse, float scale, float* __restrict__ du,
+                                                       double* __restrict__ mse_out, double* __restrict__ du_sum) {
     __shared__ double red[4];
     double s = 0, sb = 0;
-    const float k = 2.f * lambda_mse / (float)n;
+    const float k = 2.f * lambda_mse / (float)n_g;
     auto one = [&](float yv, float tv, float gs) {
         const float d = yv - tv;
         s += (double)d * (double)d;
@@ -642,7 +648,7 @@ __global__ void __launch_bounds__(256) k_vae_loss_grad(const float* __restrict__
         }
     }
     const double tt = block_sum(s, red);
-    if (threadIdx.x == 0) atomicAdd(mse_out, tt / (double)n);
+    if (threadIdx.x == 0) atomicAdd(mse_out, tt / mse_div);
     if (du && du_sum) {
         __syncthreads();
         const double tb = block_sum(sb, red);
@@ -675,10 +681,11 @@ __global__ void __launch_bounds__(256) k_add_relu_bwd(float* __restrict__ g1, co
         g1[i] = h[i] > 0.f ? g1[i] + g2[i] : 0.f;
 }
 
-// parts = {mse, kl sum, 1 - ms_ssim}: slot = {mse, kl mean, ssim loss, weighted total}
-__global__ void k_loss_slot(const double* __restrict__ parts, double kl_count, double l_mse, double l_kl, double l_ssim,
-                            double* __restrict__ slot) {
-    const double mse = parts[0], kl = parts[1] / kl_count, sl = parts[2];
+// parts = {mse, kl sum, 1 - ms_ssim} (a data-parallel shard's: {sum (y-t)^2, kl sum, sum (1 - M)}, all-reduced, with the global
+// batch's counts; 1 where a part already is a mean): slot = {mse, kl mean, ssim loss, weighted total}
+__global__ void k_loss_slot(const double* __restrict__ parts, double mse_count, double kl_count, double ssim_count, double l_mse,
+                            double l_kl, double l_ssim, double* __restrict__ slot) {
+    const double mse = parts[0] / mse_count, kl = parts[1] / kl_count, sl = parts[2] / ssim_count;
     slot[0] = mse, slot[1] = kl, slot[2] = sl, slot[3] = l_mse * mse + l_kl * kl + l_ssim * sl;
 }
 

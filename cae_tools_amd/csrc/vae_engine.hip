@@ -33,6 +33,9 @@ struct vae_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets, 
     int64_t off_ssum = 0, off_part = 0;   // doubles: [scale][BC][2]; parts {mse, kl, ssim}
     double l_mse = 1, l_kl = 1, l_ssim = 1;
     double grad_scale = 1.0;     // data-parallel half-step: every loss gradient is scaled by local / global batch at its source
+    // the data-parallel shard of the current vae_*_sync call (ShardScope); a plain step leaves them at their defaults
+    int row0 = 0;                // the shard's first row in the global batch: the noise hash counts global element indices
+    int loss_batch = 0;          // rows behind the loss means and their gradient coefficients (the global batch); 0: the local batch
     uint32_t seed = 0;
     bool row_kernels = true;     // MS-SSIM passes: row-streaming kernels (vae_set_kernel_mode 1) or the LDS tile kernels (0)
     vae::Gauss gauss;
@@ -53,19 +56,23 @@ uint32_t noise_key(const vae_engine* e) {
 // ---- the two call-backs of the trunk (trunk_api.h) ----------------------------------------------------------------------
 void hook_reparam(void* user, hipStream_t s, const float* heads, int B, int latent, int train, float* z) {
     vae_engine* e = static_cast<vae_engine*>(user);
-    hipLaunchKernelGGL(vae::k_reparam, dim3(1), dim3(256), 0, s, heads, B, latent, noise_key(e), train, z, e->f(e->eps), e->parts() + 1);
+    hipLaunchKernelGGL(vae::k_reparam, dim3(1), dim3(256), 0, s, heads, B, latent, e->row0, noise_key(e), train, z, e->f(e->eps),
+                       e->parts() + 1);
 }
 
 void hook_reparam_bwd(void* user, hipStream_t s, const float* gz, const float* heads, int B, int latent, float* gheads) {
     vae_engine* e = static_cast<vae_engine*>(user);
     hipLaunchKernelGGL(vae::k_reparam_bwd, dim3(blocks_for((long long)B * latent, 65536)), dim3(256), 0, s, gz, heads, e->f(e->eps), B, latent,
-                       (float)(e->l_kl * e->grad_scale), gheads);
+                       (float)(e->l_kl * e->grad_scale), (e->loss_batch ? e->loss_batch : B) * latent, gheads);
 }
 
 // y, target batch, MS-SSIM + MSE; with want_grad the gradient wrt the last layer's raw output goes to dec.back().gz
+// (a data-parallel shard - loss_batch set - leaves raw sums in the parts, and its gradient coefficients use the global counts)
 int loss(vae_engine* e, int which, const int32_t* perm, int64_t start, int B, int slot, bool want_grad, double* parts) {
     const int C = e->out_c, H = e->out_h, W = e->out_w, BC = B * C;
     const long long E = (long long)C * H * W, n = (long long)B * E;
+    const bool shard = e->loss_batch > 0;
+    const int Bg = shard ? e->loss_batch : B;
     if (!e->row_kernels)   // (the row-kernel path forms the finest level inside its pyramid launch)
         hipLaunchKernelGGL(vae::k_sigmoid_gather, dim3(blocks_for(n, 65536)), dim3(256), 0, e->stream, cae_internal::trunk_raw_output(e->trunk), e->ds[which].t, perm,
                            (long long)start, B, E, e->f(e->sx[0]), e->f(e->sy[0]));
@@ -112,7 +119,7 @@ int loss(vae_engine* e, int which, const int32_t* perm, int64_t start, int B, in
     }
     vae::ScaleCounts nv;
     for (int s = 0, hh = H, ww = W; s < vae::kScales; s++, hh /= 2, ww /= 2) nv.v[s] = (hh - vae::kHalo) * (ww - vae::kHalo);
-    hipLaunchKernelGGL(vae::k_msssim_finalize, dim3(1), dim3(256), 0, e->stream, ssum, BC, nv,
+    hipLaunchKernelGGL(vae::k_msssim_finalize, dim3(1), dim3(256), 0, e->stream, ssum, BC, Bg * C, shard ? 1.0 : (double)BC, nv,
                        (float)e->l_ssim, parts + 2, e->f(e->kappa));
     if (want_grad && e->row_kernels) {
         // the four coarse scales' own terms in one launch, their pooling chain folded into scale 1's map, then the finest scale
@@ -148,7 +155,8 @@ int loss(vae_engine* e, int which, const int32_t* perm, int64_t start, int B, in
         }
     }
     hipLaunchKernelGGL(vae::k_vae_loss_grad, dim3(blocks_for(n, 1024)), dim3(256), 0, e->stream, e->f(e->sx[0]), e->f(e->sy[0]),
-                       want_grad ? e->f(e->sG[0]) : (const float*)nullptr, n, (float)e->l_mse, (float)e->grad_scale,
+                       want_grad ? e->f(e->sG[0]) : (const float*)nullptr, n, (long long)Bg * E, shard ? 1.0 : (double)n,
+                       (float)e->l_mse, (float)e->grad_scale,
                        want_grad ? cae_internal::trunk_output_gradient(e->trunk) : (float*)nullptr, parts + 0,
                        want_grad && C == 1 ? cae_internal::trunk_output_bias_acc(e->trunk) : (double*)nullptr);
     (void)slot;
@@ -156,32 +164,52 @@ int loss(vae_engine* e, int which, const int32_t* perm, int64_t start, int B, in
     return CAE_OK;
 }
 
+// A data-parallel shard (vae_forward_backward_sync / vae_eval_step_sync): the all-reduce callback and, for training, the
+// BatchNorm mode handed to the trunk.  The default is a plain single-device step.
+struct Shard {
+    cae_allreduce_fn fn = nullptr;
+    void* user = nullptr;
+    int world = 0;           // >= 1: SyncBN over the global batch; 0: per-rank statistics
+    int global_batch = 0;
+};
+
 int step_common(vae_engine* e, int which, const int32_t* perm, int64_t start, int batch, int slot, bool train, float* grads_out,
-                bool optimise, double grad_scale = 1.0) {
-    int rc = check_batch(e, "vae", which, start, batch, slot, true);
-    if (rc) return rc;
+                bool optimise, double grad_scale = 1.0, const Shard& sh = Shard{}) {
+    int rc;
+    if (!sh.fn && (rc = check_batch(e, "vae", which, start, batch, slot, true))) return rc;   // (a shard is checked by its caller)
     e->grad_scale = grad_scale;
     const long long E = (long long)e->in_c * e->in_h * e->in_w;
-    hipLaunchKernelGGL(k_gather, dim3(blocks_for((long long)batch * E, 65536)), dim3(256), 0, e->stream, e->ds[which].x, perm, (long long)start,
-                       batch, E, e->f(e->xb));
+    if (batch > 0)
+        hipLaunchKernelGGL(k_gather, dim3(blocks_for((long long)batch * E, 65536)), dim3(256), 0, e->stream, e->ds[which].x, perm,
+                           (long long)start, batch, E, e->f(e->xb));
     double* parts = e->parts();
     // the MS-SSIM sums and the loss parts lie next to each other: one fill
     HIP_TRY(hipMemsetAsync(e->ws + e->off_ssum, 0, (size_t)(e->off_part + 4 * sizeof(double) - e->off_ssum), e->stream));
-    // trunk forward: encoder stack, Linear + heads, z (call-back), decoder stack; the last layer leaves its raw output
-    if ((rc = cae_internal::trunk_forward(e->trunk, e->f(e->xb), batch, train, true, nullptr))) return rc;
+    // trunk forward: encoder stack, Linear + heads, z (call-back), decoder stack; the last layer leaves its raw output.  A training
+    // shard's trunk passes its BatchNorm tables to the callback (and runs for an empty shard too: the other ranks wait on them)
+    const TrunkSync ts{train ? sh.fn : nullptr, sh.user, sh.world, sh.global_batch};
+    if ((batch > 0 || ts.fn) && (rc = cae_internal::trunk_forward(e->trunk, e->f(e->xb), batch, train, true, nullptr, ts))) return rc;
     // KL is a mean over B*latent
-    if ((rc = loss(e, which, perm, start, batch, slot, train, parts))) return rc;
-    hipLaunchKernelGGL(vae::k_loss_slot, dim3(1), dim3(1), 0, e->stream, parts, (double)batch * e->latent, e->l_mse, e->l_kl, e->l_ssim,
-                       e->losses(slot));
+    if (batch > 0 && (rc = loss(e, which, perm, start, batch, slot, train, parts))) return rc;
+    if (sh.fn) {
+        // the shard's raw sums {squared error, KL term, 1 - MS-SSIM per (b, c)} over the ranks: the global batch's means
+        if (sh.fn(sh.user, parts, 3) != 0) return fail(CAE_ERR_STATE, "vae: the all-reduce callback failed for the loss table");
+        const double bg = sh.global_batch;
+        hipLaunchKernelGGL(vae::k_loss_slot, dim3(1), dim3(1), 0, e->stream, parts, bg * e->out_c * e->out_h * e->out_w, bg * e->latent,
+                           bg * e->out_c, e->l_mse, e->l_kl, e->l_ssim, e->losses(slot));
+    } else {
+        hipLaunchKernelGGL(vae::k_loss_slot, dim3(1), dim3(1), 0, e->stream, parts, 1.0, (double)batch * e->latent, 1.0, e->l_mse,
+                           e->l_kl, e->l_ssim, e->losses(slot));
+    }
     if (train) {
         // the last layer's bias gradient = sum of dL/d(raw output) per channel (the ConvAE path gets it from its fused loss
         // epilogue; here the loss is ours)
         const int HW = e->out_h * e->out_w;
         const int chunks = (int)std::max<long long>(1, std::min<long long>(((long long)batch * HW + 2047) / 2048, 64));
-        if (e->out_c > 1)     // (a single-channel output's sum rides in k_vae_loss_grad)
+        if (e->out_c > 1 && batch > 0)     // (a single-channel output's sum rides in k_vae_loss_grad)
             hipLaunchKernelGGL(k_chan_sums, dim3(chunks, e->out_c), dim3(256), 0, e->stream, cae_internal::trunk_output_gradient(e->trunk),
                            (long long)e->out_c * HW, batch, HW, cae_internal::trunk_output_bias_acc(e->trunk), 1, 0);
-        if ((rc = cae_internal::trunk_backward(e->trunk, e->f(e->xb), batch))) return rc;
+        if ((batch > 0 || ts.fn) && (rc = cae_internal::trunk_backward(e->trunk, e->f(e->xb), batch, ts))) return rc;
         if (grads_out) {
             if ((rc = cae_internal::trunk_gradients(e->trunk, grads_out, 1.0))) return rc;   // already scaled at the sources
             if (optimise) return fail(CAE_ERR_ARG, "vae: gradients are either handed out or applied");
@@ -191,6 +219,26 @@ int step_common(vae_engine* e, int which, const int32_t* perm, int64_t start, in
         }
     }
     HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+// ---- data-parallel shards (vae_forward_backward_sync / vae_eval_step_sync) -----------------------------------------------
+// The shard's place in the global batch, for the duration of one call
+struct ShardScope {
+    vae_engine* e;
+    ShardScope(vae_engine* e_, int row0, int global_batch) : e(e_) { e->row0 = row0, e->loss_batch = global_batch; }
+    ~ShardScope() { e->row0 = 0, e->loss_batch = 0; }
+};
+
+// the checks of check_batch for a shard, which may be empty (batch 0: global batch < world, or the tail of a partial batch)
+int check_shard(const vae_engine* e, const char* who, int which, int64_t start, int batch, int row0, int global_batch, int world,
+                int slot, cae_allreduce_fn fn) {
+    if (!fn || world < 0 || global_batch < 1 || batch < 0 || row0 < 0 || (int64_t)row0 + batch > global_batch)
+        return fail(CAE_ERR_ARG, "%s: bad argument (batch %d at row %d of %d, world %d)", who, batch, row0, global_batch, world);
+    if (batch > 0) return check_batch(e, who, which, start, batch, slot, true);
+    if (!e->ws) return fail(CAE_ERR_STATE, "%s: engine is not bound", who);
+    if (which < 0 || which > 1 || !e->ds[which].x || !e->ds[which].t) return fail(CAE_ERR_STATE, "%s: data set %d is not set", who, which);
+    if (slot < 0 || slot >= kStepLossSlots) return fail(CAE_ERR_ARG, "%s: loss slot %d outside 0..%d", who, slot, kStepLossSlots - 1);
     return CAE_OK;
 }
 
@@ -291,6 +339,13 @@ int vae_forward_backward(vae_engine* e, int which, const int32_t* perm, int64_t 
     if (!grads) return fail(CAE_ERR_ARG, "vae_forward_backward: null gradient buffer");
     return step_common(e, which, perm, start, batch, loss_slot, true, grads, false, grad_scale);
 }
+int vae_forward_backward_sync(vae_engine* e, int which, const int32_t* perm, int64_t start, int batch, int row0, int global_batch,
+                              int world, int loss_slot, float* grads, cae_allreduce_fn fn, void* user) {
+    if (!e || !grads) return fail(CAE_ERR_ARG, "vae_forward_backward_sync: bad argument");
+    if (int rc = check_shard(e, "vae_forward_backward_sync", which, start, batch, row0, global_batch, world, loss_slot, fn)) return rc;
+    ShardScope scope(e, row0, global_batch);
+    return step_common(e, which, perm, start, batch, loss_slot, true, grads, false, 1.0, Shard{fn, user, world, global_batch});
+}
 int vae_apply_gradients(vae_engine* e, const float* grads) {
     if (!e || !e->ws || !grads) return fail(CAE_ERR_ARG, "vae_apply_gradients: bad argument");
     e->step += 1;     // (on the device vae_forward_backward's first kernel counted it)
@@ -298,6 +353,13 @@ int vae_apply_gradients(vae_engine* e, const float* grads) {
 }
 int vae_eval_step(vae_engine* e, int which, const int32_t* perm, int64_t start, int batch, int loss_slot) {
     return step_common(e, which, perm, start, batch, loss_slot, false, nullptr, false);
+}
+int vae_eval_step_sync(vae_engine* e, int which, const int32_t* perm, int64_t start, int batch, int row0, int global_batch,
+                       int loss_slot, cae_allreduce_fn fn, void* user) {
+    if (!e) return fail(CAE_ERR_ARG, "vae_eval_step_sync: null engine");
+    if (int rc = check_shard(e, "vae_eval_step_sync", which, start, batch, row0, global_batch, 0, loss_slot, fn)) return rc;
+    ShardScope scope(e, row0, global_batch);
+    return step_common(e, which, perm, start, batch, loss_slot, false, nullptr, false, 1.0, Shard{fn, user, 0, global_batch});
 }
 int vae_score(vae_engine* e, const float* x, int batch, float* y) {
     if (int rc = check_score(e, "vae", x, batch, y)) return rc;
@@ -307,5 +369,16 @@ int vae_score(vae_engine* e, const float* x, int batch, float* y) {
 int vae_loss_slots(const vae_engine* e) { return e ? kStepLossSlots : 0; }
 int vae_read_losses(vae_engine* e, int first_slot, int count, double* out) { return read_losses(e, "vae", first_slot, count, out); }
 int vae_sync(vae_engine* e) { return sync(e, "vae"); }
+int vae_debug_read(vae_engine* e, const char* what, float* out, int64_t count) {
+    if (!e || !e->ws || !what || !out || count < 0) return fail(CAE_ERR_ARG, "vae_debug_read: bad argument");
+    const float* src = nullptr;
+    if (!strcmp(what, "eps")) src = e->f(e->eps);
+    else if (!strcmp(what, "z")) src = cae_internal::trunk_latent(e->trunk);
+    else return fail(CAE_ERR_ARG, "vae_debug_read: unknown tensor '%s' (eps, z)", what);
+    if (count > (int64_t)e->max_batch * e->latent) return fail(CAE_ERR_ARG, "vae_debug_read: %lld floats exceed the tensor", (long long)count);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+    return CAE_OK;
+}
 
 }  // extern "C"

@@ -12,6 +12,7 @@ import time
 import numpy as np
 import torch
 
+from .. import dp as _dp
 from .. import vae_engine as _ve
 from ..utils.model_database import ModelDatabase
 from ._params import ParamBag, add_batchnorm, add_conv
@@ -65,6 +66,10 @@ class VarAEModel(EngineModel):
         self.history = {"train_loss": [], "test_loss": [], "nr_epochs": 0}
         self.db = ModelDatabase(database_path) if database_path else None
         self._engine = None
+        self.timing = None      # set by train(): seconds and images of the epoch loop, and the world size
+        # under a torch.distributed.run launch (one process per GPU) batch_size stays the GLOBAL batch; sync_bn=True computes
+        # BatchNorm statistics over it (N ranks reproduce the single-device step), False keeps per-rank statistics
+        self.sync_bn = True
 
     def get_parameters(self):
         return {"type": "VarAEModel", "input_shape": list(self.input_shape), "output_shape": list(self.output_shape),
@@ -92,24 +97,63 @@ class VarAEModel(EngineModel):
 
     def train(self, input_variables, output_variable, training_ds, testing_ds, model_path="", training_paths="",
               testing_paths="", mask_variable_name=None):
+        # Data parallel (build-only, as UNET.train()): under a torch.distributed.run launch every rank holds the model and both
+        # data sets and takes its rows of each frozen GLOBAL batch (dp.shard_bounds); the engine's sync entry points sum the
+        # BatchNorm, loss and gradient tables over the ranks, and the noise of a row is that of its global index, so that a step
+        # is the single-device step at batch_size.  Rank 0 prints and saves.
+        dist = _dp.ensure_process_group()
+        (world, rank) = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
+        lead = rank == 0
         (train_ds, test_ds, train_perm, test_perm) = self._train_prologue(input_variables, output_variable, training_ds,
                                                                           testing_ds)
-        print(f"Running on device: {torch.device('cuda')}")
+        if dist is not None:    # one frozen shuffle for everybody: rank 0's draw
+            box = [train_perm, test_perm]
+            dist.broadcast_object_list(box, src=0)
+            (train_perm, test_perm) = box
+        if lead:
+            print(f"Running on device: {torch.device('cuda')}")
         start = time.time()
-        eng = self._get_engine(int(self.batch_size))
+        eng = self._get_engine(-(-int(self.batch_size) // world))   # a rank's share of a global batch
         eng.set_hyper(lr=self.lr, weight_decay=self.weight_decay, lambda_mse=self.lambda_mse, lambda_kl=self.lambda_kl,
                       lambda_ssim=self.lambda_ssim, seed=self.noise_seed)
         eng.reset_optimizer()
         eng.set_dataset(_ve.TRAIN, train_ds.device_inputs(), train_ds.device_outputs())
         eng.set_dataset(_ve.TEST, test_ds.device_inputs(), test_ds.device_outputs())
         (train_idx, test_idx) = (eng.upload_perm(train_perm), eng.upload_perm(test_perm))
+        par = None
+        if dist is not None:
+            par = _dp.DataParallel(_dp.GradientHalfSteps(eng), dist, sync_bn=self.sync_bn)
+            par.broadcast_parameters(0)     # rank 0's initial (or loaded) weights, running statistics and moments everywhere
+
+        def one_pass(which, idx, n, train):
+            if par is None:
+                return eng.run_batches(which, idx, n, self.batch_size, train)
+            if not train and not self.sync_bn:
+                par.broadcast_buffers(0)    # every rank scores with the same running statistics
+            return par.run_batches(which, idx, n, self.batch_size, train=train)
+
         train_loss = test_loss = 0.0
+        eng.sync()
+        loop_start = time.perf_counter()
         for epoch in range(self.nr_epochs):
-            train_loss = float(np.mean([l[3] for l in eng.run_batches(_ve.TRAIN, train_idx, len(train_ds), self.batch_size, True)]))
+            train_loss = float(np.mean([l[3] for l in one_pass(_ve.TRAIN, train_idx, len(train_ds), True)]))
             if epoch % self.test_interval == 0:
-                test_loss = float(np.mean([l[3] for l in eng.run_batches(_ve.TEST, test_idx, len(test_ds), self.batch_size, False)]))
+                test_loss = float(np.mean([l[3] for l in one_pass(_ve.TEST, test_idx, len(test_ds), False)]))
                 self.history["train_loss"].append(train_loss)
                 self.history["test_loss"].append(test_loss)
-                print("%5d %.6f %.6f" % (epoch, train_loss, test_loss))
+                if lead:
+                    print("%5d %.6f %.6f" % (epoch, train_loss, test_loss))
+        eng.sync()
+        self.timing = {"epoch_loop_seconds": time.perf_counter() - loop_start, "train_images": len(train_ds) * self.nr_epochs,
+                       "epochs": self.nr_epochs, "world": world}
+        if par is not None and not self.sync_bn:
+            par.broadcast_buffers(0)
         return self._train_epilogue(start, train_ds, test_ds, train_loss, test_loss, input_variables, output_variable,
-                                    model_path, training_paths, testing_paths)
+                                    model_path, training_paths, testing_paths, lead=lead)
+
+    def _score_device(self, x):
+        # an engine that exists is used as it is (score() walks the array in chunks of its max_batch): a data-parallel
+        # rank's engine holds a share of the batch and is not re-created for scoring
+        if self._engine is not None:
+            return self._engine.score(x)
+        return super()._score_device(x)

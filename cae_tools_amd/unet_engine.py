@@ -7,8 +7,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._engine_base import TEST, TRAIN, SpecPlan, SteppedEngine, require_gpu  # noqa: F401  (public names)
-from . import _lib
+from ._engine_base import TEST, TRAIN, ShardedSteps, SpecPlan, SteppedEngine, require_gpu  # noqa: F401  (public names)
 from ._lib import CaeError, check
 
 
@@ -34,7 +33,7 @@ class UnetPlan(SpecPlan):
         return plan
 
 
-class UnetEngine(SteppedEngine, UnetPlan):
+class UnetEngine(ShardedSteps, SteppedEngine, UnetPlan):
 
     LOSSES_PER_BATCH = 2    # (mse, pearson loss)
 
@@ -67,54 +66,6 @@ class UnetEngine(SteppedEngine, UnetPlan):
     def _check_train_batch(self, batch):
         if int(batch) == 1:   # what nn.BatchNorm1d raises in the reference for a one-sample training batch
             raise ValueError(f"Expected more than 1 value per channel when training, got input size torch.Size([1, {self.fc_size}])")
-
-    # ---- data-parallel shards (unet_forward_backward_sync / unet_eval_step_sync, include/cae_unet.h) ------------------
-    def _with_allreduce(self, call, allreduce):
-        """call(cb) with cb the C callback that hands `allreduce` a float64 CUDA view of each table the library passes (inside
-        `with torch.cuda.stream(self.stream)`: it must sum the view over the ranks in place, enqueued on that stream); an
-        exception raised by `allreduce` is raised here after the C call returns"""
-        base = (self.workspace.data_ptr() + 255) // 256 * 256
-        pad = base - self.workspace.data_ptr()
-        failure = []
-
-        def _cb(user, table_ptr, count):
-            try:
-                off = pad + (table_ptr - base)
-                with torch.cuda.stream(self.stream):
-                    allreduce(self.workspace[off:off + 8 * count].view(torch.float64))
-                return 0
-            except Exception as ex:
-                failure.append(ex)
-                return 1
-
-        cb = _lib.ALLREDUCE_FN(_cb)
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        rc = call(cb)
-        if failure:
-            raise failure[0]
-        check(rc)
-
-    def forward_backward_sync(self, which, perm, start, size, row0, global_batch, world, allreduce, out=None, slot=0):
-        """forward_backward of this rank's rows [row0, row0 + size) of a global batch (samples perm[start:start+size]; size 0
-        is allowed) with the single-device arithmetic at global_batch: loss denominators over the global batch, dropout masks
-        of the global rows, and - world >= 1 - BatchNorm statistics over the global batch (world 0: per rank).  `allreduce(t)`
-        sums each fp64 table over the ranks in place.  The loss slot holds the global batch's (mse, pearson loss); the
-        gradient is this rank's share of the global loss's (the SUM over the ranks is the gradient)."""
-        self._check_train_batch(global_batch if world > 0 else size)
-        grads = out if out is not None else torch.empty(self.n_param, dtype=torch.float32, device=self.device)
-        self._with_allreduce(lambda cb: self.lib.unet_forward_backward_sync(
-            self.handle, which, None if perm is None else perm.data_ptr(), int(start), int(size), int(row0), int(global_batch),
-            int(world), int(slot), grads.data_ptr(), cb, None), allreduce)
-        self._tracked()
-        if out is None:
-            self.sync()
-        return grads
-
-    def eval_step_sync(self, which, perm, start, size, row0, global_batch, allreduce, slot=0):
-        """eval_step of this rank's shard of a global batch: the loss slot holds the global batch's losses"""
-        self._with_allreduce(lambda cb: self.lib.unet_eval_step_sync(
-            self.handle, which, None if perm is None else perm.data_ptr(), int(start), int(size), int(row0), int(global_batch),
-            int(slot), cb, None), allreduce)
 
     def debug_read(self, what, shape):
         out = np.empty(shape, dtype=np.float32)

@@ -1,12 +1,13 @@
 """VaeEngine — Python owner of one libcae_hip 'var' engine (include/cae_vae.h) and of its device memory (torch tensors as
 containers, as in engine.py / unet_engine.py)."""
+import numpy as np
 import torch
 
-from ._engine_base import TEST, TRAIN, SpecPlan, SteppedEngine, require_gpu  # noqa: F401  (public names)
+from ._engine_base import TEST, TRAIN, ShardedSteps, SpecPlan, SteppedEngine, require_gpu  # noqa: F401  (public names)
 from ._lib import check
 
 
-class VaeEngine(SteppedEngine, SpecPlan):
+class VaeEngine(ShardedSteps, SteppedEngine, SpecPlan):
 
     PREFIX = "vae_"
     LOSSES_PER_BATCH = 4    # (mse, kl, 1 - ms_ssim, total)
@@ -26,3 +27,9 @@ class VaeEngine(SteppedEngine, SpecPlan):
     def set_kernel_mode(self, mode):
         """1 (default): row-streaming MS-SSIM kernels; 0: the LDS tile kernels (same results to fp32 rounding; A/B and tests)"""
         check(self.lib.vae_set_kernel_mode(self.handle, int(mode)))
+
+    def debug_read(self, what, shape):
+        """the last training forward's noise ("eps") or latent vector ("z"), rows of (batch, latent)"""
+        out = np.empty(shape, dtype=np.float32)
+        check(self.lib.vae_debug_read(self.handle, what.encode(), out.ctypes.data, out.size))
+        return out

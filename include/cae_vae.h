@@ -57,10 +57,28 @@ int vae_forward_backward(vae_engine* e, int which, const int32_t* perm_dev, int6
  * grads_dev (torch.distributed on the same stream), then each applies the Adam step to the reduced gradient. */
 int vae_apply_gradients(vae_engine* e, const float* grads_dev);
 int vae_eval_step(vae_engine* e, int which, const int32_t* perm_dev, int64_t start, int batch, int loss_slot);
+/* Data parallelism with the single-device arithmetic (the shape of unet_forward_backward_sync, cae_unet.h): this rank holds rows
+ * [row0, row0 + batch) of a global batch of global_batch rows (samples perm[start .. start+batch)), and a step equals the
+ * one-device step at global_batch up to fp32 summation order.  The library calls fn(user, table_dev, count) (cae_hip.h) with
+ * every fp64 table that must be summed over the ranks, once it is complete and before anything reads it; fn leaves the
+ * element-wise SUM in place, ordered on the engine's stream, and returns 0.  The tables, in order: per BatchNorm layer its
+ * forward sums (encoder layers, then decoder layers), the loss table {sum of squared errors, sum of KL terms, sum over (b, c)
+ * of 1 - MS-SSIM} (3 doubles), then the BatchNorm backward sums from the decoder back to the first encoder layer: 2 calls per
+ * BatchNorm layer + 1.  The noise eps of global row r is that of row r of a whole batch.  world >= 1: the BatchNorm statistics
+ * are over the global batch (SyncBN); world 0: per rank (fn then sees the loss table only).  The loss slot receives the global
+ * batch's {mse, kl, 1 - ms_ssim, total}; grads_dev receives this rank's share of the gradient of the global loss: the SUM over
+ * the ranks is the gradient, which vae_apply_gradients applies.  batch 0 (an empty shard) is allowed and makes the same calls.
+ * vae_eval_step_sync: the eval-mode counterpart (running statistics: the loss table only). */
+int vae_forward_backward_sync(vae_engine* e, int which, const int32_t* perm_dev, int64_t start, int batch, int row0,
+                              int global_batch, int world, int loss_slot, float* grads_dev, cae_allreduce_fn fn, void* user);
+int vae_eval_step_sync(vae_engine* e, int which, const int32_t* perm_dev, int64_t start, int batch, int row0,
+                       int global_batch, int loss_slot, cae_allreduce_fn fn, void* user);
 int vae_score(vae_engine* e, const float* x_dev, int batch, float* y_dev);
 int vae_loss_slots(const vae_engine* e);
 int vae_read_losses(vae_engine* e, int first_slot, int count, double* out_host);   /* 4 doubles per slot */
 int vae_sync(vae_engine* e);
+/* blocking debug read of the last training forward's noise "eps" or latent "z" ((batch, latent) rows, count floats) */
+int vae_debug_read(vae_engine* e, const char* what, float* out_host, int64_t count);
 
 #ifdef __cplusplus
 }
