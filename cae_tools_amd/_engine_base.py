@@ -106,6 +106,31 @@ class EngineBase:
             check(fn(self.handle, x[lo:hi].data_ptr(), hi - lo, out[lo:hi].data_ptr()))
         return out
 
+    def _with_allreduce(self, call, allreduce):
+        """call(cb) with cb the C callback that hands `allreduce` a float64 CUDA view of each table the library passes (inside
+        `with torch.cuda.stream(self.stream)`: it must sum the view over the ranks in place, enqueued on that stream); an
+        exception raised by `allreduce` is raised here after the C call returns"""
+        base = (self.workspace.data_ptr() + 255) // 256 * 256
+        pad = base - self.workspace.data_ptr()
+        failure = []
+
+        def _cb(user, table_ptr, count):
+            try:
+                off = pad + (table_ptr - base)
+                with torch.cuda.stream(self.stream):
+                    allreduce(self.workspace[off:off + 8 * count].view(torch.float64))
+                return 0
+            except Exception as ex:
+                failure.append(ex)
+                return 1
+
+        cb = _lib.ALLREDUCE_FN(_cb)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        rc = call(cb)
+        if failure:
+            raise failure[0]
+        check(rc)
+
     def score(self, x):
         """eval-mode forward of (N, *in_shape) in chunks of max_batch -> (N, *out_shape) fp32 CUDA tensor"""
         x = self._prep(x)
@@ -273,31 +298,6 @@ class SteppedEngine:
 class ShardedSteps:
     """the global-batch entry points of a SteppedEngine (UNET, VAE: PREFIX + forward_backward_sync / eval_step_sync, the shape of
     include/cae_unet.h): a data-parallel rank's shard of a global batch with the single-device arithmetic at that batch"""
-
-    def _with_allreduce(self, call, allreduce):
-        """call(cb) with cb the C callback that hands `allreduce` a float64 CUDA view of each table the library passes (inside
-        `with torch.cuda.stream(self.stream)`: it must sum the view over the ranks in place, enqueued on that stream); an
-        exception raised by `allreduce` is raised here after the C call returns"""
-        base = (self.workspace.data_ptr() + 255) // 256 * 256
-        pad = base - self.workspace.data_ptr()
-        failure = []
-
-        def _cb(user, table_ptr, count):
-            try:
-                off = pad + (table_ptr - base)
-                with torch.cuda.stream(self.stream):
-                    allreduce(self.workspace[off:off + 8 * count].view(torch.float64))
-                return 0
-            except Exception as ex:
-                failure.append(ex)
-                return 1
-
-        cb = _lib.ALLREDUCE_FN(_cb)
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        rc = call(cb)
-        if failure:
-            raise failure[0]
-        check(rc)
 
     def forward_backward_sync(self, which, perm, start, size, row0, global_batch, world, allreduce, out=None, slot=0):
         """forward_backward of this rank's rows [row0, row0 + size) of a global batch (samples perm[start:start+size]; size 0

@@ -323,9 +323,7 @@ int sync_bn_table(cae_engine* e, const StepArgs& a, int bn_index) {
             return fail(CAE_ERR_STATE, "SyncBN: table %d passed out of order (position %zu)", bn_index, e->sync_pos);
         e->sync_pos++;
     }
-    if (a.sync_fn(a.sync_user, e->bn_stats(bn_index), n) != 0)
-        return fail(CAE_ERR_STATE, "the all-reduce callback failed for BatchNorm table %d", bn_index);
-    return CAE_OK;
+    return call_allreduce(ShardSync{a.sync_fn, a.sync_user}, "cae", e->bn_stats(bn_index), n);
 }
 
 // ---- specialised stride-2 kernels (kernels_s2.h): dispatch on (Cin, Cout, kh, kw) ----------------
@@ -2869,16 +2867,16 @@ float* trunk_output_gradient(cae_engine* e) { return e->fptr(e->off_glast); }
 double* trunk_output_bias_acc(cae_engine* e) { return e->gradacc() + e->dec.back().b_off; }
 float* trunk_latent(cae_engine* e) { return e->fptr(e->off_vz); }
 
-// sync.fn with sync.world >= 1: every launch that completes a BatchNorm sum table is followed by the callback (SyncBN over
+// sync.sync_bn(): every launch that completes a BatchNorm sum table is followed by the callback (SyncBN over
 // sync.global_batch rows: the means, variances and running-statistics updates use the global count, and the BatchNorm parameter
-// gradients are each rank's 1/world share of the global sums).  No callback or world 0: per-rank statistics, today's launches.
+// gradients are each rank's 1/world share of the global sums).  Otherwise per-rank statistics, today's launches.
 // The kernels that fold a BatchNorm table's production and consumption into one launch do not run here with a callback: the
 // fused k_head_fwd / k_tail_bwd (which recompute statistics inside one launch) never in trunk mode (head_plan / tail_plan refuse
 // a variational engine), k_conv_bwd_pair and the AdamConv0 fold never while syncing().  So a SyncBN trunk step takes the
 // per-layer path: every table is produced by one launch, handed to the callback, and only then read by the next.
-static StepArgs trunk_args(const float* x, int batch, bool train, const TrunkSync& sync) {
+static StepArgs trunk_args(const float* x, int batch, bool train, const ShardSync& sync) {
     StepArgs a{0, nullptr, batch, batch, batch, train, false, x, nullptr, false};
-    if (sync.fn && sync.world >= 1) {
+    if (sync.sync_bn()) {
         a.sync_fn = sync.fn;
         a.sync_user = sync.user;
         a.world = sync.world;
@@ -2920,7 +2918,7 @@ static int trunk_empty_shard(cae_engine* e, const StepArgs& a, bool fwd) {
     return CAE_OK;
 }
 
-int trunk_forward(cae_engine* e, const float* x, int batch, bool train, bool external_loss, float* yhat, const TrunkSync& sync) {
+int trunk_forward(cae_engine* e, const float* x, int batch, bool train, bool external_loss, float* yhat, const ShardSync& sync) {
     if (!e || !e->ws || !e->variational) return fail(CAE_ERR_STATE, "trunk_forward: not a bound trunk engine");
     const int min_batch = train && sync.fn ? 0 : 1;   // (an empty shard takes part in a data-parallel training step)
     if ((batch > 0 && !x) || batch < min_batch || batch > e->max_batch)
@@ -2944,7 +2942,7 @@ int trunk_forward(cae_engine* e, const float* x, int batch, bool train, bool ext
     return CAE_OK;
 }
 
-int trunk_backward(cae_engine* e, const float* x, int batch, const TrunkSync& sync) {
+int trunk_backward(cae_engine* e, const float* x, int batch, const ShardSync& sync) {
     if (!e || !e->ws || !e->variational) return fail(CAE_ERR_STATE, "trunk_backward: not a bound trunk engine");
     StepArgs a = trunk_args(x, batch, true, sync);
     a.external_loss = true;

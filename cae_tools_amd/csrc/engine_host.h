@@ -1,7 +1,8 @@
 // engine_host.h — host code shared by the four engine sources (engine.hip, unet_engine.hip, vae_engine.hip,
 // linear_engine.hip): error reporting, grid sizes, environment switches, the tensor table, workspace carving, and the state,
-// checks and entry-point bodies of the three stepped engines (UNET, var, Linear).  Internal C++ like trunk_api.h; not part
-// of the C ABI.
+// checks and entry-point bodies of the three stepped engines (UNET, var, Linear), and the data-parallel shard of the UNET and
+// var engines (ShardSync, which the var engine hands on to its ConvAE trunk).  Internal C++ like trunk_api.h; not part of the
+// C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -108,6 +109,30 @@ struct Carver {
 
 constexpr int kStepLossSlots = 4096;   // (the ConvAE engine has its own count)
 
+// A data-parallel rank's shard of a global batch (the *_forward_backward_sync / *_eval_step_sync entry points): rows
+// [row0, row0 + batch) of global_batch rows, and the caller's fn (cae_hip.h) that sums a fp64 table over the ranks in place.
+// world >= 1: the BatchNorm statistics are over the global batch (SyncBN); world 0: per rank.  The loss means are over the
+// global batch either way.  A default-constructed value is the single-device step.
+struct ShardSync {
+    cae_allreduce_fn fn = nullptr;
+    void* user = nullptr;
+    int world = 0;
+    int global_batch = 0;
+    int row0 = 0;   // random masks / noise hash the rows' global indices
+
+    bool sync_bn() const { return fn && world > 0; }   // BatchNorm sum tables go to fn too
+    // rows behind the BatchNorm statistics and behind the loss means, for a local batch of B rows
+    int stat_rows(int B) const { return sync_bn() ? global_batch : B; }
+    int loss_rows(int B) const { return fn ? global_batch : B; }
+};
+
+// fn of a shard on a complete table of `count` doubles; a failing callback is an error of engine `who`
+inline int call_allreduce(const ShardSync& s, const char* who, void* table, int64_t count) {
+    if (s.fn(s.user, table, count) != 0)
+        return fail(CAE_ERR_STATE, "%s: the all-reduce callback failed for a table of %lld doubles", who, (long long)count);
+    return CAE_OK;
+}
+
 struct DataSet {
     const float* x = nullptr;
     const float* t = nullptr;   // target, or nullptr (scoring only)
@@ -125,8 +150,16 @@ struct SteppedCore {
     int64_t off_losses = 0;   // kStepLossSlots x per_slot doubles
     int per_slot = 1;
     DataSet ds[2];
+    ShardSync shard;          // the shard of the current *_sync call (ShardScope); a plain step leaves the default
 
     double* losses(int slot) const { return reinterpret_cast<double*>(ws + off_losses) + (size_t)per_slot * slot; }
+};
+
+// a *_sync call's shard, for the duration of the call
+struct ShardScope {
+    SteppedCore* c;
+    ShardScope(SteppedCore* c_, const ShardSync& s) : c(c_) { c->shard = s; }
+    ~ShardScope() { c->shard = ShardSync{}; }
 };
 
 // pointers_ok: the engine's arena pointers are all non-null
@@ -168,6 +201,19 @@ inline int check_batch(const SteppedCore* c, const char* who, int which, int64_t
                     (long long)(start + batch), (long long)c->ds[which].n);
     if (slot < 0 || slot >= kStepLossSlots)
         return fail(CAE_ERR_ARG, "%s: loss slot %d outside 0..%d", who, slot, kStepLossSlots - 1);
+    return CAE_OK;
+}
+
+// check_batch for a shard (rows [row0, row0 + batch) of global_batch), which may be empty (batch 0: global batch < world, or
+// the tail of a partial batch)
+inline int check_shard(const SteppedCore* c, const char* who, int which, int64_t start, int batch, int row0, int global_batch,
+                       int world, int slot, cae_allreduce_fn fn) {
+    if (!fn || world < 0 || global_batch < 1 || batch < 0 || row0 < 0 || (int64_t)row0 + batch > global_batch)
+        return fail(CAE_ERR_ARG, "%s: bad argument (batch %d at row %d of %d, world %d)", who, batch, row0, global_batch, world);
+    if (batch > 0) return check_batch(c, who, which, start, batch, slot, true);
+    if (!c->ws) return fail(CAE_ERR_STATE, "%s: engine is not bound", who);
+    if (which < 0 || which > 1 || !c->ds[which].x || !c->ds[which].t) return fail(CAE_ERR_STATE, "%s: data set %d is not set", who, which);
+    if (slot < 0 || slot >= kStepLossSlots) return fail(CAE_ERR_ARG, "%s: loss slot %d outside 0..%d", who, slot, kStepLossSlots - 1);
     return CAE_OK;
 }
 

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "cae_hip.h"
+#include "engine_host.h"
 
 namespace cae_internal {
 
@@ -29,27 +30,20 @@ int trunk_create(const cae_layer_spec* enc, int n_enc, const cae_layer_spec* dec
                  int max_batch, cae_engine** out);
 void trunk_set_hooks(cae_engine* e, const TrunkHooks& hooks);
 
-// A data-parallel shard of a training step (vae_forward_backward_sync).  fn (cae_hip.h) sums a table over the ranks in place.
-// world >= 1: after every launch that completes a BatchNorm sum table, fn receives it (2 calls per BatchNorm layer per step, in
-// the engine's sync_order, checked), and the statistics are over global_batch rows; world 0: per-rank statistics, fn receives no
-// BatchNorm table.  A shard may be empty (batch 0): then no launch reads rows, and the same calls are made with zero tables.
-// The default (no fn) is the single-device step.
-struct TrunkSync {
-    cae_allreduce_fn fn = nullptr;
-    void* user = nullptr;
-    int world = 0;
-    int global_batch = 0;
-};
-
+// A data-parallel shard of a training step (vae_forward_backward_sync; engine_host.h).  sync_bn(): after every launch that
+// completes a BatchNorm sum table, fn receives it (2 calls per BatchNorm layer per step, in the engine's sync_order, checked),
+// and the statistics are over global_batch rows; otherwise per-rank statistics, and fn receives no BatchNorm table.  A shard
+// may be empty (batch 0): then no launch reads rows, and the same calls are made with zero tables.  The default (no fn) is the
+// single-device step.
 // Train-mode or eval-mode forward of an explicit input batch x (B, in_c, in_h, in_w).  external_loss: the last decoder
 // layer's raw output is left in trunk_raw_output(); otherwise its sigmoid goes to yhat (scoring).
 int trunk_forward(cae_engine* e, const float* x_dev, int batch, bool train, bool external_loss, float* yhat_dev,
-                  const TrunkSync& sync = TrunkSync{});
+                  const ShardSync& sync = ShardSync{});
 float* trunk_raw_output(cae_engine* e);          // (B, out_c, out_h, out_w)
 float* trunk_output_gradient(cae_engine* e);     // where the caller leaves dL/d(raw output) before trunk_backward
 double* trunk_output_bias_acc(cae_engine* e);    // fp64 accumulator of the last layer's bias gradient (the caller adds sum dL/d(raw))
 // backward of the last trunk_forward(train) through every layer into the fp64 accumulators
-int trunk_backward(cae_engine* e, const float* x_dev, int batch, const TrunkSync& sync = TrunkSync{});
+int trunk_backward(cae_engine* e, const float* x_dev, int batch, const ShardSync& sync = ShardSync{});
 float* trunk_latent(cae_engine* e);              // z (B, latent) of the last forward
 // Adam (L2 decay) from the accumulators, which it clears (cae_set_hyper / cae_set_adam_step configure it)
 int trunk_adam(cae_engine* e);

@@ -79,9 +79,16 @@ struct Fc {
     int64_t gh = 0, ga = 0;          // grad wrt raw output (in place of ga after activation backward), grad wrt a
 };
 
+// A sum table a data-parallel step hands to the caller's all-reduce (unet_engine::tables)
+struct SumTable {
+    int64_t off = 0, count = 0;    // dsum offset, doubles
+    const Bn* fwd = nullptr;       // a forward BatchNorm table: its layer, whose statistics are over HW values per row
+    int HW = 0;
+};
+
 }  // namespace
 
-struct unet_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets, loss slots: engine_host.h)
+struct unet_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets, loss slots, shard: engine_host.h)
     std::vector<ConvLayer> enc, dec;
     Fc fc[4];                        // enc_lin.0, enc_lin.4, dec_lin.0, dec_lin.4
     int fc_size = 0, latent = 0;
@@ -101,13 +108,10 @@ struct unet_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets,
     int specialised = 1;
     bool gacc_clean = false;   // the fp64 gradient accumulator is all zero (k_adamw clears what it consumes) but for fc_f32_dirty
     int64_t off_ltot = 0;      // dsum offset of the loss totals {sum mask, sum squared error, sum r} of a data-parallel shard
-    // the data-parallel shard of the current unet_*_sync call (ShardScope); a plain step leaves them at their defaults
-    int64_t row0 = 0;          // the shard's first row in the global batch: dropout hashes global element indices
-    int stat_batch = 0;        // rows behind the BatchNorm statistics (the global batch under SyncBN); 0: the local batch
-    int loss_batch = 0;        // rows behind the loss means (the global batch); 0: the local batch
-    cae_allreduce_fn sync_fn = nullptr;   // sums a table over the ranks (nullptr: no data parallelism)
-    void* sync_user = nullptr;
-    bool sync_bn = false;      // BatchNorm sum tables go through sync_fn too
+    // every table a SyncBN step passes to the all-reduce, in the order of include/cae_unet.h: the forward BatchNorm sums, the
+    // loss totals, the backward sums (without SyncBN: the loss totals alone).  sync_table checks each call against it.
+    std::vector<SumTable> tables;
+    size_t table_pos = 0;      // the next entry of `tables` in the current step
 
     float* f(int64_t off) const { return reinterpret_cast<float*>(ws + off_f32) + off; }
     double* dsum(int64_t off) const { return reinterpret_cast<double*>(ws + off_dsum) + off; }
@@ -131,7 +135,7 @@ Drop make_drop(const unet_engine* e, uint32_t site, bool train, int64_t per_samp
     Drop d{0, 0, 1.f, 0, 0};
     if (!train || e->dropout <= 0.0) return d;
     d.on = 1;
-    d.base = (unsigned long long)(e->row0 * per_sample);
+    d.base = (unsigned long long)((int64_t)e->shard.row0 * per_sample);
     const uint32_t k = pcg(e->seed + 0x9E3779B9u * site);
     d.key = pcg(k ^ (uint32_t)(e->step & 0xFFFFFFFF));
     double t = e->dropout * 4294967296.0;
@@ -262,13 +266,22 @@ void bn_stats(unet_engine* e, const Bn& bn, const float* x, long long bs, int B,
 const ZCat kNoCat{nullptr, nullptr, nullptr, 0};
 
 // values per channel behind a BatchNorm's statistics
-double bn_count(const unet_engine* e, int B, int HW) { return (double)(e->stat_batch ? e->stat_batch : B) * HW; }
+double bn_count(const unet_engine* e, int B, int HW) { return (double)e->shard.stat_rows(B) * HW; }
 
-// a completed sum table (`count` doubles) to the caller's all-reduce, when this is a data-parallel call that sums it
-int sync_table(unet_engine* e, double* table, int64_t count, bool bn = true) {
-    if (!e->sync_fn || (bn && !e->sync_bn)) return CAE_OK;
-    if (e->sync_fn(e->sync_user, table, count) != 0) return fail(CAE_ERR_STATE, "unet: the all-reduce callback failed");
-    return CAE_OK;
+// the completed sum table at dsum offset `off` to the caller's all-reduce, when this is a data-parallel call that sums it: every
+// table under SyncBN, each in its place in e->tables (the ranks' collectives must match), else the loss totals alone
+int sync_table(unet_engine* e, int64_t off) {
+    if (!e->shard.fn) return CAE_OK;
+    int64_t count = 3;   // (the loss totals)
+    if (e->shard.sync_bn()) {
+        if (e->table_pos >= e->tables.size() || e->tables[e->table_pos].off != off)
+            return fail(CAE_ERR_STATE, "unet: sum table at %lld passed out of order (position %zu of %zu)", (long long)off,
+                        e->table_pos, e->tables.size());
+        count = e->tables[e->table_pos++].count;
+    } else if (off != e->off_ltot) {
+        return CAE_OK;
+    }
+    return call_allreduce(e->shard, "unet", e->dsum(off), count);
 }
 
 // skip_sums: where the sums of the ReLU output go (the skip half of a decoder layer's BatchNorm statistics), or nullptr
@@ -284,10 +297,10 @@ void bn_act(unet_engine* e, const Bn& bn, const float* z, long long zbs, int B, 
 // sums are all-reduced here; this shard's dgamma / dbeta are taken from them before (k_bn_grad_local) and pass 2 adds none.
 int bn_bwd_between(unet_engine* e, const Bn& bn, double*& acc_gamma, double*& acc_beta) {
     acc_gamma = e->gacc(bn.gamma), acc_beta = e->gacc(bn.beta);
-    if (!(e->sync_fn && e->sync_bn)) return CAE_OK;
+    if (!e->shard.sync_bn()) return CAE_OK;
     hipLaunchKernelGGL(k_bn_grad_local, dim3((bn.C + 255) / 256), dim3(256), 0, e->stream, e->dsum(bn.bsums), bn.C, acc_gamma, acc_beta);
     acc_gamma = acc_beta = nullptr;
-    return sync_table(e, e->dsum(bn.bsums), 2 * bn.C);
+    return sync_table(e, bn.bsums);
 }
 
 int bn_backward(unet_engine* e, const Bn& bn, const float* gA, long long gAbs, const float* gB, long long gBbs,
@@ -498,7 +511,7 @@ int forward(unet_engine* e, const float* x, int B, bool train) {
         conv_down(e, g, cur, e->P(L.w), e->P(L.b), e->f(L.z));
         if (train) {
             bn_stats(e, L.bn, e->f(L.z), (long long)g.Cs * HW, B, HW);
-            if (int rc = sync_table(e, e->dsum(L.bn.sums), 2 * L.bn.C)) return rc;
+            if (int rc = sync_table(e, L.bn.sums)) return rc;
         }
         const Drop d = make_drop(e, SITE_ENC_CONV + i, train, (int64_t)g.Cs * HW);
         // the skip is the ReLU output; the next layer sees it through the dropout (unet.py:105-107)
@@ -516,7 +529,7 @@ int forward(unet_engine* e, const float* x, int B, bool train) {
         if (L.has_bn) {
             if (train) {
                 bn_stats(e, L.bn, e->f(L.h), L.nout, B, 1);
-                if (int rc = sync_table(e, e->dsum(L.bn.sums), 2 * L.bn.C)) return rc;
+                if (int rc = sync_table(e, L.bn.sums)) return rc;
             }
             bn_act(e, L.bn, e->f(L.h), L.nout, B, 1, train, d, nullptr, e->f(L.a));
         } else {
@@ -543,7 +556,7 @@ int forward(unet_engine* e, const float* x, int B, bool train) {
                            C, L.R, e->P(L.w1), e->P(L.w2), e->f(L.att), e->f(L.hid), psum, train ? e->dsum(L.bn.sums) : nullptr);
         // (both halves of the concatenated tensor's sums are in by now: the skip's came with the encoder's bn_act)
         if (train)
-            if (int rc = sync_table(e, e->dsum(L.bn.sums), 2 * L.bn.C)) return rc;
+            if (int rc = sync_table(e, L.bn.sums)) return rc;
         const Drop d = make_drop(e, SITE_DEC_CONV + j, train, (int64_t)2 * C * HW);
         bn_act(e, L.bn, nullptr, 0, B, HW, train, d, nullptr, e->f(L.din_next), ZCat{e->f(L.u), e->f(L.att), skip, C});
         cur = e->f(L.din_next);
@@ -572,11 +585,11 @@ int loss_forward(unet_engine* e, int which, const int32_t* perm, int64_t start, 
     int chunks = std::max(1, std::min(32, 768 / std::max(1, B * C)));
     chunks = std::min(chunks, (HW + 1023) / 1024);
     if (B > 0) hipLaunchKernelGGL(k_loss_sums, dim3(chunks, B * C), dim3(256), 0, e->stream, e->f(L.u), 1, src, C, HW, ls);
-    if (e->sync_fn) {   // a data-parallel shard: the mask count, squared error and Pearson sum are totals over the ranks
+    if (e->shard.fn) {   // a data-parallel shard: the mask count, squared error and Pearson sum are totals over the ranks
         double* tot = e->dsum(e->off_ltot);
         hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(256), 0, e->stream, ls, B, C, src.Cm, src.mask ? 1 : 0, tot);
-        if (int rc = sync_table(e, tot, 3, false)) return rc;
-        hipLaunchKernelGGL(k_loss_finalize_global, dim3(1), dim3(256), 0, e->stream, ls, B, C, tot, (double)e->loss_batch * C,
+        if (int rc = sync_table(e, e->off_ltot)) return rc;
+        hipLaunchKernelGGL(k_loss_finalize_global, dim3(1), dim3(256), 0, e->stream, ls, B, C, tot, (double)e->shard.global_batch * C,
                            e->lambda_p, e->losses(slot), want_grad ? e->f(e->coef) : nullptr);
     } else {
         hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(256), 0, e->stream, ls, B, C, src.Cm, src.mask ? 1 : 0, e->lambda_p,
@@ -737,62 +750,22 @@ int train_or_fb(unet_engine* e, int which, const int32_t* perm, int64_t start, i
 }
 
 // ---- data-parallel shards (unet_forward_backward_sync / unet_eval_step_sync) ----------------------------------------
-// The shard's place in the global batch and the all-reduce callback, for the duration of one call
-struct ShardScope {
-    unet_engine* e;
-    ShardScope(unet_engine* e_, int row0, int global_batch, bool sync_bn, cae_allreduce_fn fn, void* user) : e(e_) {
-        e->row0 = row0, e->stat_batch = sync_bn ? global_batch : 0, e->loss_batch = global_batch;
-        e->sync_fn = fn, e->sync_user = user, e->sync_bn = sync_bn;
-    }
-    ~ShardScope() {
-        e->row0 = 0, e->stat_batch = e->loss_batch = 0;
-        e->sync_fn = nullptr, e->sync_user = nullptr, e->sync_bn = false;
-    }
-};
-
-// the checks of check_batch for a shard, which may be empty (batch 0: global batch < world, or the tail of a partial batch)
-int check_shard(const unet_engine* e, const char* who, int which, int64_t start, int batch, int row0, int global_batch,
-                int world, int slot, cae_allreduce_fn fn) {
-    if (!fn || world < 0 || global_batch < 1 || batch < 0 || row0 < 0 || (int64_t)row0 + batch > global_batch)
-        return fail(CAE_ERR_ARG, "%s: bad argument (batch %d at row %d of %d, world %d)", who, batch, row0, global_batch, world);
-    if (batch > 0) return check_batch(e, who, which, start, batch, slot, true);
-    if (!e->ws) return fail(CAE_ERR_STATE, "%s: engine is not bound", who);
-    if (which < 0 || which > 1 || !e->ds[which].x || !e->ds[which].t) return fail(CAE_ERR_STATE, "%s: data set %d is not set", who, which);
-    if (slot < 0 || slot >= kStepLossSlots) return fail(CAE_ERR_ARG, "%s: loss slot %d outside 0..%d", who, slot, kStepLossSlots - 1);
-    return CAE_OK;
-}
-
 // An empty shard's step: no activations and no launch over the batch, but the same tables - zero here - go to the all-reduce in
-// the order forward(), loss_forward() and backward() pass them on the other ranks, the running statistics advance from the global
-// sums as theirs do (SyncBN; per-rank statistics have nothing to advance from), and the loss slot and the (zero) gradient are written.
+// the order of e->tables, the running statistics advance from the global sums as the other ranks' do (SyncBN; per-rank
+// statistics have nothing to advance from), and the loss slot and the (zero) gradient are written.
 int empty_shard_step(unet_engine* e, int which, int slot, float* grads_out) {
     const bool train = grads_out != nullptr;
-    const int n = (int)e->enc.size(), nd = (int)e->dec.size();
     const Drop off{0, 0, 1.f, 0, 0};
-    auto fwd_table = [&](const Bn& bn, int HW) -> int {
-        if (int rc = sync_table(e, e->dsum(bn.sums), 2 * bn.C)) return rc;
-        if (e->sync_bn) bn_act(e, bn, nullptr, 0, 0, HW, true, off, nullptr, nullptr);
-        return CAE_OK;
-    };
-    if (train) {
-        HIP_TRY(hipMemsetAsync(e->dsum(0), 0, (size_t)e->n_dsum * sizeof(double), e->stream));
-        for (auto& L : e->enc)
-            if (int rc = fwd_table(L.bn, L.g.Hs * L.g.Ws)) return rc;
-        for (int k : {0, 2})
-            if (int rc = fwd_table(e->fc[k].bn, 1)) return rc;
-        for (int j = 0; j < nd - 1; j++)
-            if (int rc = fwd_table(e->dec[j].bn, e->dec[j].g.Hl * e->dec[j].g.Wl)) return rc;
+    if (train) HIP_TRY(hipMemsetAsync(e->dsum(0), 0, (size_t)e->n_dsum * sizeof(double), e->stream));
+    for (const SumTable& t : e->tables) {
+        if (t.off == e->off_ltot) {
+            if (int rc = loss_forward(e, which, nullptr, 0, 0, slot, false)) return rc;
+        } else if (train) {
+            if (int rc = sync_table(e, t.off)) return rc;
+            if (t.fwd && e->shard.sync_bn()) bn_act(e, *t.fwd, nullptr, 0, 0, t.HW, true, off, nullptr, nullptr);
+        }
     }
-    if (int rc = loss_forward(e, which, nullptr, 0, 0, slot, false)) return rc;
-    if (train) {
-        for (int j = nd - 1; j >= 1; j--)
-            if (int rc = sync_table(e, e->dsum(e->dec[j - 1].bn.bsums), 2 * e->dec[j - 1].bn.C)) return rc;
-        for (int k : {2, 0})
-            if (int rc = sync_table(e, e->dsum(e->fc[k].bn.bsums), 2 * e->fc[k].bn.C)) return rc;
-        for (int i = n - 1; i >= 0; i--)
-            if (int rc = sync_table(e, e->dsum(e->enc[i].bn.bsums), 2 * e->enc[i].bn.C)) return rc;
-        HIP_TRY(hipMemsetAsync(grads_out, 0, (size_t)e->tab.n_param * sizeof(float), e->stream));
-    }
+    if (train) HIP_TRY(hipMemsetAsync(grads_out, 0, (size_t)e->tab.n_param * sizeof(float), e->stream));
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
@@ -909,6 +882,15 @@ int unet_engine_create(const cae_layer_spec* enc, int n_enc, const cae_layer_spe
     e->off_ltot = nd;
     nd += 4;
     e->n_dsum = nd;
+    // the tables of a SyncBN step, in the order forward(), loss_forward() and backward() pass them
+    for (auto& L : e->enc) e->tables.push_back(SumTable{L.bn.sums, 2 * L.bn.C, &L.bn, L.g.Hs * L.g.Ws});
+    for (int k : {0, 2}) e->tables.push_back(SumTable{e->fc[k].bn.sums, 2 * e->fc[k].bn.C, &e->fc[k].bn, 1});
+    for (auto& L : e->dec)
+        if (L.has_bn) e->tables.push_back(SumTable{L.bn.sums, 2 * L.bn.C, &L.bn, L.g.Hl * L.g.Wl});
+    e->tables.push_back(SumTable{e->off_ltot, 3, nullptr, 0});
+    for (int j = (int)e->dec.size() - 2; j >= 0; j--) e->tables.push_back(SumTable{e->dec[j].bn.bsums, 2 * e->dec[j].bn.C});
+    for (int k : {2, 0}) e->tables.push_back(SumTable{e->fc[k].bn.bsums, 2 * e->fc[k].bn.C});
+    for (int i = (int)e->enc.size() - 1; i >= 0; i--) e->tables.push_back(SumTable{e->enc[i].bn.bsums, 2 * e->enc[i].bn.C});
     Carver F32{64};   // the fp32 sub-arena (float offsets)
     auto carve_saved = [&](Bn& bn) { bn.saved = F32(2 * bn.C); };
     e->xb = F32(B * e->in_c * e->in_h * e->in_w);
@@ -1040,9 +1022,13 @@ int unet_forward_backward_sync(unet_engine* e, int which, const int32_t* perm, i
     if (!e || !grads) return fail(CAE_ERR_ARG, "unet_forward_backward_sync: bad argument");
     if (int rc = check_shard(e, "unet_forward_backward_sync", which, start, batch, row0, global_batch, world, loss_slot, fn))
         return rc;
-    ShardScope scope(e, row0, global_batch, world > 0, fn, user);
-    if (batch == 0) return empty_shard_step(e, which, loss_slot, grads);
-    return train_or_fb(e, which, perm, start, batch, loss_slot, grads, 1.0);
+    ShardScope scope(e, ShardSync{fn, user, world, global_batch, row0});
+    e->table_pos = 0;
+    if (int rc = batch == 0 ? empty_shard_step(e, which, loss_slot, grads) : train_or_fb(e, which, perm, start, batch, loss_slot, grads))
+        return rc;
+    if (e->shard.sync_bn() && e->table_pos != e->tables.size())
+        return fail(CAE_ERR_STATE, "unet: %zu of %zu sum tables passed to the callback", e->table_pos, e->tables.size());
+    return CAE_OK;
 }
 
 int unet_apply_gradients(unet_engine* e, const float* grads) {
@@ -1071,7 +1057,7 @@ int unet_eval_step_sync(unet_engine* e, int which, const int32_t* perm, int64_t 
     if (!e) return fail(CAE_ERR_ARG, "unet_eval_step_sync: null engine");
     int rc = check_shard(e, "unet_eval_step_sync", which, start, batch, row0, global_batch, 0, loss_slot, fn);
     if (rc) return rc;
-    ShardScope scope(e, row0, global_batch, false, fn, user);
+    ShardScope scope(e, ShardSync{fn, user, 0, global_batch, row0});
     if (batch == 0) return empty_shard_step(e, which, loss_slot, nullptr);
     if ((rc = gather_x(e, which, perm, start, batch))) return rc;
     if ((rc = forward(e, e->f(e->xb), batch, false))) return rc;

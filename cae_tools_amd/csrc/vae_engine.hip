@@ -21,7 +21,7 @@
 using namespace unet;
 using namespace cae_internal;
 
-struct vae_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets, loss slots: engine_host.h)
+struct vae_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets, loss slots, shard: engine_host.h)
     cae_engine* trunk = nullptr;   // convolutions, BatchNorm, Linear layers, Adam: the ConvAE engine in trunk mode
     int fc_size = 0, latent = 0;
     int in_c = 0, in_h = 0, in_w = 0, out_c = 0, out_h = 0, out_w = 0;
@@ -33,9 +33,6 @@ struct vae_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets, 
     int64_t off_ssum = 0, off_part = 0;   // doubles: [scale][BC][2]; parts {mse, kl, ssim}
     double l_mse = 1, l_kl = 1, l_ssim = 1;
     double grad_scale = 1.0;     // data-parallel half-step: every loss gradient is scaled by local / global batch at its source
-    // the data-parallel shard of the current vae_*_sync call (ShardScope); a plain step leaves them at their defaults
-    int row0 = 0;                // the shard's first row in the global batch: the noise hash counts global element indices
-    int loss_batch = 0;          // rows behind the loss means and their gradient coefficients (the global batch); 0: the local batch
     uint32_t seed = 0;
     bool row_kernels = true;     // MS-SSIM passes: row-streaming kernels (vae_set_kernel_mode 1) or the LDS tile kernels (0)
     vae::Gauss gauss;
@@ -56,23 +53,23 @@ uint32_t noise_key(const vae_engine* e) {
 // ---- the two call-backs of the trunk (trunk_api.h) ----------------------------------------------------------------------
 void hook_reparam(void* user, hipStream_t s, const float* heads, int B, int latent, int train, float* z) {
     vae_engine* e = static_cast<vae_engine*>(user);
-    hipLaunchKernelGGL(vae::k_reparam, dim3(1), dim3(256), 0, s, heads, B, latent, e->row0, noise_key(e), train, z, e->f(e->eps),
+    hipLaunchKernelGGL(vae::k_reparam, dim3(1), dim3(256), 0, s, heads, B, latent, e->shard.row0, noise_key(e), train, z, e->f(e->eps),
                        e->parts() + 1);
 }
 
 void hook_reparam_bwd(void* user, hipStream_t s, const float* gz, const float* heads, int B, int latent, float* gheads) {
     vae_engine* e = static_cast<vae_engine*>(user);
     hipLaunchKernelGGL(vae::k_reparam_bwd, dim3(blocks_for((long long)B * latent, 65536)), dim3(256), 0, s, gz, heads, e->f(e->eps), B, latent,
-                       (float)(e->l_kl * e->grad_scale), (e->loss_batch ? e->loss_batch : B) * latent, gheads);
+                       (float)(e->l_kl * e->grad_scale), e->shard.loss_rows(B) * latent, gheads);
 }
 
 // y, target batch, MS-SSIM + MSE; with want_grad the gradient wrt the last layer's raw output goes to dec.back().gz
-// (a data-parallel shard - loss_batch set - leaves raw sums in the parts, and its gradient coefficients use the global counts)
+// (a data-parallel shard leaves raw sums in the parts, and its gradient coefficients use the global counts)
 int loss(vae_engine* e, int which, const int32_t* perm, int64_t start, int B, int slot, bool want_grad, double* parts) {
     const int C = e->out_c, H = e->out_h, W = e->out_w, BC = B * C;
     const long long E = (long long)C * H * W, n = (long long)B * E;
-    const bool shard = e->loss_batch > 0;
-    const int Bg = shard ? e->loss_batch : B;
+    const bool shard = e->shard.fn != nullptr;
+    const int Bg = e->shard.loss_rows(B);
     if (!e->row_kernels)   // (the row-kernel path forms the finest level inside its pyramid launch)
         hipLaunchKernelGGL(vae::k_sigmoid_gather, dim3(blocks_for(n, 65536)), dim3(256), 0, e->stream, cae_internal::trunk_raw_output(e->trunk), e->ds[which].t, perm,
                            (long long)start, B, E, e->f(e->sx[0]), e->f(e->sy[0]));
@@ -164,17 +161,10 @@ int loss(vae_engine* e, int which, const int32_t* perm, int64_t start, int B, in
     return CAE_OK;
 }
 
-// A data-parallel shard (vae_forward_backward_sync / vae_eval_step_sync): the all-reduce callback and, for training, the
-// BatchNorm mode handed to the trunk.  The default is a plain single-device step.
-struct Shard {
-    cae_allreduce_fn fn = nullptr;
-    void* user = nullptr;
-    int world = 0;           // >= 1: SyncBN over the global batch; 0: per-rank statistics
-    int global_batch = 0;
-};
-
+// (within vae_forward_backward_sync / vae_eval_step_sync, e->shard is the data-parallel shard)
 int step_common(vae_engine* e, int which, const int32_t* perm, int64_t start, int batch, int slot, bool train, float* grads_out,
-                bool optimise, double grad_scale = 1.0, const Shard& sh = Shard{}) {
+                bool optimise, double grad_scale = 1.0) {
+    const ShardSync& sh = e->shard;
     int rc;
     if (!sh.fn && (rc = check_batch(e, "vae", which, start, batch, slot, true))) return rc;   // (a shard is checked by its caller)
     e->grad_scale = grad_scale;
@@ -187,13 +177,13 @@ int step_common(vae_engine* e, int which, const int32_t* perm, int64_t start, in
     HIP_TRY(hipMemsetAsync(e->ws + e->off_ssum, 0, (size_t)(e->off_part + 4 * sizeof(double) - e->off_ssum), e->stream));
     // trunk forward: encoder stack, Linear + heads, z (call-back), decoder stack; the last layer leaves its raw output.  A training
     // shard's trunk passes its BatchNorm tables to the callback (and runs for an empty shard too: the other ranks wait on them)
-    const TrunkSync ts{train ? sh.fn : nullptr, sh.user, sh.world, sh.global_batch};
+    const ShardSync ts = train ? sh : ShardSync{};
     if ((batch > 0 || ts.fn) && (rc = cae_internal::trunk_forward(e->trunk, e->f(e->xb), batch, train, true, nullptr, ts))) return rc;
     // KL is a mean over B*latent
     if (batch > 0 && (rc = loss(e, which, perm, start, batch, slot, train, parts))) return rc;
     if (sh.fn) {
         // the shard's raw sums {squared error, KL term, 1 - MS-SSIM per (b, c)} over the ranks: the global batch's means
-        if (sh.fn(sh.user, parts, 3) != 0) return fail(CAE_ERR_STATE, "vae: the all-reduce callback failed for the loss table");
+        if ((rc = call_allreduce(sh, "vae", parts, 3))) return rc;
         const double bg = sh.global_batch;
         hipLaunchKernelGGL(vae::k_loss_slot, dim3(1), dim3(1), 0, e->stream, parts, bg * e->out_c * e->out_h * e->out_w, bg * e->latent,
                            bg * e->out_c, e->l_mse, e->l_kl, e->l_ssim, e->losses(slot));
@@ -219,26 +209,6 @@ int step_common(vae_engine* e, int which, const int32_t* perm, int64_t start, in
         }
     }
     HIP_TRY(hipGetLastError());
-    return CAE_OK;
-}
-
-// ---- data-parallel shards (vae_forward_backward_sync / vae_eval_step_sync) -----------------------------------------------
-// The shard's place in the global batch, for the duration of one call
-struct ShardScope {
-    vae_engine* e;
-    ShardScope(vae_engine* e_, int row0, int global_batch) : e(e_) { e->row0 = row0, e->loss_batch = global_batch; }
-    ~ShardScope() { e->row0 = 0, e->loss_batch = 0; }
-};
-
-// the checks of check_batch for a shard, which may be empty (batch 0: global batch < world, or the tail of a partial batch)
-int check_shard(const vae_engine* e, const char* who, int which, int64_t start, int batch, int row0, int global_batch, int world,
-                int slot, cae_allreduce_fn fn) {
-    if (!fn || world < 0 || global_batch < 1 || batch < 0 || row0 < 0 || (int64_t)row0 + batch > global_batch)
-        return fail(CAE_ERR_ARG, "%s: bad argument (batch %d at row %d of %d, world %d)", who, batch, row0, global_batch, world);
-    if (batch > 0) return check_batch(e, who, which, start, batch, slot, true);
-    if (!e->ws) return fail(CAE_ERR_STATE, "%s: engine is not bound", who);
-    if (which < 0 || which > 1 || !e->ds[which].x || !e->ds[which].t) return fail(CAE_ERR_STATE, "%s: data set %d is not set", who, which);
-    if (slot < 0 || slot >= kStepLossSlots) return fail(CAE_ERR_ARG, "%s: loss slot %d outside 0..%d", who, slot, kStepLossSlots - 1);
     return CAE_OK;
 }
 
@@ -343,8 +313,8 @@ int vae_forward_backward_sync(vae_engine* e, int which, const int32_t* perm, int
                               int world, int loss_slot, float* grads, cae_allreduce_fn fn, void* user) {
     if (!e || !grads) return fail(CAE_ERR_ARG, "vae_forward_backward_sync: bad argument");
     if (int rc = check_shard(e, "vae_forward_backward_sync", which, start, batch, row0, global_batch, world, loss_slot, fn)) return rc;
-    ShardScope scope(e, row0, global_batch);
-    return step_common(e, which, perm, start, batch, loss_slot, true, grads, false, 1.0, Shard{fn, user, world, global_batch});
+    ShardScope scope(e, ShardSync{fn, user, world, global_batch, row0});
+    return step_common(e, which, perm, start, batch, loss_slot, true, grads, false);
 }
 int vae_apply_gradients(vae_engine* e, const float* grads) {
     if (!e || !e->ws || !grads) return fail(CAE_ERR_ARG, "vae_apply_gradients: bad argument");
@@ -358,8 +328,8 @@ int vae_eval_step_sync(vae_engine* e, int which, const int32_t* perm, int64_t st
                        int loss_slot, cae_allreduce_fn fn, void* user) {
     if (!e) return fail(CAE_ERR_ARG, "vae_eval_step_sync: null engine");
     if (int rc = check_shard(e, "vae_eval_step_sync", which, start, batch, row0, global_batch, 0, loss_slot, fn)) return rc;
-    ShardScope scope(e, row0, global_batch);
-    return step_common(e, which, perm, start, batch, loss_slot, false, nullptr, false, 1.0, Shard{fn, user, 0, global_batch});
+    ShardScope scope(e, ShardSync{fn, user, 0, global_batch, row0});
+    return step_common(e, which, perm, start, batch, loss_slot, false, nullptr, false);
 }
 int vae_score(vae_engine* e, const float* x, int batch, float* y) {
     if (int rc = check_score(e, "vae", x, batch, y)) return rc;

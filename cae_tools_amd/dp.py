@@ -16,10 +16,13 @@ Two engine protocols:
   from one hipGraph.  torch.distributed is only the rendezvous that carries the 128-byte RCCL id.  The engine exposes
   set_cursor / claim_slots / dp_train_steps / dp_eval_steps / dp_read_losses / dp_broadcast.
 * half-steps (UnetEngine / VaeEngine / LinearEngine behind GradientHalfSteps, and the CPU stand-ins of the gloo
-  tests): .grads, .forward_backward(which, perm, start, size, global_batch), .adam_step(); the all-reduce is
-  torch.distributed's.  run_batches additionally drives .forward_backward_sync(which, perm, start, size, row0,
-  global_batch, bn_world, allreduce) / .eval_step_sync(which, perm, start, size, row0, global_batch, allreduce), which
-  return a loss slot, and .read_losses(first, count) / .loss_slots (the UNET engine's global-batch entry points).
+  tests): .grads and .adam_step(), the gradient all-reduce between them being torch.distributed's, and one half-step
+  protocol: .forward_backward_sync(which, perm, start, size, row0, global_batch, bn_world, allreduce) /
+  .eval_step_sync(which, perm, start, size, row0, global_batch, allreduce), where this rank holds rows [row0, row0 +
+  size) of the global batch and allreduce sums each table the engine passes over the ranks; both return a loss slot
+  that .read_losses(first, count) / .loss_slots read.  train_step with sync_bn and run_batches drive it.  train_step
+  without sync_bn drives the plain .forward_backward(which, perm, start, size, global_batch) instead (per-rank
+  BatchNorm, gradient scaled by size / global_batch), which is also what bench.py's host all-reduce fallback runs.
 """
 import contextlib
 
@@ -113,7 +116,7 @@ class DataParallel:
             return slot
         if self.sync_bn:
             slot = eng.forward_backward_sync(
-                which, perm, start, size, gb, self.world,
+                which, perm, start, size, shard_bounds(gb, self.world, self.rank)[0], gb, self.world,
                 lambda table: self.dist.all_reduce(table, op=self.dist.ReduceOp.SUM, group=self.group))
         else:
             slot = eng.forward_backward(which, perm, start, size, gb)
@@ -190,14 +193,14 @@ class DataParallel:
 
 
 class GradientHalfSteps:
-    """UnetEngine / VaeEngine / LinearEngine behind the three-member interface DataParallel drives: a persistent flat
-    gradient buffer, forward_backward into it with the local/global weight applied in the kernel that narrows the fp64
-    accumulator (grad_scale of *_forward_backward), and the optimiser half-step (*_apply_gradients) after the all-reduce.
-    With forward_backward, BatchNorm statistics stay per rank and the UNET's masked MSE divides by the LOCAL mask count
-    (with unequal mask coverage the reduced gradient weights shards by sample count, not by valid-pixel count).  The UNET's
-    forward_backward_sync / eval_step_sync (what DataParallel.run_batches drives) are the single-device arithmetic at the
-    global batch instead: global loss denominators, dropout masks of the global rows and, with SyncBN, BatchNorm
-    statistics over the global batch."""
+    """UnetEngine / VaeEngine / LinearEngine behind the half-step interface DataParallel drives: a persistent flat gradient
+    buffer, the half-step protocol into it - forward_backward_sync / eval_step_sync (UNET, VAE), the single-device
+    arithmetic at the global batch: global loss denominators, random masks / noise of the global rows and, with SyncBN,
+    BatchNorm statistics over the global batch - and the optimiser half-step (*_apply_gradients) after the all-reduce.
+    The plain forward_backward (DataParallel.train_step without sync_bn, bench.py's fallback) applies the local/global
+    weight in the kernel that narrows the fp64 accumulator (grad_scale of *_forward_backward); its BatchNorm statistics
+    stay per rank and the UNET's masked MSE divides by the LOCAL mask count (with unequal mask coverage the reduced
+    gradient weights shards by sample count, not by valid-pixel count)."""
 
     def __init__(self, engine):
         self.engine = engine

@@ -84,10 +84,11 @@ int unet_eval_step(unet_engine* e, int which, const int32_t* perm_dev, int64_t s
  * engine's stream, and returns 0.  The tables, in order: per BatchNorm layer its forward sums {sum y, sum y^2} (encoder
  * layers, encoder_lin.1, decoder_lin.1, then the decoder layers' concatenated tensors), the loss totals {sum mask, sum of
  * squared masked errors, sum of per-(b, c) Pearson r} (3 doubles), and the backward sums {sum g, sum g*xhat} from the
- * decoder back to the first encoder layer: 2 (2n + 1) + 1 calls for n levels.  Dropout masks are those of the rows' global
- * indices.  world >= 1: the BatchNorm statistics are over the global batch (SyncBN); world 0: per rank (fn then sees the
- * loss table only).  grads_dev receives this rank's share of the gradient of the global loss: the SUM over the ranks is the
- * gradient, which unet_apply_gradients applies.  batch 0 (an empty shard) is allowed and makes the same calls to fn.
+ * decoder back to the first encoder layer: 2 (2n + 1) + 1 calls for n levels, checked against that order (CAE_ERR_STATE).
+ * Dropout masks are those of the rows' global indices.  world >= 1: the BatchNorm statistics are over the global batch
+ * (SyncBN); world 0: per rank (fn then sees the loss table only).  grads_dev receives this rank's share of the gradient of
+ * the global loss: the SUM over the ranks is the gradient, which unet_apply_gradients applies.  batch 0 (an empty shard) is
+ * allowed and makes the same calls to fn.
  * unet_eval_step_sync: the eval-mode counterpart (the loss table only). */
 int unet_forward_backward_sync(unet_engine* e, int which, const int32_t* perm_dev, int64_t start, int batch, int row0,
                                int global_batch, int world, int loss_slot, float* grads_dev, cae_allreduce_fn fn, void* user);

@@ -51,6 +51,9 @@ static void unet_layers(int in_c, int out_c, int size, const std::vector<int>& c
     }
 }
 
+// an all-reduce callback that sums nothing (the shard checks refuse before any table is passed)
+static int no_allreduce(void*, void*, int64_t) { return 0; }
+
 int main() {
     int failures = 0;
     auto expect = [&](bool ok, const char* what) {
@@ -107,6 +110,11 @@ int main() {
             }
             expect(mu && lv, "the heads are listed under the var model's names");
             expect(vae_train_step(v, 0, nullptr, 0, 16, 0) != 0, "a step on an unbound var engine is refused");
+            float g[1];
+            expect(vae_forward_backward_sync(v, 0, nullptr, 0, 3, 2, 4, 1, 0, g, no_allreduce, nullptr) == CAE_ERR_ARG,
+                   "var: a shard past the global batch is refused");
+            expect(vae_forward_backward_sync(v, 0, nullptr, 0, 2, 0, 4, 1, 0, g, nullptr, nullptr) == CAE_ERR_ARG,
+                   "var: a shard without a callback is refused");
             vae_engine_destroy(v);
         }
         auto small = dec_layers(3, 5, 64, 4);   // 128x128 output: MS-SSIM needs >= 176
@@ -139,6 +147,11 @@ int main() {
             expect(unet_debug_plan(u, 5, 1, plan, sizeof plan) != 0, "a plan beyond max_batch is refused");
             expect(unet_debug_plan(u, 4, 1, plan, 16) != 0, "too small a plan buffer is refused");
             expect(unet_train_step(u, 0, nullptr, 0, 4, 0) != 0, "a step on an unbound UNET engine is refused");
+            float g[1];
+            expect(unet_forward_backward_sync(u, 0, nullptr, 0, 3, 2, 4, 1, 0, g, no_allreduce, nullptr) == CAE_ERR_ARG,
+                   "UNET: a shard past the global batch is refused");
+            expect(unet_forward_backward_sync(u, 0, nullptr, 0, 2, 0, 4, 1, 0, g, nullptr, nullptr) == CAE_ERR_ARG,
+                   "UNET: a shard without a callback is refused");
             unet_engine_destroy(u);
         }
         udec[5].out_c = 2;

@@ -59,7 +59,7 @@ def test_two_ranks_with_syncbn_equal_one_device(name):
     def run(r):
         try:
             start = 0 if r == 0 else sizes[0]
-            slots[r] = ranks[r].forward_backward_sync(0, None, start, sizes[r], n, 2, allreduce_for(r))
+            slots[r] = ranks[r].forward_backward_sync(0, None, start, sizes[r], start, n, 2, allreduce_for(r))
             ranks[r].sync()
         except Exception as ex:  # pragma: no cover
             errors.append(ex)

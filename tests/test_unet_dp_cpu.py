@@ -76,7 +76,7 @@ class ShardEngine:
 
 def _worker(rank, world, port, out_dir):
     sys.path.insert(0, ROOT)
-    from cae_tools_amd.dp import DataParallel
+    from cae_tools_amd.dp import DataParallel, shard_bounds
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     torch.set_num_threads(1)
@@ -90,6 +90,12 @@ def _worker(rank, world, port, out_dir):
         train = [par.run_batches(0, perm, N, GLOBAL_BATCH, train=True) for _ in range(2)]
         test = par.run_batches(1, perm, N, GLOBAL_BATCH, train=False)
         res[sync_bn] = {"train": train, "test": test, "w": eng.w.item(), "calls": eng.calls}
+        if sync_bn:   # one train_step on this rank's rows of the first global batch
+            eng = ShardEngine()
+            (lo, hi) = shard_bounds(GLOBAL_BATCH, world, rank)
+            slot = DataParallel(eng, dist, sync_bn=True).train_step(0, perm, lo, hi - lo, GLOBAL_BATCH)
+            res["train_step"] = {"loss": eng.read_losses(slot, 1)[0][0], "w": eng.w.item(), "shard": eng.calls[0],
+                                 "want": ("shard", lo, hi - lo, lo, GLOBAL_BATCH)}
     torch.save(res, os.path.join(out_dir, f"rank{rank}.pt"))
     dist.destroy_process_group()
 
@@ -105,7 +111,7 @@ def _single_process():
     (x, t) = _data()
     perm = torch.tensor([4, 0, 6, 2, 5, 1, 3])
     w = 0.0
-    train = []
+    train, ws = [], []
     for _ in range(2):
         losses = []
         for b0 in range(0, N, GLOBAL_BATCH):
@@ -113,13 +119,14 @@ def _single_process():
             err = w * x[idx] - t[idx]
             losses.append(((err * err).sum() / len(idx)).item())
             w -= LR * ((2 * err * x[idx]).sum() / len(idx)).item()
+            ws.append(w)
         train.append(losses)
     test = []
     for b0 in range(0, N, GLOBAL_BATCH):
         idx = perm[b0:b0 + GLOBAL_BATCH]
         err = w * x[idx] - t[idx]
         test.append(((err * err).sum() / len(idx)).item())
-    return train, test, w
+    return train, test, w, ws[0]
 
 
 def test_half_step_passes_over_two_ranks(tmp_path):
@@ -127,7 +134,7 @@ def test_half_step_passes_over_two_ranks(tmp_path):
     world = 2
     mp.spawn(_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
     ranks = [torch.load(tmp_path / f"rank{r}.pt", weights_only=False) for r in range(world)]
-    (train_ref, test_ref, w_ref) = _single_process()
+    (train_ref, test_ref, w_ref, w1_ref) = _single_process()
     for sync_bn in (True, False):
         (a, b) = (ranks[0][sync_bn], ranks[1][sync_bn])
         # per-batch losses identical on both ranks (sync_bn: with the global batch's statistics too) ...
@@ -156,3 +163,9 @@ def test_half_step_passes_over_two_ranks(tmp_path):
         if sync_bn:   # the statistics table was the global batch's
             x = _data()[0][torch.tensor([4, 0, 6])]
             assert abs(a["train"][0][0][1] - x.mean().item()) <= 1e-12
+    # DataParallel.train_step with sync_bn: the first global step on both ranks
+    for r in range(world):
+        step = ranks[r]["train_step"]
+        assert step["shard"] == step["want"]
+        np.testing.assert_allclose(step["loss"], train_ref[0][0], rtol=1e-12)
+        assert abs(step["w"] - w1_ref) <= 1e-12
