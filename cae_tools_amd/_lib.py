@@ -26,6 +26,9 @@ class ProfileRecC(C.Structure):
                 ("bytes", C.c_double)]
 
 
+# enum cae_elem_kind: element kinds of cae_case_measures
+ELEM_F32, ELEM_F32_BE, ELEM_F64, ELEM_F64_BE = 0, 1, 2, 3
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 
 # name -> (restype, argtypes); every symbol include/cae_hip.h declares
@@ -90,6 +93,9 @@ SIGNATURES = {
     "cae_denormalise_f64": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, _P, _P]),
     "cae_bswap32": (C.c_int, [_P, C.c_int64, _P]),
     "cae_metric_sums": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, _P, _P]),
+    "cae_case_measures_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "cae_case_measures": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, _P,
+                                    C.c_int64, _P]),
     # ---- include/cae_unet.h ----
     "unet_engine_create": (C.c_int, [C.POINTER(LayerSpecC), C.c_int, C.POINTER(LayerSpecC), C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.POINTER(C.c_void_p)]),

@@ -2,16 +2,12 @@
 (src/cae_tools/cli/apply_cae.py:28-90): load a model folder, score the input file(s) on the GPU,
 write inputs + the denormalised prediction variable to a NetCDF file."""
 import argparse
-import json
 import os
 
 import numpy as np
 
 from ..data.arrays import DataArray, open_mfdataset
-from ..models.conv_ae_model import ConvAEModel
-from ..models.unet import UNET
-from ..models.linear_model import LinearModel
-from ..models.var_ae_model import VarAEModel
+from ..models.model_loader import load_model
 
 
 def build_parser():
@@ -37,13 +33,7 @@ def main(argv=None):
         return
     from .. import dp as _dp
     _dp.select_device()     # inside a rank: LOCAL_RANK's GPU before the first allocation
-    with open(os.path.join(args.model_folder, "parameters.json")) as f:
-        parameters = json.loads(f.read())
-    kinds = {"ConvAEModel": ConvAEModel, "UNET": UNET, "VarAEModel": VarAEModel, "LinearModel": LinearModel}
-    if parameters["type"] not in kinds:
-        raise SystemExit(f"cae_tools_amd implements {sorted(kinds)}; model folder holds a {parameters['type']}")
-    mt = kinds[parameters["type"]]()
-    mt.load(args.model_folder)
+    mt = load_model(args.model_folder)
 
     model_names = mt.get_input_variable_names()
     input_variable_names = args.input_variables

@@ -18,6 +18,7 @@ from ..models.conv_ae_model import ConvAEModel
 from ..models.unet import UNET
 from ..models.linear_model import LinearModel
 from ..models.var_ae_model import VarAEModel
+from ..models.model_loader import load_model
 from ..models.model_sizer import ModelSpec
 
 
@@ -108,13 +109,7 @@ def main(argv=None):
     broadcast_case_variables(test_ds, args.input_variables, case_dimension)
 
     if args.continue_training:
-        with open(os.path.join(args.model_folder, "parameters.json")) as f:
-            parameters = json.loads(f.read())
-        kinds = {"ConvAEModel": ConvAEModel, "UNET": UNET, "VarAEModel": VarAEModel, "LinearModel": LinearModel}
-        if parameters["type"] not in kinds:
-            raise SystemExit(f"cae_tools_amd implements {sorted(kinds)}; model folder holds a {parameters['type']}")
-        mt = kinds[parameters["type"]]()
-        mt.load(args.model_folder)
+        mt = load_model(args.model_folder)
         mt.nr_epochs = args.nr_epochs
         mt.lr = args.learning_rate
         mt.batch_size = args.batch_size

@@ -2848,6 +2848,78 @@ int cae_bswap32(void* x, int64_t n, void* hip_stream) {
     return CAE_OK;
 }
 
+// ---- evaluator -------------------------------------------------------------------------------
+
+static int64_t case_chunks(int64_t plane) { return (plane + 4 * CM_GROUPS - 1) / (4 * CM_GROUPS); }
+
+int64_t cae_case_measures_workspace_bytes(int64_t n_case, int64_t plane) {
+    if (n_case < 1 || plane < 1) return 0;
+    const int64_t nch = case_chunks(plane);
+    return nch > 1 ? n_case * nch * 2 * (int64_t)sizeof(double) : 0;
+}
+
+extern "C++" {   // the kind dispatch: templates inside the extern "C" block
+
+template <int KP, int KA>
+static void launch_case_measures(dim3 grid, hipStream_t s, const void* p, int64_t ps, const void* a, int64_t as,
+                                 int64_t plane, int nch, int64_t items, double* out) {
+    hipLaunchKernelGGL((k_case_measures<KP, KA>), grid, dim3(256), 0, s, (const unsigned char*)p, (long long)ps,
+                       (const unsigned char*)a, (long long)as, (long long)plane, nch, (long long)items, out);
+}
+
+template <int KP>
+static void launch_case_measures_a(int ka, dim3 grid, hipStream_t s, const void* p, int64_t ps, const void* a,
+                                   int64_t as, int64_t plane, int nch, int64_t items, double* out) {
+    switch (ka) {
+    case CAE_ELEM_F32: launch_case_measures<KP, 0>(grid, s, p, ps, a, as, plane, nch, items, out); break;
+    case CAE_ELEM_F32_BE: launch_case_measures<KP, 1>(grid, s, p, ps, a, as, plane, nch, items, out); break;
+    case CAE_ELEM_F64: launch_case_measures<KP, 2>(grid, s, p, ps, a, as, plane, nch, items, out); break;
+    default: launch_case_measures<KP, 3>(grid, s, p, ps, a, as, plane, nch, items, out); break;
+    }
+}
+
+}  // extern "C++"
+
+int cae_case_measures(const void* pred, int pred_kind, int64_t pred_stride, const void* actual, int actual_kind,
+                      int64_t actual_stride, int64_t n_case, int64_t plane, double* out, void* workspace,
+                      int64_t workspace_bytes, void* hip_stream) {
+    auto elem_bytes = [](int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; };
+    auto known = [](int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; };
+    if (!pred || !actual || !out || n_case < 1 || plane < 1 || !known(pred_kind) || !known(actual_kind))
+        return fail(CAE_ERR_ARG, "cae_case_measures: bad argument");
+    if (pred_stride < plane || actual_stride < plane)
+        return fail(CAE_ERR_ARG, "cae_case_measures: a case stride is shorter than the plane");
+    if (((uintptr_t)pred % elem_bytes(pred_kind)) || ((uintptr_t)actual % elem_bytes(actual_kind)) || ((uintptr_t)out & 7))
+        return fail(CAE_ERR_ARG, "cae_case_measures: pointers must be aligned to their element size");
+    const int64_t nch = case_chunks(plane);
+    if (nch > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_case_measures: plane too large");
+    const int64_t need = cae_case_measures_workspace_bytes(n_case, plane);
+    if (need > 0 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7)))
+        return fail(CAE_ERR_ARG, "cae_case_measures: needs a workspace of %lld bytes (cae_case_measures_workspace_bytes)",
+                    (long long)need);
+    hipStream_t s = (hipStream_t)hip_stream;
+    const int64_t items = n_case * nch;
+    double* dst = nch > 1 ? (double*)workspace : out;
+    int64_t blocks = (items + CM_WAVES - 1) / CM_WAVES;
+    if (blocks > 8192) blocks = 8192;
+    const dim3 grid((unsigned)blocks);
+    switch (pred_kind) {
+    case CAE_ELEM_F32: launch_case_measures_a<0>(actual_kind, grid, s, pred, pred_stride, actual, actual_stride, plane, (int)nch, items, dst); break;
+    case CAE_ELEM_F32_BE: launch_case_measures_a<1>(actual_kind, grid, s, pred, pred_stride, actual, actual_stride, plane, (int)nch, items, dst); break;
+    case CAE_ELEM_F64: launch_case_measures_a<2>(actual_kind, grid, s, pred, pred_stride, actual, actual_stride, plane, (int)nch, items, dst); break;
+    default: launch_case_measures_a<3>(actual_kind, grid, s, pred, pred_stride, actual, actual_stride, plane, (int)nch, items, dst); break;
+    }
+    HIP_TRY(hipGetLastError());
+    if (nch > 1) {
+        int64_t fb = (n_case + 255) / 256;
+        if (fb > 4096) fb = 4096;
+        hipLaunchKernelGGL(k_case_fold, dim3((unsigned)fb), dim3(256), 0, s, (const double*)workspace, (long long)n_case,
+                           (int)nch, out);
+        HIP_TRY(hipGetLastError());
+    }
+    return CAE_OK;
+}
+
 }  // extern "C"
 
 // =================================================================================================

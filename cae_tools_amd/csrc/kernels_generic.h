@@ -1250,4 +1250,139 @@ __global__ void __launch_bounds__(256) k_bswap32(unsigned* __restrict__ x, long 
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) x[(n4 << 2) + threadIdx.x] = __builtin_bswap32(x[(n4 << 2) + threadIdx.x]);
 }
 
+// ---- per-case error sums (model_evaluator.py:87-95): S|p - a| and S(p - a)^2 in fp64 over a case's first `plane` elements.
+// Element kinds of include/cae_hip.h (CAE_ELEM_*): 0 fp32, 1 fp32 big-endian, 2 fp64, 3 fp64 big-endian.  A big-endian
+// slab is the NetCDF-3 file's bytes copied to HBM as they are; the swap happens in registers.
+template <int K> struct CmElem;
+template <> struct CmElem<0> { static constexpr int bytes = 4; };
+template <> struct CmElem<1> { static constexpr int bytes = 4; };
+template <> struct CmElem<2> { static constexpr int bytes = 8; };
+template <> struct CmElem<3> { static constexpr int bytes = 8; };
+
+template <int K>
+__device__ __forceinline__ double cm_word(unsigned long long w) {
+    if constexpr (K == 0) return (double)__uint_as_float((unsigned)w);
+    else if constexpr (K == 1) return (double)__uint_as_float(__builtin_bswap32((unsigned)w));
+    else if constexpr (K == 2) return __longlong_as_double((long long)w);
+    else return __longlong_as_double((long long)__builtin_bswap64(w));
+}
+
+// element e of a case (element-aligned pointer)
+template <int K>
+__device__ __forceinline__ double cm_load1(const unsigned char* c, long long e) {
+    if constexpr (CmElem<K>::bytes == 4) return cm_word<K>(reinterpret_cast<const unsigned*>(c)[e]);
+    else return cm_word<K>(reinterpret_cast<const unsigned long long*>(c)[e]);
+}
+
+// elements e .. e+3: 16-byte loads when `vec` (the caller checked the alignment), else four scalar loads
+template <int K>
+__device__ __forceinline__ void cm_load4(const unsigned char* c, long long e, bool vec, double v[4]) {
+    if (vec) {
+        if constexpr (CmElem<K>::bytes == 4) {
+            const uint4 w = *reinterpret_cast<const uint4*>(c + e * 4);
+            v[0] = cm_word<K>(w.x);
+            v[1] = cm_word<K>(w.y);
+            v[2] = cm_word<K>(w.z);
+            v[3] = cm_word<K>(w.w);
+        } else {
+            const ulonglong2 w0 = *reinterpret_cast<const ulonglong2*>(c + e * 8);
+            const ulonglong2 w1 = *reinterpret_cast<const ulonglong2*>(c + e * 8 + 16);
+            v[0] = cm_word<K>(w0.x);
+            v[1] = cm_word<K>(w0.y);
+            v[2] = cm_word<K>(w1.x);
+            v[3] = cm_word<K>(w1.y);
+        }
+    } else {
+        for (int j = 0; j < 4; j++) v[j] = cm_load1<K>(c, e + j);
+    }
+}
+
+__device__ __forceinline__ void cm_acc(double p, double a, double& s1, double& s2) {
+    const double d = p - a;     // fp64: numpy's promotion of the float64 prediction against the target
+    s1 += fabs(d);
+    s2 += d * d;
+}
+
+// One wave per (case, chunk) item.  A case is cut at its first element h where both p and a are 16 bytes aligned: the
+// head [0, h) and the tail after the last whole 4-element group are summed element by element by the lanes of chunk 0;
+// the groups in between are split into chunks of CM_GROUPS groups, one lane taking every 64th group in order.  A lane's
+// sums, the fixed shuffle tree over the wave and the chunk-ordered fold (k_case_fold) depend on the launch shape and the
+// case's alignment only, so the result is the same bits from run to run.  No atomics: each item's two sums are plain
+// stores into out[item] - the partials (nch > 1) or the case's result (nch == 1).  NaN and Inf pass through untouched.
+constexpr int CM_GROUPS = 1024;          // 4096 elements per chunk
+constexpr int CM_WAVES = 4;              // waves per 256-thread workgroup
+
+template <int KP, int KA>
+__global__ void __launch_bounds__(256) k_case_measures(const unsigned char* __restrict__ p, long long p_stride,
+                                                       const unsigned char* __restrict__ a, long long a_stride,
+                                                       long long plane, int nch, long long items,
+                                                       double* __restrict__ out) {
+    constexpr int EP = CmElem<KP>::bytes, EA = CmElem<KA>::bytes;
+    const int lane = threadIdx.x & 63;
+    for (long long item = (long long)blockIdx.x * CM_WAVES + (threadIdx.x >> 6); item < items;
+         item += (long long)gridDim.x * CM_WAVES) {
+        const long long cs = item / nch;
+        const int ch = (int)(item - cs * nch);
+        const unsigned char* pc = p + cs * p_stride * EP;
+        const unsigned char* ac = a + cs * a_stride * EA;
+        int h = -1;
+        for (int t = 3; t >= 0; t--)
+            if ((((uintptr_t)(pc + t * EP) | (uintptr_t)(ac + t * EA)) & 15) == 0) h = t;
+        const bool vec = h >= 0;
+        const long long head = vec ? (h < plane ? h : plane) : 0;
+        const long long groups = (plane - head) >> 2;
+        const long long tail0 = head + (groups << 2);
+        double s1 = 0.0, s2 = 0.0;
+        if (ch == 0) {
+            if (lane < head) cm_acc(cm_load1<KP>(pc, lane), cm_load1<KA>(ac, lane), s1, s2);
+            else if (lane >= 4 && lane - 4 < plane - tail0)
+                cm_acc(cm_load1<KP>(pc, tail0 + lane - 4), cm_load1<KA>(ac, tail0 + lane - 4), s1, s2);
+        }
+        const long long g0 = (long long)ch * CM_GROUPS;
+        const long long g1 = g0 + CM_GROUPS < groups ? g0 + CM_GROUPS : groups;
+        long long g = g0 + lane;
+        for (; g + 3 * 64 < g1; g += 4 * 64) {      // four groups in flight per lane, summed in group order
+            double vp[4][4], va[4][4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                cm_load4<KP>(pc, head + ((g + u * 64) << 2), vec, vp[u]);
+                cm_load4<KA>(ac, head + ((g + u * 64) << 2), vec, va[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) cm_acc(vp[u][j], va[u][j], s1, s2);
+        }
+        for (; g < g1; g += 64) {
+            double vp[4], va[4];
+            cm_load4<KP>(pc, head + (g << 2), vec, vp);
+            cm_load4<KA>(ac, head + (g << 2), vec, va);
+#pragma unroll
+            for (int j = 0; j < 4; j++) cm_acc(vp[j], va[j], s1, s2);
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            s1 += __shfl_down(s1, off, 64);
+            s2 += __shfl_down(s2, off, 64);
+        }
+        if (lane == 0) {
+            out[2 * item] = s1;
+            out[2 * item + 1] = s2;
+        }
+    }
+}
+
+// out[i] = sum over chunks k = 0 .. nch-1, in that order, of part[i * nch + k]
+__global__ void __launch_bounds__(256) k_case_fold(const double* __restrict__ part, long long n_case, int nch,
+                                                   double* __restrict__ out) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_case; i += (long long)gridDim.x * 256) {
+        double s1 = 0.0, s2 = 0.0;
+        for (int k = 0; k < nch; k++) {
+            s1 += part[2 * (i * nch + k)];
+            s2 += part[2 * (i * nch + k) + 1];
+        }
+        out[2 * i] = s1;
+        out[2 * i + 1] = s2;
+    }
+}
+
 }  // namespace cae

@@ -525,25 +525,91 @@ def metric_sums(y, actual, mask, vmin, vmax):
 _STAGE_BYTES = 64 << 20
 
 
+def _upload_raw(arr, device):
+    """the bytes of a C-contiguous numpy array, unchanged, in a new uint8 CUDA tensor: copied through a pinned staging
+    buffer in pieces of at most _STAGE_BYTES"""
+    src = arr.reshape(-1).view(np.uint8)
+    nbytes = src.size
+    out = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    stage = torch.empty(min(nbytes, _STAGE_BYTES), dtype=torch.uint8).pin_memory()
+    stage_np = stage.numpy()
+    for lo in range(0, nbytes, _STAGE_BYTES):
+        hi = min(nbytes, lo + _STAGE_BYTES)
+        stage_np[:hi - lo] = src[lo:hi]
+        out[lo:hi].copy_(stage[:hi - lo], non_blocking=False)
+    return out
+
+
+def _is_big_endian_slab(arr, dtype):
+    return arr.dtype == np.dtype(dtype) and arr.dtype.byteorder == ">" and arr.flags.c_contiguous and arr.size > 0
+
+
 def upload_f32(arr, device):
     """numpy (N,...) array -> fp32 CUDA tensor.  A C-contiguous big-endian float32 array (a NetCDF-3 slab, usually a
     view of the file mapping) is copied as raw bytes through a pinned staging buffer and byte-swapped on the GPU
     (cae_bswap32); anything else is converted by numpy first."""
-    import numpy as np
     arr = np.asarray(arr)
-    if not (arr.dtype == np.dtype(">f4") and arr.dtype.byteorder == ">" and arr.flags.c_contiguous and arr.size > 0):
+    if not _is_big_endian_slab(arr, ">f4"):
         return torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).to(device)
     lib = _lib.load()
-    out = torch.empty(arr.shape, dtype=torch.float32, device=device)
-    words = out.view(-1).view(torch.int32)
-    src = arr.reshape(-1).view(np.uint8)
-    nbytes = src.size
-    stage = torch.empty(min(nbytes, _STAGE_BYTES), dtype=torch.uint8).pin_memory()
-    stage_np = stage.numpy()
-    dst_bytes = words.view(torch.uint8)
-    for lo in range(0, nbytes, _STAGE_BYTES):
-        hi = min(nbytes, lo + _STAGE_BYTES)
-        stage_np[:hi - lo] = src[lo:hi]
-        dst_bytes[lo:hi].copy_(stage[:hi - lo], non_blocking=False)
+    words = _upload_raw(arr, device).view(torch.int32)
     check(lib.cae_bswap32(words.data_ptr(), words.numel(), torch.cuda.current_stream(device).cuda_stream))
-    return out
+    return words.view(torch.float32).view(arr.shape)
+
+
+_TORCH_KINDS = {torch.float32: _lib.ELEM_F32, torch.float64: _lib.ELEM_F64}
+
+
+def _measure_operand(x, device):
+    """(device tensor kept alive, element kind, shape, case stride in elements) of one case_measures operand.  A CUDA
+    tensor is used in place; a C-contiguous big-endian >f4 / >f8 numpy array (a NetCDF-3 slab) goes up as its raw
+    bytes and is swapped inside the kernel; any other array is uploaded in its native fp32 / fp64 form."""
+    if isinstance(x, torch.Tensor):
+        if not x.is_cuda:
+            x = x.numpy()
+        else:
+            if x.dtype not in _TORCH_KINDS:
+                x = x.to(torch.float64)
+            x = x.contiguous()
+            return x, _TORCH_KINDS[x.dtype], tuple(x.shape), int(x.stride(0))
+    arr = np.asarray(x)
+    for (dtype, kind) in ((">f4", _lib.ELEM_F32_BE), (">f8", _lib.ELEM_F64_BE)):
+        if _is_big_endian_slab(arr, dtype):
+            raw = _upload_raw(arr, device)
+            return raw, kind, arr.shape, int(np.prod(arr.shape[1:]))
+    if arr.dtype.newbyteorder("=") != np.dtype(np.float32):
+        arr = arr.astype(np.float64)
+    t = torch.from_numpy(np.ascontiguousarray(arr, dtype=arr.dtype.newbyteorder("="))).to(device)
+    return t, _TORCH_KINDS[t.dtype], tuple(t.shape), int(np.prod(t.shape[1:]))
+
+
+def case_measures(pred, actual, device=None):
+    """Per-case (mae, mse) of channel 0, the reference's ModelEvaluator.compute_measure (model_evaluator.py:87-95)
+    for every case at once: mean |p - a| and mean (p - a)^2 over [i, 0, :, :] in fp64.  pred / actual: (N, C, H, W) numpy
+    arrays or CUDA tensors (fp32 or fp64; C may differ).  One streaming pass of cae_case_measures.  Returns an (N, 2)
+    float64 numpy array."""
+    if device is None:
+        device = next((x.device for x in (pred, actual) if isinstance(x, torch.Tensor) and x.is_cuda), None)
+    if device is None:
+        require_gpu()
+        device = torch.device("cuda", torch.cuda.current_device())
+    (p, pk, pshape, pstride) = _measure_operand(pred, device)
+    (a, ak, ashape, astride) = _measure_operand(actual, device)
+    if len(pshape) != 4 or len(ashape) != 4:
+        raise ValueError(f"case_measures: (N, C, H, W) arrays expected, got {pshape} and {ashape}")
+    if pshape[0] != ashape[0] or pshape[2:] != ashape[2:]:
+        raise ValueError(f"case_measures: prediction {pshape} and target {ashape} do not match")
+    (n, plane) = (int(pshape[0]), int(pshape[2] * pshape[3]))
+    out = torch.empty((n, 2), dtype=torch.float64, device=device)
+    if n == 0:
+        return np.zeros((0, 2), dtype=np.float64)
+    if plane == 0:
+        return np.full((n, 2), np.nan)      # np.mean of an empty plane
+    lib = _lib.load()
+    need = int(lib.cae_case_measures_workspace_bytes(n, plane))
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        check(lib.cae_case_measures(p.data_ptr(), pk, pstride, a.data_ptr(), ak, astride, n, plane, out.data_ptr(),
+                                    ws.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream))
+        sums = out.cpu().numpy()
+    return sums / float(plane)

@@ -111,6 +111,13 @@ class BaseModel:
               x_dimension="model_output_x", mask_variable_name=None):
         """Add `prediction_variable` (float64, denormalised, dims (case, channel, y, x)) to score_ds
         in place (:102-152)."""
+        self.apply_device(score_ds, input_variables, prediction_variable, channel_dimension, y_dimension, x_dimension,
+                          mask_variable_name)
+
+    def apply_device(self, score_ds, input_variables, prediction_variable="model_output",
+                     channel_dimension="model_output_channel", y_dimension="model_output_y",
+                     x_dimension="model_output_x", mask_variable_name=None):
+        """apply(), returning the float64 CUDA tensor whose host copy it stored (the evaluator measures it in place)"""
         from .. import dp as _dp
         _dp.ensure_process_group()      # a rank's GPU is selected before the data set is uploaded
         first = score_ds[input_variables[0]]
@@ -122,6 +129,7 @@ class BaseModel:
         out = ds.denormalise_device(y)   # fp64 on the device: min + y*(max-min), then one D2H copy
         score_ds[prediction_variable] = _make_data_array(score_ds, out.cpu().numpy(),
                                                          (n_dimension, channel_dimension, y_dimension, x_dimension))
+        return out
 
     def dump_metrics(self, title, metrics):
         print("\n" + title)

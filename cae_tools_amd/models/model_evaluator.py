@@ -1,0 +1,170 @@
+"""ModelEvaluator — the evaluate_cae back end with the reference's constructor and run() / evaluate_model_metrics() /
+build_html() / compute_measure() surface (src/cae_tools/models/model_evaluator.py).
+
+The metrics are model.evaluate() (scoring and cae_metric_sums on the GPU).  The report's per-case mae / mse of channel 0
+(:87-95, one numpy pass per case and measure there) are one streaming cae_case_measures pass per partition, reading the
+NetCDF-3 slabs as the file stores them, or the prediction the evaluator has just produced where it is still on the GPU.
+Departures from the reference: no output folder means metrics and database row only, not a crash on the
+unset report path; a missing --prediction-variable means apply()'s default "model_output", not None; the plots are SVG
+drawn by utils/report.py in place of seaborn PNGs; the netcdf2html case pages are made only where that optional package
+is installed.
+"""
+import json
+import os
+
+import numpy as np
+
+from ..data.arrays import as_numpy, open_mfdataset
+from ..engine import case_measures
+from ..utils.model_database import ModelDatabase
+from ..utils.report import evaluation_report
+from .base_model import _make_data_array
+from .ds_dataset import DSDataset
+from .model_loader import load_model
+
+MEASURES = ("mae", "mse")
+
+
+class ModelEvaluator:
+
+    def __init__(self, training_paths, testing_paths, output_html_folder="", model_output_variable="", model_path="",
+                 database_path="", input_variables=[], sample_count=None, x_coordinate="", y_coordinate="",
+                 time_coordinate=""):
+        self.training_paths = list(training_paths) if training_paths else []
+        self.testing_paths = list(testing_paths) if testing_paths else []
+        self.output_html_folder = output_html_folder
+        self.output_html_path = os.path.join(output_html_folder, "index.html") if output_html_folder else None
+        self.model_path = model_path
+        self.model_output_variable = model_output_variable or "model_output"
+        self.database_path = database_path
+        self.db = ModelDatabase(database_path) if database_path else None
+        self.input_variables = list(input_variables) if input_variables is not None else []
+        self.sample_count = sample_count
+        self.x_coordinate = x_coordinate
+        self.y_coordinate = y_coordinate
+        self.time_coordinate = time_coordinate
+
+        self.model = load_model(self.model_path)
+        print(f"Evaluating model id={self.model.get_model_id()}")
+        self.model_input_variables = self.model.get_input_variable_names()
+        self.output_variable = self.model.get_output_variable_name()
+        for input_variable in self.input_variables:
+            if input_variable not in self.model_input_variables:
+                raise Exception(f"requested {input_variable} is not a model input")
+        self._device_predictions = {}
+
+    def compute_measure(self, dataset, idx, measure):
+        """one case's mae or mse of channel 0 (:87-95); build_html computes all cases at once with case_measures"""
+        predicted = np.asarray(dataset[self.model_output_variable][idx, 0, :, :].values, dtype=np.float64)
+        actual = dataset[self.output_variable][idx, 0, :, :].values
+        if measure == "mae":
+            return np.mean(np.abs(predicted - actual))
+        elif measure == "mse":
+            return np.mean(np.power(predicted - actual, 2))
+        else:
+            raise ValueError("Unknown measure: " + measure)
+
+    def run(self):
+        (case_dimension, train_ds, test_ds, metrics) = self.evaluate_model_metrics()
+        if self.output_html_path:
+            self.build_html(case_dimension, train_ds, test_ds, metrics)
+
+    def _open(self, paths):
+        """the files of one partition concatenated along the case dimension (None when there are none)"""
+        if not paths:
+            return None
+        first = open_mfdataset(paths[:1])
+        if len(paths) == 1:
+            return first
+        return open_mfdataset(paths, concat_dim=first[self.output_variable].dims[0], combine="nested")
+
+    def _dataset(self, ds):
+        dsdata = DSDataset(ds, self.model.get_input_variable_names(), self.model.get_output_variable_name(),
+                           normalise_in=self.model.normalise_input, normalise_out=False)
+        dsdata.set_normalisation_parameters(self.model.normalisation_parameters)
+        return dsdata
+
+    def evaluate_model_metrics(self):
+        train_ds = self._open(self.training_paths)
+        test_ds = self._open(self.testing_paths)
+        either = train_ds if train_ds is not None else test_ds
+        case_dimension = either[self.output_variable].dims[0] if either is not None else None
+        training_cases_count = 0 if train_ds is None else train_ds[self.output_variable].shape[0]
+        testing_cases_count = 0 if test_ds is None else test_ds[self.output_variable].shape[0]
+        print("Evaluating training cases: %d, test cases: %d" % (training_cases_count, testing_cases_count))
+
+        metrics = {}
+        if test_ds is not None:
+            metrics["test"] = self.model.evaluate(self._dataset(test_ds))
+            self.model.dump_metrics("Test Metrics", metrics["test"])
+        if train_ds is not None:
+            metrics["train"] = self.model.evaluate(self._dataset(train_ds))
+            self.model.dump_metrics("Train Metrics", metrics["train"])
+        if self.db:
+            self.db.add_evaluation_result(self.model.get_model_id(), ",".join(self.training_paths),
+                                          ",".join(self.testing_paths), metrics)
+        return case_dimension, train_ds, test_ds, metrics
+
+    def case_measures(self, ds, partition):
+        """{"mae": (n,), "mse": (n,)} of every case of a partition; the prediction is measured on the GPU where
+        build_html has just made it, else as the dataset holds it"""
+        pred = self._device_predictions.get(partition)
+        if pred is None:
+            pred = as_numpy(ds[self.model_output_variable])
+        m = case_measures(pred, as_numpy(ds[self.output_variable]))
+        return {"mae": m[:, 0], "mse": m[:, 1]}
+
+    def build_html(self, case_dimension, train_ds, test_ds, model_metrics):
+        # partitions without scores are scored first (:163-168)
+        for (partition, ds) in (("train", train_ds), ("test", test_ds)):
+            if ds is not None and self.model_output_variable not in ds:
+                print(f"Applying model to generate {partition} scores")
+                self._device_predictions[partition] = self.model.apply_device(
+                    ds, input_variables=self.model.get_input_variable_names(),
+                    prediction_variable=self.model_output_variable)
+
+        with open(os.path.join(self.model_path, "history.json")) as f:
+            training_losses = json.loads(f.read())
+        with open(os.path.join(self.model_path, "parameters.json")) as f:
+            training_parameters = json.loads(f.read())
+
+        measures = []
+        case_links = {}
+        for (partition, ds) in (("test", test_ds), ("train", train_ds)):
+            if ds is None:
+                continue
+            values = self.case_measures(ds, partition)
+            for measure in MEASURES:
+                ds[measure] = _make_data_array(ds, values[measure], (case_dimension,))
+            measures.append((partition, values))
+            if self.x_coordinate and self.y_coordinate and self.time_coordinate:
+                if self._case_summary(case_dimension, partition, ds, train_ds, test_ds):
+                    case_links[partition] = partition + "/index.html"
+
+        page = evaluation_report(model_metrics, measures, training_parameters, training_losses, case_links)
+        os.makedirs(self.output_html_folder, exist_ok=True)
+        with open(self.output_html_path, "w") as f:
+            f.write(page)
+
+    def _case_summary(self, case_dimension, partition, ds, train_ds, test_ds):
+        """the optional netcdf2html case pages (:205-253, 285-293); False when they cannot be made"""
+        try:
+            from netcdf2html.api.netcdf2html_converter import Netcdf2HtmlConverter
+            layers = {}
+            shared = [self.output_variable, self.model_output_variable]
+            for v in self.input_variables + shared:
+                group = shared if v in shared else [v]
+                arrays = [np.asarray(d[name].values, dtype=np.float64) for d in (train_ds, test_ds) if d is not None
+                          for name in group]
+                layers[v] = {"label": v, "type": "single", "min_value": float(min(np.nanmin(a) for a in arrays)),
+                             "max_value": float(max(np.nanmax(a) for a in arrays)), "cmap": "coolwarm"}
+            config = {"dimensions": {"case": case_dimension},
+                      "coordinates": {"x": self.x_coordinate, "y": self.y_coordinate, "time": self.time_coordinate},
+                      "image": {"grid-width": 250, "max-zoom": 10}, "layers": layers}
+            converter = Netcdf2HtmlConverter(config, ds, os.path.join(self.output_html_folder, partition), title=partition,
+                                             sample_count=self.sample_count)
+            converter.run()
+            return True
+        except Exception:
+            print("Unable to create case summary")
+            return False

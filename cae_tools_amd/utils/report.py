@@ -1,0 +1,218 @@
+"""The evaluation report of evaluate_cae: a small HTML5 writer and the two plots it embeds, drawn as SVG.
+
+Standard library and numpy only (the reference draws its plots with seaborn / matplotlib, which are not dependencies
+here).  Every text and attribute value is escaped.  The plots are embedded as inline data: URIs, so index.html stands
+alone, as the reference's inlined PNGs do.
+"""
+import base64
+import html
+import math
+
+import numpy as np
+
+VOID = {"meta", "img", "br", "hr", "link"}
+
+
+class Element:
+    """one HTML element: add() appends a child element and returns it, text() appends escaped text and returns self"""
+
+    def __init__(self, tag, attrs=None):
+        self.tag = tag
+        self.attrs = dict(attrs or {})
+        self.children = []
+
+    def add(self, tag, attrs=None):
+        child = Element(tag, attrs)
+        self.children.append(child)
+        return child
+
+    def text(self, text):
+        self.children.append(str(text))
+        return self
+
+    def table(self, rows):
+        """a <table> of one <tr> per row and one <td> per cell"""
+        tbl = self.add("table")
+        for row in rows:
+            tr = tbl.add("tr")
+            for cell in row:
+                tr.add("td").text(cell)
+        return tbl
+
+    def render(self, out, depth=0):
+        pad = "  " * depth
+        attrs = "".join(f' {k}="{html.escape(str(v), quote=True)}"' for k, v in self.attrs.items() if v is not None)
+        if self.tag in VOID:
+            out.append(f"{pad}<{self.tag}{attrs}>")
+            return
+        if all(isinstance(c, str) for c in self.children):
+            out.append(f"{pad}<{self.tag}{attrs}>{''.join(html.escape(c, quote=False) for c in self.children)}</{self.tag}>")
+            return
+        out.append(f"{pad}<{self.tag}{attrs}>")
+        for c in self.children:
+            if isinstance(c, str):
+                out.append(pad + "  " + html.escape(c, quote=False))
+            else:
+                c.render(out, depth + 1)
+        out.append(f"{pad}</{self.tag}>")
+
+
+class Document:
+
+    def __init__(self, title, language="en"):
+        self.root = Element("html", {"lang": language})
+        self.head = self.root.add("head")
+        self.head.add("meta", {"charset": "utf-8"})
+        self.head.add("title").text(title)
+        self.body = self.root.add("body")
+
+    def html(self):
+        out = ["<!DOCTYPE html>"]
+        self.root.render(out)
+        return "\n".join(out) + "\n"
+
+
+def svg_data_uri(svg):
+    return "data:image/svg+xml;base64," + base64.b64encode(svg.encode("utf-8")).decode("ascii")
+
+
+# ---- plots -----------------------------------------------------------------------------------
+
+_W, _H = 640, 400
+_L, _R, _T, _B = 70, 20, 40, 50      # plot margins
+
+
+def _fmt(v):
+    return f"{v:.4g}"
+
+
+def _svg(title, body, xlabel, ylabel, x_range, y_range):
+    """an SVG document with a title, two axes labelled at their ends, and `body` (elements in plot coordinates)"""
+    (x0, x1), (y0, y1) = x_range, y_range
+    (px0, px1, py0, py1) = (_L, _W - _R, _H - _B, _T)
+    esc = html.escape
+    parts = [f'<svg xmlns="http://www.w3.org/2000/svg" width="{_W}" height="{_H}" viewBox="0 0 {_W} {_H}" '
+             'font-family="sans-serif" font-size="12">',
+             f'<rect x="0" y="0" width="{_W}" height="{_H}" fill="white"/>',
+             f'<text x="{_W / 2}" y="22" text-anchor="middle" font-size="15">{esc(title)}</text>',
+             f'<line x1="{px0}" y1="{py0}" x2="{px1}" y2="{py0}" stroke="black"/>',
+             f'<line x1="{px0}" y1="{py0}" x2="{px0}" y2="{py1}" stroke="black"/>',
+             f'<text x="{px0}" y="{py0 + 16}" text-anchor="middle">{esc(_fmt(x0))}</text>',
+             f'<text x="{px1}" y="{py0 + 16}" text-anchor="middle">{esc(_fmt(x1))}</text>',
+             f'<text x="{px0 - 6}" y="{py0}" text-anchor="end">{esc(_fmt(y0))}</text>',
+             f'<text x="{px0 - 6}" y="{py1 + 4}" text-anchor="end">{esc(_fmt(y1))}</text>',
+             f'<text x="{(px0 + px1) / 2}" y="{_H - 12}" text-anchor="middle">{esc(xlabel)}</text>',
+             f'<text x="16" y="{(py0 + py1) / 2}" text-anchor="middle" '
+             f'transform="rotate(-90 16 {(py0 + py1) / 2})">{esc(ylabel)}</text>']
+    parts.extend(body)
+    parts.append("</svg>")
+    return "\n".join(parts)
+
+
+def _scale(v, lo, hi, p_lo, p_hi):
+    return p_lo + (p_hi - p_lo) * ((v - lo) / (hi - lo) if hi > lo else 0.5)
+
+
+def histogram(values):
+    """(counts, edges) of the finite values with numpy's "auto" bins (seaborn histplot's default), and how many values
+    were left out as NaN / Inf"""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    finite = v[np.isfinite(v)]
+    if finite.size == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0), int(v.size)
+    edges = np.histogram_bin_edges(finite, "auto")
+    (counts, edges) = np.histogram(finite, bins=edges)
+    return counts, edges, int(v.size - finite.size)
+
+
+def svg_histogram(values, title):
+    """an SVG histogram: one <rect class="bar"> per bin carrying its count in data-count, in bin order"""
+    (counts, edges, dropped) = histogram(values)
+    if dropped:
+        title = f"{title} ({dropped} non-finite values not shown)"
+    if counts.size == 0:
+        return _svg(title, [], "value", "count", (0.0, 1.0), (0.0, 1.0))
+    top = max(int(counts.max()), 1)
+    (lo, hi) = (float(edges[0]), float(edges[-1]))
+    body = []
+    for k, c in enumerate(counts):
+        xa = _scale(float(edges[k]), lo, hi, _L, _W - _R)
+        xb = _scale(float(edges[k + 1]), lo, hi, _L, _W - _R)
+        y = _scale(float(c), 0.0, float(top), _H - _B, _T)
+        body.append(f'<rect class="bar" data-count="{int(c)}" x="{xa:.2f}" y="{y:.2f}" width="{max(xb - xa, 0.5):.2f}" '
+                    f'height="{(_H - _B) - y:.2f}" fill="steelblue" stroke="white" stroke-width="0.5"/>')
+    return _svg(title, body, "value", "count", (lo, hi), (0.0, float(top)))
+
+
+_COLOURS = ("steelblue", "darkorange", "seagreen", "crimson")
+
+
+def svg_lines(series, title, xlabel, ylabel):
+    """an SVG line plot of named (x, y) series; points whose y is not finite are left out"""
+    pts = {}
+    for name, (xs, ys) in series.items():
+        pts[name] = [(float(x), float(y)) for x, y in zip(xs, ys) if math.isfinite(float(y))]
+    every = [p for ps in pts.values() for p in ps]
+    if not every:
+        return _svg(title, [], xlabel, ylabel, (0.0, 1.0), (0.0, 1.0))
+    (x0, x1) = (min(p[0] for p in every), max(p[0] for p in every))
+    (y0, y1) = (min(p[1] for p in every), max(p[1] for p in every))
+    body = []
+    for k, (name, ps) in enumerate(pts.items()):
+        colour = _COLOURS[k % len(_COLOURS)]
+        xy = " ".join(f"{_scale(x, x0, x1, _L, _W - _R):.2f},{_scale(y, y0, y1, _H - _B, _T):.2f}" for x, y in ps)
+        if ps:
+            body.append(f'<polyline class="series" data-name="{html.escape(name)}" data-points="{len(ps)}" '
+                        f'points="{xy}" fill="none" stroke="{colour}" stroke-width="2"/>')
+        body.append(f'<line x1="{_W - _R - 110}" y1="{_T + 10 + 18 * k}" x2="{_W - _R - 90}" y2="{_T + 10 + 18 * k}" '
+                    f'stroke="{colour}" stroke-width="2"/>')
+        body.append(f'<text x="{_W - _R - 84}" y="{_T + 14 + 18 * k}">{html.escape(name)}</text>')
+    return _svg(title, body, xlabel, ylabel, (x0, x1), (y0, y1))
+
+
+def svg_history(history):
+    """log10 of the train and test losses against the test iteration; losses that are not positive are left out"""
+    series = {}
+    for name in ("train", "test"):
+        losses = [float(v) for v in history.get(f"{name}_loss", [])]
+        series[name] = (range(len(losses)), [math.log10(v) if v > 0 else math.nan for v in losses])
+    return svg_lines(series, "history", "test_iteration", "log_loss")
+
+
+# ---- the report ------------------------------------------------------------------------------
+
+STYLE = "body { font-family: sans-serif; margin: 1em 2em; } table { border-collapse: collapse; } " \
+        "td { border: 1px solid #bbb; padding: 2px 8px; } img { display: block; margin: 8px 0; }"
+
+
+def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None):
+    """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
+    metrics: {"test": {...}, "train": {...}} (either may be absent); measures: [(partition, {"mae": values, "mse": values})]
+    in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}."""
+    doc = Document("Model Evaluation")
+    doc.head.add("style").text(STYLE)
+    body = doc.body
+    body.add("h2").text("Model Metrics")
+    for (label, key) in (("Test Metrics", "test"), ("Train Metrics", "train")):
+        if key in metrics:
+            body.add("h3").text(label)
+            body.table([["Metric Name", "Metric Value"]] + [[k, f"{v:0.3f}"] for (k, v) in metrics[key].items()])
+    body.add("h2").text("Model Evaluation Results")
+    for (partition, values) in measures:
+        body.add("h3").text(partition)
+        for (measure, v) in values.items():
+            body.add("img", {"src": svg_data_uri(svg_histogram(v, measure)), "alt": f"{partition} {measure} histogram"})
+        if case_links and partition in case_links:
+            body.add("p").add("a", {"href": case_links[partition]}).text(f"Case summary for partition {partition}")
+    if parameters or history:
+        body.add("h2").text("Training Summary")
+    if parameters:
+        body.add("h2").text("Training Parameters")
+        rows = [["Parameter Name", "Parameter Value"]]
+        if history:
+            rows.append(["total epochs", str(history["nr_epochs"])])
+        rows.extend([k, str(v)] for (k, v) in parameters.items())
+        body.table(rows)
+    if history:
+        body.add("img", {"src": svg_data_uri(svg_history(history)), "alt": "training history", "width": 768})
+    return doc.html()

@@ -17,6 +17,7 @@
  *   models/ds_dataset.py:131-135    denormalise_output            -> cae_denormalise_f64
  *   cli/train_cae.py:58-59          xr.open_mfdataset -> float32 batches (big-endian NetCDF-3 slabs) -> cae_bswap32
  *   models/model_metric.py:25-71    ModelMetric (base_model.py:69-100 evaluate) -> cae_metric_sums
+ *   models/model_evaluator.py:87-95 ModelEvaluator.compute_measure (per-case mae / mse) -> cae_case_measures
  *
  * Conventions: plain pointers and sizes only.  Every pointer named *_dev is DEVICE memory
  * owned by the caller (the Python host allocates it as torch tensors and passes data_ptr());
@@ -292,6 +293,29 @@ int cae_bswap32(void* x_dev, int64_t n, void* hip_stream);
  *   mse/rmse/mae over all instances and averages the per-instance Pearson r.  n_inst <= 65535 per call. */
 int cae_metric_sums(const float* y_dev, const float* actual_dev, const float* mask_dev, int64_t n_inst,
                     int64_t inst_elems, double vmin, double range, double* sums_dev, void* hip_stream);
+
+/* ---- evaluator kernel (stateless) ---------------------------------------------------------- */
+
+/* Element kinds of cae_case_measures.  The big-endian kinds read a NetCDF-3 slab copied to the device as raw bytes
+ * (no cae_bswap32 pass: the bytes are swapped in registers). */
+enum cae_elem_kind {
+    CAE_ELEM_F32 = 0,       /* float, native byte order */
+    CAE_ELEM_F32_BE = 1,    /* float, big-endian */
+    CAE_ELEM_F64 = 2,       /* double, native byte order */
+    CAE_ELEM_F64_BE = 3     /* double, big-endian */
+};
+
+/* models/model_evaluator.py:87-95 (compute_measure, once per case and measure): for each case i of n_case,
+ *   out[i] = {S|p - a|, S(p - a)^2}   (fp64, p - a formed in fp64)
+ * over the first `plane` elements of the case (channel 0), which start at element i * pred_stride of pred_dev and
+ * i * actual_stride of actual_dev.  The host divides by plane for mae / mse.  NaN and Inf propagate as in IEEE
+ * arithmetic.  No atomics: per-(case, chunk) partials are folded in chunk order, so the sums are the same bits from run
+ * to run.  Any plane, stride and case start (pointers aligned to their element size); out_dev (n_case, 2) doubles.
+ * workspace_dev holds the partials: cae_case_measures_workspace_bytes(n_case, plane) bytes (0: none needed, NULL ok). */
+int64_t cae_case_measures_workspace_bytes(int64_t n_case, int64_t plane);
+int cae_case_measures(const void* pred_dev, int pred_kind, int64_t pred_case_stride, const void* actual_dev,
+                      int actual_kind, int64_t actual_case_stride, int64_t n_case, int64_t plane, double* out_dev,
+                      void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
 #ifdef __cplusplus
 }
