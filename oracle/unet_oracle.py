@@ -91,6 +91,7 @@ class ReluAlign:
     def __init__(self, decisions, tol=1e-5):
         self.decisions, self.tol, self.followed = decisions, float(tol), {}
         self.disagree = {}      # per site: (elements decided differently, the largest |pre-activation| among them)
+        self.worst = 0.0        # the largest |pre-activation| of a followed decision
 
     def __call__(self, name, x):
         own = x > 0
@@ -103,6 +104,8 @@ class ReluAlign:
             self.disagree[name] = (int(diff.sum()), float(x.detach().abs()[diff].max()) if bool(diff.any()) else 0.0)
         follow = diff & (x.detach().abs() < self.tol)
         self.followed[name] = self.followed.get(name, 0) + int(follow.sum())
+        if bool(follow.any()):
+            self.worst = max(self.worst, float(x.detach().abs()[follow].max()))
         return x * torch.where(follow, want, own).to(x.dtype)
 
     def __enter__(self):
@@ -118,6 +121,52 @@ class ReluAlign:
 
 def _relu(x, name):
     return F.relu(x) if _relu_hook is None else _relu_hook(name, x)
+
+
+# Max-pool decisions.  The attention gate pools the maximum of each (b, c) plane; where two entries of a plane are within
+# rounding of each other at the top, two fp32 implementations may pick different ones, and the whole gradient of that
+# plane's maximum lands on another pixel.  `ArgmaxAlign` hands the oracle the implementation's indices the same way
+# ReluAlign hands it ReLU decisions: followed only where the oracle's own value there is within `tol` of its own maximum.
+_argmax_hook = None
+
+
+class ArgmaxAlign:
+    """`decisions[name]`: integer array (B, C) of flat indices into each (b, c) plane, per pooling site 'att{j}' (the
+    attention gate of decoder layer j)"""
+
+    def __init__(self, decisions, tol=1e-5):
+        self.decisions, self.tol, self.followed = decisions, float(tol), {}
+        self.worst = 0.0        # the largest (own maximum - value at the followed index)
+
+    def __call__(self, name, x):
+        want = self.decisions.get(name)
+        if want is None:
+            return F.adaptive_max_pool2d(x, 1)
+        (B, C) = x.shape[:2]
+        flat = x.reshape(B, C, -1)
+        (mx, own) = flat.detach().max(dim=2)
+        want = torch.as_tensor(np.asarray(want), dtype=torch.int64).reshape(B, C)
+        gap = mx - flat.detach().gather(2, want.unsqueeze(2)).squeeze(2)
+        follow = (want != own) & (gap <= self.tol)
+        self.followed[name] = self.followed.get(name, 0) + int(follow.sum())
+        if bool(follow.any()):
+            self.worst = max(self.worst, float(gap[follow].max()))
+        idx = torch.where(follow, want, own)
+        return flat.gather(2, idx.unsqueeze(2)).reshape(B, C, 1, 1)
+
+    def __enter__(self):
+        global _argmax_hook
+        _argmax_hook = self
+        return self
+
+    def __exit__(self, *exc):
+        global _argmax_hook
+        _argmax_hook = None
+        return False
+
+
+def _maxpool(x, name):
+    return F.adaptive_max_pool2d(x, 1) if _argmax_hook is None else _argmax_hook(name, x)
 
 
 def _bn(x, st, key, train):
@@ -152,7 +201,7 @@ def channel_attention(dec, j, x):
     """unet.py:35-39: sigmoid(fc2(relu(fc1(avgpool(x)))) + fc2(relu(fc1(maxpool(x)))))"""
     w1, w2 = dec[f"attention_layers.{j}.fc1.weight"], dec[f"attention_layers.{j}.fc2.weight"]
     avg = F.adaptive_avg_pool2d(x, 1)
-    mx = F.adaptive_max_pool2d(x, 1)
+    mx = _maxpool(x, f"att{j}")
     a = F.conv2d(F.relu(F.conv2d(avg, w1)), w2)
     m = F.conv2d(F.relu(F.conv2d(mx, w1)), w2)
     return torch.sigmoid(a + m)

@@ -131,7 +131,7 @@ def hip_relu_decisions(eng, batch):
     return out
 
 
-def relu_fix_for(oracle, x, decisions, what, z_tol=2e-5, max_flips=16):
+def relu_fix_for(oracle, x, decisions, what, z_tol=1.2e-5, max_flips=12):
     """relu_fix argument (oracle/cae_oracle.py _relu) that gives `oracle` the ReLU decisions `decisions` (hip_relu_decisions)
     on input batch x - after checking that every position where the oracle decides otherwise is one it cannot decide: its own
     pre-activation there is rounding-sized (<= z_tol of the layer's scale), and there are only a handful of them.
@@ -140,20 +140,27 @@ def relu_fix_for(oracle, x, decisions, what, z_tol=2e-5, max_flips=16):
     gradient is a sum of ~N terms that cancel to ~sqrt(N) of one term, ONE flipped bit moves every upstream gradient by
     1e-4..1e-3 of its maximum (measured: tools/diag_dp64.py - a single mismatch at the 4->2 layer, |z64| = 7e-8, put the HIP
     path 1e-3 from an fp64 oracle that the fp32 oracle, which happened not to flip there, followed to 1e-6).  With the
-    decisions aligned what is left is rounding, and the strict fp64-anchored bound applies again.  Returns (fix, flips)."""
-    import torch
+    decisions aligned what is left is rounding, and the strict fp64-anchored bound applies again.
+    The window: over every caller (tests/test_full_size_gpu.py, tests/test_timed_path_gpu.py, the 16 shapes of
+    tests/test_s2_shapes_gpu.py) the worst |z| / scale of a differing decision measured 1.16e-6 (a batch-2 shape, where
+    BatchNorm over two samples amplifies rounding; 2.8e-7 at batch 32 and above) and one step showed at most 3 of them:
+    z_tol is 10x the first, max_flips 4x the second ('One ReLU bit').  Returns (fix, flips)."""
     z = oracle.relu_inputs(x)
-    (fix, flips) = ({}, 0)
+    (fix, flips, worst_all) = ({}, 0, 0.0)
     for name, passed in decisions.items():
         zk = z[name]
         d = passed.to(zk.dtype) - (zk > 0).to(zk.dtype)
         differs = d != 0
         n = int(differs.sum())
         if n:
-            worst = float(zk[differs].abs().max())
             scale = max(1.0, float(zk.abs().max()) / 8.0)
-            assert worst <= z_tol * scale, f"{what}: ReLU decision differs at {name} where the oracle's input is {worst:.3e} - not a rounding-sized input"
+            worst = float(zk[differs].abs().max()) / scale
+            worst_all = max(worst_all, worst)
+            assert worst <= z_tol, (f"{what}: ReLU decision differs at {name} where the oracle's input is {worst:.3e} of the "
+                                    f"layer's scale > {z_tol:.1e} - not a rounding-sized input")
             fix[name] = d
             flips += n
-    assert flips <= max_flips, f"{what}: {flips} ReLU decisions differ from the oracle's"
+    if flips:
+        print(f"\n[relu_fix_for] {what}: {flips} decisions followed, worst |z| / scale {worst_all:.3e}")
+    assert flips <= max_flips, f"{what}: {flips} ReLU decisions differ from the oracle's (worst |z| / scale {worst_all:.3e})"
     return fix, flips

@@ -94,11 +94,11 @@ def test_two_ranks_train_the_single_device_model(tmp_path):
     # Biases right before a BatchNorm have an exact gradient of 0, and those of the gated decoder layers nearly so (the
     # per-sample gate is all that keeps the BatchNorm from cancelling a shift): AdamW turns their rounding noise into
     # lr-sized steps of either sign on both sides, so they only get a bound on the update size.
-    from test_unet_hip_parity import _feeds_batchnorm
+    from unet_helpers import feeds_batchnorm
     last = len(one["tensors"]) and max(int(n.split(".")[1]) for n in one["tensors"] if n.startswith("dec/decoder_conv."))
 
     def noisy(key):
-        return _feeds_batchnorm(key) or (key.startswith("decoder_conv.") and key.endswith(".bias")
+        return feeds_batchnorm(key) or (key.startswith("decoder_conv.") and key.endswith(".bias")
                                          and int(key.split(".")[1]) < last)
     for (name, (arena, off, numel, _)) in one["tensors"].items():
         if arena != 0:

@@ -3,6 +3,7 @@ reference's own Encoder / Decoder / ChannelAttention / loss definitions (tests/g
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 from unet_helpers import TRAIN_CASES, UNET_CASES, UnetCase, unet_oracle
 
@@ -94,3 +95,24 @@ def test_relu_align_follows_foreign_decisions_only_near_zero():
     np.testing.assert_array_equal(y.detach().numpy(), np.array([[0.0, -3e-6, 0.0, 1.5], [0.3, 0.0, 2e-7, 0.0]], dtype=np.float32))
     np.testing.assert_array_equal(x.grad.numpy(), np.array([[0, 1, 0, 1], [1, 0, 1, 0]], dtype=np.float32))
     assert uo._relu_hook is None
+
+
+def test_argmax_align_follows_foreign_indices_only_near_ties():
+    """oracle.unet_oracle.ArgmaxAlign (the attention gate's max-pool decisions of the implementation under test): with no
+    decisions the pooling is adaptive_max_pool2d's; a foreign index is followed where the oracle's value there is within tol of
+    its own maximum (the maximum's gradient then lands on that index) and ignored anywhere else"""
+    from oracle import unet_oracle as uo
+    x = torch.tensor([[[[0.5, 1.0], [1.0 - 3e-6, -1.0]], [[2.0, 0.1], [0.2, 1.9]]]], requires_grad=True)   # (1, 2, 2, 2)
+    assert uo._argmax_hook is None
+    with uo.ArgmaxAlign({}) as al:
+        y = uo._maxpool(x, "att0")
+    assert torch.equal(y, F.adaptive_max_pool2d(x, 1)) and al.followed == {}
+    with uo.ArgmaxAlign({"att0": np.array([[2, 3]])}, tol=1e-5) as al:
+        y = uo._maxpool(x, "att0")      # plane 0: index 2 is 3e-6 below the maximum: followed; plane 1: 1.9 vs 2.0: ignored
+        other = uo._maxpool(x, "att1")  # no decisions for this site: plain max-pool
+    assert al.followed == {"att0": 1} and abs(al.worst - 3e-6) < 1e-7
+    assert torch.equal(other, F.adaptive_max_pool2d(x, 1))
+    np.testing.assert_array_equal(y.detach().numpy().reshape(-1), np.array([1.0 - 3e-6, 2.0], dtype=np.float32))
+    y.sum().backward()
+    np.testing.assert_array_equal(x.grad.numpy().reshape(2, 4), np.array([[0, 0, 1, 0], [1, 0, 0, 0]], dtype=np.float32))
+    assert uo._argmax_hook is None

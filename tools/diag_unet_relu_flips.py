@@ -9,8 +9,8 @@ import numpy as np, torch
 from cae_tools_amd.models.unet import Decoder, Encoder, unet_layer_spec
 from cae_tools_amd.unet_engine import UnetEngine
 from oracle import unet_oracle as uo
-from test_unet_hip_parity import _grad_dict, _feeds_batchnorm
-from unet_helpers import hip_relu_decisions
+from test_unet_hip_parity import _grad_dict
+from unet_helpers import feeds_batchnorm as _feeds_batchnorm, hip_relu_decisions
 spec = unet_layer_spec(3, 3, (64, 64), [32, 64, 96])
 (fc, latent, B) = (24, 6, 5)
 torch.manual_seed(123)
