@@ -26,6 +26,10 @@
 namespace unet {
 namespace {   // internal linkage: this header is compiled into more than one translation unit
 
+// every cross-workgroup fp64 sum lands on a fixed grid first (acc_add), so that its value does not depend on the order the
+// atomics arrive in
+#include "acc_grid.h"
+
 // sum of v over the block (any multiple of 64 threads), valid in thread 0.  red: LDS scratch of blockDim/64 doubles.
 template <int CTRL, int ROW_MASK = 0xF>
 __device__ __forceinline__ double dpp_d(double v) {
@@ -195,7 +199,7 @@ __global__ void __launch_bounds__(256) k_wgrad(Geom g, const float* __restrict__
         sum += (double)(S[((size_t)b * g.Cs + cs) * per + r] * L[(((size_t)b * g.Cl + cl) * g.Hl + Y) * g.Wl + X]);
     }
     const double t = block_sum(sum, red);
-    if (threadIdx.x == 0 && t != 0.0) atomicAdd(&acc[blockIdx.x], t);
+    if (threadIdx.x == 0 && t != 0.0) acc_add<ACC_GRAD>(&acc[blockIdx.x], t);
 }
 
 
@@ -323,9 +327,9 @@ __device__ __forceinline__ const float* z_plane(const float* z, long long zbs, c
 // per-channel reductions and BatchNorm (2-d: (B,C,HW); 1-d: HW = 1)
 // ---------------------------------------------------------------------------------------------
 
-// sums[c*sstride + 0..1] += sum x, sum x^2 over (b, i) of x[b*bs + c*HW + i] (the squares only if want_sq).
-// grid (chunks, C)
-template <int V>
+// sums[c*sstride + 0..1] += sum x, sum x^2 over (b, i) of x[b*bs + c*HW + i] (the squares only if want_sq), on the acc_add grid
+// KIND: ACC_STAT for BatchNorm statistics, ACC_GRAD for a bias gradient.  grid (chunks, C)
+template <int KIND, int V>
 __device__ __forceinline__ void chan_sums_body(const float* __restrict__ x, long long bs, int B, int HW, double* __restrict__ sums,
                                                int sstride, int want_sq, double* red) {
     const int c = blockIdx.y;
@@ -339,18 +343,22 @@ __device__ __forceinline__ void chan_sums_body(const float* __restrict__ x, long
             s2 += v * v;
         }
     });
+    // one workgroup per channel (BatchNorm1d, small maps): its sum is the only addend of the slot, order-free as it stands -
+    // the grid would only cost resolution, which a BatchNorm over a handful of values amplifies
+    const bool one = gridDim.x == 1;
     const double t1 = block_sum(s1, red);
-    if (threadIdx.x == 0) atomicAdd(&sums[(size_t)c * sstride], t1);
+    if (threadIdx.x == 0) one ? (void)atomicAdd(&sums[(size_t)c * sstride], t1) : acc_add<KIND>(&sums[(size_t)c * sstride], t1);
     if (want_sq) {
         const double t2 = block_sum(s2, red);
-        if (threadIdx.x == 0) atomicAdd(&sums[(size_t)c * sstride + 1], t2);
+        if (threadIdx.x == 0) one ? (void)atomicAdd(&sums[(size_t)c * sstride + 1], t2) : acc_add<KIND>(&sums[(size_t)c * sstride + 1], t2);
     }
 }
+template <int KIND>
 __global__ void __launch_bounds__(256) k_chan_sums(const float* __restrict__ x, long long bs, int B, int HW,
                                                    double* __restrict__ sums, int sstride, int want_sq) {
     __shared__ double red[4];
-    if (vec4_ok(HW, bs)) chan_sums_body<4>(x, bs, B, HW, sums, sstride, want_sq, red);
-    else chan_sums_body<1>(x, bs, B, HW, sums, sstride, want_sq, red);
+    if (vec4_ok(HW, bs)) chan_sums_body<KIND, 4>(x, bs, B, HW, sums, sstride, want_sq, red);
+    else chan_sums_body<KIND, 1>(x, bs, B, HW, sums, sstride, want_sq, red);
 }
 
 // a = dropout(relu(bn(z))), s = relu(bn(z)) (optional).  stat_mode 0: mean / invstd from `saved`; 1: running statistics
@@ -412,8 +420,8 @@ __global__ void __launch_bounds__(256) k_bn_act(const float* __restrict__ z, lon
         const double t1 = block_sum(q1, red);
         const double t2 = block_sum(q2, red);
         if (threadIdx.x == 0) {
-            atomicAdd(&skip_sums[2 * c], t1);
-            atomicAdd(&skip_sums[2 * c + 1], t2);
+            acc_add<ACC_STAT>(&skip_sums[2 * c], t1);
+            acc_add<ACC_STAT>(&skip_sums[2 * c + 1], t2);
         }
     }
 }
@@ -465,8 +473,8 @@ __global__ void __launch_bounds__(256) k_bn_bwd_reduce(const float* __restrict__
     const double t1 = block_sum(s1, red);
     const double t2 = block_sum(s2, red);
     if (threadIdx.x == 0) {
-        atomicAdd(&sums[2 * c], t1);
-        atomicAdd(&sums[2 * c + 1], t2);
+        acc_add<ACC_GRAD>(&sums[2 * c], t1);
+        acc_add<ACC_GRAD>(&sums[2 * c + 1], t2);
     }
 }
 
@@ -690,8 +698,8 @@ __global__ void __launch_bounds__(256) k_att_fwd(const float* __restrict__ pool,
         const float a = 1.f / (1.f + expf(-(oa + om)));
         att[(size_t)b * C + c] = a;
         if (sums) {   // channel c of the concatenated tensor is a * u: its sums over this sample's map
-            atomicAdd(&sums[2 * c], (double)a * psum[2 * ((size_t)b * C + c)]);
-            atomicAdd(&sums[2 * c + 1], (double)a * (double)a * psum[2 * ((size_t)b * C + c) + 1]);
+            acc_add<ACC_STAT>(&sums[2 * c], (double)a * psum[2 * ((size_t)b * C + c)]);
+            acc_add<ACC_STAT>(&sums[2 * c + 1], (double)a * (double)a * psum[2 * ((size_t)b * C + c) + 1]);
         }
     }
 }
@@ -727,13 +735,13 @@ __global__ void __launch_bounds__(256) k_att_bwd(const float* __restrict__ pool,
     for (int e = threadIdx.x; e < C * R; e += 256) {
         const int c = e / R, r = e - c * R;
         const float v = dout[c] * (fmaxf(h[r], 0.f) + fmaxf(h[R + r], 0.f));
-        if (v != 0.f) atomicAdd(&accW2[e], (double)v);
+        if (v != 0.f) acc_add<ACC_GRAD>(&accW2[e], (double)v);
     }
     __syncthreads();
     for (int e = threadIdx.x; e < R * C; e += 256) {
         const int r = e / C, c = e - r * C;
         const float v = dh[r] * avg[c] + dh[R + r] * mx[c];
-        if (v != 0.f) atomicAdd(&accW1[e], (double)v);
+        if (v != 0.f) acc_add<ACC_GRAD>(&accW1[e], (double)v);
     }
     for (int c = threadIdx.x; c < C; c += 256) {
         float ga = 0.f, gm = 0.f;
@@ -775,7 +783,7 @@ __global__ void __launch_bounds__(256) k_scale_bwd(const float* __restrict__ dca
     if (vec4_ok(HW)) body(std::integral_constant<int, 4>{});
     else body(std::integral_constant<int, 1>{});
     const double t = block_sum(s, red);
-    if (threadIdx.x == 0 && accb) atomicAdd(&accb[c], t);
+    if (threadIdx.x == 0 && accb) acc_add<ACC_GRAD>(&accb[c], t);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -906,7 +914,7 @@ __global__ void __launch_bounds__(256) k_loss_sums(const float* __restrict__ u, 
     }
     for (int k = 0; k < 7; k++) {
         const double t = block_sum(a[k], red);
-        if (threadIdx.x == 0 && t != 0.0) atomicAdd(&ls[(size_t)bc * 8 + k], t);
+        if (threadIdx.x == 0 && t != 0.0) acc_add<ACC_PLANE>(&ls[(size_t)bc * 8 + k], t);
     }
 }
 
@@ -1031,7 +1039,7 @@ __global__ void __launch_bounds__(256) k_loss_grad(const float* __restrict__ u, 
     }
     if (bias_acc) {
         const double t = block_sum(s, red);
-        if (threadIdx.x == 0 && t != 0.0) atomicAdd(&bias_acc[c], t);
+        if (threadIdx.x == 0 && t != 0.0) acc_add<ACC_GRAD>(&bias_acc[c], t);
     }
 }
 

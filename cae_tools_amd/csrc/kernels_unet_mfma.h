@@ -30,6 +30,35 @@ namespace {   // internal linkage: this header is compiled into more than one tr
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// The fp32 output of a convolution whose K is split into nsplit slices (blockIdx.z), element o of E.  Two slices add their
+// tiles to a zeroed map with fp32 atomics: 0 + a + b and 0 + b + a are the same number (fp32 addition commutes; only
+// associativity fails), so the result does not depend on which slice comes first.  With three or more it would, so then slice 0
+// stores its tile to S and slice z > 0 to part[(z - 1) * E + o]; k_slice_fold adds them to S in slice order afterwards.
+__device__ __forceinline__ void split_store(float* S, float* part, int nsplit, int z, long long E, long long o, float v) {
+    if (nsplit == 2) atomicAdd(S + o, v);
+    else if (z > 0) part[(long long)(z - 1) * E + o] = v;
+    else S[o] = v;
+}
+
+// S[o] = ((S[o] + part[o]) + part[E + o]) + ... over nparts partial maps (split_store): fp32, in slice order.  grid-stride,
+// V elements per thread (V = 4: E % 4 == 0 and 16-byte aligned maps)
+template <int V>
+__global__ void __launch_bounds__(256) k_slice_fold(float* __restrict__ S, const float* __restrict__ part, int nparts, long long E) {
+    typedef float fv __attribute__((ext_vector_type(V)));
+    for (long long o = ((long long)blockIdx.x * 256 + threadIdx.x) * V; o < E; o += (long long)gridDim.x * 256 * V) {
+        fv s = *reinterpret_cast<const fv*>(S + o);
+        for (int z = 0; z < nparts; z++) s += *reinterpret_cast<const fv*>(part + (long long)z * E + o);
+        *reinterpret_cast<fv*>(S + o) = s;
+    }
+}
+inline void slice_fold_launch(float* S, const float* part, int nparts, long long E, hipStream_t s) {
+    const bool v4 = (E & 3) == 0 && (reinterpret_cast<uintptr_t>(S) & 15) == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0;
+    const long long units = v4 ? E / 4 : E;
+    const dim3 grid((unsigned)std::min<long long>((units + 255) / 256, 4096));
+    if (v4) hipLaunchKernelGGL(k_slice_fold<4>, grid, dim3(256), 0, s, S, part, nparts, E);
+    else hipLaunchKernelGGL(k_slice_fold<1>, grid, dim3(256), 0, s, S, part, nparts, E);
+}
+
 constexpr int IG_KC = 16;   // K chunk
 constexpr int IG_KS = 16;   // LDS row pitch in floats: unpadded, quads XOR-swizzled (ig_swz)
 
@@ -57,7 +86,8 @@ struct OpDown {
     const float* __restrict__ w;
     const float* __restrict__ bias;
     float* __restrict__ S;
-    int nsplit, ksplit;   // K slices (blockIdx.z) of ksplit chunks; nsplit > 1: S is pre-zeroed and added to atomically
+    float* __restrict__ part;   // nsplit > 2: K slice z > 0 stores its tile at part + (z - 1) * (rows * cols), as S is laid out
+    int nsplit, ksplit;   // K slices (blockIdx.z) of ksplit chunks; nsplit == 2: S is pre-zeroed and both slices add to it
     struct Ctx {
         long long xbase[MD];
         unsigned vmask[MD];
@@ -121,12 +151,11 @@ struct OpDown {
         const long long b = m / HW;
         return b * g.Cs * HW + (m - b * HW);
     }
+    // (split_store: the rule for every split-K convolution of the UNET path)
     __device__ void store(long long cb, int n, float v, int z) const {
         if (n >= g.Cs || cb < 0) return;
-        float* dst = S + cb + (long long)n * g.Hs * g.Ws;
         if (z == 0 && bias) v += bias[n];
-        if (nsplit > 1) atomicAdd(dst, v);
-        else *dst = v;
+        split_store(S, part, nsplit, z, cols() * g.Cs, cb + (long long)n * g.Hs * g.Ws, v);
     }
 };
 
@@ -246,7 +275,7 @@ struct OpWgrad {
     const float* __restrict__ S;
     const float* __restrict__ L;
     double* __restrict__ acc;
-    float* __restrict__ part;   // nullptr: fp64 atomics into acc; else slice z stores its tile at part[(z * Cs + n) * Cl*16 + m]
+    float* __restrict__ part;   // nullptr: fp64 atomics into acc (ACC_GRAD grid); else slice z stores its tile at part[(z * Cs + n) * Cl*16 + m]
     int ksplit;   // chunks of 16 per z-slice
     struct Ctx {
         int dummy;
@@ -319,7 +348,7 @@ struct OpWgrad {
         atomicAdd(reinterpret_cast<float*>(acc) + (size_t)n * g.Cl * 16 + cb, v);
         return;
 #endif
-        atomicAdd(&acc[(size_t)n * g.Cl * 16 + cb], (double)v);
+        acc_add<ACC_GRAD>(&acc[(size_t)n * g.Cl * 16 + cb], (double)v);
     }
 };
 
@@ -327,7 +356,8 @@ struct OpWgrad {
 // plain GEMM through the same tile engine (the Linear layers): D[n][m] = sum_k A[n][k] * Bm[k][m] with arbitrary
 // strides (one of each operand's two strides is 1; the gather runs its lanes along that one).
 //   store 0: out[m*o_sm + n*o_sn] = v + bias[n]
-//   store 1: fp64 atomicAdd into scratch[n*cols + m]  (split K; k_gemm_finish applies store 0 afterwards)
+//   store 1: part[(z*rows + n)*cols + m] = v          (split K: K slice z's partial tile; k_gemm_finish folds the slices in
+//                                                      index order and applies store 0 afterwards)
 //   store 2: accd[n*o_sn + m*o_sm] += v               (fp64 gradient accumulator, one writer per element)
 // ---------------------------------------------------------------------------------------------
 template <int WM>
@@ -340,6 +370,7 @@ struct OpGemm {
     const float* __restrict__ bias;
     float* __restrict__ out;
     double* __restrict__ accd;
+    float* __restrict__ part;
     long long o_sn, o_sm;
     int mode, ksplit;
     struct Ctx {
@@ -393,12 +424,12 @@ struct OpGemm {
         return v;
     }
     __device__ long long col(long long m, int) const { return m < ncols ? m : -1; }
-    __device__ void store(long long m, int n, float v, int) const {
+    __device__ void store(long long m, int n, float v, int z) const {
         if (n >= nrows || m < 0) return;
         if (mode == 0) {
             out[m * o_sm + n * o_sn] = v + (bias ? bias[n] : 0.f);
         } else if (mode == 1) {
-            if (v != 0.f) atomicAdd(&accd[(size_t)n * ncols + m], (double)v);
+            part[((size_t)z * nrows + n) * ncols + m] = v;
         } else {
             accd[n * o_sn + m * o_sm] += (double)v;
         }
@@ -569,8 +600,9 @@ inline void igemm_dispatch(int rows, long long cols, int zdim, hipStream_t s, Fi
     }
 }
 
-inline void mfma_down_launch(const Geom& g, const float* L, const float* w, const float* bias, float* S, hipStream_t s) {
-    // few output tiles and a long K (the deep layers): slice K over blockIdx.z so that every CU has work
+// K slices of the tile engine's down convolution: few output tiles and a long K (the deep layers) - slice K over blockIdx.z so
+// that every CU has work
+inline int mfma_down_slices(const Geom& g) {
     const int rows = g.Cs;
     const long long cols = (long long)g.B * g.Hs * g.Ws;
     const int TN = rows <= 32 ? 32 : rows <= 64 ? 64 : 128, TM = rows <= 32 ? 512 : rows <= 64 ? 256 : 128;
@@ -581,11 +613,27 @@ inline void mfma_down_launch(const Geom& g, const float* L, const float* w, cons
 #define IG_SPLIT_TARGET 384
 #endif
     while (tiles * nsplit < IG_SPLIT_TARGET && chunks / (nsplit * 2) >= 8 && nsplit < 8) nsplit *= 2;
-    const int per = (chunks + nsplit - 1) / nsplit;
-    if (nsplit > 1) (void)hipMemsetAsync(S, 0, (size_t)cols * rows * sizeof(float), s);
+    return nsplit;
+}
+// bytes of the partial maps of K slices 1.. (split_store; 0: at most two slices)
+inline size_t mfma_down_part_bytes(const Geom& g) {
+    const int nsplit = mfma_down_slices(g);
+    return nsplit > 2 ? (size_t)(nsplit - 1) * g.B * g.Cs * g.Hs * g.Ws * sizeof(float) : 0;
+}
+
+// part: part_bytes of room for the partial maps (mfma_down_part_bytes); K is sliced at most twice when they do not fit
+inline void mfma_down_launch(const Geom& g, const float* L, const float* w, const float* bias, float* S, float* part,
+                             size_t part_bytes, hipStream_t s) {
+    const int rows = g.Cs;
+    const long long cols = (long long)g.B * g.Hs * g.Ws;
+    int nsplit = mfma_down_slices(g);
+    if (nsplit > 2 && (!part || mfma_down_part_bytes(g) > part_bytes)) nsplit = 2;
+    const int per = (g.Cl + nsplit - 1) / nsplit;
+    if (nsplit == 2) (void)hipMemsetAsync(S, 0, (size_t)cols * rows * sizeof(float), s);
     igemm_dispatch<OpDown>(rows, cols, nsplit, s, [&](auto& op) {
-        op.g = g, op.L = L, op.w = w, op.bias = bias, op.S = S, op.nsplit = nsplit, op.ksplit = per;
+        op.g = g, op.L = L, op.w = w, op.bias = bias, op.S = S, op.part = part, op.nsplit = nsplit, op.ksplit = per;
     });
+    if (nsplit > 2) slice_fold_launch(S, part, nsplit - 1, cols * rows, s);
 }
 
 // wp: the layer's weights repacked by k_pack_up_weights (Cs*Cl*16 floats)
@@ -638,7 +686,8 @@ inline size_t mfma_wgrad_part_bytes(const Geom& g) {
     return (size_t)mfma_wgrad_slices(g) * g.Cs * g.Cl * 16 * sizeof(float);
 }
 
-// part: room for mfma_wgrad_part_bytes(g) (the slices' tiles, folded in order by k_wgrad_fold) or nullptr (fp64 atomics)
+// part: room for mfma_wgrad_part_bytes(g) (the slices' tiles, folded in order by k_wgrad_fold) or nullptr (fp64 atomics on the
+// ACC_GRAD grid)
 inline void mfma_wgrad_launch(const Geom& g, const float* S, const float* L, double* acc, float* part, hipStream_t s) {
     const int rows = g.Cs;
     const long long cols = (long long)g.Cl * 16;
@@ -664,15 +713,17 @@ inline void mfma_wgrad_launch(const Geom& g, const float* S, const float* L, dou
     }
 }
 
-// out[m*o_sm + n*o_sn] = scratch[n*cols + m] + bias[n]; scratch is cleared for the next use
-__global__ void __launch_bounds__(256) k_gemm_finish(int nrows, int ncols, double* __restrict__ scratch,
+// out[m*o_sm + n*o_sn] = bias[n] + sum over the K slices z of part[(z*rows + n)*cols + m]: fp64, slices in index order (no
+// atomics: the result does not depend on timing)
+__global__ void __launch_bounds__(256) k_gemm_finish(int nrows, int ncols, int slices, const float* __restrict__ part,
                                                      const float* __restrict__ bias, float* __restrict__ out, long long o_sn,
                                                      long long o_sm) {
     const int total = nrows * ncols;
     for (int e = blockIdx.x * 256 + threadIdx.x; e < total; e += gridDim.x * 256) {
         const int n = e / ncols, m = e - n * ncols;
-        out[m * o_sm + n * o_sn] = (float)(scratch[e] + (bias ? (double)bias[n] : 0.0));
-        scratch[e] = 0.0;
+        double s = 0.0;
+        for (int z = 0; z < slices; z++) s += (double)part[(size_t)z * total + e];
+        out[m * o_sm + n * o_sn] = (float)(s + (bias ? (double)bias[n] : 0.0));
     }
 }
 
@@ -698,29 +749,44 @@ struct GemmDesc {
     int mode;
 };
 
-// scratch: zero-filled doubles, rows*cols of them, only touched when K is split
-inline void gemm_launch(const GemmDesc& d, double* scratch, hipStream_t s) {
-    const int TN = d.rows <= 32 ? 32 : d.rows <= 64 ? 64 : 128, TM = d.rows <= 32 ? 512 : d.rows <= 64 ? 256 : 128;
-    const long long tiles = (long long)((d.rows + TN - 1) / TN) * ((d.cols + TM - 1) / TM);
-    const int chunks = (d.K + IG_KC - 1) / IG_KC;
+// K slices of a store-0 GEMM through gemm_launch (1: K is not split) and the ksplit chunks each: few tiles and a long K
+inline int gemm_slices(int rows, int cols, int K, int* per_out = nullptr) {
+    const int TN = rows <= 32 ? 32 : rows <= 64 ? 64 : 128, TM = rows <= 32 ? 512 : rows <= 64 ? 256 : 128;
+    const long long tiles = (long long)((rows + TN - 1) / TN) * ((cols + TM - 1) / TM);
+    const int chunks = (K + IG_KC - 1) / IG_KC;
     int zdim = 1, per = chunks;
-    if (d.mode == 0 && scratch && tiles < 256 && chunks >= 64) {      // few tiles, long K: split it
+    if (tiles < 256 && chunks >= 64) {
         long long want = (1024 + tiles - 1) / tiles;
         per = (int)((chunks + want - 1) / want);
         if (per < 16) per = 16;
         zdim = (chunks + per - 1) / per;
     }
+    if (per_out) *per_out = per;
+    return zdim;
+}
+// bytes of the K slices' partial tiles gemm_launch writes for a store-0 GEMM of this shape (0: K is not split)
+inline size_t gemm_part_bytes(int rows, int cols, int K) {
+    const int zdim = gemm_slices(rows, cols, K);
+    return zdim > 1 ? (size_t)zdim * rows * cols * sizeof(float) : 0;
+}
+
+// part: part_bytes of room for the K slices' partial tiles, or nullptr.  K is split only when they fit (gemm_part_bytes); the
+// engines size the buffer from their plan so that they always do
+inline void gemm_launch(const GemmDesc& d, float* part, size_t part_bytes, hipStream_t s) {
+    int per = 0;
+    int zdim = gemm_slices(d.rows, d.cols, d.K, &per);
+    if (d.mode != 0 || !part || gemm_part_bytes(d.rows, d.cols, d.K) > part_bytes) zdim = 1, per = (d.K + IG_KC - 1) / IG_KC;
     const bool split = zdim > 1;
     igemm_dispatch<OpGemm>(d.rows, d.cols, zdim, s, [&](auto& op) {
         op.nrows = d.rows, op.ncols = d.cols, op.K = d.K;
         op.a = d.a, op.a_sn = d.a_sn, op.a_sk = d.a_sk;
         op.b = d.b, op.b_sk = d.b_sk, op.b_sm = d.b_sm;
-        op.bias = d.bias, op.out = d.out, op.accd = split ? scratch : d.accd;
+        op.bias = d.bias, op.out = d.out, op.accd = d.accd, op.part = part;
         op.o_sn = d.o_sn, op.o_sm = d.o_sm;
         op.mode = split ? 1 : d.mode, op.ksplit = per;
     });
     if (split)
-        hipLaunchKernelGGL(k_gemm_finish, dim3((d.rows * d.cols + 255) / 256), dim3(256), 0, s, d.rows, d.cols, scratch,
+        hipLaunchKernelGGL(k_gemm_finish, dim3((d.rows * d.cols + 255) / 256), dim3(256), 0, s, d.rows, d.cols, zdim, part,
                            d.bias, d.out, d.o_sn, d.o_sm);
 }
 

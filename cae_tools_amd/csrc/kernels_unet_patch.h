@@ -16,7 +16,8 @@
 // rows; a wave owns 32 of them and all the rows), K walked in chunks of 64 = four input channels.  The weight chunk is a
 // [rows][64 + 4] LDS tile whose taps are stored (kx0, kx2, kx1, kx3), so that one ds_read_b64 per (row block, channel, ky) gives
 // a lane its two k values; the patch is read one ds_read_b32 per step.  The next chunk's weights and patch rows are in registers while this one is
-// multiplied.  Deep layers with few pixel tiles slice K over blockIdx.z onto a zeroed output (fp32 atomics), as the tile engine.
+// multiplied.  Deep layers with few pixel tiles slice K over blockIdx.z and combine the slices as the tile engine does
+// (split_store: two slices by fp32 atomics onto a zeroed output, which commute; more through partial maps folded in slice order).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -60,10 +61,12 @@ inline size_t patch_lds_bytes(const Geom& g, int rbn) {
     return (size_t)(32 * rbn * kPatchWP + kPatchCG * patch_shape(g).planep + 4) * sizeof(float);
 }
 
-// grid (B * tiles, ceil(Cs / (32 RBN)), K slices), block 256, dynamic LDS patch_lds_bytes.  gper: channel groups per K slice
+// grid (B * tiles, ceil(Cs / (32 RBN)), K slices), block 256, dynamic LDS patch_lds_bytes.  gper: channel groups per K slice;
+// part: the partial maps of slices 1.. when there are more than two (split_store)
 template <int RBN>
 __global__ void __launch_bounds__(256) k_pdown(Geom g, const float* __restrict__ L, const float* __restrict__ w,
-                                               const float* __restrict__ bias, float* __restrict__ S, int gper, int nsplit) {
+                                               const float* __restrict__ bias, float* __restrict__ S, float* __restrict__ part,
+                                               int gper, int nsplit) {
     constexpr int TN = 32 * RBN;
     extern __shared__ float4 patch_lds4[];
     float* Wt = reinterpret_cast<float*>(patch_lds4);        // [TN][68]
@@ -147,8 +150,8 @@ __global__ void __launch_bounds__(256) k_pdown(Geom g, const float* __restrict__
                 for (int rb = 0; rb < RBN; rb++) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[rb].y, b1, acc[rb], 0, 0, 0);
             }
     }
-    float* out = S + (((long long)b * g.Cs + n0 + 4 * h) * g.Hs + y0 + yl) * g.Ws + xl;
-    const long long plane = (long long)g.Hs * g.Ws;
+    const long long o0 = (((long long)b * g.Cs + n0 + 4 * h) * g.Hs + y0 + yl) * g.Ws + xl;
+    const long long plane = (long long)g.Hs * g.Ws, E = (long long)g.B * g.Cs * plane;
 #pragma unroll
     for (int rb = 0; rb < RBN; rb++)
 #pragma unroll
@@ -158,12 +161,12 @@ __global__ void __launch_bounds__(256) k_pdown(Geom g, const float* __restrict__
             if (n >= g.Cs) continue;
             float v = acc[rb][r];
             if (bias && blockIdx.z == 0) v += bias[n];
-            if (nsplit > 1) atomicAdd(out + (long long)row * plane, v);
-            else out[(long long)row * plane] = v;
+            split_store(S, part, nsplit, blockIdx.z, E, o0 + (long long)row * plane, v);
         }
 }
 
-inline void pdown_launch(const Geom& g, const float* L, const float* w, const float* bias, float* S, hipStream_t s) {
+// row-block count (RBN) and K slices of k_pdown for this geometry
+inline int pdown_slices(const Geom& g, int* rbn_out = nullptr) {
     const PatchShape sh = patch_shape(g);
     // 64-row tiles where there are few pixel tiles (the deep layers): twice the workgroups without slicing K twice as fine -
     // half the atomics, or none (101 -> 77 us and 102 -> 84 us for the encoder's 32 x 32 and 16 x 16 layers at batch 32)
@@ -173,12 +176,32 @@ inline void pdown_launch(const Geom& g, const float* L, const float* w, const fl
     const int groups = g.Cl / kPatchCG;
     int nsplit = 1;     // few tiles and a long K: slice it so that every CU has work
     while (tiles * nsplit < 384 && groups / (nsplit * 2) >= 16 / kPatchCG && nsplit < 8) nsplit *= 2;
+    if (rbn_out) *rbn_out = rbn;
+    return nsplit;
+}
+// bytes of the partial maps of K slices 1.. (split_store; 0: at most two slices)
+inline size_t pdown_part_bytes(const Geom& g) {
+    const int nsplit = pdown_slices(g);
+    return nsplit > 2 ? (size_t)(nsplit - 1) * g.B * g.Cs * g.Hs * g.Ws * sizeof(float) : 0;
+}
+
+// part: part_bytes of room for the partial maps (pdown_part_bytes); K is sliced at most twice when they do not fit
+inline void pdown_launch(const Geom& g, const float* L, const float* w, const float* bias, float* S, float* part, size_t part_bytes,
+                         hipStream_t s) {
+    const PatchShape sh = patch_shape(g);
+    int rbn = 2;
+    int nsplit = pdown_slices(g, &rbn);
+    if (nsplit > 2 && (!part || pdown_part_bytes(g) > part_bytes)) nsplit = 2;
+    const int TN = 32 * rbn, rt = (g.Cs + TN - 1) / TN;
+    const int groups = g.Cl / kPatchCG;
     const int gper = (groups + nsplit - 1) / nsplit;
-    if (nsplit > 1) (void)hipMemsetAsync(S, 0, (size_t)g.B * g.Cs * g.Hs * g.Ws * sizeof(float), s);
+    const long long E = (long long)g.B * g.Cs * g.Hs * g.Ws;
+    if (nsplit == 2) (void)hipMemsetAsync(S, 0, (size_t)E * sizeof(float), s);
     const dim3 grid((unsigned)(g.B * sh.tiles), rt, nsplit);
     const size_t lds = patch_lds_bytes(g, rbn);
-    if (rbn == 2) hipLaunchKernelGGL(k_pdown<2>, grid, dim3(256), lds, s, g, L, w, bias, S, gper, nsplit);
-    else hipLaunchKernelGGL(k_pdown<4>, grid, dim3(256), lds, s, g, L, w, bias, S, gper, nsplit);
+    if (rbn == 2) hipLaunchKernelGGL(k_pdown<2>, grid, dim3(256), lds, s, g, L, w, bias, S, part, gper, nsplit);
+    else hipLaunchKernelGGL(k_pdown<4>, grid, dim3(256), lds, s, g, L, w, bias, S, part, gper, nsplit);
+    if (nsplit > 2) slice_fold_launch(S, part, nsplit - 1, E, s);
 }
 
 

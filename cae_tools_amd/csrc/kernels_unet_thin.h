@@ -184,7 +184,7 @@ __global__ void __launch_bounds__(256) k_thin_wgrad(Geom g, const float* __restr
         const float v = red[idx];
         if (cs >= g.Cs || t >= ncol) continue;
         if (part) part[(size_t)blockIdx.x * g.Cs * ncol + (size_t)cs * ncol + t] = v;     // k_thin_fold adds the workgroups' tiles
-        else if (v != 0.f) atomicAdd(&acc[(size_t)cs * ncol + t], (double)v);
+        else if (v != 0.f) acc_add<ACC_GRAD>(&acc[(size_t)cs * ncol + t], (double)v);
     }
 }
 
@@ -225,7 +225,7 @@ inline int thin_wgrad_groups(const Geom& g) {
 // bytes of partial tiles a launch writes (one Cs x 16 Cl tile per workgroup)
 inline size_t thin_wgrad_part_bytes(const Geom& g) { return (size_t)g.B * thin_wgrad_groups(g) * g.Cs * 16 * g.Cl * sizeof(float); }
 
-// part: room for thin_wgrad_part_bytes(g), or nullptr (fp64 atomics from every workgroup instead)
+// part: room for thin_wgrad_part_bytes(g), or nullptr (fp64 atomics on the ACC_GRAD grid from every workgroup instead)
 inline void thin_wgrad_launch(const Geom& g, const float* S, const float* L, double* acc, float* part, hipStream_t s) {
     const int tpw = thin_wgrad_tpw(g), nwg = g.B * thin_wgrad_groups(g);
     if (g.Cs <= 32) hipLaunchKernelGGL(k_thin_wgrad<1>, dim3(nwg), dim3(256), thin_lds_bytes(g, 1), s, g, S, L, acc, part, tpw);

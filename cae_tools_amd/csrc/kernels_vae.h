@@ -22,6 +22,9 @@ namespace vae {
 namespace {   // internal linkage: this header is compiled into more than one translation unit
 
 using unet::block_sum;
+using unet::acc_add;
+using unet::ACC_GRAD;
+using unet::ACC_PLANE;
 using unet::pcg;
 
 constexpr int kWin = 11, kHalo = 10, kTile = 16, kIn = kTile + kHalo;   // 26
@@ -56,7 +59,8 @@ __device__ __forceinline__ float normal_hash(uint32_t key, uint32_t idx) {
 // heads: (B, 2 * L) rows [mu | logvar] - the two heads are ONE Linear layer of the trunk (trunk_api.h).  i = b * L + j is the
 // element's index in the (B, L) latent array; the noise hash counts in the GLOBAL batch's array, (row0 + b) * L + j, so that a
 // data-parallel shard holding rows row0.. of it draws the eps of those rows (row0 0: a whole batch, what the oracle counts in).
-// z = mu + eps * exp(logvar / 2) (train) or mu (eval); kl_out += -0.5 * sum(1 + lv - mu^2 - exp(lv)).  one block per launch chunk
+// z = mu + eps * exp(logvar / 2) (train) or mu (eval); kl_out += -0.5 * sum(1 + lv - mu^2 - exp(lv)) (ACC_PLANE grid).  one block
+// per launch chunk
 __global__ void __launch_bounds__(256) k_reparam(const float* __restrict__ heads, int B, int L, int row0, uint32_t key, int train,
                                                  float* __restrict__ z, float* __restrict__ eps, double* __restrict__ kl_out) {
     __shared__ double red[4];
@@ -72,7 +76,7 @@ __global__ void __launch_bounds__(256) k_reparam(const float* __restrict__ heads
         s += (double)(1.f + l - m * m - expf(l));
     }
     const double t = block_sum(s, red);
-    if (threadIdx.x == 0) atomicAdd(kl_out, -0.5 * t);
+    if (threadIdx.x == 0) acc_add<ACC_PLANE>(kl_out, -0.5 * t);
 }
 
 // dmu = dz + lambda_kl * mu / n;  dlv = dz * eps * 0.5 * exp(lv/2) + lambda_kl * 0.5 * (exp(lv) - 1) / n;  rows [dmu | dlv]
@@ -178,8 +182,8 @@ __global__ void __launch_bounds__(256) k_ssim_fwd(const float* __restrict__ X, c
     const double t1 = block_sum(s_ssim, red);
     const double t2 = block_sum(s_cs, red);
     if (threadIdx.x == 0) {
-        atomicAdd(&sums[2 * bc], t1);
-        atomicAdd(&sums[2 * bc + 1], t2);
+        acc_add<ACC_PLANE>(&sums[2 * bc], t1);
+        acc_add<ACC_PLANE>(&sums[2 * bc + 1], t2);
     }
 }
 
@@ -309,8 +313,8 @@ __device__ __forceinline__ void ssim_fwd_rows_body(const float* __restrict__ X, 
     }
     const double t1 = ssim_wave_sum(acc_ssim), t2 = ssim_wave_sum(acc_cs);
     if (lane == 0) {
-        atomicAdd(&sums[2 * bc], t1);
-        atomicAdd(&sums[2 * bc + 1], t2);
+        acc_add<ACC_PLANE>(&sums[2 * bc], t1);
+        acc_add<ACC_PLANE>(&sums[2 * bc + 1], t2);
     }
 }
 
@@ -616,12 +620,13 @@ __global__ void __launch_bounds__(256) k_sigmoid_gather(const float* __restrict_
     }
 }
 
-// du = scale * (lambda_mse * 2 (y - t) / n_g + gssim) * y (1 - y);  mse_out += sum (y-t)^2 / mse_div
+// du = scale * (lambda_mse * 2 (y - t) / n_g + gssim) * y (1 - y);  mse_out += sum (y-t)^2 / n_g
 // (scale: the data-parallel weight local / global batch of this rank's gradient, 1 on a single device; n_g: the n of the mean,
-// n itself but for a data-parallel shard of a global batch, whose mse_div 1 leaves the raw sum for the all-reduce)
-// du_sum (single-channel outputs): += sum du = the last layer's bias gradient, in the pass that writes du
+// n itself but for a data-parallel shard of a global batch, whose share of the mean the all-reduce adds up)
+// du_sum (single-channel outputs): += sum du = the last layer's bias gradient, in the pass that writes du.  Both sums on the
+// ACC_GRAD grid (the mean squared error of outputs in (0, 1) is below 1)
 __global__ void __launch_bounds__(256) k_vae_loss_grad(const float* __restrict__ y, const float* __restrict__ t,
-                                                       const float* __restrict__ gssim, long long n, long long n_g, double mse_div,
+                                                       const float* __restrict__ gssim, long long n, long long n_g,
                                                        float lambda_mse, float scale, float* __restrict__ du,
                                                        double* __restrict__ mse_out, double* __restrict__ du_sum) {
     __shared__ double red[4];
@@ -648,11 +653,11 @@ __global__ void __launch_bounds__(256) k_vae_loss_grad(const float* __restrict__
         }
     }
     const double tt = block_sum(s, red);
-    if (threadIdx.x == 0) atomicAdd(mse_out, tt / mse_div);
+    if (threadIdx.x == 0) acc_add<ACC_GRAD>(mse_out, tt / (double)n_g);
     if (du && du_sum) {
         __syncthreads();
         const double tb = block_sum(sb, red);
-        if (threadIdx.x == 0) atomicAdd(du_sum, tb);
+        if (threadIdx.x == 0) acc_add<ACC_GRAD>(du_sum, tb);
     }
 }
 

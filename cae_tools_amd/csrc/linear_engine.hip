@@ -16,7 +16,8 @@ using namespace cae_internal;
 
 namespace {
 
-// g = 2 (y - t) / n (optional);  loss_out += sum (y - t)^2 / n;  t gathered through perm
+// g = 2 (y - t) / n (optional);  loss_out += sum (y - t)^2 / n (on the ACC_GRAD grid: exact while the loss is below 8);  t
+// gathered through perm
 __global__ void __launch_bounds__(256) k_mse(const float* __restrict__ y, const float* __restrict__ target, const int* __restrict__ perm,
                                              long long start, int B, long long E, float* __restrict__ g, double* __restrict__ loss_out) {
     __shared__ double red[4];
@@ -31,14 +32,14 @@ __global__ void __launch_bounds__(256) k_mse(const float* __restrict__ y, const 
         if (g) g[o] = k * d;
     }
     const double t = block_sum(s, red);
-    if (threadIdx.x == 0) atomicAdd(loss_out, t / (double)n);
+    if (threadIdx.x == 0) acc_add<ACC_GRAD>(loss_out, t / (double)n);
 }
 
 }  // namespace
 
 struct lin_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets, loss slots: engine_host.h)
     int64_t nin = 0, nout = 0, n_params = 0;
-    int64_t off_gacc = 0, off_gscratch = 0, off_xb = 0, off_y = 0, off_g = 0;
+    int64_t off_gacc = 0, off_gpart = 0, gpart_bytes = 0, off_xb = 0, off_y = 0, off_g = 0;
     float *params = nullptr, *m = nullptr, *v = nullptr;
     vae::AdamHyper hyper{1e-3, 0.9, 0.999, 1e-8, 1e-5};
     bool gacc_clean = false;
@@ -53,7 +54,7 @@ namespace {
 int forward(lin_engine* e, const float* x, int B, float* y) {
     // y[b][o] = bias[o] + sum_i x[b][i] W[o][i]
     GemmDesc d{(int)e->nout, B, (int)e->nin, e->params, e->nin, 1, x, 1, e->nin, e->params + e->nout * e->nin, y, nullptr, 1, e->nout, 0};
-    gemm_launch(d, reinterpret_cast<double*>(e->ws + e->off_gscratch), e->stream);
+    gemm_launch(d, reinterpret_cast<float*>(e->ws + e->off_gpart), e->gpart_bytes, e->stream);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
@@ -73,7 +74,7 @@ int step_common(lin_engine* e, int which, const int32_t* perm, int64_t start, in
         e->gacc_clean = false;
         // dW[o][i] = sum_b g[b][o] x[b][i];  db[o] = sum_b g[b][o]
         GemmDesc w{(int)e->nout, (int)e->nin, batch, e->g(), 1, e->nout, e->xb(), e->nin, 1, nullptr, nullptr, e->gacc(), e->nin, 1, 2};
-        gemm_launch(w, nullptr, e->stream);
+        gemm_launch(w, nullptr, 0, e->stream);
         hipLaunchKernelGGL(k_col_sums, dim3((unsigned)((e->nout + 255) / 256)), dim3(256), 0, e->stream, batch, (int)e->nout, e->g(),
                            e->gacc() + e->nout * e->nin);
         if (grads_out)
@@ -103,7 +104,9 @@ int lin_engine_create(int64_t n_in, int64_t n_out, int max_batch, lin_engine** o
     Carver bytes{256};
     e->off_gacc = bytes(e->n_params * 8);
     e->off_losses = bytes((int64_t)kStepLossSlots * e->per_slot * 8);
-    e->off_gscratch = bytes(std::max(n_in, n_out) * max_batch * 8);
+    for (int b = 1; b <= max_batch; b++)   // the forward's K slices (split K), any batch
+        e->gpart_bytes = std::max<int64_t>(e->gpart_bytes, (int64_t)gemm_part_bytes((int)n_out, b, (int)n_in));
+    e->off_gpart = bytes(e->gpart_bytes);
     e->off_xb = bytes((int64_t)max_batch * n_in * 4);
     e->off_y = bytes((int64_t)max_batch * n_out * 4);
     e->off_g = bytes((int64_t)max_batch * n_out * 4);

@@ -95,9 +95,10 @@ struct unet_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets,
     int in_c = 0, in_h = 0, in_w = 0, out_c = 0, out_h = 0, out_w = 0;
     TensorTable tab;
     // workspace
-    int64_t off_gacc = 0, off_dsum = 0, n_dsum = 0, off_ls = 0, off_f32 = 0, off_gscratch = 0, gscratch_bytes = 0;
+    int64_t off_gacc = 0, off_dsum = 0, n_dsum = 0, off_ls = 0, off_f32 = 0, off_gpart = 0, gpart_bytes = 0;
     int64_t off_thinpart = 0, thinpart_bytes = 0;   // weight-gradient partial tiles: per workgroup (kernels_unet_thin.h), per K slice (tile engine)
     int64_t off_linpart = 0, linpart_bytes = 0;   // K-slice partial tiles of the big Linear layers (kernels_unet_lin.h)
+    int64_t off_downpart = 0, downpart_bytes = 0; // partial maps of K slices 1.. of the split-K down convolutions (split_store)
     bool fc_f32[4] = {false, false, false, false};   // this backward stored fc[k]'s weight gradient as fp32 (F32Ranges)
     bool fc_f32_dirty[4] = {false, false, false, false};   // ... and nothing has cleared those accumulator slots since
     int64_t xb = 0, y = 0, coef = 0;
@@ -116,6 +117,7 @@ struct unet_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets,
     float* f(int64_t off) const { return reinterpret_cast<float*>(ws + off_f32) + off; }
     double* dsum(int64_t off) const { return reinterpret_cast<double*>(ws + off_dsum) + off; }
     double* gacc(int64_t off) const { return reinterpret_cast<double*>(ws + off_gacc) + off; }
+    float* downpart() const { return reinterpret_cast<float*>(ws + off_downpart); }
     float* P(int64_t off) const { return params + off; }
     float* Bf(int64_t off) const { return buffers + off; }
 };
@@ -187,8 +189,8 @@ WgradK choose_wgrad(const unet_engine* e, const Geom& g) {
 void conv_down(unet_engine* e, const Geom& g, const float* L, const float* w, const float* bias, float* S) {
     switch (choose_down(e, g)) {
         case DOWN_THIN: thin_down_launch(g, L, w, bias, S, e->stream); return;
-        case DOWN_PATCH: pdown_launch(g, L, w, bias, S, e->stream); return;
-        case DOWN_MFMA: mfma_down_launch(g, L, w, bias, S, e->stream); return;
+        case DOWN_PATCH: pdown_launch(g, L, w, bias, S, e->downpart(), e->downpart_bytes, e->stream); return;
+        case DOWN_MFMA: mfma_down_launch(g, L, w, bias, S, e->downpart(), e->downpart_bytes, e->stream); return;
         case DOWN_GENERIC: break;
     }
     const long long total = (long long)g.B * g.Cs * g.Hs * g.Ws;
@@ -248,7 +250,7 @@ dim3 red_grid(int B, int C, int HW) {
 
 void chan_sums(unet_engine* e, const float* x, long long bs, int B, int C, int HW, double* sums, int sstride, int want_sq) {
     const int chunks = (int)red_grid(B, C, HW).x;
-    hipLaunchKernelGGL(k_chan_sums, dim3(chunks, C), dim3(256), 0, e->stream, x, bs, B, HW, sums, sstride, want_sq);
+    hipLaunchKernelGGL(k_chan_sums<ACC_STAT>, dim3(chunks, C), dim3(256), 0, e->stream, x, bs, B, HW, sums, sstride, want_sq);
 }
 
 dim3 ew_grid(int B, int C, int HW) {
@@ -387,7 +389,7 @@ void lin_fwd(unet_engine* e, const Fc& L, int B, const float* in, float* out) {
         }
         case LIN_TILE: {   // out[b][o] = bias[o] + sum_i in[b][i] W[o][i]
             GemmDesc d{L.nout, B, L.nin, e->P(L.w), L.nin, 1, in, 1, L.nin, e->P(L.b), out, nullptr, 1, L.nout, 0};
-            gemm_launch(d, reinterpret_cast<double*>(e->ws + e->off_gscratch), e->stream);
+            gemm_launch(d, reinterpret_cast<float*>(e->ws + e->off_gpart), e->gpart_bytes, e->stream);
             return;
         }
         case LIN_GENERIC: break;
@@ -447,11 +449,11 @@ void lin_bwd(unet_engine* e, const Fc& L, int B, const float* in, const float* g
         case LIN_TILE: {
             // dW[o][i] += sum_b gout[b][o] in[b][i];  db[o] += sum_b gout[b][o];  gin[b][i] = sum_o gout[b][o] W[o][i]
             GemmDesc w{L.nout, L.nin, B, gout, 1, L.nout, in, L.nin, 1, nullptr, nullptr, e->gacc(L.w), L.nin, 1, 2};
-            gemm_launch(w, nullptr, e->stream);
+            gemm_launch(w, nullptr, 0, e->stream);
             hipLaunchKernelGGL(k_col_sums, dim3((L.nout + 255) / 256), dim3(256), 0, e->stream, B, L.nout, gout, e->gacc(L.b));
             if (gin) {
                 GemmDesc d{L.nin, B, L.nout, e->P(L.w), 1, L.nin, gout, 1, L.nout, nullptr, gin, nullptr, 1, L.nin, 0};
-                gemm_launch(d, reinterpret_cast<double*>(e->ws + e->off_gscratch), e->stream);
+                gemm_launch(d, reinterpret_cast<float*>(e->ws + e->off_gpart), e->gpart_bytes, e->stream);
             }
             return;
         }
@@ -931,10 +933,13 @@ int unet_engine_create(const cae_layer_spec* enc, int n_enc, const cae_layer_spe
     e->per_slot = 2;   // (mse, pearson loss)
     e->off_losses = bytes((int64_t)kStepLossSlots * e->per_slot * 8);
     e->off_ls = bytes(B * e->out_c * 8 * 8);
-    int64_t gs = 0;   // split-K scratch of the Linear GEMMs: rows x batch doubles, kept zero between uses
-    for (int k = 0; k < 4; k++) gs = std::max<int64_t>(gs, (int64_t)std::max(e->fc[k].nin, e->fc[k].nout) * B);
-    e->off_gscratch = bytes(gs * 8);
-    e->gscratch_bytes = gs * 8;
+    int64_t gp = 0;   // K slices' partial tiles of the Linear GEMMs on the tile engine (forward, input gradient), any batch
+    for (int k = 0; k < 4; k++)
+        for (int b = 1; b <= B; b++)
+            gp = std::max<int64_t>(gp, (int64_t)std::max(gemm_part_bytes(e->fc[k].nout, b, e->fc[k].nin),
+                                                          gemm_part_bytes(e->fc[k].nin, b, e->fc[k].nout)));
+    e->off_gpart = bytes(gp);
+    e->gpart_bytes = gp;
     int64_t lp = 0;   // partial tiles of the big layers' K slices (128 wide), batch <= 64
     for (int k = 0; k < 4; k++) {
         const Fc& L = e->fc[k];
@@ -955,6 +960,19 @@ int unet_engine_create(const cae_layer_spec* enc, int n_enc, const cae_layer_spe
     for (auto& L : e->dec) thin_need(L);
     e->off_thinpart = bytes(tp);
     e->thinpart_bytes = tp;
+    int64_t dp = 0;   // the split-K down convolutions' partial maps (forward of the encoder, input gradient of the decoder), any batch
+    auto down_need = [&](const ConvLayer& L) {
+        Geom g = L.g;
+        for (int b = 1; b <= B; b++) {
+            g.B = b;
+            if (patch_geom(g)) dp = std::max<int64_t>(dp, (int64_t)pdown_part_bytes(g));
+            if (mfma_down_eligible(g)) dp = std::max<int64_t>(dp, (int64_t)mfma_down_part_bytes(g));
+        }
+    };
+    for (auto& L : e->enc) down_need(L);
+    for (auto& L : e->dec) down_need(L);
+    e->off_downpart = bytes(dp);
+    e->downpart_bytes = dp;
     e->off_f32 = bytes(F32.top * 4);
     e->ws_bytes = bytes.top;
     *out = e;

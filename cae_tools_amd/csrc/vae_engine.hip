@@ -152,7 +152,7 @@ int loss(vae_engine* e, int which, const int32_t* perm, int64_t start, int B, in
         }
     }
     hipLaunchKernelGGL(vae::k_vae_loss_grad, dim3(blocks_for(n, 1024)), dim3(256), 0, e->stream, e->f(e->sx[0]), e->f(e->sy[0]),
-                       want_grad ? e->f(e->sG[0]) : (const float*)nullptr, n, (long long)Bg * E, shard ? 1.0 : (double)n,
+                       want_grad ? e->f(e->sG[0]) : (const float*)nullptr, n, (long long)Bg * E,
                        (float)e->l_mse, (float)e->grad_scale,
                        want_grad ? cae_internal::trunk_output_gradient(e->trunk) : (float*)nullptr, parts + 0,
                        want_grad && C == 1 ? cae_internal::trunk_output_bias_acc(e->trunk) : (double*)nullptr);
@@ -182,10 +182,10 @@ int step_common(vae_engine* e, int which, const int32_t* perm, int64_t start, in
     // KL is a mean over B*latent
     if (batch > 0 && (rc = loss(e, which, perm, start, batch, slot, train, parts))) return rc;
     if (sh.fn) {
-        // the shard's raw sums {squared error, KL term, 1 - MS-SSIM per (b, c)} over the ranks: the global batch's means
+        // the shard's sums {share of the mean squared error, KL term, 1 - MS-SSIM per (b, c)} over the ranks: the global batch's means
         if ((rc = call_allreduce(sh, "vae", parts, 3))) return rc;
         const double bg = sh.global_batch;
-        hipLaunchKernelGGL(vae::k_loss_slot, dim3(1), dim3(1), 0, e->stream, parts, bg * e->out_c * e->out_h * e->out_w, bg * e->latent,
+        hipLaunchKernelGGL(vae::k_loss_slot, dim3(1), dim3(1), 0, e->stream, parts, 1.0, bg * e->latent,
                            bg * e->out_c, e->l_mse, e->l_kl, e->l_ssim, e->losses(slot));
     } else {
         hipLaunchKernelGGL(vae::k_loss_slot, dim3(1), dim3(1), 0, e->stream, parts, 1.0, (double)batch * e->latent, 1.0, e->l_mse,
@@ -197,7 +197,7 @@ int step_common(vae_engine* e, int which, const int32_t* perm, int64_t start, in
         const int HW = e->out_h * e->out_w;
         const int chunks = (int)std::max<long long>(1, std::min<long long>(((long long)batch * HW + 2047) / 2048, 64));
         if (e->out_c > 1 && batch > 0)     // (a single-channel output's sum rides in k_vae_loss_grad)
-            hipLaunchKernelGGL(k_chan_sums, dim3(chunks, e->out_c), dim3(256), 0, e->stream, cae_internal::trunk_output_gradient(e->trunk),
+            hipLaunchKernelGGL(k_chan_sums<ACC_GRAD>, dim3(chunks, e->out_c), dim3(256), 0, e->stream, cae_internal::trunk_output_gradient(e->trunk),
                            (long long)e->out_c * HW, batch, HW, cae_internal::trunk_output_bias_acc(e->trunk), 1, 0);
         if ((batch > 0 || ts.fn) && (rc = cae_internal::trunk_backward(e->trunk, e->f(e->xb), batch, ts))) return rc;
         if (grads_out) {

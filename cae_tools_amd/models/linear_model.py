@@ -18,6 +18,8 @@ from .linear import Linear
 
 
 class LinearModel(EngineModel):
+    """The reference's LinearModel on the HIP engine (include/cae_linear.h).  Training is bitwise reproducible from run to
+    run: the same seeds, data and settings give the same weights and loss history."""
 
     MODEL_TYPE = "Linear"
     PARAM_KEYS = ("batch_size", "test_interval", "lr", "weight_decay", "normalise_input", "normalise_output")

@@ -137,6 +137,8 @@ def unet_layer_spec(input_channels, output_channels, size, channels, kernel_size
 
 
 class UNET(EngineModel):
+    """The reference's UNET on the HIP engine (include/cae_unet.h).  Training is bitwise reproducible from run to run: the same
+    seeds, data and settings give the same weights, running statistics and loss history."""
 
     MODEL_TYPE = "UNET"
     PARAM_KEYS = ("batch_size", "test_interval", "encoded_dim_size", "fc_size", "lr", "weight_decay", "normalise_input",

@@ -42,6 +42,8 @@ class VarEncoder(ParamBag):
 
 
 class VarAEModel(EngineModel):
+    """The 'var' model (VAE + MS-SSIM, include/cae_vae.h).  Training is bitwise reproducible from run to run: the same seeds
+    (noise_seed included), data and settings give the same weights, running statistics and loss history."""
 
     MODEL_TYPE = "VarAE"
     PARAM_KEYS = ("batch_size", "test_interval", "encoded_dim_size", "fc_size", "lr", "weight_decay", "normalise_input",

@@ -7,7 +7,8 @@
  *   linear_model.py:177-184    score                                                                 -> lin_score
  * The parameter arena is [weight (nout, nin) row-major, bias (nout)] = the state_dict entries linear.1.weight / linear.1.bias.
  * Conventions as in cae_hip.h.  The GEMMs run on the MFMA tile engine of kernels_unet_mfma.h (the 256 x 65536 weight of
- * the 16x16 -> 256x256 configuration makes every pass weight-bandwidth-bound).
+ * the 16x16 -> 256x256 configuration makes every pass weight-bandwidth-bound).  Steps are bitwise reproducible from run to
+ * run: the loss sum is on a fixed accumulation grid, a split-K forward folds its K slices in order.
  */
 #ifndef CAE_LINEAR_H
 #define CAE_LINEAR_H

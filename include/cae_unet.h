@@ -17,7 +17,9 @@
  *
  * Same conventions as cae_hip.h: plain pointers and sizes, *_dev = caller-owned device memory, every call returns
  * 0 or a negative cae_status with the message in cae_last_error(), work is enqueued on the stream given to
- * unet_set_stream.  All arithmetic fp32, reductions fp64.
+ * unet_set_stream.  All arithmetic fp32, reductions fp64.  Steps are bitwise reproducible from run to run: every fp64 sum over
+ * workgroups adds addends rounded to a fixed grid (exact, hence order-independent), and a split-K convolution combines its K
+ * slices in a fixed order.
  *
  * Dropout masks are a pure function of (seed, step, site, element index) (kernels_unet.h: pcg hash), not of
  * torch's generator: with dropout_rate 0 a step is the reference's arithmetic exactly.

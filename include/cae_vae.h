@@ -11,7 +11,8 @@
  *   Adam with L2 weight decay (conv_ae_model.py:310)
  * Layer geometry is cae_layer_spec exactly as for the ConvAE engine (no padding; output_padding on the decoder).
  * MS-SSIM needs output height and width that are multiples of 16 and at least 176.
- * Conventions as in cae_hip.h.
+ * Conventions as in cae_hip.h.  Steps are bitwise reproducible from run to run: the trunk's sums as on the ConvAE path, the
+ * KL, MS-SSIM and MSE sums of this path on fixed accumulation grids.
  */
 #ifndef CAE_VAE_H
 #define CAE_VAE_H
