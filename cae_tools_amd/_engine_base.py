@@ -228,6 +228,10 @@ class SteppedEngine:
         self.steps = int(step)
         check(self._c("set_step")(self.handle, self.steps))
 
+    def set_lr(self, lr):
+        """the learning rate alone (a scheduler step): the next optimiser launch takes it"""
+        check(self._c("set_lr")(self.handle, float(lr)))
+
     def reset_optimizer(self):
         self.sync()
         self.exp_avg.zero_()

@@ -50,6 +50,7 @@ SIGNATURES = {
     "cae_set_kernel_mode": (C.c_int, [_P, C.c_int]),
     "cae_set_capture_only": (C.c_int, [_P, C.c_int]),
     "cae_set_hyper": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "cae_set_lr": (C.c_int, [_P, C.c_double]),
     "cae_set_dataset": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64]),
     "cae_set_cursor": (C.c_int, [_P, C.c_int64, C.c_int]),
     "cae_set_adam_step": (C.c_int, [_P, C.c_int]),
@@ -77,6 +78,7 @@ SIGNATURES = {
     "cae_loss_slots": (C.c_int, [_P]),
     "cae_sync": (C.c_int, [_P]),
     "cae_graph_count": (C.c_int, [_P]),
+    "cae_graph_captures": (C.c_int64, [_P]),
     "cae_debug_read": (C.c_int64, [_P, C.c_char_p, C.c_int, _P, C.c_int64]),
     "cae_debug_plan": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p, C.c_int64]),
     "cae_profile_begin": (C.c_int, [_P]),
@@ -110,6 +112,7 @@ SIGNATURES = {
     "unet_set_kernel_mode": (C.c_int, [_P, C.c_int]),
     "unet_set_hyper": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                  C.c_uint32]),
+    "unet_set_lr": (C.c_int, [_P, C.c_double]),
     "unet_set_step": (C.c_int, [_P, C.c_int64]),
     "unet_set_dataset": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_int64]),
     "unet_train_step": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int]),
@@ -138,6 +141,7 @@ SIGNATURES = {
     "vae_set_stream": (C.c_int, [_P, _P]),
     "vae_set_hyper": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                 C.c_double, C.c_uint32]),
+    "vae_set_lr": (C.c_int, [_P, C.c_double]),
     "vae_set_kernel_mode": (C.c_int, [_P, C.c_int]),
     "vae_set_step": (C.c_int, [_P, C.c_int64]),
     "vae_set_dataset": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64]),
@@ -161,6 +165,7 @@ SIGNATURES = {
     "lin_bind": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64]),
     "lin_set_stream": (C.c_int, [_P, _P]),
     "lin_set_hyper": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "lin_set_lr": (C.c_int, [_P, C.c_double]),
     "lin_set_step": (C.c_int, [_P, C.c_int64]),
     "lin_set_dataset": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64]),
     "lin_train_step": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int]),

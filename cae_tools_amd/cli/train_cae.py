@@ -14,6 +14,7 @@ import time
 import numpy as np
 
 from ..data.arrays import DataArray, open_mfdataset
+from ..lr_schedule import check_scheduler_type
 from ..models.conv_ae_model import ConvAEModel
 from ..models.unet import UNET
 from ..models.linear_model import LinearModel
@@ -81,6 +82,11 @@ def broadcast_case_variables(ds, variables, case_dimension):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    try:    # a misspelt scheduler ends the run here, before ranks are spawned and the GPU library is loaded
+        check_scheduler_type(args.scheduler_type)
+    except ValueError as ex:
+        raise SystemExit(f"--scheduler-type: {ex}")
+    schedule = dict(scheduler_type=args.scheduler_type, lr_step_size=args.lr_step_size, lr_gamma=args.lr_gamma)
     from ._launch import maybe_spawn_ranks
     from .. import dp as _dp
     if max(int(args.gpus or 1), _dp.env_world()[2]) > 1:
@@ -112,23 +118,24 @@ def main(argv=None):
         mt = load_model(args.model_folder)
         mt.nr_epochs = args.nr_epochs
         mt.lr = args.learning_rate
+        mt._init_schedule(**schedule)
         mt.batch_size = args.batch_size
     else:
         if args.method == "conv":
             mt = ConvAEModel(fc_size=args.fc_size, encoded_dim_size=args.latent_size, nr_epochs=args.nr_epochs,
-                             batch_size=args.batch_size, lr=args.learning_rate)
+                             batch_size=args.batch_size, lr=args.learning_rate, **schedule)
         elif args.method == "unet":     # cli/train_cae.py:131-135
             mt = UNET(fc_size=args.fc_size, encoded_dim_size=args.latent_size, nr_epochs=args.nr_epochs,
                       batch_size=args.batch_size, lr=args.learning_rate, lambda_l1=args.lambda_l1,
                       lambda_pearson=args.lambda_pearson, database_path=args.database_path,
-                      weight_decay=args.weight_decay, dropout_rate=args.dropout_rate)
+                      weight_decay=args.weight_decay, dropout_rate=args.dropout_rate, **schedule)
         elif args.method == "var":      # the reference's default method; its model source is missing there
             mt = VarAEModel(fc_size=args.fc_size, encoded_dim_size=args.latent_size, nr_epochs=args.nr_epochs,
                             batch_size=args.batch_size, lr=args.learning_rate, lambda_mse=args.lambda_mse,
                             lambda_kl=args.lambda_kl, lambda_ssim=args.lambda_ssim, weight_decay=args.weight_decay,
-                            database_path=args.database_path)
+                            database_path=args.database_path, **schedule)
         elif args.method == "linear":   # cli/train_cae.py:137-138
-            mt = LinearModel(batch_size=args.batch_size, nr_epochs=args.nr_epochs, lr=args.learning_rate)
+            mt = LinearModel(batch_size=args.batch_size, nr_epochs=args.nr_epochs, lr=args.learning_rate, **schedule)
         else:
             raise SystemExit(f"--method {args.method}: cae_tools_amd implements 'conv' (ConvAEModel), 'unet' (UNET), 'var' "
                              "(VarAEModel) and 'linear' (LinearModel)")

@@ -110,6 +110,8 @@ struct cae_engine {
     const float* ds_t[2] = {nullptr, nullptr};
     int64_t ds_n[2] = {0, 0};
     bool graph_mode = true;
+    bool lr_stale = true;        // the device copy of hp.lr (StepState::lr) is behind the host's: push_lr() writes it
+    long long captures = 0;      // graphs captured since creation (cae_graph_captures)
     bool capture_only = false;   // cae_set_capture_only: step calls capture + cache their graph and launch nothing
     bool use_s2 = true;  // specialised stride-2 kernels (cae_set_kernel_mode)
     // trunk of the 'var' model (trunk_api.h): fc[1] is the pair of heads [mu | logvar] (2 * latent outputs), z = reparam(heads)
@@ -1855,8 +1857,19 @@ int launch_one(cae_engine* e, int op, const StepArgs& a) {
     return CAE_OK;
 }
 
+// The learning rate lives in the step state on the device, where k_adam reads it: written here, by a one-thread launch in
+// stream order, whenever the host's value has moved on (or the workspace is new).  Never inside a capture.
+int push_lr(cae_engine* e) {
+    if (!e->lr_stale || !e->ws) return CAE_OK;
+    hipLaunchKernelGGL(k_set_lr, dim3(1), dim3(1), 0, e->stream, e->state(), e->hp.lr);
+    HIP_TRY(hipGetLastError());
+    e->lr_stale = false;
+    return CAE_OK;
+}
+
 // run an op either directly or through a cached hipGraph
 int run_op(cae_engine* e, int op, const StepArgs& a, bool cacheable) {
+    if (int rc = push_lr(e)) return rc;
     // the legacy NULL stream cannot be captured: plain launches there
     if (!e->graph_mode || !cacheable || e->stream == nullptr || e->profiling)
         return e->capture_only ? CAE_OK : launch_op(e, op, a);
@@ -1880,6 +1893,7 @@ int run_op(cae_engine* e, int op, const StepArgs& a, bool cacheable) {
         (void)hipGraphDestroy(graph);
         if (ie != hipSuccess) return fail(CAE_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
         it = e->graphs.emplace(key, exec).first;
+        e->captures += 1;
     }
     if (e->capture_only) return CAE_OK;
     HIP_TRY(hipGraphLaunch(it->second, e->stream));
@@ -2147,6 +2161,7 @@ int cae_bind(cae_engine* e, float* params, float* grads, float* exp_avg, float* 
         return fail(CAE_ERR_ARG, "workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)e->ws_need);
     if (((uintptr_t)workspace & 255) != 0) return fail(CAE_ERR_ARG, "workspace must be 256-byte aligned");
     e->drop_graphs();
+    e->lr_stale = true;   // a new workspace: its step state has no rate yet
     e->params = params;
     e->grads = grads;
     e->m = exp_avg;
@@ -2158,7 +2173,10 @@ int cae_bind(cae_engine* e, float* params, float* grads, float* exp_avg, float* 
 
 int cae_set_stream(cae_engine* e, void* hip_stream) {
     if (!e) return fail(CAE_ERR_ARG, "null engine");
-    if (e->stream != (hipStream_t)hip_stream) e->drop_graphs();
+    if (e->stream != (hipStream_t)hip_stream) {
+        e->drop_graphs();
+        e->lr_stale = true;   // written again in the new stream's order
+    }
     e->stream = (hipStream_t)hip_stream;
     return CAE_OK;
 }
@@ -2190,9 +2208,18 @@ int cae_set_kernel_mode(cae_engine* e, int specialised) {
 int cae_set_hyper(cae_engine* e, double lr, double beta1, double beta2, double eps, double weight_decay) {
     if (!e) return fail(CAE_ERR_ARG, "null engine");
     Hyper h{lr, beta1, beta2, eps, weight_decay};
-    if (memcmp(&h, &e->hp, sizeof h) != 0) e->drop_graphs();  // hyper-parameters are baked into captured launches
+    // betas, eps and weight decay are baked into captured launches; the rate is device state (StepState::lr)
+    if (h.beta1 != e->hp.beta1 || h.beta2 != e->hp.beta2 || h.eps != e->hp.eps || h.wd != e->hp.wd) e->drop_graphs();
     e->hp = h;
-    return CAE_OK;
+    e->lr_stale = true;
+    return push_lr(e);
+}
+
+int cae_set_lr(cae_engine* e, double lr) {
+    if (!e) return fail(CAE_ERR_ARG, "null engine");
+    e->hp.lr = lr;
+    e->lr_stale = true;
+    return push_lr(e);
 }
 
 int cae_set_dataset(cae_engine* e, int which, const float* x, const float* t, int64_t n) {
@@ -2532,6 +2559,7 @@ int cae_sync(cae_engine* e) {
 }
 
 int cae_graph_count(const cae_engine* e) { return e ? (int)e->graphs.size() : 0; }
+int64_t cae_graph_captures(const cae_engine* e) { return e ? (int64_t)e->captures : 0; }
 
 // ---- roctx ranges (SURVEY.md §5 tracing): visible in `rocprofv3 --marker-trace`, free when no profiler is attached ----------
 namespace {
@@ -3027,6 +3055,7 @@ int trunk_backward(cae_engine* e, const float* x, int batch, const ShardSync& sy
 
 int trunk_adam(cae_engine* e) {
     if (!e || !e->ws) return fail(CAE_ERR_STATE, "trunk_adam: not a bound engine");
+    if (int rc = push_lr(e)) return rc;
     hipLaunchKernelGGL(k_adam, dim3(grid1(e->tab.n_param)), dim3(256), 0, e->stream, (long long)e->tab.n_param, e->params,
                        (const float*)nullptr, e->m, e->v, e->hp, (const StepState*)e->state(), e->shard_segs(),
                        step_tail_of(e, 0, 0), 0, std::log(e->hp.beta1), std::log(e->hp.beta2), AdamConv0{});
@@ -3046,6 +3075,7 @@ int trunk_gradients(cae_engine* e, float* out, double scale) {
 
 int trunk_adam_from(cae_engine* e, const float* grads) {
     if (!e || !e->ws || !grads) return fail(CAE_ERR_STATE, "trunk_adam_from: bad argument");
+    if (int rc = push_lr(e)) return rc;
     StepTail none;
     memset(&none, 0, sizeof none);
     hipLaunchKernelGGL(k_adam, dim3(grid1(e->tab.n_param)), dim3(256), 0, e->stream, (long long)e->tab.n_param, e->params, grads, e->m, e->v,

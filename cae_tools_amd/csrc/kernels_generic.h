@@ -50,11 +50,25 @@ __device__ __forceinline__ double sharded_grad(const ShardSegs& ss, long long i)
     return g;
 }
 
-struct StepState {
+struct alignas(16) StepState {
     long long batch_start;  // first position in the permutation of the current batch
     int loss_slot;          // where this step's loss is accumulated
+    int pad0;
+    // one aligned 16-byte block, which the optimiser kernel requests as a whole (optimiser_state)
+    double lr;              // learning rate of the next optimiser step (cae_set_lr / cae_set_hyper): read by k_adam, so a
+                            // captured graph follows a schedule without being captured again
     int adam_step;          // completed optimiser steps
+    int pad1;
 };
+static_assert(offsetof(StepState, lr) % 16 == 0 && offsetof(StepState, adam_step) == offsetof(StepState, lr) + 8, "StepState layout");
+
+// The step number and the learning rate, requested together.  The compiler keeps the step number a scalar load and makes
+// the rate a vector load that is waited for where it is used (the division), not ahead of the requests that follow this call.
+__device__ __forceinline__ void optimiser_state(const StepState* __restrict__ st, int& adam_step, double& lr) {
+    const int4 q = *reinterpret_cast<const int4*>(reinterpret_cast<const char*>(st) + offsetof(StepState, lr));
+    lr = __hiloint2double(q.y, q.x);
+    adam_step = q.z;
+}
 
 // How a tensor that is READ relates to BatchNorm.
 enum BnMode : int {
@@ -844,7 +858,8 @@ __device__ __forceinline__ void step_tail(const StepTail& tl, long long gid, lon
 // torch.optim.Adam single-tensor update (L2 weight decay added to the gradient), element-wise
 // over the flat arena.  Gradient source: fp64 accumulators (fused path; consumed and cleared) or
 // the fp32 arena (data-parallel path, after the all-reduce).  st->adam_step is the number of the
-// step being taken (bumped by the first kernel of the step / by cae_adam_step's own bump flag).
+// step being taken (bumped by the first kernel of the step / by cae_adam_step's own bump flag),
+// st->lr the learning rate (h.lr is the host's copy of it: no kernel reads it).
 // The first encoder layer's weight gradient, folded into the optimiser launch (k_adam): it is the last kernel of backward, a
 // reduction of B*Hs*Ws products per weight that nothing but the optimiser waits for - as its own launch 5.6 us, 3 % of the
 // step.  One extra workgroup per weight: it reduces the whole batch itself (no cross-workgroup sum, so no ordering between
@@ -878,7 +893,11 @@ __device__ __forceinline__ void adam_conv0_body(const AdamConv0& c0, float* __re
     const int cs = widx / g.Cl;
     const long long pi = c0.w_off + (blockIdx.x - c0.n_regular);
     int t = 0;
-    if (tid < 2) t = st->adam_step + t_add;
+    double lr = 0.0;
+    if (tid < 2) {
+        optimiser_state(st, t, lr);
+        t += t_add;
+    }
     float w = 0.f, mi = 0.f, vi = 0.f;
     if (tid == 0) {
         w = p[pi];
@@ -903,7 +922,7 @@ __device__ __forceinline__ void adam_conv0_body(const AdamConv0& c0, float* __re
     bn_consts(c0.bns, cs4, false);
     if (tid < 2) {
         const double bc = -expm1((double)t * (tid ? ln_b2 : ln_b1));
-        corr[tid] = tid ? (float)sqrt(bc) : (float)(h.lr / bc);
+        corr[tid] = tid ? (float)sqrt(bc) : (float)(lr / bc);
     }
     __syncthreads();
     const float4 ks = cs4[cs];
@@ -953,7 +972,11 @@ __global__ void __launch_bounds__(256) k_adam(long long n, float* __restrict__ p
     // stores ahead of them (the memory counter retires in order).
     for (long long j = i; j < tl.zero_extra_n; j += (long long)(c0.on ? c0.n_regular : (int)gridDim.x) * 256) tl.zero_extra[j] = 0.0;
     int t = 0;
-    if (threadIdx.x < 2) t = st->adam_step + t_add;
+    double lr = 0.0;
+    if (threadIdx.x < 2) {   // the rate is requested with the step number and waited for at the division below
+        optimiser_state(st, t, lr);
+        t += t_add;
+    }
     const bool moves_cursor = i == 0 && tl.st != nullptr;
     long long cursor = 0;
     int slot = 0;
@@ -1002,7 +1025,7 @@ __global__ void __launch_bounds__(256) k_adam(long long n, float* __restrict__ p
     }
     if (threadIdx.x < 2) {
         const double bc = -expm1((double)t * (threadIdx.x ? ln_b2 : ln_b1));
-        corr[threadIdx.x] = threadIdx.x ? (float)sqrt(bc) : (float)(h.lr / bc);
+        corr[threadIdx.x] = threadIdx.x ? (float)sqrt(bc) : (float)(lr / bc);
     }
     __syncthreads();
     if (mine) {
@@ -1099,6 +1122,9 @@ __global__ void k_set_state(StepState* st, long long batch_start, int loss_slot,
     }
     if (set_adam) st->adam_step = adam_step;
 }
+
+// the learning rate of the steps enqueued after this launch (stream-ordered; graphs read it, none bakes it in)
+__global__ void k_set_lr(StepState* st, double lr) { st->lr = lr; }
 
 __global__ void k_advance(StepState* st, int batch, int slot_inc, int adam_inc) {
     st->batch_start += batch;

@@ -128,6 +128,11 @@ int lin_set_hyper(lin_engine* e, double lr, double beta1, double beta2, double e
     e->hyper = vae::AdamHyper{lr, beta1, beta2, eps, weight_decay};
     return CAE_OK;
 }
+int lin_set_lr(lin_engine* e, double lr) {
+    if (!e) return fail(CAE_ERR_ARG, "lin_set_lr: null engine");
+    e->hyper.lr = lr;   // the next k_adam_l2 launch takes it by value
+    return CAE_OK;
+}
 int lin_set_step(lin_engine* e, int64_t completed_steps) { return set_step(e, "lin", completed_steps); }
 int lin_set_dataset(lin_engine* e, int which, const float* x, const float* target, int64_t n) {
     return set_dataset(e, "lin", which, DataSet{x, target, nullptr, 0, n});

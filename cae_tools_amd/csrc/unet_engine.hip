@@ -1014,6 +1014,12 @@ int unet_set_hyper(unet_engine* e, double lr, double beta1, double beta2, double
     return CAE_OK;
 }
 
+int unet_set_lr(unet_engine* e, double lr) {
+    if (!e) return fail(CAE_ERR_ARG, "unet_set_lr: null engine");
+    e->hyper.lr = lr;   // the next step's launches take it by value (adamw_consts)
+    return CAE_OK;
+}
+
 int unet_set_step(unet_engine* e, int64_t step) { return set_step(e, "unet", step); }
 
 int unet_set_dataset(unet_engine* e, int which, const float* x, const float* target, const float* mask, int mask_channels,

@@ -289,6 +289,10 @@ int vae_set_hyper(vae_engine* e, double lr, double beta1, double beta2, double e
     e->l_mse = lambda_mse, e->l_kl = lambda_kl, e->l_ssim = lambda_ssim, e->seed = noise_seed;
     return cae_set_hyper(e->trunk, lr, beta1, beta2, eps, weight_decay);
 }
+int vae_set_lr(vae_engine* e, double lr) {
+    if (!e) return fail(CAE_ERR_ARG, "vae_set_lr: null engine");
+    return cae_set_lr(e->trunk, lr);
+}
 int vae_set_kernel_mode(vae_engine* e, int mode) {
     if (!e) return fail(CAE_ERR_ARG, "vae_set_kernel_mode: null engine");
     e->row_kernels = (mode & 1) != 0;

@@ -95,6 +95,19 @@ class DataParallel:
                 with self._stream_ctx():
                     self.dist.broadcast(t, src=src, group=self.group)
 
+    def set_lr(self, lr):
+        """the learning rate of the next optimiser steps; every rank must pass the same value (see agree())"""
+        self.engine.set_lr(lr)
+
+    def agree(self, value):
+        """rank 0's `value` (a python float) on every rank: what a schedule that listens to a loss is fed, so that the ranks'
+        rates cannot part over the last bits of a reduction"""
+        device = getattr(self.engine, "device", None) or self.engine.grads.device
+        t = torch.tensor([float(value)], dtype=torch.float64, device=device)
+        src = self.dist.get_global_rank(self.group, 0) if self.group is not None else 0
+        self.dist.broadcast(t, src=src, group=self.group)
+        return float(t.item())
+
     def global_batch(self, local_size, equal=True):
         if equal:
             return local_size * self.world
@@ -240,6 +253,9 @@ class GradientHalfSteps:
 
     def adam_step(self):
         self.engine.apply_gradients(self.grads)
+
+    def set_lr(self, lr):
+        self.engine.set_lr(lr)
 
 
 # ---- process-group plumbing for the model classes and CLIs ------------------------------------------

@@ -108,6 +108,11 @@ class HipEngine(EnginePlan):
         check(self.lib.cae_set_hyper(self.handle, float(lr), float(betas[0]), float(betas[1]), float(eps),
                                      float(weight_decay)))
 
+    def set_lr(self, lr):
+        """the learning rate alone (cae_set_lr): a one-thread launch in stream order that the next steps' optimiser kernel
+        reads; captured graphs are kept"""
+        check(self.lib.cae_set_lr(self.handle, float(lr)))
+
     # ---- data ------------------------------------------------------------------------------
     def _same_device(self, a, what):
         """the kernels dereference plain pointers: a tensor on another GPU is a memory fault, not a slow path"""
@@ -236,6 +241,10 @@ class HipEngine(EnginePlan):
 
     def graph_count(self):
         return int(self.lib.cae_graph_count(self.handle))
+
+    def graph_captures(self):
+        """graphs captured since the engine was created: a graph dropped and captured again raises it, graph_count() not"""
+        return int(self.lib.cae_graph_captures(self.handle))
 
     def train_step(self, which, perm_dev, start, size):
         """a single training step on perm[start:start+size]; returns its loss (blocking)"""

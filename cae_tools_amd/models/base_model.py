@@ -11,6 +11,7 @@ import uuid
 
 import torch
 
+from .. import lr_schedule as _lrs
 from ..data.arrays import DataArray
 from .ds_dataset import DSDataset
 from .model_metric import DeviceModelMetric, ModelMetric  # noqa: F401
@@ -163,6 +164,40 @@ class BaseModel:
         pass  # implement in sub-class
 
 
+class _ScheduledRate:
+    """The learning-rate schedule of one train() call, driven from its epoch loop: steps the schedule (lr_schedule.py),
+    hands the new rate to the engine (set_lr: no graph is captured again for it) and keeps history["lr"].  With no
+    scheduler every method is a no-op and `current` stays the model's lr."""
+
+    def __init__(self, schedule, engine, history, par=None):
+        (self.schedule, self.engine, self.history, self.par) = (schedule, engine, history, par)
+
+    @property
+    def current(self):
+        return self.schedule.lr
+
+    def _push(self):
+        (self.par if self.par is not None else self.engine).set_lr(self.schedule.lr)
+
+    def after_train_pass(self):
+        """once per epoch, after its training pass (where the reference steps its scheduler: unet.py:485-487)"""
+        if self.schedule.active and not self.schedule.wants_metric:
+            self.schedule.step()
+            self._push()
+
+    def after_test_pass(self, test_loss):
+        """at an epoch whose test pass ran: the plateau schedule listens to the test loss.  Under data-parallel training
+        every rank takes rank 0's value, so that all ranks hold the same rate whatever the last bits of their losses."""
+        if self.schedule.wants_metric:
+            self.schedule.step_metric(self.par.agree(test_loss) if self.par is not None else test_loss)
+            self._push()
+
+    def record(self, rate):
+        """`rate`: the rate the recorded epoch trained with"""
+        if self.schedule.active:
+            self.history.setdefault("lr", []).append(rate)
+
+
 class EngineModel(BaseModel):
     """What the libcae_hip-backed models share: host weight containers mirrored by one engine, the model folder, and the
     parts of train() around the epoch loop.  This base implements the spec-driven encoder / decoder models; a sub-class
@@ -172,6 +207,25 @@ class EngineModel(BaseModel):
     MODEL_TYPE = None
     PARAM_KEYS = ()
     OPTIONAL_PARAM_KEYS = ("conv_kernel_size", "conv_stride", "conv_input_layer_count", "conv_output_layer_count")
+    SCHEDULE_KEYS = ("scheduler_type", "lr_step_size", "lr_gamma")     # in parameters.json only when a scheduler is set
+
+    # ---- learning-rate schedule ------------------------------------------------------------
+    def _init_schedule(self, scheduler_type=None, lr_step_size=500, lr_gamma=0.5):
+        """the three scheduler keywords of a model constructor (an unknown name is an error here, before any GPU work)"""
+        self.scheduler_type = _lrs.check_scheduler_type(scheduler_type)
+        self.lr_step_size = lr_step_size
+        self.lr_gamma = lr_gamma
+
+    def _schedule_parameters(self):
+        """what get_parameters() adds: nothing without a scheduler (parameters.json is then what it always was)"""
+        if _lrs.is_constant(self.scheduler_type):
+            return {}
+        return {key: getattr(self, key) for key in self.SCHEDULE_KEYS}
+
+    def _scheduled_rate(self, eng, par=None):
+        """a fresh schedule starting at self.lr, as the optimiser is fresh on every train()"""
+        schedule = _lrs.make_schedule(self.scheduler_type, self.lr, self.lr_step_size, self.lr_gamma)
+        return _ScheduledRate(schedule, eng, self.history, par)
 
     def _modules(self):
         """fresh host weight containers for the current spec / shapes"""
@@ -257,6 +311,9 @@ class EngineModel(BaseModel):
             setattr(self, key, p[key])
         for key in self.OPTIONAL_PARAM_KEYS:
             setattr(self, key, p.get(key, None))
+        for key in self.SCHEDULE_KEYS:
+            if key in p:
+                setattr(self, key, p[key])
         with open(os.path.join(from_folder, "history.json")) as f:
             self.history = json.loads(f.read())
         self._load_modules(from_folder)

@@ -33,8 +33,10 @@ class ConvAEModel(EngineModel):
     def __init__(self, normalise_input=True, normalise_output=True, batch_size=10,
                  nr_epochs=500, test_interval=10, encoded_dim_size=32, fc_size=128,
                  lr=0.001, weight_decay=1e-5, use_gpu=True, conv_kernel_size=3, conv_stride=2,
-                 conv_input_layer_count=None, conv_output_layer_count=None, database_path=None):
+                 conv_input_layer_count=None, conv_output_layer_count=None, database_path=None, scheduler_type=None,
+                 lr_step_size=500, lr_gamma=0.5):
         super().__init__()
+        self._init_schedule(scheduler_type, lr_step_size, lr_gamma)
         self.normalise_input = normalise_input
         self.normalise_output = normalise_output
         self.normalisation_parameters = None
@@ -82,6 +84,7 @@ class ConvAEModel(EngineModel):
             "conv_input_layer_count": self.conv_input_layer_count,
             "conv_output_layer_count": self.conv_output_layer_count,
             "model_id": self.get_model_id(),
+            **self._schedule_parameters(),
         }
 
     def _modules(self):
@@ -159,12 +162,17 @@ class ConvAEModel(EngineModel):
                 return par.run_batches(which, idx, n, self.batch_size, train=train)
 
         train_loss = test_loss = 0.0
+        rate = self._scheduled_rate(eng, par)
         eng.sync()
         loop_start = time.perf_counter()
         for epoch in range(self.nr_epochs):
+            epoch_lr = rate.current
             train_loss = float(np.mean(one_pass(_eng.TRAIN, train_idx, len(train_ds), True)))
+            rate.after_train_pass()     # one tiny launch: the step graphs read the rate from the device
             if epoch % self.test_interval == 0:
                 test_loss = float(np.mean(one_pass(_eng.TEST, test_idx, len(test_ds), False)))
+                rate.after_test_pass(test_loss)
+                rate.record(epoch_lr)
                 self.history["train_loss"].append(train_loss)
                 self.history["test_loss"].append(test_loss)
                 if lead:

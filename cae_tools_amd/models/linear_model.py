@@ -26,8 +26,9 @@ class LinearModel(EngineModel):
     OPTIONAL_PARAM_KEYS = ()
 
     def __init__(self, normalise_input=True, normalise_output=True, batch_size=10, nr_epochs=500, test_interval=10, lr=0.001,
-                 weight_decay=1e-5, use_gpu=True, database_path=None):
+                 weight_decay=1e-5, use_gpu=True, database_path=None, scheduler_type=None, lr_step_size=500, lr_gamma=0.5):
         super().__init__()
+        self._init_schedule(scheduler_type, lr_step_size, lr_gamma)
         self.normalise_input, self.normalise_output = normalise_input, normalise_output
         self.normalisation_parameters = None
         self.input_shape = self.output_shape = None
@@ -43,7 +44,7 @@ class LinearModel(EngineModel):
         return {"model_id": self.get_model_id(), "type": "LinearModel", "input_shape": list(self.input_shape),
                 "output_shape": list(self.output_shape), "batch_size": self.batch_size, "test_interval": self.test_interval,
                 "lr": self.lr, "weight_decay": self.weight_decay, "normalise_input": self.normalise_input,
-                "normalise_output": self.normalise_output}
+                "normalise_output": self.normalise_output, **self._schedule_parameters()}
 
     def summary(self):
         if not self.input_shape:
@@ -91,10 +92,15 @@ class LinearModel(EngineModel):
         eng.set_dataset(_le.TEST, test_ds.device_inputs(), test_ds.device_outputs())
         (train_idx, test_idx) = (eng.upload_perm(train_perm), eng.upload_perm(test_perm))
         train_loss = test_loss = 0.0
+        rate = self._scheduled_rate(eng)
         for epoch in range(self.nr_epochs):
+            epoch_lr = rate.current
             train_loss = float(np.mean(eng.run_batches(_le.TRAIN, train_idx, len(train_ds), self.batch_size, True)))
+            rate.after_train_pass()
             if epoch % self.test_interval == 0:
                 test_loss = float(np.mean(eng.run_batches(_le.TEST, test_idx, len(test_ds), self.batch_size, False)))
+                rate.after_test_pass(test_loss)
+                rate.record(epoch_lr)
                 self.history["train_loss"].append(train_loss)
                 self.history["test_loss"].append(test_loss)
                 print("%5d %.6f %.6f" % (epoch, train_loss, test_loss))

@@ -147,8 +147,10 @@ class UNET(EngineModel):
     def __init__(self, normalise_input=True, normalise_output=True, batch_size=10, nr_epochs=500, test_interval=10,
                  encoded_dim_size=32, fc_size=128, lr=0.001, weight_decay=1e-5, dropout_rate=0.1, use_gpu=True,
                  conv_kernel_size=3, conv_stride=2, conv_input_layer_count=None, conv_output_layer_count=None,
-                 database_path=None, lambda_l1=0.001, lambda_pearson=1, dropout_seed=0):
+                 database_path=None, lambda_l1=0.001, lambda_pearson=1, dropout_seed=0, scheduler_type=None, lr_step_size=500,
+                 lr_gamma=0.5):
         super().__init__()
+        self._init_schedule(scheduler_type, lr_step_size, lr_gamma)
         self.normalise_input = normalise_input
         self.normalise_output = normalise_output
         self.normalisation_parameters = None
@@ -202,6 +204,7 @@ class UNET(EngineModel):
             "conv_input_layer_count": self.conv_input_layer_count,
             "conv_output_layer_count": self.conv_output_layer_count,
             "model_id": self.get_model_id(),
+            **self._schedule_parameters(),
         }
 
     def summary(self):
@@ -266,12 +269,15 @@ class UNET(EngineModel):
             return par.run_batches(which, idx, n, self.batch_size, train=train)
 
         train_loss = test_loss = 0.0
+        rate = self._scheduled_rate(eng, par)
         eng.sync()
         loop_start = time.perf_counter()
         try:
             for epoch in range(self.nr_epochs):
                 e0 = time.time()
+                epoch_lr = rate.current
                 losses = one_pass(_ue.TRAIN, train_idx, len(train_ds), True)
+                rate.after_train_pass()     # the scheduler step of unet.py:485-487
                 if lead:
                     print(f"time used for training one epoch: {time.time() - e0:.2f}")
                 train_loss = float(np.mean([l[0] for l in losses]))
@@ -280,12 +286,14 @@ class UNET(EngineModel):
                     tl = one_pass(_ue.TEST, test_idx, len(test_ds), False)
                     test_loss = float(np.mean([l[0] for l in tl]))
                     test_pearson_loss = float(np.mean([l[1] for l in tl]))
+                    rate.after_test_pass(test_loss)
+                    rate.record(epoch_lr)
                     self.history["train_loss"].append(train_loss)
                     self.history["test_loss"].append(test_loss)
                     if lead:
                         print(f"epoch: {epoch}, train_mse: {train_loss:.6f}, train_pearson_loss: {train_pearson_loss:.4f}, "
                               f"test_mse: {test_loss:.6f}, test_pearson_loss: {test_pearson_loss:.4f}")
-                        print(f"learn rate: {self.lr:.6f}")
+                        print(f"learn rate: {rate.current:.6f}")
         except KeyboardInterrupt:
             print("Training interrupted. Performing cleanup...")
         eng.sync()

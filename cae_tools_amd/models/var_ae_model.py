@@ -52,8 +52,9 @@ class VarAEModel(EngineModel):
     def __init__(self, normalise_input=True, normalise_output=True, batch_size=10, nr_epochs=500, test_interval=10,
                  encoded_dim_size=32, fc_size=128, lr=0.001, weight_decay=1e-5, use_gpu=True, conv_kernel_size=3, conv_stride=2,
                  conv_input_layer_count=None, conv_output_layer_count=None, database_path=None, lambda_mse=1, lambda_kl=1,
-                 lambda_ssim=1, noise_seed=0):
+                 lambda_ssim=1, noise_seed=0, scheduler_type=None, lr_step_size=500, lr_gamma=0.5):
         super().__init__()
+        self._init_schedule(scheduler_type, lr_step_size, lr_gamma)
         self.normalise_input, self.normalise_output = normalise_input, normalise_output
         self.normalisation_parameters = None
         self.input_shape = self.output_shape = None
@@ -80,7 +81,8 @@ class VarAEModel(EngineModel):
                 "lambda_kl": self.lambda_kl, "lambda_ssim": self.lambda_ssim, "normalise_input": self.normalise_input,
                 "normalise_output": self.normalise_output, "conv_kernel_size": self.conv_kernel_size,
                 "conv_stride": self.conv_stride, "conv_input_layer_count": self.conv_input_layer_count,
-                "conv_output_layer_count": self.conv_output_layer_count, "model_id": self.get_model_id()}
+                "conv_output_layer_count": self.conv_output_layer_count, "model_id": self.get_model_id(),
+                **self._schedule_parameters()}
 
     def summary(self):
         if not self.spec:
@@ -135,12 +137,17 @@ class VarAEModel(EngineModel):
             return par.run_batches(which, idx, n, self.batch_size, train=train)
 
         train_loss = test_loss = 0.0
+        rate = self._scheduled_rate(eng, par)
         eng.sync()
         loop_start = time.perf_counter()
         for epoch in range(self.nr_epochs):
+            epoch_lr = rate.current
             train_loss = float(np.mean([l[3] for l in one_pass(_ve.TRAIN, train_idx, len(train_ds), True)]))
+            rate.after_train_pass()
             if epoch % self.test_interval == 0:
                 test_loss = float(np.mean([l[3] for l in one_pass(_ve.TEST, test_idx, len(test_ds), False)]))
+                rate.after_test_pass(test_loss)
+                rate.record(epoch_lr)
                 self.history["train_loss"].append(train_loss)
                 self.history["test_loss"].append(test_loss)
                 if lead:

@@ -114,6 +114,10 @@ int cae_set_kernel_mode(cae_engine* e, int specialised);
 /* torch.optim.Adam(lr, betas, eps, weight_decay) with L2 decay added to the gradient
  * (conv_ae_model.py:310). */
 int cae_set_hyper(cae_engine* e, double lr, double beta1, double beta2, double eps, double weight_decay);
+/* The learning rate alone (a torch.optim.lr_scheduler step, unet.py:485-496).  The rate is step state on the device, read
+ * by the optimiser kernel: the call is one tiny launch in stream order, takes effect for the steps enqueued after it, and
+ * keeps every captured graph (cae_set_hyper drops them only when betas, eps or weight_decay change). */
+int cae_set_lr(cae_engine* e, double lr);
 
 /* ---- data ------------------------------------------------------------------------------ */
 
@@ -221,6 +225,9 @@ int cae_loss_slots(const cae_engine* e);
 int cae_sync(cae_engine* e);
 /* Test hook: captured hipGraphs currently cached by the engine (one per distinct launch sequence). */
 int cae_graph_count(const cae_engine* e);
+/* Test hook: graphs captured since the engine was created (cae_graph_count is the cache size: a graph dropped and
+ * captured again leaves it unchanged, and raises this). */
+int64_t cae_graph_captures(const cae_engine* e);
 
 /* Test hook (blocking): copy an internal tensor of the LAST train-mode step to host.
  * what: "act" raw conv output of layer `index` (encoder layers first, then decoder layers except

@@ -31,6 +31,7 @@ int lin_bind(lin_engine* e, float* params_dev, float* exp_avg_dev, float* exp_av
              int64_t workspace_bytes);
 int lin_set_stream(lin_engine* e, void* hip_stream);
 int lin_set_hyper(lin_engine* e, double lr, double beta1, double beta2, double eps, double weight_decay);
+int lin_set_lr(lin_engine* e, double lr);   /* the learning rate alone (a scheduler step): the next optimiser launch takes it */
 int lin_set_step(lin_engine* e, int64_t completed_steps);
 int lin_set_dataset(lin_engine* e, int which, const float* x_dev, const float* target_dev, int64_t n);
 /* one iteration of __train_epoch on samples perm[start .. start+batch): forward, MSE, backward, Adam; loss -> slot */

@@ -59,6 +59,8 @@ int unet_set_kernel_mode(unet_engine* e, int specialised);
 /* unet.py:201-204 hyper-parameters; dropout_seed keys the dropout hash */
 int unet_set_hyper(unet_engine* e, double lr, double beta1, double beta2, double eps, double weight_decay,
                    double dropout_rate, double lambda_pearson, uint32_t dropout_seed);
+/* the learning rate alone (a scheduler step): the launches of the next unet_train_step / unet_apply_gradients take it */
+int unet_set_lr(unet_engine* e, double lr);
 /* completed optimiser steps (AdamW bias correction uses step+1; the dropout hash uses step) */
 int unet_set_step(unet_engine* e, int64_t step);
 

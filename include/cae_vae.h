@@ -42,6 +42,8 @@ int vae_bind(vae_engine* e, float* params_dev, float* exp_avg_dev, float* exp_av
 int vae_set_stream(vae_engine* e, void* hip_stream);
 int vae_set_hyper(vae_engine* e, double lr, double beta1, double beta2, double eps, double weight_decay, double lambda_mse,
                   double lambda_kl, double lambda_ssim, uint32_t noise_seed);
+/* the learning rate alone (a scheduler step): forwarded to the trunk's cae_set_lr, in stream order */
+int vae_set_lr(vae_engine* e, double lr);
 /* 1 (default): the MS-SSIM passes run the row-streaming kernels (a wave walks a strip of 64 columns, DPP neighbours, register
  * ring); 0: the LDS tile kernels they replaced.  Same arithmetic in the same order: results equal to fp32 rounding (kept
  * selectable so that the parity tests can say so). */
