@@ -35,15 +35,15 @@ struct Gauss {
     float g[kWin];
 };
 
+// The window is DATA of the definition (oracle/vae_oracle.py gaussian_window: exp(-c^2 / 4.5) / sum, evaluated in fp32 by
+// torch), not something to recompute: the same formula through libm's expf and a sequential sum lands one ulp away in seven of
+// the eleven entries and sums to 1 + 4.5e-8 instead of 1 - 3.1e-8, and because the variances are differences E[x^2] - E[x]^2 of
+// numbers near 0.25 that 7.5e-8 moved the loss by 1.2e-5 and the gradient by up to 3x the definition's own fp32 error
+// (tests/test_vae_msssim_gpu.py; tests/test_vae_msssim_criterion_cpu.py holds these bits to the oracle's).
 inline Gauss make_gauss() {
+    static const float half[kWin / 2 + 1] = {0x1.0d957p-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.10656p-2f};
     Gauss w;
-    float sum = 0.f;
-    for (int i = 0; i < kWin; i++) {
-        const float c = (float)(i - kWin / 2);
-        w.g[i] = expf(-(c * c) / (2.f * 1.5f * 1.5f));
-        sum += w.g[i];
-    }
-    for (int i = 0; i < kWin; i++) w.g[i] /= sum;
+    for (int i = 0; i < kWin; i++) w.g[i] = half[i <= kWin / 2 ? i : kWin - 1 - i];
     return w;
 }
 

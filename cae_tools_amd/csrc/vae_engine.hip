@@ -343,13 +343,21 @@ int vae_score(vae_engine* e, const float* x, int batch, float* y) {
 int vae_loss_slots(const vae_engine* e) { return e ? kStepLossSlots : 0; }
 int vae_read_losses(vae_engine* e, int first_slot, int count, double* out) { return read_losses(e, "vae", first_slot, count, out); }
 int vae_sync(vae_engine* e) { return sync(e, "vae"); }
+void vae_gauss_window(float* out11) {
+    const vae::Gauss g = vae::make_gauss();
+    memcpy(out11, g.g, sizeof g.g);
+}
 int vae_debug_read(vae_engine* e, const char* what, float* out, int64_t count) {
     if (!e || !e->ws || !what || !out || count < 0) return fail(CAE_ERR_ARG, "vae_debug_read: bad argument");
     const float* src = nullptr;
+    int64_t cap = (int64_t)e->max_batch * e->latent;
+    const int64_t maps = (int64_t)e->max_batch * e->out_c * e->out_h * e->out_w;
     if (!strcmp(what, "eps")) src = e->f(e->eps);
     else if (!strcmp(what, "z")) src = cae_internal::trunk_latent(e->trunk);
-    else return fail(CAE_ERR_ARG, "vae_debug_read: unknown tensor '%s' (eps, z)", what);
-    if (count > (int64_t)e->max_batch * e->latent) return fail(CAE_ERR_ARG, "vae_debug_read: %lld floats exceed the tensor", (long long)count);
+    else if (!strcmp(what, "y")) src = e->f(e->sx[0]), cap = maps;
+    else if (!strcmp(what, "gssim")) src = e->f(e->sG[0]), cap = maps;
+    else return fail(CAE_ERR_ARG, "vae_debug_read: unknown tensor '%s' (eps, z, y, gssim)", what);
+    if (count > cap) return fail(CAE_ERR_ARG, "vae_debug_read: %lld floats exceed the tensor", (long long)count);
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
     return CAE_OK;

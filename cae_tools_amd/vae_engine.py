@@ -29,7 +29,8 @@ class VaeEngine(ShardedSteps, SteppedEngine, SpecPlan):
         check(self.lib.vae_set_kernel_mode(self.handle, int(mode)))
 
     def debug_read(self, what, shape):
-        """the last training forward's noise ("eps") or latent vector ("z"), rows of (batch, latent)"""
+        """what the last training-mode step left: the noise ("eps") or latent vector ("z"), rows of (batch, latent); the sigmoid
+        output ("y") or the gradient of lambda_ssim * (1 - MS-SSIM) with respect to it ("gssim"), planes of (batch * channels, H, W)"""
         out = np.empty(shape, dtype=np.float32)
         check(self.lib.vae_debug_read(self.handle, what.encode(), out.ctypes.data, out.size))
         return out

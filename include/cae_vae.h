@@ -80,8 +80,12 @@ int vae_score(vae_engine* e, const float* x_dev, int batch, float* y_dev);
 int vae_loss_slots(const vae_engine* e);
 int vae_read_losses(vae_engine* e, int first_slot, int count, double* out_host);   /* 4 doubles per slot */
 int vae_sync(vae_engine* e);
-/* blocking debug read of the last training forward's noise "eps" or latent "z" ((batch, latent) rows, count floats) */
+/* blocking debug read (count floats) of what the last training-mode step left in the workspace: the noise "eps" or the latent
+ * "z" ((batch, latent) rows); the sigmoid output "y" or "gssim" = d(lambda_ssim * (1 - MS-SSIM)) / dy ((batch * channels, H, W)
+ * planes; "y" is also left by an eval step, "gssim" only by a step that computes gradients) */
 int vae_debug_read(vae_engine* e, const char* what, float* out_host, int64_t count);
+/* the 11 window values of the MS-SSIM kernels (host only, no engine, no GPU): the fp32 values of the published definition */
+void vae_gauss_window(float* out11_host);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,11 @@ Definition
             data_range 1, K = (0.01, 0.03), 5 scales with weights (0.0448, 0.2856, 0.3001, 0.2363, 0.1333), 2x2 average
             pooling (padding = size mod 2) between scales, ReLU on the per-scale terms, mean over (batch, channel)
   optimiser Adam with L2 weight decay (as the ConvAE path, conv_ae_model.py:310)
+
+Precision: everything here follows the dtype of its inputs and state.  fp32 is the definition the HIP path implements; with fp64
+inputs (VaeOracle(..., dtype=torch.float64), ms_ssim(y.double(), t.double())) the same expressions give the 'exact' answer the
+parity tests anchor their bounds to.  The constants of the definition - the window, the scale weights, the noise - are the fp32
+values in either case, cast up: they are data of the definition, not results to be recomputed more accurately.
 """
 import math
 from collections import OrderedDict
@@ -33,10 +38,16 @@ MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 WIN_SIZE, WIN_SIGMA, K1, K2 = 11, 1.5, 0.01, 0.03
 
 
-def gaussian_window():
+def gaussian_window(dtype=torch.float32):
+    """the 11 fp32 window values of the definition, in `dtype`"""
     c = torch.arange(WIN_SIZE, dtype=torch.float32) - WIN_SIZE // 2
     g = torch.exp(-(c ** 2) / (2 * WIN_SIGMA ** 2))
-    return g / g.sum()
+    return (g / g.sum()).to(dtype)
+
+
+def scale_weights(dtype=torch.float32):
+    """MS_WEIGHTS as the fp32 values of the definition, in `dtype`, shaped to weigh a (scale, batch, channel) stack"""
+    return torch.tensor(MS_WEIGHTS, dtype=torch.float32).to(dtype).view(-1, 1, 1)
 
 
 def _filter(x, g):
@@ -55,21 +66,41 @@ def _ssim_cs(x, y, g):
     return ssim_map.flatten(2).mean(-1), cs_map.flatten(2).mean(-1)
 
 
-def ms_ssim(x, y):
-    """mean over (batch, channel) of prod_s cs_s^w_s * ssim_last^w_last; x, y (B,C,H,W) in [0,1]"""
-    g = gaussian_window()
+def per_scale_terms(x, y):
+    """(5, B, C): mean cs of scales 0..3 and mean ssim of scale 4, before the ReLU; x, y (B,C,H,W) in [0,1]"""
+    g = gaussian_window(x.dtype)
     terms = []
     for s in range(len(MS_WEIGHTS)):
         (ssim_c, cs) = _ssim_cs(x, y, g)
         if s < len(MS_WEIGHTS) - 1:
-            terms.append(torch.relu(cs))
+            terms.append(cs)
             pad = [d % 2 for d in x.shape[2:]]
             x = F.avg_pool2d(x, kernel_size=2, padding=pad)
             y = F.avg_pool2d(y, kernel_size=2, padding=pad)
-    terms.append(torch.relu(ssim_c))
-    stack = torch.stack(terms, dim=0)
-    w = torch.tensor(MS_WEIGHTS, dtype=stack.dtype).view(-1, 1, 1)
-    return torch.prod(stack ** w, dim=0).mean()
+    terms.append(ssim_c)
+    return torch.stack(terms, dim=0)
+
+
+def ms_ssim(x, y):
+    """mean over (batch, channel) of prod_s relu(cs_s)^w_s * relu(ssim_last)^w_last"""
+    stack = torch.relu(per_scale_terms(x, y))
+    return torch.prod(stack ** scale_weights(stack.dtype), dim=0).mean()
+
+
+def loss_parts(y, t, mu, logvar):
+    """(mse, kl, 1 - MS-SSIM) as tensors of the inputs' dtype"""
+    mse = F.mse_loss(y, t)
+    kl = -0.5 * torch.mean(1 + logvar - mu ** 2 - torch.exp(logvar))
+    return mse, kl, 1 - ms_ssim(y, t)
+
+
+def loss_parts_and_ssim_grad(y, t, mu, logvar, lambda_ssim=1.0, dtype=torch.float32):
+    """the definition's loss evaluated AT a given output y (B,C,H,W) - no network in front of it - in `dtype`:
+    ([mse, kl, 1 - MS-SSIM] as floats, d(lambda_ssim * (1 - MS-SSIM)) / dy as a (B,C,H,W) tensor of `dtype`)"""
+    y = y.detach().to(dtype).requires_grad_(True)
+    parts = loss_parts(y, t.detach().to(dtype), mu.detach().to(dtype), logvar.detach().to(dtype))
+    (g,) = torch.autograd.grad(lambda_ssim * parts[2], y)
+    return [float(v.detach()) for v in parts], g
 
 
 def normal_noise(seed, step, shape):
@@ -103,7 +134,8 @@ def encoder_forward(spec, enc, x, train):
 class VaeOracle:
 
     def __init__(self, spec, enc_state, dec_state, lr=1e-3, weight_decay=1e-5, lambda_mse=1.0, lambda_kl=1.0, lambda_ssim=1.0,
-                 seed=0):
+                 seed=0, dtype=None):
+        """dtype None: the state's own; torch.float64: the floating-point state cast up (the fp64 answer)"""
         self.spec = spec
         (self.lambda_mse, self.lambda_kl, self.lambda_ssim, self.seed) = (lambda_mse, lambda_kl, lambda_ssim, seed)
         self.step_count = 0
@@ -111,6 +143,8 @@ class VaeOracle:
         for (dst, src) in ((self.enc, enc_state), (self.dec, dec_state)):
             for k, v in src.items():
                 t = torch.as_tensor(np.array(v)) if not torch.is_tensor(v) else v.detach().clone()
+                if dtype is not None and t.is_floating_point():
+                    t = t.to(dtype)
                 dst[k] = t.requires_grad_(True) if is_param(k) else t
         self.optim = torch.optim.Adam([{"params": [v for k, v in self.enc.items() if is_param(k)]},
                                        {"params": [v for k, v in self.dec.items() if is_param(k)]}], lr=lr,
@@ -120,14 +154,11 @@ class VaeOracle:
         (mu, logvar) = encoder_forward(self.spec, self.enc, x, train)
         z = mu
         if train:
-            z = mu + torch.from_numpy(normal_noise(self.seed, self.step_count, tuple(mu.shape))) * torch.exp(0.5 * logvar)
+            z = mu + torch.from_numpy(normal_noise(self.seed, self.step_count, tuple(mu.shape))).to(mu.dtype) * torch.exp(0.5 * logvar)
         return decoder_forward(self.spec, self.dec, z, train), mu, logvar
 
     def losses(self, y, t, mu, logvar):
-        mse = F.mse_loss(y, t)
-        kl = -0.5 * torch.mean(1 + logvar - mu ** 2 - torch.exp(logvar))
-        ssim_loss = 1 - ms_ssim(y, t)
-        return mse, kl, ssim_loss
+        return loss_parts(y, t, mu, logvar)
 
     def total(self, parts):
         return self.lambda_mse * parts[0] + self.lambda_kl * parts[1] + self.lambda_ssim * parts[2]

@@ -5,7 +5,11 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import assert_close_as_reference
+
 pytestmark = pytest.mark.gpu
+
+PARTS = ("mse", "kl", "1 - ms_ssim")
 
 
 def _setup(in_size, out_size, fc, latent, B, seed, in_ch=1, out_ch=1):
@@ -52,7 +56,8 @@ def test_losses_and_gradients_match_the_definition(lambdas):
     (spec, enc, dec, x, t) = _setup((12, 12), (176, 192), fc, latent, B, seed=5)
     hyper = dict(lambda_mse=lambdas[0], lambda_kl=lambdas[1], lambda_ssim=lambdas[2], seed=9)
     o = vo.VaeOracle(spec.save(), enc.state_dict(), dec.state_dict(), **hyper)
-    o.step_count = 4
+    o64 = vo.VaeOracle(spec.save(), enc.state_dict(), dec.state_dict(), dtype=torch.float64, **hyper)
+    o.step_count = o64.step_count = 4
     eng = _engine(spec, enc, dec, fc, latent, B, **hyper)
     eng.set_step(4)
     eng.set_dataset(0, x, t)
@@ -63,10 +68,16 @@ def test_losses_and_gradients_match_the_definition(lambdas):
     got = eng.read_losses(2, 1)[0]
     np.testing.assert_allclose(got[:3], want, rtol=2e-5, atol=1e-7)
     np.testing.assert_allclose(got[3], lambdas[0] * want[0] + lambdas[1] * want[1] + lambdas[2] * want[2], rtol=2e-5)
+    want64 = o64.eval_losses(x.double(), t.double())
+    for i, part in enumerate(PARTS):      # no further from fp64 than 3 x the fp32 definition's own error (+ 1e-5 relative)
+        assert_close_as_reference(got[i], want[i], want64[i], "eval " + part)
     # train: reparameterised sample with the shared noise hash
     g = _grad_dict(eng, eng.forward_backward(0, None, 0, B, slot=0))
     (parts, _) = o.loss_and_grads(x, t)
     np.testing.assert_allclose(eng.read_losses(0, 1)[0][:3], parts, rtol=3e-5, atol=1e-7)
+    (parts64, _) = o64.loss_and_grads(x.double(), t.double())
+    for i, part in enumerate(PARTS):
+        assert_close_as_reference(eng.read_losses(0, 1)[0][i], parts[i], parts64[i], "train " + part)
     last_bias = "dec/decoder_conv.%d.bias" % (3 * (len(spec.get_output_layers()) - 1))
     for k, w in o.grads().items():
         (gv, wv) = (g[k].numpy().astype(np.float64), w.numpy().astype(np.float64))
