@@ -98,6 +98,11 @@ SIGNATURES = {
     "cae_case_measures_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "cae_case_measures": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, _P,
                                     C.c_int64, _P]),
+    "cae_case_range_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "cae_case_range": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64,
+                                 _P]),
+    "cae_render_cases": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64,
+                                   C.c_int64, C.c_double, C.c_double, C.c_int, _P, _P]),
     # ---- include/cae_unet.h ----
     "unet_engine_create": (C.c_int, [C.POINTER(LayerSpecC), C.c_int, C.POINTER(LayerSpecC), C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.POINTER(C.c_void_p)]),

@@ -1,6 +1,10 @@
 """evaluate_cae — command line front end with the reference's flags (src/cae_tools/cli/evaluate_cae.py:23-55): the
 metrics of a model folder on training and / or test files, an optional database row, and with --output-html-folder an
-index.html report with per-case error histograms (ModelEvaluator)."""
+index.html report with per-case error histograms (ModelEvaluator).  With --x-coordinate, --y-coordinate and
+--time-coordinate it also writes <partition>/index.html case pages linked from the report: channel 0 of the
+--input-variables, the target, the prediction and their difference for --sample-count evenly spaced cases (all without
+it), worst mse first; drawn by netcdf2html where that is installed, else by the package itself on the GPU
+(utils/case_pages.py; value ranges and palette indices as models/model_evaluator.py defines them)."""
 import argparse
 
 from ..models.model_evaluator import ModelEvaluator

@@ -2948,6 +2948,134 @@ int cae_case_measures(const void* pred, int pred_kind, int64_t pred_stride, cons
     return CAE_OK;
 }
 
+// ---- case pages ------------------------------------------------------------------------------
+
+static int64_t range_blocks(int64_t n_case, int64_t plane) {
+    int64_t blocks = (n_case * case_chunks(plane) + CM_WAVES - 1) / CM_WAVES;
+    return blocks > 8192 ? 8192 : blocks;
+}
+
+int64_t cae_case_range_workspace_bytes(int64_t n_case, int64_t plane) {
+    if (n_case < 1 || plane < 1) return 0;
+    return range_blocks(n_case, plane) * 3 * (int64_t)sizeof(double);
+}
+
+extern "C++" {
+
+// one operand pair of the case-page kernels: the source and the optional operand subtracted from it (kind -1: none)
+struct CasePair {
+    const void* src;
+    int64_t src_stride;
+    const void* sub;
+    int64_t sub_stride;
+};
+
+struct RenderArgs {
+    const int* cases;
+    int64_t n_case;
+    unsigned height, width;
+    double lo, hi;
+    int flip_y;
+    unsigned char* out;
+};
+
+template <int KS, int KB>
+static void launch_case_range(dim3 grid, hipStream_t s, const CasePair& p, int64_t plane, int nch, int64_t items,
+                              double* part) {
+    hipLaunchKernelGGL((k_case_range<KS, KB>), grid, dim3(256), 0, s, (const unsigned char*)p.src, (long long)p.src_stride,
+                       (const unsigned char*)p.sub, (long long)p.sub_stride, (long long)plane, nch, (long long)items, part);
+}
+
+template <int KS, int KB>
+static void launch_render_cases(dim3 grid, hipStream_t s, const CasePair& p, const RenderArgs& r, int nch, int64_t items) {
+    hipLaunchKernelGGL((k_render_cases<KS, KB>), grid, dim3(256), 0, s, (const unsigned char*)p.src,
+                       (long long)p.src_stride, (const unsigned char*)p.sub, (long long)p.sub_stride, r.cases,
+                       (long long)r.n_case, r.height, r.width, r.lo, r.hi, r.flip_y, nch, (long long)items, r.out);
+}
+
+// CALL<KS, KB>(args...) for the run-time kinds ks (0..3) and kb (-1..3)
+#define CP_DISPATCH_B(CALL, KS, kb, ...)                  \
+    switch (kb) {                                         \
+    case CAE_ELEM_F32: CALL<KS, 0>(__VA_ARGS__); break;    \
+    case CAE_ELEM_F32_BE: CALL<KS, 1>(__VA_ARGS__); break; \
+    case CAE_ELEM_F64: CALL<KS, 2>(__VA_ARGS__); break;    \
+    case CAE_ELEM_F64_BE: CALL<KS, 3>(__VA_ARGS__); break; \
+    default: CALL<KS, -1>(__VA_ARGS__); break;             \
+    }
+#define CP_DISPATCH(CALL, ks, kb, ...)                                        \
+    switch (ks) {                                                             \
+    case CAE_ELEM_F32: CP_DISPATCH_B(CALL, 0, kb, __VA_ARGS__) break;          \
+    case CAE_ELEM_F32_BE: CP_DISPATCH_B(CALL, 1, kb, __VA_ARGS__) break;       \
+    case CAE_ELEM_F64: CP_DISPATCH_B(CALL, 2, kb, __VA_ARGS__) break;          \
+    default: CP_DISPATCH_B(CALL, 3, kb, __VA_ARGS__) break;                    \
+    }
+
+}  // extern "C++"
+
+// the shared argument checks of cae_case_range / cae_render_cases; kb is set to the dispatch kind of `sub` (-1: none)
+static int case_pair_check(const char* who, const void* src, int src_kind, int64_t src_stride, const void* sub,
+                           int sub_kind, int64_t sub_stride, int64_t plane, int* kb) {
+    auto elem_bytes = [](int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; };
+    auto known = [](int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; };
+    if (!src || !known(src_kind) || (sub && !known(sub_kind))) return fail(CAE_ERR_ARG, "%s: bad argument", who);
+    if (src_stride < plane || (sub && sub_stride < plane))
+        return fail(CAE_ERR_ARG, "%s: a case stride is shorter than the plane", who);
+    if (((uintptr_t)src % elem_bytes(src_kind)) || (sub && ((uintptr_t)sub % elem_bytes(sub_kind))))
+        return fail(CAE_ERR_ARG, "%s: pointers must be aligned to their element size", who);
+    *kb = sub ? sub_kind : -1;
+    return CAE_OK;
+}
+
+int cae_case_range(const void* src, int src_kind, int64_t src_stride, const void* sub, int sub_kind, int64_t sub_stride,
+                   int64_t n_case, int64_t plane, double* out, void* workspace, int64_t workspace_bytes,
+                   void* hip_stream) {
+    if (!out || ((uintptr_t)out & 7) || n_case < 1 || plane < 1) return fail(CAE_ERR_ARG, "cae_case_range: bad argument");
+    int kb = -1;
+    const int rc = case_pair_check("cae_case_range", src, src_kind, src_stride, sub, sub_kind, sub_stride, plane, &kb);
+    if (rc != CAE_OK) return rc;
+    const int64_t nch = case_chunks(plane);
+    if (nch > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_case_range: plane too large");
+    const int64_t need = cae_case_range_workspace_bytes(n_case, plane);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
+        return fail(CAE_ERR_ARG, "cae_case_range: needs a workspace of %lld bytes (cae_case_range_workspace_bytes)",
+                    (long long)need);
+    hipStream_t s = (hipStream_t)hip_stream;
+    const int64_t blocks = range_blocks(n_case, plane);
+    const dim3 grid((unsigned)blocks);
+    const CasePair pair{src, src_stride, sub, sub_stride};
+    CP_DISPATCH(launch_case_range, src_kind, kb, grid, s, pair, plane, (int)nch, n_case * nch, (double*)workspace)
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_range_fold, dim3(1), dim3(256), 0, s, (const double*)workspace, (int)blocks, out);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+int cae_render_cases(const void* src, int src_kind, int64_t src_stride, const void* sub, int sub_kind, int64_t sub_stride,
+                     const int32_t* cases, int64_t n_sel, int64_t n_case, int64_t height, int64_t width, double lo,
+                     double hi, int flip_y, uint8_t* out, void* hip_stream) {
+    if (!out || n_sel < 1 || n_case < 1 || height < 1 || width < 1 || ((uintptr_t)cases & 3))
+        return fail(CAE_ERR_ARG, "cae_render_cases: bad argument");
+    if (height * (width + 1) > 0x7fffffffLL || width > 0x7ffffffeLL)
+        return fail(CAE_ERR_ARG, "cae_render_cases: image too large (height * (width + 1) must stay below 2^31)");
+    if (!(lo - lo == 0.0) || !(hi - hi == 0.0) || !((hi - lo) - (hi - lo) == 0.0))
+        return fail(CAE_ERR_ARG, "cae_render_cases: lo, hi and hi - lo must be finite");
+    int kb = -1;
+    const int rc = case_pair_check("cae_render_cases", src, src_kind, src_stride, sub, sub_kind, sub_stride,
+                                   height * width, &kb);
+    if (rc != CAE_OK) return rc;
+    const int64_t len = height * (width + 1);
+    const int64_t nch = (len / 4 + RC_DWORDS - 1) / RC_DWORDS > 0 ? (len / 4 + RC_DWORDS - 1) / RC_DWORDS : 1;
+    const int64_t items = n_sel * nch;
+    int64_t blocks = (items + CM_WAVES - 1) / CM_WAVES;
+    if (blocks > 8192) blocks = 8192;
+    const dim3 grid((unsigned)blocks);
+    const CasePair pair{src, src_stride, sub, sub_stride};
+    const RenderArgs r{(const int*)cases, n_case, (unsigned)height, (unsigned)width, lo, hi, flip_y, out};
+    CP_DISPATCH(launch_render_cases, src_kind, kb, grid, (hipStream_t)hip_stream, pair, r, (int)nch, items)
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
 }  // extern "C"
 
 // =================================================================================================

@@ -1386,4 +1386,233 @@ __global__ void __launch_bounds__(256) k_case_fold(const double* __restrict__ pa
     }
 }
 
+// ---- case pages (evaluate_cae's per-case images): the value range of channel 0 and its palette indices.
+// KS is the source's element kind, KB the kind of the optional operand subtracted from it in fp64 (-1: none).
+template <int K> struct CpBytes { static constexpr int bytes = CmElem<K>::bytes; };
+template <> struct CpBytes<-1> { static constexpr int bytes = 4; };
+
+template <int KS, int KB>
+__device__ __forceinline__ double cp_value1(const unsigned char* sc, const unsigned char* bc, long long e) {
+    const double v = cm_load1<KS>(sc, e);
+    if constexpr (KB >= 0) return v - cm_load1<KB>(bc, e);
+    else return v;
+}
+
+template <int KS, int KB>
+__device__ __forceinline__ void cp_value4(const unsigned char* sc, const unsigned char* bc, long long e, bool vec,
+                                          double v[4]) {
+    cm_load4<KS>(sc, e, vec, v);
+    if constexpr (KB >= 0) {
+        double b[4];
+        cm_load4<KB>(bc, e, vec, b);
+#pragma unroll
+        for (int j = 0; j < 4; j++) v[j] -= b[j];
+    }
+}
+
+// NaN and +-Inf are left out; min / max compare by value
+__device__ __forceinline__ void cp_range_acc(double v, double& mn, double& mx, long long& n) {
+    if (fabs(v) < __builtin_huge_val()) {
+        mn = v < mn ? v : mn;
+        mx = v > mx ? v : mx;
+        n++;
+    }
+}
+
+// k_case_measures' items and loads: one wave per (case, 4096-element chunk), 16-byte loads from the case's first common
+// 16-byte phase on.  A wave keeps min / max / count over all its items, the workgroup's four waves meet in LDS and
+// part[blockIdx.x] = {min, max, count} is one plain store: no atomics.  min and max do not depend on the order and the
+// count is an integer, so the result is the same from run to run.
+template <int KS, int KB>
+__global__ void __launch_bounds__(256) k_case_range(const unsigned char* __restrict__ s, long long s_stride,
+                                                    const unsigned char* __restrict__ b, long long b_stride,
+                                                    long long plane, int nch, long long items,
+                                                    double* __restrict__ part) {
+    constexpr int ES = CpBytes<KS>::bytes, EB = CpBytes<KB>::bytes;
+    __shared__ double red[CM_WAVES][3];
+    const int lane = threadIdx.x & 63;
+    double mn = __builtin_huge_val(), mx = -__builtin_huge_val();
+    long long cnt = 0;
+    for (long long item = (long long)blockIdx.x * CM_WAVES + (threadIdx.x >> 6); item < items;
+         item += (long long)gridDim.x * CM_WAVES) {
+        const long long cs = item / nch;
+        const int ch = (int)(item - cs * nch);
+        const unsigned char* sc = s + cs * s_stride * ES;
+        const unsigned char* bc = KB >= 0 ? b + cs * b_stride * EB : nullptr;
+        int h = -1;
+        for (int t = 3; t >= 0; t--)
+            if ((((uintptr_t)(sc + t * ES) | (KB >= 0 ? (uintptr_t)(bc + t * EB) : 0)) & 15) == 0) h = t;
+        const bool vec = h >= 0;
+        const long long head = vec ? (h < plane ? h : plane) : 0;
+        const long long groups = (plane - head) >> 2;
+        const long long tail0 = head + (groups << 2);
+        if (ch == 0) {
+            if (lane < head) cp_range_acc(cp_value1<KS, KB>(sc, bc, lane), mn, mx, cnt);
+            else if (lane >= 4 && lane - 4 < plane - tail0)
+                cp_range_acc(cp_value1<KS, KB>(sc, bc, tail0 + lane - 4), mn, mx, cnt);
+        }
+        const long long g0 = (long long)ch * CM_GROUPS;
+        const long long g1 = g0 + CM_GROUPS < groups ? g0 + CM_GROUPS : groups;
+        long long g = g0 + lane;
+        for (; g + 3 * 64 < g1; g += 4 * 64) {      // four groups in flight per lane
+            double v[4][4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) cp_value4<KS, KB>(sc, bc, head + ((g + u * 64) << 2), vec, v[u]);
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) cp_range_acc(v[u][j], mn, mx, cnt);
+        }
+        for (; g < g1; g += 64) {
+            double v[4];
+            cp_value4<KS, KB>(sc, bc, head + (g << 2), vec, v);
+#pragma unroll
+            for (int j = 0; j < 4; j++) cp_range_acc(v[j], mn, mx, cnt);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double omn = __shfl_down(mn, off, 64), omx = __shfl_down(mx, off, 64);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+        cnt += __shfl_down(cnt, off, 64);
+    }
+    if (lane == 0) {
+        red[threadIdx.x >> 6][0] = mn;
+        red[threadIdx.x >> 6][1] = mx;
+        red[threadIdx.x >> 6][2] = (double)cnt;      // exact: far below 2^53
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < CM_WAVES; w++) {
+            mn = red[w][0] < mn ? red[w][0] : mn;
+            mx = red[w][1] > mx ? red[w][1] : mx;
+            red[0][2] += red[w][2];
+        }
+        part[3 * (size_t)blockIdx.x] = mn;
+        part[3 * (size_t)blockIdx.x + 1] = mx;
+        part[3 * (size_t)blockIdx.x + 2] = red[0][2];
+    }
+}
+
+// out = the fold of n_part workgroup partials {min, max, count}; one workgroup
+__global__ void __launch_bounds__(256) k_range_fold(const double* __restrict__ part, int n_part, double* __restrict__ out) {
+    __shared__ double red[CM_WAVES][3];
+    double mn = __builtin_huge_val(), mx = -__builtin_huge_val(), cnt = 0.0;
+    for (int i = threadIdx.x; i < n_part; i += 256) {
+        mn = part[3 * i] < mn ? part[3 * i] : mn;
+        mx = part[3 * i + 1] > mx ? part[3 * i + 1] : mx;
+        cnt += part[3 * i + 2];                       // integers below 2^53: exact in any order
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double omn = __shfl_down(mn, off, 64), omx = __shfl_down(mx, off, 64);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+        cnt += __shfl_down(cnt, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6][0] = mn;
+        red[threadIdx.x >> 6][1] = mx;
+        red[threadIdx.x >> 6][2] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < CM_WAVES; w++) {
+            mn = red[w][0] < mn ? red[w][0] : mn;
+            mx = red[w][1] > mx ? red[w][1] : mx;
+            cnt += red[w][2];
+        }
+        out[0] = mn;
+        out[1] = mx;
+        out[2] = cnt;
+    }
+}
+
+// The palette index of one value: 0 for NaN, else 1 + the nearest of 255 levels over [lo, hi] (all of them the middle
+// level when hi <= lo).  fp64, every operation rounded on its own - a numpy restatement gives the same bytes only if
+// the multiply and the add are not fused.
+__device__ __forceinline__ unsigned cp_index(double v, double lo, double hi) {
+#pragma clang fp contract(off)
+    if (v != v) return 0u;
+    double t = 0.5;
+    if (hi > lo) {
+        t = (v - lo) / (hi - lo);
+        t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+    }
+    const double scaled = t * 254.0;
+    return 1u + (unsigned)(int)(scaled + 0.5);
+}
+
+// A selected case's output is one flat stream of height * (width + 1) bytes: PNG scanlines, each a filter byte 0 and
+// `width` palette indices.  The stream is cut at its first 4-byte aligned address: a lane assembles one aligned dword of
+// four output bytes (the row and column of its first byte by one 32-bit division, the other three by stepping) and
+// stores it; consecutive lanes store consecutive dwords.  The up to 3 bytes before and after the dwords are byte stores
+// by lanes of chunk 0.  The four source elements of a dword are consecutive in the plane (a filter byte in between costs
+// nothing) but at any element phase, so they are element loads: four loads per lane, the wave's four covering the same
+// lines.  One wave per (selected case, RC_DWORDS dwords) item.  A case index outside [0, n_case) draws index 0.
+constexpr int RC_DWORDS = 1024;          // 4096 output bytes per chunk
+
+template <int KS, int KB>
+__device__ __forceinline__ unsigned cp_pixel(const unsigned char* sc, const unsigned char* bc, unsigned y, unsigned c,
+                                             unsigned height, unsigned width, bool flip, bool valid, double lo,
+                                             double hi) {
+    const unsigned sy = flip ? height - 1u - y : y;
+    const long long e = (long long)sy * width + (c ? c - 1u : 0u);       // always inside the plane
+    const unsigned idx = valid ? cp_index(cp_value1<KS, KB>(sc, bc, e), lo, hi) : 0u;
+    return c ? idx : 0u;
+}
+
+template <int KS, int KB>
+__global__ void __launch_bounds__(256) k_render_cases(const unsigned char* __restrict__ s, long long s_stride,
+                                                      const unsigned char* __restrict__ b, long long b_stride,
+                                                      const int* __restrict__ cases, long long n_case, unsigned height,
+                                                      unsigned width, double lo, double hi, int flip_y, int nch,
+                                                      long long items, unsigned char* __restrict__ out) {
+    constexpr int ES = CpBytes<KS>::bytes, EB = CpBytes<KB>::bytes;
+    const unsigned lane = threadIdx.x & 63;
+    const unsigned pitch = width + 1u;
+    const unsigned len = height * pitch;            // the host keeps it below 2^31
+    const bool flip = flip_y != 0;
+    for (long long item = (long long)blockIdx.x * CM_WAVES + (threadIdx.x >> 6); item < items;
+         item += (long long)gridDim.x * CM_WAVES) {
+        const long long k = item / nch;
+        const unsigned ch = (unsigned)(item - k * nch);
+        long long cs = cases ? (long long)cases[k] : k;
+        const bool valid = cs >= 0 && cs < n_case;
+        if (!valid) cs = 0;
+        const unsigned char* sc = s + cs * s_stride * ES;
+        const unsigned char* bc = KB >= 0 ? b + cs * b_stride * EB : nullptr;
+        unsigned char* ob = out + k * (long long)len;
+        unsigned head = (4u - (unsigned)((uintptr_t)ob & 3)) & 3u;
+        if (head > len) head = len;
+        const unsigned ndw = (len - head) >> 2;
+        const unsigned tail0 = head + (ndw << 2);
+        if (ch == 0) {
+            unsigned q = len;
+            if (lane < head) q = lane;
+            else if (lane >= 4 && lane - 4 < len - tail0) q = tail0 + lane - 4;
+            if (q < len) {
+                const unsigned y = q / pitch;
+                ob[q] = (unsigned char)cp_pixel<KS, KB>(sc, bc, y, q - y * pitch, height, width, flip, valid, lo, hi);
+            }
+        }
+        const unsigned d0 = ch * RC_DWORDS;
+        const unsigned d1 = d0 + RC_DWORDS < ndw ? d0 + RC_DWORDS : ndw;
+        for (unsigned d = d0 + lane; d < d1; d += 64) {
+            const unsigned q = head + (d << 2);
+            unsigned y = q / pitch;
+            unsigned c = q - y * pitch;
+            unsigned w = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                w |= cp_pixel<KS, KB>(sc, bc, y, c, height, width, flip, valid, lo, hi) << (8 * j);
+                if (++c == pitch) {
+                    c = 0;
+                    y++;
+                }
+            }
+            *reinterpret_cast<unsigned*>(ob + q) = w;
+        }
+    }
+}
+
 }  // namespace cae

@@ -569,10 +569,26 @@ def upload_f32(arr, device):
 _TORCH_KINDS = {torch.float32: _lib.ELEM_F32, torch.float64: _lib.ELEM_F64}
 
 
+class DeviceOperand(tuple):
+    """(device tensor kept alive, element kind, shape, case stride in elements): what _measure_operand returns, as a
+    type of its own so that case_measures / case_range / render_cases take it again without another upload"""
+
+    tensor = property(lambda self: self[0])
+    shape = property(lambda self: self[2])
+
+
+def device_operand(x, device=None):
+    """x (numpy array, raw NetCDF-3 slab or CUDA tensor) on the device, ready for the case kernels"""
+    return DeviceOperand(_measure_operand(x, _case_device(device, x)))
+
+
 def _measure_operand(x, device):
     """(device tensor kept alive, element kind, shape, case stride in elements) of one case_measures operand.  A CUDA
     tensor is used in place; a C-contiguous big-endian >f4 / >f8 numpy array (a NetCDF-3 slab) goes up as its raw
-    bytes and is swapped inside the kernel; any other array is uploaded in its native fp32 / fp64 form."""
+    bytes and is swapped inside the kernel; any other array is uploaded in its native fp32 / fp64 form.  An operand
+    made earlier (device_operand) is handed through, so one upload serves several calls."""
+    if isinstance(x, DeviceOperand):
+        return x
     if isinstance(x, torch.Tensor):
         if not x.is_cuda:
             x = x.numpy()
@@ -597,11 +613,7 @@ def case_measures(pred, actual, device=None):
     for every case at once: mean |p - a| and mean (p - a)^2 over [i, 0, :, :] in fp64.  pred / actual: (N, C, H, W) numpy
     arrays or CUDA tensors (fp32 or fp64; C may differ).  One streaming pass of cae_case_measures.  Returns an (N, 2)
     float64 numpy array."""
-    if device is None:
-        device = next((x.device for x in (pred, actual) if isinstance(x, torch.Tensor) and x.is_cuda), None)
-    if device is None:
-        require_gpu()
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _case_device(device, pred, actual)
     (p, pk, pshape, pstride) = _measure_operand(pred, device)
     (a, ak, ashape, astride) = _measure_operand(actual, device)
     if len(pshape) != 4 or len(ashape) != 4:
@@ -622,3 +634,89 @@ def case_measures(pred, actual, device=None):
                                     ws.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream))
         sums = out.cpu().numpy()
     return sums / float(plane)
+
+
+def _case_device(device, *operands):
+    """the device the case kernels run on: the one given, else that of a device-resident operand, else the current one"""
+    if device is None:
+        for x in operands:
+            if isinstance(x, DeviceOperand):
+                x = x.tensor
+            if isinstance(x, torch.Tensor) and x.is_cuda:
+                return x.device
+        require_gpu()
+        device = torch.device("cuda", torch.cuda.current_device())
+    return torch.device(device)
+
+
+def _case_pair(name, arr, sub, device):
+    """(source operand, subtracted operand or None, N, H, W) of case_range / render_cases"""
+    src = _measure_operand(arr, device)
+    other = _measure_operand(sub, device) if sub is not None else None
+    shape = src[2]
+    if len(shape) != 4:
+        raise ValueError(f"{name}: an (N, C, H, W) array expected, got {tuple(shape)}")
+    if other is not None and (len(other[2]) != 4 or other[2][0] != shape[0] or tuple(other[2][2:]) != tuple(shape[2:])):
+        raise ValueError(f"{name}: {tuple(shape)} and the subtracted {tuple(other[2])} do not match")
+    return src, other, int(shape[0]), int(shape[2]), int(shape[3])
+
+
+def _sub_args(other):
+    return (other[0].data_ptr(), other[1], other[3]) if other is not None else (None, 0, 0)
+
+
+def case_range(arr, sub=None, device=None):
+    """(min, max, count) of the finite values of channel 0 of arr (N, C, H, W), or of arr - sub formed in fp64: what
+    np.nanmin / np.nanmax of the fp64 copy give where nothing is infinite, in one streaming pass of cae_case_range over
+    the array as stored.  Operands as case_measures takes them.  (inf, -inf, 0) when no value is finite."""
+    device = _case_device(device, arr, sub)
+    (src, other, n, h, w) = _case_pair("case_range", arr, sub, device)
+    if n * h * w == 0:
+        return float("inf"), float("-inf"), 0
+    lib = _lib.load()
+    need = int(lib.cae_case_range_workspace_bytes(n, h * w))
+    ws = torch.empty(need, dtype=torch.uint8, device=device)
+    out = torch.empty(3, dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        check(lib.cae_case_range(src[0].data_ptr(), src[1], src[3], *_sub_args(other), n, h * w, out.data_ptr(),
+                                 ws.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream))
+        (lo, hi, count) = out.cpu().tolist()
+    return lo, hi, int(count)
+
+
+_RENDER_BYTES = 64 << 20
+
+
+def render_cases(arr, lo, hi, cases=None, sub=None, flip_y=False, device=None):
+    """Channel 0 of the selected cases of arr (N, C, H, W), or of arr - sub in fp64, as palette indices in PNG scanline
+    form (cae_render_cases, include/cae_hip.h): a (k, H, W + 1) uint8 numpy array whose rows start with the filter byte 0.
+    cases: case indices in any order, repeats allowed (None: all).  Rendered in groups of cases, so that at most about
+    _RENDER_BYTES of output are on the device and in pinned host memory at a time."""
+    device = _case_device(device, arr, sub)
+    (src, other, n, h, w) = _case_pair("render_cases", arr, sub, device)
+    sel = np.arange(n, dtype=np.int32) if cases is None else np.asarray(cases, dtype=np.int64).reshape(-1)
+    if sel.size and (sel.min() < 0 or sel.max() >= n):
+        raise IndexError(f"render_cases: case indices must lie in [0, {n})")
+    result = np.empty((sel.size, h, w + 1), dtype=np.uint8)
+    if result.size == 0:
+        return result
+    if w == 0:
+        result[:] = 0
+        return result
+    lib = _lib.load()
+    size = h * (w + 1)
+    group = max(1, min(sel.size, _RENDER_BYTES // size))
+    sel_dev = torch.from_numpy(sel.astype(np.int32)).to(device)
+    out = torch.empty(group * size, dtype=torch.uint8, device=device)
+    stage = torch.empty(group * size, dtype=torch.uint8).pin_memory()
+    flat = result.reshape(-1)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        for k0 in range(0, sel.size, group):
+            k = min(group, sel.size - k0)
+            check(lib.cae_render_cases(src[0].data_ptr(), src[1], src[3], *_sub_args(other),
+                                       sel_dev.data_ptr() + 4 * k0, k, n, h, w, float(lo), float(hi),
+                                       1 if flip_y else 0, out.data_ptr(), stream))
+            stage[:k * size].copy_(out[:k * size], non_blocking=False)
+            flat[k0 * size:(k0 + k) * size] = stage.numpy()[:k * size]
+    return result

@@ -6,8 +6,16 @@ The metrics are model.evaluate() (scoring and cae_metric_sums on the GPU).  The 
 NetCDF-3 slabs as the file stores them, or the prediction the evaluator has just produced where it is still on the GPU.
 Departures from the reference: no output folder means metrics and database row only, not a crash on the
 unset report path; a missing --prediction-variable means apply()'s default "model_output", not None; the plots are SVG
-drawn by utils/report.py in place of seaborn PNGs; the netcdf2html case pages are made only where that optional package
-is installed.
+drawn by utils/report.py in place of seaborn PNGs.
+
+The case pages (--x-coordinate, --y-coordinate and --time-coordinate all given) are netcdf2html's where that optional
+package imports.  Elsewhere the package makes its own (utils/case_pages.py): <partition>/index.html with one row per
+case, worst mse first, and channel 0 (only) of the requested input variables, the target, the prediction and the error
+prediction - target as palette PNGs.  netcdf2html is not part of the reference tree, so ranges and colours are this
+package's definition: each input variable is scaled over its own finite values in both partitions, target and
+prediction share one range, the error is scaled over +-max|prediction - target| (cae_case_range); a pixel's palette
+index is 0 for NaN and 1 + round-half-up(254 * clamp((v - lo) / (hi - lo), 0, 1)) otherwise, computed in fp64 on the GPU
+(cae_render_cases) from the slabs as stored and from the prediction where it still lies in HBM.
 """
 import json
 import os
@@ -15,7 +23,8 @@ import os
 import numpy as np
 
 from ..data.arrays import as_numpy, open_mfdataset
-from ..engine import case_measures
+from ..engine import case_measures, case_range, device_operand, render_cases
+from ..utils import case_pages
 from ..utils.model_database import ModelDatabase
 from ..utils.report import evaluation_report
 from .base_model import _make_data_array
@@ -52,6 +61,8 @@ class ModelEvaluator:
             if input_variable not in self.model_input_variables:
                 raise Exception(f"requested {input_variable} is not a model input")
         self._device_predictions = {}
+        self._page_ops = {}          # the case pages' device operands and value ranges
+        self._page_range = None
 
     def compute_measure(self, dataset, idx, measure):
         """one case's mae or mse of channel 0 (:87-95); build_html computes all cases at once with case_measures"""
@@ -141,15 +152,20 @@ class ModelEvaluator:
                 if self._case_summary(case_dimension, partition, ds, train_ds, test_ds):
                     case_links[partition] = partition + "/index.html"
 
+        self._page_ops = {}
         page = evaluation_report(model_metrics, measures, training_parameters, training_losses, case_links)
         os.makedirs(self.output_html_folder, exist_ok=True)
         with open(self.output_html_path, "w") as f:
             f.write(page)
 
     def _case_summary(self, case_dimension, partition, ds, train_ds, test_ds):
-        """the optional netcdf2html case pages (:205-253, 285-293); False when they cannot be made"""
+        """the case pages of one partition: netcdf2html's (:205-253, 285-293) where that optional package imports, else
+        the package's own (utils/case_pages.py, rendered on the GPU); False when they cannot be made"""
         try:
             from netcdf2html.api.netcdf2html_converter import Netcdf2HtmlConverter
+        except ImportError:
+            return self._native_case_summary(case_dimension, partition, ds, train_ds, test_ds)
+        try:
             layers = {}
             shared = [self.output_variable, self.model_output_variable]
             for v in self.input_variables + shared:
@@ -167,4 +183,90 @@ class ModelEvaluator:
             return True
         except Exception:
             print("Unable to create case summary")
+            return False
+
+    # ---- the package's own case pages ---------------------------------------------------------
+
+    def _page_operands(self, partition, ds):
+        """{variable: device operand} of what a partition's pages draw, uploaded once: the NetCDF slabs as stored, and
+        the prediction where build_html has just made it"""
+        ops = self._page_ops.get(partition)
+        if ops is None:
+            ops = {v: device_operand(as_numpy(ds[v])) for v in self.input_variables + [self.output_variable]}
+            pred = self._device_predictions.get(partition)
+            ops[self.model_output_variable] = device_operand(pred if pred is not None
+                                                             else as_numpy(ds[self.model_output_variable]))
+            self._page_ops[partition] = ops
+        return ops
+
+    def _page_ranges(self, train_ds, test_ds):
+        """{layer: (lo, hi)} over both partitions (cae_case_range, channel 0, finite values): each input variable its own,
+        target and prediction one shared range, the error prediction - target the symmetric +-max|d|.  A layer without
+        a finite value gets (0, 0): everything that is not NaN is then drawn at the middle level."""
+        if self._page_range is not None:
+            return self._page_range
+        parts = [self._page_operands(p, d) for (p, d) in (("train", train_ds), ("test", test_ds)) if d is not None]
+
+        def span(pairs):
+            found = [case_range(a, sub=b) for (a, b) in pairs]
+            if sum(f[2] for f in found) == 0:
+                return 0.0, 0.0
+            return min(f[0] for f in found), max(f[1] for f in found)
+
+        (target, pred) = (self.output_variable, self.model_output_variable)
+        ranges = {v: span([(ops[v], None) for ops in parts]) for v in self.input_variables}
+        ranges[target] = ranges[pred] = span([(ops[v], None) for ops in parts for v in (target, pred)])
+        (lo, hi) = span([(ops[pred], ops[target]) for ops in parts])
+        bound = max(abs(lo), abs(hi))
+        ranges[case_pages.ERROR_LAYER] = (-bound, bound)
+        self._page_range = ranges
+        return ranges
+
+    def _flip_y(self, ds, variable):
+        """True when the y coordinate lies along the variable's image rows and ascends (first case / column where it has
+        more dimensions): row 0 of the picture is then the largest y"""
+        try:
+            yc = ds[self.y_coordinate]
+        except KeyError:
+            return False
+        ydim = ds[variable].dims[-2]
+        if ydim not in yc.dims:
+            return False
+        along = np.asarray(yc.values)[tuple(slice(None) if d == ydim else 0 for d in yc.dims)]
+        return bool(along.size > 1 and along[-1] > along[0])
+
+    def _case_times(self, ds, case_dimension, cases):
+        """(the time coordinate's value of each selected case, its units), or (None, "") when the coordinate is not
+        indexed by the case dimension"""
+        try:
+            tc = ds[self.time_coordinate]
+        except KeyError:
+            return None, ""
+        if tuple(tc.dims) != (case_dimension,):
+            return None, ""
+        return np.asarray(tc.values)[cases], str(getattr(tc, "attrs", {}).get("units", ""))
+
+    def _native_case_summary(self, case_dimension, partition, ds, train_ds, test_ds):
+        try:
+            ops = self._page_operands(partition, ds)
+            ranges = self._page_ranges(train_ds, test_ds)
+            (target, pred) = (self.output_variable, self.model_output_variable)
+            cases = case_pages.select_cases(int(ds[target].shape[0]), self.sample_count)
+            flip = self._flip_y(ds, target)      # the prediction and the error are drawn the way the target is
+            layers = []
+            for v in self.input_variables:
+                layers.append((v, *ranges[v], render_cases(ops[v], *ranges[v], cases=cases, flip_y=self._flip_y(ds, v))))
+            for v in (target, pred):
+                layers.append((v, *ranges[v], render_cases(ops[v], *ranges[v], cases=cases, flip_y=flip)))
+            error = case_pages.ERROR_LAYER
+            layers.append((error, *ranges[error],
+                           render_cases(ops[pred], *ranges[error], cases=cases, sub=ops[target], flip_y=flip)))
+            measures = {m: np.asarray(ds[m].values)[cases] for m in MEASURES}
+            (times, units) = self._case_times(ds, case_dimension, cases)
+            case_pages.write_case_pages(os.path.join(self.output_html_folder, partition), partition, cases, layers,
+                                        measures, times=times, time_units=units)
+            return True
+        except Exception as ex:
+            print("Unable to create case summary")
+            print(f"\t{type(ex).__name__}: {ex}")
             return False

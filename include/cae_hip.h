@@ -324,6 +324,33 @@ int cae_case_measures(const void* pred_dev, int pred_kind, int64_t pred_case_str
                       int actual_kind, int64_t actual_case_stride, int64_t n_case, int64_t plane, double* out_dev,
                       void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- case pages (stateless): evaluate_cae's per-case images of channel 0 ------------------- */
+
+/* Both calls read the first `plane` elements (channel 0) of cases that start at element i * src_case_stride of src_dev,
+ * in any CAE_ELEM_* kind and at any element alignment.  With sub_dev != NULL (kind and stride of its own) the value of
+ * an element is (double)src - (double)sub, formed in fp64; with sub_dev == NULL sub_kind and sub_case_stride are unused.
+ *
+ * Value range: out_dev[0..2] = {min, max, count} (doubles) over the finite values of n_case cases; NaN and +-Inf are
+ * left out; with no finite value {+inf, -inf, 0}.  min and max compare by value (a zero's sign is not decided).  No
+ * atomics: one partial per workgroup in workspace_dev (cae_case_range_workspace_bytes bytes, 8-byte aligned), then one
+ * folding workgroup; the same values from run to run. */
+int64_t cae_case_range_workspace_bytes(int64_t n_case, int64_t plane);
+int cae_case_range(const void* src_dev, int src_kind, int64_t src_case_stride, const void* sub_dev, int sub_kind,
+                   int64_t sub_case_stride, int64_t n_case, int64_t plane, double* out_dev, void* workspace_dev,
+                   int64_t workspace_bytes, void* hip_stream);
+
+/* Palette indices as PNG scanlines.  For k in [0, n_sel): case i = cases_dev[k] (int32 on the device; NULL: i = k) is
+ * written to out_dev[k][height][width + 1] (uint8, any byte alignment): byte 0 of a row is the PNG filter byte 0, byte
+ * 1 + x the index of pixel (y, x), read from source row y, or row height - 1 - y when flip_y != 0.  For a value v:
+ *   NaN -> 0;  otherwise t = (v - lo) / (hi - lo) clamped to [0, 1] (t = 0.5 when hi <= lo), index = 1 + (int)(t * 254.0 + 0.5)
+ * in fp64 with every operation rounded on its own (no fused multiply-add), so +Inf -> 255 and -Inf -> 1 when hi > lo.
+ * lo, hi and hi - lo must be finite; height * (width + 1) < 2^31.  A case index outside [0, n_case) draws index 0.
+ * Nothing outside the n_sel * height * (width + 1) bytes is written.  Traffic per image: plane elements read (once
+ * more for sub), plane + height bytes written. */
+int cae_render_cases(const void* src_dev, int src_kind, int64_t src_case_stride, const void* sub_dev, int sub_kind,
+                     int64_t sub_case_stride, const int32_t* cases_dev, int64_t n_sel, int64_t n_case, int64_t height,
+                     int64_t width, double lo, double hi, int flip_y, uint8_t* out_dev, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

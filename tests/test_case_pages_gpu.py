@@ -1,0 +1,369 @@
+"""The case pages on the GPU: cae_render_cases and cae_case_range against a numpy restatement of their definitions
+(include/cae_hip.h), byte for byte and value for value, for every element kind, alignment and shape class; then
+train_cae -> apply_cae -> evaluate_cae with the coordinate flags, every PNG of the pages decoded and compared."""
+import io
+import os
+import re
+import struct
+import zlib
+from contextlib import redirect_stdout
+
+import numpy as np
+import pytest
+import torch
+
+from cae_tools_amd import _lib
+from cae_tools_amd.engine import case_range, render_cases
+
+pytestmark = pytest.mark.gpu
+
+KINDS = {"f32": (_lib.ELEM_F32, "<f4"), "f32be": (_lib.ELEM_F32_BE, ">f4"), "f64": (_lib.ELEM_F64, "<f8"),
+         "f64be": (_lib.ELEM_F64_BE, ">f8")}
+
+
+# ---- the definitions, restated in numpy ------------------------------------------------------
+
+def np_values(src, sub=None):
+    """channel 0 in fp64, minus channel 0 of sub in fp64"""
+    v = np.asarray(src)[:, 0].astype(np.float64)
+    if sub is not None:
+        with np.errstate(invalid="ignore"):
+            v = v - np.asarray(sub)[:, 0].astype(np.float64)
+    return v
+
+
+def np_index(v, lo, hi):
+    """0 for NaN, else 1 + (int)(clamp((v - lo) / (hi - lo), 0, 1) * 254.0 + 0.5), every operation rounded on its own;
+    the middle level for every value when hi <= lo"""
+    v = np.asarray(v, dtype=np.float64)
+    nan = np.isnan(v)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if hi > lo:
+            t = (np.where(nan, lo, v) - lo) / (hi - lo)
+            t = np.minimum(np.maximum(t, 0.0), 1.0)
+        else:
+            t = np.full(v.shape, 0.5)
+        scaled = t * 254.0
+        idx = 1 + (scaled + 0.5).astype(np.int64)
+    return np.where(nan, 0, idx).astype(np.uint8)
+
+
+def np_scanlines(v, lo, hi, flip_y=False):
+    """(k, H, W) values -> (k, H, W + 1) PNG scanlines: filter byte 0, then the indices; flipped rows when asked"""
+    idx = np_index(v, lo, hi)
+    if flip_y:
+        idx = idx[:, ::-1]
+    out = np.zeros(idx.shape[:2] + (idx.shape[2] + 1,), dtype=np.uint8)
+    out[:, :, 1:] = idx
+    return out
+
+
+def np_range(v):
+    f = v[np.isfinite(v)]
+    return (float(f.min()), float(f.max()), int(f.size)) if f.size else (np.inf, -np.inf, 0)
+
+
+def _field(rng, shape, dtype):
+    """values in [0, 1) with a NaN, both infinities and an exact zero sprinkled in where there is room"""
+    a = rng.random(shape).astype(dtype)
+    flat = a.reshape(-1)
+    if flat.size >= 12:
+        flat[rng.integers(0, flat.size, 3)] = np.nan
+        flat[rng.integers(0, flat.size)] = np.inf
+        flat[rng.integers(0, flat.size)] = -np.inf
+        flat[rng.integers(0, flat.size)] = 0.0
+    return a
+
+
+def _pairs(rng, shape):
+    """(source, subtracted or None) operands as the host layer takes them, with their native numpy twins"""
+    n = 3
+    a32 = _field(rng, (n, 2) + shape, np.float32)
+    a64 = _field(rng, (n, 2) + shape, np.float64)
+    b32 = _field(rng, (n, 2) + shape, np.float32)
+    b64 = _field(rng, (n, 1) + shape, np.float64)       # the channel count may differ
+    be = lambda a: a.astype(a.dtype.newbyteorder(">"))  # noqa: E731
+    dev = lambda a: torch.from_numpy(a).cuda()          # noqa: E731
+    return [(a32, None, a32, None), (be(a32), None, a32, None), (a64, None, a64, None), (be(a64), None, a64, None),
+            (a32, be(b64), a32, b64), (be(a32), b32, a32, b32), (a64, be(b32), a64, b32), (be(a64), b64, a64, b64),
+            (dev(a64), be(b32), a64, b32), (dev(a32), dev(b64), a32, b64)]
+
+
+SHAPES = [(1, 1), (3, 5), (63, 64), (64, 63), (255, 257)]
+
+
+# ---- 1. render against numpy -----------------------------------------------------------------
+
+@pytest.mark.parametrize("flip_y", [False, True])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_render_matches_numpy(shape, flip_y):
+    rng = np.random.default_rng(shape[0] * 1000 + shape[1])
+    cases = [2, 0, 2, 1]
+    for (src, sub, src_np, sub_np) in _pairs(rng, shape):
+        (lo, hi) = (0.125, 0.9) if sub is None else (-0.6, 0.45)
+        v = np_values(src_np, sub_np)
+        got = render_cases(src, lo, hi, cases=cases, sub=sub, flip_y=flip_y)
+        assert got.dtype == np.uint8 and got.shape == (4, shape[0], shape[1] + 1)
+        np.testing.assert_array_equal(got, np_scanlines(v[cases], lo, hi, flip_y))
+        np.testing.assert_array_equal(render_cases(src, lo, hi, sub=sub, flip_y=flip_y), np_scanlines(v, lo, hi, flip_y))
+
+
+def test_render_in_groups(monkeypatch):
+    """more cases than one group holds: the groups' outputs land in order"""
+    from cae_tools_amd import engine
+    rng = np.random.default_rng(8)
+    a = rng.random((11, 1, 9, 6)).astype(np.float32)
+    monkeypatch.setattr(engine, "_RENDER_BYTES", 3 * 9 * 7 + 5)
+    np.testing.assert_array_equal(render_cases(a, 0.0, 1.0), np_scanlines(np_values(a), 0.0, 1.0))
+    with pytest.raises(IndexError):
+        render_cases(a, 0.0, 1.0, cases=[11])
+
+
+# ---- 2. unaligned operands through the C ABI -------------------------------------------------
+
+def _flat(rng, kind, off, n, stride):
+    """a flat buffer of `kind` on the host (native twin) and on the device"""
+    dtype = np.dtype(KINDS[kind][1])
+    native = rng.random(off + n * stride).astype(dtype.newbyteorder("="))
+    native[rng.integers(0, native.size, 2)] = np.nan
+    stored = native.astype(dtype)
+    return native, torch.from_numpy(stored.view(np.uint8)).cuda()
+
+
+def _cases_of(buf, off, stride, n, plane):
+    return np.stack([buf[off + i * stride: off + i * stride + plane] for i in range(n)]).astype(np.float64)
+
+
+@pytest.mark.parametrize("shape", [(3, 5), (63, 64), (64, 63)])
+@pytest.mark.parametrize("offsets", [(0, 1), (1, 3), (2, 2)])
+def test_unaligned_operands_and_output(shape, offsets):
+    lib = _lib.load()
+    rng = np.random.default_rng(shape[0] * 7 + offsets[0])
+    (h, w) = shape
+    (plane, n) = (h * w, 4)
+    (so, bo) = offsets
+    (ss, bs) = (plane + 2, plane + 3)
+    sel = np.array([3, 1, 1, 0], dtype=np.int32)
+    sel_dev = torch.from_numpy(sel).cuda()
+    size = len(sel) * h * (w + 1)
+    for (sk, bk) in (("f32", None), ("f32be", "f64"), ("f64", "f32be"), ("f32", "f32"), ("f64be", "f64be")):
+        (s_np, s_dev) = _flat(rng, sk, so, n, ss)
+        v = _cases_of(s_np, so, ss, n, plane)
+        (b_ptr, b_kind, b_stride, b_dev) = (None, 0, 0, None)
+        if bk is not None:
+            (b_np, b_dev) = _flat(rng, bk, bo, n, bs)
+            v = v - _cases_of(b_np, bo, bs, n, plane)
+            (b_ptr, b_kind, b_stride) = (b_dev.data_ptr() + bo * b_np.itemsize, KINDS[bk][0], bs)
+        (lo, hi) = (0.1, 0.8) if bk is None else (-0.7, 0.7)
+        s_ptr = s_dev.data_ptr() + so * s_np.itemsize
+        want = np_scanlines(v[sel].reshape(len(sel), h, w), lo, hi, True).tobytes()
+        for out_off in range(4):
+            out = torch.full((size + 64,), 0xAA, dtype=torch.uint8, device="cuda")
+            _lib.check(lib.cae_render_cases(s_ptr, KINDS[sk][0], ss, b_ptr, b_kind, b_stride, sel_dev.data_ptr(), len(sel),
+                                            n, h, w, lo, hi, 1, out.data_ptr() + 16 + out_off, None))
+            got = out.cpu().numpy().tobytes()
+            (a, z) = (16 + out_off, 16 + out_off + size)
+            assert got[:a] == b"\xaa" * a and got[z:] == b"\xaa" * (len(got) - z)
+            assert got[a:z] == want
+        # the value range of the same operands
+        res = torch.empty(3, dtype=torch.float64, device="cuda")
+        need = int(lib.cae_case_range_workspace_bytes(n, plane))
+        ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+        _lib.check(lib.cae_case_range(s_ptr, KINDS[sk][0], ss, b_ptr, b_kind, b_stride, n, plane, res.data_ptr(),
+                                      ws.data_ptr(), need, None))
+        assert tuple(res.cpu().tolist()) == np_range(v)
+
+
+def test_null_case_list_and_bad_arguments():
+    lib = _lib.load()
+    a = np.random.default_rng(1).random((3, 1, 4, 5))
+    dev = torch.from_numpy(a).cuda()
+    out = torch.zeros(3 * 4 * 6, dtype=torch.uint8, device="cuda")
+    _lib.check(lib.cae_render_cases(dev.data_ptr(), _lib.ELEM_F64, 20, None, 0, 0, None, 3, 3, 4, 5, 0.0, 1.0, 0,
+                                    out.data_ptr(), None))
+    np.testing.assert_array_equal(out.cpu().numpy().reshape(3, 4, 6), np_scanlines(a[:, 0], 0.0, 1.0))
+    for (lo, hi) in ((np.nan, 1.0), (0.0, np.inf), (-1.7e308, 1.7e308)):
+        assert lib.cae_render_cases(dev.data_ptr(), _lib.ELEM_F64, 20, None, 0, 0, None, 3, 3, 4, 5, lo, hi, 0,
+                                    out.data_ptr(), None) < 0
+    assert lib.cae_render_cases(dev.data_ptr(), _lib.ELEM_F64, 19, None, 0, 0, None, 3, 3, 4, 5, 0.0, 1.0, 0,
+                                out.data_ptr(), None) < 0
+
+
+# ---- 3. level boundaries ---------------------------------------------------------------------
+
+@pytest.mark.parametrize("lo,hi", [(0.0, 1.0), (-3.7, 11.3), (288.1, 293.4), (-1e-3, 1e-3), (1.0, 1e9)])
+def test_level_boundaries(lo, hi):
+    """values at, just below and just above every boundary between two levels, and every level's centre: equal to numpy
+    index for index.  The kernel keeps t * 254.0 and + 0.5 apart as numpy does; a search over the doubles around
+    (0.5 - 2^-54) / 254, the one place where fusing them could round differently, found no t that tells the two apart,
+    so this pins the division, the clamp and the truncation rather than the contraction."""
+    k = np.arange(254, dtype=np.float64)
+    edge = lo + (k + 0.5) / 254.0 * (hi - lo)
+    extra = [lo, hi, np.nextafter(lo, -np.inf), np.nextafter(lo, np.inf), np.nextafter(hi, -np.inf),
+             np.nextafter(hi, np.inf), lo - 1.0, hi + 1.0, np.nan, np.inf, -np.inf, 0.0, -0.0]
+    centre = lo + np.arange(255, dtype=np.float64) / 254.0 * (hi - lo)
+    row = np.concatenate([edge, np.nextafter(edge, -np.inf), np.nextafter(edge, np.inf), centre, np.array(extra)])
+    src = row.reshape(1, 1, 1, -1)
+    want = np_scanlines(src[:, 0], lo, hi)
+    assert len(set(want.reshape(-1).tolist())) == 256          # every index occurs
+    np.testing.assert_array_equal(render_cases(src, lo, hi), want)
+    np.testing.assert_array_equal(render_cases(src.astype(">f8"), lo, hi), want)
+    # the same row as a difference: src = row + b in fp64 is not row again, numpy follows the same roundings
+    b = np.full(src.shape, 0.3, dtype=np.float32)
+    shifted = src + b.astype(np.float64)
+    np.testing.assert_array_equal(render_cases(shifted, lo, hi, sub=b), np_scanlines(np_values(shifted, b), lo, hi))
+    for (l2, h2) in ((lo, lo), (hi, lo)):                     # hi <= lo: the middle level for all but NaN
+        got = render_cases(src, l2, h2)
+        np.testing.assert_array_equal(got, np_scanlines(src[:, 0], l2, h2))
+        assert set(got[0, 0, 1:].tolist()) == {0, 128}
+
+
+# ---- 4. the value range ----------------------------------------------------------------------
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_range_matches_numpy(shape):
+    rng = np.random.default_rng(shape[0] * 31 + shape[1])
+    for (src, sub, src_np, sub_np) in _pairs(rng, shape):
+        v = np_values(src_np, sub_np)
+        assert case_range(src, sub=sub) == np_range(v)
+
+
+def test_range_of_nothing_finite():
+    a = np.full((2, 2, 5, 7), np.nan, dtype=np.float32)
+    a[:, 1] = 3.0                                             # channel 1 is not looked at
+    assert case_range(a) == (np.inf, -np.inf, 0)
+    a[1, 0, 2, 3] = np.inf
+    assert case_range(a) == (np.inf, -np.inf, 0)
+    a[1, 0, 4, 6] = -2.5
+    assert case_range(a) == (-2.5, -2.5, 1)
+
+
+def test_range_of_seventy_thousand_cases_twice():
+    rng = np.random.default_rng(70000)
+    a = rng.standard_normal((70000, 1, 4, 4))
+    b = rng.standard_normal((70000, 2, 4, 4)).astype(np.float32)
+    (ad, bd) = (torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda())
+    first = case_range(ad, sub=bd)
+    assert first == np_range(np_values(a, b))
+    assert case_range(ad.clone(), sub=bd.clone()) == first
+    big = rng.random((40, 1, 256, 256)).astype(np.float32)   # several chunks per case
+    assert case_range(big) == np_range(np_values(big)) == case_range(big.astype(">f4"))
+
+
+# ---- 5. train_cae -> apply_cae -> evaluate_cae with case pages --------------------------------
+
+def _decode_png(data):
+    """(width, height, scanline bytes) of an 8-bit palette PNG; every chunk's CRC is checked"""
+    assert data[:8] == b"\x89PNG\r\n\x1a\n"
+    (at, chunks) = (8, {})
+    while at < len(data):
+        (length,) = struct.unpack_from(">I", data, at)
+        (kind, body) = (data[at + 4:at + 8], data[at + 8:at + 8 + length])
+        assert struct.unpack_from(">I", data, at + 8 + length)[0] == zlib.crc32(kind + body) & 0xFFFFFFFF
+        chunks[kind] = body
+        at += 12 + length
+    (width, height, depth, colour) = struct.unpack(">IIBB", chunks[b"IHDR"][:10])
+    assert (depth, colour) == (8, 3) and len(chunks[b"PLTE"]) == 768 and chunks[b"tRNS"][0] == 0
+    return width, height, zlib.decompress(chunks[b"IDAT"])
+
+
+@pytest.fixture(scope="module")
+def data(tmp_path_factory):
+    """12 circle cases per partition with a time variable over the case dimension and ascending y / x coordinates"""
+    from cae_tools_amd.data import datagen
+    from cae_tools_amd.data.arrays import DataArray
+    root = tmp_path_factory.mktemp("case_pages")
+    paths = {}
+    for (part, seed) in (("train", 1234), ("test", 4321)):
+        ds = datagen.generate("circle", 12, seed=seed)
+        ds["time"] = DataArray(np.arange(12, dtype=np.float64) * 0.5 + 100.0, dims=("n",), attrs={"units": "days since 2000-01-01"})
+        ds["y"] = DataArray(np.linspace(50.0, 60.0, 256), dims=("y2",))
+        ds["x"] = DataArray(np.linspace(-5.0, 5.0, 256), dims=("x2",))
+        paths[part] = str(root / f"{part}.nc")
+        ds.to_netcdf(paths[part])
+    return root, paths
+
+
+def _check_pages(folder, partition, parts, n_rows):
+    """the pages of `partition` under `folder` against the restatement.  parts: {partition: (lowres, hires, prediction)}
+    as (N, C, H, W) arrays; ranges go over all partitions given"""
+    with open(os.path.join(folder, "index.html")) as f:
+        assert f'href="{partition}/index.html"' in f.read()
+    with open(os.path.join(folder, partition, "index.html")) as f:
+        page = f.read()
+    finite = lambda arrays: np_range(np.concatenate([np_values(a).reshape(-1) for a in arrays]))[:2]   # noqa: E731
+    ranges = {"lowres": finite([p[0] for p in parts.values()]),
+              "hires": finite([a for p in parts.values() for a in p[1:]])}
+    ranges["model_output"] = ranges["hires"]
+    bound = max(float(np.abs(np_values(p[2], p[1])).max()) for p in parts.values())
+    ranges["error"] = (-bound, bound)
+    (lowres, hires, pred) = parts[partition]
+    values = {"lowres": np_values(lowres), "hires": np_values(hires), "model_output": np_values(pred),
+              "error": np_values(pred, hires)}
+    flips = {"lowres": False, "hires": True, "model_output": True, "error": True}   # y ascends along y2 only
+    assert re.findall(r'data-layer="([^"]+)"', page) == ["lowres", "hires", "model_output", "error"]
+    n = hires.shape[0]
+    cases = [i * n // n_rows for i in range(n_rows)]
+    mse = (values["error"] ** 2).mean(axis=(1, 2))
+    want_order = sorted(cases, key=lambda c: (-mse[c], c))
+    assert [int(c) for c in re.findall(r'<tr class="case" data-case="(\d+)"', page)] == want_order
+    assert "days since 2000-01-01" in page
+    for c in cases:
+        assert f"<td>{100.0 + 0.5 * c:.15g}</td>" in page
+        for (layer, v) in values.items():
+            name = f"images/case{c:06d}_{layer}.png"
+            assert f'src="{name}"' in page
+            with open(os.path.join(folder, partition, name), "rb") as f:
+                (w, h, raw) = _decode_png(f.read())
+            assert (h, w) == v.shape[1:]
+            assert raw == np_scanlines(v[c:c + 1], *ranges[layer], flips[layer]).tobytes(), (c, layer)
+    assert len(os.listdir(os.path.join(folder, partition, "images"))) == 4 * n_rows + 1      # and the colour bar
+
+
+@pytest.mark.parametrize("method", ["conv", "linear"])
+def test_train_apply_evaluate_case_pages(data, method):
+    from cae_tools_amd.cli import apply_cae, evaluate_cae, train_cae
+    from cae_tools_amd.data.arrays import open_dataset
+    from cae_tools_amd.models.model_evaluator import ModelEvaluator
+    (root, paths) = data
+    model = str(root / f"model_{method}")
+    scored = str(root / f"scored_{method}.nc")
+    torch.manual_seed(0)
+    with redirect_stdout(io.StringIO()):
+        train_cae.main(["--train-inputs", paths["train"], "--test-inputs", paths["test"], "--model-folder", model,
+                        "--input-variables", "lowres", "--output-variable", "hires", "--method", method, "--nr-epochs", "2",
+                        "--batch-size", "6", "--latent-size", "4", "--fc-size", "16"])
+        apply_cae.main([paths["test"], scored, "--model-folder", model])
+    coords = ["--x-coordinate", "x", "--y-coordinate", "y", "--time-coordinate", "time"]
+
+    # the scored file: the prediction is read from it
+    out1 = str(root / f"report_{method}_scored")
+    log = io.StringIO()
+    with redirect_stdout(log):
+        evaluate_cae.main(["--test-inputs", scored, "--model-folder", model, "--output-html-folder", out1,
+                           "--input-variables", "lowres", "--sample-count", "5"] + coords)
+    assert "Unable to create case summary" not in log.getvalue()
+    sds = open_dataset(scored)
+    test = tuple(np.asarray(sds[v].values) for v in ("lowres", "hires", "model_output"))
+    _check_pages(out1, "test", {"test": test}, 5)
+
+    # both partitions unscored: the evaluator applies the model and draws the prediction where it lies on the GPU
+    out2 = str(root / f"report_{method}_apply")
+    log = io.StringIO()
+    with redirect_stdout(log):
+        ev = ModelEvaluator([paths["train"]], [paths["test"]], output_html_folder=out2, model_path=model,
+                            input_variables=["lowres"], sample_count=5, x_coordinate="x", y_coordinate="y",
+                            time_coordinate="time")
+        (case_dimension, train_ds, test_ds, metrics) = ev.evaluate_model_metrics()
+        ev.build_html(case_dimension, train_ds, test_ds, metrics)
+    assert "Unable to create case summary" not in log.getvalue() and "Applying model to generate test scores" in log.getvalue()
+    parts = {p: tuple(np.asarray(d[v].values) for v in ("lowres", "hires", "model_output"))
+             for (p, d) in (("train", train_ds), ("test", test_ds))}
+    _check_pages(out2, "test", parts, 5)
+    _check_pages(out2, "train", parts, 5)
+
+    # without the coordinate flags no case pages are made
+    out3 = str(root / f"report_{method}_plain")
+    with redirect_stdout(io.StringIO()):
+        evaluate_cae.main(["--test-inputs", scored, "--model-folder", model, "--output-html-folder", out3])
+    assert not os.path.exists(os.path.join(out3, "test"))
