@@ -182,6 +182,7 @@ SIGNATURES = {
     "lin_loss_slots": (C.c_int, [_P]),
     "lin_read_losses": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "lin_sync": (C.c_int, [_P]),
+    "lin_debug_plan": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p, C.c_int64]),
 }
 
 _lib = None

@@ -582,21 +582,34 @@ inline void igemm_launch(const Op& op, dim3 grid, hipStream_t s) {
     hipLaunchKernelGGL((k_igemm<WN, WM, Op>), grid, dim3(64 * WN * WM), bytes, s, op);
 }
 
-// tile shape by row count: 32 x 512, 64 x 256 or 128 x 128
+// tile shape by row count: 32 x 512, 64 x 256 or 128 x 128 (wn x wm waves of 32 x 128 each).  The one place that decides it:
+// igemm_dispatch launches what this returns and the engines' plan reports print it
+struct IgemmTile {
+    int wn, wm;
+    int tn() const { return 32 * wn; }
+    int tm() const { return 128 * wm; }
+};
+inline IgemmTile igemm_tile(int rows) { return rows <= 32 ? IgemmTile{1, 4} : rows <= 64 ? IgemmTile{2, 2} : IgemmTile{4, 1}; }
+inline dim3 igemm_grid(const IgemmTile& t, int rows, long long cols, int zdim) {
+    return dim3((unsigned)((cols + t.tm() - 1) / t.tm()), (unsigned)((rows + t.tn() - 1) / t.tn()), (unsigned)zdim);
+}
+
 template <template <int> class OpT, class Fill>
 inline void igemm_dispatch(int rows, long long cols, int zdim, hipStream_t s, Fill fill) {
-    if (rows <= 32) {
+    const IgemmTile t = igemm_tile(rows);
+    const dim3 grid = igemm_grid(t, rows, cols, zdim);
+    if (t.wn == 1) {
         OpT<4> op;
         fill(op);
-        igemm_launch<1, 4>(op, dim3((unsigned)((cols + 511) / 512), (rows + 31) / 32, zdim), s);
-    } else if (rows <= 64) {
+        igemm_launch<1, 4>(op, grid, s);
+    } else if (t.wn == 2) {
         OpT<2> op;
         fill(op);
-        igemm_launch<2, 2>(op, dim3((unsigned)((cols + 255) / 256), (rows + 63) / 64, zdim), s);
+        igemm_launch<2, 2>(op, grid, s);
     } else {
         OpT<1> op;
         fill(op);
-        igemm_launch<4, 1>(op, dim3((unsigned)((cols + 127) / 128), (rows + 127) / 128, zdim), s);
+        igemm_launch<4, 1>(op, grid, s);
     }
 }
 
@@ -751,8 +764,8 @@ struct GemmDesc {
 
 // K slices of a store-0 GEMM through gemm_launch (1: K is not split) and the ksplit chunks each: few tiles and a long K
 inline int gemm_slices(int rows, int cols, int K, int* per_out = nullptr) {
-    const int TN = rows <= 32 ? 32 : rows <= 64 ? 64 : 128, TM = rows <= 32 ? 512 : rows <= 64 ? 256 : 128;
-    const long long tiles = (long long)((rows + TN - 1) / TN) * ((cols + TM - 1) / TM);
+    const dim3 grid = igemm_grid(igemm_tile(rows), rows, cols, 1);
+    const long long tiles = (long long)grid.y * grid.x;
     const int chunks = (K + IG_KC - 1) / IG_KC;
     int zdim = 1, per = chunks;
     if (tiles < 256 && chunks >= 64) {
@@ -770,23 +783,43 @@ inline size_t gemm_part_bytes(int rows, int cols, int K) {
     return zdim > 1 ? (size_t)zdim * rows * cols * sizeof(float) : 0;
 }
 
+// what gemm_launch runs for a GEMM of this shape and store mode, given part_room bytes for partial tiles (have_part: there is
+// such a buffer): the tile, the grid (x column tiles, y row tiles, z K slices), the chunks per slice and the bytes of partial
+// tiles written (0: K is not split).  gemm_launch launches from this; lin_debug_plan prints it
+struct GemmPlan {
+    IgemmTile tile;
+    dim3 grid;
+    int slices, per;
+    size_t part_bytes;
+};
+inline GemmPlan gemm_plan(int rows, int cols, int K, int mode, bool have_part, size_t part_room) {
+    GemmPlan p;
+    p.slices = gemm_slices(rows, cols, K, &p.per);
+    if (mode != 0 || !have_part || gemm_part_bytes(rows, cols, K) > part_room) p.slices = 1, p.per = (K + IG_KC - 1) / IG_KC;
+    p.part_bytes = p.slices > 1 ? gemm_part_bytes(rows, cols, K) : 0;
+    p.tile = igemm_tile(rows);
+    p.grid = igemm_grid(p.tile, rows, cols, p.slices);
+    return p;
+}
+inline GemmPlan gemm_plan(const GemmDesc& d, bool have_part, size_t part_room) {
+    return gemm_plan(d.rows, d.cols, d.K, d.mode, have_part, part_room);
+}
+
 // part: part_bytes of room for the K slices' partial tiles, or nullptr.  K is split only when they fit (gemm_part_bytes); the
 // engines size the buffer from their plan so that they always do
 inline void gemm_launch(const GemmDesc& d, float* part, size_t part_bytes, hipStream_t s) {
-    int per = 0;
-    int zdim = gemm_slices(d.rows, d.cols, d.K, &per);
-    if (d.mode != 0 || !part || gemm_part_bytes(d.rows, d.cols, d.K) > part_bytes) zdim = 1, per = (d.K + IG_KC - 1) / IG_KC;
-    const bool split = zdim > 1;
-    igemm_dispatch<OpGemm>(d.rows, d.cols, zdim, s, [&](auto& op) {
+    const GemmPlan p = gemm_plan(d, part != nullptr, part_bytes);
+    const bool split = p.slices > 1;
+    igemm_dispatch<OpGemm>(d.rows, d.cols, p.slices, s, [&](auto& op) {
         op.nrows = d.rows, op.ncols = d.cols, op.K = d.K;
         op.a = d.a, op.a_sn = d.a_sn, op.a_sk = d.a_sk;
         op.b = d.b, op.b_sk = d.b_sk, op.b_sm = d.b_sm;
         op.bias = d.bias, op.out = d.out, op.accd = d.accd, op.part = part;
         op.o_sn = d.o_sn, op.o_sm = d.o_sm;
-        op.mode = split ? 1 : d.mode, op.ksplit = per;
+        op.mode = split ? 1 : d.mode, op.ksplit = p.per;
     });
     if (split)
-        hipLaunchKernelGGL(k_gemm_finish, dim3((d.rows * d.cols + 255) / 256), dim3(256), 0, s, d.rows, d.cols, zdim, part,
+        hipLaunchKernelGGL(k_gemm_finish, dim3((d.rows * d.cols + 255) / 256), dim3(256), 0, s, d.rows, d.cols, p.slices, part,
                            d.bias, d.out, d.o_sn, d.o_sm);
 }
 

@@ -708,13 +708,16 @@ __global__ void __launch_bounds__(256) k_adam_l2(long long n, float* __restrict_
     }
     __syncthreads();
     const float step_size = corr[0], bc2_sqrt = corr[1];
-    const float b1 = (float)h.beta1, b2 = (float)h.beta2, eps = (float)h.eps, wd = (float)h.wd;
+    const float b2 = (float)h.beta2, eps = (float)h.eps, wd = (float)h.wd;
+    // 1 - beta in fp64, rounded once, as the reference's scalars are: 1.f - (float)0.999 is 1.3e-5 short of 0.001, which moved
+    // every update by 6e-6 of its size, all weights the same way
+    const float omb1 = (float)(1.0 - h.beta1), omb2 = (float)(1.0 - h.beta2);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const float w = p[i];
         const float g = fmaf(wd, w, (float)gacc[i]);      // grad = grad.add(param, alpha=weight_decay)
         gacc[i] = 0.0;
-        const float mi = m[i] + (g - m[i]) * (1.f - b1);
-        const float vi = fmaf(g * g, 1.f - b2, v[i] * b2);
+        const float mi = m[i] + (g - m[i]) * omb1;
+        const float vi = fmaf(g * g, omb2, v[i] * b2);
         p[i] = w - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
         m[i] = mi;
         v[i] = vi;

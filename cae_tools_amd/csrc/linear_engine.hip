@@ -4,6 +4,8 @@
 
 #include <algorithm>
 #include <cstdio>
+#include <cstring>
+#include <string>
 
 #include "cae_linear.h"
 #include "kernels_unet.h"
@@ -51,9 +53,20 @@ struct lin_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets, 
 
 namespace {
 
+// The two GEMM shapes of a step.  forward() and step_common() launch these descriptors and lin_debug_plan reports the plan of
+// the same ones (with null operands: a plan depends on the shape and the store mode alone)
+// y[b][o] = bias[o] + sum_i x[b][i] W[o][i]
+GemmDesc fwd_gemm(const lin_engine* e, const float* x, int B, float* y) {
+    const float* W = e->params;
+    return GemmDesc{(int)e->nout, B, (int)e->nin, W, e->nin, 1, x, 1, e->nin, W ? W + e->nout * e->nin : nullptr, y, nullptr, 1, e->nout, 0};
+}
+// dW[o][i] = sum_b g[b][o] x[b][i]
+GemmDesc wgrad_gemm(const lin_engine* e, int batch, const float* g, const float* xb, double* acc) {
+    return GemmDesc{(int)e->nout, (int)e->nin, batch, g, 1, e->nout, xb, e->nin, 1, nullptr, nullptr, acc, e->nin, 1, 2};
+}
+
 int forward(lin_engine* e, const float* x, int B, float* y) {
-    // y[b][o] = bias[o] + sum_i x[b][i] W[o][i]
-    GemmDesc d{(int)e->nout, B, (int)e->nin, e->params, e->nin, 1, x, 1, e->nin, e->params + e->nout * e->nin, y, nullptr, 1, e->nout, 0};
+    const GemmDesc d = fwd_gemm(e, x, B, y);
     gemm_launch(d, reinterpret_cast<float*>(e->ws + e->off_gpart), e->gpart_bytes, e->stream);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
@@ -72,8 +85,8 @@ int step_common(lin_engine* e, int which, const int32_t* perm, int64_t start, in
     if (train) {
         if (!e->gacc_clean) HIP_TRY(hipMemsetAsync(e->gacc(), 0, (size_t)e->n_params * sizeof(double), e->stream));
         e->gacc_clean = false;
-        // dW[o][i] = sum_b g[b][o] x[b][i];  db[o] = sum_b g[b][o]
-        GemmDesc w{(int)e->nout, (int)e->nin, batch, e->g(), 1, e->nout, e->xb(), e->nin, 1, nullptr, nullptr, e->gacc(), e->nin, 1, 2};
+        // dW through the tile engine;  db[o] = sum_b g[b][o]
+        const GemmDesc w = wgrad_gemm(e, batch, e->g(), e->xb(), e->gacc());
         gemm_launch(w, nullptr, 0, e->stream);
         hipLaunchKernelGGL(k_col_sums, dim3((unsigned)((e->nout + 255) / 256)), dim3(256), 0, e->stream, batch, (int)e->nout, e->g(),
                            e->gacc() + e->nout * e->nin);
@@ -165,5 +178,31 @@ int lin_score(lin_engine* e, const float* x, int batch, float* y) {
 int lin_loss_slots(const lin_engine* e) { return e ? kStepLossSlots : 0; }
 int lin_read_losses(lin_engine* e, int first_slot, int count, double* out) { return read_losses(e, "lin", first_slot, count, out); }
 int lin_sync(lin_engine* e) { return sync(e, "lin"); }
+
+int lin_debug_plan(const lin_engine* e, int batch, int train, char* out, int64_t out_bytes) {
+    if (!e || !out || out_bytes < 1) return fail(CAE_ERR_ARG, "lin_debug_plan: bad argument");
+    if (batch < 1 || batch > e->max_batch) return fail(CAE_ERR_ARG, "lin_debug_plan: batch %d outside 1 .. %d", batch, e->max_batch);
+    auto tile = [](const GemmPlan& p) { return std::to_string(p.tile.tn()) + "x" + std::to_string(p.tile.tm()); };
+    std::string s;
+    char line[256];
+    // forward(): the K slices go to gpart, which a bound engine always has (lin_engine_create sized it)
+    const GemmPlan f = gemm_plan(fwd_gemm(e, nullptr, batch, nullptr), true, (size_t)e->gpart_bytes);
+    snprintf(line, sizeof line, "fwd tile=%s grid=%ux%u slices=%d per=%d part_bytes=%zu\n", tile(f).c_str(), f.grid.x, f.grid.y, f.slices,
+             f.per, f.part_bytes);
+    s += line;
+    if (train) {   // step_common(): no room for partial tiles, one writer per element of the fp64 accumulator
+        const GemmPlan w = gemm_plan(wgrad_gemm(e, batch, nullptr, nullptr, nullptr), false, 0);
+        snprintf(line, sizeof line, "wgrad tile=%s grid=%ux%u slices=%d\n", tile(w).c_str(), w.grid.x, w.grid.y, w.slices);
+    } else {
+        snprintf(line, sizeof line, "wgrad -\n");
+    }
+    s += line;
+    snprintf(line, sizeof line, "room gpart_bytes=%lld\n", (long long)e->gpart_bytes);
+    s += line;
+    if ((int64_t)s.size() + 1 > out_bytes)
+        return fail(CAE_ERR_ARG, "lin_debug_plan: the report needs %zu bytes, got %lld", s.size() + 1, (long long)out_bytes);
+    memcpy(out, s.c_str(), s.size() + 1);
+    return CAE_OK;
+}
 
 }  // extern "C"

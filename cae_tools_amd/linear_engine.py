@@ -1,4 +1,5 @@
 """LinearEngine — Python owner of one libcae_hip LinearModel engine (include/cae_linear.h)."""
+import ctypes as C
 from collections import OrderedDict
 
 import numpy as np
@@ -9,18 +10,38 @@ from ._engine_base import TEST, TRAIN, EngineBase, SteppedEngine, require_gpu  #
 from ._lib import CaeError, check
 
 
-class LinearEngine(SteppedEngine, EngineBase):
+class LinearPlan(EngineBase):
+    """geometry-only view (no GPU needed): parameter count, workspace size and the launches of a step"""
 
     PREFIX = "lin_"
-    RUNNING_STATS = False
 
-    def __init__(self, in_shape, out_shape, max_batch, device=None):
-        require_gpu()
+    def __init__(self, in_shape, out_shape, max_batch):
         self.lib = _lib.load()
         self.in_shape, self.out_shape = tuple(int(v) for v in in_shape), tuple(int(v) for v in out_shape)
         self.nin, self.nout, self.max_batch = int(np.prod(self.in_shape)), int(np.prod(self.out_shape)), int(max_batch)
         self._create(self.nin, self.nout, self.max_batch)
         self.workspace_bytes = int(self.lib.lin_workspace_bytes(self.handle))
+
+    def kernel_plan(self, batch, train):
+        """the GEMM launches of a step at this batch (lin_debug_plan, include/cae_linear.h), no GPU needed:
+        {"fwd": {"tile": "32x512", "grid": "2x1", "slices": "5", "per": "16", "part_bytes": "312000"},
+         "wgrad": {"tile": "32x512", "grid": "3x1", "slices": "1"} ({} for an eval step), "room": {"gpart_bytes": "312000"}}"""
+        buf = C.create_string_buffer(1 << 10)
+        check(self.lib.lin_debug_plan(self.handle, int(batch), 1 if train else 0, buf, len(buf)))
+        plan = {}
+        for line in buf.value.decode().splitlines():
+            (name, *fields) = line.split()
+            plan[name] = dict(f.split("=", 1) for f in fields if f != "-")
+        return plan
+
+
+class LinearEngine(SteppedEngine, LinearPlan):
+
+    RUNNING_STATS = False
+
+    def __init__(self, in_shape, out_shape, max_batch, device=None):
+        require_gpu()
+        super().__init__(in_shape, out_shape, max_batch)
         self._bind(device)
         torch.cuda.synchronize(self.device)
         self._start()

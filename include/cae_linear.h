@@ -47,6 +47,15 @@ int lin_score(lin_engine* e, const float* x_dev, int batch, float* y_dev);
 int lin_loss_slots(const lin_engine* e);
 int lin_read_losses(lin_engine* e, int first_slot, int count, double* out_host);
 int lin_sync(lin_engine* e);
+/* Test hook, no GPU and no bound workspace needed: the launches of a step at this batch (1 .. max_batch), from the same tile
+ * choice and K-split rule the launch code runs (igemm_tile / gemm_plan in kernels_unet_mfma.h), as text lines
+ *   fwd tile=<32x512|64x256|128x128> grid=<column tiles>x<row tiles> slices=<K slices> per=<16-wide K chunks per slice> part_bytes=<n>
+ *   wgrad tile=... grid=... slices=1                      (train != 0; "wgrad -" otherwise)
+ *   room gpart_bytes=<n>
+ * part_bytes: the partial tiles the forward's K slices write before k_gemm_finish folds them in slice order (0: K is not
+ * split); gpart_bytes: the room the workspace holds for them, sized at creation over every batch 1 .. max_batch.  Fails for a
+ * batch outside 1 .. max_batch or a buffer too short for the report. */
+int lin_debug_plan(const lin_engine* e, int batch, int train, char* out_host, int64_t out_bytes);
 
 #ifdef __cplusplus
 }
