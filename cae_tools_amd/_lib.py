@@ -103,6 +103,9 @@ SIGNATURES = {
                                  _P]),
     "cae_render_cases": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64,
                                    C.c_int64, C.c_double, C.c_double, C.c_int, _P, _P]),
+    "cae_ensemble_moments_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "cae_ensemble_moments": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double,
+                                       C.c_double, _P, _P, _P, C.c_int64, _P]),
     # ---- include/cae_unet.h ----
     "unet_engine_create": (C.c_int, [C.POINTER(LayerSpecC), C.c_int, C.POINTER(LayerSpecC), C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.POINTER(C.c_void_p)]),
@@ -155,6 +158,9 @@ SIGNATURES = {
     "vae_apply_gradients": (C.c_int, [_P, _P]),
     "vae_eval_step": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int]),
     "vae_score": (C.c_int, [_P, _P, C.c_int, _P]),
+    "vae_encode": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "vae_decode": (C.c_int, [_P, _P, C.c_int, _P]),
+    "vae_sample_latent": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_uint32, _P]),
     "vae_loss_slots": (C.c_int, [_P]),
     "vae_read_losses": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "vae_sync": (C.c_int, [_P]),

@@ -2,6 +2,7 @@
 (src/cae_tools/cli/apply_cae.py:28-90): load a model folder, score the input file(s) on the GPU,
 write inputs + the denormalised prediction variable to a NetCDF file."""
 import argparse
+import json
 import os
 
 import numpy as np
@@ -20,11 +21,39 @@ def build_parser():
                    default="model_output")
     p.add_argument("--mask-variable", type=str, help="name of the mask variable", default=None)
     p.add_argument("--gpus", type=int, default=1, help="build-only: shard the cases over this many GPUs of the node")
+    p.add_argument("--ensemble-size", type=int, default=None, metavar="K",
+                   help="build-only, --method var models: decode K sampled latents per case and store their per-pixel mean")
+    p.add_argument("--spread-variable", default=None, metavar="NAME",
+                   help="with --ensemble-size K >= 2: also store the per-pixel standard deviation of the K fields under NAME")
+    p.add_argument("--ensemble-seed", type=int, default=0, metavar="S", help="seed of the ensemble's noise")
+    p.add_argument("--latent-variable", default=None, metavar="NAME",
+                   help="--method var models: also store the latent mean and log-variance as NAME_mu and NAME_logvar")
     return p
+
+
+def ensemble_keywords(args):
+    """the VarAEModel.apply keywords the command line asks for (empty: the plain apply).  They need a VarAEModel folder:
+    parameters.json is read here, before any rank is spawned or the GPU touched, and anything else is refused."""
+    asked = {k: v for k, v in (("ensemble_size", args.ensemble_size), ("spread_variable", args.spread_variable),
+                               ("latent_variable", args.latent_variable)) if v is not None}
+    if not asked and not args.ensemble_seed:
+        return {}
+    with open(os.path.join(args.model_folder, "parameters.json")) as f:
+        model_type = json.load(f).get("type")
+    if model_type != "VarAEModel":
+        raise SystemExit("--ensemble-size / --spread-variable / --ensemble-seed / --latent-variable need a VarAEModel folder "
+                         f"(the VAE, train_cae --method var): {args.model_folder} holds a {model_type}")
+    if args.spread_variable is not None and (args.ensemble_size is None or args.ensemble_size < 2):
+        raise SystemExit("--spread-variable needs --ensemble-size K with K >= 2")
+    if args.ensemble_size is not None and args.ensemble_size < 1:
+        raise SystemExit("--ensemble-size must be at least 1")
+    asked["ensemble_seed"] = args.ensemble_seed
+    return asked
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    ensemble = ensemble_keywords(args)
     from ._launch import maybe_spawn_ranks
     rc = maybe_spawn_ranks("cae_tools_amd.cli.apply_cae", args.gpus, argv)   # before anything touches the GPU
     if rc is not None:
@@ -54,7 +83,7 @@ def main(argv=None):
             score_ds[var] = DataArray(np.broadcast_to(vals[:, None, None, None], (vals.shape[0], 1, y_dim, x_dim)).copy(),
                                       dims=(case_dimension, "channel", "y", "x"))
     print("Applying model for %d cases" % score_ds[case_dimension].shape[0])
-    mt.apply(score_ds, input_variable_names, args.prediction_variable, mask_variable_name=args.mask_variable)
+    mt.apply(score_ds, input_variable_names, args.prediction_variable, mask_variable_name=args.mask_variable, **ensemble)
     if int(os.environ.get("RANK", "0")) == 0:       # every rank holds all predictions (all-gather); rank 0 writes
         score_ds.to_netcdf(args.output_path)
 

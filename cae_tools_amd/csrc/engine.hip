@@ -1140,7 +1140,7 @@ int launch_forward(cae_engine* e, const StepArgs& a) {
                                    e->params + F.b_off, F.relu ? 1 : 0, e->fptr(F.act_off));
             }
             in = e->fptr(F.act_off);
-            if (i == 1 && e->variational) {   // heads -> z (trunk_api.h)
+            if (i == 1 && e->variational && a.part != 1) {   // heads -> z (trunk_api.h; trunk_encode hands out the heads themselves)
                 if (!e->hooks.reparam) return fail(CAE_ERR_STATE, "trunk engine without a reparameterisation hook");
                 e->hooks.reparam(e->hooks.user, s, in, B, e->latent, a.train ? 1 : 0, e->fptr(e->off_vz));
                 in = e->fptr(e->off_vz);
@@ -2948,6 +2948,61 @@ int cae_case_measures(const void* pred, int pred_kind, int64_t pred_stride, cons
     return CAE_OK;
 }
 
+// ---- ensemble moments --------------------------------------------------------------------------
+
+int64_t cae_ensemble_moments_workspace_bytes(int64_t n_case, int64_t plane) {
+    if (n_case < 1 || plane < 1) return 0;
+    return n_case * plane * (int64_t)(2 * sizeof(double) + sizeof(float));
+}
+
+int cae_ensemble_moments(const float* draws, int64_t case_stride, int64_t draw_stride, int64_t n_case, int64_t plane,
+                         int k_call, int k_done, int k_total, double vmin, double range, double* mean, double* sd,
+                         void* workspace, int64_t workspace_bytes, void* hip_stream) {
+    if (!draws || !mean || n_case < 1 || plane < 1 || k_total < 2 || k_call < 1 || k_done < 0 || k_done + (int64_t)k_call > k_total)
+        return fail(CAE_ERR_ARG, "cae_ensemble_moments: bad argument (k_total >= 2, 1 <= k_call, k_done + k_call <= k_total)");
+    if ((n_case > 1 && case_stride < 0) || (k_call > 1 && draw_stride < 0))
+        return fail(CAE_ERR_ARG, "cae_ensemble_moments: negative stride");
+    // the planes of one call must not overlap: both layouts, [case][draw] and [draw][case], and anything looser
+    const bool case_major = case_stride >= (int64_t)(k_call - 1) * draw_stride + plane && (k_call == 1 || draw_stride >= plane);
+    const bool draw_major = draw_stride >= (n_case - 1) * case_stride + plane && (n_case == 1 || case_stride >= plane);
+    if (!case_major && !draw_major) return fail(CAE_ERR_ARG, "cae_ensemble_moments: the strides make planes overlap");
+    if (((uintptr_t)draws & 3) || ((uintptr_t)mean & 7) || ((uintptr_t)sd & 7))
+        return fail(CAE_ERR_ARG, "cae_ensemble_moments: pointers must be aligned to their element size");
+    const bool first = k_done == 0, last = k_done + k_call == k_total;
+    const int64_t n = n_case * plane;
+    EmArgs a;
+    memset(&a, 0, sizeof a);
+    if (!(first && last)) {
+        const int64_t need = cae_ensemble_moments_workspace_bytes(n_case, plane);
+        if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
+            return fail(CAE_ERR_ARG, "cae_ensemble_moments: draws delivered over several calls need a workspace of %lld bytes "
+                                     "(cae_ensemble_moments_workspace_bytes)", (long long)need);
+        a.w1 = (double*)workspace;
+        a.w2 = a.w1 + n;
+        a.w0 = (float*)(a.w2 + n);
+    }
+    // one wave per (case, chunk of 4-pixel groups): about 4096 waves in all where the call is large enough, chunks of 64 ..
+    // CM_GROUPS groups (nothing is folded, so the cut is free: a pixel's result does not depend on it)
+    const int64_t groups = (plane + 3) / 4;
+    int64_t chunk = (n_case * groups / 4096 + 63) / 64 * 64;
+    chunk = chunk < 64 ? 64 : (chunk > CM_GROUPS ? CM_GROUPS : chunk);
+    const int64_t nch = (groups + chunk - 1) / chunk;
+    if (nch > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_ensemble_moments: plane too large");
+    a.y = draws, a.case_stride = case_stride, a.draw_stride = draw_stride, a.plane = plane;
+    a.kc = k_call, a.K = k_total, a.nch = (int)nch, a.chunk = (int)chunk, a.items = n_case * nch;
+    a.vmin = vmin, a.range = range, a.mean = mean, a.sd = sd;
+    int64_t blocks = (a.items + CM_WAVES - 1) / CM_WAVES;
+    if (blocks > 65536) blocks = 65536;
+    const dim3 grid((unsigned)blocks);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (first && last) hipLaunchKernelGGL((k_ensemble_moments<true, true>), grid, dim3(256), 0, s, a);
+    else if (first) hipLaunchKernelGGL((k_ensemble_moments<true, false>), grid, dim3(256), 0, s, a);
+    else if (last) hipLaunchKernelGGL((k_ensemble_moments<false, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_ensemble_moments<false, false>), grid, dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
 // ---- case pages ------------------------------------------------------------------------------
 
 static int64_t range_blocks(int64_t n_case, int64_t plane) {
@@ -3169,6 +3224,24 @@ int trunk_forward(cae_engine* e, const float* x, int batch, bool train, bool ext
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
+
+// the two halves of the eval-mode forward on their own (cae_encode / cae_decode of the plain engine): the same per-layer launches
+// as trunk_forward(train = false), cut after the heads / entered at the decoder's first Linear
+static int trunk_part(cae_engine* e, const char* who, int part, const float* in, int batch, float* out) {
+    if (!e || !e->ws || !e->variational) return fail(CAE_ERR_STATE, "%s: not a bound trunk engine", who);
+    if (!in || !out || batch < 1 || batch > e->max_batch)
+        return fail(CAE_ERR_ARG, "%s: null pointer or batch %d outside [1, %d]", who, batch, e->max_batch);
+    StepArgs a = trunk_args(part == 1 ? in : nullptr, batch, false, ShardSync{});
+    a.part = part;
+    if (part == 1) a.z_out = out;
+    else a.z_in = in, a.yhat = out;
+    if (int rc = launch_forward(e, a)) return rc;
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+int trunk_encode(cae_engine* e, const float* x, int batch, float* heads) { return trunk_part(e, "trunk_encode", 1, x, batch, heads); }
+int trunk_decode(cae_engine* e, const float* z, int batch, float* yhat) { return trunk_part(e, "trunk_decode", 2, z, batch, yhat); }
 
 int trunk_backward(cae_engine* e, const float* x, int batch, const ShardSync& sync) {
     if (!e || !e->ws || !e->variational) return fail(CAE_ERR_STATE, "trunk_backward: not a bound trunk engine");

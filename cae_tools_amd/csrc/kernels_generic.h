@@ -1386,6 +1386,144 @@ __global__ void __launch_bounds__(256) k_case_fold(const double* __restrict__ pa
     }
 }
 
+// ---- ensemble moments (VarAEModel.apply(ensemble_size=K), include/cae_hip.h): per pixel the mean and the sample standard
+// deviation of K fp32 draws, denormalised, in fp64.  Nothing crosses a lane: a pixel's draws are summed by one lane in draw
+// order (d_k = y_k - y_0, s1 = S d_k, s2 = S d_k^2), so there is no fold, no atomic and no order to fix beyond that one.
+// Items and loads are k_case_measures': one wave per (case, chunk of `chunk` 4-pixel groups), a lane takes every 64th group
+// and reads it from each draw with one 16-byte load (four draws in flight), the head before the case's first 16-byte phase
+// and the tail after its last whole group go element by element to the lanes of chunk 0.  With nothing to fold the chunk
+// length is the host's to choose (64 .. CM_GROUPS groups): short chunks when a call brings few cases, so that the waves
+// still cover the device.  The draws of a case share that phase
+// when draw_stride is a multiple of 4 (or one draw arrives); otherwise every load is scalar.
+// FIRST: this call brings draw 0 (y_0 is read from it); otherwise {y_0, s1, s2} come from the workspace planes w0, w1, w2.
+// LAST: this call brings draw K-1 and writes mean / sd (16-byte stores where the case's plane starts on one); otherwise the
+// three values go back to the workspace.  <true, true> touches no workspace: K * 4 bytes read and 16 written per pixel.
+template <int N>
+__device__ __forceinline__ void em_load(const float* c, long long e, bool vec, float v[N]) {
+    if constexpr (N == 4) {
+        if (vec) {
+            const float4 w = *reinterpret_cast<const float4*>(c + e);
+            v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
+            return;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) v[j] = c[e + j];
+}
+
+template <int N>
+__device__ __forceinline__ void em_store(double* dst, long long o, bool vec2, const double v[N]) {
+    if constexpr (N == 4) {
+        if (vec2) {
+            reinterpret_cast<double2*>(dst + o)[0] = make_double2(v[0], v[1]);
+            reinterpret_cast<double2*>(dst + o)[1] = make_double2(v[2], v[3]);
+            return;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) dst[o + j] = v[j];
+}
+
+struct EmArgs {
+    const float* y;             // draw j of case c of this call: y + c * case_stride + j * draw_stride, `plane` floats
+    long long case_stride, draw_stride, plane;
+    int kc, K;                  // draws in this call, draws in all
+    int nch, chunk;             // chunks per case, 4-pixel groups per chunk
+    long long items;
+    double vmin, range;
+    double* mean;               // (n_case, plane) each; sd may be null
+    double* sd;
+    float* w0;                  // workspace planes (n_case, plane): y_0, s1, s2
+    double* w1;
+    double* w2;
+};
+
+// N pixels from element e of the case that starts at yc; o = the pixels' index in the (n_case, plane) output planes
+template <bool FIRST, bool LAST, int N>
+__device__ __forceinline__ void em_pixels(const EmArgs& a, const float* yc, long long e, long long o, bool vec, bool vec2) {
+    double y0[N], s1[N], s2[N];
+    int k = 0;
+    if constexpr (FIRST) {
+        float v[N];
+        em_load<N>(yc, e, vec, v);
+#pragma unroll
+        for (int j = 0; j < N; j++) y0[j] = (double)v[j], s1[j] = 0.0, s2[j] = 0.0;    // (d_0 = 0 adds nothing)
+        k = 1;
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++) y0[j] = (double)a.w0[o + j], s1[j] = a.w1[o + j], s2[j] = a.w2[o + j];
+    }
+    for (; k + 3 < a.kc; k += 4) {      // four draws in flight per lane, summed in draw order
+        float v[4][N];
+#pragma unroll
+        for (int u = 0; u < 4; u++) em_load<N>(yc + (k + u) * a.draw_stride, e, vec, v[u]);
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+#pragma unroll
+            for (int j = 0; j < N; j++) {
+                const double d = (double)v[u][j] - y0[j];
+                s1[j] += d;
+                s2[j] += d * d;
+            }
+    }
+    for (; k < a.kc; k++) {
+        float v[N];
+        em_load<N>(yc + k * a.draw_stride, e, vec, v);
+#pragma unroll
+        for (int j = 0; j < N; j++) {
+            const double d = (double)v[j] - y0[j];
+            s1[j] += d;
+            s2[j] += d * d;
+        }
+    }
+    if constexpr (LAST) {
+        const double K = (double)a.K, ar = fabs(a.range);
+        double m[N], s[N];
+#pragma unroll
+        for (int j = 0; j < N; j++) {
+            m[j] = a.vmin + (y0[j] + s1[j] / K) * a.range;
+            const double var = (s2[j] - s1[j] * s1[j] / K) / (K - 1.0);
+            s[j] = sqrt(var < 0.0 ? 0.0 : var) * ar;      // (a NaN stays a NaN)
+        }
+        em_store<N>(a.mean, o, vec2, m);
+        if (a.sd) em_store<N>(a.sd, o, vec2, s);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++) a.w0[o + j] = (float)y0[j], a.w1[o + j] = s1[j], a.w2[o + j] = s2[j];
+    }
+}
+
+template <bool FIRST, bool LAST>
+__global__ void __launch_bounds__(256) k_ensemble_moments(const EmArgs a) {
+    const int lane = threadIdx.x & 63;
+    const bool same_phase = (a.draw_stride & 3) == 0 || a.kc == 1;
+    for (long long item = (long long)blockIdx.x * CM_WAVES + (threadIdx.x >> 6); item < a.items;
+         item += (long long)gridDim.x * CM_WAVES) {
+        const long long cs = item / a.nch;
+        const int ch = (int)(item - cs * a.nch);
+        const float* yc = a.y + cs * a.case_stride;
+        const long long o0 = cs * a.plane;
+        int h = 0;
+        if (same_phase)
+            for (int t = 3; t >= 0; t--)
+                if (((uintptr_t)(yc + t) & 15) == 0) h = t;
+        const long long head = h < a.plane ? h : a.plane;
+        const long long groups = (a.plane - head) >> 2;
+        const long long tail0 = head + (groups << 2);
+        // 16-byte stores: the first group of the case lands on a 16-byte boundary of both output planes
+        const bool vec2 = (((uintptr_t)(a.mean + o0 + head) | (a.sd ? (uintptr_t)(a.sd + o0 + head) : 0)) & 15) == 0;
+        if (ch == 0) {
+            if (lane < head) em_pixels<FIRST, LAST, 1>(a, yc, lane, o0 + lane, false, false);
+            else if (lane >= 4 && lane - 4 < a.plane - tail0)
+                em_pixels<FIRST, LAST, 1>(a, yc, tail0 + lane - 4, o0 + tail0 + lane - 4, false, false);
+        }
+        const long long g0 = (long long)ch * a.chunk;
+        const long long g1 = g0 + a.chunk < groups ? g0 + a.chunk : groups;
+        for (long long g = g0 + lane; g < g1; g += 64)
+            em_pixels<FIRST, LAST, 4>(a, yc, head + (g << 2), o0 + head + (g << 2), same_phase, vec2);
+    }
+}
+
 // ---- case pages (evaluate_cae's per-case images): the value range of channel 0 and its palette indices.
 // KS is the source's element kind, KB the kind of the optional operand subtracted from it in fp64 (-1: none).
 template <int K> struct CpBytes { static constexpr int bytes = CmElem<K>::bytes; };

@@ -79,6 +79,32 @@ __global__ void __launch_bounds__(256) k_reparam(const float* __restrict__ heads
     if (threadIdx.x == 0) acc_add<ACC_PLANE>(kl_out, -0.5 * t);
 }
 
+// heads (B, 2 * L) rows [mu | logvar] -> the two (B, L) arrays vae_encode hands out
+__global__ void __launch_bounds__(256) k_split_heads(const float* __restrict__ heads, int B, int L, float* __restrict__ mu,
+                                                     float* __restrict__ logvar) {
+    const int n = B * L;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const int b = i / L, j = i - b * L;
+        mu[i] = heads[(size_t)b * 2 * L + j];
+        logvar[i] = heads[(size_t)b * 2 * L + L + j];
+    }
+}
+
+// vae_sample_latent: z = mu + eps * exp(logvar / 2), k_reparam's arithmetic on (B, L) arrays, for the draws draw0 + blockIdx.y:
+// z (gridDim.y, B, L).  eps is element (first + b) * L + j of the noise array of pcg(seed_key ^ draw) (the caller keeps that index
+// below 2^31: normal_hash doubles it).  A null mu or logvar is 0.
+__global__ void __launch_bounds__(256) k_sample_latent(const float* __restrict__ mu, const float* __restrict__ logvar, int B, int L,
+                                                       long long first, uint32_t seed_key, long long draw0, float* __restrict__ z) {
+    const int n = B * L;
+    const uint32_t key = pcg(seed_key ^ (uint32_t)((draw0 + blockIdx.y) & 0xFFFFFFFF));
+    float* zd = z + (size_t)blockIdx.y * n;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const float m = mu ? mu[i] : 0.f, l = logvar ? logvar[i] : 0.f;
+        const float e = normal_hash(key, (uint32_t)(first * L + i));
+        zd[i] = m + e * expf(0.5f * l);
+    }
+}
+
 // dmu = dz + lambda_kl * mu / n;  dlv = dz * eps * 0.5 * exp(lv/2) + lambda_kl * 0.5 * (exp(lv) - 1) / n;  rows [dmu | dlv]
 // (n_kl: the n of the KL mean, B * L on a single device, the global batch's under data parallelism)
 __global__ void __launch_bounds__(256) k_reparam_bwd(const float* __restrict__ dz, const float* __restrict__ heads,

@@ -39,6 +39,11 @@ void trunk_set_hooks(cae_engine* e, const TrunkHooks& hooks);
 // layer's raw output is left in trunk_raw_output(); otherwise its sigmoid goes to yhat (scoring).
 int trunk_forward(cae_engine* e, const float* x_dev, int batch, bool train, bool external_loss, float* yhat_dev,
                   const ShardSync& sync = ShardSync{});
+// The halves of the eval-mode forward (running statistics), the launches trunk_forward(train = false) makes: the encoder up to
+// the heads, heads_dev (batch, 2 * latent) rows [mu | logvar] and no reparameterisation call-back; the decoder from a given
+// latent z_dev (batch, latent) to the sigmoid output yhat_dev.
+int trunk_encode(cae_engine* e, const float* x_dev, int batch, float* heads_dev);
+int trunk_decode(cae_engine* e, const float* z_dev, int batch, float* yhat_dev);
 float* trunk_raw_output(cae_engine* e);          // (B, out_c, out_h, out_w)
 float* trunk_output_gradient(cae_engine* e);     // where the caller leaves dL/d(raw output) before trunk_backward
 double* trunk_output_bias_acc(cae_engine* e);    // fp64 accumulator of the last layer's bias gradient (the caller adds sum dL/d(raw))

@@ -27,7 +27,7 @@ struct vae_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets, 
     int in_c = 0, in_h = 0, in_w = 0, out_c = 0, out_h = 0, out_w = 0;
     int64_t n_params = 0, n_buffers = 0, trunk_ws = 0;
     int64_t off_trunk = 0, off_grads = 0, off_f32 = 0;
-    int64_t xb = 0, eps = 0, kappa = 0;
+    int64_t xb = 0, eps = 0, kappa = 0, heads = 0;   // (heads: vae_encode's (B, 2 * latent) rows before they are split)
     int64_t sx[vae::kScales] = {0}, sy[vae::kScales] = {0}, sA[vae::kScales] = {0}, sB[vae::kScales] = {0},
             sC[vae::kScales] = {0}, sG[vae::kScales] = {0};
     int64_t off_ssum = 0, off_part = 0;   // doubles: [scale][BC][2]; parts {mse, kl, ssim}
@@ -46,9 +46,9 @@ struct vae_engine : SteppedCore {   // (ws, stream, max_batch, step, data sets, 
 
 namespace {
 
-uint32_t noise_key(const vae_engine* e) {
-    return pcg(pcg(e->seed + 0x9E3779B9u * 977u) ^ (uint32_t)(e->step & 0xFFFFFFFF));
-}
+// the key of the noise array of (seed, step): oracle/vae_oracle.py normal_noise
+uint32_t seed_key(uint32_t seed) { return pcg(seed + 0x9E3779B9u * 977u); }
+uint32_t noise_key(const vae_engine* e) { return pcg(seed_key(e->seed) ^ (uint32_t)(e->step & 0xFFFFFFFF)); }
 
 // ---- the two call-backs of the trunk (trunk_api.h) ----------------------------------------------------------------------
 void hook_reparam(void* user, hipStream_t s, const float* heads, int B, int latent, int train, float* z) {
@@ -244,6 +244,7 @@ int vae_engine_create(const cae_layer_spec* enc, int n_enc, const cae_layer_spec
     Carver F32{64};   // the fp32 sub-arena (float offsets)
     e->xb = F32(B * e->in_c * e->in_h * e->in_w);
     e->eps = F32(B * latent_size);
+    e->heads = F32(B * 2 * latent_size);
     const int64_t BC = B * e->out_c;
     for (int s = 0, h = e->out_h, w = e->out_w; s < vae::kScales; s++, h /= 2, w /= 2) {
         e->sx[s] = F32(BC * h * w), e->sy[s] = F32(BC * h * w), e->sG[s] = F32(BC * h * w);
@@ -339,6 +340,33 @@ int vae_score(vae_engine* e, const float* x, int batch, float* y) {
     if (int rc = check_score(e, "vae", x, batch, y)) return rc;
     HIP_TRY(hipMemsetAsync(e->parts(), 0, 4 * sizeof(double), e->stream));
     return cae_internal::trunk_forward(e->trunk, x, batch, false, false, y);
+}
+int vae_encode(vae_engine* e, const float* x, int batch, float* mu, float* logvar) {
+    if (!e || !e->ws) return fail(CAE_ERR_STATE, "vae_encode: vae_bind has not been called");
+    if (!x || !mu || !logvar || batch < 1 || batch > e->max_batch) return fail(CAE_ERR_ARG, "vae_encode: bad argument");
+    if (int rc = cae_internal::trunk_encode(e->trunk, x, batch, e->f(e->heads))) return rc;
+    hipLaunchKernelGGL(vae::k_split_heads, dim3(blocks_for((long long)batch * e->latent, 65536)), dim3(256), 0, e->stream, e->f(e->heads),
+                       batch, e->latent, mu, logvar);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+int vae_decode(vae_engine* e, const float* z, int batch, float* y) {
+    if (!e || !e->ws) return fail(CAE_ERR_STATE, "vae_decode: vae_bind has not been called");
+    if (!z || !y || batch < 1 || batch > e->max_batch) return fail(CAE_ERR_ARG, "vae_decode: bad argument");
+    return cae_internal::trunk_decode(e->trunk, z, batch, y);
+}
+int vae_sample_latent(vae_engine* e, const float* mu, const float* logvar, int batch, int64_t first_case, int64_t draw, int n_draws,
+                      uint32_t seed, float* z) {
+    if (!e || !e->ws) return fail(CAE_ERR_STATE, "vae_sample_latent: vae_bind has not been called");
+    if (!z || batch < 1 || first_case < 0 || draw < 0 || n_draws < 1 || n_draws > 65535)
+        return fail(CAE_ERR_ARG, "vae_sample_latent: bad argument");
+    if ((first_case + batch) * (int64_t)e->latent >= (1LL << 31))
+        return fail(CAE_ERR_ARG, "vae_sample_latent: case %lld x latent %d reaches noise index 2^31, where the hash index wraps",
+                    (long long)(first_case + batch), e->latent);
+    hipLaunchKernelGGL(vae::k_sample_latent, dim3(blocks_for((long long)batch * e->latent, 65536), n_draws), dim3(256), 0, e->stream, mu,
+                       logvar, batch, e->latent, (long long)first_case, seed_key(seed), (long long)draw, z);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
 }
 int vae_loss_slots(const vae_engine* e) { return e ? kStepLossSlots : 0; }
 int vae_read_losses(vae_engine* e, int first_slot, int count, double* out) { return read_losses(e, "vae", first_slot, count, out); }

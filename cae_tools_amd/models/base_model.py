@@ -84,7 +84,14 @@ class BaseModel:
             return self._score_device(x)
         (world, rank) = (dist.get_world_size(), dist.get_rank())
         (lo, hi) = _dp.shard_bounds(n, world, rank)
-        mine = self._score_device(x[lo:hi])
+        return self._gather_cases(self._score_device(x[lo:hi]), n, dist)
+
+    @staticmethod
+    def _gather_cases(mine, n, dist):
+        """all-gather of per-case rows sharded by dp.shard_bounds(n, world, rank): every rank returns all n rows"""
+        from .. import dp as _dp
+        (world, rank) = (dist.get_world_size(), dist.get_rank())
+        (lo, hi) = _dp.shard_bounds(n, world, rank)
         per = -(-n // world)
         pad = torch.zeros((per,) + tuple(mine.shape[1:]), dtype=mine.dtype, device=mine.device)
         pad[:hi - lo] = mine
@@ -109,9 +116,12 @@ class BaseModel:
 
     def apply(self, score_ds, input_variables, prediction_variable="model_output",
               channel_dimension="model_output_channel", y_dimension="model_output_y",
-              x_dimension="model_output_x", mask_variable_name=None):
+              x_dimension="model_output_x", mask_variable_name=None, **vae_only):
         """Add `prediction_variable` (float64, denormalised, dims (case, channel, y, x)) to score_ds
         in place (:102-152)."""
+        if vae_only:    # ensemble_size / spread_variable / ensemble_seed / latent_variable: VarAEModel.apply's own keywords
+            raise TypeError(f"{type(self).__name__}.apply() got {sorted(vae_only)}: only VarAEModel (the VAE, --method var) has a "
+                            "stochastic latent to draw an ensemble from")
         self.apply_device(score_ds, input_variables, prediction_variable, channel_dimension, y_dimension, x_dimension,
                           mask_variable_name)
 

@@ -16,8 +16,9 @@ from .. import dp as _dp
 from .. import vae_engine as _ve
 from ..utils.model_database import ModelDatabase
 from ._params import ParamBag, add_batchnorm, add_conv
-from .base_model import EngineModel
+from .base_model import EngineModel, _make_data_array
 from .decoder import Decoder
+from .ds_dataset import DSDataset
 
 
 class VarEncoder(ParamBag):
@@ -37,8 +38,19 @@ class VarEncoder(ParamBag):
         add_conv(self, "encoder_mu", (encoded_space_dim, fc_size), encoded_space_dim)
         add_conv(self, "encoder_logvar", (encoded_space_dim, fc_size), encoded_space_dim)
 
+        self._engine = None
+
+    def attach(self, engine):
+        self._engine = engine
+
     def forward(self, x):
-        raise RuntimeError("VarEncoder.forward on its own is not a product path: use VarAEModel.score / apply / train")
+        """x (B, C, h, w) fp32 CUDA tensor -> (mu, logvar), (B, encoded_space_dim) each; eval mode, on the attached engine"""
+        if self._engine is None:
+            raise RuntimeError("VarEncoder.forward needs an attached VaeEngine (VarAEModel attaches one when it builds or loads "
+                               "a model): there is no CPU path")
+        return self._engine.encode(x)
+
+    __call__ = forward
 
 
 class VarAEModel(EngineModel):
@@ -98,6 +110,11 @@ class VarAEModel(EngineModel):
 
     def _make_engine(self, max_batch):
         return _ve.VaeEngine(self.spec, self.fc_size, self.encoded_dim_size, max_batch=max_batch)
+
+    def _load_engine(self, eng):
+        super()._load_engine(eng)
+        self.encoder.attach(eng)
+        self.decoder.attach(eng)
 
     def train(self, input_variables, output_variable, training_ds, testing_ds, model_path="", training_paths="",
               testing_paths="", mask_variable_name=None):
@@ -166,3 +183,88 @@ class VarAEModel(EngineModel):
         if self._engine is not None:
             return self._engine.score(x)
         return super()._score_device(x)
+
+    # ---- the model as a generative one (the build's own definition, parity unpinned) -------------------------
+    def _inference_engine(self, n):
+        """the engine encode / decode / apply run on: the one that exists, else one for min(batch_size, n) rows"""
+        if self._engine is not None:
+            return self._engine
+        return self._get_engine(max(1, min(int(self.batch_size), int(n))))
+
+    def _denormalise(self, y):
+        """as apply() denormalises (ds_dataset.denormalise_device): min + y * (max - min) of the output variable, float64"""
+        from .. import engine as _eng
+        return _eng.denormalise_f64(y, self.normalisation_parameters[2], self.normalisation_parameters[3])
+
+    def encode(self, score_ds, input_variables):
+        """(mu, logvar) of every case of score_ds: float32 numpy arrays (N, encoded_dim_size); eval mode"""
+        _dp.select_device()
+        ds = DSDataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input)
+        ds.set_normalisation_parameters(self.normalisation_parameters)
+        x = ds.device_inputs()
+        (mu, logvar) = self._inference_engine(x.shape[0]).encode(x)
+        return mu.cpu().numpy(), logvar.cpu().numpy()
+
+    def decode(self, z):
+        """z (N, encoded_dim_size) -> the denormalised float64 numpy array (N, C, H, W) the decoder makes of it; eval mode"""
+        _dp.select_device()
+        z = torch.as_tensor(np.asarray(z), dtype=torch.float32).cuda()
+        return self._denormalise(self._inference_engine(z.shape[0]).decode(z)).cpu().numpy()
+
+    def generate(self, n, seed=0):
+        """n fields decoded from the prior: the latents are normal_noise(seed, 0, (n, encoded_dim_size)) (oracle/vae_oracle.py)"""
+        _dp.select_device()
+        eng = self._inference_engine(n)
+        return self._denormalise(eng.decode(eng.sample_latent(None, None, draw=0, seed=seed, n=n))).cpu().numpy()
+
+    def apply(self, score_ds, input_variables, prediction_variable="model_output", channel_dimension="model_output_channel",
+              y_dimension="model_output_y", x_dimension="model_output_x", mask_variable_name=None, ensemble_size=None,
+              spread_variable=None, ensemble_seed=0, latent_variable=None):
+        """BaseModel.apply, and with ensemble_size=K the model's own spread: every case is encoded once, K latents
+        z_k = mu + eps_k * exp(logvar / 2) are decoded (eps_k: the noise of (ensemble_seed, draw k, global case index)), and
+        `prediction_variable` receives the per-pixel mean of the K fields, `spread_variable` (K >= 2) their sample standard
+        deviation (same dimensions, float64, denormalised).  latent_variable=NAME stores NAME_mu and NAME_logvar, float32
+        (case, "model_latent").  With none of the four keywords this is BaseModel.apply (z = mu), bit for bit."""
+        if ensemble_size is not None and (int(ensemble_size) != ensemble_size or int(ensemble_size) < 1):
+            raise ValueError(f"ensemble_size must be a positive integer, got {ensemble_size!r}")
+        if spread_variable is not None and (ensemble_size is None or int(ensemble_size) < 2):
+            raise ValueError("spread_variable needs ensemble_size >= 2: one draw has no spread")
+        if ensemble_size is None and latent_variable is None:
+            return super().apply(score_ds, input_variables, prediction_variable, channel_dimension, y_dimension, x_dimension,
+                                 mask_variable_name)
+        n = int(score_ds[input_variables[0]].shape[0])
+        _ve.check_noise_index(n, self.encoded_dim_size)
+        dist = _dp.ensure_process_group()      # a rank's GPU is selected before the data set is uploaded
+        n_dimension = score_ds[input_variables[0]].dims[0]
+        ds = DSDataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input,
+                       mask_variable_name=mask_variable_name)
+        ds.set_normalisation_parameters(self.normalisation_parameters)
+        x = ds.device_inputs()
+        # cases sharded over the GPUs of a torch.distributed.run launch as _score_all shards them; the noise counts in the
+        # global case index (first_case), so the result does not depend on the number of ranks
+        (lo, hi) = (0, n)
+        if dist is not None and n >= dist.get_world_size():
+            (lo, hi) = _dp.shard_bounds(n, dist.get_world_size(), dist.get_rank())
+        else:
+            dist = None
+        eng = self._inference_engine(hi - lo)
+        (mu, logvar) = eng.encode(x[lo:hi])
+        (vmin, vmax) = (ds.min_output, ds.max_output)      # what ds.denormalise_device applies
+        std = None
+        if ensemble_size is None:
+            mean = ds.denormalise_device(eng.decode(mu))
+        elif int(ensemble_size) == 1:
+            mean = ds.denormalise_device(eng.decode(eng.sample_latent(mu, logvar, draw=0, seed=ensemble_seed, first_case=lo)))
+        else:
+            (mean, std) = eng.ensemble(mu, logvar, int(ensemble_size), seed=ensemble_seed, first_case=lo, vmin=vmin, vmax=vmax,
+                                       want_std=spread_variable is not None)
+        if dist is not None:
+            (mean, mu, logvar) = (self._gather_cases(t, n, dist) for t in (mean, mu, logvar))
+            std = None if std is None else self._gather_cases(std, n, dist)
+        dims = (n_dimension, channel_dimension, y_dimension, x_dimension)
+        score_ds[prediction_variable] = _make_data_array(score_ds, mean.cpu().numpy(), dims)
+        if std is not None:
+            score_ds[spread_variable] = _make_data_array(score_ds, std.cpu().numpy(), dims)
+        if latent_variable is not None:
+            for (suffix, t) in (("_mu", mu), ("_logvar", logvar)):
+                score_ds[latent_variable + suffix] = _make_data_array(score_ds, t.cpu().numpy(), (n_dimension, "model_latent"))

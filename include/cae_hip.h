@@ -324,6 +324,24 @@ int cae_case_measures(const void* pred_dev, int pred_kind, int64_t pred_case_str
                       int actual_kind, int64_t actual_case_stride, int64_t n_case, int64_t plane, double* out_dev,
                       void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- ensemble moments (stateless): VarAEModel.apply(ensemble_size=K) ---------------------- */
+
+/* Per pixel p of case c, from its K = k_total >= 2 fp32 draws y_0 .. y_{K-1} (fp64 throughout, sums in ascending draw order):
+ *   d_k = (double)y_k - (double)y_0,  s1 = S d_k,  s2 = S d_k^2
+ *   mean_dev[c][p] = vmin + (y_0 + s1 / K) * range
+ *   std_dev[c][p]  = sqrt(max(0, (s2 - s1^2 / K) / (K - 1))) * |range|      (sample standard deviation; std_dev may be NULL)
+ * mean_dev and std_dev are (n_case, plane) doubles.  Draw j of this call's k_call draws of case c is the `plane` floats from
+ * element c * case_stride + j * draw_stride of draws_dev; any element alignment, any plane, [case][draw] or [draw][case] order.
+ * All K draws in one call (k_done 0, k_call == k_total) need no workspace: K * plane * 4 bytes read and plane * 16 written per
+ * case.  Otherwise the draws arrive in order over several calls with the same n_case, plane and workspace, k_done = the
+ * draws already delivered; y_0, s1 and s2 wait in workspace_dev (cae_ensemble_moments_workspace_bytes bytes, 8-byte aligned)
+ * and the call that brings the last draw writes the outputs.  A pixel is summed by one lane: no atomics, no fold, the same
+ * bits from run to run and however the draws are cut into calls.  NaN and Inf propagate. */
+int64_t cae_ensemble_moments_workspace_bytes(int64_t n_case, int64_t plane);
+int cae_ensemble_moments(const float* draws_dev, int64_t case_stride, int64_t draw_stride, int64_t n_case, int64_t plane,
+                         int k_call, int k_done, int k_total, double vmin, double range, double* mean_dev, double* std_dev,
+                         void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 /* ---- case pages (stateless): evaluate_cae's per-case images of channel 0 ------------------- */
 
 /* Both calls read the first `plane` elements (channel 0) of cases that start at element i * src_case_stride of src_dev,

@@ -77,6 +77,21 @@ int vae_forward_backward_sync(vae_engine* e, int which, const int32_t* perm_dev,
 int vae_eval_step_sync(vae_engine* e, int which, const int32_t* perm_dev, int64_t start, int batch, int row0,
                        int global_batch, int loss_slot, cae_allreduce_fn fn, void* user);
 int vae_score(vae_engine* e, const float* x_dev, int batch, float* y_dev);
+/* The model as a generative one (the build's own definition, parity unpinned).  All three run on the engine's
+ * stream and take at most max_batch rows (vae_sample_latent: any number).
+ * vae_encode: the eval-mode encoder (running statistics) up to the two heads: mu_dev and logvar_dev, (batch, latent) fp32 each.
+ * vae_decode: the eval-mode decoder from a given latent z_dev (batch, latent), sigmoid applied: y_dev (batch, C, H, W).
+ *   vae_score(x) is vae_decode(mu of vae_encode(x)): the same launches on the same values, bit for bit at the same batch.
+ * vae_sample_latent: z[b][j] = mu[b][j] + eps * expf(0.5f * logvar[b][j]) with eps element (first_case + b) * latent + j of
+ *   normal_noise(seed, step = draw, .) (oracle/vae_oracle.py), the counter-based noise of training; with n_draws > 1 the
+ *   draws draw .. draw + n_draws - 1 in one launch, z_dev (n_draws, batch, latent).  A NULL mu_dev or logvar_dev
+ *   stands for zeros (the prior).  The noise of a case depends on its index, the draw and the seed alone - not on batch, on
+ *   how the cases are cut into calls, or on which rank holds them.  (first_case + batch) * latent must stay below 2^31: the
+ *   hash index would wrap. */
+int vae_encode(vae_engine* e, const float* x_dev, int batch, float* mu_dev, float* logvar_dev);
+int vae_decode(vae_engine* e, const float* z_dev, int batch, float* y_dev);
+int vae_sample_latent(vae_engine* e, const float* mu_dev, const float* logvar_dev, int batch, int64_t first_case, int64_t draw,
+                      int n_draws, uint32_t seed, float* z_dev);
 int vae_loss_slots(const vae_engine* e);
 int vae_read_losses(vae_engine* e, int first_slot, int count, double* out_host);   /* 4 doubles per slot */
 int vae_sync(vae_engine* e);
