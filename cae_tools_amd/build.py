@@ -3,8 +3,9 @@
     python -m cae_tools_amd.build            # (re)build what is older than its sources
     python -m cae_tools_amd.build --force
 
-Each .hip source is compiled to an object under csrc/_obj/ (only when it or one of its headers changed, the
-sources in parallel), then the objects are linked into csrc/libcae_hip.so.
+Each .hip source is compiled to an object under csrc/_obj/, the sources in parallel, then the objects are linked into
+csrc/libcae_hip.so.  hipcc writes the files each object was compiled from beside it (-MD); an object is compiled again when
+one of them is newer, or when it has no such list.
 """
 import os
 import shutil
@@ -18,14 +19,7 @@ OBJ = os.path.join(CSRC, "_obj")
 INC = os.path.join(ROOT, "include")
 LIB = os.path.join(CSRC, "libcae_hip.so")
 ARCH = "gfx950"
-# source -> headers it includes (csrc/ or include/)
-SOURCES = {
-    "engine.hip": ["kernels_generic.h", "acc_grid.h", "kernels_s2.h", "kernels_last.h", "kernels_rows.h", "kernels_gemm.h", "kernels_igemm.h", "kernels_ctlds.h", "kernels_ctbwd.h", "kernels_head.h", "dp_comm.h", "cae_hip.h", "trunk_api.h", "engine_host.h"],
-    "ctbwd.hip": ["kernels_generic.h", "acc_grid.h", "kernels_gemm.h", "kernels_ctbwd.h"],
-    "unet_engine.hip": ["kernels_unet.h", "kernels_unet_mfma.h", "kernels_unet_lin.h", "kernels_unet_thin.h", "kernels_unet_patch.h", "kernels_generic.h", "acc_grid.h", "kernels_gemm.h", "cae_unet.h", "cae_hip.h", "engine_host.h"],
-    "vae_engine.hip": ["kernels_unet.h", "acc_grid.h", "kernels_vae.h", "cae_vae.h", "cae_hip.h", "trunk_api.h", "engine_host.h"],
-    "linear_engine.hip": ["kernels_unet.h", "acc_grid.h", "kernels_unet_mfma.h", "kernels_vae.h", "cae_linear.h", "cae_hip.h", "engine_host.h"],
-}
+SOURCES = ["engine.hip", "ctbwd.hip", "unet_engine.hip", "vae_engine.hip", "linear_engine.hip"]
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-cuda-compat", "-Wno-pass-failed"]
 FLAGS += os.environ.get("CAE_HIPCC_FLAGS", "").split()     # tuning experiments: e.g. CAE_HIPCC_FLAGS=-DIG_KCW=32
 
@@ -37,26 +31,34 @@ def _hipcc():
     raise RuntimeError("hipcc not found: cannot build libcae_hip.so")
 
 
-def _path(name):
-    p = os.path.join(CSRC, name)
-    return p if os.path.exists(p) else os.path.join(INC, name)
-
-
-def _stale(target, deps):
-    if not os.path.exists(target):
-        return True
-    t = os.path.getmtime(target)
-    return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
-
-
 def _obj(src):
     return os.path.join(OBJ, os.path.splitext(src)[0] + ".o")
 
 
-def needs_build():
-    if any(_stale(_obj(s), [_path(s)] + [_path(h) for h in hs]) for s, hs in SOURCES.items()):
+def _deps(obj):
+    """The files hipcc read for obj, from the dependency file it wrote beside it (None: there is none)."""
+    try:
+        with open(obj + ".d") as f:
+            rule = f.read().replace("\\\n", " ")
+    except OSError:
+        return None
+    return rule.split(": ", 1)[1].split()
+
+
+def _stale(src):
+    """An object is stale without a dependency file, or when a file named there is newer or gone."""
+    obj, deps = _obj(src), _deps(_obj(src))
+    if deps is None or not os.path.exists(obj):
         return True
-    return _stale(LIB, [_obj(s) for s in SOURCES])
+    t = os.path.getmtime(obj)
+    return any(not os.path.exists(d) or os.path.getmtime(d) > t for d in deps)
+
+
+def needs_build():
+    if any(_stale(s) for s in SOURCES) or not os.path.exists(LIB):
+        return True
+    t = os.path.getmtime(LIB)
+    return any(os.path.getmtime(_obj(s)) > t for s in SOURCES)
 
 
 def build(force=False, verbose=True):
@@ -65,9 +67,9 @@ def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
     jobs = []
-    for src, headers in SOURCES.items():
-        if force or _stale(_obj(src), [_path(src)] + [_path(h) for h in headers]):
-            cmd = [hipcc] + FLAGS + ["-I" + INC, "-I" + CSRC, "-c", _path(src), "-o", _obj(src)]
+    for src in SOURCES:
+        if force or _stale(src):
+            cmd = [hipcc] + FLAGS + ["-I" + INC, "-I" + CSRC, "-MD", "-MF", _obj(src) + ".d", "-c", os.path.join(CSRC, src), "-o", _obj(src)]
             if verbose:
                 print(" ".join(cmd), flush=True)
             jobs.append((src, subprocess.Popen(cmd)))

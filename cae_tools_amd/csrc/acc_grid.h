@@ -1,8 +1,8 @@
 // acc_grid.h — the fixed accumulation grids of every cross-workgroup fp64 sum (bitwise reproducible training steps).
 //
 // A header FRAGMENT without an include guard: it holds only force-inlined device templates and is included inside the
-// namespace of its includer - kernels_generic.h (namespace cae; unet_engine.hip and ctbwd.hip compile that file once more
-// inside namespaces of their own) and kernels_unet.h (namespace unet, for the UNET, VAE and Linear engines).  Including it
+// namespace of its includer - device_common.h (namespace cae; unet_engine.hip compiles that file once more inside a
+// namespace of its own) and kernels_unet.h (namespace unet, for the UNET, VAE and Linear engines).  Including it
 // twice into ONE namespace is a compile error, not a silent second definition.
 
 // ---- order-independent accumulation -----------------------------------------------------------------------------------------

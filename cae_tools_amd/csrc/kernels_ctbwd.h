@@ -18,7 +18,9 @@
 //      then one fp64 atomic per channel and workgroup), stores.
 // Only 3x3 kernels at stride 2 without padding (OH >= 2H + 1): everything else stays on k_ig_bwd_pair.
 #pragma once
-#include "kernels_gemm.h"
+#include <type_traits>
+
+#include "device_common.h"
 
 namespace cae {
 

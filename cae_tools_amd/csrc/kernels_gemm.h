@@ -8,11 +8,9 @@
 // global memory into the MFMA lane layout (lane l: A[row l&15][k0 + (l>>4)], B[k0 + (l>>4)][col l&15]).
 // 4 waves per workgroup; grid = ceil(tiles / 4).
 #pragma once
-#include "kernels_generic.h"
+#include "device_common.h"
 
 namespace cae {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 enum GemmEpi : int {
     GE_STORE = 0,        // C = acc (+bias[n]) (relu)

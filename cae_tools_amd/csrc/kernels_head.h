@@ -200,7 +200,7 @@ __device__ __forceinline__ void mfma_stage(int M, int N, int K, int tm0, int TM,
     else mfma_stage_d<APAD, BFAST, 8>(M, N, K, tm0, TM, tn0, TN, sp, part, fa, fb, fe);
 }
 
-// fp64 wave sum, valid in lane 63 (kernels_generic.h)
+// fp64 wave sum, valid in lane 63 (device_common.h)
 __device__ __forceinline__ double head_wave_sum(double v) { return wave_sum_lane63(v); }
 
 // Everything small the kernel reads from global memory (encoder parameters and running statistics, Linear biases), copied

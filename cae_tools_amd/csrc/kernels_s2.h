@@ -19,7 +19,7 @@
 // into LDS (NCHW -> LDS patch tile).  Accumulators stay in registers across all tiles a
 // workgroup walks; one wave-shuffle + LDS reduction and one fp64 atomic per value at the end.
 #pragma once
-#include "kernels_generic.h"
+#include "device_common.h"
 
 namespace cae {
 

@@ -1,0 +1,631 @@
+// kernels_stateless.h — the kernels behind the stateless entry points of include/cae_hip.h (at the end of engine.hip's
+// extern "C" block): the loader
+// (scan, normalise + pack, permutation inverse, denormalise, metric sums, byte swap), the evaluator's per-case measures, the
+// ensemble moments and the case pages.  None of them touches an engine.
+#pragma once
+#include "device_common.h"
+
+namespace cae {
+
+// ---------------------------------------------------------------------------------------------
+// loader kernels (ds_dataset.py)
+// ---------------------------------------------------------------------------------------------
+
+// per-block partial {nan count, min, max}; out [gridDim.x][3] doubles
+__global__ void __launch_bounds__(256) k_scan(const float* __restrict__ x, long long n, double* __restrict__ out) {
+    __shared__ double red[3][4];
+    double cnt = 0;
+    float lo = INFINITY, hi = -INFINITY;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float v = x[i];
+        if (v != v) {
+            cnt += 1;
+        } else {
+            lo = fminf(lo, v);
+            hi = fmaxf(hi, v);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        cnt += __shfl_down(cnt, off, 64);
+        lo = fminf(lo, __shfl_down(lo, off, 64));
+        hi = fmaxf(hi, __shfl_down(hi, off, 64));
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[0][wv] = cnt;
+        red[1][wv] = lo;
+        red[2][wv] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double c = 0, l = INFINITY, h = -INFINITY;
+        for (int i = 0; i < 4; i++) {
+            c += red[0][i];
+            l = fmin(l, red[1][i]);
+            h = fmax(h, red[2][i]);
+        }
+        out[3 * blockIdx.x + 0] = c;
+        out[3 * blockIdx.x + 1] = l;
+        out[3 * blockIdx.x + 2] = h;
+    }
+}
+
+// dst[row(i)][c_off + c][:] = (src[i][c][:] - vmin) / range   (two correctly rounded fp32 ops, as numpy)
+// row(i) = dst_row[i] when a table is given (the frozen shuffle's inverse: normalisation writes the samples in batch order
+// in the pass it makes anyway - the reference's DataLoader + collate stacking, conv_ae_model.py:291-292,315-325), else i.
+__global__ void __launch_bounds__(256) k_normalise_pack(const float* __restrict__ src, long long total, int c_src,
+                                                         long long hw, float* __restrict__ dst, int c_dst, int c_off,
+                                                         float vmin, float range, int enable,
+                                                         const int* __restrict__ dst_row) {
+    const long long per = (long long)c_src * hw;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long s = i / per, r = i - s * per;
+        float v = src[i];
+        if (enable) v = (range == 0.f) ? 0.f : __fdiv_rn(__fsub_rn(v, vmin), range);
+        const long long d = dst_row ? (long long)dst_row[s] : s;
+        dst[(d * c_dst + c_off) * hw + r] = v;
+    }
+}
+
+// inv[perm[i]] = i: the destination-row table of k_normalise_pack from a frozen sample order
+__global__ void __launch_bounds__(256) k_invert_perm(const int* __restrict__ perm, long long n, int* __restrict__ inv) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const int p = perm[i];
+        if (p >= 0 && p < n) inv[p] = (int)i;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_denorm_f64(const float* __restrict__ y, long long n, double vmin, double range,
+                                                     double* __restrict__ out) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+        out[i] = __dadd_rn(vmin, __dmul_rn((double)y[i], range));
+}
+
+// model_metric.py:47-71 per instance: sums[inst][8] += {n, Σa', Σe', Σa'², Σe'², Σa'e', Σ|a-e|, Σ(a-e)²} over the
+// pixels whose mask is non-zero, with e = vmin + (double)y*range (the denormalised score of base_model.py:90) and
+// a' = a - vmin, e' = e - vmin (shifted so the second moments do not cancel).  grid (chunks, n_inst), block 256.
+__global__ void __launch_bounds__(256) k_metric_sums(const float* __restrict__ y, const float* __restrict__ a,
+                                                      const float* __restrict__ mask, long long elems, double vmin,
+                                                      double range, double* __restrict__ sums) {
+    __shared__ double red[4];
+    const long long base = (long long)blockIdx.y * elems;
+    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < elems; i += (long long)gridDim.x * 256) {
+        if (mask && mask[base + i] == 0.f) continue;
+        const double e = __dadd_rn(vmin, __dmul_rn((double)y[base + i], range));
+        const double av = (double)a[base + i];
+        const double d = av - e, as = av - vmin, es = e - vmin;
+        acc[0] += 1.0;
+        acc[1] += as;
+        acc[2] += es;
+        acc[3] += as * as;
+        acc[4] += es * es;
+        acc[5] += as * es;
+        acc[6] += fabs(d);
+        acc[7] += d * d;
+    }
+    for (int k = 0; k < 8; k++) {
+        const double t = block_sum(acc[k], red);
+        if (threadIdx.x == 0 && t != 0.0) atomicAdd(&sums[(size_t)blockIdx.y * 8 + k], t);
+    }
+}
+
+// NetCDF-3 stores big-endian words: swap n 32-bit words in place (16 bytes per lane per trip)
+__global__ void __launch_bounds__(256) k_bswap32(unsigned* __restrict__ x, long long n) {
+    const long long n4 = n >> 2;
+    uint4* x4 = reinterpret_cast<uint4*>(x);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        uint4 v = x4[i];
+        v.x = __builtin_bswap32(v.x);
+        v.y = __builtin_bswap32(v.y);
+        v.z = __builtin_bswap32(v.z);
+        v.w = __builtin_bswap32(v.w);
+        x4[i] = v;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) x[(n4 << 2) + threadIdx.x] = __builtin_bswap32(x[(n4 << 2) + threadIdx.x]);
+}
+
+// ---- per-case error sums (model_evaluator.py:87-95): S|p - a| and S(p - a)^2 in fp64 over a case's first `plane` elements.
+// Element kinds of include/cae_hip.h (CAE_ELEM_*): 0 fp32, 1 fp32 big-endian, 2 fp64, 3 fp64 big-endian.  A big-endian
+// slab is the NetCDF-3 file's bytes copied to HBM as they are; the swap happens in registers.
+template <int K> struct CmElem;
+template <> struct CmElem<0> { static constexpr int bytes = 4; };
+template <> struct CmElem<1> { static constexpr int bytes = 4; };
+template <> struct CmElem<2> { static constexpr int bytes = 8; };
+template <> struct CmElem<3> { static constexpr int bytes = 8; };
+
+template <int K>
+__device__ __forceinline__ double cm_word(unsigned long long w) {
+    if constexpr (K == 0) return (double)__uint_as_float((unsigned)w);
+    else if constexpr (K == 1) return (double)__uint_as_float(__builtin_bswap32((unsigned)w));
+    else if constexpr (K == 2) return __longlong_as_double((long long)w);
+    else return __longlong_as_double((long long)__builtin_bswap64(w));
+}
+
+// element e of a case (element-aligned pointer)
+template <int K>
+__device__ __forceinline__ double cm_load1(const unsigned char* c, long long e) {
+    if constexpr (CmElem<K>::bytes == 4) return cm_word<K>(reinterpret_cast<const unsigned*>(c)[e]);
+    else return cm_word<K>(reinterpret_cast<const unsigned long long*>(c)[e]);
+}
+
+// elements e .. e+3: 16-byte loads when `vec` (the caller checked the alignment), else four scalar loads
+template <int K>
+__device__ __forceinline__ void cm_load4(const unsigned char* c, long long e, bool vec, double v[4]) {
+    if (vec) {
+        if constexpr (CmElem<K>::bytes == 4) {
+            const uint4 w = *reinterpret_cast<const uint4*>(c + e * 4);
+            v[0] = cm_word<K>(w.x);
+            v[1] = cm_word<K>(w.y);
+            v[2] = cm_word<K>(w.z);
+            v[3] = cm_word<K>(w.w);
+        } else {
+            const ulonglong2 w0 = *reinterpret_cast<const ulonglong2*>(c + e * 8);
+            const ulonglong2 w1 = *reinterpret_cast<const ulonglong2*>(c + e * 8 + 16);
+            v[0] = cm_word<K>(w0.x);
+            v[1] = cm_word<K>(w0.y);
+            v[2] = cm_word<K>(w1.x);
+            v[3] = cm_word<K>(w1.y);
+        }
+    } else {
+        for (int j = 0; j < 4; j++) v[j] = cm_load1<K>(c, e + j);
+    }
+}
+
+__device__ __forceinline__ void cm_acc(double p, double a, double& s1, double& s2) {
+    const double d = p - a;     // fp64: numpy's promotion of the float64 prediction against the target
+    s1 += fabs(d);
+    s2 += d * d;
+}
+
+// One wave per (case, chunk) item.  A case is cut at its first element h where both p and a are 16 bytes aligned: the
+// head [0, h) and the tail after the last whole 4-element group are summed element by element by the lanes of chunk 0;
+// the groups in between are split into chunks of CM_GROUPS groups, one lane taking every 64th group in order.  A lane's
+// sums, the fixed shuffle tree over the wave and the chunk-ordered fold (k_case_fold) depend on the launch shape and the
+// case's alignment only, so the result is the same bits from run to run.  No atomics: each item's two sums are plain
+// stores into out[item] - the partials (nch > 1) or the case's result (nch == 1).  NaN and Inf pass through untouched.
+constexpr int CM_GROUPS = 1024;          // 4096 elements per chunk
+constexpr int CM_WAVES = 4;              // waves per 256-thread workgroup
+
+template <int KP, int KA>
+__global__ void __launch_bounds__(256) k_case_measures(const unsigned char* __restrict__ p, long long p_stride,
+                                                       const unsigned char* __restrict__ a, long long a_stride,
+                                                       long long plane, int nch, long long items,
+                                                       double* __restrict__ out) {
+    constexpr int EP = CmElem<KP>::bytes, EA = CmElem<KA>::bytes;
+    const int lane = threadIdx.x & 63;
+    for (long long item = (long long)blockIdx.x * CM_WAVES + (threadIdx.x >> 6); item < items;
+         item += (long long)gridDim.x * CM_WAVES) {
+        const long long cs = item / nch;
+        const int ch = (int)(item - cs * nch);
+        const unsigned char* pc = p + cs * p_stride * EP;
+        const unsigned char* ac = a + cs * a_stride * EA;
+        int h = -1;
+        for (int t = 3; t >= 0; t--)
+            if ((((uintptr_t)(pc + t * EP) | (uintptr_t)(ac + t * EA)) & 15) == 0) h = t;
+        const bool vec = h >= 0;
+        const long long head = vec ? (h < plane ? h : plane) : 0;
+        const long long groups = (plane - head) >> 2;
+        const long long tail0 = head + (groups << 2);
+        double s1 = 0.0, s2 = 0.0;
+        if (ch == 0) {
+            if (lane < head) cm_acc(cm_load1<KP>(pc, lane), cm_load1<KA>(ac, lane), s1, s2);
+            else if (lane >= 4 && lane - 4 < plane - tail0)
+                cm_acc(cm_load1<KP>(pc, tail0 + lane - 4), cm_load1<KA>(ac, tail0 + lane - 4), s1, s2);
+        }
+        const long long g0 = (long long)ch * CM_GROUPS;
+        const long long g1 = g0 + CM_GROUPS < groups ? g0 + CM_GROUPS : groups;
+        long long g = g0 + lane;
+        for (; g + 3 * 64 < g1; g += 4 * 64) {      // four groups in flight per lane, summed in group order
+            double vp[4][4], va[4][4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                cm_load4<KP>(pc, head + ((g + u * 64) << 2), vec, vp[u]);
+                cm_load4<KA>(ac, head + ((g + u * 64) << 2), vec, va[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) cm_acc(vp[u][j], va[u][j], s1, s2);
+        }
+        for (; g < g1; g += 64) {
+            double vp[4], va[4];
+            cm_load4<KP>(pc, head + (g << 2), vec, vp);
+            cm_load4<KA>(ac, head + (g << 2), vec, va);
+#pragma unroll
+            for (int j = 0; j < 4; j++) cm_acc(vp[j], va[j], s1, s2);
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            s1 += __shfl_down(s1, off, 64);
+            s2 += __shfl_down(s2, off, 64);
+        }
+        if (lane == 0) {
+            out[2 * item] = s1;
+            out[2 * item + 1] = s2;
+        }
+    }
+}
+
+// out[i] = sum over chunks k = 0 .. nch-1, in that order, of part[i * nch + k]
+__global__ void __launch_bounds__(256) k_case_fold(const double* __restrict__ part, long long n_case, int nch,
+                                                   double* __restrict__ out) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_case; i += (long long)gridDim.x * 256) {
+        double s1 = 0.0, s2 = 0.0;
+        for (int k = 0; k < nch; k++) {
+            s1 += part[2 * (i * nch + k)];
+            s2 += part[2 * (i * nch + k) + 1];
+        }
+        out[2 * i] = s1;
+        out[2 * i + 1] = s2;
+    }
+}
+
+// ---- ensemble moments (VarAEModel.apply(ensemble_size=K), include/cae_hip.h): per pixel the mean and the sample standard
+// deviation of K fp32 draws, denormalised, in fp64.  Nothing crosses a lane: a pixel's draws are summed by one lane in draw
+// order (d_k = y_k - y_0, s1 = S d_k, s2 = S d_k^2), so there is no fold, no atomic and no order to fix beyond that one.
+// Items and loads are k_case_measures': one wave per (case, chunk of `chunk` 4-pixel groups), a lane takes every 64th group
+// and reads it from each draw with one 16-byte load (four draws in flight), the head before the case's first 16-byte phase
+// and the tail after its last whole group go element by element to the lanes of chunk 0.  With nothing to fold the chunk
+// length is the host's to choose (64 .. CM_GROUPS groups): short chunks when a call brings few cases, so that the waves
+// still cover the device.  The draws of a case share that phase
+// when draw_stride is a multiple of 4 (or one draw arrives); otherwise every load is scalar.
+// FIRST: this call brings draw 0 (y_0 is read from it); otherwise {y_0, s1, s2} come from the workspace planes w0, w1, w2.
+// LAST: this call brings draw K-1 and writes mean / sd (16-byte stores where the case's plane starts on one); otherwise the
+// three values go back to the workspace.  <true, true> touches no workspace: K * 4 bytes read and 16 written per pixel.
+template <int N>
+__device__ __forceinline__ void em_load(const float* c, long long e, bool vec, float v[N]) {
+    if constexpr (N == 4) {
+        if (vec) {
+            const float4 w = *reinterpret_cast<const float4*>(c + e);
+            v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
+            return;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) v[j] = c[e + j];
+}
+
+template <int N>
+__device__ __forceinline__ void em_store(double* dst, long long o, bool vec2, const double v[N]) {
+    if constexpr (N == 4) {
+        if (vec2) {
+            reinterpret_cast<double2*>(dst + o)[0] = make_double2(v[0], v[1]);
+            reinterpret_cast<double2*>(dst + o)[1] = make_double2(v[2], v[3]);
+            return;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) dst[o + j] = v[j];
+}
+
+struct EmArgs {
+    const float* y;             // draw j of case c of this call: y + c * case_stride + j * draw_stride, `plane` floats
+    long long case_stride, draw_stride, plane;
+    int kc, K;                  // draws in this call, draws in all
+    int nch, chunk;             // chunks per case, 4-pixel groups per chunk
+    long long items;
+    double vmin, range;
+    double* mean;               // (n_case, plane) each; sd may be null
+    double* sd;
+    float* w0;                  // workspace planes (n_case, plane): y_0, s1, s2
+    double* w1;
+    double* w2;
+};
+
+// N pixels from element e of the case that starts at yc; o = the pixels' index in the (n_case, plane) output planes
+template <bool FIRST, bool LAST, int N>
+__device__ __forceinline__ void em_pixels(const EmArgs& a, const float* yc, long long e, long long o, bool vec, bool vec2) {
+    double y0[N], s1[N], s2[N];
+    int k = 0;
+    if constexpr (FIRST) {
+        float v[N];
+        em_load<N>(yc, e, vec, v);
+#pragma unroll
+        for (int j = 0; j < N; j++) y0[j] = (double)v[j], s1[j] = 0.0, s2[j] = 0.0;    // (d_0 = 0 adds nothing)
+        k = 1;
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++) y0[j] = (double)a.w0[o + j], s1[j] = a.w1[o + j], s2[j] = a.w2[o + j];
+    }
+    for (; k + 3 < a.kc; k += 4) {      // four draws in flight per lane, summed in draw order
+        float v[4][N];
+#pragma unroll
+        for (int u = 0; u < 4; u++) em_load<N>(yc + (k + u) * a.draw_stride, e, vec, v[u]);
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+#pragma unroll
+            for (int j = 0; j < N; j++) {
+                const double d = (double)v[u][j] - y0[j];
+                s1[j] += d;
+                s2[j] += d * d;
+            }
+    }
+    for (; k < a.kc; k++) {
+        float v[N];
+        em_load<N>(yc + k * a.draw_stride, e, vec, v);
+#pragma unroll
+        for (int j = 0; j < N; j++) {
+            const double d = (double)v[j] - y0[j];
+            s1[j] += d;
+            s2[j] += d * d;
+        }
+    }
+    if constexpr (LAST) {
+        const double K = (double)a.K, ar = fabs(a.range);
+        double m[N], s[N];
+#pragma unroll
+        for (int j = 0; j < N; j++) {
+            m[j] = a.vmin + (y0[j] + s1[j] / K) * a.range;
+            const double var = (s2[j] - s1[j] * s1[j] / K) / (K - 1.0);
+            s[j] = sqrt(var < 0.0 ? 0.0 : var) * ar;      // (a NaN stays a NaN)
+        }
+        em_store<N>(a.mean, o, vec2, m);
+        if (a.sd) em_store<N>(a.sd, o, vec2, s);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++) a.w0[o + j] = (float)y0[j], a.w1[o + j] = s1[j], a.w2[o + j] = s2[j];
+    }
+}
+
+template <bool FIRST, bool LAST>
+__global__ void __launch_bounds__(256) k_ensemble_moments(const EmArgs a) {
+    const int lane = threadIdx.x & 63;
+    const bool same_phase = (a.draw_stride & 3) == 0 || a.kc == 1;
+    for (long long item = (long long)blockIdx.x * CM_WAVES + (threadIdx.x >> 6); item < a.items;
+         item += (long long)gridDim.x * CM_WAVES) {
+        const long long cs = item / a.nch;
+        const int ch = (int)(item - cs * a.nch);
+        const float* yc = a.y + cs * a.case_stride;
+        const long long o0 = cs * a.plane;
+        int h = 0;
+        if (same_phase)
+            for (int t = 3; t >= 0; t--)
+                if (((uintptr_t)(yc + t) & 15) == 0) h = t;
+        const long long head = h < a.plane ? h : a.plane;
+        const long long groups = (a.plane - head) >> 2;
+        const long long tail0 = head + (groups << 2);
+        // 16-byte stores: the first group of the case lands on a 16-byte boundary of both output planes
+        const bool vec2 = (((uintptr_t)(a.mean + o0 + head) | (a.sd ? (uintptr_t)(a.sd + o0 + head) : 0)) & 15) == 0;
+        if (ch == 0) {
+            if (lane < head) em_pixels<FIRST, LAST, 1>(a, yc, lane, o0 + lane, false, false);
+            else if (lane >= 4 && lane - 4 < a.plane - tail0)
+                em_pixels<FIRST, LAST, 1>(a, yc, tail0 + lane - 4, o0 + tail0 + lane - 4, false, false);
+        }
+        const long long g0 = (long long)ch * a.chunk;
+        const long long g1 = g0 + a.chunk < groups ? g0 + a.chunk : groups;
+        for (long long g = g0 + lane; g < g1; g += 64)
+            em_pixels<FIRST, LAST, 4>(a, yc, head + (g << 2), o0 + head + (g << 2), same_phase, vec2);
+    }
+}
+
+// ---- case pages (evaluate_cae's per-case images): the value range of channel 0 and its palette indices.
+// KS is the source's element kind, KB the kind of the optional operand subtracted from it in fp64 (-1: none).
+template <int K> struct CpBytes { static constexpr int bytes = CmElem<K>::bytes; };
+template <> struct CpBytes<-1> { static constexpr int bytes = 4; };
+
+template <int KS, int KB>
+__device__ __forceinline__ double cp_value1(const unsigned char* sc, const unsigned char* bc, long long e) {
+    const double v = cm_load1<KS>(sc, e);
+    if constexpr (KB >= 0) return v - cm_load1<KB>(bc, e);
+    else return v;
+}
+
+template <int KS, int KB>
+__device__ __forceinline__ void cp_value4(const unsigned char* sc, const unsigned char* bc, long long e, bool vec,
+                                          double v[4]) {
+    cm_load4<KS>(sc, e, vec, v);
+    if constexpr (KB >= 0) {
+        double b[4];
+        cm_load4<KB>(bc, e, vec, b);
+#pragma unroll
+        for (int j = 0; j < 4; j++) v[j] -= b[j];
+    }
+}
+
+// NaN and +-Inf are left out; min / max compare by value
+__device__ __forceinline__ void cp_range_acc(double v, double& mn, double& mx, long long& n) {
+    if (fabs(v) < __builtin_huge_val()) {
+        mn = v < mn ? v : mn;
+        mx = v > mx ? v : mx;
+        n++;
+    }
+}
+
+// k_case_measures' items and loads: one wave per (case, 4096-element chunk), 16-byte loads from the case's first common
+// 16-byte phase on.  A wave keeps min / max / count over all its items, the workgroup's four waves meet in LDS and
+// part[blockIdx.x] = {min, max, count} is one plain store: no atomics.  min and max do not depend on the order and the
+// count is an integer, so the result is the same from run to run.
+template <int KS, int KB>
+__global__ void __launch_bounds__(256) k_case_range(const unsigned char* __restrict__ s, long long s_stride,
+                                                    const unsigned char* __restrict__ b, long long b_stride,
+                                                    long long plane, int nch, long long items,
+                                                    double* __restrict__ part) {
+    constexpr int ES = CpBytes<KS>::bytes, EB = CpBytes<KB>::bytes;
+    __shared__ double red[CM_WAVES][3];
+    const int lane = threadIdx.x & 63;
+    double mn = __builtin_huge_val(), mx = -__builtin_huge_val();
+    long long cnt = 0;
+    for (long long item = (long long)blockIdx.x * CM_WAVES + (threadIdx.x >> 6); item < items;
+         item += (long long)gridDim.x * CM_WAVES) {
+        const long long cs = item / nch;
+        const int ch = (int)(item - cs * nch);
+        const unsigned char* sc = s + cs * s_stride * ES;
+        const unsigned char* bc = KB >= 0 ? b + cs * b_stride * EB : nullptr;
+        int h = -1;
+        for (int t = 3; t >= 0; t--)
+            if ((((uintptr_t)(sc + t * ES) | (KB >= 0 ? (uintptr_t)(bc + t * EB) : 0)) & 15) == 0) h = t;
+        const bool vec = h >= 0;
+        const long long head = vec ? (h < plane ? h : plane) : 0;
+        const long long groups = (plane - head) >> 2;
+        const long long tail0 = head + (groups << 2);
+        if (ch == 0) {
+            if (lane < head) cp_range_acc(cp_value1<KS, KB>(sc, bc, lane), mn, mx, cnt);
+            else if (lane >= 4 && lane - 4 < plane - tail0)
+                cp_range_acc(cp_value1<KS, KB>(sc, bc, tail0 + lane - 4), mn, mx, cnt);
+        }
+        const long long g0 = (long long)ch * CM_GROUPS;
+        const long long g1 = g0 + CM_GROUPS < groups ? g0 + CM_GROUPS : groups;
+        long long g = g0 + lane;
+        for (; g + 3 * 64 < g1; g += 4 * 64) {      // four groups in flight per lane
+            double v[4][4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) cp_value4<KS, KB>(sc, bc, head + ((g + u * 64) << 2), vec, v[u]);
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) cp_range_acc(v[u][j], mn, mx, cnt);
+        }
+        for (; g < g1; g += 64) {
+            double v[4];
+            cp_value4<KS, KB>(sc, bc, head + (g << 2), vec, v);
+#pragma unroll
+            for (int j = 0; j < 4; j++) cp_range_acc(v[j], mn, mx, cnt);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double omn = __shfl_down(mn, off, 64), omx = __shfl_down(mx, off, 64);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+        cnt += __shfl_down(cnt, off, 64);
+    }
+    if (lane == 0) {
+        red[threadIdx.x >> 6][0] = mn;
+        red[threadIdx.x >> 6][1] = mx;
+        red[threadIdx.x >> 6][2] = (double)cnt;      // exact: far below 2^53
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < CM_WAVES; w++) {
+            mn = red[w][0] < mn ? red[w][0] : mn;
+            mx = red[w][1] > mx ? red[w][1] : mx;
+            red[0][2] += red[w][2];
+        }
+        part[3 * (size_t)blockIdx.x] = mn;
+        part[3 * (size_t)blockIdx.x + 1] = mx;
+        part[3 * (size_t)blockIdx.x + 2] = red[0][2];
+    }
+}
+
+// out = the fold of n_part workgroup partials {min, max, count}; one workgroup
+__global__ void __launch_bounds__(256) k_range_fold(const double* __restrict__ part, int n_part, double* __restrict__ out) {
+    __shared__ double red[CM_WAVES][3];
+    double mn = __builtin_huge_val(), mx = -__builtin_huge_val(), cnt = 0.0;
+    for (int i = threadIdx.x; i < n_part; i += 256) {
+        mn = part[3 * i] < mn ? part[3 * i] : mn;
+        mx = part[3 * i + 1] > mx ? part[3 * i + 1] : mx;
+        cnt += part[3 * i + 2];                       // integers below 2^53: exact in any order
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double omn = __shfl_down(mn, off, 64), omx = __shfl_down(mx, off, 64);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+        cnt += __shfl_down(cnt, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6][0] = mn;
+        red[threadIdx.x >> 6][1] = mx;
+        red[threadIdx.x >> 6][2] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < CM_WAVES; w++) {
+            mn = red[w][0] < mn ? red[w][0] : mn;
+            mx = red[w][1] > mx ? red[w][1] : mx;
+            cnt += red[w][2];
+        }
+        out[0] = mn;
+        out[1] = mx;
+        out[2] = cnt;
+    }
+}
+
+// The palette index of one value: 0 for NaN, else 1 + the nearest of 255 levels over [lo, hi] (all of them the middle
+// level when hi <= lo).  fp64, every operation rounded on its own - a numpy restatement gives the same bytes only if
+// the multiply and the add are not fused.
+__device__ __forceinline__ unsigned cp_index(double v, double lo, double hi) {
+#pragma clang fp contract(off)
+    if (v != v) return 0u;
+    double t = 0.5;
+    if (hi > lo) {
+        t = (v - lo) / (hi - lo);
+        t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+    }
+    const double scaled = t * 254.0;
+    return 1u + (unsigned)(int)(scaled + 0.5);
+}
+
+// A selected case's output is one flat stream of height * (width + 1) bytes: PNG scanlines, each a filter byte 0 and
+// `width` palette indices.  The stream is cut at its first 4-byte aligned address: a lane assembles one aligned dword of
+// four output bytes (the row and column of its first byte by one 32-bit division, the other three by stepping) and
+// stores it; consecutive lanes store consecutive dwords.  The up to 3 bytes before and after the dwords are byte stores
+// by lanes of chunk 0.  The four source elements of a dword are consecutive in the plane (a filter byte in between costs
+// nothing) but at any element phase, so they are element loads: four loads per lane, the wave's four covering the same
+// lines.  One wave per (selected case, RC_DWORDS dwords) item.  A case index outside [0, n_case) draws index 0.
+constexpr int RC_DWORDS = 1024;          // 4096 output bytes per chunk
+
+template <int KS, int KB>
+__device__ __forceinline__ unsigned cp_pixel(const unsigned char* sc, const unsigned char* bc, unsigned y, unsigned c,
+                                             unsigned height, unsigned width, bool flip, bool valid, double lo,
+                                             double hi) {
+    const unsigned sy = flip ? height - 1u - y : y;
+    const long long e = (long long)sy * width + (c ? c - 1u : 0u);       // always inside the plane
+    const unsigned idx = valid ? cp_index(cp_value1<KS, KB>(sc, bc, e), lo, hi) : 0u;
+    return c ? idx : 0u;
+}
+
+template <int KS, int KB>
+__global__ void __launch_bounds__(256) k_render_cases(const unsigned char* __restrict__ s, long long s_stride,
+                                                      const unsigned char* __restrict__ b, long long b_stride,
+                                                      const int* __restrict__ cases, long long n_case, unsigned height,
+                                                      unsigned width, double lo, double hi, int flip_y, int nch,
+                                                      long long items, unsigned char* __restrict__ out) {
+    constexpr int ES = CpBytes<KS>::bytes, EB = CpBytes<KB>::bytes;
+    const unsigned lane = threadIdx.x & 63;
+    const unsigned pitch = width + 1u;
+    const unsigned len = height * pitch;            // the host keeps it below 2^31
+    const bool flip = flip_y != 0;
+    for (long long item = (long long)blockIdx.x * CM_WAVES + (threadIdx.x >> 6); item < items;
+         item += (long long)gridDim.x * CM_WAVES) {
+        const long long k = item / nch;
+        const unsigned ch = (unsigned)(item - k * nch);
+        long long cs = cases ? (long long)cases[k] : k;
+        const bool valid = cs >= 0 && cs < n_case;
+        if (!valid) cs = 0;
+        const unsigned char* sc = s + cs * s_stride * ES;
+        const unsigned char* bc = KB >= 0 ? b + cs * b_stride * EB : nullptr;
+        unsigned char* ob = out + k * (long long)len;
+        unsigned head = (4u - (unsigned)((uintptr_t)ob & 3)) & 3u;
+        if (head > len) head = len;
+        const unsigned ndw = (len - head) >> 2;
+        const unsigned tail0 = head + (ndw << 2);
+        if (ch == 0) {
+            unsigned q = len;
+            if (lane < head) q = lane;
+            else if (lane >= 4 && lane - 4 < len - tail0) q = tail0 + lane - 4;
+            if (q < len) {
+                const unsigned y = q / pitch;
+                ob[q] = (unsigned char)cp_pixel<KS, KB>(sc, bc, y, q - y * pitch, height, width, flip, valid, lo, hi);
+            }
+        }
+        const unsigned d0 = ch * RC_DWORDS;
+        const unsigned d1 = d0 + RC_DWORDS < ndw ? d0 + RC_DWORDS : ndw;
+        for (unsigned d = d0 + lane; d < d1; d += 64) {
+            const unsigned q = head + (d << 2);
+            unsigned y = q / pitch;
+            unsigned c = q - y * pitch;
+            unsigned w = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                w |= cp_pixel<KS, KB>(sc, bc, y, c, height, width, flip, valid, lo, hi) << (8 * j);
+                if (++c == pitch) {
+                    c = 0;
+                    y++;
+                }
+            }
+            *reinterpret_cast<unsigned*>(ob + q) = w;
+        }
+    }
+}
+
+}  // namespace cae

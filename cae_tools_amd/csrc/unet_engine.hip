@@ -28,10 +28,11 @@
 
 // The ConvAE path's 16x16-tile MFMA GEMM (kernels_gemm.h: four waves split K, one launch for a Linear layer's weight gradient
 // beside its input gradient) for the SMALL Linear layers here (fc -> latent -> fc): the convolution tile engine's strided
-// GEMM policy runs such a layer in a single workgroup's chunk loop, 30-40 us for a few hundred kFLOP.  Its own namespace, as
-// in ctbwd.hip, so that the kernels' host stubs do not collide with engine.hip's.
+// GEMM policy runs such a layer in a single workgroup's chunk loop, 30-40 us for a few hundred kFLOP.  The GEMM header and
+// the helpers it uses, and nothing else, inside a namespace of this file: engine.hip's unit defines k_gemm16 / k_gemm16_pair
+// too, and the kernels' host stubs must not collide with its.
 namespace ugemm {
-#include "kernels_generic.h"
+#include "device_common.h"
 #include "kernels_gemm.h"
 }  // namespace ugemm
 

@@ -1,7 +1,7 @@
 """Bitwise run-to-run reproducibility of the training step (SURVEY.md §5 / §7 "deterministic reduction mode").
 
 Every cross-workgroup sum of the ConvAE path is a set of fp64 atomic adds whose order varies from run to run.  The addends
-are rounded to a fixed power-of-two grid first (kernels_generic.h acc_add), which makes the adds exact and hence independent
+are rounded to a fixed power-of-two grid first (acc_grid.h acc_add), which makes the adds exact and hence independent
 of their order; the few cross-wave sums that went through fp32 LDS atomics now have one writer per slot and a fixed fold
 order.  So two runs of the same steps from the same state give the same BITS - not "equal to 1e-16" - in every parameter,
 moment, running statistic and loss, whether the steps are replayed from a captured graph, launched one by one, or taken

@@ -12,7 +12,10 @@ mkdir -p "$OBJ"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -fsanitize=address -fno-gpu-sanitize -Wno-cuda-compat -Wno-pass-failed -I$ROOT/include -I$ROOT/cae_tools_amd/csrc"
 pids=()
-for f in engine ctbwd vae_engine unet_engine linear_engine; do
+objs=()
+for src in "$ROOT"/cae_tools_amd/csrc/*.hip; do
+  f=$(basename "$src" .hip)
+  objs+=("$OBJ/$f.o")
   if [ ! -f "$OBJ/$f.o" ] || [ -n "$(find "$ROOT/cae_tools_amd/csrc" "$ROOT/include" -newer "$OBJ/$f.o" \( -name '*.h' -o -name "$f.hip" \) | head -1)" ]; then
     $HIPCC $FLAGS -c "$ROOT/cae_tools_amd/csrc/$f.hip" -o "$OBJ/$f.o" > "$OBJ/$f.log" 2>&1 &
     pids+=($!)
@@ -20,5 +23,5 @@ for f in engine ctbwd vae_engine unet_engine linear_engine; do
 done
 for p in "${pids[@]}"; do wait "$p"; done
 /opt/rocm/lib/llvm/bin/clang++ -std=c++17 -g -fsanitize=address -I"$ROOT/include" -c "$ROOT/tests/asan/plan_check.cpp" -o "$OBJ/plan_check.o"
-$HIPCC --offload-arch=gfx950 -fsanitize=address -fno-gpu-sanitize -o "$OBJ/plan_check" "$OBJ/plan_check.o" "$OBJ/engine.o" "$OBJ/ctbwd.o" "$OBJ/vae_engine.o" "$OBJ/unet_engine.o" "$OBJ/linear_engine.o" -ldl > "$OBJ/link.log" 2>&1
+$HIPCC --offload-arch=gfx950 -fsanitize=address -fno-gpu-sanitize -o "$OBJ/plan_check" "$OBJ/plan_check.o" "${objs[@]}" -ldl > "$OBJ/link.log" 2>&1
 ASAN_OPTIONS=detect_leaks=1:protect_shadow_gap=0 "$OBJ/plan_check"
