@@ -668,7 +668,7 @@ bool ct_fwd_plan(const cae_engine* e, int batch, const ConvLayer& L, int layer, 
     c.B = batch; c.Cin = L.cin; c.H = L.hin; c.W = L.win; c.Cout = L.cout; c.OH = L.hout; c.OW = L.wout;
     c.QH = (L.hout + 1) / 2; c.QW = (L.wout + 1) / 2;
     c.PW = c.QW + 1;
-    c.plane = ((c.QH + 1) * c.PW) | 1;
+    c.inv_qw = 1.0f / (float)c.QW; c.inv_w = 1.0f / (float)c.W;
     c.tiles = (c.QH * c.QW + 15) / 16;
     const int taps = ((L.kh + 1) / 2 + L.kh / 2) * ((L.kw + 1) / 2 + L.kw / 2);   // sum of n_p over the four parities = kh * kw
     const int mf = L.cin * taps / 4;
@@ -680,8 +680,19 @@ bool ct_fwd_plan(const cae_engine* e, int batch, const ConvLayer& L, int layer, 
     c.ks = ks; c.rt = rt;
     c.tg = (c.tiles + rt - 1) / rt;
     waves = rt * ks;
+    // A workgroup stages the band of input rows its tile group reads, (first quad row - 1) .. last quad row: the LDS plane
+    // holds the tallest band of the image.  Which layers take this kernel is still decided on the whole padded image, as it
+    // was when every workgroup staged it (the splits above were only measured on maps that small).
+    int brows = 0;
+    for (int g = 0; g < c.tg; g++) {
+        const int qs = g * rt * 16, qe = std::min(qs + rt * 16, c.QH * c.QW);
+        brows = std::max(brows, (qe - 1) / c.QW - qs / c.QW + 2);
+    }
+    c.plane = (brows * c.PW) | 1;
+    const int whole = ((c.QH + 1) * c.PW) | 1;
     lds = ct_fwd_lds_bytes(L.cin, c.plane, L.kh, L.kw, waves, ks);
-    return !(lds > 150 * 1024 || c.plane >= kDivSmallMaxD || (long long)L.cin * c.plane >= kDivSmallMaxN);
+    return !(ct_fwd_lds_bytes(L.cin, whole, L.kh, L.kw, waves, ks) > 150 * 1024 || whole >= kDivSmallMaxD ||
+             (long long)L.cin * whole >= kDivSmallMaxN);
 }
 
 // the layer's forward on k_ct_fwd_lds: only where ct_fwd_plan holds (choose_dec_fwd)

@@ -4,8 +4,9 @@
 // global memory and re-applied BatchNorm+ReLU per use: 53 vector instructions per MFMA, bound by instruction issue.
 //
 // Here a workgroup owns one image (or a band of its output) and one block of 16 output channels:
-//   1. coalesced global reads -> LDS:  the image, BatchNorm+ReLU of the producer applied ONCE per element, inside a zero
-//      border (so a tap outside the map needs no predicate), and the weight slice [Cin][16 co][kh*kw] as stored;
+//   1. coalesced global reads -> LDS:  the rows of the image its quads read, BatchNorm+ReLU of the producer applied ONCE per
+//      element, inside a zero border (so a tap outside the map needs no predicate), and the weight slice [Cin][16 co][kh*kw]
+//      as stored;
 //   2. v_mfma_f32_16x16x4_f32 with both operands read from LDS by one ds_read_b32 each at loop-invariant lane offsets
 //      (no address arithmetic in the loop: the channel stride is an immediate offset);
 //   3. bias, stores and the BatchNorm sums of THIS layer in the epilogue.
@@ -22,7 +23,9 @@ namespace cae {
 
 struct CtFwd {
     int B, Cin, H, W, Cout, OH, OW, QH, QW;
-    int PW, plane;   // padded image in LDS: rows -1 .. QH-1 ((QH+1) rows) of PW = QW+1 columns; plane = odd size of one channel
+    int PW, plane;   // padded band in LDS: input rows (first quad row - 1) .. last quad row of the workgroup's tile group, PW = QW+1
+                     // columns from -1; plane = odd size of one channel, sized for the tallest band of the image
+    float inv_qw, inv_w;   // 1.0f / QW, 1.0f / W for div_small (from the host: a division ahead of the first load delays it)
     int tiles;       // row tiles (16 quads) per image
     int rt;          // row tiles per workgroup
     int ks;          // waves that share a row tile and split the input channels; blockDim = 64 * rt * ks
@@ -55,7 +58,7 @@ __device__ __forceinline__ void ct_load4(const float* __restrict__ ap, const flo
 }
 
 // grid (B * tg, ceil(Cout / 16)), block 64 * rt * ks, dynamic LDS = ct_fwd_lds_bytes(...)
-constexpr int kCtImgRegs = 12;   // image elements a thread holds between the global loads and the LDS scatter
+constexpr int kCtImgRegs = 8;    // band elements a thread holds between the global loads and the LDS scatter
 
 template <int KH, int KW>
 __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
@@ -92,14 +95,37 @@ __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
     }
     const int cb = blockIdx.y;
 
-    // Every global read of the prologue is issued before anything waits: the image (in source order: coalesced, no
-    // predicates), then the weight slice, then the BatchNorm sums inside bn_consts.  A load under a predicate is a branch
-    // around the load plus a wait at its consumer - one memory round trip per loop iteration (3.6 us for nine of them).
-    const int HW = a.H * a.W, n_img = a.Cin * HW;
-    const float* src = a.in + (size_t)b * n_img;
+    // The band: this tile group's quads qs .. qs + nq - 1 cover quad rows qy0 .. qy1 and read input rows qy0 - 1 .. qy1 (a quad
+    // (m, n) sees inputs (m - j, n - i), j, i in {0, 1}).  Only those rows are staged - the ones inside the map, ry0 .. ry0 + nr - 1,
+    // from memory, what lies outside stays the zero border - where every group of an image used to stage the whole image.
+    const int Q = a.QH * a.QW;
+    const float inv_qw = a.inv_qw;
+    const int qs = g * a.rt * 16, nq = min(a.rt * 16, Q - qs);
+    const int qy0 = div_small(qs, inv_qw), qy1 = div_small(qs + nq - 1, inv_qw);
+    const int ry0 = max(qy0 - 1, 0), nr = max(min(qy1, a.H - 1) - ry0 + 1, 0);   // (a band below the map reads nothing)
+    // A channel's band is one run of RW consecutive floats.  Thread slots are dealt P = 2^lg >= RW to a channel, so that a
+    // slot's channel and position are a shift and a mask: the loads wait for no division.
+    const int HW = a.H * a.W, RW = nr * a.W;
+    const int lg = 32 - __clz(max(RW, 2) - 1), n_slots = a.Cin << lg;
+
+    // Every global read of the prologue is issued before anything waits: the band (no predicates: a slot past its run or past
+    // the last channel reads a clamped address), then the weight slice, then the BatchNorm sums inside bn_consts.  A load
+    // under a predicate is a branch around the load plus a wait at its consumer - one memory round trip per loop iteration
+    // (3.6 us for nine of them).
+    const float* src = a.in + (size_t)b * a.Cin * HW + min(ry0, a.H - 1) * a.W;
     float iv[kCtImgRegs];
+    auto fetch = [&](int slot) { return src[min(slot >> lg, a.Cin - 1) * HW + min(slot & ((1 << lg) - 1), max(RW, 1) - 1)]; };
 #pragma unroll
-    for (int u = 0; u < kCtImgRegs; u++) iv[u] = src[min(tid + u * nthr, n_img - 1)];
+    for (int u = 0; u < kCtImgRegs / 2; u++) iv[u] = fetch(tid + u * nthr);
+    // (the second half only where the band has that many slots - a branch the whole workgroup takes alike: a load that reads
+    // nothing still costs its issue slot ahead of the weight requests)
+    const bool more = n_slots > kCtImgRegs / 2 * nthr;
+#pragma unroll
+    for (int u = kCtImgRegs / 2; u < kCtImgRegs; u++) iv[u] = 0.f;
+    if (more) {
+#pragma unroll
+        for (int u = kCtImgRegs / 2; u < kCtImgRegs; u++) iv[u] = fetch(tid + u * nthr);
+    }
 
     // the producer's BatchNorm sums (the usual mode: batch statistics, one thread per input channel) are requested here, with
     // the image and ahead of the weights, and turned into constants behind the weight stores: one wait covers all three
@@ -168,38 +194,33 @@ __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
         }
     }
     if (tid < 32) lstat[tid] = 0.0;
-    {   // zero the padded image (its border stays zero: a tap outside the map then needs no predicate)
+    {   // zero the padded band (its border stays zero: a tap outside the map then needs no predicate)
         const int n4 = (a.Cin * a.plane + 3) >> 2;
         for (int idx = tid; idx < n4; idx += nthr) reinterpret_cast<float4*>(img)[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
-    {   // the image: BatchNorm + ReLU once per element, scattered into the zero border
-        const float inv_hw = 1.0f / (float)HW, inv_w = 1.0f / (float)a.W;
+    {   // the band: BatchNorm + ReLU once per element, scattered into the zero border
         const bool bn = a.bn_in.mode != BN_NONE;
-#pragma unroll
-        for (int u = 0; u < kCtImgRegs; u++) {
-            const int idx = tid + u * nthr;
-            if (idx < n_img) {
-                const int ci = div_small(idx, inv_hw), pos = idx - ci * HW;
-                const int iy = div_small(pos, inv_w), ix = pos - iy * a.W;
-                float v = iv[u];
+        const int lrow0 = ry0 - (qy0 - 1);                           // LDS row of input row ry0 (row 0 is input row qy0 - 1)
+        auto put = [&](int slot, float v) {
+            const int ci = slot >> lg, pos = slot & ((1 << lg) - 1);
+            if (ci < a.Cin && pos < RW) {
+                const int iy = div_small(pos, a.inv_w), ix = pos - iy * a.W;
                 if (bn) {
                     const float4 k = cin4[ci];
                     v = fmaxf(0.f, fmaf(v - k.x, k.y, k.z));
                 }
-                img[ci * a.plane + (iy + 1) * a.PW + ix + 1] = v;
+                img[ci * a.plane + (iy + lrow0) * a.PW + ix + 1] = v;
             }
+        };
+#pragma unroll
+        for (int u = 0; u < kCtImgRegs / 2; u++) put(tid + u * nthr, iv[u]);
+        if (more) {
+#pragma unroll
+            for (int u = kCtImgRegs / 2; u < kCtImgRegs; u++) put(tid + u * nthr, iv[u]);
         }
-        for (int idx = tid + kCtImgRegs * nthr; idx < n_img; idx += nthr) {   // images beyond the register batch (rare)
-            const int ci = div_small(idx, inv_hw), pos = idx - ci * HW;
-            const int iy = div_small(pos, inv_w), ix = pos - iy * a.W;
-            float v = src[idx];
-            if (bn) {
-                const float4 k = cin4[ci];
-                v = fmaxf(0.f, fmaf(v - k.x, k.y, k.z));
-            }
-            img[ci * a.plane + (iy + 1) * a.PW + ix + 1] = v;
-        }
+        for (int slot = tid + kCtImgRegs * nthr; slot < n_slots; slot += nthr)   // bands beyond the register batch (rare)
+            put(slot, fetch(slot));
     }
     __syncthreads();
 
@@ -208,10 +229,8 @@ __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
     const int tl = wv / a.ks, kslot = wv - tl * a.ks;
     const int tile = g * a.rt + tl;
     const bool tile_ok = tile < a.tiles;                         // uniform per wave
-    const int Q = a.QH * a.QW;
-    const float inv_qw = 1.0f / (float)a.QW;
     const int qi = tile * 16 + r;
-    const int qic = (tile_ok && qi < Q) ? qi : 0;                // idle rows read quad 0 (never stored)
+    const int qic = (tile_ok && qi < Q) ? qi : qs;               // idle rows read the band's first quad (never stored)
     const int qy = div_small(qic, inv_qw), qx = qic - qy * a.QW;
     const int cper = a.Cin / a.ks, c0 = kslot * cper;            // host: cper % 4 == 0
     const int co = cb * 16 + r;
@@ -225,7 +244,7 @@ __global__ void __launch_bounds__(512) k_ct_fwd_lds(CtFwd a) {
         const float* BP;                                                                             \
         {                                                                                            \
             const int t = q % (NP), dci = q / (NP), j = t / (NI), i = t - j * (NI);                   \
-            AP = img + (c0 + dci) * a.plane + (qy - j + 1) * a.PW + (qx - i + 1);                    \
+            AP = img + (c0 + dci) * a.plane + (qy - j - qy0 + 1) * a.PW + (qx - i + 1);                 \
             BP = wl + (c0 + dci) * WS + r * KKp + ((PY) + 2 * j) * KW + (PX) + 2 * i;                \
         }
         CT_PTRS(NP00, NI0, 0, 0, ap00, bp00)
