@@ -1,0 +1,352 @@
+// stateless_host.h - host only: the entry points of cae_hip.h that use no engine (loader, evaluator, ensemble moments, case
+// pages) over kernels_stateless.h.  Included by engine.hip alone, at the place this code has always had in it.
+#pragma once
+
+extern "C" {
+
+// ---- loader -------------------------------------------------------------------------------------
+
+int cae_scan_f32(const float* x, int64_t n, void* hip_stream, double* out3) {
+    if (!x || n < 1 || !out3) return fail(CAE_ERR_ARG, "cae_scan_f32: bad argument");
+    hipStream_t s = (hipStream_t)hip_stream;
+    int blocks = (int)((n + 256 * 16 - 1) / (256 * 16));
+    if (blocks > 1024) blocks = 1024;
+    if (blocks < 1) blocks = 1;
+    double* part = nullptr;
+    HIP_TRY(hipMalloc(&part, (size_t)blocks * 3 * sizeof(double)));
+    hipLaunchKernelGGL(k_scan, dim3(blocks), dim3(256), 0, s, x, (long long)n, part);
+    std::vector<double> host((size_t)blocks * 3);
+    hipError_t ce = hipMemcpyAsync(host.data(), part, host.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (ce == hipSuccess) ce = hipStreamSynchronize(s);
+    (void)hipFree(part);
+    if (ce != hipSuccess) return fail(CAE_ERR_HIP, "cae_scan_f32: %s", hipGetErrorString(ce));
+    double cnt = 0, lo = INFINITY, hi = -INFINITY;
+    for (int i = 0; i < blocks; i++) {
+        cnt += host[3 * i];
+        lo = std::fmin(lo, host[3 * i + 1]);
+        hi = std::fmax(hi, host[3 * i + 2]);
+    }
+    out3[0] = cnt;
+    out3[1] = lo;
+    out3[2] = hi;
+    return CAE_OK;
+}
+
+int cae_normalise_pack_rows(const float* src, int64_t n, int c_src, int64_t hw, float* dst, int c_dst, int c_off,
+                            float vmin, float range, int enable, const int32_t* dst_row_dev, void* hip_stream) {
+    if (!src || !dst || n < 1 || c_src < 1 || hw < 1 || c_off < 0 || c_off + c_src > c_dst)
+        return fail(CAE_ERR_ARG, "cae_normalise_pack: bad argument");
+    if (n > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_normalise_pack: more than 2^31 - 1 rows");
+    const long long total = (long long)n * c_src * hw;
+    int blocks = (int)((total + 256 * 8 - 1) / (256 * 8));
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_normalise_pack, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream, src, total, c_src,
+                       (long long)hw, dst, c_dst, c_off, vmin, range, enable, (const int*)dst_row_dev);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+int cae_normalise_pack(const float* src, int64_t n, int c_src, int64_t hw, float* dst, int c_dst, int c_off,
+                       float vmin, float range, int enable, void* hip_stream) {
+    return cae_normalise_pack_rows(src, n, c_src, hw, dst, c_dst, c_off, vmin, range, enable, nullptr, hip_stream);
+}
+
+int cae_invert_permutation(const int32_t* perm_dev, int64_t n, int32_t* inverse_dev, void* hip_stream) {
+    if (!perm_dev || !inverse_dev || n < 1 || n > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_invert_permutation: bad argument");
+    hipLaunchKernelGGL(k_invert_perm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream,
+                       (const int*)perm_dev, (long long)n, (int*)inverse_dev);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+int cae_denormalise_f64(const float* y, int64_t n, double vmin, double range, double* out, void* hip_stream) {
+    if (!y || !out || n < 1) return fail(CAE_ERR_ARG, "cae_denormalise_f64: bad argument");
+    int blocks = (int)((n + 256 * 8 - 1) / (256 * 8));
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_denorm_f64, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream, y, (long long)n, vmin, range, out);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+int cae_metric_sums(const float* y, const float* actual, const float* mask, int64_t n_inst, int64_t inst_elems,
+                    double vmin, double range, double* sums, void* hip_stream) {
+    if (!y || !actual || !sums || n_inst < 1 || inst_elems < 1 || n_inst > 65535)
+        return fail(CAE_ERR_ARG, "cae_metric_sums: bad argument");
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(hipMemsetAsync(sums, 0, (size_t)n_inst * 8 * sizeof(double), s));
+    int chunks = (int)((inst_elems + 256 * 16 - 1) / (256 * 16));
+    if (chunks > 64) chunks = 64;
+    hipLaunchKernelGGL(k_metric_sums, dim3(chunks, (unsigned)n_inst), dim3(256), 0, s, y, actual, mask,
+                       (long long)inst_elems, vmin, range, sums);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+int cae_bswap32(void* x, int64_t n, void* hip_stream) {
+    if (!x || n < 0 || ((uintptr_t)x & 15)) return fail(CAE_ERR_ARG, "cae_bswap32: bad argument (16-byte aligned device pointer)");
+    if (n == 0) return CAE_OK;
+    int blocks = (int)((n / 4 + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(k_bswap32, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream, (unsigned*)x, (long long)n);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+// ---- evaluator -------------------------------------------------------------------------------
+
+static int64_t case_chunks(int64_t plane) { return (plane + 4 * CM_GROUPS - 1) / (4 * CM_GROUPS); }
+
+int64_t cae_case_measures_workspace_bytes(int64_t n_case, int64_t plane) {
+    if (n_case < 1 || plane < 1) return 0;
+    const int64_t nch = case_chunks(plane);
+    return nch > 1 ? n_case * nch * 2 * (int64_t)sizeof(double) : 0;
+}
+
+extern "C++" {   // the kind dispatch: templates inside the extern "C" block
+
+template <int KP, int KA>
+static void launch_case_measures(dim3 grid, hipStream_t s, const void* p, int64_t ps, const void* a, int64_t as,
+                                 int64_t plane, int nch, int64_t items, double* out) {
+    hipLaunchKernelGGL((k_case_measures<KP, KA>), grid, dim3(256), 0, s, (const unsigned char*)p, (long long)ps,
+                       (const unsigned char*)a, (long long)as, (long long)plane, nch, (long long)items, out);
+}
+
+template <int KP>
+static void launch_case_measures_a(int ka, dim3 grid, hipStream_t s, const void* p, int64_t ps, const void* a,
+                                   int64_t as, int64_t plane, int nch, int64_t items, double* out) {
+    switch (ka) {
+    case CAE_ELEM_F32: launch_case_measures<KP, 0>(grid, s, p, ps, a, as, plane, nch, items, out); break;
+    case CAE_ELEM_F32_BE: launch_case_measures<KP, 1>(grid, s, p, ps, a, as, plane, nch, items, out); break;
+    case CAE_ELEM_F64: launch_case_measures<KP, 2>(grid, s, p, ps, a, as, plane, nch, items, out); break;
+    default: launch_case_measures<KP, 3>(grid, s, p, ps, a, as, plane, nch, items, out); break;
+    }
+}
+
+}  // extern "C++"
+
+int cae_case_measures(const void* pred, int pred_kind, int64_t pred_stride, const void* actual, int actual_kind,
+                      int64_t actual_stride, int64_t n_case, int64_t plane, double* out, void* workspace,
+                      int64_t workspace_bytes, void* hip_stream) {
+    auto elem_bytes = [](int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; };
+    auto known = [](int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; };
+    if (!pred || !actual || !out || n_case < 1 || plane < 1 || !known(pred_kind) || !known(actual_kind))
+        return fail(CAE_ERR_ARG, "cae_case_measures: bad argument");
+    if (pred_stride < plane || actual_stride < plane)
+        return fail(CAE_ERR_ARG, "cae_case_measures: a case stride is shorter than the plane");
+    if (((uintptr_t)pred % elem_bytes(pred_kind)) || ((uintptr_t)actual % elem_bytes(actual_kind)) || ((uintptr_t)out & 7))
+        return fail(CAE_ERR_ARG, "cae_case_measures: pointers must be aligned to their element size");
+    const int64_t nch = case_chunks(plane);
+    if (nch > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_case_measures: plane too large");
+    const int64_t need = cae_case_measures_workspace_bytes(n_case, plane);
+    if (need > 0 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7)))
+        return fail(CAE_ERR_ARG, "cae_case_measures: needs a workspace of %lld bytes (cae_case_measures_workspace_bytes)",
+                    (long long)need);
+    hipStream_t s = (hipStream_t)hip_stream;
+    const int64_t items = n_case * nch;
+    double* dst = nch > 1 ? (double*)workspace : out;
+    int64_t blocks = (items + CM_WAVES - 1) / CM_WAVES;
+    if (blocks > 8192) blocks = 8192;
+    const dim3 grid((unsigned)blocks);
+    switch (pred_kind) {
+    case CAE_ELEM_F32: launch_case_measures_a<0>(actual_kind, grid, s, pred, pred_stride, actual, actual_stride, plane, (int)nch, items, dst); break;
+    case CAE_ELEM_F32_BE: launch_case_measures_a<1>(actual_kind, grid, s, pred, pred_stride, actual, actual_stride, plane, (int)nch, items, dst); break;
+    case CAE_ELEM_F64: launch_case_measures_a<2>(actual_kind, grid, s, pred, pred_stride, actual, actual_stride, plane, (int)nch, items, dst); break;
+    default: launch_case_measures_a<3>(actual_kind, grid, s, pred, pred_stride, actual, actual_stride, plane, (int)nch, items, dst); break;
+    }
+    HIP_TRY(hipGetLastError());
+    if (nch > 1) {
+        int64_t fb = (n_case + 255) / 256;
+        if (fb > 4096) fb = 4096;
+        hipLaunchKernelGGL(k_case_fold, dim3((unsigned)fb), dim3(256), 0, s, (const double*)workspace, (long long)n_case,
+                           (int)nch, out);
+        HIP_TRY(hipGetLastError());
+    }
+    return CAE_OK;
+}
+
+// ---- ensemble moments --------------------------------------------------------------------------
+
+int64_t cae_ensemble_moments_workspace_bytes(int64_t n_case, int64_t plane) {
+    if (n_case < 1 || plane < 1) return 0;
+    return n_case * plane * (int64_t)(2 * sizeof(double) + sizeof(float));
+}
+
+int cae_ensemble_moments(const float* draws, int64_t case_stride, int64_t draw_stride, int64_t n_case, int64_t plane,
+                         int k_call, int k_done, int k_total, double vmin, double range, double* mean, double* sd,
+                         void* workspace, int64_t workspace_bytes, void* hip_stream) {
+    if (!draws || !mean || n_case < 1 || plane < 1 || k_total < 2 || k_call < 1 || k_done < 0 || k_done + (int64_t)k_call > k_total)
+        return fail(CAE_ERR_ARG, "cae_ensemble_moments: bad argument (k_total >= 2, 1 <= k_call, k_done + k_call <= k_total)");
+    if ((n_case > 1 && case_stride < 0) || (k_call > 1 && draw_stride < 0))
+        return fail(CAE_ERR_ARG, "cae_ensemble_moments: negative stride");
+    // the planes of one call must not overlap: both layouts, [case][draw] and [draw][case], and anything looser
+    const bool case_major = case_stride >= (int64_t)(k_call - 1) * draw_stride + plane && (k_call == 1 || draw_stride >= plane);
+    const bool draw_major = draw_stride >= (n_case - 1) * case_stride + plane && (n_case == 1 || case_stride >= plane);
+    if (!case_major && !draw_major) return fail(CAE_ERR_ARG, "cae_ensemble_moments: the strides make planes overlap");
+    if (((uintptr_t)draws & 3) || ((uintptr_t)mean & 7) || ((uintptr_t)sd & 7))
+        return fail(CAE_ERR_ARG, "cae_ensemble_moments: pointers must be aligned to their element size");
+    const bool first = k_done == 0, last = k_done + k_call == k_total;
+    const int64_t n = n_case * plane;
+    EmArgs a;
+    memset(&a, 0, sizeof a);
+    if (!(first && last)) {
+        const int64_t need = cae_ensemble_moments_workspace_bytes(n_case, plane);
+        if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
+            return fail(CAE_ERR_ARG, "cae_ensemble_moments: draws delivered over several calls need a workspace of %lld bytes "
+                                     "(cae_ensemble_moments_workspace_bytes)", (long long)need);
+        a.w1 = (double*)workspace;
+        a.w2 = a.w1 + n;
+        a.w0 = (float*)(a.w2 + n);
+    }
+    // one wave per (case, chunk of 4-pixel groups): about 4096 waves in all where the call is large enough, chunks of 64 ..
+    // CM_GROUPS groups (nothing is folded, so the cut is free: a pixel's result does not depend on it)
+    const int64_t groups = (plane + 3) / 4;
+    int64_t chunk = (n_case * groups / 4096 + 63) / 64 * 64;
+    chunk = chunk < 64 ? 64 : (chunk > CM_GROUPS ? CM_GROUPS : chunk);
+    const int64_t nch = (groups + chunk - 1) / chunk;
+    if (nch > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_ensemble_moments: plane too large");
+    a.y = draws, a.case_stride = case_stride, a.draw_stride = draw_stride, a.plane = plane;
+    a.kc = k_call, a.K = k_total, a.nch = (int)nch, a.chunk = (int)chunk, a.items = n_case * nch;
+    a.vmin = vmin, a.range = range, a.mean = mean, a.sd = sd;
+    int64_t blocks = (a.items + CM_WAVES - 1) / CM_WAVES;
+    if (blocks > 65536) blocks = 65536;
+    const dim3 grid((unsigned)blocks);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (first && last) hipLaunchKernelGGL((k_ensemble_moments<true, true>), grid, dim3(256), 0, s, a);
+    else if (first) hipLaunchKernelGGL((k_ensemble_moments<true, false>), grid, dim3(256), 0, s, a);
+    else if (last) hipLaunchKernelGGL((k_ensemble_moments<false, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_ensemble_moments<false, false>), grid, dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+// ---- case pages ------------------------------------------------------------------------------
+
+static int64_t range_blocks(int64_t n_case, int64_t plane) {
+    int64_t blocks = (n_case * case_chunks(plane) + CM_WAVES - 1) / CM_WAVES;
+    return blocks > 8192 ? 8192 : blocks;
+}
+
+int64_t cae_case_range_workspace_bytes(int64_t n_case, int64_t plane) {
+    if (n_case < 1 || plane < 1) return 0;
+    return range_blocks(n_case, plane) * 3 * (int64_t)sizeof(double);
+}
+
+extern "C++" {
+
+// one operand pair of the case-page kernels: the source and the optional operand subtracted from it (kind -1: none)
+struct CasePair {
+    const void* src;
+    int64_t src_stride;
+    const void* sub;
+    int64_t sub_stride;
+};
+
+struct RenderArgs {
+    const int* cases;
+    int64_t n_case;
+    unsigned height, width;
+    double lo, hi;
+    int flip_y;
+    unsigned char* out;
+};
+
+template <int KS, int KB>
+static void launch_case_range(dim3 grid, hipStream_t s, const CasePair& p, int64_t plane, int nch, int64_t items,
+                              double* part) {
+    hipLaunchKernelGGL((k_case_range<KS, KB>), grid, dim3(256), 0, s, (const unsigned char*)p.src, (long long)p.src_stride,
+                       (const unsigned char*)p.sub, (long long)p.sub_stride, (long long)plane, nch, (long long)items, part);
+}
+
+template <int KS, int KB>
+static void launch_render_cases(dim3 grid, hipStream_t s, const CasePair& p, const RenderArgs& r, int nch, int64_t items) {
+    hipLaunchKernelGGL((k_render_cases<KS, KB>), grid, dim3(256), 0, s, (const unsigned char*)p.src,
+                       (long long)p.src_stride, (const unsigned char*)p.sub, (long long)p.sub_stride, r.cases,
+                       (long long)r.n_case, r.height, r.width, r.lo, r.hi, r.flip_y, nch, (long long)items, r.out);
+}
+
+// CALL<KS, KB>(args...) for the run-time kinds ks (0..3) and kb (-1..3)
+#define CP_DISPATCH_B(CALL, KS, kb, ...)                  \
+    switch (kb) {                                         \
+    case CAE_ELEM_F32: CALL<KS, 0>(__VA_ARGS__); break;    \
+    case CAE_ELEM_F32_BE: CALL<KS, 1>(__VA_ARGS__); break; \
+    case CAE_ELEM_F64: CALL<KS, 2>(__VA_ARGS__); break;    \
+    case CAE_ELEM_F64_BE: CALL<KS, 3>(__VA_ARGS__); break; \
+    default: CALL<KS, -1>(__VA_ARGS__); break;             \
+    }
+#define CP_DISPATCH(CALL, ks, kb, ...)                                        \
+    switch (ks) {                                                             \
+    case CAE_ELEM_F32: CP_DISPATCH_B(CALL, 0, kb, __VA_ARGS__) break;          \
+    case CAE_ELEM_F32_BE: CP_DISPATCH_B(CALL, 1, kb, __VA_ARGS__) break;       \
+    case CAE_ELEM_F64: CP_DISPATCH_B(CALL, 2, kb, __VA_ARGS__) break;          \
+    default: CP_DISPATCH_B(CALL, 3, kb, __VA_ARGS__) break;                    \
+    }
+
+}  // extern "C++"
+
+// the shared argument checks of cae_case_range / cae_render_cases; kb is set to the dispatch kind of `sub` (-1: none)
+static int case_pair_check(const char* who, const void* src, int src_kind, int64_t src_stride, const void* sub,
+                           int sub_kind, int64_t sub_stride, int64_t plane, int* kb) {
+    auto elem_bytes = [](int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; };
+    auto known = [](int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; };
+    if (!src || !known(src_kind) || (sub && !known(sub_kind))) return fail(CAE_ERR_ARG, "%s: bad argument", who);
+    if (src_stride < plane || (sub && sub_stride < plane))
+        return fail(CAE_ERR_ARG, "%s: a case stride is shorter than the plane", who);
+    if (((uintptr_t)src % elem_bytes(src_kind)) || (sub && ((uintptr_t)sub % elem_bytes(sub_kind))))
+        return fail(CAE_ERR_ARG, "%s: pointers must be aligned to their element size", who);
+    *kb = sub ? sub_kind : -1;
+    return CAE_OK;
+}
+
+int cae_case_range(const void* src, int src_kind, int64_t src_stride, const void* sub, int sub_kind, int64_t sub_stride,
+                   int64_t n_case, int64_t plane, double* out, void* workspace, int64_t workspace_bytes,
+                   void* hip_stream) {
+    if (!out || ((uintptr_t)out & 7) || n_case < 1 || plane < 1) return fail(CAE_ERR_ARG, "cae_case_range: bad argument");
+    int kb = -1;
+    const int rc = case_pair_check("cae_case_range", src, src_kind, src_stride, sub, sub_kind, sub_stride, plane, &kb);
+    if (rc != CAE_OK) return rc;
+    const int64_t nch = case_chunks(plane);
+    if (nch > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_case_range: plane too large");
+    const int64_t need = cae_case_range_workspace_bytes(n_case, plane);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
+        return fail(CAE_ERR_ARG, "cae_case_range: needs a workspace of %lld bytes (cae_case_range_workspace_bytes)",
+                    (long long)need);
+    hipStream_t s = (hipStream_t)hip_stream;
+    const int64_t blocks = range_blocks(n_case, plane);
+    const dim3 grid((unsigned)blocks);
+    const CasePair pair{src, src_stride, sub, sub_stride};
+    CP_DISPATCH(launch_case_range, src_kind, kb, grid, s, pair, plane, (int)nch, n_case * nch, (double*)workspace)
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_range_fold, dim3(1), dim3(256), 0, s, (const double*)workspace, (int)blocks, out);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+int cae_render_cases(const void* src, int src_kind, int64_t src_stride, const void* sub, int sub_kind, int64_t sub_stride,
+                     const int32_t* cases, int64_t n_sel, int64_t n_case, int64_t height, int64_t width, double lo,
+                     double hi, int flip_y, uint8_t* out, void* hip_stream) {
+    if (!out || n_sel < 1 || n_case < 1 || height < 1 || width < 1 || ((uintptr_t)cases & 3))
+        return fail(CAE_ERR_ARG, "cae_render_cases: bad argument");
+    if (height * (width + 1) > 0x7fffffffLL || width > 0x7ffffffeLL)
+        return fail(CAE_ERR_ARG, "cae_render_cases: image too large (height * (width + 1) must stay below 2^31)");
+    if (!(lo - lo == 0.0) || !(hi - hi == 0.0) || !((hi - lo) - (hi - lo) == 0.0))
+        return fail(CAE_ERR_ARG, "cae_render_cases: lo, hi and hi - lo must be finite");
+    int kb = -1;
+    const int rc = case_pair_check("cae_render_cases", src, src_kind, src_stride, sub, sub_kind, sub_stride,
+                                   height * width, &kb);
+    if (rc != CAE_OK) return rc;
+    const int64_t len = height * (width + 1);
+    const int64_t nch = (len / 4 + RC_DWORDS - 1) / RC_DWORDS > 0 ? (len / 4 + RC_DWORDS - 1) / RC_DWORDS : 1;
+    const int64_t items = n_sel * nch;
+    int64_t blocks = (items + CM_WAVES - 1) / CM_WAVES;
+    if (blocks > 8192) blocks = 8192;
+    const dim3 grid((unsigned)blocks);
+    const CasePair pair{src, src_stride, sub, sub_stride};
+    const RenderArgs r{(const int*)cases, n_case, (unsigned)height, (unsigned)width, lo, hi, flip_y, out};
+    CP_DISPATCH(launch_render_cases, src_kind, kb, grid, (hipStream_t)hip_stream, pair, r, (int)nch, items)
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 """The LDS-staged forward of the channel-rich decoder layers (k_ct_fwd_lds, kernels_ctlds.h) against the fp64 oracle, over the
-splits, bands and output shapes its host plan (ct_fwd_plan in engine.hip) can give it.
+splits, bands and output shapes its host plan (ct_fwd_plan in engine_choose.h) can give it.
 
 A workgroup of that kernel owns a tile group of one image: rt row tiles of 16 quads (2x2 output pixels), each shared by ks
 waves that split the input channels; an image has tg = ceil(tiles / rt) groups.  It stages only the band of input rows its

@@ -1,6 +1,6 @@
 """Every shape of the stride-2 decoder kernels (kernels_s2.h, kernels_last.h, kernels_rows.h) against the fp64 oracle.
 
-The 16 shapes are S2_SHAPES x S2_KERNELS in engine.hip: Cin->Cout in 2->1, 4->2, 8->4, 6->3 times taps 3x3, 4x4, 3x4, 4x3.
+The 16 shapes are S2_SHAPES x S2_KERNELS in engine_choose.h: Cin->Cout in 2->1, 4->2, 8->4, 6->3 times taps 3x3, 4x4, 3x4, 4x3.
 GEOMETRIES are sizer-made models (create_model_spec, 16x16 inputs) whose decoders, together, put every shape in every position
 a sizer-made decoder can give it (2->1 and 6->3 only as the last layer, 8->4 only in the middle), with odd, even and
 non-square outputs and 1-3 output channels: 3-tap last layers (a parity with 2 taps one way and 1 the other), 3x4 / 4x3 last
@@ -60,7 +60,7 @@ LARGE_BATCH = {
 # (geometry, batch, kernel modes) of every parity case
 CASES = [(g, b, (1, 0)) for g in GEOMETRIES for b in BATCHES] + [(g, b, (1,)) for g, (b, _) in LARGE_BATCH.items()]
 
-# launch label (ProfScope in engine.hip) of each kernel family that cae_debug_plan reports
+# launch label (ProfScope in engine_launch.h) of each kernel family that cae_debug_plan reports
 _FWD_LABEL = {"s2_fwd_rows": "s2_convt_fwd", "s2_fwd": "s2_convt_fwd", "s2_fwd_cs": "s2_convt_fwd", "s2_fwd2": "s2_convt_fwd",
               "ct_fwd_lds": "ct_convt_fwd", "ig_fwd_s2": "ig_convt_fwd", "up": "dec_convt_fwd"}
 _BWD_LABEL = {"(fused)": ["s2_convt_last_fused"], "s2_bwd_rows": ["s2_convt_bwd"], "s2_bwd2": ["s2_convt_bwd"],
