@@ -258,6 +258,12 @@ class GradientHalfSteps:
         self.engine.set_lr(lr)
 
 
+def data_parallel(engine, dist, sync_bn=False):
+    """the DataParallel that drives `engine`: a native engine (HipEngine) as it is, any other behind GradientHalfSteps"""
+    native = hasattr(engine, "dp_train_steps")
+    return DataParallel(engine if native else GradientHalfSteps(engine), dist, sync_bn=sync_bn)
+
+
 # ---- process-group plumbing for the model classes and CLIs ------------------------------------------
 
 def env_world():

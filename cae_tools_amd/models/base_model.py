@@ -4,14 +4,17 @@ evaluate (:69-100), apply (:102-152), dump_metrics (:154-157), save/load of inpu
 output_spec.json (:162-180).  Scoring, denormalisation and the metric reductions run on the GPU
 through libcae_hip; only per-case sums and the final fp64 predictions cross PCIe.
 EngineModel is what the four engine-backed models (ConvAE, UNET, VarAE, Linear) share on top of that."""
+import contextlib
 import json
 import os
 import time
 import uuid
 
+import numpy as np
 import torch
 
 from .. import lr_schedule as _lrs
+from .._engine_base import TEST, TRAIN
 from ..data.arrays import DataArray
 from .ds_dataset import DSDataset
 from .model_metric import DeviceModelMetric, ModelMetric  # noqa: F401
@@ -32,6 +35,11 @@ def _index_batches(n, batch_size):
     batches (conv_ae_model.py:291-292, 315-325)"""
     loader = torch.utils.data.DataLoader(torch.arange(n), batch_size=batch_size, shuffle=True)
     return torch.cat([b for b in loader]).to(torch.int32).numpy()
+
+
+def _mean_loss(losses, column=None):
+    """a pass's loss: the mean over its batches of the engine's per-batch loss (entry `column` where that is a tuple)"""
+    return float(np.mean(losses if column is None else [l[column] for l in losses]))
 
 
 class BaseModel:
@@ -209,15 +217,27 @@ class _ScheduledRate:
 
 
 class EngineModel(BaseModel):
-    """What the libcae_hip-backed models share: host weight containers mirrored by one engine, the model folder, and the
-    parts of train() around the epoch loop.  This base implements the spec-driven encoder / decoder models; a sub-class
-    supplies MODEL_TYPE (its model-database type), PARAM_KEYS (parameters.json entries load() restores), _modules() and
-    _make_engine(max_batch)."""
+    """What the libcae_hip-backed models share: host weight containers mirrored by one engine, the model folder, and
+    train() with its epoch loop.  This base implements the spec-driven encoder / decoder models; a sub-class supplies
+    MODEL_TYPE (its model-database type), PARAM_KEYS (parameters.json entries load() restores), _modules() and
+    _make_engine(max_batch), and says where its training differs with the attributes below and by overriding _hyper(),
+    _bind_data() and _report_epoch()."""
 
     MODEL_TYPE = None
     PARAM_KEYS = ()
     OPTIONAL_PARAM_KEYS = ("conv_kernel_size", "conv_stride", "conv_input_layer_count", "conv_output_layer_count")
     SCHEDULE_KEYS = ("scheduler_type", "lr_step_size", "lr_gamma")     # in parameters.json only when a scheduler is set
+
+    # ---- where train() differs between the model classes --------------------------------------
+    DATA_PARALLEL = True        # trains one rank per GPU under a torch.distributed.run launch (LinearModel: no such path)
+    LOSS_COLUMN = None          # which entry of a batch's loss tuple is THE loss; None: the engine returns one float
+    MASKED_LOSS = False         # the loss reads the data sets' mask variable (UNET)
+    ALWAYS_BROADCAST_BUFFERS = False    # rank 0's running statistics go out before a test pass and at the end even with
+                                        # SyncBN, which keeps them equal on its own (ConvAEModel does; the others do not)
+    INTERRUPTIBLE = False       # Ctrl-C ends the epoch loop and the model is still saved (UNET, as the reference's)
+
+    timing = None       # set by train(): seconds and images of the epoch loop, and the world size (build-only attribute)
+    _lead = True        # this process prints (rank 0 of a data-parallel run)
 
     # ---- learning-rate schedule ------------------------------------------------------------
     def _init_schedule(self, scheduler_type=None, lr_step_size=500, lr_gamma=0.5):
@@ -254,8 +274,10 @@ class EngineModel(BaseModel):
 
     # ---- engine ----------------------------------------------------------------------------
     def _load_engine(self, eng):
-        """host state -> a new engine"""
+        """host state -> a new engine, which the containers then run their own forward on"""
         eng.load_state(self.encoder.state_dict(), self.decoder.state_dict())
+        self.encoder.attach(eng)
+        self.decoder.attach(eng)
 
     def _pull_weights(self):
         """device arenas -> the host containers (state_dict source for save())"""
@@ -275,6 +297,10 @@ class EngineModel(BaseModel):
         return self._engine
 
     def _score_device(self, x):
+        # an engine that exists is used as it is (score() walks the array in chunks of its max_batch): a data-parallel
+        # rank's engine holds a share of the batch and is not re-created for scoring
+        if self._engine is not None:
+            return self._engine.score(x)
         return self._get_engine(max(1, min(int(self.batch_size), int(x.shape[0])))).score(x)
 
     def score(self, batches, save_arr):
@@ -334,7 +360,7 @@ class EngineModel(BaseModel):
 
     # ---- training --------------------------------------------------------------------------
     def _progress(self, message):
-        """a progress line of train()'s set-up; only UNET prints them"""
+        """a progress line of train(); only UNET prints them"""
 
     def _build(self):
         """spec and host containers for a model trained from scratch (kept when training continues)"""
@@ -370,6 +396,102 @@ class EngineModel(BaseModel):
         test_perm = _index_batches(len(test_ds), self.batch_size)
         self._progress("finished train_loarder and test_loader")
         return train_ds, test_ds, train_perm, test_perm
+
+    def _hyper(self):
+        """the keywords of the engine's set_hyper"""
+        return {"lr": self.lr, "weight_decay": self.weight_decay}
+
+    def _bind_data(self, eng, train_ds, test_ds, train_perm, test_perm):
+        """both data sets bound to the engine: the device index of each frozen shuffle, (train, test)"""
+        eng.set_dataset(TRAIN, train_ds.device_inputs(), train_ds.device_outputs())
+        eng.set_dataset(TEST, test_ds.device_inputs(), test_ds.device_outputs())
+        return eng.upload_perm(train_perm), eng.upload_perm(test_perm)
+
+    def _report_epoch(self, epoch, train_losses, test_losses, lr):
+        """the lead rank's line(s) for an epoch whose test pass ran, from the per-batch losses of both passes"""
+        column = self.LOSS_COLUMN
+        print("%5d %.6f %.6f" % (epoch, _mean_loss(train_losses, column), _mean_loss(test_losses, column)))
+
+    def train(self, input_variables, output_variable, training_ds, testing_ds, model_path="", training_paths="",
+              testing_paths="", mask_variable_name=None):
+        """Train (or continue training): see the reference docstring (conv_ae_model.py:241-252).  Data flow: both data sets
+        are scanned / normalised / packed on the GPU once, the shuffle is frozen once (:315-325), and every epoch is one
+        run_batches per pass plus one loss read-back.
+
+        Data parallel (build-only; the reference selects ONE device at :294-297): under a torch.distributed.run launch every
+        rank holds the model and both data sets and takes its rows of each frozen GLOBAL batch (dp.shard_bounds); gradients,
+        and with sync_bn the BatchNorm and loss tables, are summed over the ranks, so that a step is the single-device step
+        at batch_size.  Rank 0 prints and saves."""
+        from .. import dp as _dp
+        # a rank works on ITS GPU from the first allocation on (the data sets below are uploaded to the current device, the
+        # engine is created on it)
+        dist = _dp.ensure_process_group() if self.DATA_PARALLEL else None
+        (world, rank) = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
+        self._lead = lead = rank == 0
+        (train_ds, test_ds, train_perm, test_perm) = self._train_prologue(
+            input_variables, output_variable, training_ds, testing_ds, mask_variable_name if self.MASKED_LOSS else None)
+        if dist is not None:    # one frozen shuffle for everybody: rank 0's draw
+            box = [train_perm, test_perm]
+            dist.broadcast_object_list(box, src=0)
+            (train_perm, test_perm) = box
+        if lead:
+            print(f"Running on device: {torch.device('cuda')}")
+        start = time.time()
+
+        eng = self._get_engine(-(-int(self.batch_size) // world))   # a rank's share of a global batch
+        eng.set_hyper(**self._hyper())
+        eng.reset_optimizer()       # the reference re-creates its optimiser on every train() (:310)
+        (train_idx, test_idx) = self._bind_data(eng, train_ds, test_ds, train_perm, test_perm)
+        par = None
+        if dist is not None:
+            par = _dp.data_parallel(eng, dist, sync_bn=self.sync_bn)
+            par.broadcast_parameters(0)     # rank 0's initial (or loaded) weights, running statistics and moments everywhere
+        # per-rank BatchNorm lets the ranks' running statistics part: rank 0's go to every rank before they are scored with
+        send_buffers = par is not None and (self.ALWAYS_BROADCAST_BUFFERS or not self.sync_bn)
+        trace_range = getattr(eng, "trace_range", contextlib.nullcontext)    # named profiler ranges: the ConvAE engine's
+
+        def one_pass(which, idx, ds, train):
+            with trace_range("cae_tools_amd.train_epoch" if train else "cae_tools_amd.test_epoch"):
+                if par is None:
+                    return eng.run_batches(which, idx, len(ds), self.batch_size, train=train)
+                if not train and send_buffers:
+                    par.broadcast_buffers(0)
+                return par.run_batches(which, idx, len(ds), self.batch_size, train=train)
+
+        train_loss = test_loss = 0.0
+        rate = self._scheduled_rate(eng, par)
+        eng.sync()
+        loop_start = time.perf_counter()
+        try:
+            for epoch in range(self.nr_epochs):
+                epoch_start = time.time()
+                epoch_lr = rate.current
+                train_losses = one_pass(TRAIN, train_idx, train_ds, True)
+                rate.after_train_pass()     # where the reference steps its scheduler (unet.py:485-487); one tiny launch
+                self._progress(f"time used for training one epoch: {time.time() - epoch_start:.2f}")
+                train_loss = _mean_loss(train_losses, self.LOSS_COLUMN)
+                if epoch % self.test_interval == 0:
+                    test_losses = one_pass(TEST, test_idx, test_ds, False)
+                    test_loss = _mean_loss(test_losses, self.LOSS_COLUMN)
+                    rate.after_test_pass(test_loss)
+                    rate.record(epoch_lr)
+                    self.history["train_loss"].append(train_loss)
+                    self.history["test_loss"].append(test_loss)
+                    if lead:
+                        self._report_epoch(epoch, train_losses, test_losses, rate.current)
+        except KeyboardInterrupt:
+            if not self.INTERRUPTIBLE:
+                raise
+            print("Training interrupted. Performing cleanup...")
+        eng.sync()
+        # SURVEY §8(d)'s metric: images through the epoch loop (conv_ae_model.py:328-334, the test pass every test_interval
+        # epochs included) per second; bench.py's train_api leg reads it
+        self.timing = {"epoch_loop_seconds": time.perf_counter() - loop_start, "train_images": len(train_ds) * self.nr_epochs,
+                       "epochs": self.nr_epochs, "world": world}
+        if send_buffers:
+            par.broadcast_buffers(0)
+        return self._train_epilogue(start, train_ds, test_ds, train_loss, test_loss, input_variables, output_variable,
+                                    model_path, training_paths, testing_paths, lead=lead)
 
     def _train_epilogue(self, start, train_ds, test_ds, train_loss, test_loss, input_variables, output_variable, model_path,
                         training_paths, testing_paths, lead=True):

@@ -10,12 +10,6 @@ implements the intended behaviour: DSDataset's 4-tuples are accepted, train() ta
 mask_variable_name the CLI passes (ignored by the 'conv' method: its loss is plain MSE), and the
 evaluation mask covers every output pixel.
 """
-import time
-
-import numpy as np
-import torch
-
-from .. import dp as _dp
 from .. import engine as _eng
 from .base_model import EngineModel
 from .ds_dataset import DSDataset  # noqa: F401  (this module's public name since before EngineModel built the data sets)
@@ -29,6 +23,7 @@ class ConvAEModel(EngineModel):
     MODEL_TYPE = "ConvAE"
     PARAM_KEYS = ("batch_size", "test_interval", "encoded_dim_size", "fc_size", "lr", "weight_decay", "normalise_input",
                   "normalise_output")
+    ALWAYS_BROADCAST_BUFFERS = True
 
     def __init__(self, normalise_input=True, normalise_output=True, batch_size=10,
                  nr_epochs=500, test_interval=10, encoded_dim_size=32, fc_size=128,
@@ -56,7 +51,6 @@ class ConvAEModel(EngineModel):
         self.conv_output_layer_count = conv_output_layer_count
         self.spec = None
         self.history = {"train_loss": [], "test_loss": [], "nr_epochs": 0}
-        self.timing = None      # set by train(): seconds and images of the epoch loop (build-only attribute)
         self.optim = None
         self.db = ModelDatabase(database_path) if database_path else None   # conv_ae_model.py:75
         self._engine = None
@@ -100,46 +94,8 @@ class ConvAEModel(EngineModel):
     def _make_engine(self, max_batch):
         return _eng.HipEngine(self.spec, self.fc_size, self.encoded_dim_size, max_batch=max_batch)
 
-    def _load_engine(self, eng):
-        super()._load_engine(eng)
-        self.encoder.attach(eng)
-        self.decoder.attach(eng)
-
-    def _score_device(self, x):
-        # an engine that exists is used as it is (score() walks the array in chunks of its max_batch)
-        if self._engine is not None:
-            return self._engine.score(x)
-        return super()._score_device(x)
-
     # ---- training --------------------------------------------------------------------------
-    def train(self, input_variables, output_variable, training_ds, testing_ds, model_path="", training_paths="",
-              testing_paths="", mask_variable_name=None):
-        """Train (or continue training): see the reference docstring (:241-252).  Data flow: both
-        datasets are scanned / normalised / packed on the GPU once, the shuffle is frozen once
-        (:315-325), and every epoch is nb calls of cae_train_step plus one loss read-back."""
-        # a rank of a torch.distributed.run launch works on ITS GPU from the first allocation on (the data sets below
-        # are uploaded to the current device, the engine is created on it)
-        dist = _dp.ensure_process_group()
-        (train_ds, test_ds, train_perm, test_perm) = self._train_prologue(input_variables, output_variable, training_ds,
-                                                                          testing_ds)
-
-        # Data parallel (build-only; the reference selects ONE device at :294-297 and moves the modules there at :312-313):
-        # under a torch.distributed.run launch every rank holds the model and both data sets, takes its rows of each frozen
-        # GLOBAL batch (dp.shard_bounds) and the gradients are all-reduced inside libcae_hip; rank 0 prints and saves.
-        (world, rank) = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
-        lead = rank == 0
-        if dist is not None:    # one frozen shuffle for everybody: rank 0's draw
-            box = [train_perm, test_perm]
-            dist.broadcast_object_list(box, src=0)
-            (train_perm, test_perm) = box
-
-        if lead:
-            print(f"Running on device: {torch.device('cuda')}")
-        start = time.time()
-
-        eng = self._get_engine(-(-int(self.batch_size) // world))   # a rank's share of a global batch
-        eng.set_hyper(lr=self.lr, weight_decay=self.weight_decay)
-        eng.reset_optimizer()      # torch.optim.Adam is re-created on every train() (:310)
+    def _bind_data(self, eng, train_ds, test_ds, train_perm, test_perm):
         # The reference stacks its shuffled batches ONCE and reuses that list every epoch (:315-325).  The same here: both data
         # sets are laid out in batch order once - by the normalisation kernel itself, which writes every sample to its row of
         # the frozen order (DSDataset.device_batches -> cae_normalise_pack_rows) - so a batch is a contiguous run of rows and
@@ -147,46 +103,7 @@ class ConvAEModel(EngineModel):
         # gathering kernel: the encoder's head, the last layer's targets, the first conv's weight gradient).
         eng.set_dataset(_eng.TRAIN, *train_ds.device_batches(train_perm))
         eng.set_dataset(_eng.TEST, *test_ds.device_batches(test_perm))
-        train_idx = test_idx = None
-        par = None
-        if dist is not None:
-            par = _dp.DataParallel(eng, dist, sync_bn=self.sync_bn)
-            par.broadcast_parameters(0)     # rank 0's initial (or loaded) weights and running statistics everywhere
-
-        def one_pass(which, idx, n, train):
-            with eng.trace_range("cae_tools_amd.train_epoch" if train else "cae_tools_amd.test_epoch"):
-                if par is None:
-                    return eng.run_batches(which, idx, n, self.batch_size, train=train)
-                if not train:
-                    par.broadcast_buffers(0)    # every rank scores with the same running statistics
-                return par.run_batches(which, idx, n, self.batch_size, train=train)
-
-        train_loss = test_loss = 0.0
-        rate = self._scheduled_rate(eng, par)
-        eng.sync()
-        loop_start = time.perf_counter()
-        for epoch in range(self.nr_epochs):
-            epoch_lr = rate.current
-            train_loss = float(np.mean(one_pass(_eng.TRAIN, train_idx, len(train_ds), True)))
-            rate.after_train_pass()     # one tiny launch: the step graphs read the rate from the device
-            if epoch % self.test_interval == 0:
-                test_loss = float(np.mean(one_pass(_eng.TEST, test_idx, len(test_ds), False)))
-                rate.after_test_pass(test_loss)
-                rate.record(epoch_lr)
-                self.history["train_loss"].append(train_loss)
-                self.history["test_loss"].append(test_loss)
-                if lead:
-                    print("%5d %.6f %.6f" % (epoch, train_loss, test_loss))
-        eng.sync()
-        # SURVEY §8(d)'s metric: images through the epoch loop (conv_ae_model.py:328-334, the test pass every test_interval
-        # epochs included) per second; bench.py's train_api leg reads it
-        self.timing = {"epoch_loop_seconds": time.perf_counter() - loop_start, "train_images": len(train_ds) * self.nr_epochs,
-                       "epochs": self.nr_epochs, "world": world}
-        if par is not None:
-            par.broadcast_buffers(0)
-
-        return self._train_epilogue(start, train_ds, test_ds, train_loss, test_loss, input_variables, output_variable,
-                                    model_path, training_paths, testing_paths, lead=lead)
+        return None, None
 
     def summary(self):
         if not self.spec:

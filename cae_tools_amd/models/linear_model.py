@@ -6,11 +6,6 @@ history.json, summary.txt, input_spec.json, output_spec.json) and printed lines.
 (its epoch loops unpack three values from DSDataset's four-tuple, :146,166; `test_paths` is undefined at :281) the evident
 intent is implemented.  The step (forward, MSELoss, backward, Adam(lr, weight_decay): :146-153,241,247) runs in the HIP
 kernels behind include/cae_linear.h."""
-import time
-
-import numpy as np
-import torch
-
 from .. import linear_engine as _le
 from ..utils.model_database import ModelDatabase
 from .base_model import EngineModel
@@ -24,6 +19,7 @@ class LinearModel(EngineModel):
     MODEL_TYPE = "Linear"
     PARAM_KEYS = ("batch_size", "test_interval", "lr", "weight_decay", "normalise_input", "normalise_output")
     OPTIONAL_PARAM_KEYS = ()
+    DATA_PARALLEL = False
 
     def __init__(self, normalise_input=True, normalise_output=True, batch_size=10, nr_epochs=500, test_interval=10, lr=0.001,
                  weight_decay=1e-5, use_gpu=True, database_path=None, scheduler_type=None, lr_step_size=500, lr_gamma=0.5):
@@ -79,30 +75,6 @@ class LinearModel(EngineModel):
         if self._engine is not None:
             self.weights.load_state_dict(self._engine.export_state())
 
-    def train(self, input_variables, output_variable, training_ds, testing_ds, model_path="", training_paths="",
-              testing_paths="", mask_variable_name=None):
-        (train_ds, test_ds, train_perm, test_perm) = self._train_prologue(input_variables, output_variable, training_ds,
-                                                                          testing_ds)   # both loaders shuffle (:228-229)
-        print(f"Running on device: {torch.device('cuda')}")
-        start = time.time()
-        eng = self._get_engine(int(self.batch_size))
-        eng.set_hyper(lr=self.lr, weight_decay=self.weight_decay)
-        eng.reset_optimizer()
-        eng.set_dataset(_le.TRAIN, train_ds.device_inputs(), train_ds.device_outputs())
-        eng.set_dataset(_le.TEST, test_ds.device_inputs(), test_ds.device_outputs())
-        (train_idx, test_idx) = (eng.upload_perm(train_perm), eng.upload_perm(test_perm))
-        train_loss = test_loss = 0.0
-        rate = self._scheduled_rate(eng)
-        for epoch in range(self.nr_epochs):
-            epoch_lr = rate.current
-            train_loss = float(np.mean(eng.run_batches(_le.TRAIN, train_idx, len(train_ds), self.batch_size, True)))
-            rate.after_train_pass()
-            if epoch % self.test_interval == 0:
-                test_loss = float(np.mean(eng.run_batches(_le.TEST, test_idx, len(test_ds), self.batch_size, False)))
-                rate.after_test_pass(test_loss)
-                rate.record(epoch_lr)
-                self.history["train_loss"].append(train_loss)
-                self.history["test_loss"].append(test_loss)
-                print("%5d %.6f %.6f" % (epoch, train_loss, test_loss))
-        return self._train_epilogue(start, train_ds, test_ds, train_loss, test_loss, input_variables, output_variable,
-                                    model_path, training_paths, testing_paths)
+    def _score_device(self, x):
+        """an engine too small for the rows is re-created"""
+        return self._get_engine(max(1, min(int(self.batch_size), int(x.shape[0])))).score(x)

@@ -17,14 +17,12 @@ What differs from the reference, on purpose:
 """
 import time
 
-import numpy as np
 import torch
 
-from .. import dp as _dp
 from .. import unet_engine as _ue
 from ..utils.model_database import ModelDatabase
 from ._params import ParamBag, add_batchnorm, default_layer_init
-from .base_model import EngineModel
+from .base_model import EngineModel, _mean_loss
 from .model_sizer import ModelSpec
 
 
@@ -143,6 +141,9 @@ class UNET(EngineModel):
     MODEL_TYPE = "UNET"
     PARAM_KEYS = ("batch_size", "test_interval", "encoded_dim_size", "fc_size", "lr", "weight_decay", "normalise_input",
                   "normalise_output")
+    LOSS_COLUMN = 0     # of (masked mse, pearson loss)
+    MASKED_LOSS = True
+    INTERRUPTIBLE = True
 
     def __init__(self, normalise_input=True, normalise_output=True, batch_size=10, nr_epochs=500, test_interval=10,
                  encoded_dim_size=32, fc_size=128, lr=0.001, weight_decay=1e-5, dropout_rate=0.1, use_gpu=True,
@@ -177,11 +178,9 @@ class UNET(EngineModel):
         self.dropout_seed = dropout_seed
         self._engine = None
         self._steps_done = 0
-        self.timing = None      # set by train(): seconds and images of the epoch loop, and the world size
         # under a torch.distributed.run launch (one process per GPU) batch_size stays the GLOBAL batch; sync_bn=True computes
         # BatchNorm statistics over it (N ranks reproduce the single-device step), False keeps per-rank statistics
         self.sync_bn = True
-        self._lead = True       # this process prints (rank 0 of a data-parallel run)
 
     # ---- persistence ---------------------------------------------------------------------------------
     def get_parameters(self):
@@ -225,91 +224,27 @@ class UNET(EngineModel):
         return _ue.UnetEngine(self.spec, self.fc_size, self.encoded_dim_size, max_batch=max_batch)
 
     # ---- training --------------------------------------------------------------------------------------
-    def train(self, input_variables, output_variable, training_ds, testing_ds, model_path="", training_paths="",
-              testing_paths="", mask_variable_name=None):
-        # Data parallel (build-only; the reference trains on one device): under a torch.distributed.run launch every rank
-        # holds the model and both data sets and takes its rows of each frozen GLOBAL batch (dp.shard_bounds); the engine's
-        # sync entry points sum the BatchNorm, loss and gradient tables over the ranks, so that a step is the single-device
-        # step at batch_size.  Rank 0 prints and saves.
-        dist = _dp.ensure_process_group()
-        (world, rank) = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
-        self._lead = lead = rank == 0
-        (train_ds, test_ds, train_perm, test_perm) = self._train_prologue(input_variables, output_variable, training_ds,
-                                                                          testing_ds, mask_variable_name)
-        if dist is not None:    # one frozen shuffle for everybody: rank 0's draw
-            box = [train_perm, test_perm]
-            dist.broadcast_object_list(box, src=0)
-            (train_perm, test_perm) = box
-        if lead:
-            print(f"Running on device: {torch.device('cuda')}")
-        start = time.time()
+    def _load_engine(self, eng):
+        eng.load_state(self.encoder.state_dict(), self.decoder.state_dict())    # the containers run nothing on their own
 
-        eng = self._get_engine(-(-int(self.batch_size) // world))   # a rank's share of a global batch
-        eng.set_hyper(lr=self.lr, weight_decay=self.weight_decay, dropout_rate=self.dropout_rate,
-                      lambda_pearson=self.lambda_pearson, seed=self.dropout_seed)
-        eng.reset_optimizer()       # AdamW is re-created on every train() (:457)
+    def _hyper(self):
+        return {"lr": self.lr, "weight_decay": self.weight_decay, "dropout_rate": self.dropout_rate,
+                "lambda_pearson": self.lambda_pearson, "seed": self.dropout_seed}
+
+    def _bind_data(self, eng, train_ds, test_ds, train_perm, test_perm):
         eng.set_step(0)
         t0 = time.time()
         for (which, ds) in ((_ue.TRAIN, train_ds), (_ue.TEST, test_ds)):
             eng.set_dataset(which, ds.device_inputs(), ds.device_outputs(), self._loss_mask(ds))
-        train_idx = eng.upload_perm(train_perm)
-        test_idx = eng.upload_perm(test_perm)
-        if lead:
-            print(f"finished batching in {time.time() - t0:.2f} seconds")
-        par = None
-        if dist is not None:
-            par = _dp.DataParallel(_dp.GradientHalfSteps(eng), dist, sync_bn=self.sync_bn)
-            par.broadcast_parameters(0)     # rank 0's initial (or loaded) weights, running statistics and moments everywhere
+        idx = (eng.upload_perm(train_perm), eng.upload_perm(test_perm))
+        self._progress(f"finished batching in {time.time() - t0:.2f} seconds")
+        return idx
 
-        def one_pass(which, idx, n, train):
-            if par is None:
-                return eng.run_batches(which, idx, n, self.batch_size, train=train)
-            if not train and not self.sync_bn:
-                par.broadcast_buffers(0)    # every rank scores with the same running statistics
-            return par.run_batches(which, idx, n, self.batch_size, train=train)
-
-        train_loss = test_loss = 0.0
-        rate = self._scheduled_rate(eng, par)
-        eng.sync()
-        loop_start = time.perf_counter()
-        try:
-            for epoch in range(self.nr_epochs):
-                e0 = time.time()
-                epoch_lr = rate.current
-                losses = one_pass(_ue.TRAIN, train_idx, len(train_ds), True)
-                rate.after_train_pass()     # the scheduler step of unet.py:485-487
-                if lead:
-                    print(f"time used for training one epoch: {time.time() - e0:.2f}")
-                train_loss = float(np.mean([l[0] for l in losses]))
-                train_pearson_loss = float(np.mean([l[1] for l in losses]))
-                if epoch % self.test_interval == 0:
-                    tl = one_pass(_ue.TEST, test_idx, len(test_ds), False)
-                    test_loss = float(np.mean([l[0] for l in tl]))
-                    test_pearson_loss = float(np.mean([l[1] for l in tl]))
-                    rate.after_test_pass(test_loss)
-                    rate.record(epoch_lr)
-                    self.history["train_loss"].append(train_loss)
-                    self.history["test_loss"].append(test_loss)
-                    if lead:
-                        print(f"epoch: {epoch}, train_mse: {train_loss:.6f}, train_pearson_loss: {train_pearson_loss:.4f}, "
-                              f"test_mse: {test_loss:.6f}, test_pearson_loss: {test_pearson_loss:.4f}")
-                        print(f"learn rate: {rate.current:.6f}")
-        except KeyboardInterrupt:
-            print("Training interrupted. Performing cleanup...")
-        eng.sync()
-        self.timing = {"epoch_loop_seconds": time.perf_counter() - loop_start, "train_images": len(train_ds) * self.nr_epochs,
-                       "epochs": self.nr_epochs, "world": world}
-        if par is not None and not self.sync_bn:
-            par.broadcast_buffers(0)
-        return self._train_epilogue(start, train_ds, test_ds, train_loss, test_loss, input_variables, output_variable,
-                                    model_path, training_paths, testing_paths, lead=lead)
-
-    def _score_device(self, x):
-        # an engine that exists is used as it is (score() walks the array in chunks of its max_batch): a data-parallel
-        # rank's engine holds a share of the batch and is not re-created for scoring
-        if self._engine is not None:
-            return self._engine.score(x)
-        return super()._score_device(x)
+    def _report_epoch(self, epoch, train_losses, test_losses, lr):
+        print(f"epoch: {epoch}, train_mse: {_mean_loss(train_losses, 0):.6f}, "
+              f"train_pearson_loss: {_mean_loss(train_losses, 1):.4f}, test_mse: {_mean_loss(test_losses, 0):.6f}, "
+              f"test_pearson_loss: {_mean_loss(test_losses, 1):.4f}")
+        print(f"learn rate: {lr:.6f}")
 
     def _progress(self, message):
         if self._lead:

@@ -7,8 +7,6 @@ ConvAEModel (same constructor keywords plus the three lambdas, same train / appl
 folder), with the arithmetic published in oracle/vae_oracle.py and computed by the HIP kernels behind include/cae_vae.h:
 ConvAE encoder stack -> Linear -> ReLU -> (mu, logvar) heads -> z = mu + eps*exp(logvar/2) -> ConvAE decoder;
 loss = lambda_mse*MSE + lambda_kl*KL + lambda_ssim*(1 - MS-SSIM); Adam with L2 weight decay."""
-import time
-
 import numpy as np
 import torch
 
@@ -60,6 +58,7 @@ class VarAEModel(EngineModel):
     MODEL_TYPE = "VarAE"
     PARAM_KEYS = ("batch_size", "test_interval", "encoded_dim_size", "fc_size", "lr", "weight_decay", "normalise_input",
                   "normalise_output", "lambda_mse", "lambda_kl", "lambda_ssim")
+    LOSS_COLUMN = 3     # of (mse, kl, 1 - ms_ssim, total)
 
     def __init__(self, normalise_input=True, normalise_output=True, batch_size=10, nr_epochs=500, test_interval=10,
                  encoded_dim_size=32, fc_size=128, lr=0.001, weight_decay=1e-5, use_gpu=True, conv_kernel_size=3, conv_stride=2,
@@ -81,7 +80,6 @@ class VarAEModel(EngineModel):
         self.history = {"train_loss": [], "test_loss": [], "nr_epochs": 0}
         self.db = ModelDatabase(database_path) if database_path else None
         self._engine = None
-        self.timing = None      # set by train(): seconds and images of the epoch loop, and the world size
         # under a torch.distributed.run launch (one process per GPU) batch_size stays the GLOBAL batch; sync_bn=True computes
         # BatchNorm statistics over it (N ranks reproduce the single-device step), False keeps per-rank statistics
         self.sync_bn = True
@@ -111,78 +109,9 @@ class VarAEModel(EngineModel):
     def _make_engine(self, max_batch):
         return _ve.VaeEngine(self.spec, self.fc_size, self.encoded_dim_size, max_batch=max_batch)
 
-    def _load_engine(self, eng):
-        super()._load_engine(eng)
-        self.encoder.attach(eng)
-        self.decoder.attach(eng)
-
-    def train(self, input_variables, output_variable, training_ds, testing_ds, model_path="", training_paths="",
-              testing_paths="", mask_variable_name=None):
-        # Data parallel (build-only, as UNET.train()): under a torch.distributed.run launch every rank holds the model and both
-        # data sets and takes its rows of each frozen GLOBAL batch (dp.shard_bounds); the engine's sync entry points sum the
-        # BatchNorm, loss and gradient tables over the ranks, and the noise of a row is that of its global index, so that a step
-        # is the single-device step at batch_size.  Rank 0 prints and saves.
-        dist = _dp.ensure_process_group()
-        (world, rank) = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
-        lead = rank == 0
-        (train_ds, test_ds, train_perm, test_perm) = self._train_prologue(input_variables, output_variable, training_ds,
-                                                                          testing_ds)
-        if dist is not None:    # one frozen shuffle for everybody: rank 0's draw
-            box = [train_perm, test_perm]
-            dist.broadcast_object_list(box, src=0)
-            (train_perm, test_perm) = box
-        if lead:
-            print(f"Running on device: {torch.device('cuda')}")
-        start = time.time()
-        eng = self._get_engine(-(-int(self.batch_size) // world))   # a rank's share of a global batch
-        eng.set_hyper(lr=self.lr, weight_decay=self.weight_decay, lambda_mse=self.lambda_mse, lambda_kl=self.lambda_kl,
-                      lambda_ssim=self.lambda_ssim, seed=self.noise_seed)
-        eng.reset_optimizer()
-        eng.set_dataset(_ve.TRAIN, train_ds.device_inputs(), train_ds.device_outputs())
-        eng.set_dataset(_ve.TEST, test_ds.device_inputs(), test_ds.device_outputs())
-        (train_idx, test_idx) = (eng.upload_perm(train_perm), eng.upload_perm(test_perm))
-        par = None
-        if dist is not None:
-            par = _dp.DataParallel(_dp.GradientHalfSteps(eng), dist, sync_bn=self.sync_bn)
-            par.broadcast_parameters(0)     # rank 0's initial (or loaded) weights, running statistics and moments everywhere
-
-        def one_pass(which, idx, n, train):
-            if par is None:
-                return eng.run_batches(which, idx, n, self.batch_size, train)
-            if not train and not self.sync_bn:
-                par.broadcast_buffers(0)    # every rank scores with the same running statistics
-            return par.run_batches(which, idx, n, self.batch_size, train=train)
-
-        train_loss = test_loss = 0.0
-        rate = self._scheduled_rate(eng, par)
-        eng.sync()
-        loop_start = time.perf_counter()
-        for epoch in range(self.nr_epochs):
-            epoch_lr = rate.current
-            train_loss = float(np.mean([l[3] for l in one_pass(_ve.TRAIN, train_idx, len(train_ds), True)]))
-            rate.after_train_pass()
-            if epoch % self.test_interval == 0:
-                test_loss = float(np.mean([l[3] for l in one_pass(_ve.TEST, test_idx, len(test_ds), False)]))
-                rate.after_test_pass(test_loss)
-                rate.record(epoch_lr)
-                self.history["train_loss"].append(train_loss)
-                self.history["test_loss"].append(test_loss)
-                if lead:
-                    print("%5d %.6f %.6f" % (epoch, train_loss, test_loss))
-        eng.sync()
-        self.timing = {"epoch_loop_seconds": time.perf_counter() - loop_start, "train_images": len(train_ds) * self.nr_epochs,
-                       "epochs": self.nr_epochs, "world": world}
-        if par is not None and not self.sync_bn:
-            par.broadcast_buffers(0)
-        return self._train_epilogue(start, train_ds, test_ds, train_loss, test_loss, input_variables, output_variable,
-                                    model_path, training_paths, testing_paths, lead=lead)
-
-    def _score_device(self, x):
-        # an engine that exists is used as it is (score() walks the array in chunks of its max_batch): a data-parallel
-        # rank's engine holds a share of the batch and is not re-created for scoring
-        if self._engine is not None:
-            return self._engine.score(x)
-        return super()._score_device(x)
+    def _hyper(self):
+        return {"lr": self.lr, "weight_decay": self.weight_decay, "lambda_mse": self.lambda_mse, "lambda_kl": self.lambda_kl,
+                "lambda_ssim": self.lambda_ssim, "seed": self.noise_seed}
 
     # ---- the model as a generative one (the build's own definition, parity unpinned) -------------------------
     def _inference_engine(self, n):
