@@ -541,7 +541,7 @@ int cae_debug_plan(const cae_engine* e, int batch, int train, char* out, int64_t
     const bool tr = train != 0, ext = e->variational;
     const StepArgs a{0, nullptr, batch, batch, batch, tr, true, nullptr, nullptr, false};
     std::string s;
-    char line[256];
+    char line[512];
     {
         HeadArgs h;
         size_t lds = 0;
@@ -552,7 +552,7 @@ int cae_debug_plan(const cae_engine* e, int batch, int train, char* out, int64_t
     for (int l = 0; l < (int)e->dec.size(); l++) {
         const ConvLayer& L = e->dec[l];
         const int ci = L.cin, co = L.cout, kh = L.kh, kw = L.kw;
-        char f[128], b[128];
+        char f[128], b[256];
         switch (choose_dec_fwd(e, L, l, batch, tr, ext)) {
             case DF_FUSED_LAST: {
                 const LastPick p = choose_last(L, l > 0 && e->dec[l - 1].has_bn);
@@ -592,8 +592,19 @@ int cae_debug_plan(const cae_engine* e, int batch, int train, char* out, int64_t
                     else snprintf(b, sizeof b, "s2_bwd<%d,%d,%d,%d,%d>", ci, p.ct, co, kh, kw);
                     break;
                 }
-                case DB_CT_LDS: snprintf(b, sizeof b, "ct_bwd_lds"); break;
-                case DB_IG: snprintf(b, sizeof b, "ig_bwd_pair"); break;
+                case DB_CT_LDS: {   // what bwd_ct_lds launches: the kernel, its grid (groups, Cin / 16, parts) and the accumulator
+                    CtBwdPlan p;
+                    (void)ct_bwd_plan(e, batch, L, l, p);
+                    snprintf(b, sizeof b, "ct_bwd_lds ctb_kernel=%s ctb_imgs=%d ctb_groups=%d ctb_parts=%d ctb_bands=%d ctb_hb=%d ctb_sharded=%d",
+                             p.bands > 1 ? "band" : "lds", p.imgs, p.groups, p.parts, p.bands, p.hb, (int)(L.sh_w >= 0));
+                    break;
+                }
+                case DB_IG: {
+                    const IgBwdPlan p = ig_bwd_plan(L, batch);
+                    snprintf(b, sizeof b, "ig_bwd_pair ig_ksplit=%d ig_tpw=%d ig_chunks=%d ig_per=%d ig_dgroup=%d ig_wn8=%d", p.ksplit,
+                             p.tiles_per_wave, p.chunks, p.per, p.d_group, p.w_n8);
+                    break;
+                }
                 case DB_GENERIC: snprintf(b, sizeof b, "wgrad+down"); break;
             }
         }

@@ -32,7 +32,9 @@ class EnginePlan(SpecPlan):
     def kernel_plan(self, batch, train):
         """the kernels a step at this batch runs (cae_debug_plan, include/cae_hip.h), no GPU needed:
         {"head": {"fwd": "fused"}, "dec0": {"fwd": "ct_fwd_lds<3,3>", "bwd": "ig_bwd_pair"}, ...,
-        "dec4": {"fwd": "last_fused<2,1,4,4>", "hb": "4", "vec4": "1", "bn": "1", "bwd": "(fused)"}, "tail": {"bwd": "fused"}}"""
+        "dec4": {"fwd": "last_fused<2,1,4,4>", "hb": "4", "vec4": "1", "bn": "1", "bwd": "(fused)"}, "tail": {"bwd": "fused"}}.
+        A layer whose backward is "ct_bwd_lds" also has ctb_kernel ("lds" | "band"), ctb_imgs, ctb_groups, ctb_parts, ctb_bands,
+        ctb_hb and ctb_sharded; one on "ig_bwd_pair" has ig_ksplit, ig_tpw, ig_chunks, ig_per, ig_dgroup and ig_wn8 (all strings)"""
         buf = C.create_string_buffer(1 << 16)
         check(self.lib.cae_debug_plan(self.handle, int(batch), 1 if train else 0, buf, len(buf)))
         plan = {}

@@ -238,7 +238,13 @@ int64_t cae_debug_read(cae_engine* e, const char* what, int index, void* host_ou
 /* Which kernels a step at `batch` runs (the choosers the launch code switches on), without a GPU: a NUL-terminated report
  * in out_host, one line per decoder layer ("dec3 fwd=s2_fwd_cs<8,4,3,4,32> epi=raw_stats bwd=s2_bwd<8,2,4,3,4>") between
  * "head fwd=fused|layers" and "tail bwd=fused|layers|-".  train = 0: the eval forward (bwd=-).  Follows cae_set_kernel_mode;
- * reports the single-device step without SyncBN.  Fails for a batch outside 1 .. max_batch or too short a buffer. */
+ * reports the single-device step without SyncBN.  The two backward families whose launch depends on the batch add the
+ * fields their launch code switches on, as key=value pairs after bwd=:
+ *   "bwd=ct_bwd_lds ctb_kernel=lds|band ctb_imgs=<images per workgroup> ctb_groups=<grid x> ctb_parts=<grid z> ctb_bands=<0 or
+ *    the bands of an image> ctb_hb=<input rows per band> ctb_sharded=<1: the weight-gradient accumulator is the sharded table>"
+ *   "bwd=ig_bwd_pair ig_ksplit=<K split of the input-gradient half> ig_tpw=<its tiles per wave> ig_chunks=<weight-gradient
+ *    chunks> ig_per=<k-steps per chunk> ig_dgroup=<input-gradient blocks per chunk> ig_wn8=<chunk rounds of 8>"
+ * Fails for a batch outside 1 .. max_batch or too short a buffer. */
 int cae_debug_plan(const cae_engine* e, int batch, int train, char* out_host, int64_t out_bytes);
 
 /* ---- measurement ------------------------------------------------------------------------- */

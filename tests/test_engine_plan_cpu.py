@@ -107,11 +107,23 @@ def branches_of(spec, batch):
     return out
 
 
+def _ig(ksplit, tpw, chunks, per, dgroup, wn8):
+    """the fields of a k_ig_bwd_pair layer's report (ig_bwd_plan)"""
+    return {"bwd": "ig_bwd_pair", "ig_ksplit": str(ksplit), "ig_tpw": str(tpw), "ig_chunks": str(chunks), "ig_per": str(per),
+            "ig_dgroup": str(dgroup), "ig_wn8": str(wn8)}
+
+
+def _ctb(kernel, imgs, groups, parts, bands, hb, sharded):
+    """the fields of a k_ct_bwd_lds / k_ct_bwd_band layer's report (ct_bwd_plan)"""
+    return {"bwd": "ct_bwd_lds", "ctb_kernel": kernel, "ctb_imgs": str(imgs), "ctb_groups": str(groups), "ctb_parts": str(parts),
+            "ctb_bands": str(bands), "ctb_hb": str(hb), "ctb_sharded": str(sharded)}
+
+
 CFG2_TRAIN = {
     "head": {"fwd": "fused"},
-    "dec0": {"fwd": "ct_fwd_lds<3,3>", "bwd": "ig_bwd_pair"},
-    "dec1": {"fwd": "ct_fwd_lds<3,3>", "bwd": "ig_bwd_pair"},
-    "dec2": {"fwd": "ct_fwd_lds<3,3>", "bwd": "ct_bwd_lds"},
+    "dec0": {"fwd": "ct_fwd_lds<3,3>", **_ig(4, 1, 5, 32, 8, 1)},
+    "dec1": {"fwd": "ct_fwd_lds<3,3>", **_ig(4, 1, 25, 32, 8, 4)},
+    "dec2": {"fwd": "ct_fwd_lds<3,3>", **_ctb("band", 1, 64, 4, 4, 4, 1)},
     "dec3": {"fwd": "s2_fwd_rows<8,4,1,2>", "bwd": "s2_bwd_rows<8,2,4,3,3,4,2,1>"},
     "dec4": {"fwd": "s2_fwd_rows<4,2,2,1>", "bwd": "s2_bwd_rows<4,4,2,3,3,2,1,3>"},
     "dec5": {"fwd": "last_fused<2,1,4,4>", "hb": "4", "vec4": "1", "bn": "1", "bwd": "(fused)"},
@@ -145,9 +157,11 @@ def test_kernel_modes():
         assert generic[False][f"dec{l}"] == {"fwd": "up", "bwd": "-"}
     every_ctb = _plan(spec, 64, 128, 32, mode=3)[True]   # bit 1: the LDS-staged backward wherever it fits
     gather = _plan(spec, 64, 128, 32, mode=5)[True]      # bit 2: the gather forward on the channel-rich layers
+    # mode 3 at batch 64: 64->32 and 32->16 stage whole images (8 and 2 per workgroup, unsharded accumulators), 16->8 as by default
+    ctb = (_ctb("lds", 8, 8, 8, 0, 0, 0), _ctb("lds", 2, 32, 4, 0, 0, 0), _ctb("band", 1, 64, 4, 4, 4, 1))
     for l in range(3):
-        assert every_ctb[f"dec{l}"] == {"fwd": "ct_fwd_lds<3,3>", "bwd": "ct_bwd_lds"}
-        assert gather[f"dec{l}"] == {"fwd": "ig_fwd_s2", "bwd": CFG2_TRAIN[f"dec{l}"]["bwd"]}
+        assert every_ctb[f"dec{l}"] == {"fwd": "ct_fwd_lds<3,3>", **ctb[l]}
+        assert gather[f"dec{l}"] == {**CFG2_TRAIN[f"dec{l}"], "fwd": "ig_fwd_s2"}
     for name in ("head", "dec3", "dec4", "dec5", "tail"):
         assert every_ctb[name] == CFG2_TRAIN[name] and gather[name] == CFG2_TRAIN[name]
 
