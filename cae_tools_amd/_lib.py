@@ -103,6 +103,11 @@ SIGNATURES = {
                                  _P]),
     "cae_render_cases": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64,
                                    C.c_int64, C.c_double, C.c_double, C.c_int, _P, _P]),
+    "cae_pixel_sums_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "cae_pixel_sums": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double,
+                                 C.c_int64, _P, _P, C.c_int64, _P]),
+    "cae_pixel_sums_about": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, _P,
+                                       _P, C.c_int64, _P]),
     "cae_ensemble_moments_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "cae_ensemble_moments": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double,
                                        C.c_double, _P, _P, _P, C.c_int64, _P]),

@@ -27,8 +27,8 @@ def build_parser():
     return p
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
+def run(args, **evaluator_options):
+    """the evaluator over parsed flags; evaluator_options: further ModelEvaluator keywords (cli/skill_maps.py)"""
     mt = ModelEvaluator(training_paths=args.train_inputs,
                         testing_paths=args.test_inputs,
                         output_html_folder=args.output_html_folder,
@@ -39,8 +39,12 @@ def main(argv=None):
                         database_path=args.database_path,
                         x_coordinate=args.x_coordinate,
                         y_coordinate=args.y_coordinate,
-                        time_coordinate=args.time_coordinate)
+                        time_coordinate=args.time_coordinate, **evaluator_options)
     mt.run()
+
+
+def main(argv=None):
+    run(build_parser().parse_args(argv))
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 // kernels_stateless.h — the kernels behind the stateless entry points of include/cae_hip.h (at the end of engine.hip's
 // extern "C" block): the loader
 // (scan, normalise + pack, permutation inverse, denormalise, metric sums, byte swap), the evaluator's per-case measures, the
-// ensemble moments and the case pages.  None of them touches an engine.
+// ensemble moments, the case pages and the per-pixel skill sums.  None of them touches an engine.
 #pragma once
 #include "device_common.h"
 
@@ -625,6 +625,201 @@ __global__ void __launch_bounds__(256) k_render_cases(const unsigned char* __res
             }
             *reinterpret_cast<unsigned*>(ob + q) = w;
         }
+    }
+}
+
+// ---- per-pixel skill sums (include/cae_hip.h, cae_pixel_sums): the reduction along the case axis.  For pixel x, over the
+// cases whose prediction p and target a at x are both finite, in fp64: {n, S d, S|d|, S d^2, S a', S p', S a'^2, S p'^2,
+// S a'p'} with d = p - a, a' = a - shift, p' = p - shift; ABOUT (cae_pixel_sums_about): a shift of its own per pixel, one
+// plane for a and one for p, read once per lane and chunk.
+// One wave (a workgroup of its own) per (tile of 256 consecutive pixels, chunk of `chunk` consecutive cases).  A lane
+// owns one 4-pixel group of the tile and walks the chunk's cases in case order with PsFlight cases' loads in flight
+// (128 bytes per lane, or 96), the 36 accumulators in registers (the four counts as integers).  A case that is no pair at a pixel adds exact zeros
+// there (both values are replaced by `shift`), so it leaves that pixel's sums as skipping it would and touches no other
+// pixel.  Nothing crosses a lane: the item's nine values per pixel are plain stores into plane k of out[chunk] - the
+// partials, or the result itself when there is one chunk - and k_pixel_fold adds the chunks' partials in chunk order.  No
+// atomics; the sums depend on the arguments alone.  16-byte loads need every case's group on one 16-byte phase: the host
+// finds case 0's first element `head` where both operands are 16 bytes aligned and sets `vec` when both case strides keep
+// that phase; the `head` pixels before it and the up to 3 after the last whole group go element by element to lanes of
+// tile 0.  Otherwise head = 0 and every load is an element load.
+// Registers: the loaded words wait unconverted (cm_word turns one pixel's pair into doubles when it is summed) and a
+// scheduling barrier after every pixel keeps the compiler from converting a whole round of loads ahead of the sums, which
+// costs 100 registers more.  A case's byte offset is wave-uniform (ps_uniform), the lane adds a 32-bit offset of its own.
+constexpr int PS_SUMS = 9;
+constexpr int PS_TILE = 64;             // 4-pixel groups per tile: one per lane
+
+struct PsArgs {
+    const unsigned char* p;     // case c: elements c * stride .. + plane
+    const unsigned char* a;
+    long long p_stride, a_stride, n_case, plane;
+    long long chunk, n_chunk;   // cases per chunk, chunks
+    int head, vec;
+    double shift;
+    const double* shifts;       // ABOUT: a' = a - shifts[x], p' = p - shifts[plane + x] in place of `shift`
+    double* out;                // (chunks, PS_SUMS, plane)
+};
+
+template <int K> struct PsWord { typedef unsigned long long type; };
+template <> struct PsWord<0> { typedef unsigned type; };
+template <> struct PsWord<1> { typedef unsigned type; };
+
+// cases in flight per lane: four of two 4-byte operands, else two (the per-pixel shifts of ABOUT take 16 registers more)
+template <int KP, int KA, bool ABOUT> struct PsFlight {
+    static constexpr int cases = !ABOUT && CmElem<KP>::bytes + CmElem<KA>::bytes == 8 ? 4 : 2;
+};
+
+// a wave-uniform byte offset, said so to the compiler: it then stays in scalar registers
+__device__ __forceinline__ long long ps_uniform(long long v) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// the stored words of N elements from byte b of the case at c (c wave-uniform, b the lane's: a scalar base and a 32-bit
+// offset for the load): 16-byte loads when `vec`, else element loads
+template <int K, int N>
+__device__ __forceinline__ void ps_load(const unsigned char* c, unsigned b, bool vec, typename PsWord<K>::type w[N]) {
+    typedef typename PsWord<K>::type W;
+    if constexpr (N == 4) {
+        if (vec) {
+            if constexpr (CmElem<K>::bytes == 4) {
+                const uint4 q = *reinterpret_cast<const uint4*>(c + b);
+                w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
+            } else {
+                const ulonglong2 q0 = *reinterpret_cast<const ulonglong2*>(c + b);
+                const ulonglong2 q1 = *reinterpret_cast<const ulonglong2*>(c + (b + 16u));
+                w[0] = q0.x, w[1] = q0.y, w[2] = q1.x, w[3] = q1.y;
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) w[j] = *reinterpret_cast<const W*>(c + (b + (unsigned)(j * CmElem<K>::bytes)));
+}
+
+// acc: S d, S|d|, S d^2, S a', S p', S a'^2, S p'^2, S a'p' with a' = a - sa, p' = p - sp.  DIFF: sa and sp may differ, so
+// the d of a case that is no pair is set to zero on its own
+template <bool DIFF>
+__device__ __forceinline__ void ps_acc(double p, double a, double sa, double sp, unsigned& n, double acc[8]) {
+    const bool pair = fabs(p) < __builtin_huge_val() && fabs(a) < __builtin_huge_val();
+    p = pair ? p : sp;
+    a = pair ? a : sa;
+    n += pair ? 1u : 0u;
+    double d = p - a;
+    if constexpr (DIFF) d = pair ? d : 0.0;
+    const double as = a - sa, ps = p - sp;
+    acc[0] += d;
+    acc[1] += fabs(d);
+    acc[2] += d * d;
+    acc[3] += as;
+    acc[4] += ps;
+    acc[5] += as * as;
+    acc[6] += ps * ps;
+    acc[7] += as * ps;
+}
+
+// pixels e0 + e .. + N-1 (e0 wave-uniform, e the lane's) over the cases [c0, c1), stored to the nine planes at dst
+template <int KP, int KA, bool ABOUT, int N>
+__device__ __forceinline__ void ps_walk(const PsArgs& s, long long c0, long long c1, long long e0, unsigned e, bool vec,
+                                        double* __restrict__ dst) {
+    constexpr int EP = CmElem<KP>::bytes, EA = CmElem<KA>::bytes, U = PsFlight<KP, KA, ABOUT>::cases;
+    typedef typename PsWord<KP>::type WP;
+    typedef typename PsWord<KA>::type WA;
+    double acc[N][8];
+    unsigned n[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        n[j] = 0u;
+#pragma unroll
+        for (int k = 0; k < 8; k++) acc[j][k] = 0.0;
+    }
+    double sa[ABOUT ? N : 1], sp[ABOUT ? N : 1];        // the shifts: per pixel (ABOUT) or the one of the call
+#pragma unroll
+    for (int j = 0; j < (ABOUT ? N : 1); j++) {
+        sa[j] = ABOUT ? s.shifts[e0 + e + j] : s.shift;
+        sp[j] = ABOUT ? s.shifts[s.plane + e0 + e + j] : s.shift;
+    }
+    const long long pstep = s.p_stride * EP, astep = s.a_stride * EA;
+    long long pc = c0 * pstep + e0 * EP, ac = c0 * astep + e0 * EA;      // byte offsets of the case in flight
+    long long c = c0;
+    for (; c + U - 1 < c1; c += U) {        // U cases in flight per lane, summed in case order
+        WP wp[U][N];
+        WA wa[U][N];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            ps_load<KP, N>(s.p + ps_uniform(pc + u * pstep), e * EP, vec, wp[u]);
+            ps_load<KA, N>(s.a + ps_uniform(ac + u * astep), e * EA, vec, wa[u]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+#pragma unroll
+            for (int j = 0; j < N; j++) {
+                ps_acc<ABOUT>(cm_word<KP>(wp[u][j]), cm_word<KA>(wa[u][j]), sa[ABOUT ? j : 0], sp[ABOUT ? j : 0], n[j], acc[j]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        pc += U * pstep;
+        ac += U * astep;
+    }
+    for (; c < c1; c++) {
+        WP wp[N];
+        WA wa[N];
+        ps_load<KP, N>(s.p + ps_uniform(pc), e * EP, vec, wp);
+        ps_load<KA, N>(s.a + ps_uniform(ac), e * EA, vec, wa);
+#pragma unroll
+        for (int j = 0; j < N; j++)
+            ps_acc<ABOUT>(cm_word<KP>(wp[j]), cm_word<KA>(wa[j]), sa[ABOUT ? j : 0], sp[ABOUT ? j : 0], n[j], acc[j]);
+        pc += pstep;
+        ac += astep;
+    }
+    dst += e0 + e;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        dst[j] = (double)n[j];
+#pragma unroll
+        for (int k = 0; k < 8; k++) dst[(k + 1) * s.plane + j] = acc[j][k];
+    }
+}
+
+// grid (tiles, chunks walked with stride gridDim.y), one wave per workgroup
+template <int KP, int KA, bool ABOUT>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) k_pixel_sums(const PsArgs s) {
+    const unsigned lane = threadIdx.x;
+    const bool vec = s.vec != 0;
+    const long long head = s.head;
+    const long long groups = (s.plane - head) >> 2;
+    const long long tail0 = head + (groups << 2);
+    const long long g0 = (long long)blockIdx.x * PS_TILE;
+    for (long long ch = blockIdx.y; ch < s.n_chunk; ch += gridDim.y) {
+        const long long c0 = ch * s.chunk;
+        const long long c1 = c0 + s.chunk < s.n_case ? c0 + s.chunk : s.n_case;
+        double* dst = s.out + ch * PS_SUMS * s.plane;
+        if (g0 + lane < groups) ps_walk<KP, KA, ABOUT, 4>(s, c0, c1, head + (g0 << 2), lane << 2, vec, dst);
+        if (blockIdx.x == 0) {
+            if (lane < head) ps_walk<KP, KA, ABOUT, 1>(s, c0, c1, 0, lane, false, dst);
+            else if (lane >= 4 && lane - 4 < s.plane - tail0) ps_walk<KP, KA, ABOUT, 1>(s, c0, c1, tail0, lane - 4, false, dst);
+        }
+    }
+}
+
+// out[j] = sum over chunks k = 0 .. n_chunk-1, in that order, of part[k * n + j]  (n = PS_SUMS * plane); eight partials
+// in flight per lane
+__global__ void __launch_bounds__(256) k_pixel_fold(const double* __restrict__ part, long long n_chunk, long long n,
+                                                    double* __restrict__ out) {
+    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < n; j += (long long)gridDim.x * 256) {
+        const double* col = part + j;
+        double sum = 0.0;
+        long long k = 0;
+        for (; k + 7 < n_chunk; k += 8) {
+            double v[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) v[u] = col[(k + u) * n];
+#pragma unroll
+            for (int u = 0; u < 8; u++) sum += v[u];
+        }
+        for (; k < n_chunk; k++) sum += col[k * n];
+        out[j] = sum;
     }
 }
 

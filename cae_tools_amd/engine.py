@@ -638,6 +638,42 @@ def case_measures(pred, actual, device=None):
     return sums / float(plane)
 
 
+def pixel_sums(pred, actual, shift=0.0, case_chunk=0, device=None):
+    """The nine per-pixel sums of channel 0 over the cases (cae_pixel_sums, include/cae_hip.h): a (9, H, W) float64 numpy
+    array {n, S d, S|d|, S d^2, S a', S p', S a'^2, S p'^2, S a'p'} with d = p - a, a' = a - shift, p' = p - shift over the
+    cases whose two values at the pixel are finite.  Operands as case_measures takes them; case_chunk 0 leaves the cut
+    of the cases to the library.  shift: one number, or a (2, H, W) array of per-pixel shifts for a and p
+    (cae_pixel_sums_about).  utils/skill_maps.maps_from_sums turns the sums into the skill maps."""
+    device = _case_device(device, pred, actual)
+    (p, pk, pshape, pstride) = _measure_operand(pred, device)
+    (a, ak, ashape, astride) = _measure_operand(actual, device)
+    if len(pshape) != 4 or len(ashape) != 4:
+        raise ValueError(f"pixel_sums: (N, C, H, W) arrays expected, got {pshape} and {ashape}")
+    if pshape[0] != ashape[0] or pshape[2:] != ashape[2:]:
+        raise ValueError(f"pixel_sums: prediction {pshape} and target {ashape} do not match")
+    (n, h, w) = (int(pshape[0]), int(pshape[2]), int(pshape[3]))
+    plane = h * w
+    about = np.ndim(shift) != 0
+    if about and np.shape(shift) != (2, h, w):
+        raise ValueError(f"pixel_sums: per-pixel shifts of shape (2, {h}, {w}) expected, got {np.shape(shift)}")
+    if n == 0 or plane == 0:
+        return np.zeros((9, h, w), dtype=np.float64)
+    lib = _lib.load()
+    need = int(lib.cae_pixel_sums_workspace_bytes(n, plane, int(case_chunk)))
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+    out = torch.empty((9, h, w), dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        if about:
+            shifts = torch.from_numpy(np.ascontiguousarray(shift, dtype=np.float64)).to(device)
+            check(lib.cae_pixel_sums_about(p.data_ptr(), pk, pstride, a.data_ptr(), ak, astride, n, plane, shifts.data_ptr(),
+                                           int(case_chunk), out.data_ptr(), ws.data_ptr(), need, stream))
+        else:
+            check(lib.cae_pixel_sums(p.data_ptr(), pk, pstride, a.data_ptr(), ak, astride, n, plane, float(shift),
+                                     int(case_chunk), out.data_ptr(), ws.data_ptr(), need, stream))
+        return out.cpu().numpy()
+
+
 def _case_device(device, *operands):
     """the device the case kernels run on: the one given, else that of a device-resident operand, else the current one"""
     if device is None:

@@ -16,6 +16,13 @@ package's definition: each input variable is scaled over its own finite values i
 prediction share one range, the error is scaled over +-max|prediction - target| (cae_case_range); a pixel's palette
 index is 0 for NaN and 1 + round-half-up(254 * clamp((v - lo) / (hi - lo), 0, 1)) otherwise, computed in fp64 on the GPU
 (cae_render_cases) from the slabs as stored and from the prediction where it still lies in HBM.
+
+skill_maps=True (cli/skill_maps.py; not a reference feature) adds the transposed reduction: per partition the per-pixel
+count, bias, mae, rmse, correlation and sd_ratio of channel 0 over the cases, from two streaming passes over the operands
+on the GPU (cae_pixel_sums about the midpoint of the output normalisation range, then cae_pixel_sums_about each pixel's
+means for the variances; utils/skill_maps.py), written as skill_<partition>.nc beside index.html and drawn on
+maps/index.html, which the report then links.  The six maps of a partition go to the GPU as six one-channel cases and are ranged and drawn by the case
+pages' kernels; ranges go over both partitions (count over [0, largest number of cases], bias over +-max|bias|).
 """
 import json
 import os
@@ -23,8 +30,8 @@ import os
 import numpy as np
 
 from ..data.arrays import as_numpy, open_mfdataset
-from ..engine import case_measures, case_range, device_operand, render_cases
-from ..utils import case_pages
+from ..engine import case_measures, case_range, device_operand, pixel_sums, render_cases
+from ..utils import case_pages, skill_maps
 from ..utils.model_database import ModelDatabase
 from ..utils.report import evaluation_report
 from .base_model import _make_data_array
@@ -38,7 +45,7 @@ class ModelEvaluator:
 
     def __init__(self, training_paths, testing_paths, output_html_folder="", model_output_variable="", model_path="",
                  database_path="", input_variables=[], sample_count=None, x_coordinate="", y_coordinate="",
-                 time_coordinate=""):
+                 time_coordinate="", skill_maps=False):
         self.training_paths = list(training_paths) if training_paths else []
         self.testing_paths = list(testing_paths) if testing_paths else []
         self.output_html_folder = output_html_folder
@@ -52,6 +59,7 @@ class ModelEvaluator:
         self.x_coordinate = x_coordinate
         self.y_coordinate = y_coordinate
         self.time_coordinate = time_coordinate
+        self.skill_maps = skill_maps
 
         self.model = load_model(self.model_path)
         print(f"Evaluating model id={self.model.get_model_id()}")
@@ -152,8 +160,9 @@ class ModelEvaluator:
                 if self._case_summary(case_dimension, partition, ds, train_ds, test_ds):
                     case_links[partition] = partition + "/index.html"
 
+        maps_link = self._skill_maps(train_ds, test_ds) if self.skill_maps else None
         self._page_ops = {}
-        page = evaluation_report(model_metrics, measures, training_parameters, training_losses, case_links)
+        page = evaluation_report(model_metrics, measures, training_parameters, training_losses, case_links, maps_link)
         os.makedirs(self.output_html_folder, exist_ok=True)
         with open(self.output_html_path, "w") as f:
             f.write(page)
@@ -270,3 +279,55 @@ class ModelEvaluator:
             print("Unable to create case summary")
             print(f"\t{type(ex).__name__}: {ex}")
             return False
+
+    # ---- per-pixel skill maps ------------------------------------------------------------------
+
+    def _skill_shift(self):
+        """the midpoint of the model's output normalisation range, or 0.0 when that is not finite: the sums' second
+        moments are taken about it"""
+        try:
+            mid = 0.5 * (float(self.model.normalisation_parameters[2]) + float(self.model.normalisation_parameters[3]))
+        except (TypeError, ValueError, IndexError):
+            return 0.0
+        return mid if np.isfinite(mid) else 0.0
+
+    def _skill_coordinates(self, ds, dims):
+        """{name: (dimension, values, attrs)} of the y / x coordinate variables that are 1-D along the target's image
+        dimensions"""
+        found = {}
+        for (name, dim) in ((self.y_coordinate, dims[0]), (self.x_coordinate, dims[1])):
+            if name and name in ds and tuple(ds[name].dims) == (dim,):
+                found[name] = (dim, np.asarray(ds[name].values), dict(getattr(ds[name], "attrs", {})))
+        return found
+
+    def _skill_maps(self, train_ds, test_ds):
+        """skill_<partition>.nc and maps/index.html; returns the page's href for the report"""
+        (target, pred) = (self.output_variable, self.model_output_variable)
+        shift = self._skill_shift()
+        parts = []
+        for (partition, ds) in (("test", test_ds), ("train", train_ds)):
+            if ds is None:
+                continue
+            ops = self._page_ops.get(partition, {})         # what the case pages have uploaded already
+            p = ops.get(pred, self._device_predictions.get(partition))
+            (p, a) = (device_operand(p if p is not None else as_numpy(ds[pred])),
+                      device_operand(ops.get(target, as_numpy(ds[target]))))
+            sums = pixel_sums(p, a, shift)
+            # the second moments once more about each pixel's own means: variances without the cancellation
+            centred = pixel_sums(p, a, skill_maps.pixel_means(sums, shift))
+            maps = skill_maps.maps_from_sums(sums, centred)
+            dims = tuple(ds[target].dims[-2:])
+            skill_maps.write_netcdf(os.path.join(self.output_html_folder, f"skill_{partition}.nc"), maps, dims,
+                                    self._skill_coordinates(ds, dims))
+            flip = bool(self.y_coordinate) and self._flip_y(ds, target)
+            parts.append((partition, int(ds[target].shape[0]), device_operand(skill_maps.stack_maps(maps)), flip))
+        if not parts:
+            return None
+        n_case = max(p[1] for p in parts)
+        ranges = {}
+        for (k, name) in enumerate(skill_maps.MAPS):
+            ranges[name] = skill_maps.map_range(name, [case_range(op.tensor[k:k + 1]) for (_, _, op, _) in parts], n_case)
+        pages = [(partition, n, [(name, *ranges[name], render_cases(op, *ranges[name], cases=[k], flip_y=flip)[0])
+                                 for (k, name) in enumerate(skill_maps.MAPS)]) for (partition, n, op, flip) in parts]
+        skill_maps.write_maps_page(os.path.join(self.output_html_folder, "maps"), pages)
+        return "maps/index.html"

@@ -185,10 +185,11 @@ STYLE = "body { font-family: sans-serif; margin: 1em 2em; } table { border-colla
         "td { border: 1px solid #bbb; padding: 2px 8px; } img { display: block; margin: 8px 0; }"
 
 
-def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None):
+def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None):
     """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
     metrics: {"test": {...}, "train": {...}} (either may be absent); measures: [(partition, {"mae": values, "mse": values})]
-    in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}."""
+    in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}; maps_link: href of
+    the per-pixel skill maps page (utils/skill_maps.py), linked after the partitions when given."""
     doc = Document("Model Evaluation")
     doc.head.add("style").text(STYLE)
     body = doc.body
@@ -204,6 +205,8 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
             body.add("img", {"src": svg_data_uri(svg_histogram(v, measure)), "alt": f"{partition} {measure} histogram"})
         if case_links and partition in case_links:
             body.add("p").add("a", {"href": case_links[partition]}).text(f"Case summary for partition {partition}")
+    if maps_link:
+        body.add("p").add("a", {"href": maps_link}).text("Skill maps per pixel")
     if parameters or history:
         body.add("h2").text("Training Summary")
     if parameters:

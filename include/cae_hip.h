@@ -375,6 +375,40 @@ int cae_render_cases(const void* src_dev, int src_kind, int64_t src_case_stride,
                      int64_t sub_case_stride, const int32_t* cases_dev, int64_t n_sel, int64_t n_case, int64_t height,
                      int64_t width, double lo, double hi, int flip_y, uint8_t* out_dev, void* hip_stream);
 
+/* ---- per-pixel skill sums (stateless): the reduction along the case axis ------------------- */
+
+/* For pixel x of `plane` (channel 0), over the cases i of n_case whose two values at x are both finite (a "pair"; any
+ * other case is skipped for that pixel only), all in fp64:
+ *   d = (double)p - (double)a,  a' = a - shift,  p' = p - shift
+ *   sums_dev[k][x], k = 0..8  =  {n, S d, S|d|, S d^2, S a', S p', S a'^2, S p'^2, S a'p'}
+ * sums_dev is nine contiguous planes of `plane` doubles; the call writes it whole, and a pixel without a pair gets nine
+ * zeros (so does every pixel when n_case == 0; plane == 0 writes nothing).  The host forms bias, mae, rmse, correlation
+ * and the ratio of the standard deviations from it (cae_tools_amd/utils/skill_maps.py); a shift near the data's centre
+ * keeps the second moments small.  Operands as cae_case_measures takes them: CAE_ELEM_* kinds read as stored, case i at
+ * element i * case_stride, pointers aligned to their element size, any plane and stride >= plane.
+ * No atomics.  The cases are cut into chunks of case_chunk consecutive cases (0: the library's choice - the longest chunk
+ * that still gives about 4096 (256-pixel tile, chunk) wave items, the waves the device holds at once, and at least 8 cases).
+ * One lane sums a pixel over a chunk in case order and a fold adds the chunks' partials in chunk order, so the same
+ * arguments give the same bits from run to run.  One chunk needs no workspace and no fold; otherwise workspace_dev
+ * (8-byte aligned) holds n_chunk * 9 * plane doubles: cae_pixel_sums_workspace_bytes bytes (0: none needed, NULL ok).
+ * Bad kinds, n_case < 0, plane < 0, case_chunk < 0, a shift that is not finite or too small a workspace: CAE_ERR_ARG,
+ * nothing written. */
+int64_t cae_pixel_sums_workspace_bytes(int64_t n_case, int64_t plane, int64_t case_chunk);
+int cae_pixel_sums(const void* pred_dev, int pred_kind, int64_t pred_case_stride,
+                   const void* actual_dev, int actual_kind, int64_t actual_case_stride,
+                   int64_t n_case, int64_t plane, double shift, int64_t case_chunk,
+                   double* sums_dev, void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
+/* The same sums about a shift of its own for every pixel: a' = a - shifts_dev[x], p' = p - shifts_dev[plane + x]
+ * (two planes of `plane` finite doubles; d = p - a as before).  With the pixel's means of a first cae_pixel_sums call as
+ * shifts, S a'^2, S p'^2 and S a'p' are the centred second moments themselves and the variances the host forms from them
+ * lose nothing to cancellation, however small they are beside the values' distance from one common shift (a two-pass
+ * variance; the evaluator's second call).  Workspace, chunks, order and errors as cae_pixel_sums. */
+int cae_pixel_sums_about(const void* pred_dev, int pred_kind, int64_t pred_case_stride,
+                         const void* actual_dev, int actual_kind, int64_t actual_case_stride,
+                         int64_t n_case, int64_t plane, const double* shifts_dev, int64_t case_chunk,
+                         double* sums_dev, void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
