@@ -1,7 +1,7 @@
 // kernels_stateless.h — the kernels behind the stateless entry points of include/cae_hip.h (at the end of engine.hip's
 // extern "C" block): the loader
 // (scan, normalise + pack, permutation inverse, denormalise, metric sums, byte swap), the evaluator's per-case measures, the
-// ensemble moments, the case pages and the per-pixel skill sums.  None of them touches an engine.
+// ensemble moments, the ensemble verification, the case pages and the per-pixel skill sums.  None of them touches an engine.
 #pragma once
 #include "device_common.h"
 
@@ -396,6 +396,270 @@ __global__ void __launch_bounds__(256) k_ensemble_moments(const EmArgs a) {
         const long long g1 = g0 + a.chunk < groups ? g0 + a.chunk : groups;
         for (long long g = g0 + lane; g < g1; g += 64)
             em_pixels<FIRST, LAST, 4>(a, yc, head + (g << 2), o0 + head + (g << 2), same_phase, vec2);
+    }
+}
+
+// ---- ensemble verification (include/cae_hip.h, cae_ensemble_verify): the K draws of a pixel against its target.  Per counted
+// pixel (the target and all K draws finite) A = S_k |m_k - a| / K, B = S_{i<j} |m_i - m_j| / K^2, (mbar - a)^2 and s^2 with
+// m_k = vmin + (double)y_k * range (two roundings), mbar and s^2 formed as k_ensemble_moments forms them; per case the five
+// sums {n, S A, S B, S (mbar - a)^2, S s^2}; per call the histogram of below = #{k: m_k < a} and the number of ties.
+// One wave (a workgroup of its own) per (case, chunk of `chunk` 4-pixel groups) item, items and loads as
+// k_ensemble_moments' (the host picks the chunk, 64 .. CM_GROUPS groups, from the size of the call alone, so that a call
+// with few cases still covers the device): the wave walks the chunk in blocks of EV_PIX = 256 pixels.  A lane loads its 4-pixel group of every
+// draw (one 16-byte load per draw where the draws share a phase, else four element loads a wave reads along a line) into
+// the [K][EV_PIX] fp32 tile in LDS - the members are never a register array - and then takes the pixels lane, lane + 64,
+// lane + 128, lane + 192 of the block, each alone: one walk down its column in ascending draw order, eight members at a time
+// in registers (then four, then one), gathers {finite?, S|m - a|, below, tied, s1, s2} and pairs each block with itself and
+// with every member j below it: all K (K - 1) / 2 pairs, no sort.  The members are converted again at every read
+// (cvt, mul, add in fp64): fp64 columns would double the tile, which at K = 64 is already 64 KiB.  The head before the
+// case's first 16-byte phase and the tail after its last whole group go to lanes of chunk 0, one pixel each.
+// Fixed order, no atomics of any kind: a lane adds its pixels in block order, the wave's lanes meet in a fixed shuffle tree,
+// item sums are plain stores (the partials, or the case's result when it has one chunk) and k_verify_fold adds a case's
+// chunks in chunk order: the same bits from run to run.  The ranks are integers: per pixel row one ballot per bin, lane b
+// keeps bin b of the workgroup (bin 64 and the ties sit in wave-uniform counters), plain stores of the workgroup's K + 2
+// counts to the workspace, and the fold adds the workgroups' counts into rank_counts with a load, an add and a store per bin.
+constexpr int EV_SUMS = 5;
+constexpr int EV_PIX = 256;
+
+struct EvArgs {
+    const float* y;             // draw k of case c: y + c * case_stride + k * draw_stride, `plane` floats
+    long long case_stride, draw_stride;
+    const unsigned char* a;     // target of case c: element c * a_stride
+    long long a_stride, plane;
+    int K, nch, chunk;          // draws, chunks per case, 4-pixel groups per chunk (a multiple of 64)
+    long long items;
+    double vmin, range;
+    double* sums;               // (items, EV_SUMS)
+    long long* ranks;           // (gridDim.x, K + 2)
+};
+
+struct EvAcc {
+    unsigned n;
+    double sa, sb, e, v;        // S_x S_k |m_k - a|, S_x S_{i<j} |m_i - m_j|, S (mbar - a)^2, S s^2
+};
+
+// member k of the pixel whose draws are col[k * EV_PIX]
+__device__ __forceinline__ double ev_member(const EvArgs& s, const float* col, int k) {
+#pragma clang fp contract(off)
+    const double t = (double)col[k * EV_PIX] * s.range;
+    return s.vmin + t;
+}
+
+// what one walk over a pixel's members in ascending draw order gathers
+struct EvWalk {
+    double av, y0, s1, s2, sa;
+    int below;
+    bool ok, tie;
+};
+
+// member k, and its share of the walk
+__device__ __forceinline__ double ev_visit(const EvArgs& s, const float* col, int k, EvWalk& w) {
+#pragma clang fp contract(off)
+    const float yf = col[k * EV_PIX];
+    w.ok = w.ok && fabsf(yf) < __builtin_huge_valf();
+    const double y = (double)yf;
+    const double t = y * s.range;
+    const double m = s.vmin + t;
+    const double d = y - w.y0;
+    w.s1 += d;
+    w.s2 += d * d;
+    w.sa += fabs(m - w.av);
+    w.below += m < w.av ? 1 : 0;
+    w.tie = w.tie || m == w.av;
+    return m;
+}
+
+// R members i0 .. i0 + R - 1 in registers (visited as they are read): their pairs among themselves and with every j < i0
+template <int R>
+__device__ __forceinline__ void ev_block(const EvArgs& s, const float* col, int i0, EvWalk& w, double b[4]) {
+    double r[R];
+#pragma unroll
+    for (int u = 0; u < R; u++) r[u] = ev_visit(s, col, i0 + u, w);
+#pragma unroll
+    for (int u = 1; u < R; u++)
+#pragma unroll
+        for (int v = 0; v < u; v++) b[(u + v) & 3] += fabs(r[u] - r[v]);
+#pragma unroll 2
+    for (int j = 0; j < i0; j++) {
+        const double mj = ev_member(s, col, j);
+#pragma unroll
+        for (int u = 0; u < R; u++) b[u & 3] += fabs(r[u] - mj);
+    }
+}
+
+// the pixel whose draws are col[k * EV_PIX] and whose target is element e of the case at ac: its sums into acc;
+// returns `below`, or -1 when the pixel is not counted.  One walk in ascending draw order, in blocks of 8, 4 and 1 members
+template <int KA>
+__device__ __forceinline__ int ev_pixel(const EvArgs& s, const float* col, const unsigned char* ac, long long e, EvAcc& acc,
+                                        bool& tied) {
+#pragma clang fp contract(off)
+    const int K = s.K;
+    EvWalk w;
+    w.av = cm_load1<KA>(ac, e);
+    w.ok = fabs(w.av) < __builtin_huge_val();
+    w.y0 = (double)col[0];
+    w.s1 = 0.0, w.s2 = 0.0, w.sa = 0.0, w.below = 0, w.tie = false;
+    double b[4] = {0.0, 0.0, 0.0, 0.0};
+    int i = 0;
+    for (; i + 8 <= K; i += 8) ev_block<8>(s, col, i, w, b);
+    if (i + 4 <= K) {
+        ev_block<4>(s, col, i, w, b);
+        i += 4;
+    }
+    for (; i < K; i++) ev_block<1>(s, col, i, w, b);
+    if (!w.ok) return -1;
+    const double Kd = (double)K;
+    const double mbar = s.vmin + (w.y0 + w.s1 / Kd) * s.range;
+    const double var = (w.s2 - w.s1 * w.s1 / Kd) / (Kd - 1.0);
+    const double dm = mbar - w.av;
+    acc.n += 1u;
+    acc.sa += w.sa;
+    acc.sb += (b[0] + b[1]) + (b[2] + b[3]);
+    acc.e += dm * dm;
+    acc.v += (var < 0.0 ? 0.0 : var) * s.range * s.range;
+    tied = w.tie;
+    return w.below;
+}
+
+// one pixel row of the wave into the rank counters: lane b keeps bin b, c64 and ctied are wave-uniform.  Every lane of the
+// wave calls it (below = -1: no counted pixel in this lane)
+__device__ __forceinline__ void ev_count(int K, int lane, int below, bool tied, unsigned long long& mine,
+                                         unsigned long long& c64, unsigned long long& ctied) {
+    for (int b = 0; b <= K; b++) {
+        const unsigned long long c = (unsigned long long)__popcll(__ballot(below == b));
+        if (b < 64) mine += lane == b ? c : 0ull;
+        else c64 += c;
+    }
+    ctied += (unsigned long long)__popcll(__ballot(below >= 0 && tied));
+}
+
+template <int KA>
+__global__ void __launch_bounds__(64) k_ensemble_verify(const EvArgs s) {
+    extern __shared__ __align__(16) float ev_tile[];          // [K][EV_PIX]
+    constexpr int EA = CmElem<KA>::bytes;
+    const int lane = threadIdx.x;
+    const int K = s.K;
+    const bool same_phase = (s.draw_stride & 3) == 0;
+    unsigned long long mine = 0ull, c64 = 0ull, ctied = 0ull;
+    for (long long item = blockIdx.x; item < s.items; item += gridDim.x) {
+        const long long cs = item / s.nch;
+        const int ch = (int)(item - cs * s.nch);
+        const float* yc = s.y + cs * s.case_stride;
+        const unsigned char* ac = s.a + cs * s.a_stride * EA;
+        int h = 0;
+        if (same_phase)
+            for (int t = 3; t >= 0; t--)
+                if (((uintptr_t)(yc + t) & 15) == 0) h = t;
+        const long long head = h < s.plane ? h : s.plane;
+        const long long groups = (s.plane - head) >> 2;
+        const long long tail0 = head + (groups << 2);
+        EvAcc acc = {0u, 0.0, 0.0, 0.0, 0.0};
+        if (ch == 0 && (head > 0 || tail0 < s.plane)) {
+            long long e = -1;
+            if (lane < head) e = lane;
+            else if (lane >= 4 && lane - 4 < s.plane - tail0) e = tail0 + lane - 4;
+            int below = -1;
+            bool tied = false;
+            if (e >= 0) {
+                for (int k = 0; k < K; k++) ev_tile[k * EV_PIX + lane] = yc[k * s.draw_stride + e];
+                below = ev_pixel<KA>(s, ev_tile + lane, ac, e, acc, tied);
+            }
+            ev_count(K, lane, below, tied, mine, c64, ctied);
+            __syncthreads();
+        }
+        const long long g0 = (long long)ch * s.chunk;
+        const long long g1 = g0 + s.chunk < groups ? g0 + s.chunk : groups;
+        for (long long gb = g0; gb < g1; gb += 64) {
+            const long long e0 = head + (gb << 2);
+            const int npix = (int)(g1 - gb < 64 ? g1 - gb : 64) << 2;
+            if (same_phase) {
+                if (gb + lane < g1) {
+                    const float* src = yc + e0 + 4 * lane;
+#pragma unroll 4
+                    for (int k = 0; k < K; k++)
+                        *reinterpret_cast<float4*>(ev_tile + k * EV_PIX + 4 * lane) =
+                            *reinterpret_cast<const float4*>(src + k * s.draw_stride);
+                }
+            } else {
+                for (int c = lane; c < npix; c += 64) {
+                    const float* src = yc + e0 + c;
+#pragma unroll 4
+                    for (int k = 0; k < K; k++) ev_tile[k * EV_PIX + c] = src[k * s.draw_stride];
+                }
+            }
+            __syncthreads();
+            for (int c0 = 0; c0 < npix; c0 += 64) {
+                const int c = c0 + lane;
+                int below = -1;
+                bool tied = false;
+                if (c < npix) below = ev_pixel<KA>(s, ev_tile + c, ac, e0 + c, acc, tied);
+                ev_count(K, lane, below, tied, mine, c64, ctied);
+            }
+            __syncthreads();
+        }
+        const double Kd = (double)K;
+        double v0 = acc.sa / Kd, v1 = acc.sb / (Kd * Kd), v2 = acc.e, v3 = acc.v;
+        unsigned n = acc.n;
+        for (int off = 32; off > 0; off >>= 1) {
+            n += __shfl_down(n, off, 64);
+            v0 += __shfl_down(v0, off, 64);
+            v1 += __shfl_down(v1, off, 64);
+            v2 += __shfl_down(v2, off, 64);
+            v3 += __shfl_down(v3, off, 64);
+        }
+        if (lane == 0) {
+            double* o = s.sums + item * EV_SUMS;
+            o[0] = (double)n;
+            o[1] = v0;
+            o[2] = v1;
+            o[3] = v2;
+            o[4] = v3;
+        }
+    }
+    long long* rp = s.ranks + (long long)blockIdx.x * (K + 2);
+    if (lane <= K) rp[lane] = (long long)mine;      // (lane <= 63: bin 64 of K = 64 follows)
+    if (lane == 0) {
+        if (K == 64) rp[64] = (long long)c64;
+        rp[K + 1] = (long long)ctied;
+    }
+}
+
+// Workgroup b < n_bin: ranks[b] += the sum over the n_block workgroups' counts of bin b (integers: exact in any order; one
+// load, add and store of ranks[b]).  The workgroups after them, when a case has nch > 1 chunks: out[i][q] = the sum over
+// chunks k = 0 .. nch-1, in that order, of part[(i * nch + k)][q]
+__global__ void __launch_bounds__(256) k_verify_fold(const double* __restrict__ part, long long n_case, int nch,
+                                                     double* __restrict__ out, const long long* __restrict__ rpart,
+                                                     int n_block, int n_bin, long long* __restrict__ ranks) {
+    __shared__ long long red[CM_WAVES];
+    if ((int)blockIdx.x < n_bin) {
+        const int b = blockIdx.x;
+        long long t = 0;
+        for (int i = threadIdx.x; i < n_block; i += 256) t += rpart[(long long)i * n_bin + b];
+        for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < CM_WAVES; w++) t += red[w];
+            ranks[b] = ranks[b] + t;
+        }
+        return;
+    }
+    // one thread per (case, sum): its chunks' partials in chunk order, sixteen loads in flight
+    const long long nb = (long long)gridDim.x - n_bin;
+    for (long long j = ((long long)blockIdx.x - n_bin) * 256 + threadIdx.x; j < n_case * EV_SUMS; j += nb * 256) {
+        const long long i = j / EV_SUMS;
+        const double* col = part + i * nch * EV_SUMS + (j - i * EV_SUMS);
+        double sum = 0.0;
+        int k = 0;
+        for (; k + 15 < nch; k += 16) {
+            double v[16];
+#pragma unroll
+            for (int u = 0; u < 16; u++) v[u] = col[(long long)(k + u) * EV_SUMS];
+#pragma unroll
+            for (int u = 0; u < 16; u++) sum += v[u];
+        }
+        for (; k < nch; k++) sum += col[(long long)k * EV_SUMS];
+        out[j] = sum;
     }
 }
 

@@ -1,4 +1,4 @@
-// stateless_host.h - host only: the entry points of cae_hip.h that use no engine (loader, evaluator, ensemble moments, case
+// stateless_host.h - host only: the entry points of cae_hip.h that use no engine (loader, evaluator, ensemble moments and verification, case
 // pages, per-pixel skill sums) over kernels_stateless.h.  Included by engine.hip alone, at the place this code has always had in it.
 #pragma once
 
@@ -216,6 +216,95 @@ int cae_ensemble_moments(const float* draws, int64_t case_stride, int64_t draw_s
     else if (first) hipLaunchKernelGGL((k_ensemble_moments<true, false>), grid, dim3(256), 0, s, a);
     else if (last) hipLaunchKernelGGL((k_ensemble_moments<false, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_ensemble_moments<false, false>), grid, dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+// ---- ensemble verification ---------------------------------------------------------------------
+
+constexpr int64_t EV_MAX_BLOCKS = 8192;
+
+// 4-pixel groups per chunk: cae_ensemble_moments' rule - about 4096 wave items where the call is large enough, chunks of
+// 64 .. CM_GROUPS groups.  It depends on n_case and plane alone, so the same call folds in the same order every time; a
+// call with few cases (VaeEngine.ensemble brings max_batch / K) is cut finer and still covers the device.
+static int64_t verify_chunk(int64_t n_case, int64_t plane) {
+    const int64_t groups = (plane + 3) / 4;
+    const int64_t chunk = (n_case * groups / 4096 + 63) / 64 * 64;
+    return chunk < 64 ? 64 : (chunk > CM_GROUPS ? CM_GROUPS : chunk);
+}
+
+static int64_t verify_chunks(int64_t n_case, int64_t plane) {
+    const int64_t chunk = verify_chunk(n_case, plane);
+    return ((plane + 3) / 4 + chunk - 1) / chunk;
+}
+
+static int64_t verify_blocks(int64_t n_case, int64_t plane) {
+    const int64_t items = n_case * verify_chunks(n_case, plane);
+    return items < EV_MAX_BLOCKS ? items : EV_MAX_BLOCKS;
+}
+
+int64_t cae_ensemble_verify_workspace_bytes(int64_t n_case, int64_t plane, int k_total) {
+    if (n_case < 1 || plane < 1 || k_total < 2 || k_total > 64) return 0;
+    const int64_t nch = verify_chunks(n_case, plane);
+    const int64_t part = nch > 1 ? n_case * nch * EV_SUMS * (int64_t)sizeof(double) : 0;
+    return part + verify_blocks(n_case, plane) * (k_total + 2) * (int64_t)sizeof(int64_t);
+}
+
+int cae_ensemble_verify(const float* draws, int64_t case_stride, int64_t draw_stride, const void* actual, int actual_kind,
+                        int64_t actual_stride, int64_t n_case, int64_t plane, int k_total, double vmin, double range,
+                        double* case_sums, int64_t* rank_counts, void* workspace, int64_t workspace_bytes,
+                        void* hip_stream) {
+    if (n_case < 0 || plane < 0 || k_total < 2 || k_total > 64 || actual_kind < CAE_ELEM_F32 || actual_kind > CAE_ELEM_F64_BE)
+        return fail(CAE_ERR_ARG, "cae_ensemble_verify: bad argument (n_case >= 0, plane >= 0, 2 <= k_total <= 64, a CAE_ELEM_* kind)");
+    if (case_stride < 0 || draw_stride < 0 || actual_stride < 0) return fail(CAE_ERR_ARG, "cae_ensemble_verify: negative stride");
+    if (!(vmin - vmin == 0.0) || !(range - range == 0.0) || range < 0.0)
+        return fail(CAE_ERR_ARG, "cae_ensemble_verify: vmin must be finite, range finite and not negative");
+    if (n_case == 0 || plane == 0) return CAE_OK;
+    if (!draws || !actual || !case_sums || !rank_counts) return fail(CAE_ERR_ARG, "cae_ensemble_verify: null pointer");
+    // extents in 128 bits: no stride, however large, wraps a product; what the kernel indexes stays below 2^60 elements
+    const __int128 draws_of_case = (__int128)(k_total - 1) * draw_stride + plane;
+    const __int128 cases_of_draw = (__int128)(n_case - 1) * case_stride + plane;
+    const __int128 limit = (__int128)1 << 60;
+    if (draws_of_case + (__int128)(n_case - 1) * case_stride > limit || (__int128)(n_case - 1) * actual_stride + plane > limit)
+        return fail(CAE_ERR_ARG, "cae_ensemble_verify: an operand reaches 2^60 elements from its pointer");
+    const bool case_major = case_stride >= draws_of_case && draw_stride >= plane;
+    const bool draw_major = draw_stride >= cases_of_draw && (n_case == 1 || case_stride >= plane);
+    if (!case_major && !draw_major) return fail(CAE_ERR_ARG, "cae_ensemble_verify: the strides make planes overlap");
+    if (actual_stride < plane) return fail(CAE_ERR_ARG, "cae_ensemble_verify: the target's case stride is shorter than the plane");
+    const int ea = actual_kind == CAE_ELEM_F32 || actual_kind == CAE_ELEM_F32_BE ? 4 : 8;
+    if (((uintptr_t)draws & 3) || ((uintptr_t)actual % ea) || ((uintptr_t)case_sums & 7) || ((uintptr_t)rank_counts & 7))
+        return fail(CAE_ERR_ARG, "cae_ensemble_verify: pointers must be aligned to their element size");
+    const int64_t nch = verify_chunks(n_case, plane);
+    if (nch > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_ensemble_verify: plane too large");
+    const int64_t need = cae_ensemble_verify_workspace_bytes(n_case, plane, k_total);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
+        return fail(CAE_ERR_ARG, "cae_ensemble_verify: needs a workspace of %lld bytes (cae_ensemble_verify_workspace_bytes)",
+                    (long long)need);
+    const int64_t blocks = verify_blocks(n_case, plane);
+    const int64_t part = nch > 1 ? n_case * nch * EV_SUMS : 0;          // doubles before the rank partials
+    EvArgs a;
+    memset(&a, 0, sizeof a);
+    a.y = draws, a.case_stride = case_stride, a.draw_stride = draw_stride;
+    a.a = (const unsigned char*)actual, a.a_stride = actual_stride, a.plane = plane;
+    a.K = k_total, a.nch = (int)nch, a.chunk = (int)verify_chunk(n_case, plane), a.items = n_case * nch;
+    a.vmin = vmin, a.range = range;
+    a.sums = nch > 1 ? (double*)workspace : case_sums;
+    a.ranks = (long long*)((double*)workspace + part);
+    hipStream_t s = (hipStream_t)hip_stream;
+    const dim3 grid((unsigned)blocks);
+    const size_t lds = (size_t)k_total * EV_PIX * sizeof(float);        // at most 64 KiB
+    switch (actual_kind) {
+    case CAE_ELEM_F32: hipLaunchKernelGGL((k_ensemble_verify<0>), grid, dim3(64), lds, s, a); break;
+    case CAE_ELEM_F32_BE: hipLaunchKernelGGL((k_ensemble_verify<1>), grid, dim3(64), lds, s, a); break;
+    case CAE_ELEM_F64: hipLaunchKernelGGL((k_ensemble_verify<2>), grid, dim3(64), lds, s, a); break;
+    default: hipLaunchKernelGGL((k_ensemble_verify<3>), grid, dim3(64), lds, s, a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    const int n_bin = k_total + 2;
+    int64_t fb = nch > 1 ? (n_case * EV_SUMS + 255) / 256 : 0;
+    if (fb > 4096) fb = 4096;
+    hipLaunchKernelGGL(k_verify_fold, dim3((unsigned)(n_bin + fb)), dim3(256), 0, s, (const double*)workspace, (long long)n_case,
+                       (int)nch, case_sums, (const long long*)a.ranks, (int)blocks, n_bin, (long long*)rank_counts);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }

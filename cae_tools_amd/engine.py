@@ -674,6 +674,42 @@ def pixel_sums(pred, actual, shift=0.0, case_chunk=0, device=None):
         return out.cpu().numpy()
 
 
+def ensemble_verify(draws, actual, vmin, vmax, layout="case", device=None):
+    """cae_ensemble_verify (include/cae_hip.h) on the K draws of every case at once: draws is a float32 numpy array or CUDA
+    tensor (N, K, H, W) or (N, K, C, H, W) for layout "case", (K, N, H, W) or (K, N, C, H, W) for layout "draw" - the
+    normalised decoder output, channel 0 is verified - and actual an (N, C, H, W) target in physical units as case_measures
+    takes it.  The members are vmin + y * (vmax - vmin).  Returns (case_sums (N, 5) float64 {n, S A, S B, S (mbar - a)^2,
+    S s^2}, rank_counts (K + 2,) int64); utils/ensemble_scores.scores_from_sums turns them into the scores."""
+    if layout not in ("case", "draw"):
+        raise ValueError(f"ensemble_verify: layout must be 'case' or 'draw', got {layout!r}")
+    device = _case_device(device, draws, actual)
+    if not isinstance(draws, torch.Tensor):
+        draws = torch.from_numpy(np.ascontiguousarray(draws, dtype=np.float32))
+    if draws.dtype != torch.float32 or draws.dim() not in (4, 5):
+        raise ValueError(f"ensemble_verify: float32 draws of 4 or 5 dimensions expected, got {draws.dtype} {tuple(draws.shape)}")
+    y = draws.to(device).contiguous()
+    (a, ak, ashape, astride) = _measure_operand(actual, device)
+    (n, k) = (int(y.shape[0]), int(y.shape[1])) if layout == "case" else (int(y.shape[1]), int(y.shape[0]))
+    if len(ashape) != 4 or ashape[0] != n or tuple(ashape[2:]) != tuple(y.shape[-2:]):
+        raise ValueError(f"ensemble_verify: draws {tuple(y.shape)} ({layout} major) and target {tuple(ashape)} do not match")
+    if not 2 <= k <= 64:
+        raise ValueError(f"ensemble_verify: 2 to 64 draws expected, got {k}")
+    plane = int(y.shape[-2] * y.shape[-1])
+    field = plane * (int(y.shape[2]) if y.dim() == 5 else 1)
+    (case_stride, draw_stride) = (k * field, field) if layout == "case" else (field, n * field)
+    sums = torch.zeros((n, 5), dtype=torch.float64, device=device)
+    ranks = torch.zeros(k + 2, dtype=torch.int64, device=device)
+    if n and plane:
+        lib = _lib.load()
+        need = int(lib.cae_ensemble_verify_workspace_bytes(n, plane, k))
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            check(lib.cae_ensemble_verify(y.data_ptr(), case_stride, draw_stride, a.data_ptr(), ak, astride, n, plane, k,
+                                          float(vmin), float(vmax) - float(vmin), sums.data_ptr(), ranks.data_ptr(),
+                                          ws.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream))
+    return sums.cpu().numpy(), ranks.cpu().numpy()
+
+
 def _case_device(device, *operands):
     """the device the case kernels run on: the one given, else that of a device-resident operand, else the current one"""
     if device is None:

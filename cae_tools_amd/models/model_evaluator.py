@@ -23,6 +23,11 @@ on the GPU (cae_pixel_sums about the midpoint of the output normalisation range,
 means for the variances; utils/skill_maps.py), written as skill_<partition>.nc beside index.html and drawn on
 maps/index.html, which the report then links.  The six maps of a partition go to the GPU as six one-channel cases and are ranged and drawn by the case
 pages' kernels; ranges go over both partitions (count over [0, largest number of cases], bias over +-max|bias|).
+
+ensemble_size=K (cli/verify_ensemble.py; a VarAEModel only, not a reference feature) verifies the model's K-member ensemble
+against the target per partition (VarAEModel.verify_ensemble, cae_ensemble_verify on the GPU): ensemble_<partition>.json
+with the scores, rank counts, K and seed (strict JSON: a score that is not finite is null), a per-case crps variable beside mae / mse in the data set, and the report's
+"Ensemble verification" section.
 """
 import json
 import os
@@ -31,7 +36,7 @@ import numpy as np
 
 from ..data.arrays import as_numpy, open_mfdataset
 from ..engine import case_measures, case_range, device_operand, pixel_sums, render_cases
-from ..utils import case_pages, skill_maps
+from ..utils import case_pages, ensemble_scores, skill_maps
 from ..utils.model_database import ModelDatabase
 from ..utils.report import evaluation_report
 from .base_model import _make_data_array
@@ -45,7 +50,7 @@ class ModelEvaluator:
 
     def __init__(self, training_paths, testing_paths, output_html_folder="", model_output_variable="", model_path="",
                  database_path="", input_variables=[], sample_count=None, x_coordinate="", y_coordinate="",
-                 time_coordinate="", skill_maps=False):
+                 time_coordinate="", skill_maps=False, ensemble_size=None, ensemble_seed=0):
         self.training_paths = list(training_paths) if training_paths else []
         self.testing_paths = list(testing_paths) if testing_paths else []
         self.output_html_folder = output_html_folder
@@ -61,7 +66,14 @@ class ModelEvaluator:
         self.time_coordinate = time_coordinate
         self.skill_maps = skill_maps
 
+        (self.ensemble_size, self.ensemble_seed) = (ensemble_size, int(ensemble_seed))
+        if ensemble_size is not None and (int(ensemble_size) != ensemble_size or not 2 <= int(ensemble_size) <= 64):
+            raise ValueError(f"ensemble_size must be an integer from 2 to 64, got {ensemble_size!r}")
+
         self.model = load_model(self.model_path)
+        if ensemble_size is not None and type(self.model).__name__ != "VarAEModel":
+            raise ValueError(f"ensemble_size needs a VarAEModel (train_cae --method var): {self.model_path} holds a "
+                             f"{type(self.model).__name__}")
         print(f"Evaluating model id={self.model.get_model_id()}")
         self.model_input_variables = self.model.get_input_variable_names()
         self.output_variable = self.model.get_output_variable_name()
@@ -148,6 +160,7 @@ class ModelEvaluator:
             training_parameters = json.loads(f.read())
 
         measures = []
+        ensemble = []
         case_links = {}
         for (partition, ds) in (("test", test_ds), ("train", train_ds)):
             if ds is None:
@@ -155,6 +168,8 @@ class ModelEvaluator:
             values = self.case_measures(ds, partition)
             for measure in MEASURES:
                 ds[measure] = _make_data_array(ds, values[measure], (case_dimension,))
+            if self.ensemble_size is not None:
+                ds["crps"] = _make_data_array(ds, self._verify_ensemble(partition, ds, values, ensemble), (case_dimension,))
             measures.append((partition, values))
             if self.x_coordinate and self.y_coordinate and self.time_coordinate:
                 if self._case_summary(case_dimension, partition, ds, train_ds, test_ds):
@@ -162,10 +177,25 @@ class ModelEvaluator:
 
         maps_link = self._skill_maps(train_ds, test_ds) if self.skill_maps else None
         self._page_ops = {}
-        page = evaluation_report(model_metrics, measures, training_parameters, training_losses, case_links, maps_link)
+        page = evaluation_report(model_metrics, measures, training_parameters, training_losses, case_links, maps_link,
+                                 ensemble=ensemble or None)
         os.makedirs(self.output_html_folder, exist_ok=True)
         with open(self.output_html_path, "w") as f:
             f.write(page)
+
+    def _verify_ensemble(self, partition, ds, values, records):
+        """VarAEModel.verify_ensemble on one partition: ensemble_<partition>.json in the output folder, the report's record
+        appended to `records`; returns the per-case crps"""
+        scores = self.model.verify_ensemble(ds, self.model.get_input_variable_names(), self.output_variable,
+                                            int(self.ensemble_size), self.ensemble_seed)
+        record = {k: v for (k, v) in scores.items() if k not in ("case_sums", "case_crps")}
+        record["mae"] = float(np.mean(values["mae"])) if len(values["mae"]) else float("nan")
+        os.makedirs(self.output_html_folder, exist_ok=True)
+        with open(os.path.join(self.output_html_folder, f"ensemble_{partition}.json"), "w") as f:
+            # strict JSON: what is not finite (no counted pixel) is written as null
+            json.dump(ensemble_scores.json_record({**record, "case_crps": scores["case_crps"]}), f, indent=1, allow_nan=False)
+        records.append((partition, {**record, "case_crps": scores["case_crps"]}))
+        return scores["case_crps"]
 
     def _case_summary(self, case_dimension, partition, ds, train_ds, test_ds):
         """the case pages of one partition: netcdf2html's (:205-253, 285-293) where that optional package imports, else

@@ -197,3 +197,27 @@ class VarAEModel(EngineModel):
         if latent_variable is not None:
             for (suffix, t) in (("_mu", mu), ("_logvar", logvar)):
                 score_ds[latent_variable + suffix] = _make_data_array(score_ds, t.cpu().numpy(), (n_dimension, "model_latent"))
+
+    def verify_ensemble(self, score_ds, input_variables, output_variable, ensemble_size, ensemble_seed=0):
+        """The K = ensemble_size draws of apply(ensemble_size=K) verified against score_ds[output_variable] (channel 0, in
+        physical units) where they are decoded (cae_ensemble_verify, include/cae_hip.h): the dict of
+        utils/ensemble_scores.scores_from_sums - n, crps, fair_crps, rmse_mean, spread, spread_skill, rank_counts,
+        rank_frequencies, tied, tied_fraction and the per-case "case_crps" (N,) - with the "case_sums" (N, 5) they come from and
+        "ensemble_seed".  2 <= K <= 64.  Under a process group every rank computes all cases."""
+        from ..data.arrays import as_numpy
+        from ..utils import ensemble_scores
+        if int(ensemble_size) != ensemble_size or not 2 <= int(ensemble_size) <= 64:
+            raise ValueError(f"ensemble_size must be an integer from 2 to 64 to be verified, got {ensemble_size!r}")
+        k = int(ensemble_size)
+        n = int(score_ds[input_variables[0]].shape[0])
+        _ve.check_noise_index(n, self.encoded_dim_size)
+        _dp.select_device()
+        ds = DSDataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input)
+        ds.set_normalisation_parameters(self.normalisation_parameters)
+        x = ds.device_inputs()
+        eng = self._inference_engine(n)
+        (mu, logvar) = eng.encode(x)
+        (_, _, sums, ranks) = eng.ensemble(mu, logvar, k, seed=ensemble_seed, vmin=ds.min_output, vmax=ds.max_output,
+                                           want_std=False, target=as_numpy(score_ds[output_variable]))
+        scores = ensemble_scores.scores_from_sums(sums, ranks, k)
+        return {**scores, "case_sums": sums, "ensemble_seed": int(ensemble_seed)}

@@ -144,6 +144,26 @@ def svg_histogram(values, title):
     return _svg(title, body, "value", "count", (lo, hi), (0.0, float(top)))
 
 
+def svg_rank_histogram(counts, title):
+    """the rank histogram of an ensemble: one <rect class="rank"> per rank 0 .. K carrying its count in data-count, and the
+    level of a flat histogram as a dashed line"""
+    counts = [int(c) for c in counts]
+    top = max(max(counts, default=0), 1)
+    nb = max(len(counts), 1)
+    body = []
+    for k, c in enumerate(counts):
+        xa = _scale(float(k), 0.0, float(nb), _L, _W - _R)
+        xb = _scale(float(k + 1), 0.0, float(nb), _L, _W - _R)
+        y = _scale(float(c), 0.0, float(top), _H - _B, _T)
+        body.append(f'<rect class="rank" data-count="{c}" x="{xa:.2f}" y="{y:.2f}" width="{max(xb - xa, 0.5):.2f}" '
+                    f'height="{(_H - _B) - y:.2f}" fill="seagreen" stroke="white" stroke-width="0.5"/>')
+    if counts and sum(counts) > 0:
+        y = _scale(sum(counts) / nb, 0.0, float(top), _H - _B, _T)
+        body.append(f'<line class="flat" x1="{_L}" y1="{y:.2f}" x2="{_W - _R}" y2="{y:.2f}" stroke="black" '
+                    'stroke-dasharray="4 3"/>')
+    return _svg(title, body, "members below the target", "pixels", (0.0, float(nb - 1)), (0.0, float(top)))
+
+
 _COLOURS = ("steelblue", "darkorange", "seagreen", "crimson")
 
 
@@ -185,11 +205,17 @@ STYLE = "body { font-family: sans-serif; margin: 1em 2em; } table { border-colla
         "td { border: 1px solid #bbb; padding: 2px 8px; } img { display: block; margin: 8px 0; }"
 
 
-def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None):
+ENSEMBLE_ROWS = (("crps", "crps"), ("fair crps", "fair_crps"), ("mean per-case mae (deterministic)", "mae"),
+                 ("rmse of the ensemble mean", "rmse_mean"), ("spread", "spread"), ("spread-skill ratio", "spread_skill"))
+
+
+def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None, ensemble=None):
     """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
     metrics: {"test": {...}, "train": {...}} (either may be absent); measures: [(partition, {"mae": values, "mse": values})]
     in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}; maps_link: href of
-    the per-pixel skill maps page (utils/skill_maps.py), linked after the partitions when given."""
+    the per-pixel skill maps page (utils/skill_maps.py), linked after the partitions when given; ensemble: [(partition,
+    record)] of VarAEModel.verify_ensemble's scores with "mae" (the mean per-case mae of the deterministic prediction) added:
+    an "Ensemble verification" section with the ENSEMBLE_ROWS table, the rank histogram and the per-case CRPS histogram."""
     doc = Document("Model Evaluation")
     doc.head.add("style").text(STYLE)
     body = doc.body
@@ -207,6 +233,14 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
             body.add("p").add("a", {"href": case_links[partition]}).text(f"Case summary for partition {partition}")
     if maps_link:
         body.add("p").add("a", {"href": maps_link}).text("Skill maps per pixel")
+    if ensemble:
+        body.add("h2").text("Ensemble verification")
+        for (partition, rec) in ensemble:
+            body.add("h3").text(f"{partition}: {rec['ensemble_size']} members, {rec['n']} pixels, {rec['tied']} tied")
+            body.table([["Score Name", "Score Value"]] + [[label, f"{float(rec[key]):0.6g}"] for (label, key) in ENSEMBLE_ROWS])
+            body.add("img", {"src": svg_data_uri(svg_rank_histogram(rec["rank_counts"], "rank histogram")),
+                             "alt": f"{partition} rank histogram"})
+            body.add("img", {"src": svg_data_uri(svg_histogram(rec["case_crps"], "crps")), "alt": f"{partition} crps histogram"})
     if parameters or history:
         body.add("h2").text("Training Summary")
     if parameters:

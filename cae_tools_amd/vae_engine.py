@@ -104,13 +104,18 @@ class VaeEngine(ShardedSteps, SteppedEngine, SpecPlan):
         cases = max(1, self.max_batch // k)
         return cases, min(k, self.max_batch // cases)
 
-    def ensemble(self, mu, logvar, ensemble_size, seed=0, first_case=0, vmin=0.0, vmax=1.0, want_std=True):
+    def ensemble(self, mu, logvar, ensemble_size, seed=0, first_case=0, vmin=0.0, vmax=1.0, want_std=True, target=None):
         """The K = ensemble_size >= 2 draws z_k = sample_latent(mu, logvar, k) of every case decoded and reduced per pixel by
         cae_ensemble_moments (include/cae_hip.h): (mean, std) float64 CUDA tensors (N, *out_shape), denormalised with
-        vmin + y * (vmax - vmin); std (ddof = 1) is None unless want_std.  The decoded draws live in one max_batch-row buffer."""
+        vmin + y * (vmax - vmin); std (ddof = 1) is None unless want_std.  The decoded draws live in one max_batch-row buffer.
+        target (the N cases' truth in physical units: an (N, C, H, W) array, CUDA tensor or engine.device_operand) also
+        verifies the draws of channel 0 against it where they lie (cae_ensemble_verify, K <= 64) and returns (mean, std,
+        case_sums, rank_counts): numpy arrays (N, 5) float64 and (K + 2,) int64 for utils/ensemble_scores.py."""
         k = int(ensemble_size)
         if k < 2:
             raise ValueError("an ensemble has at least 2 draws")
+        if target is not None:
+            return self._ensemble_verified(mu, logvar, k, seed, first_case, vmin, vmax, want_std, target)
         (mu, logvar) = (self._rows(mu, (self.latent_size,), "ensemble()"), self._rows(logvar, (self.latent_size,), "ensemble()"))
         n = mu.shape[0]
         check_noise_index(int(first_case) + n, self.latent_size)
@@ -141,3 +146,55 @@ class VaeEngine(ShardedSteps, SteppedEngine, SpecPlan):
                                                     self.stream.cuda_stream))
         self.sync()
         return mean, std
+
+    def _ensemble_verified(self, mu, logvar, k, seed, first_case, vmin, vmax, want_std, target):
+        """ensemble() with a target: the K draws of a group of cases are decoded into one buffer of K rows per case ([draw][case]
+        order, in pieces of at most max_batch rows), which one cae_ensemble_moments call (all K draws, no workspace) and one
+        cae_ensemble_verify call then reduce"""
+        from .engine import _measure_operand
+        if k > 64:
+            raise ValueError("an ensemble is verified with at most 64 draws")
+        (mu, logvar) = (self._rows(mu, (self.latent_size,), "ensemble()"), self._rows(logvar, (self.latent_size,), "ensemble()"))
+        n = mu.shape[0]
+        check_noise_index(int(first_case) + n, self.latent_size)
+        (a, kind, ashape, astride) = _measure_operand(target, self.device)
+        if len(ashape) != 4 or ashape[0] != n or tuple(ashape[2:]) != tuple(self.out_shape[-2:]):
+            raise CaeError(f"ensemble(): the target {tuple(ashape)} does not match {n} cases of {tuple(self.out_shape)}")
+        if a.device != self.device:
+            raise CaeError("ensemble(): the target lies on another device")
+        elem = 4 if kind in (0, 1) else 8
+        field = int(np.prod(self.out_shape))
+        plane = int(self.out_shape[-2] * self.out_shape[-1])
+        cases = max(1, self.max_batch // k)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        mean = torch.empty((n,) + self.out_shape, **f64)
+        std = torch.empty((n,) + self.out_shape, **f64) if want_std else None
+        sums = torch.zeros((n, 5), **f64)
+        ranks = torch.zeros(k + 2, dtype=torch.int64, device=self.device)
+        z = torch.empty((k, cases, self.latent_size), dtype=torch.float32, device=self.device)
+        y = torch.empty((k, cases, field), dtype=torch.float32, device=self.device)
+        # the workspace a call needs depends on its number of cases, and fewer cases can need more (they are cut into finer
+        # chunks): the largest need of the group sizes this run has, the full groups and the short last one
+        ws_bytes = max(int(self.lib.cae_ensemble_verify_workspace_bytes(g, plane, k)) for g in {min(cases, n), n % cases} if g)
+        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=self.device)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        for lo in range(0, n, cases):
+            g = min(cases, n - lo)
+            # rows [draw][case] of this group: z and y are used as (k, g, .) contiguous
+            self._sample_into(z.view(-1)[:k * g * self.latent_size], mu[lo:lo + g], logvar[lo:lo + g], first_case + lo, 0, seed,
+                              n_draws=k)
+            for r0 in range(0, k * g, self.max_batch):
+                rows = min(self.max_batch, k * g - r0)
+                check(self.lib.vae_decode(self.handle, z.data_ptr() + 4 * r0 * self.latent_size, rows,
+                                          y.data_ptr() + 4 * r0 * field))
+            check(self.lib.cae_ensemble_moments(y.data_ptr(), field, g * field, g, field, k, 0, k, float(vmin),
+                                                float(vmax) - float(vmin), mean[lo:lo + g].data_ptr(),
+                                                None if std is None else std[lo:lo + g].data_ptr(), None, 0,
+                                                self.stream.cuda_stream))
+            check(self.lib.cae_ensemble_verify(y.data_ptr(), field, g * field, a.data_ptr() + lo * astride * elem, kind, astride,
+                                               g, plane, k, float(vmin), float(vmax) - float(vmin), sums[lo:lo + g].data_ptr(),
+                                               ranks.data_ptr(), ws.data_ptr(), ws_bytes, self.stream.cuda_stream))
+        self.sync()
+        for t in (a, mu, logvar):
+            t.record_stream(self.stream)
+        return mean, std, sums.cpu().numpy(), ranks.cpu().numpy()

@@ -348,6 +348,41 @@ int cae_ensemble_moments(const float* draws_dev, int64_t case_stride, int64_t dr
                          int k_call, int k_done, int k_total, double vmin, double range, double* mean_dev, double* std_dev,
                          void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- ensemble verification (stateless): VarAEModel.verify_ensemble ------------------------- */
+
+/* The K = k_total draws of every pixel of channel 0 against the target, where cae_ensemble_moments runs and over the same
+ * buffer.  For pixel x of case c, with the fp32 draws y_0 .. y_{K-1} (normalised decoder output) and the target a (any
+ * CAE_ELEM_* kind, read as stored, in physical units), all in fp64:
+ *   m_k = vmin + (double)y_k * range            (the multiply and the add each rounded on its own: no fused multiply-add)
+ *   a pixel counts only if a and all K draws are finite; any other pixel is skipped, for that case only
+ *   A_x = (1/K) S_k |m_k - a|,   B_x = (1/K^2) S_{i<j} |m_i - m_j|
+ *   d_k = y_k - y_0, s1 = S d_k, s2 = S d_k^2 in ascending draw order (as cae_ensemble_moments),
+ *   mbar = vmin + (y_0 + s1 / K) * range,   s^2 = max(0, (s2 - s1^2 / K) / (K - 1)) * range * range
+ *   below = #{k : m_k < a},   tied = any k with m_k == a
+ * case_sums_dev[c][0..4] = {n, S A_x, S B_x, S (mbar - a)^2, S s^2} over the counted pixels of case c; it is written whole,
+ * a case without a counted pixel gets five zeros.  rank_counts_dev holds K + 2 int64 that the caller zeroes before the
+ * first call of a verification; every call adds counts[below] += 1 for each counted pixel (a tied pixel is counted at its
+ * lowest rank) and counts[K + 1] += 1 for each tied pixel.  The host forms crps = (S A - S B) / n, the fair crps, the
+ * spread-skill ratio and the rank frequencies (cae_tools_amd/utils/ensemble_scores.py).
+ * Draw k of case c is the `plane` floats from element c * case_stride + k * draw_stride of draws_dev ([case][draw] or
+ * [draw][case] order, any element alignment, 16-byte loads where draw_stride is a multiple of 4); the target of case c
+ * starts at element c * actual_case_stride.  One call brings all K draws, 2 <= k_total <= 64.
+ * No floating-point atomics: a pixel is handled by one lane; a lane's sums, a fixed shuffle tree and the chunk-ordered fold
+ * give the same bits from run to run (the cut of a case into chunks depends on n_case and plane alone).  The ranks are counted by wave ballots, stored per workgroup and added into
+ * rank_counts_dev by the fold launch with one load, add and store per bin.  S A and S B: a lane divides its sum over its
+ * pixels by K (K^2) once.  workspace_dev (8-byte aligned): cae_ensemble_verify_workspace_bytes bytes for exactly this
+ * n_case, plane and k_total (a call with fewer cases is cut into finer chunks and can need more, not less).
+ * A bad kind, negative sizes or strides, overlapping planes, range negative or not finite, vmin not finite, k_total outside
+ * [2, 64], operands that reach 2^60 elements from their pointer, too small a workspace or a pointer not aligned to its
+ * element size: CAE_ERR_ARG, nothing written.  n_case == 0
+ * or plane == 0 writes no sums and adds nothing. */
+int64_t cae_ensemble_verify_workspace_bytes(int64_t n_case, int64_t plane, int k_total);
+int cae_ensemble_verify(const float* draws_dev, int64_t case_stride, int64_t draw_stride,
+                        const void* actual_dev, int actual_kind, int64_t actual_case_stride,
+                        int64_t n_case, int64_t plane, int k_total, double vmin, double range,
+                        double* case_sums_dev, int64_t* rank_counts_dev,
+                        void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 /* ---- case pages (stateless): evaluate_cae's per-case images of channel 0 ------------------- */
 
 /* Both calls read the first `plane` elements (channel 0) of cases that start at element i * src_case_stride of src_dev,
