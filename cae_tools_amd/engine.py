@@ -674,6 +674,51 @@ def pixel_sums(pred, actual, shift=0.0, case_chunk=0, device=None):
         return out.cpu().numpy()
 
 
+_SPECTRA_CASES = 512         # cases per cae_case_spectra call: bounds the workspace; a case's sums do not depend on the cut
+
+
+def case_spectra(pred, actual, device=None):
+    """The four binned spectral sums of channel 0 per case (cae_case_spectra, include/cae_hip.h): (sums (N, n_bin, 4) float64
+    {S w|P|^2, S w|A|^2, S w Re(P conj A), S w|D|^2}, counted (N,) bool) for the Hann-windowed, mean-free prediction P,
+    target A and error D = (p - a) over the radial bins of utils/spectra.bin_table(H, W).  A case with a value that is
+    not finite is not counted and has zero sums.  Operands as pixel_sums takes them.
+    utils/spectra.curves_from_sums turns the sums into the spectra, their ratio, the coherence and the error share."""
+    from .utils import spectra
+    device = _case_device(device, pred, actual)
+    (p, pk, pshape, pstride) = _measure_operand(pred, device)
+    (a, ak, ashape, astride) = _measure_operand(actual, device)
+    if len(pshape) != 4 or len(ashape) != 4:
+        raise ValueError(f"case_spectra: (N, C, H, W) arrays expected, got {pshape} and {ashape}")
+    if pshape[0] != ashape[0] or pshape[2:] != ashape[2:]:
+        raise ValueError(f"case_spectra: prediction {pshape} and target {ashape} do not match")
+    (n, h, w) = (int(pshape[0]), int(pshape[2]), int(pshape[3]))
+    if not (1 <= h <= 2048 and 1 <= w <= 2048):
+        raise ValueError(f"case_spectra: planes of 1 to 2048 pixels a side expected, got {h} x {w}")
+    table = spectra.bin_table(h, w)
+    n_bin = spectra.bin_count(h, w)
+    if table.shape != (h, w // 2 + 1) or table.min() < -1 or table.max() >= n_bin:
+        raise ValueError("case_spectra: the bin table does not fit its bins")
+    if n == 0:
+        return np.zeros((0, n_bin, 4), dtype=np.float64), np.zeros(0, dtype=bool)
+    lib = _lib.load()
+    (pe, ae) = (4 if pk in (_lib.ELEM_F32, _lib.ELEM_F32_BE) else 8, 4 if ak in (_lib.ELEM_F32, _lib.ELEM_F32_BE) else 8)
+    sums = torch.empty((n, n_bin, 4), dtype=torch.float64, device=device)
+    counted = torch.empty(n, dtype=torch.int32, device=device)
+    wy = torch.from_numpy(spectra.window(h)).to(device)
+    wx = torch.from_numpy(spectra.window(w)).to(device)
+    bins = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)).to(device)
+    need = int(lib.cae_case_spectra_workspace_bytes(min(n, _SPECTRA_CASES), h, w, n_bin))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        for lo in range(0, n, _SPECTRA_CASES):
+            g = min(n, lo + _SPECTRA_CASES) - lo
+            check(lib.cae_case_spectra(p.data_ptr() + lo * pstride * pe, pk, pstride, a.data_ptr() + lo * astride * ae, ak,
+                                       astride, g, h, w, wy.data_ptr(), wx.data_ptr(), bins.data_ptr(), n_bin,
+                                       sums[lo:].data_ptr(), counted[lo:].data_ptr(), ws.data_ptr(), need, stream))
+        return sums.cpu().numpy(), counted.cpu().numpy() != 0
+
+
 def ensemble_verify(draws, actual, vmin, vmax, layout="case", device=None):
     """cae_ensemble_verify (include/cae_hip.h) on the K draws of every case at once: draws is a float32 numpy array or CUDA
     tensor (N, K, H, W) or (N, K, C, H, W) for layout "case", (K, N, H, W) or (K, N, C, H, W) for layout "draw" - the

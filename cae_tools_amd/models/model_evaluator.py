@@ -28,6 +28,11 @@ ensemble_size=K (cli/verify_ensemble.py; a VarAEModel only, not a reference feat
 against the target per partition (VarAEModel.verify_ensemble, cae_ensemble_verify on the GPU): ensemble_<partition>.json
 with the scores, rank counts, K and seed (strict JSON: a score that is not finite is null), a per-case crps variable beside mae / mse in the data set, and the report's
 "Ensemble verification" section.
+
+spectra=True (cli/spectra.py; not a reference feature) adds the reduction along scale: per partition the radially binned
+power spectra of prediction and target, their ratio, the spectral coherence and the error spectrum of channel 0 from one
+cae_case_spectra pass on the GPU (a direct fp64 DFT of every case; utils/spectra.py), written as
+spectra_<partition>.json and drawn on spectra/index.html, which the report then links.
 """
 import json
 import os
@@ -35,8 +40,9 @@ import os
 import numpy as np
 
 from ..data.arrays import as_numpy, open_mfdataset
-from ..engine import case_measures, case_range, device_operand, pixel_sums, render_cases
+from ..engine import case_measures, case_range, case_spectra, device_operand, pixel_sums, render_cases
 from ..utils import case_pages, ensemble_scores, skill_maps
+from ..utils import spectra as spectra_curves
 from ..utils.model_database import ModelDatabase
 from ..utils.report import evaluation_report
 from .base_model import _make_data_array
@@ -50,7 +56,7 @@ class ModelEvaluator:
 
     def __init__(self, training_paths, testing_paths, output_html_folder="", model_output_variable="", model_path="",
                  database_path="", input_variables=[], sample_count=None, x_coordinate="", y_coordinate="",
-                 time_coordinate="", skill_maps=False, ensemble_size=None, ensemble_seed=0):
+                 time_coordinate="", skill_maps=False, ensemble_size=None, ensemble_seed=0, spectra=False):
         self.training_paths = list(training_paths) if training_paths else []
         self.testing_paths = list(testing_paths) if testing_paths else []
         self.output_html_folder = output_html_folder
@@ -65,6 +71,7 @@ class ModelEvaluator:
         self.y_coordinate = y_coordinate
         self.time_coordinate = time_coordinate
         self.skill_maps = skill_maps
+        self.spectra = spectra
 
         (self.ensemble_size, self.ensemble_seed) = (ensemble_size, int(ensemble_seed))
         if ensemble_size is not None and (int(ensemble_size) != ensemble_size or not 2 <= int(ensemble_size) <= 64):
@@ -176,9 +183,10 @@ class ModelEvaluator:
                     case_links[partition] = partition + "/index.html"
 
         maps_link = self._skill_maps(train_ds, test_ds) if self.skill_maps else None
+        spectra_link = self._spectra(train_ds, test_ds) if self.spectra else None
         self._page_ops = {}
         page = evaluation_report(model_metrics, measures, training_parameters, training_losses, case_links, maps_link,
-                                 ensemble=ensemble or None)
+                                 ensemble=ensemble or None, spectra_link=spectra_link)
         os.makedirs(self.output_html_folder, exist_ok=True)
         with open(self.output_html_path, "w") as f:
             f.write(page)
@@ -361,3 +369,31 @@ class ModelEvaluator:
                                  for (k, name) in enumerate(skill_maps.MAPS)]) for (partition, n, op, flip) in parts]
         skill_maps.write_maps_page(os.path.join(self.output_html_folder, "maps"), pages)
         return "maps/index.html"
+
+    # ---- power spectra ---------------------------------------------------------------------------
+
+    def _spectra(self, train_ds, test_ds):
+        """spectra_<partition>.json and spectra/index.html; returns the page's href for the report.  Every rank would
+        compute all cases: the pass is not sharded."""
+        (target, pred) = (self.output_variable, self.model_output_variable)
+        parts = []
+        for (partition, ds) in (("test", test_ds), ("train", train_ds)):
+            if ds is None:
+                continue
+            ops = self._page_ops.get(partition, {})         # what the case pages have uploaded already
+            p = ops.get(pred, self._device_predictions.get(partition))
+            (p, a) = (device_operand(p if p is not None else as_numpy(ds[pred])),
+                      device_operand(ops.get(target, as_numpy(ds[target]))))
+            (sums, counted) = case_spectra(p, a)
+            (h, w) = (int(a.shape[2]), int(a.shape[3]))
+            curves = spectra_curves.curves_from_sums(sums, counted, h, w)
+            os.makedirs(self.output_html_folder, exist_ok=True)
+            spectra_curves.write_json(os.path.join(self.output_html_folder, f"spectra_{partition}.json"), curves, h, w)
+            er = curves["effective_resolution"]
+            print(f"spectra {partition}: effective_resolution {'none' if er is None else format(er, '.6g')} pixels, "
+                  f"{curves['n_counted']}/{curves['n_cases']} cases")
+            parts.append((partition, curves))
+        if not parts:
+            return None
+        spectra_curves.write_page(os.path.join(self.output_html_folder, "spectra"), parts)
+        return "spectra/index.html"

@@ -209,13 +209,15 @@ ENSEMBLE_ROWS = (("crps", "crps"), ("fair crps", "fair_crps"), ("mean per-case m
                  ("rmse of the ensemble mean", "rmse_mean"), ("spread", "spread"), ("spread-skill ratio", "spread_skill"))
 
 
-def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None, ensemble=None):
+def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None, ensemble=None,
+                      spectra_link=None):
     """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
     metrics: {"test": {...}, "train": {...}} (either may be absent); measures: [(partition, {"mae": values, "mse": values})]
     in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}; maps_link: href of
     the per-pixel skill maps page (utils/skill_maps.py), linked after the partitions when given; ensemble: [(partition,
     record)] of VarAEModel.verify_ensemble's scores with "mae" (the mean per-case mae of the deterministic prediction) added:
-    an "Ensemble verification" section with the ENSEMBLE_ROWS table, the rank histogram and the per-case CRPS histogram."""
+    an "Ensemble verification" section with the ENSEMBLE_ROWS table, the rank histogram and the per-case CRPS histogram;
+    spectra_link: href of the power spectra page (utils/spectra.py), linked after the skill maps when given."""
     doc = Document("Model Evaluation")
     doc.head.add("style").text(STYLE)
     body = doc.body
@@ -233,6 +235,8 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
             body.add("p").add("a", {"href": case_links[partition]}).text(f"Case summary for partition {partition}")
     if maps_link:
         body.add("p").add("a", {"href": maps_link}).text("Skill maps per pixel")
+    if spectra_link:
+        body.add("p").add("a", {"href": spectra_link}).text("Power spectra of prediction against target")
     if ensemble:
         body.add("h2").text("Ensemble verification")
         for (partition, rec) in ensemble:

@@ -444,6 +444,38 @@ int cae_pixel_sums_about(const void* pred_dev, int pred_kind, int64_t pred_case_
                          int64_t n_case, int64_t plane, const double* shifts_dev, int64_t case_chunk,
                          double* sums_dev, void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- power spectra (stateless): the reduction along scale -------------------------------------- */
+
+/* For case c of n_case, channel 0 (h x w), prediction p and target a converted to fp64 as stored and d = p - a per pixel,
+ * for each field x of {p, a, d}:
+ *   mu = (S x) / (h w),   x'[j][i] = (x[j][i] - mu) * wy[j] * wx[i],
+ *   X[ky][kx] = S_j S_i x'[j][i] e^{-2 pi i (ky j / h + kx i / w)}   for ky in [0, h), kx in [0, w / 2]
+ * (a direct DFT in fp64: twiddle indices ky j mod h and kx i mod w formed in integers, cos / sin(2 pi m / N) from sincospi),
+ * and with weight(kx) = 1 if kx == 0 or 2 kx == w, else 2 (the other half plane):
+ *   sums_dev[c][b][0..3] = {S weight |P|^2, S weight |A|^2, S weight Re(P conj A), S weight |D|^2}
+ * over the modes with bin_dev[ky][kx] == b (int32, [h][w / 2 + 1]); an entry that is negative or >= n_bin leaves its mode
+ * out.  D is transformed on its own, from d formed per pixel.  A case in which any pixel of p or a is not finite is not
+ * counted: counted_dev[c] = 0 and its sums are zeros; otherwise counted_dev[c] = 1.  sums_dev (n_case, n_bin, 4) doubles
+ * and counted_dev (n_case) int32 are written whole.  The host forms the spectra, their ratio, the coherence and the error
+ * share from the sums and makes wy, wx (h and w doubles) and the table (cae_tools_amd/utils/spectra.py).
+ * Operands as cae_case_measures takes them: CAE_ELEM_* kinds read as stored, case i at element i * case_stride, pointers
+ * aligned to their element size, any stride >= h w.  1 <= h, w <= 2048.
+ * No floating-point atomics.  One workgroup per (case, band of nb consecutive kx columns), nb from (h, w) alone: the row
+ * transform of the band into LDS, the column transform from it, and each bin of the band added by one lane in mode order;
+ * plain stores of the (case, band, bin) partials, which a fold launch adds in band order.  The case's means are made once
+ * by a launch of their own in a fixed order.  The same arguments give the same bits from run to run, and a case's sums do
+ * not depend on the other cases of the call.  workspace_dev (16-byte aligned) holds the twiddle tables (filled on the
+ * device), the means and the partials: cae_case_spectra_workspace_bytes bytes.
+ * Bad kinds, n_case < 0, h or w outside 1 .. 2048, n_bin < 1, a stride shorter than the plane, NULL or misaligned pointers or
+ * too small a workspace: CAE_ERR_ARG, nothing written.  n_case == 0 writes nothing and succeeds. */
+int64_t cae_case_spectra_workspace_bytes(int64_t n_case, int64_t h, int64_t w, int64_t n_bin);
+int cae_case_spectra(const void* pred_dev, int pred_kind, int64_t pred_case_stride,
+                     const void* actual_dev, int actual_kind, int64_t actual_case_stride,
+                     int64_t n_case, int64_t h, int64_t w,
+                     const double* wy_dev, const double* wx_dev, const int32_t* bin_dev, int64_t n_bin,
+                     double* sums_dev /* [n_case][n_bin][4] */, int32_t* counted_dev /* [n_case] */,
+                     void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
