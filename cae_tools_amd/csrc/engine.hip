@@ -18,6 +18,7 @@
 #include "kernels_generic.h"
 #include "kernels_stateless.h"   // here: the place its kernels have always had in this code object (file map)
 #include "kernels_spectra.h"     // after kernels_stateless.h: it uses its element loads
+#include "kernels_ssim.h"        // likewise
 #include "kernels_s2.h"
 #include "kernels_last.h"
 #include "kernels_rows.h"

@@ -1,5 +1,5 @@
 // stateless_host.h - host only: the entry points of cae_hip.h that use no engine (loader, evaluator, ensemble moments and verification, case
-// pages, per-pixel skill sums, power spectra) over kernels_stateless.h and kernels_spectra.h.  Included by engine.hip alone, at the place
+// pages, per-pixel skill sums, power spectra, structural similarity) over kernels_stateless.h, kernels_spectra.h and kernels_ssim.h.  Included by engine.hip alone, at the place
 // this code has always had in it.
 #pragma once
 
@@ -665,6 +665,107 @@ int cae_case_spectra(const void* pred, int pred_kind, int64_t pred_stride, const
     if (fb > 8192) fb = 8192;
     hipLaunchKernelGGL(k_spectra_fold, dim3((unsigned)fb), dim3(256), 0, s, (const double*)a.part, (long long)n_case, (int)n_band,
                        (int)n_bin, sums);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+// ---- structural similarity of prediction against target ---------------------------------------------
+
+// the side of the next scale: 2 x 2 pooling with padding size mod 2 on both sides
+static int64_t ssim_pooled(int64_t side) { return (side + 2 * (side & 1)) / 2; }
+
+// the scales' shapes and the cut of each into (band, strip) items, from (h, w) alone; returns the items of one case
+static int64_t ssim_plan(int64_t h, int64_t w, int n_scale, SsScale* sc, int64_t* plane_doubles) {
+    int64_t per_case = 0, planes = 0;
+    for (int s = 0; s < n_scale; s++) {
+        sc[s].h = (int)h, sc[s].w = (int)w;
+        sc[s].rb = ss_band_rows((int)h);
+        const bool any = h >= SS_WIN && w >= SS_WIN;
+        sc[s].n_band = any ? (int)((h - SS_HALO + sc[s].rb - 1) / sc[s].rb) : 0;
+        sc[s].n_strip = any ? (int)((w - SS_HALO + SS_COLS - 1) / SS_COLS) : 0;
+        per_case += (int64_t)sc[s].n_band * sc[s].n_strip;
+        if (s > 0) planes += 2 * h * w;
+        h = ssim_pooled(h), w = ssim_pooled(w);
+    }
+    if (plane_doubles) *plane_doubles = planes;
+    return per_case;
+}
+
+static bool ssim_sizes_ok(int64_t n_case, int64_t h, int64_t w, int n_scale) {
+    if (n_case < 0 || h < 1 || h > SS_MAX_SIDE || w < 1 || w > SS_MAX_SIDE || n_scale < 1 || n_scale > SS_SCALES) return false;
+    SsScale sc[SS_SCALES];
+    int64_t planes = 0;
+    const int64_t per_case = ssim_plan(h, w, n_scale, sc, &planes);
+    return (__int128)n_case * per_case <= 0x7fffffffLL && (__int128)n_case * planes < ((__int128)1 << 56);
+}
+
+int64_t cae_case_ssim_workspace_bytes(int64_t n_case, int64_t h, int64_t w, int n_scale) {
+    if (n_case < 1 || !ssim_sizes_ok(n_case, h, w, n_scale)) return 0;
+    SsScale sc[SS_SCALES];
+    int64_t planes = 0;
+    const int64_t per_case = ssim_plan(h, w, n_scale, sc, &planes);
+    return n_case * (planes + 3 * per_case) * (int64_t)sizeof(double);
+}
+
+int cae_case_ssim(const void* pred, int pred_kind, int64_t pred_stride, const void* actual, int actual_kind,
+                  int64_t actual_stride, int64_t n_case, int64_t h, int64_t w, int n_scale, double shift, double scale,
+                  const double* window, double* sums, void* workspace, int64_t workspace_bytes, void* hip_stream) {
+    auto elem_bytes = [](int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; };
+    auto known = [](int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; };
+    if (!known(pred_kind) || !known(actual_kind) || !ssim_sizes_ok(n_case, h, w, n_scale))
+        return fail(CAE_ERR_ARG, "cae_case_ssim: bad argument (CAE_ELEM_* kinds, n_case >= 0, 1 <= h, w <= %d, 1 <= n_scale <= %d)",
+                    SS_MAX_SIDE, SS_SCALES);
+    if (!(shift - shift == 0.0) || !(scale - scale == 0.0)) return fail(CAE_ERR_ARG, "cae_case_ssim: shift and scale must be finite");
+    if (n_case == 0) return CAE_OK;
+    const int64_t plane = h * w;
+    if (!pred || !actual || !window || !sums) return fail(CAE_ERR_ARG, "cae_case_ssim: null pointer");
+    if (pred_stride < plane || actual_stride < plane)
+        return fail(CAE_ERR_ARG, "cae_case_ssim: a case stride is shorter than the plane");
+    if ((__int128)(n_case - 1) * pred_stride + plane > ((__int128)1 << 60) || (__int128)(n_case - 1) * actual_stride + plane > ((__int128)1 << 60))
+        return fail(CAE_ERR_ARG, "cae_case_ssim: an operand reaches 2^60 elements from its pointer");
+    if (((uintptr_t)pred % elem_bytes(pred_kind)) || ((uintptr_t)actual % elem_bytes(actual_kind)) || ((uintptr_t)sums & 7) ||
+        ((uintptr_t)workspace & 7))
+        return fail(CAE_ERR_ARG, "cae_case_ssim: pointers must be aligned to their element size, the workspace to 8 bytes");
+    const int64_t need = cae_case_ssim_workspace_bytes(n_case, h, w, n_scale);
+    if (need > 0 && (!workspace || workspace_bytes < need))
+        return fail(CAE_ERR_ARG, "cae_case_ssim: needs a workspace of %lld bytes (cae_case_ssim_workspace_bytes)", (long long)need);
+    hipStream_t s = (hipStream_t)hip_stream;
+    SsArgs a;
+    memset(&a, 0, sizeof a);
+    int64_t planes = 0;
+    const int64_t per_case = ssim_plan(h, w, n_scale, a.s, &planes);
+    a.n_scale = n_scale, a.n_case = n_case, a.items = n_case * per_case;
+    a.shift = shift, a.scale = scale;
+    for (int t = 0; t < SS_WIN; t++) a.win.g[t] = window[t];
+    double* ws = (double*)workspace;
+    a.part = ws + n_case * planes;
+    a.s[0].x = (const unsigned char*)pred, a.s[0].y = (const unsigned char*)actual;
+    a.s[0].x_stride = pred_stride, a.s[0].y_stride = actual_stride, a.s[0].xk = pred_kind, a.s[0].yk = actual_kind;
+    int64_t first = 0;
+    for (int k = 0; k < n_scale; k++) {
+        SsScale& c = a.s[k];
+        c.first = first;
+        first += n_case * c.n_band * c.n_strip;
+        if (k + 1 == n_scale) break;
+        // the planes of scale k + 1: [case][x | y][h][w] doubles, pooled from scale k
+        SsScale& d = a.s[k + 1];
+        const int64_t per = (int64_t)d.h * d.w;
+        d.x = (const unsigned char*)ws, d.y = (const unsigned char*)(ws + per);
+        d.x_stride = d.y_stride = 2 * per, d.xk = d.yk = CAE_ELEM_F64;
+        int64_t pb = (n_case * per + 255) / 256;
+        if (pb > 65536) pb = 65536;
+        hipLaunchKernelGGL(k_ssim_pool, dim3((unsigned)pb), dim3(256), 0, s, c.x, c.xk, (long long)c.x_stride, c.y, c.yk,
+                           (long long)c.y_stride, (long long)n_case, c.h, c.w, k == 0 ? shift : 0.0, k == 0 ? scale : 1.0, ws);
+        HIP_TRY(hipGetLastError());
+        ws += n_case * 2 * per;
+    }
+    if (a.items > 0) {
+        hipLaunchKernelGGL(k_case_ssim, dim3((unsigned)((a.items + 3) / 4)), dim3(256), 0, s, a);
+        HIP_TRY(hipGetLastError());
+    }
+    int64_t fb = (n_case * n_scale * 3 + 255) / 256;
+    if (fb > 4096) fb = 4096;
+    hipLaunchKernelGGL(k_ssim_fold, dim3((unsigned)fb), dim3(256), 0, s, a, sums);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }

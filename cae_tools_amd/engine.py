@@ -5,6 +5,7 @@ running-stat arenas and the workspace, a side stream, and (in dp.py) torch.distr
 FLOP of the model runs in the HIP kernels behind include/cae_hip.h.
 """
 import ctypes as C
+import math
 from collections import OrderedDict
 
 import numpy as np
@@ -717,6 +718,50 @@ def case_spectra(pred, actual, device=None):
                                        astride, g, h, w, wy.data_ptr(), wx.data_ptr(), bins.data_ptr(), n_bin,
                                        sums[lo:].data_ptr(), counted[lo:].data_ptr(), ws.data_ptr(), need, stream))
         return sums.cpu().numpy(), counted.cpu().numpy() != 0
+
+
+_SSIM_CASES = 256            # cases per cae_case_ssim call: bounds the workspace (the pooled planes); a case's sums do not depend on the cut
+
+
+def case_ssim(pred, actual, vmin, vmax, n_scale=None, device=None):
+    """The SSIM sums of channel 0 per case and scale (cae_case_ssim, include/cae_hip.h): an (N, n_scale, 3) float64 numpy
+    array {n, S ssim, S cs} over the counted 11 x 11 windows of scale s, for x = (p - vmin) * (1 / (vmax - vmin)) and y
+    likewise (data_range 1, the VAE loss's definition).  A window over a value that is not finite is left out, for that case
+    and scale only.  n_scale None: 5 where min(H, W) > 160 (MS-SSIM is defined), else 1.  Operands as case_spectra takes them.
+    utils/ssim.scores_from_sums turns the sums into ssim, ms_ssim and psnr."""
+    from .utils import ssim
+    device = _case_device(device, pred, actual)
+    (p, pk, pshape, pstride) = _measure_operand(pred, device)
+    (a, ak, ashape, astride) = _measure_operand(actual, device)
+    if len(pshape) != 4 or len(ashape) != 4:
+        raise ValueError(f"case_ssim: (N, C, H, W) arrays expected, got {pshape} and {ashape}")
+    if pshape[0] != ashape[0] or pshape[2:] != ashape[2:]:
+        raise ValueError(f"case_ssim: prediction {pshape} and target {ashape} do not match")
+    (n, h, w) = (int(pshape[0]), int(pshape[2]), int(pshape[3]))
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        raise ValueError(f"case_ssim: planes of 1 to 16384 pixels a side expected, got {h} x {w}")
+    n_scale = ssim.default_scales(h, w) if n_scale is None else int(n_scale)
+    if not 1 <= n_scale <= ssim.MAX_SCALES:
+        raise ValueError(f"case_ssim: n_scale must be 1 to {ssim.MAX_SCALES}, got {n_scale}")
+    (shift, scale) = (float(vmin), 1.0 / (float(vmax) - float(vmin)) if float(vmax) != float(vmin) else math.inf)
+    if not (math.isfinite(shift) and math.isfinite(scale)):
+        raise ValueError(f"case_ssim: vmin and 1 / (vmax - vmin) must be finite, got vmin {vmin!r} and vmax {vmax!r}")
+    if n == 0:
+        return np.zeros((0, n_scale, 3), dtype=np.float64)
+    lib = _lib.load()
+    (pe, ae) = (4 if pk in (_lib.ELEM_F32, _lib.ELEM_F32_BE) else 8, 4 if ak in (_lib.ELEM_F32, _lib.ELEM_F32_BE) else 8)
+    sums = torch.empty((n, n_scale, 3), dtype=torch.float64, device=device)
+    win = (C.c_double * ssim.WIN_SIZE)(*ssim.window().tolist())
+    need = int(lib.cae_case_ssim_workspace_bytes(min(n, _SSIM_CASES), h, w, n_scale))
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        for lo in range(0, n, _SSIM_CASES):
+            g = min(n, lo + _SSIM_CASES) - lo
+            check(lib.cae_case_ssim(p.data_ptr() + lo * pstride * pe, pk, pstride, a.data_ptr() + lo * astride * ae, ak,
+                                    astride, g, h, w, n_scale, shift, scale, win, sums[lo:].data_ptr(), ws.data_ptr(), need,
+                                    stream))
+        return sums.cpu().numpy()
 
 
 def ensemble_verify(draws, actual, vmin, vmax, layout="case", device=None):

@@ -33,6 +33,12 @@ spectra=True (cli/spectra.py; not a reference feature) adds the reduction along 
 power spectra of prediction and target, their ratio, the spectral coherence and the error spectrum of channel 0 from one
 cae_case_spectra pass on the GPU (a direct fp64 DFT of every case; utils/spectra.py), written as
 spectra_<partition>.json and drawn on spectra/index.html, which the report then links.
+
+ssim=True (cli/ssim.py; not a reference feature) adds the structural scores: per partition and case the SSIM, the MS-SSIM
+(five scales, where min(h, w) > 160) and the PSNR of channel 0 against the model's output normalisation range, from one
+cae_case_ssim pass on the GPU (fp64, the VAE loss's definition with a rule for missing data; utils/ssim.py, DESIGN.md
+section 9) and the mse already measured: ssim_<partition>.json, per-case ssim / ms_ssim / psnr variables beside mae / mse
+in the data set, and the report's "Structural similarity" section.
 """
 import json
 import os
@@ -40,9 +46,10 @@ import os
 import numpy as np
 
 from ..data.arrays import as_numpy, open_mfdataset
-from ..engine import case_measures, case_range, case_spectra, device_operand, pixel_sums, render_cases
+from ..engine import case_measures, case_range, case_spectra, case_ssim, device_operand, pixel_sums, render_cases
 from ..utils import case_pages, ensemble_scores, skill_maps
 from ..utils import spectra as spectra_curves
+from ..utils import ssim as ssim_scores
 from ..utils.model_database import ModelDatabase
 from ..utils.report import evaluation_report
 from .base_model import _make_data_array
@@ -56,7 +63,7 @@ class ModelEvaluator:
 
     def __init__(self, training_paths, testing_paths, output_html_folder="", model_output_variable="", model_path="",
                  database_path="", input_variables=[], sample_count=None, x_coordinate="", y_coordinate="",
-                 time_coordinate="", skill_maps=False, ensemble_size=None, ensemble_seed=0, spectra=False):
+                 time_coordinate="", skill_maps=False, ensemble_size=None, ensemble_seed=0, spectra=False, ssim=False):
         self.training_paths = list(training_paths) if training_paths else []
         self.testing_paths = list(testing_paths) if testing_paths else []
         self.output_html_folder = output_html_folder
@@ -72,6 +79,7 @@ class ModelEvaluator:
         self.time_coordinate = time_coordinate
         self.skill_maps = skill_maps
         self.spectra = spectra
+        self.ssim = ssim
 
         (self.ensemble_size, self.ensemble_seed) = (ensemble_size, int(ensemble_seed))
         if ensemble_size is not None and (int(ensemble_size) != ensemble_size or not 2 <= int(ensemble_size) <= 64):
@@ -168,6 +176,7 @@ class ModelEvaluator:
 
         measures = []
         ensemble = []
+        ssim = []
         case_links = {}
         for (partition, ds) in (("test", test_ds), ("train", train_ds)):
             if ds is None:
@@ -181,12 +190,15 @@ class ModelEvaluator:
             if self.x_coordinate and self.y_coordinate and self.time_coordinate:
                 if self._case_summary(case_dimension, partition, ds, train_ds, test_ds):
                     case_links[partition] = partition + "/index.html"
+            if self.ssim:       # after the case pages: their uploads are used again
+                for (name, v) in self._ssim(partition, ds, values, ssim).items():
+                    ds[name] = _make_data_array(ds, v, (case_dimension,))
 
         maps_link = self._skill_maps(train_ds, test_ds) if self.skill_maps else None
         spectra_link = self._spectra(train_ds, test_ds) if self.spectra else None
         self._page_ops = {}
         page = evaluation_report(model_metrics, measures, training_parameters, training_losses, case_links, maps_link,
-                                 ensemble=ensemble or None, spectra_link=spectra_link)
+                                 ensemble=ensemble or None, spectra_link=spectra_link, ssim=ssim or None)
         os.makedirs(self.output_html_folder, exist_ok=True)
         with open(self.output_html_path, "w") as f:
             f.write(page)
@@ -397,3 +409,23 @@ class ModelEvaluator:
             return None
         spectra_curves.write_page(os.path.join(self.output_html_folder, "spectra"), parts)
         return "spectra/index.html"
+
+    # ---- structural similarity -------------------------------------------------------------------
+
+    def _ssim(self, partition, ds, values, records):
+        """ssim_<partition>.json in the output folder and the report's record appended to `records`; returns the per-case
+        {"ssim", "ms_ssim", "psnr"} arrays.  The range of SSIM and PSNR is the model's output normalisation range."""
+        (target, pred) = (self.output_variable, self.model_output_variable)
+        (vmin, vmax) = (float(self.model.normalisation_parameters[2]), float(self.model.normalisation_parameters[3]))
+        ops = self._page_ops.get(partition, {})         # what the case pages have uploaded already
+        p = ops.get(pred, self._device_predictions.get(partition))
+        (p, a) = (device_operand(p if p is not None else as_numpy(ds[pred])),
+                  device_operand(ops.get(target, as_numpy(ds[target]))))
+        (h, w) = (int(a.shape[2]), int(a.shape[3]))
+        scores = ssim_scores.scores_from_sums(case_ssim(p, a, vmin, vmax), h, w, mse=values["mse"], vmin=vmin, vmax=vmax)
+        record = ssim_scores.summary(scores, h, w, vmin, vmax)
+        os.makedirs(self.output_html_folder, exist_ok=True)
+        ssim_scores.write_json(os.path.join(self.output_html_folder, f"ssim_{partition}.json"), record)
+        print(ssim_scores.line(partition, record))
+        records.append((partition, record))
+        return {k: scores[k] for k in ("ssim", "ms_ssim", "psnr")}

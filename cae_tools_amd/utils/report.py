@@ -210,14 +210,16 @@ ENSEMBLE_ROWS = (("crps", "crps"), ("fair crps", "fair_crps"), ("mean per-case m
 
 
 def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None, ensemble=None,
-                      spectra_link=None):
+                      spectra_link=None, ssim=None):
     """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
     metrics: {"test": {...}, "train": {...}} (either may be absent); measures: [(partition, {"mae": values, "mse": values})]
     in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}; maps_link: href of
     the per-pixel skill maps page (utils/skill_maps.py), linked after the partitions when given; ensemble: [(partition,
     record)] of VarAEModel.verify_ensemble's scores with "mae" (the mean per-case mae of the deterministic prediction) added:
     an "Ensemble verification" section with the ENSEMBLE_ROWS table, the rank histogram and the per-case CRPS histogram;
-    spectra_link: href of the power spectra page (utils/spectra.py), linked after the skill maps when given."""
+    spectra_link: href of the power spectra page (utils/spectra.py), linked after the skill maps when given; ssim:
+    [(partition, record)] of utils/ssim.summary: a "Structural similarity" section with the table of the mean ssim, ms_ssim
+    and psnr and the histogram of the per-case ssim."""
     doc = Document("Model Evaluation")
     doc.head.add("style").text(STYLE)
     body = doc.body
@@ -245,6 +247,14 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
             body.add("img", {"src": svg_data_uri(svg_rank_histogram(rec["rank_counts"], "rank histogram")),
                              "alt": f"{partition} rank histogram"})
             body.add("img", {"src": svg_data_uri(svg_histogram(rec["case_crps"], "crps")), "alt": f"{partition} crps histogram"})
+    if ssim:
+        from . import ssim as ssim_scores
+        body.add("h2").text("Structural similarity")
+        for (partition, rec) in ssim:
+            body.add("h3").text(f"{partition}: {rec['n_counted']} of {rec['n_cases']} cases, {len(rec['scales'])} "
+                                f"scale{'s' if len(rec['scales']) != 1 else ''}")
+            body.table(ssim_scores.section_rows(rec))
+            body.add("img", {"src": svg_data_uri(svg_histogram(rec["case_ssim"], "ssim")), "alt": f"{partition} ssim histogram"})
     if parameters or history:
         body.add("h2").text("Training Summary")
     if parameters:

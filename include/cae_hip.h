@@ -476,6 +476,51 @@ int cae_case_spectra(const void* pred_dev, int pred_kind, int64_t pred_case_stri
                      double* sums_dev /* [n_case][n_bin][4] */, int32_t* counted_dev /* [n_case] */,
                      void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- structural similarity (stateless): per-case SSIM and MS-SSIM sums ---------------------------- */
+
+/* The definition is the VAE loss's (oracle/vae_oracle.py) in fp64, per case and scale, with a rule for
+ * values that are not finite.  For case c of n_case, channel 0 (h x w):
+ *   prediction p and target a are read as stored and converted to fp64, then normalised once per pixel,
+ *     x = (p - shift) * scale,  y = (a - shift) * scale   (the subtraction and the product each rounded on its own, no fused
+ *     multiply-add); the host passes shift = vmin and scale = 1 / (vmax - vmin) of the model's output normalisation, so that
+ *     SSIM's data_range is 1 as in the VAE loss.
+ *   window: 11 taps, sigma 1.5 - the fp32 values of vae_oracle.gaussian_window cast to double, passed as 11 HOST doubles.
+ *     The filter G is separable and valid: along the row (w) first, then along the column (h); taps in ascending order,
+ *     each a fused multiply-add onto a sum that starts at 0.  C1 = 0.01^2, C2 = 0.03^2.
+ *   scales s = 0 .. n_scale - 1, 1 <= n_scale <= 5: scale 0 is (x, y); scale s + 1 is the 2 x 2 average of scale s with
+ *     padding pad = size mod 2 on both sides of an axis, padded pixels zeros, divisor always 4, output side
+ *     (size + 2 pad) / 2, value ((x00 + x01) + (x10 + x11)) * 0.25 in that order.  IEEE arithmetic carries NaN and +-Inf into
+ *     the pooled pixel: that is the whole missing-data rule of the pooling.
+ *   at each scale, for every valid window position:
+ *     mu1 = G(x), mu2 = G(y), s11 = G(x x) - mu1^2, s22 = G(y y) - mu2^2, s12 = G(x y) - mu1 mu2   (the same operation
+ *     sequence for the three: with p bit-identical to a they are the same bits, and cs = ssim = 1 exactly)
+ *     cs = (2 s12 + C2) / (s11 + s22 + C2),   ssim = ((2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1)) * cs
+ *   a window counts only if all 121 values of both fields under it are finite at that scale; any other window is left out,
+ *     for that case and scale only.  A value that is not finite enters the filters as 0, so it cannot poison its
+ *     neighbours' windows.
+ *   sums_dev[c][s][0..2] = {n, S ssim, S cs} over the counted windows (doubles, n exact).  The array (n_case, n_scale, 3) is
+ *     written whole; a scale with a side below 11 or without a counted window gets three zeros, none of them negative.
+ *     A case's sums do not depend on the other cases of the call.
+ * The host forms ssim = S ssim_0 / n_0, ms_ssim = prod_{s<4} relu(S cs_s / n_s)^w_s * relu(S ssim_4 / n_4)^w_4 (defined for
+ * min(h, w) > 160 and five counted scales) and psnr from cae_case_measures' mse (cae_tools_amd/utils/ssim.py).
+ * Operands as cae_case_measures takes them: CAE_ELEM_* kinds read as stored, case i at element i * case_stride, pointers
+ * aligned to their element size, any stride >= h w.  1 <= h, w <= 16384.
+ * No floating-point atomics.  A launch per level writes the normalised, pooled fp64 planes of scales 1 .. n_scale - 1 to the
+ * workspace; one launch walks every scale: a wave owns 64 input columns (54 outputs) and a band of 8, 16 or 32 output rows
+ * (by the scale's height: below 200, below 400, above), and stores its {n, S ssim, S cs} plainly; a fold launch adds the
+ * partials of a (case, scale) in (band, strip) order.  The cut depends on (h, w, scale) alone: the same arguments give the
+ * same bits from run to run and however the cases are cut into calls.  workspace_dev (8-byte aligned) holds the planes and
+ * the partials: cae_case_ssim_workspace_bytes bytes (0: none needed, NULL ok).
+ * Bad kinds, negative sizes, h or w outside 1 .. 16384, a stride shorter than the plane, n_scale outside 1 .. 5, a shift or
+ * scale that is not finite, NULL or misaligned pointers or too small a workspace: CAE_ERR_ARG, nothing written.
+ * n_case == 0 writes nothing and succeeds. */
+int64_t cae_case_ssim_workspace_bytes(int64_t n_case, int64_t h, int64_t w, int n_scale);
+int cae_case_ssim(const void* pred_dev, int pred_kind, int64_t pred_case_stride,
+                  const void* actual_dev, int actual_kind, int64_t actual_case_stride,
+                  int64_t n_case, int64_t h, int64_t w, int n_scale, double shift, double scale,
+                  const double* window_host /* [11] */, double* sums_dev /* [n_case][n_scale][3] */,
+                  void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
