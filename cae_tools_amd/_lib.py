@@ -120,6 +120,9 @@ SIGNATURES = {
     "cae_case_ssim_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int]),
     "cae_case_ssim": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                 C.c_double, C.c_double, _P, _P, _P, C.c_int64, _P]),
+    "cae_case_baseline_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "cae_case_baseline": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64,
+                                    C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, C.c_int64, _P]),
     # ---- include/cae_unet.h ----
     "unet_engine_create": (C.c_int, [C.POINTER(LayerSpecC), C.c_int, C.POINTER(LayerSpecC), C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.POINTER(C.c_void_p)]),

@@ -19,6 +19,7 @@
 #include "kernels_stateless.h"   // here: the place its kernels have always had in this code object (file map)
 #include "kernels_spectra.h"     // after kernels_stateless.h: it uses its element loads
 #include "kernels_ssim.h"        // likewise
+#include "kernels_baseline.h"    // after kernels_ssim.h: it uses its raw loads and wave sum
 #include "kernels_s2.h"
 #include "kernels_last.h"
 #include "kernels_rows.h"

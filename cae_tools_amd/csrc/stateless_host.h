@@ -1,5 +1,6 @@
 // stateless_host.h - host only: the entry points of cae_hip.h that use no engine (loader, evaluator, ensemble moments and verification, case
-// pages, per-pixel skill sums, power spectra, structural similarity) over kernels_stateless.h, kernels_spectra.h and kernels_ssim.h.  Included by engine.hip alone, at the place
+// pages, per-pixel skill sums, power spectra, structural similarity, interpolation baseline) over kernels_stateless.h, kernels_spectra.h,
+// kernels_ssim.h and kernels_baseline.h.  Included by engine.hip alone, at the place
 // this code has always had in it.
 #pragma once
 
@@ -766,6 +767,84 @@ int cae_case_ssim(const void* pred, int pred_kind, int64_t pred_stride, const vo
     int64_t fb = (n_case * n_scale * 3 + 255) / 256;
     if (fb > 4096) fb = 4096;
     hipLaunchKernelGGL(k_ssim_fold, dim3((unsigned)fb), dim3(256), 0, s, a, sums);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+// ---- skill against interpolating the input ------------------------------------------------------------
+
+// the (band, strip) items of one case, from (h_out, w_out) alone
+static int64_t baseline_items(int64_t h_out, int64_t w_out) {
+    return ((h_out + BL_ROWS - 1) / BL_ROWS) * ((w_out + BL_COLS - 1) / BL_COLS);
+}
+
+static bool baseline_sizes_ok(int64_t n_case, int64_t h_out, int64_t w_out) {
+    return n_case >= 0 && h_out >= 1 && h_out <= BL_MAX_SIDE && w_out >= 1 && w_out <= BL_MAX_SIDE &&
+           (__int128)n_case * baseline_items(h_out, w_out) <= 0x7fffffffLL;
+}
+
+int64_t cae_case_baseline_workspace_bytes(int64_t n_case, int64_t h_out, int64_t w_out) {
+    if (n_case < 1 || !baseline_sizes_ok(n_case, h_out, w_out)) return 0;
+    return n_case * baseline_items(h_out, w_out) * BL_SUMS * (int64_t)sizeof(double);
+}
+
+int cae_case_baseline(const void* low, int low_kind, int64_t low_stride, int64_t h_in, int64_t w_in, const void* pred,
+                      int pred_kind, int64_t pred_stride, const void* actual, int actual_kind, int64_t actual_stride,
+                      int64_t n_case, int64_t h_out, int64_t w_out, int mode, double* sums, double* field, void* workspace,
+                      int64_t workspace_bytes, void* hip_stream) {
+    auto elem_bytes = [](int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; };
+    auto known = [](int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; };
+    if (!known(low_kind) || !known(actual_kind) || (pred && !known(pred_kind)) || mode < CAE_INTERP_NEAREST ||
+        mode > CAE_INTERP_BICUBIC || h_in < 1 || h_in > BL_MAX_SIDE || w_in < 1 || w_in > BL_MAX_SIDE ||
+        !baseline_sizes_ok(n_case, h_out, w_out))
+        return fail(CAE_ERR_ARG, "cae_case_baseline: bad argument (CAE_ELEM_* kinds, a CAE_INTERP_* mode, n_case >= 0, sides of 1 to 2^30)");
+    if (low_stride < 0 || actual_stride < 0 || (pred && pred_stride < 0)) return fail(CAE_ERR_ARG, "cae_case_baseline: negative stride");
+    if (n_case == 0) return CAE_OK;
+    const int64_t plane_in = h_in * w_in, plane = h_out * w_out;
+    if (!low || !actual || !sums) return fail(CAE_ERR_ARG, "cae_case_baseline: null pointer");
+    if (low_stride < plane_in || actual_stride < plane || (pred && pred_stride < plane))
+        return fail(CAE_ERR_ARG, "cae_case_baseline: a case stride is shorter than the plane");
+    const __int128 limit = (__int128)1 << 60;
+    if ((__int128)(n_case - 1) * low_stride + plane_in > limit || (__int128)(n_case - 1) * actual_stride + plane > limit ||
+        (pred && (__int128)(n_case - 1) * pred_stride + plane > limit) || (field && (__int128)n_case * plane > limit))
+        return fail(CAE_ERR_ARG, "cae_case_baseline: an operand reaches 2^60 elements from its pointer");
+    if (((uintptr_t)low % elem_bytes(low_kind)) || ((uintptr_t)actual % elem_bytes(actual_kind)) ||
+        (pred && ((uintptr_t)pred % elem_bytes(pred_kind))) || ((uintptr_t)sums & 7) || ((uintptr_t)field & 7) ||
+        ((uintptr_t)workspace & 7))
+        return fail(CAE_ERR_ARG, "cae_case_baseline: pointers must be aligned to their element size, the workspace to 8 bytes");
+    const int64_t need = cae_case_baseline_workspace_bytes(n_case, h_out, w_out);
+    if (!workspace || workspace_bytes < need)
+        return fail(CAE_ERR_ARG, "cae_case_baseline: needs a workspace of %lld bytes (cae_case_baseline_workspace_bytes)", (long long)need);
+    hipStream_t s = (hipStream_t)hip_stream;
+    BlArgs a;
+    memset(&a, 0, sizeof a);
+    a.low = (const unsigned char*)low, a.p = (const unsigned char*)pred, a.a = (const unsigned char*)actual;
+    a.low_stride = low_stride, a.p_stride = pred ? pred_stride : 0, a.a_stride = actual_stride;
+    a.lk = low_kind, a.pk = pred ? pred_kind : 0, a.ak = actual_kind;
+    a.h_in = (int)h_in, a.w_in = (int)w_in, a.h_out = (int)h_out, a.w_out = (int)w_out;
+    a.sy = (double)h_in / (double)h_out, a.sx = (double)w_in / (double)w_out;
+    a.n_band = (int)((h_out + BL_ROWS - 1) / BL_ROWS), a.n_strip = (int)((w_out + BL_COLS - 1) / BL_COLS);
+    a.items = n_case * baseline_items(h_out, w_out);
+    a.part = (double*)workspace, a.field = field;
+    if (!pred) a.pk = a.ak;                 // read as a second a, never used
+    const dim3 grid((unsigned)((a.items + 3) / 4));
+    const int ea = elem_bytes(a.ak), ep = elem_bytes(a.pk);
+#define BL_LAUNCH(MODE)                                                                                      \
+    if (ea == 4 && ep == 4) hipLaunchKernelGGL((k_case_baseline<MODE, 4, 4>), grid, dim3(256), 0, s, a);      \
+    else if (ea == 4) hipLaunchKernelGGL((k_case_baseline<MODE, 4, 8>), grid, dim3(256), 0, s, a);            \
+    else if (ep == 4) hipLaunchKernelGGL((k_case_baseline<MODE, 8, 4>), grid, dim3(256), 0, s, a);            \
+    else hipLaunchKernelGGL((k_case_baseline<MODE, 8, 8>), grid, dim3(256), 0, s, a);
+    switch (mode) {
+    case CAE_INTERP_NEAREST: BL_LAUNCH(0) break;
+    case CAE_INTERP_BILINEAR: BL_LAUNCH(1) break;
+    default: BL_LAUNCH(2) break;
+    }
+#undef BL_LAUNCH
+    HIP_TRY(hipGetLastError());
+    int64_t fb = (n_case * BL_SUMS + 255) / 256;
+    if (fb > 4096) fb = 4096;
+    hipLaunchKernelGGL(k_baseline_fold, dim3((unsigned)fb), dim3(256), 0, s, (const double*)workspace, (long long)n_case,
+                       (int)baseline_items(h_out, w_out), sums);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }

@@ -764,6 +764,76 @@ def case_ssim(pred, actual, vmin, vmax, n_scale=None, device=None):
         return sums.cpu().numpy()
 
 
+_BASELINE_FIELD_BYTES = 256 << 20       # of fp64 field per cae_case_baseline call when the field is asked for
+
+
+def _elem_bytes(kind):
+    return 4 if kind in (_lib.ELEM_F32, _lib.ELEM_F32_BE) else 8
+
+
+def case_baseline(low, pred, actual, mode="bicubic", field=False, device=None):
+    """Skill against interpolating the input (cae_case_baseline, include/cae_hip.h): channel 0 of low (N, C, h, w) is
+    interpolated to the grid of actual (N, C, H, W) - mode "nearest", "bilinear" or "bicubic", the formulas of
+    torch.nn.functional.interpolate with align_corners=False - inside the kernel that compares it: an (N, 6) float64 numpy
+    array {n, S|b - a|, S(b - a)^2, S|p - a|, S(p - a)^2, n_won} per case over the pixels where a, p and every tap of b
+    are finite.  pred None: entries 3..5 are zero.  field=True returns (sums, b) with b the (N, H, W) float64 interpolated
+    field, NaN where a tap is not finite.  Operands as case_ssim takes them.  utils/baseline.scores_from_sums turns the
+    sums into baseline_mse, skill and win_fraction."""
+    from .utils import baseline
+    if mode not in baseline.MODES:
+        raise ValueError(f"case_baseline: mode must be one of {', '.join(baseline.MODES)}, got {mode!r}")
+    device = _case_device(device, low, pred, actual)
+    (lo_t, lk, lshape, lstride) = _measure_operand(low, device)
+    (a, ak, ashape, astride) = _measure_operand(actual, device)
+    if len(lshape) != 4 or len(ashape) != 4 or lshape[0] != ashape[0]:
+        raise ValueError(f"case_baseline: (N, C, h, w) and (N, C, H, W) arrays expected, got {lshape} and {ashape}")
+    (p, pk, pstride) = (None, 0, 0)
+    if pred is not None:
+        (p, pk, pshape, pstride) = _measure_operand(pred, device)
+        if len(pshape) != 4 or pshape[0] != ashape[0] or pshape[2:] != ashape[2:]:
+            raise ValueError(f"case_baseline: prediction {pshape} and target {ashape} do not match")
+    (n, h_in, w_in, h, w) = (int(ashape[0]), int(lshape[2]), int(lshape[3]), int(ashape[2]), int(ashape[3]))
+    if min(h_in, w_in, h, w) < 1:
+        raise ValueError(f"case_baseline: planes of at least one pixel expected, got {h_in} x {w_in} and {h} x {w}")
+    if n == 0:
+        empty = np.zeros((0, 6), dtype=np.float64)
+        return (empty, np.zeros((0, h, w), dtype=np.float64)) if field else empty
+    lib = _lib.load()
+    (le, pe, ae) = (_elem_bytes(lk), _elem_bytes(pk), _elem_bytes(ak))
+    group = max(1, min(n, _BASELINE_FIELD_BYTES // (8 * h * w))) if field else n
+    sums = torch.empty((n, 6), dtype=torch.float64, device=device)
+    need = int(lib.cae_case_baseline_workspace_bytes(group, h, w))
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+    out = np.empty((n, h, w), dtype=np.float64) if field else None
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        for c0 in range(0, n, group):
+            g = min(n, c0 + group) - c0
+            b = torch.empty((g, h, w), dtype=torch.float64, device=device) if field else None
+            check(lib.cae_case_baseline(lo_t.data_ptr() + c0 * lstride * le, lk, lstride, h_in, w_in,
+                                        p.data_ptr() + c0 * pstride * pe if p is not None else None, pk, pstride,
+                                        a.data_ptr() + c0 * astride * ae, ak, astride, g, h, w, baseline.MODES[mode],
+                                        sums[c0:].data_ptr(), b.data_ptr() if field else None, ws.data_ptr(), need, stream))
+            if field:
+                out[c0:c0 + g] = b.cpu().numpy()
+        sums = sums.cpu().numpy()
+    return (sums, out) if field else sums
+
+
+def upsample(low, out_shape, mode="bicubic", device=None):
+    """Channel 0 of low (N, C, h, w) interpolated to out_shape = (H, W) as case_baseline does it: an (N, H, W) float64 numpy
+    array, NaN where a tap is not finite (the field output of cae_case_baseline against a target of zeros)."""
+    device = _case_device(device, low)
+    op = device_operand(low, device)
+    if len(op.shape) != 4:
+        raise ValueError(f"upsample: an (N, C, h, w) array expected, got {tuple(op.shape)}")
+    (h, w) = (int(out_shape[0]), int(out_shape[1]))
+    if min(h, w) < 1:
+        raise ValueError(f"upsample: an output of at least one pixel expected, got {h} x {w}")
+    zeros = torch.zeros((int(op.shape[0]), 1, h, w), dtype=torch.float32, device=device)
+    return case_baseline(op, None, zeros, mode=mode, field=True, device=device)[1]
+
+
 def ensemble_verify(draws, actual, vmin, vmax, layout="case", device=None):
     """cae_ensemble_verify (include/cae_hip.h) on the K draws of every case at once: draws is a float32 numpy array or CUDA
     tensor (N, K, H, W) or (N, K, C, H, W) for layout "case", (K, N, H, W) or (K, N, C, H, W) for layout "draw" - the

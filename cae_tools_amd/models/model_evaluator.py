@@ -39,6 +39,13 @@ ssim=True (cli/ssim.py; not a reference feature) adds the structural scores: per
 cae_case_ssim pass on the GPU (fp64, the VAE loss's definition with a rule for missing data; utils/ssim.py, DESIGN.md
 section 9) and the mse already measured: ssim_<partition>.json, per-case ssim / ms_ssim / psnr variables beside mae / mse
 in the data set, and the report's "Structural similarity" section.
+
+baseline=True (cli/baseline.py; not a reference feature) answers whether the model is better than interpolating its own
+input: channel 0 of baseline_variable (default: the model's first input variable) is interpolated to the target's grid
+(baseline_mode "nearest", "bilinear" or "bicubic", torch's align_corners=False formulas) inside the kernel that compares it,
+one cae_case_baseline pass on the GPU (fp64; utils/baseline.py): baseline_<partition>.json with the
+pooled and per-case skill 1 - model_mse / baseline_mse, per-case baseline_mse / skill variables beside mae / mse in the
+data set, and the report's "Skill against interpolation" section.
 """
 import json
 import os
@@ -46,7 +53,8 @@ import os
 import numpy as np
 
 from ..data.arrays import as_numpy, open_mfdataset
-from ..engine import case_measures, case_range, case_spectra, case_ssim, device_operand, pixel_sums, render_cases
+from ..engine import case_baseline, case_measures, case_range, case_spectra, case_ssim, device_operand, pixel_sums, render_cases
+from ..utils import baseline as baseline_scores
 from ..utils import case_pages, ensemble_scores, skill_maps
 from ..utils import spectra as spectra_curves
 from ..utils import ssim as ssim_scores
@@ -63,7 +71,8 @@ class ModelEvaluator:
 
     def __init__(self, training_paths, testing_paths, output_html_folder="", model_output_variable="", model_path="",
                  database_path="", input_variables=[], sample_count=None, x_coordinate="", y_coordinate="",
-                 time_coordinate="", skill_maps=False, ensemble_size=None, ensemble_seed=0, spectra=False, ssim=False):
+                 time_coordinate="", skill_maps=False, ensemble_size=None, ensemble_seed=0, spectra=False, ssim=False,
+                 baseline=False, baseline_variable=None, baseline_mode="bicubic"):
         self.training_paths = list(training_paths) if training_paths else []
         self.testing_paths = list(testing_paths) if testing_paths else []
         self.output_html_folder = output_html_folder
@@ -80,6 +89,9 @@ class ModelEvaluator:
         self.skill_maps = skill_maps
         self.spectra = spectra
         self.ssim = ssim
+        (self.baseline, self.baseline_variable, self.baseline_mode) = (baseline, baseline_variable, baseline_mode)
+        if baseline and baseline_mode not in baseline_scores.MODES:
+            raise ValueError(f"baseline_mode must be one of {', '.join(baseline_scores.MODES)}, got {baseline_mode!r}")
 
         (self.ensemble_size, self.ensemble_seed) = (ensemble_size, int(ensemble_seed))
         if ensemble_size is not None and (int(ensemble_size) != ensemble_size or not 2 <= int(ensemble_size) <= 64):
@@ -95,6 +107,8 @@ class ModelEvaluator:
         for input_variable in self.input_variables:
             if input_variable not in self.model_input_variables:
                 raise Exception(f"requested {input_variable} is not a model input")
+        if self.baseline and not self.baseline_variable:
+            self.baseline_variable = self.model_input_variables[0]
         self._device_predictions = {}
         self._page_ops = {}          # the case pages' device operands and value ranges
         self._page_range = None
@@ -177,6 +191,7 @@ class ModelEvaluator:
         measures = []
         ensemble = []
         ssim = []
+        baseline = []
         case_links = {}
         for (partition, ds) in (("test", test_ds), ("train", train_ds)):
             if ds is None:
@@ -193,12 +208,16 @@ class ModelEvaluator:
             if self.ssim:       # after the case pages: their uploads are used again
                 for (name, v) in self._ssim(partition, ds, values, ssim).items():
                     ds[name] = _make_data_array(ds, v, (case_dimension,))
+            if self.baseline:
+                for (name, v) in self._baseline(partition, ds, baseline).items():
+                    ds[name] = _make_data_array(ds, v, (case_dimension,))
 
         maps_link = self._skill_maps(train_ds, test_ds) if self.skill_maps else None
         spectra_link = self._spectra(train_ds, test_ds) if self.spectra else None
         self._page_ops = {}
         page = evaluation_report(model_metrics, measures, training_parameters, training_losses, case_links, maps_link,
-                                 ensemble=ensemble or None, spectra_link=spectra_link, ssim=ssim or None)
+                                 ensemble=ensemble or None, spectra_link=spectra_link, ssim=ssim or None,
+                                 **({"baseline": baseline} if baseline else {}))
         os.makedirs(self.output_html_folder, exist_ok=True)
         with open(self.output_html_path, "w") as f:
             f.write(page)
@@ -429,3 +448,25 @@ class ModelEvaluator:
         print(ssim_scores.line(partition, record))
         records.append((partition, record))
         return {k: scores[k] for k in ("ssim", "ms_ssim", "psnr")}
+
+    # ---- skill against interpolating the input ---------------------------------------------------
+
+    def _baseline(self, partition, ds, records):
+        """baseline_<partition>.json in the output folder and the report's record appended to `records`; returns the
+        per-case {"baseline_mse", "skill"} arrays"""
+        (target, pred, name) = (self.output_variable, self.model_output_variable, self.baseline_variable)
+        if name not in ds or len(ds[name].shape) != 4:
+            raise ValueError(f"baseline variable {name!r} is not a 4-dimensional variable of the {partition} data set")
+        ops = self._page_ops.get(partition, {})         # what the case pages have uploaded already
+        p = ops.get(pred, self._device_predictions.get(partition))
+        (low, p, a) = (device_operand(ops.get(name, as_numpy(ds[name]))),
+                       device_operand(p if p is not None else as_numpy(ds[pred])),
+                       device_operand(ops.get(target, as_numpy(ds[target]))))
+        sums = case_baseline(low, p, a, mode=self.baseline_mode)
+        record = baseline_scores.summary(sums, self.baseline_mode, name, low.shape[2:], a.shape[2:])
+        os.makedirs(self.output_html_folder, exist_ok=True)
+        baseline_scores.write_json(os.path.join(self.output_html_folder, f"baseline_{partition}.json"), record)
+        print(baseline_scores.line(partition, record))
+        records.append((partition, record))
+        return {"baseline_mse": np.asarray(record["case_baseline_mse"], dtype=np.float64),
+                "skill": np.asarray(record["case_skill"], dtype=np.float64)}

@@ -210,7 +210,7 @@ ENSEMBLE_ROWS = (("crps", "crps"), ("fair crps", "fair_crps"), ("mean per-case m
 
 
 def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None, ensemble=None,
-                      spectra_link=None, ssim=None):
+                      spectra_link=None, ssim=None, baseline=None):
     """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
     metrics: {"test": {...}, "train": {...}} (either may be absent); measures: [(partition, {"mae": values, "mse": values})]
     in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}; maps_link: href of
@@ -219,7 +219,9 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
     an "Ensemble verification" section with the ENSEMBLE_ROWS table, the rank histogram and the per-case CRPS histogram;
     spectra_link: href of the power spectra page (utils/spectra.py), linked after the skill maps when given; ssim:
     [(partition, record)] of utils/ssim.summary: a "Structural similarity" section with the table of the mean ssim, ms_ssim
-    and psnr and the histogram of the per-case ssim."""
+    and psnr and the histogram of the per-case ssim; baseline: [(partition, record)] of utils/baseline.summary: a "Skill
+    against interpolation" section with the table of the pooled and per-case skill against the interpolated input and the
+    histogram of the per-case skill."""
     doc = Document("Model Evaluation")
     doc.head.add("style").text(STYLE)
     body = doc.body
@@ -255,6 +257,15 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
                                 f"scale{'s' if len(rec['scales']) != 1 else ''}")
             body.table(ssim_scores.section_rows(rec))
             body.add("img", {"src": svg_data_uri(svg_histogram(rec["case_ssim"], "ssim")), "alt": f"{partition} ssim histogram"})
+    if baseline:
+        from . import baseline as baseline_scores
+        body.add("h2").text("Skill against interpolation")
+        for (partition, rec) in baseline:
+            body.add("h3").text(f"{partition}: {rec['mode']} interpolation of {rec['variable']}, {rec['in_shape'][0]} x "
+                                f"{rec['in_shape'][1]} to {rec['out_shape'][0]} x {rec['out_shape'][1]}, {rec['n_counted']} of "
+                                f"{rec['n_cases']} cases")
+            body.table(baseline_scores.section_rows(rec))
+            body.add("img", {"src": svg_data_uri(svg_histogram(rec["case_skill"], "skill")), "alt": f"{partition} skill histogram"})
     if parameters or history:
         body.add("h2").text("Training Summary")
     if parameters:

@@ -521,6 +521,61 @@ int cae_case_ssim(const void* pred_dev, int pred_kind, int64_t pred_case_stride,
                   const double* window_host /* [11] */, double* sums_dev /* [n_case][n_scale][3] */,
                   void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- skill against interpolating the input (stateless): per-case sums of baseline and prediction ---- */
+
+enum {
+    CAE_INTERP_NEAREST = 0,
+    CAE_INTERP_BILINEAR = 1,
+    CAE_INTERP_BICUBIC = 2
+};
+
+/* Is the model better than interpolating its own input?  For case c of n_case, channel 0, in physical units as stored:
+ *   low     h_in x w_in, the baseline input variable
+ *   pred    h_out x w_out, may be NULL
+ *   actual  h_out x w_out
+ * Both grids cover the same extent and are pixel-centred (what block-mean coarsening produces).  Any sizes >= 1, ratios need
+ * not be integers, the two axes may differ; downscaling uses the same formulas without antialiasing.
+ * Coordinates are fp64, every operation rounded on its own (no fused multiply-add), so that a host restatement gets the same
+ * bits for src, i and t.  Per axis with n_in input and n_out output samples, output index o:
+ *     s = (double)n_in / (double)n_out,   src = (o + 0.5) * s - 0.5
+ *   CAE_INTERP_NEAREST   i = min((long)floor((o + 0.5) * s), n_in - 1)
+ *   CAE_INTERP_BILINEAR  src = max(src, 0), i0 = min((long)floor(src), n_in - 1), i1 = min(i0 + 1, n_in - 1), t = src - i0;
+ *                        weights (1 - t, t)
+ *   CAE_INTERP_BICUBIC   i = floor(src), t = src - i; taps i - 1 .. i + 2 with indices clamped to [0, n_in - 1]; cubic
+ *                        convolution weights with A = -0.75: inner taps ((A + 2) x - (A + 3)) x^2 + 1 at x = t and x = 1 - t,
+ *                        outer taps ((A x - 5 A) x + 8 A) x - 4 A at x = t + 1 and x = 2 - t
+ * (the formulas of torch.nn.functional.interpolate with align_corners=False: nearest-exact, bilinear, bicubic).  The
+ * weights are evaluated in fp64 from t in the factored form of the same cubics, (1 - t)(1 + t - 1.25 t^2) and
+ * -0.75 t (1 - t)^2 and their mirror images, each within 8 * 2^-53 of the weight relative to it; at t = 0 they are (0, 1, 0, 0).
+ * The interpolation is separable, along the row first: every tapped low-resolution row j gives r_j(x) = S_k wx_k low[j][ix_k],
+ * and b = S_j wy_j r_j, taps in ascending order, every product and sum rounded on its own.  Equal sizes give b = low, the
+ * same bits, in every mode.
+ * A pixel counts only if a, p (when given) and every tap the mode reads for it - 1, 2 x 2 or 4 x 4 before clamping - are
+ * finite, whatever the tap's weight; any other pixel is left out, for that case only: a NaN in the low-resolution field
+ * removes its whole footprint.
+ *   sums_dev[c][0..5] = {n, S|b - a|, S(b - a)^2, S|p - a|, S(p - a)^2, n_won},  n_won = #{|p - a| < |b - a|} (strict)
+ * over the counted pixels, doubles, n and n_won exact.  Without pred entries 3..5 are zero; a case without a counted pixel
+ * gets six zeros, none of them negative.  field_dev, when not NULL, receives b itself, (n_case, h_out, w_out) doubles, NaN
+ * where the taps are not all finite.  A case's results do not depend on the other cases of the call.
+ * Operands as cae_case_measures takes them: CAE_ELEM_* kinds read as stored, case i at element i * case_stride, pointers
+ * aligned to their element size, any stride >= the plane.  Sides of 1 to 2^30, n_case * ceil(h_out / 64) * ceil(w_out / 64)
+ * below 2^31.
+ * No floating-point atomics.  One launch: a wave owns 64 output columns and a band of 64 output rows, keeps the horizontally
+ * interpolated low-resolution rows it needs in a register ring that moves on only when floor(src_y) does, and stores its six
+ * sums plainly; a fold launch adds the partials of a case in (band, strip) order.  The cut depends on (h_out, w_out) alone:
+ * the same arguments give the same bits from run to run and however the cases are cut into calls.  workspace_dev (8-byte
+ * aligned) holds the partials: cae_case_baseline_workspace_bytes bytes (0 only for arguments the call refuses).
+ * Bad kinds or mode, sizes below 1 or above 2^30, negative strides, a stride shorter than the plane, an operand reaching 2^60
+ * elements from its pointer, NULL (low, actual, sums, workspace) or misaligned pointers or too small a workspace:
+ * CAE_ERR_ARG, nothing written.  n_case == 0 writes nothing and succeeds. */
+int64_t cae_case_baseline_workspace_bytes(int64_t n_case, int64_t h_out, int64_t w_out);
+int cae_case_baseline(const void* low_dev, int low_kind, int64_t low_case_stride, int64_t h_in, int64_t w_in,
+                      const void* pred_dev /* NULL: none */, int pred_kind, int64_t pred_case_stride,
+                      const void* actual_dev, int actual_kind, int64_t actual_case_stride,
+                      int64_t n_case, int64_t h_out, int64_t w_out, int mode,
+                      double* sums_dev /* [n_case][6] */, double* field_dev /* NULL or [n_case][h_out][w_out] */,
+                      void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
