@@ -282,9 +282,17 @@ int lds_take(int64_t& top, int64_t floats) {
 }
 
 // Fills the descriptor shared by k_head_fwd and k_tail_bwd and lays out their LDS.  Returns false when the model or
-// the batch does not fit (the caller then runs the per-layer launches).
-bool head_plan(const cae_engine* e, const StepArgs& a, HeadArgs& h, size_t& lds_bytes) {
-    if (!e->use_s2 || a.syncing() || e->variational || (int)e->enc.size() > kHeadMaxEnc) return false;
+// the batch does not fit (the caller then runs the per-layer launches); *why then names the first condition that failed
+// (cae_debug_plan reports it).
+bool head_plan(const cae_engine* e, const StepArgs& a, HeadArgs& h, size_t& lds_bytes, const char** why = nullptr) {
+    auto no = [&](const char* reason) {
+        if (why) *why = reason;
+        return false;
+    };
+    if (!e->use_s2) return no("mode");
+    if (a.syncing()) return no("syncing");
+    if (e->variational) return no("variational");
+    if ((int)e->enc.size() > kHeadMaxEnc) return no("depth");
     memset(&h, 0, sizeof h);
     h.B = a.batch;
     h.n_enc = (int)e->enc.size();
@@ -302,7 +310,7 @@ bool head_plan(const cae_engine* e, const StepArgs& a, HeadArgs& h, size_t& lds_
     int maxc = 1;
     for (int l = 0; l < h.n_enc; l++) {
         const ConvLayer& L = e->enc[l];
-        if (L.cout > kHeadMaxC) return false;
+        if (L.cout > kHeadMaxC) return no("channels");
         HeadConv& c = h.enc[l];
         c.cin = L.cin; c.hin = L.hin; c.win = L.win; c.cout = L.cout; c.hout = L.hout; c.wout = L.wout;
         c.kh = L.kh; c.kw = L.kw; c.s = L.stride;
@@ -317,7 +325,8 @@ bool head_plan(const cae_engine* e, const StepArgs& a, HeadArgs& h, size_t& lds_
         }
         {   // two burst segments: [conv weight .. BatchNorm bias] of the parameter arena, [running mean .. var] of the buffers
             const int64_t pn = L.beta_off + L.cout - L.w_off, bnn = L.rv_off + L.cout - L.rm_off;
-            if (pn > kHeadThreads || bnn > kHeadThreads || pn <= 0 || bnn <= 0 || h.n_seg + 2 > kHeadMaxSeg) return false;
+            if (pn > kHeadThreads || bnn > kHeadThreads || pn <= 0 || bnn <= 0) return no("params");
+            if (h.n_seg + 2 > kHeadMaxSeg) return no("segments");
             c.o_w = take(pn);
             c.o_b = c.o_w + (int)(L.b_off - L.w_off);
             c.o_gamma = c.o_w + (int)(L.gamma_off - L.w_off);
@@ -353,7 +362,7 @@ bool head_plan(const cae_engine* e, const StepArgs& a, HeadArgs& h, size_t& lds_
         int start4 = 0;
         for (int i = 0; i < 4; i++) {
             const FcLayer& F = e->fc[i];
-            if (F.nin % 4) return false;   // whole k-steps and 16-byte rows
+            if (F.nin % 4) return no("nin4");   // whole k-steps and 16-byte rows
             const int rows = i == 3 ? 16 * h.tiles_per_wg : (F.nout + 15) / 16 * 16;
             HeadW& w = h.wmat[i];
             w.src = e->params + F.w_off;
@@ -367,7 +376,7 @@ bool head_plan(const cae_engine* e, const StepArgs& a, HeadArgs& h, size_t& lds_
         }
         wf += 64;   // k-batches read past the last row
         h.w_total4 = start4;
-        if (h.w_total4 > kHeadW4 * kHeadThreads) return false;
+        if (h.w_total4 > kHeadW4 * kHeadThreads) return no("weights");
         for (int j = 0; j < kHeadW4; j++) {
             const int lo = j * kHeadThreads, hi = std::min((j + 1) * kHeadThreads, h.w_total4) - 1;   // float4s of piece j
             h.piece_m[j] = -1;
@@ -390,44 +399,52 @@ bool head_plan(const cae_engine* e, const StepArgs& a, HeadArgs& h, size_t& lds_
     }
     for (int i = 0; i < 4; i++) {
         const int cnt = i == 3 ? 16 * h.tiles_per_wg : e->fc[i].nout;
-        if (cnt > kHeadThreads || h.n_seg + 1 > kHeadMaxSeg) return false;
+        if (cnt > kHeadThreads) return no("biases");
+        if (h.n_seg + 1 > kHeadMaxSeg) return no("segments");
         h.o_bias[i] = take(cnt);
         // Linear 3: a strip of 16 * tiles_per_wg biases per workgroup column; the last strip may read past the vector
         // (clamped reads inside the parameter arena, masked by the epilogue's n < N)
         h.seg[h.n_seg++] = HeadSeg{e->params + e->fc[i].b_off, i == 3 ? std::min(cnt, e->fc[3].nout) : cnt, h.o_bias[i], i == 3 ? 1 : 0};
     }
     for (int i = 0; i < 4; i++) {
-        if (e->fc[i].nin % 4) return false;   // stage_prefetch walks whole k-steps
+        if (e->fc[i].nin % 4) return no("nin4");   // stage_prefetch walks whole k-steps
         const int tiles = i == 3 ? h.tiles_per_wg : (e->fc[i].nout + 15) / 16;
         h.fc_split[i] = stage_split(tiles, e->fc[i].nin);
     }
     lds_bytes = (size_t)align_up(top, 4) * sizeof(float);
-    return lds_bytes <= 152 * 1024;
+    return lds_bytes <= 152 * 1024 || no("lds");
 }
 
 
-// k_tail_bwd (kernels_head.h): Linear 2..0 backward in one launch.  False: run the per-layer pair launches.
-bool tail_plan(const cae_engine* e, const StepArgs& a, TailArgs& t, size_t& lds_bytes) {
-    if (!e->use_s2 || a.syncing() || e->variational) return false;
+// k_tail_bwd (kernels_head.h): Linear 2..0 backward in one launch.  False: run the per-layer pair launches; *why then names
+// the first condition that failed.
+bool tail_plan(const cae_engine* e, const StepArgs& a, TailArgs& t, size_t& lds_bytes, const char** why = nullptr) {
+    auto no = [&](const char* reason) {
+        if (why) *why = reason;
+        return false;
+    };
+    if (!e->use_s2) return no("mode");
+    if (a.syncing()) return no("syncing");
+    if (e->variational) return no("variational");
     memset(&t, 0, sizeof t);
     const ConvLayer& P = e->enc.back();
     double* acc = e->gradacc();
     t.B = a.batch;
     for (int i = 0; i < 3; i++) {
         const FcLayer& F = e->fc[i];
-        if (F.nin % 4 || F.nout % 4) return false;          // 16-byte rows, whole k-steps
-        if (16 * F.nout / 4 > 2 * kHeadThreads) return false;   // a 16-row panel in two loads per thread
+        if (F.nin % 4 || F.nout % 4) return no("fc4");              // 16-byte rows, whole k-steps
+        if (16 * F.nout / 4 > 2 * kHeadThreads) return no("panel");   // a 16-row panel in two loads per thread
         HeadFc& f = t.fc[i];
         f.nin = F.nin; f.nout = F.nout; f.relu = F.relu ? 1 : 0;
         f.w = e->params + F.w_off; f.bias = e->params + F.b_off;
         f.act = e->fptr(F.act_off); f.grad = e->fptr(F.grad_off);
         f.w_acc = acc + F.w_off; f.b_acc = acc + F.b_off;
         t.w4[i] = F.nin * F.nout / 4;
-        if (t.w4[i] > 2 * kHeadThreads) return false;
+        if (t.w4[i] > 2 * kHeadThreads) return no("weights");
         const int r16 = (F.nin + 15) / 16 * 16;
         t.ldw[i] = r16 % 32 == 0 ? r16 + 16 : r16;   // = 16 mod 32: the four k rows of an operand read land on distinct banks
     }
-    if (P.cout > kHeadMaxC || e->fc[0].nin != P.cout * P.hout * P.wout) return false;
+    if (P.cout > kHeadMaxC || e->fc[0].nin != P.cout * P.hout * P.wout) return no("channels");
     t.y_last = e->fptr(P.act_off);
     t.g_last = e->fptr(P.grad_off);
     t.gamma = e->params + P.gamma_off;
@@ -458,7 +475,7 @@ bool tail_plan(const cae_engine* e, const StepArgs& a, TailArgs& t, size_t& lds_
     t.o_w = take(wmax + 64);
     t.o_part = take(kHeadWaves * 256);
     lds_bytes = (size_t)align_up(top, 4) * sizeof(float);
-    if (lds_bytes > 152 * 1024) return false;
+    if (lds_bytes > 152 * 1024) return no("lds");
     // chain (16 rows): g1 (N = fc2.nin, K = fc2.nout), g0 (N = fc1.nin, K = fc1.nout), gx (N = fc0.nin, K = fc0.nout)
     for (int i = 0; i < 3; i++) t.sp_d[i] = stage_split((e->fc[2 - i].nin + 15) / 16, e->fc[2 - i].nout);
     // weight-gradient shares: M = nout, N = nin + 1, K = 16 rows
@@ -523,11 +540,25 @@ DecBwdK choose_dec_bwd(const cae_engine* e, const ConvLayer& L, int l, int B, bo
 }
 
 // The first encoder layer's weight gradient inside the optimiser launch (kernels_generic.h AdamConv0): a single-device training step
-// whose k_head_fwd left the batch's inputs behind, a layer small enough for k_adam's extra blocks, its BatchNorm table first in the swept range
-bool enc_conv0_in_adam_ok(const cae_engine* e, const StepArgs& a, const ConvLayer& L) {
-    return a.adam_follows && e->x_published && e->use_s2 && !a.syncing() && a.world == 1 && L.cout <= 64 &&
+// whose k_head_fwd left the batch's inputs behind, a layer small enough for k_adam's extra blocks, its BatchNorm table first in the swept range.
+// enc_conv0_fits_adam: what the engine and the layer decide (cae_debug_plan reports it for a step with a fused head);
+// enc_conv0_in_adam_ok adds the two facts of the step at hand: the optimiser follows, k_head_fwd published the inputs
+bool enc_conv0_fits_adam(const cae_engine* e, const StepArgs& a, const ConvLayer& L) {
+    return e->use_s2 && !a.syncing() && a.world == 1 && L.cout <= 64 &&
            (int64_t)L.cin * L.cout * L.kh * L.kw <= 4096 && (int64_t)a.batch * L.hout * L.wout < kDivSmallMaxN &&
            L.hout * L.wout < kDivSmallMaxD && e->bn_stat_off[L.bn_index] == e->off_zero_begin;
+}
+
+bool enc_conv0_in_adam_ok(const cae_engine* e, const StepArgs& a, const ConvLayer& L) {
+    return a.adam_follows && e->x_published && enc_conv0_fits_adam(e, a, L);
+}
+
+// how head_stage_inputs (kernels_head.h) brings the batch to LDS without a permutation: one contiguous block of 16-byte loads,
+// 16-byte loads through the sample table, or scalar loads (inputs per sample no multiple of 4)
+const char* head_staging(const HeadArgs& h) {
+    const int per = h.enc[0].cin * h.enc[0].hin * h.enc[0].win;
+    if (per & 3) return "scalar";
+    return h.B * (per >> 2) <= 4 * kHeadThreads ? "direct" : "gather4";
 }
 
 }  // namespace
@@ -542,10 +573,24 @@ int cae_debug_plan(const cae_engine* e, int batch, int train, char* out, int64_t
     const StepArgs a{0, nullptr, batch, batch, batch, tr, true, nullptr, nullptr, false};
     std::string s;
     char line[512];
+    bool head_fused = false;
     {
         HeadArgs h;
         size_t lds = 0;
-        snprintf(line, sizeof line, "head fwd=%s\n", head_plan(e, a, h, lds) ? "fused" : "layers");
+        const char* why = "";
+        head_fused = head_plan(e, a, h, lds, &why);
+        if (head_fused) {
+            int straddle = 0;
+            for (int j = 0; j < kHeadW4 && j * kHeadThreads < h.w_total4; j++) straddle += h.piece_m[j] == -1;
+            const int T = (e->fc[3].nout + 15) / 16;
+            snprintf(line, sizeof line,
+                     "head fwd=fused enc=%d grid=%dx%d stage=%s w4=%d late=%d straddle=%d fc0=%d:%d fc1=%d:%d fc2=%d:%d fc3=%d:%d lds=%zu\n",
+                     h.n_enc, (batch + 15) / 16, (T + h.tiles_per_wg - 1) / h.tiles_per_wg, head_staging(h), h.w_total4,
+                     (int)(h.w_total4 > kHeadEarly * kHeadThreads), straddle, h.fc_split[0].lg, h.fc_split[0].per, h.fc_split[1].lg,
+                     h.fc_split[1].per, h.fc_split[2].lg, h.fc_split[2].per, h.fc_split[3].lg, h.fc_split[3].per, lds);
+        } else {
+            snprintf(line, sizeof line, "head fwd=layers why=%s\n", why);
+        }
         s += line;
     }
     static const char* const kEpiName[] = {"raw_stats", "sigmse", "sigout", "raw"};   // S2Epi
@@ -614,7 +659,25 @@ int cae_debug_plan(const cae_engine* e, int batch, int train, char* out, int64_t
     {
         TailArgs t;
         size_t lds = 0;
-        snprintf(line, sizeof line, "tail bwd=%s\n", !tr ? "-" : (tail_plan(e, a, t, lds) ? "fused" : "layers"));
+        const char* why = "";
+        if (!tr) {
+            snprintf(line, sizeof line, "tail bwd=-\n");
+        } else if (tail_plan(e, a, t, lds, &why)) {
+            const int rows = (batch + 15) / 16;
+            snprintf(line, sizeof line, "tail bwd=fused rows=%d sums=%s g1=%d:%d g0=%d:%d gx=%d:%d w2=%d:%d w1=%d:%d w0=%d:%d lds=%zu\n", rows,
+                     rows <= kStatShards ? "stored" : "added", t.sp_d[0].lg, t.sp_d[0].per, t.sp_d[1].lg, t.sp_d[1].per, t.sp_d[2].lg,
+                     t.sp_d[2].per, t.sp_w[0].lg, t.sp_w[0].per, t.sp_w[1].lg, t.sp_w[1].per, t.sp_w[2].lg, t.sp_w[2].per, lds);
+        } else {
+            snprintf(line, sizeof line, "tail bwd=layers why=%s\n", why);
+        }
+        s += line;
+    }
+    if (tr) {
+        // the encoder's backward (launch_backward): layer 0's weight gradient rides in the optimiser launch of a cae_train_step
+        // whose head was fused (enc_conv0_in_adam_ok), the inner layers take k_conv_bwd_pair
+        const bool in_adam = head_fused && enc_conv0_fits_adam(e, a, e->enc[0]);
+        snprintf(line, sizeof line, "enc conv0=%s inner=%s\n", in_adam ? "adam" : "own",
+                 e->enc.size() < 2 ? "-" : (e->use_s2 && !a.syncing() ? "pair" : "layers"));
         s += line;
     }
     if ((int64_t)s.size() + 1 > out_bytes)

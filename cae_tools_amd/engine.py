@@ -35,7 +35,13 @@ class EnginePlan(SpecPlan):
         {"head": {"fwd": "fused"}, "dec0": {"fwd": "ct_fwd_lds<3,3>", "bwd": "ig_bwd_pair"}, ...,
         "dec4": {"fwd": "last_fused<2,1,4,4>", "hb": "4", "vec4": "1", "bn": "1", "bwd": "(fused)"}, "tail": {"bwd": "fused"}}.
         A layer whose backward is "ct_bwd_lds" also has ctb_kernel ("lds" | "band"), ctb_imgs, ctb_groups, ctb_parts, ctb_bands,
-        ctb_hb and ctb_sharded; one on "ig_bwd_pair" has ig_ksplit, ig_tpw, ig_chunks, ig_per, ig_dgroup and ig_wn8 (all strings)"""
+        ctb_hb and ctb_sharded; one on "ig_bwd_pair" has ig_ksplit, ig_tpw, ig_chunks, ig_per, ig_dgroup and ig_wn8 (all strings).
+        A fused head also has enc (encoder layers), grid ("<row groups>x<Linear-3 strips>"), stage ("direct" | "gather4" | "scalar":
+        the input staging without a permutation), w4, late, straddle and fc0..fc3 ("<lg>:<per>" of the four Linear stages) and
+        lds; a fused tail rows, sums ("stored" | "added"), g1 / g0 / gx and w2 / w1 / w0 ("<lg>:<per>" of the chain and
+        weight-gradient stages) and lds; a head or tail on "layers" has why, the first condition its planner refused.  A training
+        step's plan ends with "enc": {"conv0": "adam" | "own", "inner": "pair" | "layers" | "-"} - whether train_step computes
+        the first encoder layer's weight gradient in the optimiser launch, and the inner encoder layers' backward"""
         buf = C.create_string_buffer(1 << 16)
         check(self.lib.cae_debug_plan(self.handle, int(batch), 1 if train else 0, buf, len(buf)))
         plan = {}

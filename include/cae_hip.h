@@ -237,13 +237,25 @@ int64_t cae_debug_read(cae_engine* e, const char* what, int index, void* host_ou
 
 /* Which kernels a step at `batch` runs (the choosers the launch code switches on), without a GPU: a NUL-terminated report
  * in out_host, one line per decoder layer ("dec3 fwd=s2_fwd_cs<8,4,3,4,32> epi=raw_stats bwd=s2_bwd<8,2,4,3,4>") between
- * "head fwd=fused|layers" and "tail bwd=fused|layers|-".  train = 0: the eval forward (bwd=-).  Follows cae_set_kernel_mode;
+ * "head fwd=fused|layers ..." and "tail bwd=fused|layers|- ...".  train = 0: the eval forward (bwd=-).  Follows cae_set_kernel_mode;
  * reports the single-device step without SyncBN.  The two backward families whose launch depends on the batch add the
  * fields their launch code switches on, as key=value pairs after bwd=:
  *   "bwd=ct_bwd_lds ctb_kernel=lds|band ctb_imgs=<images per workgroup> ctb_groups=<grid x> ctb_parts=<grid z> ctb_bands=<0 or
  *    the bands of an image> ctb_hb=<input rows per band> ctb_sharded=<1: the weight-gradient accumulator is the sharded table>"
  *   "bwd=ig_bwd_pair ig_ksplit=<K split of the input-gradient half> ig_tpw=<its tiles per wave> ig_chunks=<weight-gradient
  *    chunks> ig_per=<k-steps per chunk> ig_dgroup=<input-gradient blocks per chunk> ig_wn8=<chunk rounds of 8>"
+ * The head and tail lines name the branches of the fused kernels (kernels_head.h), or why a planner refused:
+ *   "head fwd=fused enc=<encoder layers> grid=<row groups>x<Linear-3 strips> stage=direct|gather4|scalar (the input staging
+ *    without a permutation) w4=<float4s of Linear weights> late=<1: pieces requested after the encoder> straddle=<used pieces
+ *    that lie in two matrices> fc0=<lg>:<per> fc1=.. fc2=.. fc3=.. (2^lg waves share a tile's k-steps, `per` each) lds=<bytes>"
+ *   "head fwd=layers why=mode|syncing|variational|depth|channels|params|segments|nin4|weights|biases|lds" (the first condition
+ *    of head_plan that failed, in that order)
+ *   "tail bwd=fused rows=<row groups> sums=stored|added (the BatchNorm sums of more than 8 row groups are added) g1= g0= gx=
+ *    (chain stages) w2= w1= w0= (weight-gradient stages, <lg>:<per>) lds=<bytes>"
+ *   "tail bwd=layers why=mode|syncing|variational|fc4|panel|weights|channels|lds"
+ * A training step ends with "enc conv0=adam|own inner=pair|layers|-": whether a cae_train_step computes the first encoder
+ * layer's weight gradient inside the optimiser launch (only behind a fused head), and whether the inner encoder layers take
+ * k_conv_bwd_pair (-: there are none).
  * Fails for a batch outside 1 .. max_batch or too short a buffer. */
 int cae_debug_plan(const cae_engine* e, int batch, int train, char* out_host, int64_t out_bytes);
 

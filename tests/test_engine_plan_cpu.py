@@ -119,18 +119,22 @@ def _ctb(kernel, imgs, groups, parts, bands, hb, sharded):
             "ctb_bands": str(bands), "ctb_hb": str(hb), "ctb_sharded": str(sharded)}
 
 
+CFG2_HEAD = {"fwd": "fused", "enc": "2", "grid": "4x36", "stage": "direct", "w4": "3712", "late": "0", "straddle": "3",
+             "fc0": "0:9", "fc1": "3:4", "fc2": "0:8", "fc3": "4:2", "lds": "136112"}
 CFG2_TRAIN = {
-    "head": {"fwd": "fused"},
+    "head": CFG2_HEAD,
     "dec0": {"fwd": "ct_fwd_lds<3,3>", **_ig(4, 1, 5, 32, 8, 1)},
     "dec1": {"fwd": "ct_fwd_lds<3,3>", **_ig(4, 1, 25, 32, 8, 4)},
     "dec2": {"fwd": "ct_fwd_lds<3,3>", **_ctb("band", 1, 64, 4, 4, 4, 1)},
     "dec3": {"fwd": "s2_fwd_rows<8,4,1,2>", "bwd": "s2_bwd_rows<8,2,4,3,3,4,2,1>"},
     "dec4": {"fwd": "s2_fwd_rows<4,2,2,1>", "bwd": "s2_bwd_rows<4,4,2,3,3,2,1,3>"},
     "dec5": {"fwd": "last_fused<2,1,4,4>", "hb": "4", "vec4": "1", "bn": "1", "bwd": "(fused)"},
-    "tail": {"bwd": "fused"},
+    "tail": {"bwd": "fused", "rows": "4", "sums": "stored", "g1": "3:4", "g0": "0:8", "gx": "2:8", "w2": "0:4", "w1": "0:4", "w0": "0:4",
+             "lds": "65984"},
+    "enc": {"conv0": "adam", "inner": "pair"},
 }
 CFG2_EVAL = {
-    "head": {"fwd": "fused"},
+    "head": CFG2_HEAD,
     "dec0": {"fwd": "ct_fwd_lds<3,3>", "bwd": "-"},
     "dec1": {"fwd": "ct_fwd_lds<3,3>", "bwd": "-"},
     "dec2": {"fwd": "ct_fwd_lds<3,3>", "bwd": "-"},

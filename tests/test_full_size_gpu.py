@@ -116,6 +116,12 @@ def test_other_geometries_of_the_row_and_fused_kernels(in_size, out_size, batch)
     eng.load_state(enc.state_dict(), dec.state_dict())
     eng.set_hyper(lr=1e-3, weight_decay=1e-5)
     eng.set_dataset(0, x.cuda(), t.cuda())
+    # 32x32 and 20x36 run the fused head and tail; 8x8 cannot (2 x 3 x 3 = 18 inputs of Linear 0: no whole k-steps)
+    plan = eng.kernel_plan(batch, True)
+    if in_size == (8, 8):
+        assert plan["head"] == {"fwd": "layers", "why": "nin4"} and plan["tail"] == {"bwd": "layers", "why": "fc4"}, plan
+    else:
+        assert plan["head"]["fwd"] == "fused" and plan["tail"]["bwd"] == "fused", plan
     ref = orc.OracleModel(spec.save(), enc.state_dict(), dec.state_dict(), lr=1e-3, weight_decay=1e-5)
     slot = eng.forward_backward(0, None, 0, batch, batch)
     loss = eng._read_losses(slot, 1)[0]
