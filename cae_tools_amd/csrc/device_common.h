@@ -243,6 +243,31 @@ __device__ __forceinline__ void bn_batch_finish(const BnDesc& d, int c, bool upd
     }
 }
 
+// BN_BWD constants of channel c in the same two halves (k_adam's per-weight workgroups request them ahead of their operands)
+struct BnBwdReq {
+    double2 t[kStatShards];
+    float gamma, mean, invstd;
+};
+__device__ __forceinline__ void bn_bwd_request(const BnDesc& d, int c, BnBwdReq& r) {
+    r.gamma = d.gamma[c];
+#pragma unroll
+    for (int sh = 0; sh < kStatShards; sh++) r.t[sh] = *reinterpret_cast<const double2*>(d.stats + ((size_t)sh * d.C + c) * 4 + 2);
+    r.mean = d.saved[2 * c];
+    r.invstd = d.saved[2 * c + 1];
+}
+__device__ __forceinline__ float4 bn_bwd_finish(const BnDesc& d, const BnBwdReq& r) {
+    double dbeta = 0.0, dgamma = 0.0;
+#pragma unroll
+    for (int sh = 0; sh < kStatShards; sh++) {
+        dbeta += r.t[sh].x;
+        dgamma += r.t[sh].y;
+    }
+    const float scale = r.gamma * r.invstd;
+    const float k2 = (float)((double)scale * dbeta * d.inv_count);
+    const float k3 = (float)((double)scale * (double)r.invstd * dgamma * d.inv_count);
+    return make_float4(r.mean, scale, k2, k3);
+}
+
 // `first`: the thread that takes channel 0.  A kernel with two descriptors gives the second one to its second wave
 // (first = 64): on one wave the two would be two trips to memory one after the other, the loads of the second behind the
 // wait of the first.
@@ -263,28 +288,18 @@ __device__ __forceinline__ void bn_consts(const BnDesc& d, float4* out, bool des
             bn_batch_finish(d, c, upd, rq, out);
             continue;
         }
+        if (d.mode == BN_BWD) {
+            BnBwdReq rq;
+            bn_bwd_request(d, c, rq);
+            out[c] = bn_bwd_finish(d, rq);
+            continue;
+        }
         const float gamma = d.gamma[c];
         if (d.mode == BN_RUNNING) {
             const float beta = d.beta[c];
             mean = d.rmean[c];
             invstd = 1.0f / sqrtf(d.rvar[c] + d.eps);
             out[c] = make_float4(mean, gamma * invstd, beta, invstd);
-        } else if (d.mode == BN_BWD) {
-            double2 t[kStatShards];
-#pragma unroll
-            for (int sh = 0; sh < kStatShards; sh++) t[sh] = *reinterpret_cast<const double2*>(d.stats + ((size_t)sh * d.C + c) * 4 + 2);
-            mean = d.saved[2 * c];
-            invstd = d.saved[2 * c + 1];
-            double dbeta = 0.0, dgamma = 0.0;
-#pragma unroll
-            for (int sh = 0; sh < kStatShards; sh++) {
-                dbeta += t[sh].x;
-                dgamma += t[sh].y;
-            }
-            const float scale = gamma * invstd;
-            const float k2 = (float)((double)scale * dbeta * d.inv_count);
-            const float k3 = (float)((double)scale * (double)invstd * dgamma * d.inv_count);
-            out[c] = make_float4(mean, scale, k2, k3);
         } else {   // saved statistics of this step (activation recomputed in the backward pass)
             const float beta = d.beta[c];
             mean = d.saved[2 * c];

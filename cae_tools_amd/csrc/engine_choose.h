@@ -543,10 +543,13 @@ DecBwdK choose_dec_bwd(const cae_engine* e, const ConvLayer& L, int l, int B, bo
 // whose k_head_fwd left the batch's inputs behind, a layer small enough for k_adam's extra blocks, its BatchNorm table first in the swept range.
 // enc_conv0_fits_adam: what the engine and the layer decide (cae_debug_plan reports it for a step with a fused head);
 // enc_conv0_in_adam_ok adds the two facts of the step at hand: the optimiser follows, k_head_fwd published the inputs
+// (the per-weight workgroups' index arithmetic, adam_conv0_body: small divisors, 24-bit factors, 32-bit byte offsets)
 bool enc_conv0_fits_adam(const cae_engine* e, const StepArgs& a, const ConvLayer& L) {
     return e->use_s2 && !a.syncing() && a.world == 1 && L.cout <= 64 &&
            (int64_t)L.cin * L.cout * L.kh * L.kw <= 4096 && (int64_t)a.batch * L.hout * L.wout < kDivSmallMaxN &&
-           L.hout * L.wout < kDivSmallMaxD && e->bn_stat_off[L.bn_index] == e->off_zero_begin;
+           L.hout * L.wout < kDivSmallMaxD && L.in_elems() < (1 << 24) && L.out_elems() < (1 << 24) &&
+           (int64_t)a.batch * L.in_elems() < (1 << 30) && (int64_t)a.batch * L.out_elems() < (1 << 30) &&
+           e->bn_stat_off[L.bn_index] == e->off_zero_begin;
 }
 
 bool enc_conv0_in_adam_ok(const cae_engine* e, const StepArgs& a, const ConvLayer& L) {

@@ -594,32 +594,50 @@ __device__ __forceinline__ void adam_conv0_body(const AdamConv0& c0, float* __re
         optimiser_state(st, t, lr);
         t += t_add;
     }
+    const int hw = g.Hs * g.Ws, n = g.B * hw;
+    const float inv_hw = 1.0f / (float)hw, inv_w = 1.0f / (float)g.Ws;
+    // Sixteen positions' addresses stand ahead of the first operand load, so their arithmetic is the front of the launch's
+    // longest workgroups: 24-bit multiplies (full rate; a 32-bit one takes four times as long, the 64-bit index arithmetic
+    // this replaces longer) and 32-bit byte offsets from the wave-uniform bases.  enc_conv0_fits_adam keeps every factor below
+    // 2^24 and every offset below 2^32; the elements read, and the order they are added in, are what they were.
+    const unsigned small_b = (unsigned)(g.Cs * hw), big_b = (unsigned)(g.Cl * g.Hl * g.Wl), big_y = (unsigned)(g.s * g.Wl);
+    const unsigned small_0 = (unsigned)(cs * hw), big_0 = (unsigned)((cl * g.Hl + ky) * g.Wl + kx);
+    auto at = [](const float* base, unsigned elem) {
+        return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (size_t)(elem * 4u));
+    };
+    auto fetch = [&](int pp, float& sp, float& sq, float& lp) {
+        const int b = div_small(pp, inv_hw), r = pp - __mul24(b, hw);
+        const int y = div_small(r, inv_w), x = r - __mul24(y, g.Ws);
+        const unsigned so = __umul24((unsigned)b, small_b) + small_0 + (unsigned)r;
+        sp = at(c0.small.p, so);
+        sq = at(c0.small.q, so);
+        lp = at(c0.xb, __umul24((unsigned)b, big_b) + __umul24((unsigned)y, big_y) + __umul24((unsigned)x, (unsigned)g.s) + big_0);
+    };
+    float sp[kAdamConv0Pos], sq[kAdamConv0Pos], lp[kAdamConv0Pos];
+#pragma unroll
+    for (int u = 0; u < kAdamConv0Pos; u++) fetch(min(tid + u * 256, n - 1), sp[u], sq[u], lp[u]);
+    // Behind the operands, in the same burst (loads return in the order they were requested, so nothing here is waited for
+    // ahead of them): the BatchNorm constants' inputs, one channel per thread of the LAST wave (C <= 64) - bn_consts used to
+    // request them behind the operands' wait, a second trip to memory - and the parameter with its moments.
+    BnBwdReq rq;
+    const int bc_ = tid - 192;
+    const bool has_c = bc_ >= 0 && bc_ < c0.bns.C;
+    if (has_c) bn_bwd_request(c0.bns, bc_, rq);
     float w = 0.f, mi = 0.f, vi = 0.f;
     if (tid == 0) {
         w = p[pi];
         mi = m[pi];
         vi = v[pi];
     }
-    const int hw = g.Hs * g.Ws, n = g.B * hw;
-    const float inv_hw = 1.0f / (float)hw, inv_w = 1.0f / (float)g.Ws;
-    auto fetch = [&](int pp, float& sp, float& sq, float& lp) {
-        const int b = div_small(pp, inv_hw), r = pp - b * hw;
-        const int y = div_small(r, inv_w), x = r - y * g.Ws;
-        const size_t so = ((size_t)(b * g.Cs + cs) * g.Hs + y) * g.Ws + x;
-        sp = c0.small.p[so];
-        sq = c0.small.q[so];
-        lp = c0.xb[((size_t)(b * g.Cl + cl) * g.Hl + (y * g.s + ky)) * g.Wl + x * g.s + kx];
-    };
-    float sp[kAdamConv0Pos], sq[kAdamConv0Pos], lp[kAdamConv0Pos];
-#pragma unroll
-    for (int u = 0; u < kAdamConv0Pos; u++) fetch(min(tid + u * 256, n - 1), sp[u], sq[u], lp[u]);
-#pragma unroll
-    for (int u = 0; u < kAdamConv0Pos; u++) asm volatile("" : "+v"(sp[u]), "+v"(sq[u]), "+v"(lp[u]));
-    bn_consts(c0.bns, cs4, false);
+    // the bias corrections while all of that travels (two lanes of the first wave: an fp64 chain that used to start behind the
+    // operands' wait)
     if (tid < 2) {
         const double bc = -expm1((double)t * (tid ? ln_b2 : ln_b1));
         corr[tid] = tid ? (float)sqrt(bc) : (float)(lr / bc);
     }
+#pragma unroll
+    for (int u = 0; u < kAdamConv0Pos; u++) asm volatile("" : "+v"(sp[u]), "+v"(sq[u]), "+v"(lp[u]));
+    if (has_c) cs4[bc_] = bn_bwd_finish(c0.bns, rq);
     __syncthreads();
     const float4 ks = cs4[cs];
     float sum = 0.f;
