@@ -26,6 +26,10 @@ class ProfileRecC(C.Structure):
                 ("bytes", C.c_double)]
 
 
+class SceneGeomC(C.Structure):
+    _fields_ = [("Y", C.c_int64), ("X", C.c_int64)] + [(n, C.c_int32) for n in ("h", "w", "oy", "ox", "sy", "sx")]
+
+
 # enum cae_elem_kind: element kinds of cae_case_measures
 ELEM_F32, ELEM_F32_BE, ELEM_F64, ELEM_F64_BE = 0, 1, 2, 3
 
@@ -123,6 +127,10 @@ SIGNATURES = {
     "cae_case_baseline_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "cae_case_baseline": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64,
                                     C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, C.c_int64, _P]),
+    "cae_scene_gather": (C.c_int, [C.POINTER(SceneGeomC), _P, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                   _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P]),
+    "cae_scene_blend": (C.c_int, [C.POINTER(SceneGeomC), _P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64,
+                                  C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_double, _P, C.c_int64, _P, _P]),
     # ---- include/cae_unet.h ----
     "unet_engine_create": (C.c_int, [C.POINTER(LayerSpecC), C.c_int, C.POINTER(LayerSpecC), C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.POINTER(C.c_void_p)]),

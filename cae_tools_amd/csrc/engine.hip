@@ -861,6 +861,7 @@ int cae_profile_end(cae_engine* e, cae_profile_rec* out, int capacity) {
 
 }  // extern "C"
 
+#include "kernels_scene.h"   // the scene kernels, after every kernel of the step: those keep their places in the code object
 #include "stateless_host.h"
 
 // =================================================================================================

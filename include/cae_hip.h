@@ -588,6 +588,49 @@ int cae_case_baseline(const void* low_dev, int low_kind, int64_t low_case_stride
                       double* sums_dev /* [n_case][6] */, double* field_dev /* NULL or [n_case][h_out][w_out] */,
                       void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- scene apply (stateless): a box model applied to a whole scene ----------------------------- */
+
+/* A model maps an input box (c, h, w) to an output box (c_out, H, W) with H = h * sy, W = w * sx.  A scene variable is
+ * (n_t, c, Y, X) with Y >= h, X >= w.  The scene is cut into overlapping boxes: with the overlap (oy, ox), 0 <= oy < h, the
+ * stride is s = h - oy, the origins along y are y_k = min(k * s, Y - h) for k = 0 .. n_y - 1, n_y = 1 + ceil((Y - h) / s), along
+ * x likewise: every tile is a full box and the last one is shifted inward, so a pixel can lie in three and more tiles of an
+ * axis.  Tiles are numbered (k_y, k_x) row-major within a time step. */
+typedef struct {
+    int64_t Y, X;       /* the scene, low-resolution pixels */
+    int32_t h, w;       /* the input box */
+    int32_t oy, ox;     /* the overlap, low-resolution pixels */
+    int32_t sy, sx;     /* output pixels per input pixel (cae_scene_blend only) */
+} cae_scene_geom;
+
+/* The boxes of one variable, normalised, into the packed batch the model scores: for the time steps t0 .. t0 + n_t_call - 1
+ * and the tile rows ky0 .. ky0 + n_ky - 1, tile ((t - t0) * n_ky + (k_y - ky0)) * n_x + k_x of dst_dev (n_tile, c_dst, h, w)
+ * receives at channels c_off .. c_off + c_src - 1 the box of src_dev (n_t, c_src, Y, X; any CAE_ELEM_* kind, read as stored)
+ * with cae_normalise_pack's arithmetic: the value rounded to fp32 first, then (v - vmin) / range in two rounded fp32
+ * operations, 0 where range == 0, v itself with enable == 0.  invalid_dev[tile] (int32) is ORed with 1 when a value of the box
+ * is not finite as fp32; the caller clears it before the first variable of a batch.  One launch, no workspace. */
+int cae_scene_gather(const cae_scene_geom* geom, const void* src_dev, int src_kind, int64_t n_t, int c_src, int64_t t0,
+                     int64_t n_t_call, int64_t ky0, int64_t n_ky, float* dst_dev, int c_dst, int c_off, float vmin, float range,
+                     int enable, int32_t* invalid_dev, void* hip_stream);
+
+/* The scored boxes folded back into the scene, output rows row0 .. row1 - 1 of n_t_call time steps.  On the output grid a
+ * tile's row r has m = min(r, H - 1 - r) and the weight w_y(r) = min(2 m + 1, 2 oy sy) (1 when oy == 0), columns likewise,
+ * w = w_y w_x: integers, and geom is refused unless 4 H W < 2^29, so that w * (double)p is exact for every fp32 p.  Per pixel
+ *   v = (S_t w_t (double)p_t) / S_t w_t     over the covering tiles with invalid == 0, in ascending tile number, plain fp64 adds
+ *   out = vmin + v * range                  (cae_denormalise_f64's two rounded operations)
+ * and NaN where no valid tile covers the pixel; nan_pixels_dev[t - t0] (int64, added to: the caller clears it) counts those
+ * pixels once, whatever c_out.  A pixel under one valid tile is that tile's value denormalised, bit for bit.
+ * pred_dev (n_t_call, n_k, n_x, c_out, H, W) fp32 and invalid_dev (n_t_call, n_k, n_x) hold the tile rows k0 .. k0 + n_k - 1;
+ * carry_pred_dev / carry_invalid_dev, laid out alike, the tile rows carry_k0 .. + carry_n_k - 1 of an earlier call, all below
+ * k0 (carry_n_k == 0: none).  Every tile row that covers an output row of the call must be in one of the two runs, or the call
+ * is refused: a scene blended in pieces of whole tile rows gives the bits of one call.  out_dev is the scene of time step t0,
+ * (c_out, Y sy, X sx) doubles, the next time step out_t_stride elements on.  A gather per output pixel: each output element is
+ * written once, each prediction element read once, element loads at any alignment; no floating-point atomics, no workspace.
+ * n_t_call * c_out <= 65535, output sides up to 2^30. */
+int cae_scene_blend(const cae_scene_geom* geom, const float* pred_dev, const int32_t* invalid_dev, int64_t k0, int64_t n_k,
+                    const float* carry_pred_dev, const int32_t* carry_invalid_dev, int64_t carry_k0, int64_t carry_n_k,
+                    int64_t n_t_call, int c_out, int64_t row0, int64_t row1, double vmin, double range, double* out_dev,
+                    int64_t out_t_stride, int64_t* nan_pixels_dev, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
