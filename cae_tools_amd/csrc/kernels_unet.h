@@ -148,7 +148,7 @@ __global__ void __launch_bounds__(256) k_up(Geom g, const float* __restrict__ S,
     for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
         const Nchw o = nchw_of(idx, g.Cl, g.Hl, g.Wl);
         const int X = o.x, Y = o.y, cl = o.c, b = o.b;
-        float acc = bias ? bias[cl] : 0.f;
+        double acc = bias ? (double)bias[cl] : 0.0;   // (fp64: an fp32 product is exact in it and the Cs * taps terms are rounded once, not one after another)
         // only the taps of this output's parity: ky = (Y + p) mod s, + s, ... reading row y = (Y + p) / s, - 1, ... (one
         // division per dimension per output instead of a modulo and a division per tap)
         const int y0 = (Y + g.p) / g.s, x0 = (X + g.p) / g.s;
@@ -160,10 +160,10 @@ __global__ void __launch_bounds__(256) k_up(Geom g, const float* __restrict__ S,
                 const float* sp = S + (size_t)b * g.Cs * g.Hs * g.Ws + (size_t)y * g.Ws + x;
                 const float* wp = w + ((size_t)cl * g.kh + ky) * g.kw + kx;
                 for (int cs = 0; cs < g.Cs; cs++)
-                    acc = fmaf(sp[(size_t)cs * g.Hs * g.Ws], wp[(size_t)cs * g.Cl * g.kh * g.kw], acc);
+                    acc = fma((double)sp[(size_t)cs * g.Hs * g.Ws], (double)wp[(size_t)cs * g.Cl * g.kh * g.kw], acc);
             }
         }
-        L[idx] = acc;
+        L[idx] = (float)acc;
     }
 }
 

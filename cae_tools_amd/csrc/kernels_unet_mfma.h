@@ -634,13 +634,20 @@ inline size_t mfma_down_part_bytes(const Geom& g) {
     return nsplit > 2 ? (size_t)(nsplit - 1) * g.B * g.Cs * g.Hs * g.Ws * sizeof(float) : 0;
 }
 
+// the K slices mfma_down_launch runs given part_bytes of room for partial maps (have_part: there is such a buffer); the
+// launch takes this and unet_debug_plan prints it
+inline int mfma_down_nsplit(const Geom& g, bool have_part, size_t part_bytes) {
+    int nsplit = mfma_down_slices(g);
+    if (nsplit > 2 && (!have_part || mfma_down_part_bytes(g) > part_bytes)) nsplit = 2;
+    return nsplit;
+}
+
 // part: part_bytes of room for the partial maps (mfma_down_part_bytes); K is sliced at most twice when they do not fit
 inline void mfma_down_launch(const Geom& g, const float* L, const float* w, const float* bias, float* S, float* part,
                              size_t part_bytes, hipStream_t s) {
     const int rows = g.Cs;
     const long long cols = (long long)g.B * g.Hs * g.Ws;
-    int nsplit = mfma_down_slices(g);
-    if (nsplit > 2 && (!part || mfma_down_part_bytes(g) > part_bytes)) nsplit = 2;
+    const int nsplit = mfma_down_nsplit(g, part != nullptr, part_bytes);
     const int per = (g.Cl + nsplit - 1) / nsplit;
     if (nsplit == 2) (void)hipMemsetAsync(S, 0, (size_t)cols * rows * sizeof(float), s);
     igemm_dispatch<OpDown>(rows, cols, nsplit, s, [&](auto& op) {
@@ -699,24 +706,44 @@ inline size_t mfma_wgrad_part_bytes(const Geom& g) {
     return (size_t)mfma_wgrad_slices(g) * g.Cs * g.Cl * 16 * sizeof(float);
 }
 
+// what mfma_wgrad_launch runs: the single-wave path or the 4-wave tile of igemm_tile, the K slices (blockIdx.z) and the
+// chunks of IG_KC pixels each.  The launch takes this and unet_debug_plan prints it
+struct MfmaWgradPlan {
+    bool one_wave;
+    int zdim, per;
+};
+inline MfmaWgradPlan mfma_wgrad_plan(const Geom& g) {
+    const int rows = g.Cs;
+    const long long cols = (long long)g.Cl * 16;
+    const int chunks = (g.B * g.Hs * g.Ws + IG_KC - 1) / IG_KC;
+    MfmaWgradPlan p;
+    p.one_wave = cols <= IG_WG1;   // <= 8 channels on the big side: single-wave 32 x 128 tiles, the parallelism comes from K
+    if (p.one_wave) {
+        const int rt = (rows + 31) / 32, ct = (int)((cols + 127) / 128);
+        p.per = (int)(((long long)chunks * rt * ct + 2047) / 2048);                // ~2048 single-wave workgroups (8 per CU)
+        if (p.per < 8) p.per = 8;
+        p.zdim = (chunks + p.per - 1) / p.per;
+    } else {
+        p.zdim = mfma_wgrad_slices(g);
+        p.per = (chunks + p.zdim - 1) / p.zdim;
+    }
+    return p;
+}
+
 // part: room for mfma_wgrad_part_bytes(g) (the slices' tiles, folded in order by k_wgrad_fold) or nullptr (fp64 atomics on the
 // ACC_GRAD grid)
 inline void mfma_wgrad_launch(const Geom& g, const float* S, const float* L, double* acc, float* part, hipStream_t s) {
     const int rows = g.Cs;
     const long long cols = (long long)g.Cl * 16;
-    if (cols <= IG_WG1) {   // <= 8 channels on the big side: single-wave 32 x 128 tiles, the parallelism comes from K
-        const int chunks = (g.B * g.Hs * g.Ws + IG_KC - 1) / IG_KC;
+    const MfmaWgradPlan pl = mfma_wgrad_plan(g);
+    if (pl.one_wave) {
         const int rt = (rows + 31) / 32, ct = (int)((cols + 127) / 128);
-        int per = (int)(((long long)chunks * rt * ct + 2047) / 2048);                // ~2048 single-wave workgroups (8 per CU)
-        if (per < 8) per = 8;
         OpWgrad<1> op;
-        op.g = g, op.S = S, op.L = L, op.acc = acc, op.part = nullptr, op.ksplit = per;
-        igemm_launch<1, 1>(op, dim3(ct, rt, (chunks + per - 1) / per), s);
+        op.g = g, op.S = S, op.L = L, op.acc = acc, op.part = nullptr, op.ksplit = pl.per;
+        igemm_launch<1, 1>(op, dim3(ct, rt, pl.zdim), s);
         return;
     }
-    const int chunks = (g.B * g.Hs * g.Ws + IG_KC - 1) / IG_KC;
-    const int zdim = mfma_wgrad_slices(g);
-    const int per = (chunks + zdim - 1) / zdim;
+    const int zdim = pl.zdim, per = pl.per;
     igemm_dispatch<OpWgrad>(rows, cols, zdim, s, [&](auto& op) {
         op.g = g, op.S = S, op.L = L, op.acc = acc, op.part = part, op.ksplit = per;
     });

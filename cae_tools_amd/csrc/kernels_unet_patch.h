@@ -185,13 +185,24 @@ inline size_t pdown_part_bytes(const Geom& g) {
     return nsplit > 2 ? (size_t)(nsplit - 1) * g.B * g.Cs * g.Hs * g.Ws * sizeof(float) : 0;
 }
 
+// what pdown_launch runs given part_bytes of room for partial maps (have_part: there is such a buffer): the row-block count and
+// the K slices after the room check.  pdown_launch launches from this; unet_debug_plan prints it
+struct PdownPlan {
+    int rbn, nsplit;
+};
+inline PdownPlan pdown_plan(const Geom& g, bool have_part, size_t part_bytes) {
+    PdownPlan p{2, 1};
+    p.nsplit = pdown_slices(g, &p.rbn);
+    if (p.nsplit > 2 && (!have_part || pdown_part_bytes(g) > part_bytes)) p.nsplit = 2;
+    return p;
+}
+
 // part: part_bytes of room for the partial maps (pdown_part_bytes); K is sliced at most twice when they do not fit
 inline void pdown_launch(const Geom& g, const float* L, const float* w, const float* bias, float* S, float* part, size_t part_bytes,
                          hipStream_t s) {
     const PatchShape sh = patch_shape(g);
-    int rbn = 2;
-    int nsplit = pdown_slices(g, &rbn);
-    if (nsplit > 2 && (!part || pdown_part_bytes(g) > part_bytes)) nsplit = 2;
+    const PdownPlan pl = pdown_plan(g, part != nullptr, part_bytes);
+    const int rbn = pl.rbn, nsplit = pl.nsplit;
     const int TN = 32 * rbn, rt = (g.Cs + TN - 1) / TN;
     const int groups = g.Cl / kPatchCG;
     const int gper = (groups + nsplit - 1) / nsplit;
@@ -352,11 +363,14 @@ __global__ void __launch_bounds__(256) k_pup(Geom g, const float* __restrict__ S
         }
 }
 
+// row blocks of k_pup (pup_launch launches it, unet_debug_plan prints it):
+// 32-row tiles where there are few pixel tiles (the 16 x 16 layers at batch 32: 256 -> 512 workgroups, 82 -> 77 us)
+inline int pup_rbn(const Geom& g) { return (g.Cl <= 32 || (long long)g.B * pup_shape(g).tiles <= 64) ? 1 : 2; }
+
 // wp: the layer's weights repacked per parity by k_pack_up_weights
 inline void pup_launch(const Geom& g, const float* S, const float* wp, const float* bias, float* L, hipStream_t s) {
     const PatchShape sh = pup_shape(g);
-    // 32-row tiles where there are few pixel tiles (the 16 x 16 layers at batch 32: 256 -> 512 workgroups, 82 -> 77 us)
-    const int rbn = (g.Cl <= 32 || (long long)g.B * sh.tiles <= 64) ? 1 : 2;
+    const int rbn = pup_rbn(g);
     const int TN = 32 * rbn;
     const dim3 grid((unsigned)(g.B * sh.tiles), (g.Cl + TN - 1) / TN, 2);
     const size_t lds = pup_lds_bytes(g, rbn);
@@ -512,8 +526,10 @@ __global__ void __launch_bounds__(256) k_pwgrad(Geom g, const float* __restrict_
 }
 
 // K slices and bytes of partial tiles of a launch
+// wave rows of k_pwgrad<WR, WC>, WC = 4 / WR (pwgrad_launch switches on it, unet_debug_plan prints it)
+inline int pwgrad_wr(const Geom& g) { return g.Cs >= 128 ? 4 : 2; }
 inline int pwgrad_tpw(const Geom& g) {
-    const int rows = g.Cs >= 128 ? 128 : 64;
+    const int rows = 32 * pwgrad_wr(g);
     const long long tiles_out = (long long)(g.Cl / 8) * ((g.Cs + rows - 1) / rows);
     const int total = g.B * pwgrad_shape(g).tiles;
     long long want = (512 + tiles_out - 1) / tiles_out;    // slices to aim at (512 workgroups): two resident workgroups per CU
@@ -531,7 +547,7 @@ inline size_t pwgrad_part_bytes(const Geom& g) { return (size_t)pwgrad_slices(g)
 // part: room for pwgrad_part_bytes(g)
 inline void pwgrad_launch(const Geom& g, const float* S, const float* L, double* acc, float* part, hipStream_t s) {
     const int tpw = pwgrad_tpw(g), slices = pwgrad_slices(g);
-    if (g.Cs >= 128) {
+    if (pwgrad_wr(g) == 4) {
         const dim3 grid(g.Cl / 8, (g.Cs + 127) / 128, slices);
         hipLaunchKernelGGL((k_pwgrad<4, 1>), grid, dim3(256), pwgrad_lds_bytes(g, 4), s, g, S, L, part, tpw);
     } else {

@@ -217,6 +217,13 @@ __global__ void __launch_bounds__(256) k_thin_fold(const float* __restrict__ par
     }
 }
 
+// The template arguments and grids of the thin launches.  The one place that decides them: the launches below switch on what
+// these return and unet_debug_plan prints it.
+// row blocks of 32 channels of S (RBN): k_thin_wgrad and k_thin_down
+inline int thin_rbn(const Geom& g) { return g.Cs <= 32 ? 1 : 2; }
+// the large-side channel count the kernels are instantiated for (CL): k_thin_down, k_thin_up, k_up_thin
+inline int thin_cl(const Geom& g) { return g.Cl >= 1 && g.Cl <= 3 ? g.Cl : 4; }
+
 inline int thin_wgrad_tpw(const Geom& g) { return std::min(8, thin_shape(g).tiles); }
 inline int thin_wgrad_groups(const Geom& g) {
     const int tpw = thin_wgrad_tpw(g);
@@ -228,7 +235,7 @@ inline size_t thin_wgrad_part_bytes(const Geom& g) { return (size_t)g.B * thin_w
 // part: room for thin_wgrad_part_bytes(g), or nullptr (fp64 atomics on the ACC_GRAD grid from every workgroup instead)
 inline void thin_wgrad_launch(const Geom& g, const float* S, const float* L, double* acc, float* part, hipStream_t s) {
     const int tpw = thin_wgrad_tpw(g), nwg = g.B * thin_wgrad_groups(g);
-    if (g.Cs <= 32) hipLaunchKernelGGL(k_thin_wgrad<1>, dim3(nwg), dim3(256), thin_lds_bytes(g, 1), s, g, S, L, acc, part, tpw);
+    if (thin_rbn(g) == 1) hipLaunchKernelGGL(k_thin_wgrad<1>, dim3(nwg), dim3(256), thin_lds_bytes(g, 1), s, g, S, L, acc, part, tpw);
     else hipLaunchKernelGGL(k_thin_wgrad<2>, dim3(nwg), dim3(256), thin_lds_bytes(g, 2), s, g, S, L, acc, part, tpw);
     if (part) {
         const int E = g.Cs * 16 * g.Cl;
@@ -339,13 +346,17 @@ __global__ void __launch_bounds__(256) k_thin_down(Geom g, const float* __restri
 }
 
 inline int thin_down_tpw(const Geom& g) { return std::min(8, thin_shape(g).tiles); }
+inline int thin_down_groups(const Geom& g) {
+    const int tpw = thin_down_tpw(g);
+    return (thin_shape(g).tiles + tpw - 1) / tpw;
+}
 template <int RBN>
 inline void thin_down_launch_cl(const Geom& g, const float* L, const float* w, const float* bias, float* S, hipStream_t s) {
     const ThinShape sh = thin_shape(g);
-    const int tpw = thin_down_tpw(g), nwg = g.B * ((sh.tiles + tpw - 1) / tpw);
+    const int tpw = thin_down_tpw(g), nwg = g.B * thin_down_groups(g);
     // the patch; before the first tile the same area holds the weights once
     const size_t lds = (size_t)std::max(g.Cl * sh.planep + 4, 32 * RBN * g.Cl * 16) * sizeof(float);
-    switch (g.Cl) {
+    switch (thin_cl(g)) {
         case 1: hipLaunchKernelGGL((k_thin_down<RBN, 1>), dim3(nwg), dim3(256), lds, s, g, L, w, bias, S, tpw); break;
         case 2: hipLaunchKernelGGL((k_thin_down<RBN, 2>), dim3(nwg), dim3(256), lds, s, g, L, w, bias, S, tpw); break;
         case 3: hipLaunchKernelGGL((k_thin_down<RBN, 3>), dim3(nwg), dim3(256), lds, s, g, L, w, bias, S, tpw); break;
@@ -353,7 +364,7 @@ inline void thin_down_launch_cl(const Geom& g, const float* L, const float* w, c
     }
 }
 inline void thin_down_launch(const Geom& g, const float* L, const float* w, const float* bias, float* S, hipStream_t s) {
-    if (g.Cs <= 32) thin_down_launch_cl<1>(g, L, w, bias, S, s);
+    if (thin_rbn(g) == 1) thin_down_launch_cl<1>(g, L, w, bias, S, s);
     else thin_down_launch_cl<2>(g, L, w, bias, S, s);
 }
 
@@ -446,11 +457,13 @@ inline bool thin_up_geom(const Geom& g) {
     return g.kh == 4 && g.kw == 4 && g.s == 2 && g.p == 1 && g.Hl == 2 * g.Hs && g.Wl == 2 * g.Ws && g.Cl >= 1 && g.Cl <= 4 &&
            g.Ws == 128 && g.Hs % 2 == 0 && (long long)g.B * g.Cs * g.Hs * g.Ws < (1ll << 31);
 }
+// one wave per band of two input rows (T = 2), four waves per workgroup: the last workgroup's spare waves return at once
+inline int thin_up_waves(const Geom& g) { return g.B * (g.Hs / 2); }
+inline int thin_up_wgs(const Geom& g) { return (thin_up_waves(g) + 3) / 4; }
 // wq: the layer's weights in k_thin_up's order (k_pack_up_weights, thin entry)
 inline void thin_up_launch(const Geom& g, const float* S, const float* wq, const float* bias, float* L, hipStream_t s) {
-    const int waves = g.B * (g.Hs / 2);
-    const dim3 grid((waves + 3) / 4);
-    switch (g.Cl) {
+    const dim3 grid(thin_up_wgs(g));
+    switch (thin_cl(g)) {
         case 1: hipLaunchKernelGGL((k_thin_up<1, 2>), grid, dim3(256), 0, s, g, S, wq, bias, L); break;
         case 2: hipLaunchKernelGGL((k_thin_up<2, 2>), grid, dim3(256), 0, s, g, S, wq, bias, L); break;
         case 3: hipLaunchKernelGGL((k_thin_up<3, 2>), grid, dim3(256), 0, s, g, S, wq, bias, L); break;

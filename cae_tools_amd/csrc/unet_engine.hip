@@ -204,7 +204,7 @@ void conv_up(unet_engine* e, const Geom& g, const float* S, const float* w, cons
         case UP_THIN: thin_up_launch(g, S, wp, bias, L, e->stream); return;
         case UP_THIN_CL: {
             const int blocks = blocks_for((long long)g.B * g.Hs * g.Ws, 65536);
-            switch (g.Cl) {
+            switch (thin_cl(g)) {
                 case 1: hipLaunchKernelGGL(k_up_thin<1>, dim3(blocks), dim3(256), 0, e->stream, g, S, w, bias, L); break;
                 case 2: hipLaunchKernelGGL(k_up_thin<2>, dim3(blocks), dim3(256), 0, e->stream, g, S, w, bias, L); break;
                 case 3: hipLaunchKernelGGL(k_up_thin<3>, dim3(blocks), dim3(256), 0, e->stream, g, S, w, bias, L); break;
@@ -341,15 +341,34 @@ bool lin_big(const unet_engine* e, const Fc& L, int B) {
     return need <= e->linpart_bytes;
 }
 
+// what lin_gemm runs for a batch of B rows and a sum over K: row blocks of 32 batch rows (RB), tiles of kLinKT per workgroup,
+// K slices (more than one: partial tiles and k_lin_fold) and whether the last tile of K is partly filled (zero fill of k >= K).
+// lin_gemm launches from this; unet_debug_plan prints it
+struct LinGemmPlan {
+    int rb, kiters, slices;
+    bool partial;
+};
+LinGemmPlan lin_gemm_plan(int B, int K) {
+    LinGemmPlan p;
+    p.kiters = 2;
+    p.slices = (K + p.kiters * kLinKT - 1) / (p.kiters * kLinKT);
+    p.rb = B > 32 ? 2 : 1;
+    p.partial = K % kLinKT != 0;
+    return p;
+}
+// dynamic LDS of k_lin_outer at this batch: above 64 KiB (batch > 56) lin_bwd raises the kernel's limit first
+size_t lin_outer_lds(int B) { return (size_t)2 * ((B + 7) & ~7) * kLinPN * sizeof(float); }
+
 // Y[b][n] = bias[n] + sum_k X[b][k] W[..]: nt = W[n][k] (forward), else W[k][n] (input gradient)
 void lin_gemm(unet_engine* e, bool nt, const float* X, long long x_ld, const float* W, long long w_ld, const float* bias, float* Y,
               int B, int N, int K) {
+    const LinGemmPlan pl = lin_gemm_plan(B, K);
     LinArgs a;
-    a.X = X, a.x_ld = x_ld, a.W = W, a.w_ld = w_ld, a.bias = bias, a.Y = Y, a.y_ld = N, a.B = B, a.N = N, a.K = K, a.kiters = 2;
-    const int slices = (K + a.kiters * kLinKT - 1) / (a.kiters * kLinKT);
+    a.X = X, a.x_ld = x_ld, a.W = W, a.w_ld = w_ld, a.bias = bias, a.Y = Y, a.y_ld = N, a.B = B, a.N = N, a.K = K, a.kiters = pl.kiters;
+    const int slices = pl.slices;
     a.part = slices > 1 ? reinterpret_cast<float*>(e->ws + e->off_linpart) : nullptr;
     const dim3 grid((N + kLinNT - 1) / kLinNT, slices);
-    const int RB = B > 32 ? 2 : 1;
+    const int RB = pl.rb;
     if (nt) {
         const size_t lds = (size_t)(32 * RB + 128) * kLinPK * sizeof(float);
         if (RB == 1) hipLaunchKernelGGL(k_lin_nt<1>, grid, dim3(256), lds, e->stream, a);
@@ -413,8 +432,7 @@ void lin_bwd(unet_engine* e, const Fc& L, int B, const float* in, const float* g
             // dW[o][i] = sum_b gout[b][o] in[b][i] as fp32 in the first half of the weight's accumulator slots (F32Ranges),
             // db[o] = sum_b gout[b][o];  gin[b][i] = sum_o gout[b][o] W[o][i]
             e->fc_f32_dirty[fk] = true;
-            const int B8 = (B + 7) & ~7;
-            const size_t lds = (size_t)2 * B8 * kLinPN * sizeof(float);
+            const size_t lds = lin_outer_lds(B);
             static bool raised = false;   // above the 64 KiB a kernel gets without asking (batch > 56)
             if (lds > 65536 && !raised) {
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lin_outer), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * kLinPN * 4);
@@ -1137,28 +1155,121 @@ int unet_debug_plan(const unet_engine* e, int batch, int train, char* out, int64
         return g;
     };
     std::string s;
-    char line[256];
+    char line[256];   // (one field group at a time: a layer's line is built piecewise)
+    auto tile_name = [&](int rows) {
+        const IgemmTile t = igemm_tile(rows);
+        return std::to_string(t.tn()) + "x" + std::to_string(t.tm());
+    };
+    // what the launch of each family switches on below the family, from the functions the launches call
+    auto down_fields = [&](const Geom& g) {
+        line[0] = 0;
+        switch (choose_down(e, g)) {
+            case DOWN_THIN:
+                snprintf(line, sizeof line, " down.rbn=%d down.cl=%d down.tpw=%d down.groups=%d down.Ws=%d", thin_rbn(g), thin_cl(g),
+                         thin_down_tpw(g), thin_down_groups(g), g.Ws);
+                break;
+            case DOWN_PATCH: {
+                const PdownPlan p = pdown_plan(g, true, (size_t)e->downpart_bytes);
+                snprintf(line, sizeof line, " down.rbn=%d down.nsplit=%d down.Ws=%d", p.rbn, p.nsplit, g.Ws);
+                break;
+            }
+            case DOWN_MFMA:
+                snprintf(line, sizeof line, " down.tile=%s down.nsplit=%d", tile_name(g.Cs).c_str(),
+                         mfma_down_nsplit(g, true, (size_t)e->downpart_bytes));
+                break;
+            case DOWN_GENERIC: break;
+        }
+        s += line;
+    };
+    auto up_fields = [&](const Geom& g, bool has_wp) {
+        line[0] = 0;
+        switch (choose_up(e, g, has_wp)) {
+            case UP_THIN:
+                snprintf(line, sizeof line, " up.cl=%d up.waves=%d up.wgs=%d", thin_cl(g), thin_up_waves(g), thin_up_wgs(g));
+                break;
+            case UP_THIN_CL: snprintf(line, sizeof line, " up.cl=%d", thin_cl(g)); break;
+            case UP_PATCH: snprintf(line, sizeof line, " up.rbn=%d up.Ws=%d", pup_rbn(g), g.Ws); break;
+            case UP_MFMA: snprintf(line, sizeof line, " up.tile=%s", tile_name(g.Cl).c_str()); break;
+            case UP_GENERIC: break;
+        }
+        s += line;
+    };
+    auto wgrad_fields = [&](const Geom& g) {
+        line[0] = 0;
+        switch (choose_wgrad(e, g)) {
+            case WG_THIN:
+            case WG_THIN_ATOMIC:
+                snprintf(line, sizeof line, " wgrad.rbn=%d wgrad.tpw=%d wgrad.groups=%d", thin_rbn(g), thin_wgrad_tpw(g), thin_wgrad_groups(g));
+                break;
+            case WG_PATCH:
+                snprintf(line, sizeof line, " wgrad.wrxwc=%dx%d wgrad.tpw=%d wgrad.slices=%d", pwgrad_wr(g), 4 / pwgrad_wr(g), pwgrad_tpw(g),
+                         pwgrad_slices(g));
+                break;
+            case WG_MFMA:
+            case WG_MFMA_ATOMIC: {
+                const MfmaWgradPlan p = mfma_wgrad_plan(g);
+                snprintf(line, sizeof line, " wgrad.tile=%s wgrad.slices=%d wgrad.per=%d", p.one_wave ? "1wave" : tile_name(g.Cs).c_str(),
+                         p.zdim, p.per);
+                break;
+            }
+            case WG_GENERIC: break;
+        }
+        s += line;
+    };
     // the calls forward() and backward() make: an encoder layer runs OpDown forward, its weight gradient and (but the first)
     // OpUp for its input gradient; a decoder layer runs OpUp forward, its weight gradient and OpDown for its input gradient
     for (size_t i = 0; i < e->enc.size(); i++) {
         const ConvLayer& L = e->enc[i];
         const Geom g = geom(L);
-        snprintf(line, sizeof line, "enc%zu down=%s up=%s wgrad=%s wp=%d packed=%d\n", i, kDownName[choose_down(e, g)],
+        snprintf(line, sizeof line, "enc%zu down=%s up=%s wgrad=%s wp=%d packed=%d", i, kDownName[choose_down(e, g)],
                  train && i > 0 ? kUpName[choose_up(e, g, L.wp >= 0)] : "-", train ? kWgradName[choose_wgrad(e, g)] : "-",
                  (int)(L.wp >= 0), in_pack(L));
         s += line;
+        down_fields(g);
+        if (train && i > 0) up_fields(g, L.wp >= 0);
+        if (train) wgrad_fields(g);
+        s += "\n";
     }
     for (int k = 0; k < 4; k++) {
-        const char* fam = kLinName[choose_lin(e, e->fc[k], batch)];
-        snprintf(line, sizeof line, "fc%d fwd=%s bwd=%s\n", k, fam, train ? fam : "-");
+        const Fc& L = e->fc[k];
+        const LinK kind = choose_lin(e, L, batch);
+        const char* fam = kLinName[kind];
+        snprintf(line, sizeof line, "fc%d fwd=%s bwd=%s", k, fam, train ? fam : "-");
         s += line;
+        if (kind == LIN_BIG) {   // lin_fwd: N = nout, K = nin;  lin_bwd: k_lin_outer, then the input gradient with N = nin, K = nout
+            const LinGemmPlan f = lin_gemm_plan(batch, L.nin);
+            snprintf(line, sizeof line, " fwd.rb=%d fwd.slices=%d fwd.kiters=%d fwd.partial=%d fwd.ntiles=%d fwd.nlast=%d", f.rb, f.slices,
+                     f.kiters, (int)f.partial, (L.nout + kLinNT - 1) / kLinNT, L.nout - (L.nout - 1) / kLinNT * kLinNT);
+            s += line;
+            if (train) {
+                const LinGemmPlan b = lin_gemm_plan(batch, L.nout);
+                snprintf(line, sizeof line, " bwd.rb=%d bwd.slices=%d bwd.kiters=%d bwd.partial=%d outer_lds=%zu", b.rb, b.slices, b.kiters,
+                         (int)b.partial, lin_outer_lds(batch));
+                s += line;
+            }
+        } else if (kind == LIN_TILE) {   // the GEMMs lin_fwd and lin_bwd hand to gemm_launch
+            const GemmPlan f = gemm_plan(L.nout, batch, L.nin, 0, true, (size_t)e->gpart_bytes);
+            snprintf(line, sizeof line, " fwd.tile=%dx%d fwd.slices=%d fwd.per=%d", f.tile.tn(), f.tile.tm(), f.slices, f.per);
+            s += line;
+            if (train) {
+                const GemmPlan w = gemm_plan(L.nout, L.nin, batch, 2, false, 0), d = gemm_plan(L.nin, batch, L.nout, 0, true, (size_t)e->gpart_bytes);
+                snprintf(line, sizeof line, " wgrad.tile=%dx%d wgrad.slices=%d bwd.tile=%dx%d bwd.slices=%d bwd.per=%d", w.tile.tn(), w.tile.tm(),
+                         w.slices, d.tile.tn(), d.tile.tm(), d.slices, d.per);
+                s += line;
+            }
+        }
+        s += "\n";
     }
     for (size_t j = 0; j < e->dec.size(); j++) {
         const ConvLayer& L = e->dec[j];
         const Geom g = geom(L);
-        snprintf(line, sizeof line, "dec%zu down=%s up=%s wgrad=%s wp=%d packed=%d\n", j, train ? kDownName[choose_down(e, g)] : "-",
+        snprintf(line, sizeof line, "dec%zu down=%s up=%s wgrad=%s wp=%d packed=%d", j, train ? kDownName[choose_down(e, g)] : "-",
                  kUpName[choose_up(e, g, L.wp >= 0)], train ? kWgradName[choose_wgrad(e, g)] : "-", (int)(L.wp >= 0), in_pack(L));
         s += line;
+        if (train) down_fields(g);
+        up_fields(g, L.wp >= 0);
+        if (train) wgrad_fields(g);
+        s += "\n";
     }
     snprintf(line, sizeof line, "pack entries=%zu launches=%d\n", packed.size(), pack_launches(packed.size()));
     s += line;

@@ -23,7 +23,9 @@ class UnetPlan(SpecPlan):
     def kernel_plan(self, batch, train):
         """the kernel families a step at this batch runs (unet_debug_plan, include/cae_unet.h), no GPU needed:
         {"enc0": {"down": "thin", "up": "-", "wgrad": "thin", "wp": "0", "packed": "0"}, ..., "fc0": {"fwd": ..., "bwd": ...},
-        ..., "dec0": {...}, "pack": {"entries": "7", "launches": "1"}}"""
+        ..., "dec0": {...}, "pack": {"entries": "7", "launches": "1"}}.  Beside the family every layer carries what its launch
+        switches on below it, from the functions the launch calls: "down.rbn", "down.nsplit", "up.cl", "wgrad.tile", "fwd.rb",
+        "fwd.slices", "outer_lds", ... (the list is in include/cae_unet.h)"""
         buf = C.create_string_buffer(1 << 16)
         check(self.lib.unet_debug_plan(self.handle, int(batch), 1 if train else 0, buf, len(buf)))
         plan = {}

@@ -111,7 +111,20 @@ int unet_debug_read(unet_engine* e, const char* what, float* out_host, int64_t c
  *   "enc<i> down=<family> up=<family> wgrad=<family> wp=<0|1> packed=<0|1>"   (dec<j> likewise; "-": not run in this mode)
  *   "fc<k> fwd=<family> bwd=<family>"
  * then "pack entries=<n> launches=<m>".  wp: the layer has a repack buffer; packed: its weights are repacked before the
- * step.  Writes a NUL-terminated string of at most out_bytes bytes. */
+ * step.  After these, every line carries what the launch of each family switches on below the family, as <op>.<field>=<value>,
+ * each from the host function the launch itself calls:
+ *   down=thin    down.rbn down.cl (template arguments) down.tpw down.groups (tiles per workgroup, workgroups per image) down.Ws
+ *   down=patch   down.rbn down.nsplit (K slices after the room check of the partial maps: 1, 2 = atomics, > 2 = fold) down.Ws
+ *   down=mfma    down.tile (rows x columns of the tile engine's tile) down.nsplit
+ *   up=thin      up.cl up.waves up.wgs        up=up_thin  up.cl        up=patch  up.rbn up.Ws        up=mfma  up.tile
+ *   wgrad=thin|thin_atomic   wgrad.rbn wgrad.tpw wgrad.groups
+ *   wgrad=patch              wgrad.wrxwc wgrad.tpw wgrad.slices
+ *   wgrad=mfma|mfma_atomic   wgrad.tile (or "1wave") wgrad.slices wgrad.per (chunks of 16 pixels per slice)
+ *   fwd=lin_big  fwd.rb fwd.slices fwd.kiters fwd.partial (the last K tile is partly filled) fwd.ntiles fwd.nlast (column
+ *                tiles, width of the last); training: bwd.rb bwd.slices bwd.kiters bwd.partial (the input gradient) and
+ *                outer_lds (bytes of dynamic LDS of the weight-gradient kernel)
+ *   fwd=tile     fwd.tile fwd.slices fwd.per; training: wgrad.tile wgrad.slices bwd.tile bwd.slices bwd.per
+ * Writes a NUL-terminated string of at most out_bytes bytes. */
 int unet_debug_plan(const unet_engine* e, int batch, int train, char* out_host, int64_t out_bytes);
 
 #ifdef __cplusplus

@@ -1,14 +1,13 @@
 """UNET HIP path (include/cae_unet.h) against the reference-generated vectors (tests/golden/unet_*.npz) and, for
 train-mode dropout (whose masks are a hash both sides share), against the pinned CPU oracle."""
-import math
 import time
 
 import numpy as np
 import pytest
 import torch
 
-from unet_helpers import (DEEP_CASES, MEDIUM_CASES, TRAIN_CASES, UNET_CASES, UnetCase, aligned_oracle_grads, assert_unet_grads,
-                          feeds_batchnorm, grad_ratios, hip_argmax_decisions, hip_relu_decisions, unet_oracle)
+from unet_helpers import (ARGMAX_CAP, ARGMAX_TOL, DEEP_CASES, MEDIUM_CASES, RELU_TOL, TRAIN_CASES, UNET_CASES,  # noqa: F401
+                          UnetCase, _against_aligned_oracles, _check_alignment, _grad_dict, feeds_batchnorm, relu_cap, unet_oracle)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,68 +20,6 @@ def _engine(case, max_batch=None, dropout=None, specialised=True, seed=0):
     eng.set_hyper(lr=m["lr"], weight_decay=m["weight_decay"], dropout_rate=m["dropout"] if dropout is None else dropout,
                   lambda_pearson=m["lambda_pearson"], seed=seed)
     return eng
-
-
-def _grad_dict(eng, flat):
-    flat = flat.cpu()
-    return {n: flat[off:off + numel].view(shape) for n, (arena, off, numel, shape) in eng.tensors.items() if arena == 0}
-
-
-# Alignment windows.  ReLU: a BatchNorm output that the HIP run and an oracle put on different sides of zero is followed where
-# the oracle's own value is within RELU_TOL of zero.  Measured over every geometry of this file (Row 1): with
-# dropout off (cfg3 batch 32, 28 decisions followed) every followed decision is a noise flip, the worst at |z| = 4.0e-6; a
-# 1e-5 window left the dropout-on geometries at up to 9.8e-6.  So the window is 1e-4, 10x the largest.  (With dropout on, a
-# HIP 'False' may also be a dropped element, which then fills the window: harmless, the element is zero either way.)
-# Max-pool: a HIP index is followed where the oracle's value there is within ARGMAX_TOL of its own maximum; the one gap
-# followed measured 4.8e-7 (64 px, generic kernels): 1e-5 is 20x that.
-RELU_TOL = 1e-4
-ARGMAX_TOL = 1e-5
-# Count caps.  A decision can differ only where |z| is within the noise of zero.  With N ReLU outputs of unit-variance
-# BatchNorm (density ~0.4 at zero) and a noise of at most RELU_TOL / 10 = 1e-5, the expected count is N x 0.4 x 2e-5 =
-# 8e-6 N; the cap is that plus 8: 488 at cfg3 batch 32 (N ~ 6e7), where 28 were followed.  The gate pools B x C planes of
-# 1e2 .. 1e5 entries; two entries at the top within 1e-6 of each other showed up once in all the planes of this file
-# (~2e4): 4 is generous.
-ARGMAX_CAP = 4
-
-
-def relu_cap(decisions):
-    return 8 + math.ceil(8e-6 * sum(np.asarray(v).size for v in decisions.values()))
-
-
-def _check_alignment(rep, relu, what):
-    cap = relu_cap(relu)
-    for side in ("fp32", "fp64"):
-        r = rep[side]
-        assert r["relu"] <= cap, (f"{what} ({side} oracle): {r['relu']} ReLU decisions followed > cap {cap} (worst |z| followed "
-                                  f"{r['relu_worst']:.2e}; per site {r['relu_sites']})")
-        assert r["argmax"] <= ARGMAX_CAP, (f"{what} ({side} oracle): {r['argmax']} max-pool decisions followed > {ARGMAX_CAP} "
-                                           f"(worst gap followed {r['argmax_worst']:.2e})")
-
-
-def _against_aligned_oracles(eng, spec_json, enc_sd, dec_sd, x, t, m, fc, latent, what, dropout_rate=0.0, seed=0, step=0,
-                             lambda_pearson=1.0, loss_rtol=3e-5):
-    """one forward_backward of `eng` (dataset 0 set, its hyper-parameters matching the arguments) against the fp32 and fp64
-    oracles, both following this run's ReLU and max-pool decisions where they cannot decide them: losses, every gradient
-    tensor through assert_unet_grads.  Returns (fp32 oracle, HIP gradients, worst ratio, alignment report)"""
-    B = x.shape[0]
-    grads = _grad_dict(eng, eng.forward_backward(0, None, 0, B, slot=0))
-    got_losses = eng.read_losses(0, 1)[0]
-    # (read before anything else overwrites the activations: score() would)
-    relu = hip_relu_decisions(eng, spec_json, fc, latent, B)
-    amax = hip_argmax_decisions(eng, spec_json, B)
-    (o32, losses, g32, g64, rep) = aligned_oracle_grads(spec_json, enc_sd, dec_sd, x, t, m, relu, amax, dropout_rate=dropout_rate,
-                                                        seed=seed, step=step, relu_tol=RELU_TOL, argmax_tol=ARGMAX_TOL,
-                                                        lambda_pearson=lambda_pearson)
-    ratios = grad_ratios(grads, g32, g64)
-    top = sorted(((e / b, k) for k, (e, b, _) in ratios.items()), reverse=True)[:3]
-    print(f"\n[unet parity] {what}: worst |hip-fp64|/bound {top[0][0]:.3f} ({top[0][1]}), next {[(round(r, 3), k) for r, k in top[1:]]}; "
-          f"ReLU followed {rep['fp32']['relu']}/{rep['fp64']['relu']} (cap {relu_cap(relu)}) worst |z| "
-          f"{max(rep['fp32']['relu_worst'], rep['fp64']['relu_worst']):.2e}; argmax followed {rep['fp32']['argmax']}/"
-          f"{rep['fp64']['argmax']} worst gap {max(rep['fp32']['argmax_worst'], rep['fp64']['argmax_worst']):.2e}")
-    _check_alignment(rep, relu, what)
-    np.testing.assert_allclose(got_losses, losses, rtol=loss_rtol)
-    worst = assert_unet_grads(grads, g32, g64, what)
-    return o32, grads, worst, rep
 
 
 @pytest.mark.parametrize("specialised", [True, False])
