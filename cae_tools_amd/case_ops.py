@@ -1,0 +1,365 @@
+"""The case kernels of libcae_hip (include/cae_hip.h) as functions, no engine needed: measures, per-pixel sums, spectra, SSIM,
+interpolation baseline, ensemble verification, value range and rendered pages of channel 0 of (N, C, H, W) operands."""
+import ctypes as C
+import math
+from contextlib import contextmanager
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._engine_base import require_gpu
+from ._lib import check
+from .device_ops import _is_big_endian_slab, _upload_raw
+
+_TORCH_KINDS = {torch.float32: _lib.ELEM_F32, torch.float64: _lib.ELEM_F64}
+# cases per call, which bounds the workspace (for SSIM the pooled planes); a case's sums do not depend on the cut
+(_SPECTRA_CASES, _SSIM_CASES) = (512, 256)
+_BASELINE_FIELD_BYTES = 256 << 20       # of fp64 field per cae_case_baseline call when the field is asked for
+_RENDER_BYTES = 64 << 20                # of rendered pages per group of cae_render_cases calls
+
+
+@dataclass(frozen=True, eq=False)
+class DeviceOperand:
+    """One operand of the case kernels on the device: what device_operand returns, and takes again without another upload"""
+
+    tensor: torch.Tensor        # kept alive; the raw bytes of a big-endian slab, else the array itself
+    kind: int                   # _lib.ELEM_*
+    shape: tuple                # of the array
+    stride: int                 # from one case to the next, in elements
+
+    @property
+    def elem_bytes(self):
+        return 4 if self.kind in (_lib.ELEM_F32, _lib.ELEM_F32_BE) else 8
+
+    def args(self, case0=0):
+        """(pointer to case case0, element kind, case stride): the three C arguments of an operand"""
+        return self.tensor.data_ptr() + case0 * self.stride * self.elem_bytes, self.kind, self.stride
+
+
+def _args(op, case0=0):
+    """op.args(case0), or the C arguments of an optional operand that is not there (the caller keeps op alive over the call)"""
+    return op.args(case0) if op is not None else (None, 0, 0)
+
+
+def device_operand(x, device=None):
+    """x (numpy array, raw NetCDF-3 slab or CUDA tensor) on the device, ready for the case kernels.  A CUDA tensor is used in
+    place; a C-contiguous big-endian >f4 / >f8 numpy array (a NetCDF-3 slab) goes up as its raw bytes and is swapped inside
+    the kernel; any other array is uploaded in its native fp32 / fp64 form.  An operand made earlier is handed through, so
+    one upload serves several calls."""
+    if isinstance(x, DeviceOperand):
+        return x
+    device = _case_device(device, x)
+    if isinstance(x, torch.Tensor):
+        if not x.is_cuda:
+            x = x.numpy()
+        else:
+            if x.dtype not in _TORCH_KINDS:
+                x = x.to(torch.float64)
+            x = x.contiguous()
+            return DeviceOperand(x, _TORCH_KINDS[x.dtype], tuple(x.shape), int(x.stride(0)))
+    arr = np.asarray(x)
+    for (dtype, kind) in ((">f4", _lib.ELEM_F32_BE), (">f8", _lib.ELEM_F64_BE)):
+        if _is_big_endian_slab(arr, dtype):
+            return DeviceOperand(_upload_raw(arr, device), kind, arr.shape, int(np.prod(arr.shape[1:])))
+    if arr.dtype.newbyteorder("=") != np.dtype(np.float32):
+        arr = arr.astype(np.float64)
+    t = torch.from_numpy(np.ascontiguousarray(arr, dtype=arr.dtype.newbyteorder("="))).to(device)
+    return DeviceOperand(t, _TORCH_KINDS[t.dtype], tuple(t.shape), int(np.prod(t.shape[1:])))
+
+
+def device_operands(xs, device=None):
+    """(device, the operands xs on it): the device given, else that of a device-resident operand, else the current one"""
+    device = _case_device(device, *xs)
+    return device, [device_operand(x, device) for x in xs]
+
+
+def _case_device(device, *operands):
+    """the device the case kernels run on: the one given, else that of a device-resident operand, else the current one"""
+    if device is None:
+        for x in operands:
+            if isinstance(x, DeviceOperand):
+                x = x.tensor
+            if isinstance(x, torch.Tensor) and x.is_cuda:
+                return x.device
+        require_gpu()
+        device = torch.device("cuda", torch.cuda.current_device())
+    return torch.device(device)
+
+
+def _pair(name, pred, actual, device):
+    """(device, prediction, target, N, H, W) of a function over pairs of cases: (N, C, H, W) operands with N, H and W in common"""
+    (device, (p, a)) = device_operands((pred, actual), device)
+    if len(p.shape) != 4 or len(a.shape) != 4:
+        raise ValueError(f"{name}: (N, C, H, W) arrays expected, got {p.shape} and {a.shape}")
+    if p.shape[0] != a.shape[0] or p.shape[2:] != a.shape[2:]:
+        raise ValueError(f"{name}: prediction {p.shape} and target {a.shape} do not match")
+    return device, p, a, int(p.shape[0]), int(p.shape[2]), int(p.shape[3])
+
+
+def _workspace(device, size_fn, *args, least=8):
+    """(uint8 CUDA tensor, the bytes size_fn(*args) asks for): the workspace of a call, allocated with at least `least` bytes"""
+    need = int(size_fn(*args))
+    return torch.empty(max(need, least), dtype=torch.uint8, device=device), need
+
+
+@contextmanager
+def _stream(device):
+    """the current stream of `device` as the C argument, with the device current"""
+    with torch.cuda.device(device):
+        yield torch.cuda.current_stream(device).cuda_stream
+
+
+def case_measures(pred, actual, device=None):
+    """Per-case (mae, mse) of channel 0, the reference's ModelEvaluator.compute_measure (model_evaluator.py:87-95)
+    for every case at once: mean |p - a| and mean (p - a)^2 over [i, 0, :, :] in fp64.  pred / actual: (N, C, H, W) numpy
+    arrays or CUDA tensors (fp32 or fp64; C may differ).  One streaming pass of cae_case_measures.  Returns an (N, 2)
+    float64 numpy array."""
+    (device, p, a, n, h, w) = _pair("case_measures", pred, actual, device)
+    plane = h * w
+    out = torch.empty((n, 2), dtype=torch.float64, device=device)
+    if n == 0:
+        return np.zeros((0, 2), dtype=np.float64)
+    if plane == 0:
+        return np.full((n, 2), np.nan)      # np.mean of an empty plane
+    lib = _lib.load()
+    (ws, need) = _workspace(device, lib.cae_case_measures_workspace_bytes, n, plane)
+    with _stream(device) as stream:
+        check(lib.cae_case_measures(*p.args(), *a.args(), n, plane, out.data_ptr(), ws.data_ptr(), need, stream))
+        sums = out.cpu().numpy()
+    return sums / float(plane)
+
+
+def pixel_sums(pred, actual, shift=0.0, case_chunk=0, device=None):
+    """The nine per-pixel sums of channel 0 over the cases (cae_pixel_sums, include/cae_hip.h): a (9, H, W) float64 numpy
+    array {n, S d, S|d|, S d^2, S a', S p', S a'^2, S p'^2, S a'p'} with d = p - a, a' = a - shift, p' = p - shift over the
+    cases whose two values at the pixel are finite.  Operands as case_measures takes them; case_chunk 0 leaves the cut
+    of the cases to the library.  shift: one number, or a (2, H, W) array of per-pixel shifts for a and p
+    (cae_pixel_sums_about).  utils/skill_maps.maps_from_sums turns the sums into the skill maps."""
+    (device, p, a, n, h, w) = _pair("pixel_sums", pred, actual, device)
+    plane = h * w
+    about = np.ndim(shift) != 0
+    if about and np.shape(shift) != (2, h, w):
+        raise ValueError(f"pixel_sums: per-pixel shifts of shape (2, {h}, {w}) expected, got {np.shape(shift)}")
+    if n == 0 or plane == 0:
+        return np.zeros((9, h, w), dtype=np.float64)
+    lib = _lib.load()
+    (ws, need) = _workspace(device, lib.cae_pixel_sums_workspace_bytes, n, plane, int(case_chunk))
+    out = torch.empty((9, h, w), dtype=torch.float64, device=device)
+    with _stream(device) as stream:
+        shifts = torch.from_numpy(np.ascontiguousarray(shift, dtype=np.float64)).to(device) if about else None
+        (fn, by) = (lib.cae_pixel_sums_about, shifts.data_ptr()) if about else (lib.cae_pixel_sums, float(shift))
+        check(fn(*p.args(), *a.args(), n, plane, by, int(case_chunk), out.data_ptr(), ws.data_ptr(), need, stream))
+        return out.cpu().numpy()
+
+
+def case_spectra(pred, actual, device=None):
+    """The four binned spectral sums of channel 0 per case (cae_case_spectra, include/cae_hip.h): (sums (N, n_bin, 4) float64
+    {S w|P|^2, S w|A|^2, S w Re(P conj A), S w|D|^2}, counted (N,) bool) for the Hann-windowed, mean-free prediction P,
+    target A and error D = (p - a) over the radial bins of utils/spectra.bin_table(H, W).  A case with a value that is
+    not finite is not counted and has zero sums.  Operands as pixel_sums takes them.
+    utils/spectra.curves_from_sums turns the sums into the spectra, their ratio, the coherence and the error share."""
+    from .utils import spectra
+    (device, p, a, n, h, w) = _pair("case_spectra", pred, actual, device)
+    if not (1 <= h <= 2048 and 1 <= w <= 2048):
+        raise ValueError(f"case_spectra: planes of 1 to 2048 pixels a side expected, got {h} x {w}")
+    table = spectra.bin_table(h, w)
+    n_bin = spectra.bin_count(h, w)
+    if table.shape != (h, w // 2 + 1) or table.min() < -1 or table.max() >= n_bin:
+        raise ValueError("case_spectra: the bin table does not fit its bins")
+    if n == 0:
+        return np.zeros((0, n_bin, 4), dtype=np.float64), np.zeros(0, dtype=bool)
+    lib = _lib.load()
+    sums = torch.empty((n, n_bin, 4), dtype=torch.float64, device=device)
+    counted = torch.empty(n, dtype=torch.int32, device=device)
+    (wy, wx) = (torch.from_numpy(spectra.window(side)).to(device) for side in (h, w))
+    bins = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)).to(device)
+    (ws, need) = _workspace(device, lib.cae_case_spectra_workspace_bytes, min(n, _SPECTRA_CASES), h, w, n_bin, least=16)
+    with _stream(device) as stream:
+        for lo in range(0, n, _SPECTRA_CASES):
+            g = min(n, lo + _SPECTRA_CASES) - lo
+            check(lib.cae_case_spectra(*p.args(lo), *a.args(lo), g, h, w, wy.data_ptr(), wx.data_ptr(), bins.data_ptr(), n_bin,
+                                       sums[lo:].data_ptr(), counted[lo:].data_ptr(), ws.data_ptr(), need, stream))
+        return sums.cpu().numpy(), counted.cpu().numpy() != 0
+
+
+def case_ssim(pred, actual, vmin, vmax, n_scale=None, device=None):
+    """The SSIM sums of channel 0 per case and scale (cae_case_ssim, include/cae_hip.h): an (N, n_scale, 3) float64 numpy
+    array {n, S ssim, S cs} over the counted 11 x 11 windows of scale s, for x = (p - vmin) * (1 / (vmax - vmin)) and y
+    likewise (data_range 1, the VAE loss's definition).  A window over a value that is not finite is left out, for that case
+    and scale only.  n_scale None: 5 where min(H, W) > 160 (MS-SSIM is defined), else 1.  Operands as case_spectra takes them.
+    utils/ssim.scores_from_sums turns the sums into ssim, ms_ssim and psnr."""
+    from .utils import ssim
+    (device, p, a, n, h, w) = _pair("case_ssim", pred, actual, device)
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        raise ValueError(f"case_ssim: planes of 1 to 16384 pixels a side expected, got {h} x {w}")
+    n_scale = ssim.default_scales(h, w) if n_scale is None else int(n_scale)
+    if not 1 <= n_scale <= ssim.MAX_SCALES:
+        raise ValueError(f"case_ssim: n_scale must be 1 to {ssim.MAX_SCALES}, got {n_scale}")
+    (shift, scale) = (float(vmin), 1.0 / (float(vmax) - float(vmin)) if float(vmax) != float(vmin) else math.inf)
+    if not (math.isfinite(shift) and math.isfinite(scale)):
+        raise ValueError(f"case_ssim: vmin and 1 / (vmax - vmin) must be finite, got vmin {vmin!r} and vmax {vmax!r}")
+    if n == 0:
+        return np.zeros((0, n_scale, 3), dtype=np.float64)
+    lib = _lib.load()
+    sums = torch.empty((n, n_scale, 3), dtype=torch.float64, device=device)
+    win = (C.c_double * ssim.WIN_SIZE)(*ssim.window().tolist())
+    (ws, need) = _workspace(device, lib.cae_case_ssim_workspace_bytes, min(n, _SSIM_CASES), h, w, n_scale)
+    with _stream(device) as stream:
+        for lo in range(0, n, _SSIM_CASES):
+            g = min(n, lo + _SSIM_CASES) - lo
+            check(lib.cae_case_ssim(*p.args(lo), *a.args(lo), g, h, w, n_scale, shift, scale, win, sums[lo:].data_ptr(),
+                                    ws.data_ptr(), need, stream))
+        return sums.cpu().numpy()
+
+
+def case_baseline(low, pred, actual, mode="bicubic", field=False, device=None):
+    """Skill against interpolating the input (cae_case_baseline, include/cae_hip.h): channel 0 of low (N, C, h, w) is
+    interpolated to the grid of actual (N, C, H, W) - mode "nearest", "bilinear" or "bicubic", the formulas of
+    torch.nn.functional.interpolate with align_corners=False - inside the kernel that compares it: an (N, 6) float64 numpy
+    array {n, S|b - a|, S(b - a)^2, S|p - a|, S(p - a)^2, n_won} per case over the pixels where a, p and every tap of b
+    are finite.  pred None: entries 3..5 are zero.  field=True returns (sums, b) with b the (N, H, W) float64 interpolated
+    field, NaN where a tap is not finite.  Operands as case_ssim takes them.  utils/baseline.scores_from_sums turns the
+    sums into baseline_mse, skill and win_fraction."""
+    from .utils import baseline
+    if mode not in baseline.MODES:
+        raise ValueError(f"case_baseline: mode must be one of {', '.join(baseline.MODES)}, got {mode!r}")
+    device = _case_device(device, low, pred, actual)
+    (lo, a) = (device_operand(low, device), device_operand(actual, device))
+    if len(lo.shape) != 4 or len(a.shape) != 4 or lo.shape[0] != a.shape[0]:
+        raise ValueError(f"case_baseline: (N, C, h, w) and (N, C, H, W) arrays expected, got {lo.shape} and {a.shape}")
+    p = device_operand(pred, device) if pred is not None else None
+    if p is not None and (len(p.shape) != 4 or p.shape[0] != a.shape[0] or p.shape[2:] != a.shape[2:]):
+        raise ValueError(f"case_baseline: prediction {p.shape} and target {a.shape} do not match")     # _pair's rule, one text
+    (n, h_in, w_in, h, w) = (int(a.shape[0]), int(lo.shape[2]), int(lo.shape[3]), int(a.shape[2]), int(a.shape[3]))
+    if min(h_in, w_in, h, w) < 1:
+        raise ValueError(f"case_baseline: planes of at least one pixel expected, got {h_in} x {w_in} and {h} x {w}")
+    if n == 0:
+        empty = np.zeros((0, 6), dtype=np.float64)
+        return (empty, np.zeros((0, h, w), dtype=np.float64)) if field else empty
+    lib = _lib.load()
+    group = max(1, min(n, _BASELINE_FIELD_BYTES // (8 * h * w))) if field else n
+    sums = torch.empty((n, 6), dtype=torch.float64, device=device)
+    (ws, need) = _workspace(device, lib.cae_case_baseline_workspace_bytes, group, h, w)
+    out = np.empty((n, h, w), dtype=np.float64) if field else None
+    with _stream(device) as stream:
+        for c0 in range(0, n, group):
+            g = min(n, c0 + group) - c0
+            b = torch.empty((g, h, w), dtype=torch.float64, device=device) if field else None
+            check(lib.cae_case_baseline(*lo.args(c0), h_in, w_in, *_args(p, c0), *a.args(c0),
+                                        g, h, w, baseline.MODES[mode], sums[c0:].data_ptr(), b.data_ptr() if field else None,
+                                        ws.data_ptr(), need, stream))
+            if field:
+                out[c0:c0 + g] = b.cpu().numpy()
+        sums = sums.cpu().numpy()
+    return (sums, out) if field else sums
+
+
+def upsample(low, out_shape, mode="bicubic", device=None):
+    """Channel 0 of low (N, C, h, w) interpolated to out_shape = (H, W) as case_baseline does it: an (N, H, W) float64 numpy
+    array, NaN where a tap is not finite (the field output of cae_case_baseline against a target of zeros)."""
+    device = _case_device(device, low)
+    op = device_operand(low, device)
+    if len(op.shape) != 4:
+        raise ValueError(f"upsample: an (N, C, h, w) array expected, got {tuple(op.shape)}")
+    (h, w) = (int(out_shape[0]), int(out_shape[1]))
+    if min(h, w) < 1:
+        raise ValueError(f"upsample: an output of at least one pixel expected, got {h} x {w}")
+    zeros = torch.zeros((int(op.shape[0]), 1, h, w), dtype=torch.float32, device=device)
+    return case_baseline(op, None, zeros, mode=mode, field=True, device=device)[1]
+
+
+def ensemble_verify(draws, actual, vmin, vmax, layout="case", device=None):
+    """cae_ensemble_verify (include/cae_hip.h) on the K draws of every case at once: draws is a float32 numpy array or CUDA
+    tensor (N, K, H, W) or (N, K, C, H, W) for layout "case", (K, N, H, W) or (K, N, C, H, W) for layout "draw" - the
+    normalised decoder output, channel 0 is verified - and actual an (N, C, H, W) target in physical units as case_measures
+    takes it.  The members are vmin + y * (vmax - vmin).  Returns (case_sums (N, 5) float64 {n, S A, S B, S (mbar - a)^2,
+    S s^2}, rank_counts (K + 2,) int64); utils/ensemble_scores.scores_from_sums turns them into the scores."""
+    if layout not in ("case", "draw"):
+        raise ValueError(f"ensemble_verify: layout must be 'case' or 'draw', got {layout!r}")
+    device = _case_device(device, draws, actual)
+    if not isinstance(draws, torch.Tensor):
+        draws = torch.from_numpy(np.ascontiguousarray(draws, dtype=np.float32))
+    if draws.dtype != torch.float32 or draws.dim() not in (4, 5):
+        raise ValueError(f"ensemble_verify: float32 draws of 4 or 5 dimensions expected, got {draws.dtype} {tuple(draws.shape)}")
+    y = draws.to(device).contiguous()
+    a = device_operand(actual, device)
+    (n, k) = (int(y.shape[0]), int(y.shape[1])) if layout == "case" else (int(y.shape[1]), int(y.shape[0]))
+    if len(a.shape) != 4 or a.shape[0] != n or tuple(a.shape[2:]) != tuple(y.shape[-2:]):
+        raise ValueError(f"ensemble_verify: draws {tuple(y.shape)} ({layout} major) and target {tuple(a.shape)} do not match")
+    if not 2 <= k <= 64:
+        raise ValueError(f"ensemble_verify: 2 to 64 draws expected, got {k}")
+    plane = int(y.shape[-2] * y.shape[-1])
+    field = plane * (int(y.shape[2]) if y.dim() == 5 else 1)
+    (case_stride, draw_stride) = (k * field, field) if layout == "case" else (field, n * field)
+    sums = torch.zeros((n, 5), dtype=torch.float64, device=device)
+    ranks = torch.zeros(k + 2, dtype=torch.int64, device=device)
+    if n and plane:
+        lib = _lib.load()
+        (ws, need) = _workspace(device, lib.cae_ensemble_verify_workspace_bytes, n, plane, k)
+        with _stream(device) as stream:
+            check(lib.cae_ensemble_verify(y.data_ptr(), case_stride, draw_stride, *a.args(), n, plane, k, float(vmin),
+                                          float(vmax) - float(vmin), sums.data_ptr(), ranks.data_ptr(), ws.data_ptr(), need, stream))
+    return sums.cpu().numpy(), ranks.cpu().numpy()
+
+
+def _case_pair(name, arr, sub, device):
+    """(device, source, subtracted operand or None, N, H, W) of case_range / render_cases: _pair with texts of its own"""
+    device = _case_device(device, arr, sub)
+    src = device_operand(arr, device)
+    other = device_operand(sub, device) if sub is not None else None
+    shape = src.shape
+    if len(shape) != 4:
+        raise ValueError(f"{name}: an (N, C, H, W) array expected, got {tuple(shape)}")
+    if other is not None and (len(other.shape) != 4 or other.shape[0] != shape[0] or tuple(other.shape[2:]) != tuple(shape[2:])):
+        raise ValueError(f"{name}: {tuple(shape)} and the subtracted {tuple(other.shape)} do not match")
+    return device, src, other, int(shape[0]), int(shape[2]), int(shape[3])
+
+
+def case_range(arr, sub=None, device=None):
+    """(min, max, count) of the finite values of channel 0 of arr (N, C, H, W), or of arr - sub formed in fp64: what
+    np.nanmin / np.nanmax of the fp64 copy give where nothing is infinite, in one streaming pass of cae_case_range over
+    the array as stored.  Operands as case_measures takes them.  (inf, -inf, 0) when no value is finite."""
+    (device, src, other, n, h, w) = _case_pair("case_range", arr, sub, device)
+    if n * h * w == 0:
+        return float("inf"), float("-inf"), 0
+    lib = _lib.load()
+    (ws, need) = _workspace(device, lib.cae_case_range_workspace_bytes, n, h * w, least=0)
+    out = torch.empty(3, dtype=torch.float64, device=device)
+    with _stream(device) as stream:
+        check(lib.cae_case_range(*src.args(), *_args(other), n, h * w, out.data_ptr(), ws.data_ptr(), need, stream))
+        (lo, hi, count) = out.cpu().tolist()
+    return lo, hi, int(count)
+
+
+def render_cases(arr, lo, hi, cases=None, sub=None, flip_y=False, device=None):
+    """Channel 0 of the selected cases of arr (N, C, H, W), or of arr - sub in fp64, as palette indices in PNG scanline
+    form (cae_render_cases, include/cae_hip.h): a (k, H, W + 1) uint8 numpy array whose rows start with the filter byte 0.
+    cases: case indices in any order, repeats allowed (None: all).  Rendered in groups of cases, so that at most about
+    _RENDER_BYTES of output are on the device and in pinned host memory at a time."""
+    (device, src, other, n, h, w) = _case_pair("render_cases", arr, sub, device)
+    sel = np.arange(n, dtype=np.int32) if cases is None else np.asarray(cases, dtype=np.int64).reshape(-1)
+    if sel.size and (sel.min() < 0 or sel.max() >= n):
+        raise IndexError(f"render_cases: case indices must lie in [0, {n})")
+    result = np.empty((sel.size, h, w + 1), dtype=np.uint8)
+    if result.size == 0:
+        return result
+    if w == 0:
+        result[:] = 0
+        return result
+    lib = _lib.load()
+    size = h * (w + 1)
+    group = max(1, min(sel.size, _RENDER_BYTES // size))
+    sel_dev = torch.from_numpy(sel.astype(np.int32)).to(device)
+    out = torch.empty(group * size, dtype=torch.uint8, device=device)
+    stage = torch.empty(group * size, dtype=torch.uint8).pin_memory()
+    flat = result.reshape(-1)
+    with _stream(device) as stream:
+        for k0 in range(0, sel.size, group):
+            k = min(group, sel.size - k0)
+            check(lib.cae_render_cases(*src.args(), *_args(other), sel_dev.data_ptr() + 4 * k0, k, n, h, w, float(lo), float(hi),
+                                       1 if flip_y else 0, out.data_ptr(), stream))
+            stage[:k * size].copy_(out[:k * size], non_blocking=False)
+            flat[k0 * size:(k0 + k) * size] = stage.numpy()[:k * size]
+    return result

@@ -3,6 +3,61 @@
 // kernels_spectra.h, kernels_ssim.h, kernels_baseline.h and kernels_scene.h.  Included by engine.hip alone, at the place
 // this code has always had in it.
 #pragma once
+#include <type_traits>
+
+// ---- the vocabulary of the entry points below: element kinds, case operands, grid sizes ---------------
+
+static int elem_bytes(int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; }
+static bool kind_known(int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; }
+
+// One operand of a case kernel: channel 0 of the cases, `stride` elements from one case to the next.  The checks are
+// functions over it; each entry point calls the ones it has always called, in its own order and under its own texts.
+struct CaseOperand {
+    const void* p;
+    int kind;
+    int64_t stride;
+};
+static bool known(const CaseOperand& o) { return kind_known(o.kind); }
+static bool shorter(const CaseOperand& o, int64_t plane) { return o.stride < plane; }
+static bool misaligned(const CaseOperand& o) { return (uintptr_t)o.p % elem_bytes(o.kind) != 0; }
+// the last case ends above 2^60 elements from the pointer; in 128 bits, so that no stride, however large, wraps the product
+static bool reaches(const CaseOperand& o, int64_t n_case, int64_t plane) {
+    return (__int128)(n_case - 1) * o.stride + plane > ((__int128)1 << 60);
+}
+// no workspace of `need` bytes, 8 bytes aligned
+static bool workspace_short(const void* ws, int64_t bytes, int64_t need) { return !ws || bytes < need || ((uintptr_t)ws & 7); }
+
+// ceil(n / per), at most cap: so many workgroups for n items (the grid-stride kernels walk the rest)
+static int64_t ceil_capped(int64_t n, int64_t per, int64_t cap) {
+    const int64_t b = (n + per - 1) / per;
+    return b < cap ? b : cap;
+}
+
+// The kind dispatch: f(std::integral_constant<int, K>()) for the run-time element kind, which the caller has checked
+// (kind_known).  The kind-templated kernels are instantiated through it alone, the kinds in ascending order and "none"
+// last, as the switches it replaces had them: a kernel's place in the code object follows the order of instantiation,
+// and moving code inside the code object has cost the training step time before.
+template <class F>
+static void with_kind(int kind, F&& f) {
+    switch (kind) {
+    case CAE_ELEM_F32: f(std::integral_constant<int, 0>()); break;
+    case CAE_ELEM_F32_BE: f(std::integral_constant<int, 1>()); break;
+    case CAE_ELEM_F64: f(std::integral_constant<int, 2>()); break;
+    default: f(std::integral_constant<int, 3>()); break;
+    }
+}
+
+// the same for an optional operand: kind -1 stands for "none"
+template <class F>
+static void with_kind_or_none(int kind, F&& f) {
+    switch (kind) {
+    case CAE_ELEM_F32: f(std::integral_constant<int, 0>()); break;
+    case CAE_ELEM_F32_BE: f(std::integral_constant<int, 1>()); break;
+    case CAE_ELEM_F64: f(std::integral_constant<int, 2>()); break;
+    case CAE_ELEM_F64_BE: f(std::integral_constant<int, 3>()); break;
+    default: f(std::integral_constant<int, -1>()); break;
+    }
+}
 
 extern "C" {
 
@@ -11,9 +66,7 @@ extern "C" {
 int cae_scan_f32(const float* x, int64_t n, void* hip_stream, double* out3) {
     if (!x || n < 1 || !out3) return fail(CAE_ERR_ARG, "cae_scan_f32: bad argument");
     hipStream_t s = (hipStream_t)hip_stream;
-    int blocks = (int)((n + 256 * 16 - 1) / (256 * 16));
-    if (blocks > 1024) blocks = 1024;
-    if (blocks < 1) blocks = 1;
+    const int blocks = (int)ceil_capped(n, 256 * 16, 1024);
     double* part = nullptr;
     HIP_TRY(hipMalloc(&part, (size_t)blocks * 3 * sizeof(double)));
     hipLaunchKernelGGL(k_scan, dim3(blocks), dim3(256), 0, s, x, (long long)n, part);
@@ -40,8 +93,7 @@ int cae_normalise_pack_rows(const float* src, int64_t n, int c_src, int64_t hw, 
         return fail(CAE_ERR_ARG, "cae_normalise_pack: bad argument");
     if (n > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_normalise_pack: more than 2^31 - 1 rows");
     const long long total = (long long)n * c_src * hw;
-    int blocks = (int)((total + 256 * 8 - 1) / (256 * 8));
-    if (blocks > 8192) blocks = 8192;
+    const int blocks = (int)ceil_capped(total, 256 * 8, 8192);
     hipLaunchKernelGGL(k_normalise_pack, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream, src, total, c_src,
                        (long long)hw, dst, c_dst, c_off, vmin, range, enable, (const int*)dst_row_dev);
     HIP_TRY(hipGetLastError());
@@ -63,8 +115,7 @@ int cae_invert_permutation(const int32_t* perm_dev, int64_t n, int32_t* inverse_
 
 int cae_denormalise_f64(const float* y, int64_t n, double vmin, double range, double* out, void* hip_stream) {
     if (!y || !out || n < 1) return fail(CAE_ERR_ARG, "cae_denormalise_f64: bad argument");
-    int blocks = (int)((n + 256 * 8 - 1) / (256 * 8));
-    if (blocks > 8192) blocks = 8192;
+    const int blocks = (int)ceil_capped(n, 256 * 8, 8192);
     hipLaunchKernelGGL(k_denorm_f64, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream, y, (long long)n, vmin, range, out);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
@@ -76,8 +127,7 @@ int cae_metric_sums(const float* y, const float* actual, const float* mask, int6
         return fail(CAE_ERR_ARG, "cae_metric_sums: bad argument");
     hipStream_t s = (hipStream_t)hip_stream;
     HIP_TRY(hipMemsetAsync(sums, 0, (size_t)n_inst * 8 * sizeof(double), s));
-    int chunks = (int)((inst_elems + 256 * 16 - 1) / (256 * 16));
-    if (chunks > 64) chunks = 64;
+    const int chunks = (int)ceil_capped(inst_elems, 256 * 16, 64);
     hipLaunchKernelGGL(k_metric_sums, dim3(chunks, (unsigned)n_inst), dim3(256), 0, s, y, actual, mask,
                        (long long)inst_elems, vmin, range, sums);
     HIP_TRY(hipGetLastError());
@@ -105,63 +155,37 @@ int64_t cae_case_measures_workspace_bytes(int64_t n_case, int64_t plane) {
     return nch > 1 ? n_case * nch * 2 * (int64_t)sizeof(double) : 0;
 }
 
-extern "C++" {   // the kind dispatch: templates inside the extern "C" block
-
-template <int KP, int KA>
-static void launch_case_measures(dim3 grid, hipStream_t s, const void* p, int64_t ps, const void* a, int64_t as,
-                                 int64_t plane, int nch, int64_t items, double* out) {
-    hipLaunchKernelGGL((k_case_measures<KP, KA>), grid, dim3(256), 0, s, (const unsigned char*)p, (long long)ps,
-                       (const unsigned char*)a, (long long)as, (long long)plane, nch, (long long)items, out);
-}
-
-template <int KP>
-static void launch_case_measures_a(int ka, dim3 grid, hipStream_t s, const void* p, int64_t ps, const void* a,
-                                   int64_t as, int64_t plane, int nch, int64_t items, double* out) {
-    switch (ka) {
-    case CAE_ELEM_F32: launch_case_measures<KP, 0>(grid, s, p, ps, a, as, plane, nch, items, out); break;
-    case CAE_ELEM_F32_BE: launch_case_measures<KP, 1>(grid, s, p, ps, a, as, plane, nch, items, out); break;
-    case CAE_ELEM_F64: launch_case_measures<KP, 2>(grid, s, p, ps, a, as, plane, nch, items, out); break;
-    default: launch_case_measures<KP, 3>(grid, s, p, ps, a, as, plane, nch, items, out); break;
-    }
-}
-
-}  // extern "C++"
-
 int cae_case_measures(const void* pred, int pred_kind, int64_t pred_stride, const void* actual, int actual_kind,
                       int64_t actual_stride, int64_t n_case, int64_t plane, double* out, void* workspace,
                       int64_t workspace_bytes, void* hip_stream) {
-    auto elem_bytes = [](int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; };
-    auto known = [](int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; };
-    if (!pred || !actual || !out || n_case < 1 || plane < 1 || !known(pred_kind) || !known(actual_kind))
+    const CaseOperand P{pred, pred_kind, pred_stride}, A{actual, actual_kind, actual_stride};
+    if (!P.p || !A.p || !out || n_case < 1 || plane < 1 || !known(P) || !known(A))
         return fail(CAE_ERR_ARG, "cae_case_measures: bad argument");
-    if (pred_stride < plane || actual_stride < plane)
+    if (shorter(P, plane) || shorter(A, plane))
         return fail(CAE_ERR_ARG, "cae_case_measures: a case stride is shorter than the plane");
-    if (((uintptr_t)pred % elem_bytes(pred_kind)) || ((uintptr_t)actual % elem_bytes(actual_kind)) || ((uintptr_t)out & 7))
+    if (misaligned(P) || misaligned(A) || ((uintptr_t)out & 7))
         return fail(CAE_ERR_ARG, "cae_case_measures: pointers must be aligned to their element size");
     const int64_t nch = case_chunks(plane);
     if (nch > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_case_measures: plane too large");
     const int64_t need = cae_case_measures_workspace_bytes(n_case, plane);
-    if (need > 0 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7)))
+    if (need > 0 && workspace_short(workspace, workspace_bytes, need))
         return fail(CAE_ERR_ARG, "cae_case_measures: needs a workspace of %lld bytes (cae_case_measures_workspace_bytes)",
                     (long long)need);
     hipStream_t s = (hipStream_t)hip_stream;
     const int64_t items = n_case * nch;
     double* dst = nch > 1 ? (double*)workspace : out;
-    int64_t blocks = (items + CM_WAVES - 1) / CM_WAVES;
-    if (blocks > 8192) blocks = 8192;
-    const dim3 grid((unsigned)blocks);
-    switch (pred_kind) {
-    case CAE_ELEM_F32: launch_case_measures_a<0>(actual_kind, grid, s, pred, pred_stride, actual, actual_stride, plane, (int)nch, items, dst); break;
-    case CAE_ELEM_F32_BE: launch_case_measures_a<1>(actual_kind, grid, s, pred, pred_stride, actual, actual_stride, plane, (int)nch, items, dst); break;
-    case CAE_ELEM_F64: launch_case_measures_a<2>(actual_kind, grid, s, pred, pred_stride, actual, actual_stride, plane, (int)nch, items, dst); break;
-    default: launch_case_measures_a<3>(actual_kind, grid, s, pred, pred_stride, actual, actual_stride, plane, (int)nch, items, dst); break;
-    }
+    const dim3 grid((unsigned)ceil_capped(items, CM_WAVES, 8192));
+    with_kind(P.kind, [&](auto KP) {
+        with_kind(A.kind, [&](auto KA) {
+            hipLaunchKernelGGL((k_case_measures<decltype(KP)::value, decltype(KA)::value>), grid, dim3(256), 0, s,
+                               (const unsigned char*)P.p, (long long)P.stride, (const unsigned char*)A.p, (long long)A.stride,
+                               (long long)plane, (int)nch, (long long)items, dst);
+        });
+    });
     HIP_TRY(hipGetLastError());
     if (nch > 1) {
-        int64_t fb = (n_case + 255) / 256;
-        if (fb > 4096) fb = 4096;
-        hipLaunchKernelGGL(k_case_fold, dim3((unsigned)fb), dim3(256), 0, s, (const double*)workspace, (long long)n_case,
-                           (int)nch, out);
+        hipLaunchKernelGGL(k_case_fold, dim3((unsigned)ceil_capped(n_case, 256, 4096)), dim3(256), 0, s,
+                           (const double*)workspace, (long long)n_case, (int)nch, out);
         HIP_TRY(hipGetLastError());
     }
     return CAE_OK;
@@ -193,7 +217,7 @@ int cae_ensemble_moments(const float* draws, int64_t case_stride, int64_t draw_s
     memset(&a, 0, sizeof a);
     if (!(first && last)) {
         const int64_t need = cae_ensemble_moments_workspace_bytes(n_case, plane);
-        if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
+        if (workspace_short(workspace, workspace_bytes, need))
             return fail(CAE_ERR_ARG, "cae_ensemble_moments: draws delivered over several calls need a workspace of %lld bytes "
                                      "(cae_ensemble_moments_workspace_bytes)", (long long)need);
         a.w1 = (double*)workspace;
@@ -210,9 +234,7 @@ int cae_ensemble_moments(const float* draws, int64_t case_stride, int64_t draw_s
     a.y = draws, a.case_stride = case_stride, a.draw_stride = draw_stride, a.plane = plane;
     a.kc = k_call, a.K = k_total, a.nch = (int)nch, a.chunk = (int)chunk, a.items = n_case * nch;
     a.vmin = vmin, a.range = range, a.mean = mean, a.sd = sd;
-    int64_t blocks = (a.items + CM_WAVES - 1) / CM_WAVES;
-    if (blocks > 65536) blocks = 65536;
-    const dim3 grid((unsigned)blocks);
+    const dim3 grid((unsigned)ceil_capped(a.items, CM_WAVES, 65536));
     hipStream_t s = (hipStream_t)hip_stream;
     if (first && last) hipLaunchKernelGGL((k_ensemble_moments<true, true>), grid, dim3(256), 0, s, a);
     else if (first) hipLaunchKernelGGL((k_ensemble_moments<true, false>), grid, dim3(256), 0, s, a);
@@ -256,30 +278,29 @@ int cae_ensemble_verify(const float* draws, int64_t case_stride, int64_t draw_st
                         int64_t actual_stride, int64_t n_case, int64_t plane, int k_total, double vmin, double range,
                         double* case_sums, int64_t* rank_counts, void* workspace, int64_t workspace_bytes,
                         void* hip_stream) {
-    if (n_case < 0 || plane < 0 || k_total < 2 || k_total > 64 || actual_kind < CAE_ELEM_F32 || actual_kind > CAE_ELEM_F64_BE)
+    const CaseOperand A{actual, actual_kind, actual_stride};
+    if (n_case < 0 || plane < 0 || k_total < 2 || k_total > 64 || !known(A))
         return fail(CAE_ERR_ARG, "cae_ensemble_verify: bad argument (n_case >= 0, plane >= 0, 2 <= k_total <= 64, a CAE_ELEM_* kind)");
-    if (case_stride < 0 || draw_stride < 0 || actual_stride < 0) return fail(CAE_ERR_ARG, "cae_ensemble_verify: negative stride");
+    if (case_stride < 0 || draw_stride < 0 || A.stride < 0) return fail(CAE_ERR_ARG, "cae_ensemble_verify: negative stride");
     if (!(vmin - vmin == 0.0) || !(range - range == 0.0) || range < 0.0)
         return fail(CAE_ERR_ARG, "cae_ensemble_verify: vmin must be finite, range finite and not negative");
     if (n_case == 0 || plane == 0) return CAE_OK;
-    if (!draws || !actual || !case_sums || !rank_counts) return fail(CAE_ERR_ARG, "cae_ensemble_verify: null pointer");
+    if (!draws || !A.p || !case_sums || !rank_counts) return fail(CAE_ERR_ARG, "cae_ensemble_verify: null pointer");
     // extents in 128 bits: no stride, however large, wraps a product; what the kernel indexes stays below 2^60 elements
     const __int128 draws_of_case = (__int128)(k_total - 1) * draw_stride + plane;
     const __int128 cases_of_draw = (__int128)(n_case - 1) * case_stride + plane;
-    const __int128 limit = (__int128)1 << 60;
-    if (draws_of_case + (__int128)(n_case - 1) * case_stride > limit || (__int128)(n_case - 1) * actual_stride + plane > limit)
+    if (draws_of_case + (__int128)(n_case - 1) * case_stride > ((__int128)1 << 60) || reaches(A, n_case, plane))
         return fail(CAE_ERR_ARG, "cae_ensemble_verify: an operand reaches 2^60 elements from its pointer");
     const bool case_major = case_stride >= draws_of_case && draw_stride >= plane;
     const bool draw_major = draw_stride >= cases_of_draw && (n_case == 1 || case_stride >= plane);
     if (!case_major && !draw_major) return fail(CAE_ERR_ARG, "cae_ensemble_verify: the strides make planes overlap");
-    if (actual_stride < plane) return fail(CAE_ERR_ARG, "cae_ensemble_verify: the target's case stride is shorter than the plane");
-    const int ea = actual_kind == CAE_ELEM_F32 || actual_kind == CAE_ELEM_F32_BE ? 4 : 8;
-    if (((uintptr_t)draws & 3) || ((uintptr_t)actual % ea) || ((uintptr_t)case_sums & 7) || ((uintptr_t)rank_counts & 7))
+    if (shorter(A, plane)) return fail(CAE_ERR_ARG, "cae_ensemble_verify: the target's case stride is shorter than the plane");
+    if (((uintptr_t)draws & 3) || misaligned(A) || ((uintptr_t)case_sums & 7) || ((uintptr_t)rank_counts & 7))
         return fail(CAE_ERR_ARG, "cae_ensemble_verify: pointers must be aligned to their element size");
     const int64_t nch = verify_chunks(n_case, plane);
     if (nch > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_ensemble_verify: plane too large");
     const int64_t need = cae_ensemble_verify_workspace_bytes(n_case, plane, k_total);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
+    if (workspace_short(workspace, workspace_bytes, need))
         return fail(CAE_ERR_ARG, "cae_ensemble_verify: needs a workspace of %lld bytes (cae_ensemble_verify_workspace_bytes)",
                     (long long)need);
     const int64_t blocks = verify_blocks(n_case, plane);
@@ -287,7 +308,7 @@ int cae_ensemble_verify(const float* draws, int64_t case_stride, int64_t draw_st
     EvArgs a;
     memset(&a, 0, sizeof a);
     a.y = draws, a.case_stride = case_stride, a.draw_stride = draw_stride;
-    a.a = (const unsigned char*)actual, a.a_stride = actual_stride, a.plane = plane;
+    a.a = (const unsigned char*)A.p, a.a_stride = A.stride, a.plane = plane;
     a.K = k_total, a.nch = (int)nch, a.chunk = (int)verify_chunk(n_case, plane), a.items = n_case * nch;
     a.vmin = vmin, a.range = range;
     a.sums = nch > 1 ? (double*)workspace : case_sums;
@@ -295,16 +316,10 @@ int cae_ensemble_verify(const float* draws, int64_t case_stride, int64_t draw_st
     hipStream_t s = (hipStream_t)hip_stream;
     const dim3 grid((unsigned)blocks);
     const size_t lds = (size_t)k_total * EV_PIX * sizeof(float);        // at most 64 KiB
-    switch (actual_kind) {
-    case CAE_ELEM_F32: hipLaunchKernelGGL((k_ensemble_verify<0>), grid, dim3(64), lds, s, a); break;
-    case CAE_ELEM_F32_BE: hipLaunchKernelGGL((k_ensemble_verify<1>), grid, dim3(64), lds, s, a); break;
-    case CAE_ELEM_F64: hipLaunchKernelGGL((k_ensemble_verify<2>), grid, dim3(64), lds, s, a); break;
-    default: hipLaunchKernelGGL((k_ensemble_verify<3>), grid, dim3(64), lds, s, a); break;
-    }
+    with_kind(A.kind, [&](auto KA) { hipLaunchKernelGGL((k_ensemble_verify<decltype(KA)::value>), grid, dim3(64), lds, s, a); });
     HIP_TRY(hipGetLastError());
     const int n_bin = k_total + 2;
-    int64_t fb = nch > 1 ? (n_case * EV_SUMS + 255) / 256 : 0;
-    if (fb > 4096) fb = 4096;
+    const int64_t fb = nch > 1 ? ceil_capped(n_case * EV_SUMS, 256, 4096) : 0;
     hipLaunchKernelGGL(k_verify_fold, dim3((unsigned)(n_bin + fb)), dim3(256), 0, s, (const double*)workspace, (long long)n_case,
                        (int)nch, case_sums, (const long long*)a.ranks, (int)blocks, n_bin, (long long*)rank_counts);
     HIP_TRY(hipGetLastError());
@@ -313,79 +328,22 @@ int cae_ensemble_verify(const float* draws, int64_t case_stride, int64_t draw_st
 
 // ---- case pages ------------------------------------------------------------------------------
 
-static int64_t range_blocks(int64_t n_case, int64_t plane) {
-    int64_t blocks = (n_case * case_chunks(plane) + CM_WAVES - 1) / CM_WAVES;
-    return blocks > 8192 ? 8192 : blocks;
-}
+static int64_t range_blocks(int64_t n_case, int64_t plane) { return ceil_capped(n_case * case_chunks(plane), CM_WAVES, 8192); }
 
 int64_t cae_case_range_workspace_bytes(int64_t n_case, int64_t plane) {
     if (n_case < 1 || plane < 1) return 0;
     return range_blocks(n_case, plane) * 3 * (int64_t)sizeof(double);
 }
 
-extern "C++" {
-
-// one operand pair of the case-page kernels: the source and the optional operand subtracted from it (kind -1: none)
-struct CasePair {
-    const void* src;
-    int64_t src_stride;
-    const void* sub;
-    int64_t sub_stride;
-};
-
-struct RenderArgs {
-    const int* cases;
-    int64_t n_case;
-    unsigned height, width;
-    double lo, hi;
-    int flip_y;
-    unsigned char* out;
-};
-
-template <int KS, int KB>
-static void launch_case_range(dim3 grid, hipStream_t s, const CasePair& p, int64_t plane, int nch, int64_t items,
-                              double* part) {
-    hipLaunchKernelGGL((k_case_range<KS, KB>), grid, dim3(256), 0, s, (const unsigned char*)p.src, (long long)p.src_stride,
-                       (const unsigned char*)p.sub, (long long)p.sub_stride, (long long)plane, nch, (long long)items, part);
-}
-
-template <int KS, int KB>
-static void launch_render_cases(dim3 grid, hipStream_t s, const CasePair& p, const RenderArgs& r, int nch, int64_t items) {
-    hipLaunchKernelGGL((k_render_cases<KS, KB>), grid, dim3(256), 0, s, (const unsigned char*)p.src,
-                       (long long)p.src_stride, (const unsigned char*)p.sub, (long long)p.sub_stride, r.cases,
-                       (long long)r.n_case, r.height, r.width, r.lo, r.hi, r.flip_y, nch, (long long)items, r.out);
-}
-
-// CALL<KS, KB>(args...) for the run-time kinds ks (0..3) and kb (-1..3)
-#define CP_DISPATCH_B(CALL, KS, kb, ...)                  \
-    switch (kb) {                                         \
-    case CAE_ELEM_F32: CALL<KS, 0>(__VA_ARGS__); break;    \
-    case CAE_ELEM_F32_BE: CALL<KS, 1>(__VA_ARGS__); break; \
-    case CAE_ELEM_F64: CALL<KS, 2>(__VA_ARGS__); break;    \
-    case CAE_ELEM_F64_BE: CALL<KS, 3>(__VA_ARGS__); break; \
-    default: CALL<KS, -1>(__VA_ARGS__); break;             \
-    }
-#define CP_DISPATCH(CALL, ks, kb, ...)                                        \
-    switch (ks) {                                                             \
-    case CAE_ELEM_F32: CP_DISPATCH_B(CALL, 0, kb, __VA_ARGS__) break;          \
-    case CAE_ELEM_F32_BE: CP_DISPATCH_B(CALL, 1, kb, __VA_ARGS__) break;       \
-    case CAE_ELEM_F64: CP_DISPATCH_B(CALL, 2, kb, __VA_ARGS__) break;          \
-    default: CP_DISPATCH_B(CALL, 3, kb, __VA_ARGS__) break;                    \
-    }
-
-}  // extern "C++"
-
-// the shared argument checks of cae_case_range / cae_render_cases; kb is set to the dispatch kind of `sub` (-1: none)
-static int case_pair_check(const char* who, const void* src, int src_kind, int64_t src_stride, const void* sub,
-                           int sub_kind, int64_t sub_stride, int64_t plane, int* kb) {
-    auto elem_bytes = [](int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; };
-    auto known = [](int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; };
-    if (!src || !known(src_kind) || (sub && !known(sub_kind))) return fail(CAE_ERR_ARG, "%s: bad argument", who);
-    if (src_stride < plane || (sub && sub_stride < plane))
+// The shared argument checks of cae_case_range / cae_render_cases: the source S and the optional operand B subtracted from
+// it (a null pointer: none, and its kind and stride are not looked at).  The three texts of cae_case_measures; neither
+// entry point has the 2^60 check.
+static int case_pair_check(const char* who, const CaseOperand& S, const CaseOperand& B, int64_t plane) {
+    if (!S.p || !known(S) || (B.p && !known(B))) return fail(CAE_ERR_ARG, "%s: bad argument", who);
+    if (shorter(S, plane) || (B.p && shorter(B, plane)))
         return fail(CAE_ERR_ARG, "%s: a case stride is shorter than the plane", who);
-    if (((uintptr_t)src % elem_bytes(src_kind)) || (sub && ((uintptr_t)sub % elem_bytes(sub_kind))))
+    if (misaligned(S) || (B.p && misaligned(B)))
         return fail(CAE_ERR_ARG, "%s: pointers must be aligned to their element size", who);
-    *kb = sub ? sub_kind : -1;
     return CAE_OK;
 }
 
@@ -393,20 +351,25 @@ int cae_case_range(const void* src, int src_kind, int64_t src_stride, const void
                    int64_t n_case, int64_t plane, double* out, void* workspace, int64_t workspace_bytes,
                    void* hip_stream) {
     if (!out || ((uintptr_t)out & 7) || n_case < 1 || plane < 1) return fail(CAE_ERR_ARG, "cae_case_range: bad argument");
-    int kb = -1;
-    const int rc = case_pair_check("cae_case_range", src, src_kind, src_stride, sub, sub_kind, sub_stride, plane, &kb);
+    const CaseOperand S{src, src_kind, src_stride}, B{sub, sub_kind, sub_stride};
+    const int rc = case_pair_check("cae_case_range", S, B, plane);
     if (rc != CAE_OK) return rc;
     const int64_t nch = case_chunks(plane);
     if (nch > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_case_range: plane too large");
     const int64_t need = cae_case_range_workspace_bytes(n_case, plane);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
+    if (workspace_short(workspace, workspace_bytes, need))
         return fail(CAE_ERR_ARG, "cae_case_range: needs a workspace of %lld bytes (cae_case_range_workspace_bytes)",
                     (long long)need);
     hipStream_t s = (hipStream_t)hip_stream;
     const int64_t blocks = range_blocks(n_case, plane);
     const dim3 grid((unsigned)blocks);
-    const CasePair pair{src, src_stride, sub, sub_stride};
-    CP_DISPATCH(launch_case_range, src_kind, kb, grid, s, pair, plane, (int)nch, n_case * nch, (double*)workspace)
+    with_kind(S.kind, [&](auto KS) {
+        with_kind_or_none(B.p ? B.kind : -1, [&](auto KB) {
+            hipLaunchKernelGGL((k_case_range<decltype(KS)::value, decltype(KB)::value>), grid, dim3(256), 0, s,
+                               (const unsigned char*)S.p, (long long)S.stride, (const unsigned char*)B.p, (long long)B.stride,
+                               (long long)plane, (int)nch, (long long)(n_case * nch), (double*)workspace);
+        });
+    });
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_range_fold, dim3(1), dim3(256), 0, s, (const double*)workspace, (int)blocks, out);
     HIP_TRY(hipGetLastError());
@@ -422,19 +385,21 @@ int cae_render_cases(const void* src, int src_kind, int64_t src_stride, const vo
         return fail(CAE_ERR_ARG, "cae_render_cases: image too large (height * (width + 1) must stay below 2^31)");
     if (!(lo - lo == 0.0) || !(hi - hi == 0.0) || !((hi - lo) - (hi - lo) == 0.0))
         return fail(CAE_ERR_ARG, "cae_render_cases: lo, hi and hi - lo must be finite");
-    int kb = -1;
-    const int rc = case_pair_check("cae_render_cases", src, src_kind, src_stride, sub, sub_kind, sub_stride,
-                                   height * width, &kb);
+    const CaseOperand S{src, src_kind, src_stride}, B{sub, sub_kind, sub_stride};
+    const int rc = case_pair_check("cae_render_cases", S, B, height * width);
     if (rc != CAE_OK) return rc;
     const int64_t len = height * (width + 1);
     const int64_t nch = (len / 4 + RC_DWORDS - 1) / RC_DWORDS > 0 ? (len / 4 + RC_DWORDS - 1) / RC_DWORDS : 1;
     const int64_t items = n_sel * nch;
-    int64_t blocks = (items + CM_WAVES - 1) / CM_WAVES;
-    if (blocks > 8192) blocks = 8192;
-    const dim3 grid((unsigned)blocks);
-    const CasePair pair{src, src_stride, sub, sub_stride};
-    const RenderArgs r{(const int*)cases, n_case, (unsigned)height, (unsigned)width, lo, hi, flip_y, out};
-    CP_DISPATCH(launch_render_cases, src_kind, kb, grid, (hipStream_t)hip_stream, pair, r, (int)nch, items)
+    const dim3 grid((unsigned)ceil_capped(items, CM_WAVES, 8192));
+    with_kind(S.kind, [&](auto KS) {
+        with_kind_or_none(B.p ? B.kind : -1, [&](auto KB) {
+            hipLaunchKernelGGL((k_render_cases<decltype(KS)::value, decltype(KB)::value>), grid, dim3(256), 0,
+                               (hipStream_t)hip_stream, (const unsigned char*)S.p, (long long)S.stride, (const unsigned char*)B.p,
+                               (long long)B.stride, (const int*)cases, (long long)n_case, (unsigned)height, (unsigned)width, lo, hi,
+                               flip_y, (int)nch, (long long)items, out);
+        });
+    });
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
@@ -470,33 +435,11 @@ int64_t cae_pixel_sums_workspace_bytes(int64_t n_case, int64_t plane, int64_t ca
     return n_chunk > 1 ? n_chunk * PS_SUMS * plane * (int64_t)sizeof(double) : 0;
 }
 
-extern "C++" {
-
-template <int KP, int KA>
-static void launch_pixel_sums(dim3 grid, hipStream_t s, const PsArgs& a) {
-    if (a.shifts) hipLaunchKernelGGL((k_pixel_sums<KP, KA, true>), grid, dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((k_pixel_sums<KP, KA, false>), grid, dim3(64), 0, s, a);
-}
-
-template <int KP>
-static void launch_pixel_sums_a(int ka, dim3 grid, hipStream_t s, const PsArgs& a) {
-    switch (ka) {
-    case CAE_ELEM_F32: launch_pixel_sums<KP, 0>(grid, s, a); break;
-    case CAE_ELEM_F32_BE: launch_pixel_sums<KP, 1>(grid, s, a); break;
-    case CAE_ELEM_F64: launch_pixel_sums<KP, 2>(grid, s, a); break;
-    default: launch_pixel_sums<KP, 3>(grid, s, a); break;
-    }
-}
-
-}  // extern "C++"
-
 // cae_pixel_sums (shifts == NULL) and cae_pixel_sums_about (per-pixel shifts, `shift` unused)
-static int pixel_sums_run(const void* pred, int pred_kind, int64_t pred_stride, const void* actual, int actual_kind,
-                          int64_t actual_stride, int64_t n_case, int64_t plane, double shift, const double* shifts,
-                          int64_t case_chunk, double* sums, void* workspace, int64_t workspace_bytes, void* hip_stream) {
-    auto elem_bytes = [](int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; };
-    auto known = [](int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; };
-    if (n_case < 0 || plane < 0 || case_chunk < 0 || !known(pred_kind) || !known(actual_kind) || !(shift - shift == 0.0))
+static int pixel_sums_run(const CaseOperand& P, const CaseOperand& A, int64_t n_case, int64_t plane, double shift,
+                          const double* shifts, int64_t case_chunk, double* sums, void* workspace, int64_t workspace_bytes,
+                          void* hip_stream) {
+    if (n_case < 0 || plane < 0 || case_chunk < 0 || !known(P) || !known(A) || !(shift - shift == 0.0))
         return fail(CAE_ERR_ARG, "cae_pixel_sums: bad argument");
     if (plane == 0) return CAE_OK;
     if (!sums || ((uintptr_t)sums & 7)) return fail(CAE_ERR_ARG, "cae_pixel_sums: sums_dev must be an 8-byte aligned pointer");
@@ -505,16 +448,16 @@ static int pixel_sums_run(const void* pred, int pred_kind, int64_t pred_stride, 
         HIP_TRY(hipMemsetAsync(sums, 0, (size_t)plane * PS_SUMS * sizeof(double), s));
         return CAE_OK;
     }
-    if (!pred || !actual) return fail(CAE_ERR_ARG, "cae_pixel_sums: bad argument");
-    if (pred_stride < plane || actual_stride < plane)
+    if (!P.p || !A.p) return fail(CAE_ERR_ARG, "cae_pixel_sums: bad argument");
+    if (shorter(P, plane) || shorter(A, plane))
         return fail(CAE_ERR_ARG, "cae_pixel_sums: a case stride is shorter than the plane");
-    const int ep = elem_bytes(pred_kind), ea = elem_bytes(actual_kind);
-    if (((uintptr_t)pred % ep) || ((uintptr_t)actual % ea))
+    if (misaligned(P) || misaligned(A))
         return fail(CAE_ERR_ARG, "cae_pixel_sums: pointers must be aligned to their element size");
+    const int ep = elem_bytes(P.kind), ea = elem_bytes(A.kind);
     const int64_t chunk = pixel_chunk(n_case, plane, case_chunk);
     const int64_t n_chunk = (n_case + chunk - 1) / chunk;
     const int64_t need = cae_pixel_sums_workspace_bytes(n_case, plane, case_chunk);
-    if (need > 0 && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7)))
+    if (need > 0 && workspace_short(workspace, workspace_bytes, need))
         return fail(CAE_ERR_ARG, "cae_pixel_sums: needs a workspace of %lld bytes (cae_pixel_sums_workspace_bytes)",
                     (long long)need);
     PsArgs a;
@@ -522,31 +465,30 @@ static int pixel_sums_run(const void* pred, int pred_kind, int64_t pred_stride, 
     // 16-byte loads: case 0 has an element where both operands are 16 bytes aligned, and every case stride keeps it
     int h = -1;
     for (int t = 3; t >= 0; t--)
-        if ((((uintptr_t)pred + (uintptr_t)t * ep) | ((uintptr_t)actual + (uintptr_t)t * ea)) % 16 == 0) h = t;
-    const bool keep = n_case == 1 || ((pred_stride * ep) % 16 == 0 && (actual_stride * ea) % 16 == 0);
+        if ((((uintptr_t)P.p + (uintptr_t)t * ep) | ((uintptr_t)A.p + (uintptr_t)t * ea)) % 16 == 0) h = t;
+    const bool keep = n_case == 1 || ((P.stride * ep) % 16 == 0 && (A.stride * ea) % 16 == 0);
     a.vec = h >= 0 && keep;
     a.head = a.vec ? (int)(h < plane ? h : plane) : 0;
-    a.p = (const unsigned char*)pred, a.a = (const unsigned char*)actual;
-    a.p_stride = pred_stride, a.a_stride = actual_stride, a.n_case = n_case, a.plane = plane;
+    a.p = (const unsigned char*)P.p, a.a = (const unsigned char*)A.p;
+    a.p_stride = P.stride, a.a_stride = A.stride, a.n_case = n_case, a.plane = plane;
     a.chunk = chunk, a.n_chunk = n_chunk;
     a.shift = shift, a.shifts = shifts;
     a.out = n_chunk > 1 ? (double*)workspace : sums;
     const int64_t n_tile = pixel_tiles(plane);
     if (n_tile > 0x7fffffffLL) return fail(CAE_ERR_ARG, "cae_pixel_sums: plane too large");
     const dim3 grid((unsigned)n_tile, (unsigned)(n_chunk < 65535 ? n_chunk : 65535));     // one wave per workgroup
-    switch (pred_kind) {
-    case CAE_ELEM_F32: launch_pixel_sums_a<0>(actual_kind, grid, s, a); break;
-    case CAE_ELEM_F32_BE: launch_pixel_sums_a<1>(actual_kind, grid, s, a); break;
-    case CAE_ELEM_F64: launch_pixel_sums_a<2>(actual_kind, grid, s, a); break;
-    default: launch_pixel_sums_a<3>(actual_kind, grid, s, a); break;
-    }
+    with_kind(P.kind, [&](auto KP) {
+        with_kind(A.kind, [&](auto KA) {
+            constexpr int kp = decltype(KP)::value, ka = decltype(KA)::value;
+            if (a.shifts) hipLaunchKernelGGL((k_pixel_sums<kp, ka, true>), grid, dim3(64), 0, s, a);
+            else hipLaunchKernelGGL((k_pixel_sums<kp, ka, false>), grid, dim3(64), 0, s, a);
+        });
+    });
     HIP_TRY(hipGetLastError());
     if (n_chunk > 1) {
         const int64_t n = PS_SUMS * plane;
-        int64_t fb = (n + 255) / 256;
-        if (fb > 8192) fb = 8192;
-        hipLaunchKernelGGL(k_pixel_fold, dim3((unsigned)fb), dim3(256), 0, s, (const double*)workspace, (long long)n_chunk,
-                           (long long)n, sums);
+        hipLaunchKernelGGL(k_pixel_fold, dim3((unsigned)ceil_capped(n, 256, 8192)), dim3(256), 0, s, (const double*)workspace,
+                           (long long)n_chunk, (long long)n, sums);
         HIP_TRY(hipGetLastError());
     }
     return CAE_OK;
@@ -555,7 +497,7 @@ static int pixel_sums_run(const void* pred, int pred_kind, int64_t pred_stride, 
 int cae_pixel_sums(const void* pred, int pred_kind, int64_t pred_stride, const void* actual, int actual_kind,
                    int64_t actual_stride, int64_t n_case, int64_t plane, double shift, int64_t case_chunk, double* sums,
                    void* workspace, int64_t workspace_bytes, void* hip_stream) {
-    return pixel_sums_run(pred, pred_kind, pred_stride, actual, actual_kind, actual_stride, n_case, plane, shift, nullptr,
+    return pixel_sums_run({pred, pred_kind, pred_stride}, {actual, actual_kind, actual_stride}, n_case, plane, shift, nullptr,
                           case_chunk, sums, workspace, workspace_bytes, hip_stream);
 }
 
@@ -564,7 +506,7 @@ int cae_pixel_sums_about(const void* pred, int pred_kind, int64_t pred_stride, c
                          double* sums, void* workspace, int64_t workspace_bytes, void* hip_stream) {
     if (plane > 0 && n_case > 0 && (!shifts || ((uintptr_t)shifts & 7)))
         return fail(CAE_ERR_ARG, "cae_pixel_sums_about: shifts_dev must be an 8-byte aligned pointer");
-    return pixel_sums_run(pred, pred_kind, pred_stride, actual, actual_kind, actual_stride, n_case, plane, 0.0,
+    return pixel_sums_run({pred, pred_kind, pred_stride}, {actual, actual_kind, actual_stride}, n_case, plane, 0.0,
                           n_case > 0 ? shifts : nullptr, case_chunk, sums, workspace, workspace_bytes, hip_stream);
 }
 
@@ -616,20 +558,19 @@ int cae_case_spectra(const void* pred, int pred_kind, int64_t pred_stride, const
                      int64_t actual_stride, int64_t n_case, int64_t h, int64_t w, const double* wy, const double* wx,
                      const int32_t* bin, int64_t n_bin, double* sums, int32_t* counted, void* workspace,
                      int64_t workspace_bytes, void* hip_stream) {
-    auto elem_bytes = [](int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; };
-    auto known = [](int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; };
-    if (!known(pred_kind) || !known(actual_kind) || !spectra_sizes_ok(n_case, h, w, n_bin))
+    const CaseOperand P{pred, pred_kind, pred_stride}, A{actual, actual_kind, actual_stride};
+    if (!known(P) || !known(A) || !spectra_sizes_ok(n_case, h, w, n_bin))
         return fail(CAE_ERR_ARG, "cae_case_spectra: bad argument (CAE_ELEM_* kinds, n_case >= 0, 1 <= h, w <= %d, n_bin >= 1)", SP_MAX_SIDE);
     if (n_case == 0) return CAE_OK;
     const int64_t plane = h * w;
-    if (!pred || !actual || !wy || !wx || !bin || !sums || !counted || !workspace)
+    if (!P.p || !A.p || !wy || !wx || !bin || !sums || !counted || !workspace)
         return fail(CAE_ERR_ARG, "cae_case_spectra: null pointer");
-    if (pred_stride < plane || actual_stride < plane)
+    if (shorter(P, plane) || shorter(A, plane))
         return fail(CAE_ERR_ARG, "cae_case_spectra: a case stride is shorter than the plane");
-    if ((__int128)(n_case - 1) * pred_stride + plane > ((__int128)1 << 60) || (__int128)(n_case - 1) * actual_stride + plane > ((__int128)1 << 60))
+    if (reaches(P, n_case, plane) || reaches(A, n_case, plane))
         return fail(CAE_ERR_ARG, "cae_case_spectra: an operand reaches 2^60 elements from its pointer");
-    if (((uintptr_t)pred % elem_bytes(pred_kind)) || ((uintptr_t)actual % elem_bytes(actual_kind)) || ((uintptr_t)wy & 7) ||
-        ((uintptr_t)wx & 7) || ((uintptr_t)bin & 3) || ((uintptr_t)sums & 7) || ((uintptr_t)counted & 3) || ((uintptr_t)workspace & 15))
+    if (misaligned(P) || misaligned(A) || ((uintptr_t)wy & 7) || ((uintptr_t)wx & 7) || ((uintptr_t)bin & 3) ||
+        ((uintptr_t)sums & 7) || ((uintptr_t)counted & 3) || ((uintptr_t)workspace & 15))
         return fail(CAE_ERR_ARG, "cae_case_spectra: pointers must be aligned to their element size, the workspace to 16 bytes");
     const int64_t need = cae_case_spectra_workspace_bytes(n_case, h, w, n_bin);
     if (workspace_bytes < need)
@@ -662,10 +603,8 @@ int cae_case_spectra(const void* pred, int pred_kind, int64_t pred_stride, const
     default: launch_case_spectra<1>(grid, lds, s, a); break;
     }
     HIP_TRY(hipGetLastError());
-    int64_t fb = (n_case * n_bin * 4 + 255) / 256;
-    if (fb > 8192) fb = 8192;
-    hipLaunchKernelGGL(k_spectra_fold, dim3((unsigned)fb), dim3(256), 0, s, (const double*)a.part, (long long)n_case, (int)n_band,
-                       (int)n_bin, sums);
+    hipLaunchKernelGGL(k_spectra_fold, dim3((unsigned)ceil_capped(n_case * n_bin * 4, 256, 8192)), dim3(256), 0, s,
+                       (const double*)a.part, (long long)n_case, (int)n_band, (int)n_bin, sums);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
@@ -711,21 +650,19 @@ int64_t cae_case_ssim_workspace_bytes(int64_t n_case, int64_t h, int64_t w, int 
 int cae_case_ssim(const void* pred, int pred_kind, int64_t pred_stride, const void* actual, int actual_kind,
                   int64_t actual_stride, int64_t n_case, int64_t h, int64_t w, int n_scale, double shift, double scale,
                   const double* window, double* sums, void* workspace, int64_t workspace_bytes, void* hip_stream) {
-    auto elem_bytes = [](int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; };
-    auto known = [](int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; };
-    if (!known(pred_kind) || !known(actual_kind) || !ssim_sizes_ok(n_case, h, w, n_scale))
+    const CaseOperand P{pred, pred_kind, pred_stride}, A{actual, actual_kind, actual_stride};
+    if (!known(P) || !known(A) || !ssim_sizes_ok(n_case, h, w, n_scale))
         return fail(CAE_ERR_ARG, "cae_case_ssim: bad argument (CAE_ELEM_* kinds, n_case >= 0, 1 <= h, w <= %d, 1 <= n_scale <= %d)",
                     SS_MAX_SIDE, SS_SCALES);
     if (!(shift - shift == 0.0) || !(scale - scale == 0.0)) return fail(CAE_ERR_ARG, "cae_case_ssim: shift and scale must be finite");
     if (n_case == 0) return CAE_OK;
     const int64_t plane = h * w;
-    if (!pred || !actual || !window || !sums) return fail(CAE_ERR_ARG, "cae_case_ssim: null pointer");
-    if (pred_stride < plane || actual_stride < plane)
+    if (!P.p || !A.p || !window || !sums) return fail(CAE_ERR_ARG, "cae_case_ssim: null pointer");
+    if (shorter(P, plane) || shorter(A, plane))
         return fail(CAE_ERR_ARG, "cae_case_ssim: a case stride is shorter than the plane");
-    if ((__int128)(n_case - 1) * pred_stride + plane > ((__int128)1 << 60) || (__int128)(n_case - 1) * actual_stride + plane > ((__int128)1 << 60))
+    if (reaches(P, n_case, plane) || reaches(A, n_case, plane))
         return fail(CAE_ERR_ARG, "cae_case_ssim: an operand reaches 2^60 elements from its pointer");
-    if (((uintptr_t)pred % elem_bytes(pred_kind)) || ((uintptr_t)actual % elem_bytes(actual_kind)) || ((uintptr_t)sums & 7) ||
-        ((uintptr_t)workspace & 7))
+    if (misaligned(P) || misaligned(A) || ((uintptr_t)sums & 7) || ((uintptr_t)workspace & 7))
         return fail(CAE_ERR_ARG, "cae_case_ssim: pointers must be aligned to their element size, the workspace to 8 bytes");
     const int64_t need = cae_case_ssim_workspace_bytes(n_case, h, w, n_scale);
     if (need > 0 && (!workspace || workspace_bytes < need))
@@ -753,10 +690,9 @@ int cae_case_ssim(const void* pred, int pred_kind, int64_t pred_stride, const vo
         const int64_t per = (int64_t)d.h * d.w;
         d.x = (const unsigned char*)ws, d.y = (const unsigned char*)(ws + per);
         d.x_stride = d.y_stride = 2 * per, d.xk = d.yk = CAE_ELEM_F64;
-        int64_t pb = (n_case * per + 255) / 256;
-        if (pb > 65536) pb = 65536;
-        hipLaunchKernelGGL(k_ssim_pool, dim3((unsigned)pb), dim3(256), 0, s, c.x, c.xk, (long long)c.x_stride, c.y, c.yk,
-                           (long long)c.y_stride, (long long)n_case, c.h, c.w, k == 0 ? shift : 0.0, k == 0 ? scale : 1.0, ws);
+        hipLaunchKernelGGL(k_ssim_pool, dim3((unsigned)ceil_capped(n_case * per, 256, 65536)), dim3(256), 0, s, c.x, c.xk,
+                           (long long)c.x_stride, c.y, c.yk, (long long)c.y_stride, (long long)n_case, c.h, c.w,
+                           k == 0 ? shift : 0.0, k == 0 ? scale : 1.0, ws);
         HIP_TRY(hipGetLastError());
         ws += n_case * 2 * per;
     }
@@ -764,9 +700,7 @@ int cae_case_ssim(const void* pred, int pred_kind, int64_t pred_stride, const vo
         hipLaunchKernelGGL(k_case_ssim, dim3((unsigned)((a.items + 3) / 4)), dim3(256), 0, s, a);
         HIP_TRY(hipGetLastError());
     }
-    int64_t fb = (n_case * n_scale * 3 + 255) / 256;
-    if (fb > 4096) fb = 4096;
-    hipLaunchKernelGGL(k_ssim_fold, dim3((unsigned)fb), dim3(256), 0, s, a, sums);
+    hipLaunchKernelGGL(k_ssim_fold, dim3((unsigned)ceil_capped(n_case * n_scale * 3, 256, 4096)), dim3(256), 0, s, a, sums);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
@@ -792,24 +726,21 @@ int cae_case_baseline(const void* low, int low_kind, int64_t low_stride, int64_t
                       int pred_kind, int64_t pred_stride, const void* actual, int actual_kind, int64_t actual_stride,
                       int64_t n_case, int64_t h_out, int64_t w_out, int mode, double* sums, double* field, void* workspace,
                       int64_t workspace_bytes, void* hip_stream) {
-    auto elem_bytes = [](int kind) { return kind == CAE_ELEM_F32 || kind == CAE_ELEM_F32_BE ? 4 : 8; };
-    auto known = [](int kind) { return kind >= CAE_ELEM_F32 && kind <= CAE_ELEM_F64_BE; };
-    if (!known(low_kind) || !known(actual_kind) || (pred && !known(pred_kind)) || mode < CAE_INTERP_NEAREST ||
+    const CaseOperand L{low, low_kind, low_stride}, P{pred, pred_kind, pred_stride}, A{actual, actual_kind, actual_stride};
+    if (!known(L) || !known(A) || (P.p && !known(P)) || mode < CAE_INTERP_NEAREST ||
         mode > CAE_INTERP_BICUBIC || h_in < 1 || h_in > BL_MAX_SIDE || w_in < 1 || w_in > BL_MAX_SIDE ||
         !baseline_sizes_ok(n_case, h_out, w_out))
         return fail(CAE_ERR_ARG, "cae_case_baseline: bad argument (CAE_ELEM_* kinds, a CAE_INTERP_* mode, n_case >= 0, sides of 1 to 2^30)");
-    if (low_stride < 0 || actual_stride < 0 || (pred && pred_stride < 0)) return fail(CAE_ERR_ARG, "cae_case_baseline: negative stride");
+    if (L.stride < 0 || A.stride < 0 || (P.p && P.stride < 0)) return fail(CAE_ERR_ARG, "cae_case_baseline: negative stride");
     if (n_case == 0) return CAE_OK;
     const int64_t plane_in = h_in * w_in, plane = h_out * w_out;
-    if (!low || !actual || !sums) return fail(CAE_ERR_ARG, "cae_case_baseline: null pointer");
-    if (low_stride < plane_in || actual_stride < plane || (pred && pred_stride < plane))
+    if (!L.p || !A.p || !sums) return fail(CAE_ERR_ARG, "cae_case_baseline: null pointer");
+    if (shorter(L, plane_in) || shorter(A, plane) || (P.p && shorter(P, plane)))
         return fail(CAE_ERR_ARG, "cae_case_baseline: a case stride is shorter than the plane");
-    const __int128 limit = (__int128)1 << 60;
-    if ((__int128)(n_case - 1) * low_stride + plane_in > limit || (__int128)(n_case - 1) * actual_stride + plane > limit ||
-        (pred && (__int128)(n_case - 1) * pred_stride + plane > limit) || (field && (__int128)n_case * plane > limit))
+    if (reaches(L, n_case, plane_in) || reaches(A, n_case, plane) || (P.p && reaches(P, n_case, plane)) ||
+        (field && (__int128)n_case * plane > ((__int128)1 << 60)))
         return fail(CAE_ERR_ARG, "cae_case_baseline: an operand reaches 2^60 elements from its pointer");
-    if (((uintptr_t)low % elem_bytes(low_kind)) || ((uintptr_t)actual % elem_bytes(actual_kind)) ||
-        (pred && ((uintptr_t)pred % elem_bytes(pred_kind))) || ((uintptr_t)sums & 7) || ((uintptr_t)field & 7) ||
+    if (misaligned(L) || misaligned(A) || (P.p && misaligned(P)) || ((uintptr_t)sums & 7) || ((uintptr_t)field & 7) ||
         ((uintptr_t)workspace & 7))
         return fail(CAE_ERR_ARG, "cae_case_baseline: pointers must be aligned to their element size, the workspace to 8 bytes");
     const int64_t need = cae_case_baseline_workspace_bytes(n_case, h_out, w_out);
@@ -841,10 +772,8 @@ int cae_case_baseline(const void* low, int low_kind, int64_t low_stride, int64_t
     }
 #undef BL_LAUNCH
     HIP_TRY(hipGetLastError());
-    int64_t fb = (n_case * BL_SUMS + 255) / 256;
-    if (fb > 4096) fb = 4096;
-    hipLaunchKernelGGL(k_baseline_fold, dim3((unsigned)fb), dim3(256), 0, s, (const double*)workspace, (long long)n_case,
-                       (int)baseline_items(h_out, w_out), sums);
+    hipLaunchKernelGGL(k_baseline_fold, dim3((unsigned)ceil_capped(n_case * BL_SUMS, 256, 4096)), dim3(256), 0, s,
+                       (const double*)workspace, (long long)n_case, (int)baseline_items(h_out, w_out), sums);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
@@ -877,7 +806,7 @@ int cae_scene_gather(const cae_scene_geom* geom, const void* src, int src_kind, 
                      int enable, int32_t* invalid, void* hip_stream) {
     const int rc = scene_geom_check("cae_scene_gather", geom, false);
     if (rc != CAE_OK) return rc;
-    if (src_kind < CAE_ELEM_F32 || src_kind > CAE_ELEM_F64_BE || n_t < 0 || c_src < 1 || c_off < 0 || c_off > c_dst - c_src ||
+    if (!kind_known(src_kind) || n_t < 0 || c_src < 1 || c_off < 0 || c_off > c_dst - c_src ||
         t0 < 0 || n_t_call < 0 || t0 > n_t - n_t_call || ky0 < 0 || n_ky < 0)
         return fail(CAE_ERR_ARG, "cae_scene_gather: bad argument (a CAE_ELEM_* kind, the time range inside the variable, the channels inside the batch)");
     const int64_t n_y = scene_tiles_along(geom->Y, geom->h, geom->oy), n_x = scene_tiles_along(geom->X, geom->w, geom->ox);
@@ -885,8 +814,7 @@ int cae_scene_gather(const cae_scene_geom* geom, const void* src, int src_kind, 
                                       (long long)(ky0 + n_ky), (long long)n_y);
     if (n_t_call == 0 || n_ky == 0) return CAE_OK;
     if (!src || !dst || !invalid) return fail(CAE_ERR_ARG, "cae_scene_gather: null pointer");
-    const int es = src_kind == CAE_ELEM_F32 || src_kind == CAE_ELEM_F32_BE ? 4 : 8;
-    if (((uintptr_t)src % es) || ((uintptr_t)dst & 3) || ((uintptr_t)invalid & 3))
+    if (((uintptr_t)src % elem_bytes(src_kind)) || ((uintptr_t)dst & 3) || ((uintptr_t)invalid & 3))
         return fail(CAE_ERR_ARG, "cae_scene_gather: pointers must be aligned to their element size");
     const __int128 per = (__int128)c_src * geom->h * geom->w, tiles = (__int128)n_t_call * n_ky * n_x;
     if (per > 0x7fffffffLL || (__int128)c_dst * geom->h * geom->w > 0x7fffffffLL || tiles > 0x7fffffffLL ||
@@ -898,16 +826,9 @@ int cae_scene_gather(const cae_scene_geom* geom, const void* src, int src_kind, 
     a.stride_y = geom->h - geom->oy, a.stride_x = geom->w - geom->ox, a.n_x = n_x;
     a.t0 = t0, a.ky0 = ky0, a.n_ky = n_ky, a.total = (long long)(tiles * per);
     a.dst = dst, a.c_dst = c_dst, a.c_off = c_off, a.vmin = vmin, a.range = range, a.enable = enable, a.invalid = (int*)invalid;
-    int64_t blocks = (a.total + 256 * 4 - 1) / (256 * 4);
-    if (blocks > 8192) blocks = 8192;
-    const dim3 grid((unsigned)blocks);
+    const dim3 grid((unsigned)ceil_capped(a.total, 256 * 4, 8192));
     hipStream_t s = (hipStream_t)hip_stream;
-    switch (src_kind) {
-    case CAE_ELEM_F32: hipLaunchKernelGGL((k_scene_gather<0>), grid, dim3(256), 0, s, a); break;
-    case CAE_ELEM_F32_BE: hipLaunchKernelGGL((k_scene_gather<1>), grid, dim3(256), 0, s, a); break;
-    case CAE_ELEM_F64: hipLaunchKernelGGL((k_scene_gather<2>), grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((k_scene_gather<3>), grid, dim3(256), 0, s, a); break;
-    }
+    with_kind(src_kind, [&](auto KS) { hipLaunchKernelGGL((k_scene_gather<decltype(KS)::value>), grid, dim3(256), 0, s, a); });
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }

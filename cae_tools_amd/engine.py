@@ -5,8 +5,7 @@ running-stat arenas and the workspace, a side stream, and (in dp.py) torch.distr
 FLOP of the model runs in the HIP kernels behind include/cae_hip.h.
 """
 import ctypes as C
-import math
-from collections import OrderedDict, namedtuple
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -462,699 +461,8 @@ class HipEngine(EnginePlan):
         return buf[:n]
 
 
-# ---- stateless loader kernels ------------------------------------------------------------------
 
-def scan_f32(x):
-    """(nan_count, nanmin, nanmax) of an fp32 CUDA tensor as python numbers (ds_dataset.py:43-58)"""
-    lib = _lib.load()
-    x = x.contiguous()
-    out = (C.c_double * 3)()
-    torch.cuda.synchronize(x.device)
-    check(lib.cae_scan_f32(x.data_ptr(), x.numel(), None, out))
-    return int(out[0]), float(out[1]), float(out[2])
-
-
-def normalise_pack(src, dst, c_off, vmin, vmax, enable=True, dst_rows=None):
-    """dst[row(i), c_off:c_off+Cv] = normalise(src[i]) on the device (ds_dataset.py:99-113,137-147).
-    The range is formed in fp64 from python floats and rounded to fp32, as numpy does.
-    dst_rows: int32 CUDA tensor, row(i) = dst_rows[i] (inverse_permutation() of a frozen sample order: the samples land in
-    batch order, which is the DataLoader + collate stacking of conv_ae_model.py:291-292,315-325); None: row(i) = i."""
-    lib = _lib.load()
-    (n, c_src) = (int(src.shape[0]), int(src.shape[1]))
-    hw = int(np.prod(src.shape[2:]))
-    rng = float(vmax) - float(vmin)
-    if dst_rows is not None:
-        if dst_rows.dtype != torch.int32 or dst_rows.device != src.device or dst_rows.numel() != n or int(dst.shape[0]) != n:
-            raise CaeError("normalise_pack: dst_rows must be an int32 tensor of one entry per sample on the data's device")
-    with torch.cuda.device(src.device):
-        check(lib.cae_normalise_pack_rows(src.data_ptr(), n, c_src, hw, dst.data_ptr(), int(dst.shape[1]), int(c_off),
-                                          C.c_float(float(np.float32(vmin))), C.c_float(float(np.float32(rng))),
-                                          1 if enable else 0, dst_rows.data_ptr() if dst_rows is not None else None,
-                                          torch.cuda.current_stream(src.device).cuda_stream))
-
-
-def inverse_permutation(order, device):
-    """int32 CUDA tensor inv with inv[order[i]] = i (cae_invert_permutation): where each sample goes when the data set is
-    laid out in the frozen order `order` (host sequence of sample indices, every index exactly once)."""
-    lib = _lib.load()
-    order = np.ascontiguousarray(np.asarray(order, dtype=np.int32))
-    n = int(order.size)
-    if n < 1 or not np.array_equal(np.sort(order), np.arange(n, dtype=np.int32)):
-        raise CaeError("inverse_permutation: `order` must hold every sample index 0..n-1 exactly once")
-    perm = torch.from_numpy(order).to(device)
-    inv = torch.empty(n, dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        check(lib.cae_invert_permutation(perm.data_ptr(), n, inv.data_ptr(), torch.cuda.current_stream(device).cuda_stream))
-    torch.cuda.synchronize(device)
-    return inv
-
-
-def denormalise_f64(y, vmin, vmax):
-    """float64 CUDA tensor min + y*(max-min) (ds_dataset.py:131-135 on base_model.py:123's fp64 array)"""
-    lib = _lib.load()
-    y = y.contiguous()
-    out = torch.empty(y.shape, dtype=torch.float64, device=y.device)
-    check(lib.cae_denormalise_f64(y.data_ptr(), y.numel(), float(vmin), float(vmax) - float(vmin), out.data_ptr(),
-                                  torch.cuda.current_stream(y.device).cuda_stream))
-    return out
-
-
-def metric_sums(y, actual, mask, vmin, vmax):
-    """cae_metric_sums: per-instance fp64 sums (n, 8) of the denormalised scores `vmin + y*(vmax-vmin)` against
-    `actual` over the pixels where `mask` (same shape, or None = all) is non-zero.  CUDA fp32 tensors (n, ...)."""
-    lib = _lib.load()
-    y, actual = y.contiguous(), actual.contiguous()
-    if y.shape != actual.shape:
-        raise ValueError("The shapes of 'actual' and 'estimates' must match.")
-    n = int(y.shape[0])
-    elems = y.numel() // max(n, 1)
-    if mask is not None:
-        mask = mask.to(device=y.device, dtype=torch.float32).expand(y.shape).contiguous()
-    out = torch.empty((n, 8), dtype=torch.float64, device=y.device)
-    stream = torch.cuda.current_stream(y.device).cuda_stream
-    for lo in range(0, n, 65535):
-        hi = min(n, lo + 65535)
-        check(lib.cae_metric_sums(y[lo:hi].data_ptr(), actual[lo:hi].data_ptr(),
-                                  mask[lo:hi].data_ptr() if mask is not None else None, hi - lo, elems,
-                                  float(vmin), float(vmax) - float(vmin), out[lo:hi].data_ptr(), stream))
-    return out
-
-
-_STAGE_BYTES = 64 << 20
-
-
-def _upload_raw(arr, device):
-    """the bytes of a C-contiguous numpy array, unchanged, in a new uint8 CUDA tensor: copied through a pinned staging
-    buffer in pieces of at most _STAGE_BYTES"""
-    src = arr.reshape(-1).view(np.uint8)
-    nbytes = src.size
-    out = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    stage = torch.empty(min(nbytes, _STAGE_BYTES), dtype=torch.uint8).pin_memory()
-    stage_np = stage.numpy()
-    for lo in range(0, nbytes, _STAGE_BYTES):
-        hi = min(nbytes, lo + _STAGE_BYTES)
-        stage_np[:hi - lo] = src[lo:hi]
-        out[lo:hi].copy_(stage[:hi - lo], non_blocking=False)
-    return out
-
-
-def _is_big_endian_slab(arr, dtype):
-    return arr.dtype == np.dtype(dtype) and arr.dtype.byteorder == ">" and arr.flags.c_contiguous and arr.size > 0
-
-
-def upload_f32(arr, device):
-    """numpy (N,...) array -> fp32 CUDA tensor.  A C-contiguous big-endian float32 array (a NetCDF-3 slab, usually a
-    view of the file mapping) is copied as raw bytes through a pinned staging buffer and byte-swapped on the GPU
-    (cae_bswap32); anything else is converted by numpy first."""
-    arr = np.asarray(arr)
-    if not _is_big_endian_slab(arr, ">f4"):
-        return torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).to(device)
-    lib = _lib.load()
-    words = _upload_raw(arr, device).view(torch.int32)
-    check(lib.cae_bswap32(words.data_ptr(), words.numel(), torch.cuda.current_stream(device).cuda_stream))
-    return words.view(torch.float32).view(arr.shape)
-
-
-_TORCH_KINDS = {torch.float32: _lib.ELEM_F32, torch.float64: _lib.ELEM_F64}
-
-
-class DeviceOperand(tuple):
-    """(device tensor kept alive, element kind, shape, case stride in elements): what _measure_operand returns, as a
-    type of its own so that case_measures / case_range / render_cases take it again without another upload"""
-
-    tensor = property(lambda self: self[0])
-    shape = property(lambda self: self[2])
-
-
-def device_operand(x, device=None):
-    """x (numpy array, raw NetCDF-3 slab or CUDA tensor) on the device, ready for the case kernels"""
-    return DeviceOperand(_measure_operand(x, _case_device(device, x)))
-
-
-def _measure_operand(x, device):
-    """(device tensor kept alive, element kind, shape, case stride in elements) of one case_measures operand.  A CUDA
-    tensor is used in place; a C-contiguous big-endian >f4 / >f8 numpy array (a NetCDF-3 slab) goes up as its raw
-    bytes and is swapped inside the kernel; any other array is uploaded in its native fp32 / fp64 form.  An operand
-    made earlier (device_operand) is handed through, so one upload serves several calls."""
-    if isinstance(x, DeviceOperand):
-        return x
-    if isinstance(x, torch.Tensor):
-        if not x.is_cuda:
-            x = x.numpy()
-        else:
-            if x.dtype not in _TORCH_KINDS:
-                x = x.to(torch.float64)
-            x = x.contiguous()
-            return x, _TORCH_KINDS[x.dtype], tuple(x.shape), int(x.stride(0))
-    arr = np.asarray(x)
-    for (dtype, kind) in ((">f4", _lib.ELEM_F32_BE), (">f8", _lib.ELEM_F64_BE)):
-        if _is_big_endian_slab(arr, dtype):
-            raw = _upload_raw(arr, device)
-            return raw, kind, arr.shape, int(np.prod(arr.shape[1:]))
-    if arr.dtype.newbyteorder("=") != np.dtype(np.float32):
-        arr = arr.astype(np.float64)
-    t = torch.from_numpy(np.ascontiguousarray(arr, dtype=arr.dtype.newbyteorder("="))).to(device)
-    return t, _TORCH_KINDS[t.dtype], tuple(t.shape), int(np.prod(t.shape[1:]))
-
-
-def case_measures(pred, actual, device=None):
-    """Per-case (mae, mse) of channel 0, the reference's ModelEvaluator.compute_measure (model_evaluator.py:87-95)
-    for every case at once: mean |p - a| and mean (p - a)^2 over [i, 0, :, :] in fp64.  pred / actual: (N, C, H, W) numpy
-    arrays or CUDA tensors (fp32 or fp64; C may differ).  One streaming pass of cae_case_measures.  Returns an (N, 2)
-    float64 numpy array."""
-    device = _case_device(device, pred, actual)
-    (p, pk, pshape, pstride) = _measure_operand(pred, device)
-    (a, ak, ashape, astride) = _measure_operand(actual, device)
-    if len(pshape) != 4 or len(ashape) != 4:
-        raise ValueError(f"case_measures: (N, C, H, W) arrays expected, got {pshape} and {ashape}")
-    if pshape[0] != ashape[0] or pshape[2:] != ashape[2:]:
-        raise ValueError(f"case_measures: prediction {pshape} and target {ashape} do not match")
-    (n, plane) = (int(pshape[0]), int(pshape[2] * pshape[3]))
-    out = torch.empty((n, 2), dtype=torch.float64, device=device)
-    if n == 0:
-        return np.zeros((0, 2), dtype=np.float64)
-    if plane == 0:
-        return np.full((n, 2), np.nan)      # np.mean of an empty plane
-    lib = _lib.load()
-    need = int(lib.cae_case_measures_workspace_bytes(n, plane))
-    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        check(lib.cae_case_measures(p.data_ptr(), pk, pstride, a.data_ptr(), ak, astride, n, plane, out.data_ptr(),
-                                    ws.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream))
-        sums = out.cpu().numpy()
-    return sums / float(plane)
-
-
-def pixel_sums(pred, actual, shift=0.0, case_chunk=0, device=None):
-    """The nine per-pixel sums of channel 0 over the cases (cae_pixel_sums, include/cae_hip.h): a (9, H, W) float64 numpy
-    array {n, S d, S|d|, S d^2, S a', S p', S a'^2, S p'^2, S a'p'} with d = p - a, a' = a - shift, p' = p - shift over the
-    cases whose two values at the pixel are finite.  Operands as case_measures takes them; case_chunk 0 leaves the cut
-    of the cases to the library.  shift: one number, or a (2, H, W) array of per-pixel shifts for a and p
-    (cae_pixel_sums_about).  utils/skill_maps.maps_from_sums turns the sums into the skill maps."""
-    device = _case_device(device, pred, actual)
-    (p, pk, pshape, pstride) = _measure_operand(pred, device)
-    (a, ak, ashape, astride) = _measure_operand(actual, device)
-    if len(pshape) != 4 or len(ashape) != 4:
-        raise ValueError(f"pixel_sums: (N, C, H, W) arrays expected, got {pshape} and {ashape}")
-    if pshape[0] != ashape[0] or pshape[2:] != ashape[2:]:
-        raise ValueError(f"pixel_sums: prediction {pshape} and target {ashape} do not match")
-    (n, h, w) = (int(pshape[0]), int(pshape[2]), int(pshape[3]))
-    plane = h * w
-    about = np.ndim(shift) != 0
-    if about and np.shape(shift) != (2, h, w):
-        raise ValueError(f"pixel_sums: per-pixel shifts of shape (2, {h}, {w}) expected, got {np.shape(shift)}")
-    if n == 0 or plane == 0:
-        return np.zeros((9, h, w), dtype=np.float64)
-    lib = _lib.load()
-    need = int(lib.cae_pixel_sums_workspace_bytes(n, plane, int(case_chunk)))
-    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
-    out = torch.empty((9, h, w), dtype=torch.float64, device=device)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        if about:
-            shifts = torch.from_numpy(np.ascontiguousarray(shift, dtype=np.float64)).to(device)
-            check(lib.cae_pixel_sums_about(p.data_ptr(), pk, pstride, a.data_ptr(), ak, astride, n, plane, shifts.data_ptr(),
-                                           int(case_chunk), out.data_ptr(), ws.data_ptr(), need, stream))
-        else:
-            check(lib.cae_pixel_sums(p.data_ptr(), pk, pstride, a.data_ptr(), ak, astride, n, plane, float(shift),
-                                     int(case_chunk), out.data_ptr(), ws.data_ptr(), need, stream))
-        return out.cpu().numpy()
-
-
-_SPECTRA_CASES = 512         # cases per cae_case_spectra call: bounds the workspace; a case's sums do not depend on the cut
-
-
-def case_spectra(pred, actual, device=None):
-    """The four binned spectral sums of channel 0 per case (cae_case_spectra, include/cae_hip.h): (sums (N, n_bin, 4) float64
-    {S w|P|^2, S w|A|^2, S w Re(P conj A), S w|D|^2}, counted (N,) bool) for the Hann-windowed, mean-free prediction P,
-    target A and error D = (p - a) over the radial bins of utils/spectra.bin_table(H, W).  A case with a value that is
-    not finite is not counted and has zero sums.  Operands as pixel_sums takes them.
-    utils/spectra.curves_from_sums turns the sums into the spectra, their ratio, the coherence and the error share."""
-    from .utils import spectra
-    device = _case_device(device, pred, actual)
-    (p, pk, pshape, pstride) = _measure_operand(pred, device)
-    (a, ak, ashape, astride) = _measure_operand(actual, device)
-    if len(pshape) != 4 or len(ashape) != 4:
-        raise ValueError(f"case_spectra: (N, C, H, W) arrays expected, got {pshape} and {ashape}")
-    if pshape[0] != ashape[0] or pshape[2:] != ashape[2:]:
-        raise ValueError(f"case_spectra: prediction {pshape} and target {ashape} do not match")
-    (n, h, w) = (int(pshape[0]), int(pshape[2]), int(pshape[3]))
-    if not (1 <= h <= 2048 and 1 <= w <= 2048):
-        raise ValueError(f"case_spectra: planes of 1 to 2048 pixels a side expected, got {h} x {w}")
-    table = spectra.bin_table(h, w)
-    n_bin = spectra.bin_count(h, w)
-    if table.shape != (h, w // 2 + 1) or table.min() < -1 or table.max() >= n_bin:
-        raise ValueError("case_spectra: the bin table does not fit its bins")
-    if n == 0:
-        return np.zeros((0, n_bin, 4), dtype=np.float64), np.zeros(0, dtype=bool)
-    lib = _lib.load()
-    (pe, ae) = (4 if pk in (_lib.ELEM_F32, _lib.ELEM_F32_BE) else 8, 4 if ak in (_lib.ELEM_F32, _lib.ELEM_F32_BE) else 8)
-    sums = torch.empty((n, n_bin, 4), dtype=torch.float64, device=device)
-    counted = torch.empty(n, dtype=torch.int32, device=device)
-    wy = torch.from_numpy(spectra.window(h)).to(device)
-    wx = torch.from_numpy(spectra.window(w)).to(device)
-    bins = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)).to(device)
-    need = int(lib.cae_case_spectra_workspace_bytes(min(n, _SPECTRA_CASES), h, w, n_bin))
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        for lo in range(0, n, _SPECTRA_CASES):
-            g = min(n, lo + _SPECTRA_CASES) - lo
-            check(lib.cae_case_spectra(p.data_ptr() + lo * pstride * pe, pk, pstride, a.data_ptr() + lo * astride * ae, ak,
-                                       astride, g, h, w, wy.data_ptr(), wx.data_ptr(), bins.data_ptr(), n_bin,
-                                       sums[lo:].data_ptr(), counted[lo:].data_ptr(), ws.data_ptr(), need, stream))
-        return sums.cpu().numpy(), counted.cpu().numpy() != 0
-
-
-_SSIM_CASES = 256            # cases per cae_case_ssim call: bounds the workspace (the pooled planes); a case's sums do not depend on the cut
-
-
-def case_ssim(pred, actual, vmin, vmax, n_scale=None, device=None):
-    """The SSIM sums of channel 0 per case and scale (cae_case_ssim, include/cae_hip.h): an (N, n_scale, 3) float64 numpy
-    array {n, S ssim, S cs} over the counted 11 x 11 windows of scale s, for x = (p - vmin) * (1 / (vmax - vmin)) and y
-    likewise (data_range 1, the VAE loss's definition).  A window over a value that is not finite is left out, for that case
-    and scale only.  n_scale None: 5 where min(H, W) > 160 (MS-SSIM is defined), else 1.  Operands as case_spectra takes them.
-    utils/ssim.scores_from_sums turns the sums into ssim, ms_ssim and psnr."""
-    from .utils import ssim
-    device = _case_device(device, pred, actual)
-    (p, pk, pshape, pstride) = _measure_operand(pred, device)
-    (a, ak, ashape, astride) = _measure_operand(actual, device)
-    if len(pshape) != 4 or len(ashape) != 4:
-        raise ValueError(f"case_ssim: (N, C, H, W) arrays expected, got {pshape} and {ashape}")
-    if pshape[0] != ashape[0] or pshape[2:] != ashape[2:]:
-        raise ValueError(f"case_ssim: prediction {pshape} and target {ashape} do not match")
-    (n, h, w) = (int(pshape[0]), int(pshape[2]), int(pshape[3]))
-    if not (1 <= h <= 16384 and 1 <= w <= 16384):
-        raise ValueError(f"case_ssim: planes of 1 to 16384 pixels a side expected, got {h} x {w}")
-    n_scale = ssim.default_scales(h, w) if n_scale is None else int(n_scale)
-    if not 1 <= n_scale <= ssim.MAX_SCALES:
-        raise ValueError(f"case_ssim: n_scale must be 1 to {ssim.MAX_SCALES}, got {n_scale}")
-    (shift, scale) = (float(vmin), 1.0 / (float(vmax) - float(vmin)) if float(vmax) != float(vmin) else math.inf)
-    if not (math.isfinite(shift) and math.isfinite(scale)):
-        raise ValueError(f"case_ssim: vmin and 1 / (vmax - vmin) must be finite, got vmin {vmin!r} and vmax {vmax!r}")
-    if n == 0:
-        return np.zeros((0, n_scale, 3), dtype=np.float64)
-    lib = _lib.load()
-    (pe, ae) = (4 if pk in (_lib.ELEM_F32, _lib.ELEM_F32_BE) else 8, 4 if ak in (_lib.ELEM_F32, _lib.ELEM_F32_BE) else 8)
-    sums = torch.empty((n, n_scale, 3), dtype=torch.float64, device=device)
-    win = (C.c_double * ssim.WIN_SIZE)(*ssim.window().tolist())
-    need = int(lib.cae_case_ssim_workspace_bytes(min(n, _SSIM_CASES), h, w, n_scale))
-    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        for lo in range(0, n, _SSIM_CASES):
-            g = min(n, lo + _SSIM_CASES) - lo
-            check(lib.cae_case_ssim(p.data_ptr() + lo * pstride * pe, pk, pstride, a.data_ptr() + lo * astride * ae, ak,
-                                    astride, g, h, w, n_scale, shift, scale, win, sums[lo:].data_ptr(), ws.data_ptr(), need,
-                                    stream))
-        return sums.cpu().numpy()
-
-
-_BASELINE_FIELD_BYTES = 256 << 20       # of fp64 field per cae_case_baseline call when the field is asked for
-
-
-def _elem_bytes(kind):
-    return 4 if kind in (_lib.ELEM_F32, _lib.ELEM_F32_BE) else 8
-
-
-def case_baseline(low, pred, actual, mode="bicubic", field=False, device=None):
-    """Skill against interpolating the input (cae_case_baseline, include/cae_hip.h): channel 0 of low (N, C, h, w) is
-    interpolated to the grid of actual (N, C, H, W) - mode "nearest", "bilinear" or "bicubic", the formulas of
-    torch.nn.functional.interpolate with align_corners=False - inside the kernel that compares it: an (N, 6) float64 numpy
-    array {n, S|b - a|, S(b - a)^2, S|p - a|, S(p - a)^2, n_won} per case over the pixels where a, p and every tap of b
-    are finite.  pred None: entries 3..5 are zero.  field=True returns (sums, b) with b the (N, H, W) float64 interpolated
-    field, NaN where a tap is not finite.  Operands as case_ssim takes them.  utils/baseline.scores_from_sums turns the
-    sums into baseline_mse, skill and win_fraction."""
-    from .utils import baseline
-    if mode not in baseline.MODES:
-        raise ValueError(f"case_baseline: mode must be one of {', '.join(baseline.MODES)}, got {mode!r}")
-    device = _case_device(device, low, pred, actual)
-    (lo_t, lk, lshape, lstride) = _measure_operand(low, device)
-    (a, ak, ashape, astride) = _measure_operand(actual, device)
-    if len(lshape) != 4 or len(ashape) != 4 or lshape[0] != ashape[0]:
-        raise ValueError(f"case_baseline: (N, C, h, w) and (N, C, H, W) arrays expected, got {lshape} and {ashape}")
-    (p, pk, pstride) = (None, 0, 0)
-    if pred is not None:
-        (p, pk, pshape, pstride) = _measure_operand(pred, device)
-        if len(pshape) != 4 or pshape[0] != ashape[0] or pshape[2:] != ashape[2:]:
-            raise ValueError(f"case_baseline: prediction {pshape} and target {ashape} do not match")
-    (n, h_in, w_in, h, w) = (int(ashape[0]), int(lshape[2]), int(lshape[3]), int(ashape[2]), int(ashape[3]))
-    if min(h_in, w_in, h, w) < 1:
-        raise ValueError(f"case_baseline: planes of at least one pixel expected, got {h_in} x {w_in} and {h} x {w}")
-    if n == 0:
-        empty = np.zeros((0, 6), dtype=np.float64)
-        return (empty, np.zeros((0, h, w), dtype=np.float64)) if field else empty
-    lib = _lib.load()
-    (le, pe, ae) = (_elem_bytes(lk), _elem_bytes(pk), _elem_bytes(ak))
-    group = max(1, min(n, _BASELINE_FIELD_BYTES // (8 * h * w))) if field else n
-    sums = torch.empty((n, 6), dtype=torch.float64, device=device)
-    need = int(lib.cae_case_baseline_workspace_bytes(group, h, w))
-    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
-    out = np.empty((n, h, w), dtype=np.float64) if field else None
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        for c0 in range(0, n, group):
-            g = min(n, c0 + group) - c0
-            b = torch.empty((g, h, w), dtype=torch.float64, device=device) if field else None
-            check(lib.cae_case_baseline(lo_t.data_ptr() + c0 * lstride * le, lk, lstride, h_in, w_in,
-                                        p.data_ptr() + c0 * pstride * pe if p is not None else None, pk, pstride,
-                                        a.data_ptr() + c0 * astride * ae, ak, astride, g, h, w, baseline.MODES[mode],
-                                        sums[c0:].data_ptr(), b.data_ptr() if field else None, ws.data_ptr(), need, stream))
-            if field:
-                out[c0:c0 + g] = b.cpu().numpy()
-        sums = sums.cpu().numpy()
-    return (sums, out) if field else sums
-
-
-def upsample(low, out_shape, mode="bicubic", device=None):
-    """Channel 0 of low (N, C, h, w) interpolated to out_shape = (H, W) as case_baseline does it: an (N, H, W) float64 numpy
-    array, NaN where a tap is not finite (the field output of cae_case_baseline against a target of zeros)."""
-    device = _case_device(device, low)
-    op = device_operand(low, device)
-    if len(op.shape) != 4:
-        raise ValueError(f"upsample: an (N, C, h, w) array expected, got {tuple(op.shape)}")
-    (h, w) = (int(out_shape[0]), int(out_shape[1]))
-    if min(h, w) < 1:
-        raise ValueError(f"upsample: an output of at least one pixel expected, got {h} x {w}")
-    zeros = torch.zeros((int(op.shape[0]), 1, h, w), dtype=torch.float32, device=device)
-    return case_baseline(op, None, zeros, mode=mode, field=True, device=device)[1]
-
-
-def ensemble_verify(draws, actual, vmin, vmax, layout="case", device=None):
-    """cae_ensemble_verify (include/cae_hip.h) on the K draws of every case at once: draws is a float32 numpy array or CUDA
-    tensor (N, K, H, W) or (N, K, C, H, W) for layout "case", (K, N, H, W) or (K, N, C, H, W) for layout "draw" - the
-    normalised decoder output, channel 0 is verified - and actual an (N, C, H, W) target in physical units as case_measures
-    takes it.  The members are vmin + y * (vmax - vmin).  Returns (case_sums (N, 5) float64 {n, S A, S B, S (mbar - a)^2,
-    S s^2}, rank_counts (K + 2,) int64); utils/ensemble_scores.scores_from_sums turns them into the scores."""
-    if layout not in ("case", "draw"):
-        raise ValueError(f"ensemble_verify: layout must be 'case' or 'draw', got {layout!r}")
-    device = _case_device(device, draws, actual)
-    if not isinstance(draws, torch.Tensor):
-        draws = torch.from_numpy(np.ascontiguousarray(draws, dtype=np.float32))
-    if draws.dtype != torch.float32 or draws.dim() not in (4, 5):
-        raise ValueError(f"ensemble_verify: float32 draws of 4 or 5 dimensions expected, got {draws.dtype} {tuple(draws.shape)}")
-    y = draws.to(device).contiguous()
-    (a, ak, ashape, astride) = _measure_operand(actual, device)
-    (n, k) = (int(y.shape[0]), int(y.shape[1])) if layout == "case" else (int(y.shape[1]), int(y.shape[0]))
-    if len(ashape) != 4 or ashape[0] != n or tuple(ashape[2:]) != tuple(y.shape[-2:]):
-        raise ValueError(f"ensemble_verify: draws {tuple(y.shape)} ({layout} major) and target {tuple(ashape)} do not match")
-    if not 2 <= k <= 64:
-        raise ValueError(f"ensemble_verify: 2 to 64 draws expected, got {k}")
-    plane = int(y.shape[-2] * y.shape[-1])
-    field = plane * (int(y.shape[2]) if y.dim() == 5 else 1)
-    (case_stride, draw_stride) = (k * field, field) if layout == "case" else (field, n * field)
-    sums = torch.zeros((n, 5), dtype=torch.float64, device=device)
-    ranks = torch.zeros(k + 2, dtype=torch.int64, device=device)
-    if n and plane:
-        lib = _lib.load()
-        need = int(lib.cae_ensemble_verify_workspace_bytes(n, plane, k))
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            check(lib.cae_ensemble_verify(y.data_ptr(), case_stride, draw_stride, a.data_ptr(), ak, astride, n, plane, k,
-                                          float(vmin), float(vmax) - float(vmin), sums.data_ptr(), ranks.data_ptr(),
-                                          ws.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream))
-    return sums.cpu().numpy(), ranks.cpu().numpy()
-
-
-def _case_device(device, *operands):
-    """the device the case kernels run on: the one given, else that of a device-resident operand, else the current one"""
-    if device is None:
-        for x in operands:
-            if isinstance(x, DeviceOperand):
-                x = x.tensor
-            if isinstance(x, torch.Tensor) and x.is_cuda:
-                return x.device
-        require_gpu()
-        device = torch.device("cuda", torch.cuda.current_device())
-    return torch.device(device)
-
-
-def _case_pair(name, arr, sub, device):
-    """(source operand, subtracted operand or None, N, H, W) of case_range / render_cases"""
-    src = _measure_operand(arr, device)
-    other = _measure_operand(sub, device) if sub is not None else None
-    shape = src[2]
-    if len(shape) != 4:
-        raise ValueError(f"{name}: an (N, C, H, W) array expected, got {tuple(shape)}")
-    if other is not None and (len(other[2]) != 4 or other[2][0] != shape[0] or tuple(other[2][2:]) != tuple(shape[2:])):
-        raise ValueError(f"{name}: {tuple(shape)} and the subtracted {tuple(other[2])} do not match")
-    return src, other, int(shape[0]), int(shape[2]), int(shape[3])
-
-
-def _sub_args(other):
-    return (other[0].data_ptr(), other[1], other[3]) if other is not None else (None, 0, 0)
-
-
-def case_range(arr, sub=None, device=None):
-    """(min, max, count) of the finite values of channel 0 of arr (N, C, H, W), or of arr - sub formed in fp64: what
-    np.nanmin / np.nanmax of the fp64 copy give where nothing is infinite, in one streaming pass of cae_case_range over
-    the array as stored.  Operands as case_measures takes them.  (inf, -inf, 0) when no value is finite."""
-    device = _case_device(device, arr, sub)
-    (src, other, n, h, w) = _case_pair("case_range", arr, sub, device)
-    if n * h * w == 0:
-        return float("inf"), float("-inf"), 0
-    lib = _lib.load()
-    need = int(lib.cae_case_range_workspace_bytes(n, h * w))
-    ws = torch.empty(need, dtype=torch.uint8, device=device)
-    out = torch.empty(3, dtype=torch.float64, device=device)
-    with torch.cuda.device(device):
-        check(lib.cae_case_range(src[0].data_ptr(), src[1], src[3], *_sub_args(other), n, h * w, out.data_ptr(),
-                                 ws.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream))
-        (lo, hi, count) = out.cpu().tolist()
-    return lo, hi, int(count)
-
-
-_RENDER_BYTES = 64 << 20
-
-
-def render_cases(arr, lo, hi, cases=None, sub=None, flip_y=False, device=None):
-    """Channel 0 of the selected cases of arr (N, C, H, W), or of arr - sub in fp64, as palette indices in PNG scanline
-    form (cae_render_cases, include/cae_hip.h): a (k, H, W + 1) uint8 numpy array whose rows start with the filter byte 0.
-    cases: case indices in any order, repeats allowed (None: all).  Rendered in groups of cases, so that at most about
-    _RENDER_BYTES of output are on the device and in pinned host memory at a time."""
-    device = _case_device(device, arr, sub)
-    (src, other, n, h, w) = _case_pair("render_cases", arr, sub, device)
-    sel = np.arange(n, dtype=np.int32) if cases is None else np.asarray(cases, dtype=np.int64).reshape(-1)
-    if sel.size and (sel.min() < 0 or sel.max() >= n):
-        raise IndexError(f"render_cases: case indices must lie in [0, {n})")
-    result = np.empty((sel.size, h, w + 1), dtype=np.uint8)
-    if result.size == 0:
-        return result
-    if w == 0:
-        result[:] = 0
-        return result
-    lib = _lib.load()
-    size = h * (w + 1)
-    group = max(1, min(sel.size, _RENDER_BYTES // size))
-    sel_dev = torch.from_numpy(sel.astype(np.int32)).to(device)
-    out = torch.empty(group * size, dtype=torch.uint8, device=device)
-    stage = torch.empty(group * size, dtype=torch.uint8).pin_memory()
-    flat = result.reshape(-1)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        for k0 in range(0, sel.size, group):
-            k = min(group, sel.size - k0)
-            check(lib.cae_render_cases(src[0].data_ptr(), src[1], src[3], *_sub_args(other),
-                                       sel_dev.data_ptr() + 4 * k0, k, n, h, w, float(lo), float(hi),
-                                       1 if flip_y else 0, out.data_ptr(), stream))
-            stage[:k * size].copy_(out[:k * size], non_blocking=False)
-            flat[k0 * size:(k0 + k) * size] = stage.numpy()[:k * size]
-    return result
-
-
-# ---- a box model applied to a whole scene (cae_scene_gather, cae_scene_blend) ---------------------------------
-
-_SCENE_PRED_BYTES = 256 << 20       # of fp32 tile predictions scored per chunk of a scene
-
-
-class ScenePlan(namedtuple("ScenePlan", "Y X h w H W sy sx oy ox ys xs")):
-    """The tiling of a (Y, X) scene by a model's boxes (scene_plan): pure Python, nothing here needs a GPU.
-    ys / xs are the tile origins in low-resolution pixels; tiles are numbered (k_y, k_x) row-major within a time step."""
-
-    __slots__ = ()
-
-    n_y = property(lambda self: len(self.ys))
-    n_x = property(lambda self: len(self.xs))
-    n_tile = property(lambda self: len(self.ys) * len(self.xs))
-    out_shape = property(lambda self: (self.Y * self.sy, self.X * self.sx))
-
-    def rows_done(self, k1):
-        """the output rows [0, rows_done) that no tile row k >= k1 touches: complete once the tile rows below k1 are in"""
-        return self.ys[k1] * self.sy if k1 < self.n_y else self.Y * self.sy
-
-    def first_row_over(self, row):
-        """the first tile row that covers output row `row`"""
-        return next(k for k, y in enumerate(self.ys) if (y + self.h) * self.sy > row)
-
-    def geom(self):
-        return _lib.SceneGeomC(self.Y, self.X, self.h, self.w, self.oy, self.ox, self.sy, self.sx)
-
-
-def _origins(extent, box, overlap):
-    stride = box - overlap
-    n = 1 + -(-(extent - box) // stride)
-    return tuple(min(k * stride, extent - box) for k in range(n))
-
-
-def scene_plan(Y, X, box, overlap=None):
-    """How a (Y, X) scene of low-resolution pixels is cut into a model's boxes.  box = (input shape, output shape), each
-    (channels, rows, columns) or (rows, columns); overlap = None for (h // 4, w // 4), one number for both axes, or (oy, ox)
-    in low-resolution pixels.  Along y the stride is h - oy and the origins are min(k * stride, Y - h) for
-    k = 0 .. ceil((Y - h) / stride): every tile is a full box, the last one shifted inward.  ValueError for output sides
-    that are no whole multiple of the input's, an overlap outside [0, box), a scene smaller than a box, or 4 H W >= 2^29."""
-    (in_shape, out_shape) = (tuple(int(v) for v in box[0]), tuple(int(v) for v in box[1]))
-    ((h, w), (H, W)) = (in_shape[-2:], out_shape[-2:])
-    if min(h, w, H, W) < 1 or H % h or W % w:
-        raise ValueError(f"scene_plan: the output box {out_shape} must be a whole multiple of the input box {in_shape} along y and x")
-    if overlap is None:
-        overlap = (h // 4, w // 4)
-    elif np.ndim(overlap) == 0:
-        overlap = (overlap, overlap)
-    (oy, ox) = (int(v) for v in overlap)
-    if not (0 <= oy < h and 0 <= ox < w):
-        raise ValueError(f"scene_plan: the overlap ({oy}, {ox}) must be at least 0 and below the input box ({h}, {w})")
-    (Y, X) = (int(Y), int(X))
-    if Y < h or X < w:
-        raise ValueError(f"scene_plan: a scene of {Y} x {X} pixels is smaller than the input box {h} x {w}")
-    if 4 * H * W >= 1 << 29:
-        raise ValueError(f"scene_plan: an output box of {H} x {W} is too large (4 H W must stay below 2^29)")
-    return ScenePlan(Y, X, h, w, H, W, H // h, W // w, oy, ox, _origins(Y, h, oy), _origins(X, w, ox))
-
-
-def _scene_operand(x, plan, device):
-    op = x if isinstance(x, DeviceOperand) else device_operand(x, device)
-    shape = tuple(op.shape)
-    if len(shape) != 4 or shape[2:] != (plan.Y, plan.X):
-        raise ValueError(f"scene variables must be (time, channel, {plan.Y}, {plan.X}); got {shape}")
-    return op
-
-
-def scene_tiles(variables, plan, norms, t0=0, n_t=None, ky0=0, n_ky=None, normalise=True, device=None):
-    """The boxes of a scene as the model's input batch (cae_scene_gather).  variables: the scene's input variables, each
-    (T, Cv, Y, X) as case_measures takes operands (NetCDF-3 slabs go up as stored); norms: (vmin, vmax) per variable.
-    Returns (x, invalid) for the time steps t0 .. t0 + n_t - 1 and the tile rows ky0 .. ky0 + n_ky - 1: x the normalised fp32
-    CUDA batch (n_t * n_ky * n_x, C, h, w), tiles in (time, k_y, k_x) order, channels in variable order; invalid an int32
-    CUDA tensor, 1 for a tile whose box holds a value that is not finite."""
-    device = _case_device(device, *variables)
-    ops = [_scene_operand(v, plan, device) for v in variables]
-    T = int(ops[0].shape[0])
-    if any(int(op.shape[0]) != T for op in ops):
-        raise ValueError(f"scene variables differ in their first dimension: {[tuple(op.shape) for op in ops]}")
-    n_t = T - t0 if n_t is None else int(n_t)
-    n_ky = plan.n_y - ky0 if n_ky is None else int(n_ky)
-    if not (0 <= t0 and 0 <= n_t and t0 + n_t <= T and 0 <= ky0 and 0 <= n_ky and ky0 + n_ky <= plan.n_y):
-        raise ValueError(f"scene_tiles: time steps {t0}..{t0 + n_t} of {T}, tile rows {ky0}..{ky0 + n_ky} of {plan.n_y}")
-    channels = int(sum(op.shape[1] for op in ops))
-    n_tile = n_t * n_ky * plan.n_x
-    x = torch.empty((n_tile, channels, plan.h, plan.w), dtype=torch.float32, device=device)
-    invalid = torch.zeros(n_tile, dtype=torch.int32, device=device)
-    if n_tile == 0:
-        return x, invalid
-    lib = _lib.load()
-    geom = plan.geom()
-    off = 0
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        for (op, (vmin, vmax)) in zip(ops, norms):
-            rng = float(vmax) - float(vmin)
-            check(lib.cae_scene_gather(C.byref(geom), op.tensor.data_ptr(), op[1], T, int(op.shape[1]), int(t0), n_t, int(ky0), n_ky,
-                                       x.data_ptr(), channels, off, C.c_float(float(np.float32(vmin))),
-                                       C.c_float(float(np.float32(rng))), 1 if normalise else 0, invalid.data_ptr(), stream))
-            off += int(op.shape[1])
-    return x, invalid
-
-
-def scene_blend(pred, invalid, plan, vmin, vmax, n_t=1, k0=0, carry=None, rows=None, out=None, nan_pixels=None):
-    """Scored boxes folded back into the scene (cae_scene_blend).  pred: fp32 CUDA (n_t * n_k * n_x, Co, H, W), the tile rows
-    k0 .. k0 + n_k - 1 of n_t time steps in scene_tiles' order, with their invalid flags; carry: None or (pred, invalid, k0) of
-    earlier tile rows that the output rows still need.  rows = (row0, row1): the output rows to write; None: the rows the
-    tile rows complete, plan.rows_done(k0) .. plan.rows_done(k0 + n_k).  out: float64 CUDA (n_t, Co, Y sy, X sx) to write
-    into (None: a new one, NaN outside the rows); nan_pixels: int64 CUDA (n_t) to add the pixels without a valid tile to.
-    Per pixel (S w p) / S w over the valid covering tiles in ascending tile number, then vmin + v * (vmax - vmin).
-    Returns (out, nan_pixels)."""
-    device = pred.device
-    pred = pred.contiguous()
-    (Co, n_t) = (int(pred.shape[1]), int(n_t))
-    if pred.dtype != torch.float32 or tuple(pred.shape[2:]) != (plan.H, plan.W) or n_t < 1 or int(pred.shape[0]) % (n_t * plan.n_x):
-        raise ValueError(f"scene_blend: fp32 predictions (n_t * n_k * {plan.n_x}, Co, {plan.H}, {plan.W}) expected, got "
-                         f"{tuple(pred.shape)} {pred.dtype} for {n_t} time steps")
-    n_k = int(pred.shape[0]) // (n_t * plan.n_x)
-    if invalid.dtype != torch.int32 or invalid.numel() != pred.shape[0] or invalid.device != device:
-        raise ValueError("scene_blend: one int32 invalid flag per tile expected, on the predictions' device")
-    (cp, ci, ck0, cnk) = (None, None, 0, 0)
-    if carry is not None:
-        (cp, ci, ck0) = (carry[0].contiguous(), carry[1].contiguous(), int(carry[2]))
-        if cp.dtype != torch.float32 or tuple(cp.shape[1:]) != tuple(pred.shape[1:]) or int(cp.shape[0]) % (n_t * plan.n_x) or \
-                ci.dtype != torch.int32 or ci.numel() != cp.shape[0]:
-            raise ValueError("scene_blend: the carried tile rows must be laid out as the new ones")
-        cnk = int(cp.shape[0]) // (n_t * plan.n_x)
-    (Ys, Xs) = plan.out_shape
-    (row0, row1) = (plan.rows_done(k0) if k0 else 0, plan.rows_done(k0 + n_k)) if rows is None else (int(rows[0]), int(rows[1]))
-    if out is None:
-        out = torch.full((n_t, Co, Ys, Xs), math.nan, dtype=torch.float64, device=device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (n_t, Co, Ys, Xs) or out.device != device or \
-            not out[0].is_contiguous():
-        raise ValueError(f"scene_blend: out must be a float64 tensor ({n_t}, {Co}, {Ys}, {Xs}) on the predictions' device")
-    if nan_pixels is None:
-        nan_pixels = torch.zeros(n_t, dtype=torch.int64, device=device)
-    lib = _lib.load()
-    geom = plan.geom()
-    with torch.cuda.device(device):
-        check(lib.cae_scene_blend(C.byref(geom), pred.data_ptr(), invalid.data_ptr(), int(k0), n_k,
-                                  cp.data_ptr() if cnk else None, ci.data_ptr() if cnk else None, ck0, cnk, n_t, Co, row0, row1,
-                                  float(vmin), float(vmax) - float(vmin), out.data_ptr(), int(out.stride(0)), nan_pixels.data_ptr(),
-                                  torch.cuda.current_stream(device).cuda_stream))
-    return out, nan_pixels
-
-
-def scene_chunks(plan, T, c_out, tile_rows=None):
-    """The (t0, n_t, k0, n_k) pieces scene_apply scores one after the other: whole tile rows, tile_rows of them at a time.
-    None: as many as keep a piece's fp32 predictions within _SCENE_PRED_BYTES, and whole time steps, several at a time,
-    once a time step fits.  Pure Python."""
-    row_bytes = plan.n_x * c_out * plan.H * plan.W * 4
-    n_t = 1
-    if tile_rows is None:
-        tile_rows = max(1, min(plan.n_y, _SCENE_PRED_BYTES // row_bytes))
-        if tile_rows == plan.n_y:
-            n_t = max(1, min(T, _SCENE_PRED_BYTES // (row_bytes * plan.n_y), 65535 // c_out))
-    tile_rows = int(tile_rows)
-    if tile_rows < 1:
-        raise ValueError(f"scene_apply: tile_rows must be at least 1, got {tile_rows}")
-    return [(t0, min(n_t, T - t0), k0, min(tile_rows, plan.n_y - k0))
-            for t0 in range(0, T, n_t) for k0 in range(0, plan.n_y, tile_rows)]
-
-
-def scene_apply(variables, norms, plan, score, c_out, vmin, vmax, tile_rows=None, normalise=True, device=None):
-    """A box model over a whole scene: scene_tiles -> score -> scene_blend in pieces of whole tile rows (scene_chunks), so that
-    the tile predictions of a large scene are never all resident.  score: callable, the fp32 CUDA batch (n, C, h, w) -> the fp32
-    CUDA scores (n, c_out, H, W).  The tile rows a later piece's output rows still need are carried (the previous piece's
-    scores are kept, not copied), so the result does not depend on tile_rows, bit for bit.
-    Returns (out float64 CUDA (T, c_out, Y sy, X sx), invalid_tiles (T,) int64 numpy, nan_pixels (T,) int64 numpy)."""
-    device = _case_device(device, *variables)
-    ops = [_scene_operand(v, plan, device) for v in variables]
-    T = int(ops[0].shape[0])
-    c_out = int(c_out)
-    out = torch.empty((T, c_out) + plan.out_shape, dtype=torch.float64, device=device)
-    invalid_tiles = torch.zeros(T, dtype=torch.int64, device=device)
-    nan_pixels = torch.zeros(T, dtype=torch.int64, device=device)
-    carry = None
-    for (t0, n_t, k0, n_k) in scene_chunks(plan, T, c_out, tile_rows):
-        (x, inv) = scene_tiles(ops, plan, norms, t0, n_t, k0, n_k, normalise=normalise, device=device)
-        y = score(x)
-        if y.dtype != torch.float32 or tuple(y.shape) != (int(x.shape[0]), c_out, plan.H, plan.W):
-            raise CaeError(f"scene_apply: the model returned {tuple(y.shape)} {y.dtype} for {tuple(x.shape)}; fp32 "
-                           f"({int(x.shape[0])}, {c_out}, {plan.H}, {plan.W}) expected")
-        invalid_tiles[t0:t0 + n_t] += inv.view(n_t, -1).sum(dim=1)
-        scene_blend(y, inv, plan, vmin, vmax, n_t=n_t, k0=k0, carry=carry, out=out[t0:t0 + n_t], nan_pixels=nan_pixels[t0:t0 + n_t])
-        k1 = k0 + n_k
-        if k1 == plan.n_y:
-            carry = None
-            continue
-        # what the next piece's output rows need of the tile rows seen so far (a piece of part of a time step has n_t == 1)
-        keep = plan.first_row_over(plan.rows_done(k1))
-        if keep >= k0:
-            carry = (y[(keep - k0) * plan.n_x:], inv[(keep - k0) * plan.n_x:], keep)
-        else:                   # pieces thinner than the cover: the older rows are copied on
-            skip = (keep - carry[2]) * plan.n_x
-            carry = (torch.cat([carry[0][skip:], y]), torch.cat([carry[1][skip:], inv]), keep)
-    return out, invalid_tiles.cpu().numpy(), nan_pixels.cpu().numpy()
+# the entry points that use no engine live beside this module; they keep the names they have always had here
+from .device_ops import denormalise_f64, inverse_permutation, metric_sums, normalise_pack, scan_f32, upload_f32  # noqa: E402,F401
+from .case_ops import (_SSIM_CASES, DeviceOperand, case_baseline, case_measures, case_range, case_spectra, case_ssim, device_operand, ensemble_verify, pixel_sums, render_cases, upsample)  # noqa: E402,F401
+from .scene import ScenePlan, scene_apply, scene_blend, scene_chunks, scene_plan, scene_tiles  # noqa: E402,F401

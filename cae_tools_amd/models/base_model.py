@@ -155,14 +155,14 @@ class BaseModel:
                     tile_rows=None):
         """Apply the model to a whole scene (build-only; DESIGN.md §9 'scene apply').  The input variables are (T, Cv, Y, X)
         with Y and X at least the model's input box, or (T,) and broadcast; the scene is cut into overlapping boxes
-        (engine.scene_plan; overlap None: a quarter of the box), the boxes are scored through _score_all in pieces of whole
+        (scene.scene_plan; overlap None: a quarter of the box), the boxes are scored through _score_all in pieces of whole
         tile rows (tile_rows None: a byte budget), and the scores are blended with integer tent weights into
         `prediction_variable`, float64 (T, Co, Y sy, X sx), denormalised as apply() writes it.  A box with a value that is
         not finite is left out of the blend; a pixel no valid box covers is NaN.  The result does not depend on tile_rows.
         Stores the variable on the scene's first dimension, keeps the tile grid and the per-time-step counts of invalid
         tiles and NaN pixels in self.scene_report, and returns the float64 CUDA tensor."""
         from .. import dp as _dp
-        from .. import engine as _eng
+        from .. import scene as _scene
         from ..data.arrays import as_numpy
         _dp.ensure_process_group()
         (in_shape, out_shape) = (tuple(self.input_shape), tuple(self.output_shape))
@@ -172,7 +172,7 @@ class BaseModel:
             raise ValueError("apply_scene: scene variables must be 4-D (time, channel, y, x), or 1-D (time) beside one that is; "
                              f"got shapes {[a.shape for a in shaped]}")
         (T, Y, X) = (int(full[0].shape[0]), int(full[0].shape[2]), int(full[0].shape[3]))
-        plan = _eng.scene_plan(Y, X, (in_shape, out_shape), overlap)
+        plan = _scene.scene_plan(Y, X, (in_shape, out_shape), overlap)
         variables = [np.broadcast_to(np.asarray(a, dtype=a.dtype.newbyteorder("="))[:, None, None, None], (a.shape[0], 1, Y, X)).copy()
                      if a.ndim == 1 else a for a in shaped]
         if sum(int(v.shape[1]) for v in variables) != in_shape[0]:
@@ -180,7 +180,7 @@ class BaseModel:
                              f"box {in_shape} has {in_shape[0]}")
         (min_in, max_in, min_out, max_out) = tuple(self.normalisation_parameters)
         norms = [(min_in[name], max_in[name]) for name in input_variables]
-        (out, invalid_tiles, nan_pixels) = _eng.scene_apply(variables, norms, plan, self._score_all, out_shape[0], min_out, max_out,
+        (out, invalid_tiles, nan_pixels) = _scene.scene_apply(variables, norms, plan, self._score_all, out_shape[0], min_out, max_out,
                                                             tile_rows=tile_rows, normalise=self.normalise_input)
         self.scene_report = {"plan": plan, "time_steps": T, "invalid_tiles": invalid_tiles, "nan_pixels": nan_pixels}
         time_dimension = scene_ds[input_variables[0]].dims[0]

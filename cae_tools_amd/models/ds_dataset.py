@@ -12,12 +12,13 @@ import numpy as np
 import torch
 
 from ..data.arrays import as_numpy
-from .. import engine as _eng
+from .. import device_ops as _ops
+from .._lib import CaeError
 
 
 def _device():
     if not torch.cuda.is_available():
-        raise _eng.CaeError("DSDataset needs a ROCm GPU: the loader arithmetic runs in libcae_hip (no CPU fallback)")
+        raise CaeError("DSDataset needs a ROCm GPU: the loader arithmetic runs in libcae_hip (no CPU fallback)")
     return torch.device("cuda", torch.cuda.current_device())
 
 
@@ -45,12 +46,12 @@ class DSDataset(torch.utils.data.Dataset):
         # the reference scans the output first (and requires it: :42-46)
         out_da = ds[output_variable_name]
         self._raw_out = self._upload(out_da, dev)
-        (nans, omin, omax) = _eng.scan_f32(self._raw_out)
+        (nans, omin, omax) = _ops.scan_f32(self._raw_out)
         if nans > 0:
             raise ValueError(f"output variable contains {nans} NaN values")
         self.min_inputs, self.max_inputs, self.input_spec = {}, {}, []
         for name, da, raw in zip(self.input_variable_names, self.input_das, self._raw_in):
-            (nans, lo, hi) = _eng.scan_f32(raw)
+            (nans, lo, hi) = _ops.scan_f32(raw)
             self.min_inputs[name] = lo
             self.max_inputs[name] = hi
             if nans > 0:
@@ -75,7 +76,7 @@ class DSDataset(torch.utils.data.Dataset):
         arr = as_numpy(da)
         if arr.ndim != 4:
             raise ValueError(f"variables must be 4-D (case, channel, y, x); got shape {arr.shape}")
-        return _eng.upload_f32(arr, dev)
+        return _ops.upload_f32(arr, dev)
 
     # -- reference accessors ---------------------------------------------------------------
     def set_normalise_output(self, normalise_out):
@@ -110,7 +111,7 @@ class DSDataset(torch.utils.data.Dataset):
 
     def denormalise_device(self, y):
         """fp32 CUDA scores -> fp64 CUDA tensor (cae_denormalise_f64)"""
-        return _eng.denormalise_f64(y, self.min_output, self.max_output)
+        return _ops.denormalise_f64(y, self.min_output, self.max_output)
 
     # -- device-resident normalised arrays (what the training loop consumes) ---------------------
     def device_inputs(self):
@@ -119,7 +120,7 @@ class DSDataset(torch.utils.data.Dataset):
                             device=self._raw_in[0].device)
             off = 0
             for name, raw in zip(self.input_variable_names, self._raw_in):
-                _eng.normalise_pack(raw, x, off, self.min_inputs[name], self.max_inputs[name], enable=self.normalise_in)
+                _ops.normalise_pack(raw, x, off, self.min_inputs[name], self.max_inputs[name], enable=self.normalise_in)
                 off += raw.shape[1]
             torch.cuda.synchronize(x.device)
             self._x = x
@@ -132,7 +133,7 @@ class DSDataset(torch.utils.data.Dataset):
             return self._raw_out        # the un-normalised target IS the uploaded variable (one variable, no concat)
         if self._t is None or self._t_norm_flag != self.normalise_out:
             t = torch.empty_like(self._raw_out)
-            _eng.normalise_pack(self._raw_out, t, 0, self.min_output, self.max_output, enable=self.normalise_out)
+            _ops.normalise_pack(self._raw_out, t, 0, self.min_output, self.max_output, enable=self.normalise_out)
             torch.cuda.synchronize(t.device)
             self._t, self._t_norm_flag = t, self.normalise_out
         return self._t
@@ -143,18 +144,18 @@ class DSDataset(torch.utils.data.Dataset):
         DataLoader(shuffle=True) + default collate, whose stacked batches are built once and reused every epoch
         (conv_ae_model.py:291-292, 315-325); here the stacking is the normalisation pass itself (cae_normalise_pack_rows
         writes each sample to its destination row), straight from the raw variables: no second normalised copy."""
-        rows = _eng.inverse_permutation(order, self._raw_in[0].device)
+        rows = _ops.inverse_permutation(order, self._raw_in[0].device)
         x = torch.empty((self.n, self.input_chan, self.input_y, self.input_x), dtype=torch.float32,
                         device=self._raw_in[0].device)
         off = 0
         for name, raw in zip(self.input_variable_names, self._raw_in):
-            _eng.normalise_pack(raw, x, off, self.min_inputs[name], self.max_inputs[name], enable=self.normalise_in,
+            _ops.normalise_pack(raw, x, off, self.min_inputs[name], self.max_inputs[name], enable=self.normalise_in,
                                 dst_rows=rows)
             off += raw.shape[1]
         t = None
         if self._raw_out is not None:
             t = torch.empty_like(self._raw_out)
-            _eng.normalise_pack(self._raw_out, t, 0, self.min_output, self.max_output, enable=self.normalise_out,
+            _ops.normalise_pack(self._raw_out, t, 0, self.min_output, self.max_output, enable=self.normalise_out,
                                 dst_rows=rows)
         torch.cuda.synchronize(x.device)
         return x, t

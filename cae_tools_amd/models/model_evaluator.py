@@ -53,7 +53,7 @@ import os
 import numpy as np
 
 from ..data.arrays import as_numpy, open_mfdataset
-from ..engine import case_baseline, case_measures, case_range, case_spectra, case_ssim, device_operand, pixel_sums, render_cases
+from ..case_ops import case_baseline, case_measures, case_range, case_spectra, case_ssim, device_operand, pixel_sums, render_cases
 from ..utils import baseline as baseline_scores
 from ..utils import case_pages, ensemble_scores, skill_maps
 from ..utils import spectra as spectra_curves

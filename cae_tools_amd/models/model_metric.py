@@ -64,8 +64,8 @@ class DeviceModelMetric:
         self.sums = []
 
     def accumulate(self, actual, scores, mask, vmin, vmax):
-        from .. import engine as _eng
-        self.sums.append(_eng.metric_sums(scores, actual, mask, vmin, vmax))
+        from ..device_ops import metric_sums
+        self.sums.append(metric_sums(scores, actual, mask, vmin, vmax))
 
     def get_metrics(self):
         if not self.sums:

@@ -122,8 +122,8 @@ class VarAEModel(EngineModel):
 
     def _denormalise(self, y):
         """as apply() denormalises (ds_dataset.denormalise_device): min + y * (max - min) of the output variable, float64"""
-        from .. import engine as _eng
-        return _eng.denormalise_f64(y, self.normalisation_parameters[2], self.normalisation_parameters[3])
+        from ..device_ops import denormalise_f64
+        return denormalise_f64(y, self.normalisation_parameters[2], self.normalisation_parameters[3])
 
     def encode(self, score_ds, input_variables):
         """(mu, logvar) of every case of score_ds: float32 numpy arrays (N, encoded_dim_size); eval mode"""

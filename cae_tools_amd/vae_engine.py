@@ -108,7 +108,7 @@ class VaeEngine(ShardedSteps, SteppedEngine, SpecPlan):
         """The K = ensemble_size >= 2 draws z_k = sample_latent(mu, logvar, k) of every case decoded and reduced per pixel by
         cae_ensemble_moments (include/cae_hip.h): (mean, std) float64 CUDA tensors (N, *out_shape), denormalised with
         vmin + y * (vmax - vmin); std (ddof = 1) is None unless want_std.  The decoded draws live in one max_batch-row buffer.
-        target (the N cases' truth in physical units: an (N, C, H, W) array, CUDA tensor or engine.device_operand) also
+        target (the N cases' truth in physical units: an (N, C, H, W) array, CUDA tensor or case_ops.device_operand) also
         verifies the draws of channel 0 against it where they lie (cae_ensemble_verify, K <= 64) and returns (mean, std,
         case_sums, rank_counts): numpy arrays (N, 5) float64 and (K + 2,) int64 for utils/ensemble_scores.py."""
         k = int(ensemble_size)
@@ -151,18 +151,17 @@ class VaeEngine(ShardedSteps, SteppedEngine, SpecPlan):
         """ensemble() with a target: the K draws of a group of cases are decoded into one buffer of K rows per case ([draw][case]
         order, in pieces of at most max_batch rows), which one cae_ensemble_moments call (all K draws, no workspace) and one
         cae_ensemble_verify call then reduce"""
-        from .engine import _measure_operand
+        from .case_ops import device_operand
         if k > 64:
             raise ValueError("an ensemble is verified with at most 64 draws")
         (mu, logvar) = (self._rows(mu, (self.latent_size,), "ensemble()"), self._rows(logvar, (self.latent_size,), "ensemble()"))
         n = mu.shape[0]
         check_noise_index(int(first_case) + n, self.latent_size)
-        (a, kind, ashape, astride) = _measure_operand(target, self.device)
-        if len(ashape) != 4 or ashape[0] != n or tuple(ashape[2:]) != tuple(self.out_shape[-2:]):
-            raise CaeError(f"ensemble(): the target {tuple(ashape)} does not match {n} cases of {tuple(self.out_shape)}")
-        if a.device != self.device:
+        target = device_operand(target, self.device)
+        if len(target.shape) != 4 or target.shape[0] != n or tuple(target.shape[2:]) != tuple(self.out_shape[-2:]):
+            raise CaeError(f"ensemble(): the target {tuple(target.shape)} does not match {n} cases of {tuple(self.out_shape)}")
+        if target.tensor.device != self.device:
             raise CaeError("ensemble(): the target lies on another device")
-        elem = 4 if kind in (0, 1) else 8
         field = int(np.prod(self.out_shape))
         plane = int(self.out_shape[-2] * self.out_shape[-1])
         cases = max(1, self.max_batch // k)
@@ -191,10 +190,10 @@ class VaeEngine(ShardedSteps, SteppedEngine, SpecPlan):
                                                 float(vmax) - float(vmin), mean[lo:lo + g].data_ptr(),
                                                 None if std is None else std[lo:lo + g].data_ptr(), None, 0,
                                                 self.stream.cuda_stream))
-            check(self.lib.cae_ensemble_verify(y.data_ptr(), field, g * field, a.data_ptr() + lo * astride * elem, kind, astride,
-                                               g, plane, k, float(vmin), float(vmax) - float(vmin), sums[lo:lo + g].data_ptr(),
+            check(self.lib.cae_ensemble_verify(y.data_ptr(), field, g * field, *target.args(lo), g, plane, k, float(vmin),
+                                               float(vmax) - float(vmin), sums[lo:lo + g].data_ptr(),
                                                ranks.data_ptr(), ws.data_ptr(), ws_bytes, self.stream.cuda_stream))
         self.sync()
-        for t in (a, mu, logvar):
+        for t in (target.tensor, mu, logvar):
             t.record_stream(self.stream)
         return mean, std, sums.cpu().numpy(), ranks.cpu().numpy()

@@ -110,7 +110,7 @@ def test_render_matches_numpy(shape, flip_y):
 
 def test_render_in_groups(monkeypatch):
     """more cases than one group holds: the groups' outputs land in order"""
-    from cae_tools_amd import engine
+    from cae_tools_amd import case_ops as engine
     rng = np.random.default_rng(8)
     a = rng.random((11, 1, 9, 6)).astype(np.float32)
     monkeypatch.setattr(engine, "_RENDER_BYTES", 3 * 9 * 7 + 5)

@@ -248,7 +248,7 @@ def test_filled_pixel_reaches_dsdataset_as_nan(tmp_path):
 @pytest.mark.gpu
 def test_big_endian_slab_is_swapped_on_the_gpu(tmp_path, monkeypatch):
     import torch
-    from cae_tools_amd import engine as eng
+    from cae_tools_amd import device_ops as eng
     rng = np.random.default_rng(6)
     a = rng.standard_normal((7, 3, 33, 35)).astype(np.float32)       # 24,255 words: not a multiple of 4
     a.reshape(-1)[:3] = [np.nan, np.inf, -0.0]
