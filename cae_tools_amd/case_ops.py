@@ -1,5 +1,5 @@
 """The case kernels of libcae_hip (include/cae_hip.h) as functions, no engine needed: measures, per-pixel sums, spectra, SSIM,
-interpolation baseline, ensemble verification, value range and rendered pages of channel 0 of (N, C, H, W) operands."""
+interpolation baseline, value distributions, ensemble verification, value range and rendered pages of channel 0 of (N, C, H, W) operands."""
 import ctypes as C
 import math
 from contextlib import contextmanager
@@ -254,6 +254,38 @@ def case_baseline(low, pred, actual, mode="bicubic", field=False, device=None):
                 out[c0:c0 + g] = b.cpu().numpy()
         sums = sums.cpu().numpy()
     return (sums, out) if field else sums
+
+
+def joint_histogram(pred, actual, lo, hi, n_bin=128, sub=8, device=None):
+    """The value distributions of channel 0 (cae_joint_hist, include/cae_hip.h) over the pixels where prediction p and
+    target a are both finite: (joint (n_bin, n_bin) int64 with joint[ia][ip] the count of the coarse bin pair, marginals
+    (2, n_bin * sub) int64 fine counts of a and of p, cond (2, n_bin, 4) float64 {S d, S|d|, S d^2, S (a - lo)} keyed by
+    the bin of a and {S d, S|d|, S d^2, S (p - lo)} keyed by the bin of p with d = p - a, outside (4,) int64
+    {a < lo, a > hi, p < lo, p > hi}).  n_bin coarse bins of `sub` fine bins each over [lo, hi]; a value outside goes to
+    the nearest bin, hi itself to the last.  Operands as case_baseline takes them.  utils/distribution.curves_from_counts
+    turns the arrays into the conditional bias, reliability, quantiles and exceedance scores."""
+    (device, p, a, n, h, w) = _pair("joint_histogram", pred, actual, device)
+    (lo, hi) = (float(lo), float(hi))
+    if int(n_bin) != n_bin or not 1 <= int(n_bin) <= 128:
+        raise ValueError(f"joint_histogram: n_bin must be an integer from 1 to 128, got {n_bin!r}")
+    if int(sub) != sub or not 1 <= int(sub) <= 32:
+        raise ValueError(f"joint_histogram: sub must be an integer from 1 to 32, got {sub!r}")
+    (n_bin, sub) = (int(n_bin), int(sub))
+    if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo and math.isfinite(hi - lo) and math.isfinite(n_bin * sub / (hi - lo))):
+        raise ValueError(f"joint_histogram: lo and hi must be finite with hi > lo and n_bin * sub / (hi - lo) finite, got {lo!r} and {hi!r}")
+    plane = h * w
+    if n * plane >= 1 << 40:
+        raise ValueError(f"joint_histogram: fewer than 2^40 pixels a call expected, got {n} x {plane}")
+    joint = torch.empty((n_bin, n_bin), dtype=torch.int64, device=device)
+    marg = torch.empty((2, n_bin * sub), dtype=torch.int64, device=device)
+    cond = torch.empty((2, n_bin, 4), dtype=torch.float64, device=device)
+    outside = torch.empty(4, dtype=torch.int64, device=device)
+    lib = _lib.load()
+    (ws, need) = _workspace(device, lib.cae_joint_hist_workspace_bytes, n, plane, n_bin, sub)
+    with _stream(device) as stream:
+        check(lib.cae_joint_hist(*p.args(), *a.args(), n, plane, lo, hi, n_bin, sub, joint.data_ptr(), marg.data_ptr(),
+                                 cond.data_ptr(), outside.data_ptr(), ws.data_ptr(), need, stream))
+        return joint.cpu().numpy(), marg.cpu().numpy(), cond.cpu().numpy(), outside.cpu().numpy()
 
 
 def upsample(low, out_shape, mode="bicubic", device=None):

@@ -46,6 +46,14 @@ input: channel 0 of baseline_variable (default: the model's first input variable
 one cae_case_baseline pass on the GPU (fp64; utils/baseline.py): baseline_<partition>.json with the
 pooled and per-case skill 1 - model_mse / baseline_mse, per-case baseline_mse / skill variables beside mae / mse in the
 data set, and the report's "Skill against interpolation" section.
+
+distribution=True (cli/distribution.py; not a reference feature) adds the reduction along value: per partition the joint
+histogram of prediction against target over distribution_bins (1 to 128) coarse bins, the two fine marginal histograms and
+the per-bin error sums of channel 0 from one cae_joint_hist pass on the GPU (utils/distribution.py)
+over the range of the finite values of target and prediction in the partitions present (cae_case_range; hi = lo + 1 where
+that range is degenerate): distribution_<partition>.json with the conditional bias, reliability, quantiles, Wasserstein-1
+distance, Perkins score and exceedance scores, distribution/index.html with the joint density and the curves, and the
+report's "Value distribution" section.
 """
 import json
 import os
@@ -53,9 +61,11 @@ import os
 import numpy as np
 
 from ..data.arrays import as_numpy, open_mfdataset
-from ..case_ops import case_baseline, case_measures, case_range, case_spectra, case_ssim, device_operand, pixel_sums, render_cases
+from ..case_ops import (case_baseline, case_measures, case_range, case_spectra, case_ssim, device_operand, joint_histogram, pixel_sums,
+                        render_cases)
 from ..utils import baseline as baseline_scores
 from ..utils import case_pages, ensemble_scores, skill_maps
+from ..utils import distribution as distribution_curves
 from ..utils import spectra as spectra_curves
 from ..utils import ssim as ssim_scores
 from ..utils.model_database import ModelDatabase
@@ -72,7 +82,7 @@ class ModelEvaluator:
     def __init__(self, training_paths, testing_paths, output_html_folder="", model_output_variable="", model_path="",
                  database_path="", input_variables=[], sample_count=None, x_coordinate="", y_coordinate="",
                  time_coordinate="", skill_maps=False, ensemble_size=None, ensemble_seed=0, spectra=False, ssim=False,
-                 baseline=False, baseline_variable=None, baseline_mode="bicubic"):
+                 baseline=False, baseline_variable=None, baseline_mode="bicubic", distribution=False, distribution_bins=128):
         self.training_paths = list(training_paths) if training_paths else []
         self.testing_paths = list(testing_paths) if testing_paths else []
         self.output_html_folder = output_html_folder
@@ -92,6 +102,10 @@ class ModelEvaluator:
         (self.baseline, self.baseline_variable, self.baseline_mode) = (baseline, baseline_variable, baseline_mode)
         if baseline and baseline_mode not in baseline_scores.MODES:
             raise ValueError(f"baseline_mode must be one of {', '.join(baseline_scores.MODES)}, got {baseline_mode!r}")
+
+        (self.distribution, self.distribution_bins) = (distribution, distribution_bins)
+        if distribution and (int(distribution_bins) != distribution_bins or not 1 <= int(distribution_bins) <= 128):
+            raise ValueError(f"distribution_bins must be an integer from 1 to 128, got {distribution_bins!r}")
 
         (self.ensemble_size, self.ensemble_seed) = (ensemble_size, int(ensemble_seed))
         if ensemble_size is not None and (int(ensemble_size) != ensemble_size or not 2 <= int(ensemble_size) <= 64):
@@ -214,10 +228,12 @@ class ModelEvaluator:
 
         maps_link = self._skill_maps(train_ds, test_ds) if self.skill_maps else None
         spectra_link = self._spectra(train_ds, test_ds) if self.spectra else None
+        distribution = self._distribution(train_ds, test_ds) if self.distribution else None
         self._page_ops = {}
         page = evaluation_report(model_metrics, measures, training_parameters, training_losses, case_links, maps_link,
                                  ensemble=ensemble or None, spectra_link=spectra_link, ssim=ssim or None,
-                                 **({"baseline": baseline} if baseline else {}))
+                                 **({"baseline": baseline} if baseline else {}),
+                                 **({"distribution": distribution} if distribution else {}))
         os.makedirs(self.output_html_folder, exist_ok=True)
         with open(self.output_html_path, "w") as f:
             f.write(page)
@@ -428,6 +444,41 @@ class ModelEvaluator:
             return None
         spectra_curves.write_page(os.path.join(self.output_html_folder, "spectra"), parts)
         return "spectra/index.html"
+
+    # ---- value distributions ---------------------------------------------------------------------
+
+    DISTRIBUTION_SUB = 8        # fine bins of a coarse bin: 1024 fine bins at the default 128
+
+    def _distribution(self, train_ds, test_ds):
+        """distribution_<partition>.json and distribution/index.html; returns ([(partition, curves)], the page's href) for
+        the report, or None without a partition.  The range is shared by the partitions present: the minimum and the
+        maximum of the finite values of target and prediction (cae_case_range), hi = lo + 1 where it is degenerate."""
+        (target, pred) = (self.output_variable, self.model_output_variable)
+        found = []
+        for (partition, ds) in (("test", test_ds), ("train", train_ds)):
+            if ds is None:
+                continue
+            ops = self._page_ops.get(partition, {})         # what the case pages have uploaded already
+            p = ops.get(pred, self._device_predictions.get(partition))
+            found.append((partition, device_operand(p if p is not None else as_numpy(ds[pred])),
+                          device_operand(ops.get(target, as_numpy(ds[target])))))
+        if not found:
+            return None
+        spans = [case_range(op) for (_, p, a) in found for op in (p, a)]
+        spans = [s for s in spans if s[2] > 0]
+        (lo, hi) = (min(s[0] for s in spans), max(s[1] for s in spans)) if spans else (0.0, 0.0)
+        if not (np.isfinite(hi - lo) and hi > lo and np.isfinite(self.distribution_bins * self.DISTRIBUTION_SUB / (hi - lo))):
+            hi = lo + 1.0
+        parts = []
+        os.makedirs(self.output_html_folder, exist_ok=True)
+        for (partition, p, a) in found:
+            counts = joint_histogram(p, a, lo, hi, n_bin=int(self.distribution_bins), sub=self.DISTRIBUTION_SUB)
+            curves = distribution_curves.curves_from_counts(*counts, lo, hi, n_pixels=int(a.shape[0]) * int(a.shape[2]) * int(a.shape[3]))
+            distribution_curves.write_json(os.path.join(self.output_html_folder, f"distribution_{partition}.json"), curves)
+            print(distribution_curves.line(partition, curves))
+            parts.append((partition, curves))
+        distribution_curves.write_page(os.path.join(self.output_html_folder, "distribution"), parts)
+        return parts, "distribution/index.html"
 
     # ---- structural similarity -------------------------------------------------------------------
 

@@ -210,7 +210,7 @@ ENSEMBLE_ROWS = (("crps", "crps"), ("fair crps", "fair_crps"), ("mean per-case m
 
 
 def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None, ensemble=None,
-                      spectra_link=None, ssim=None, baseline=None):
+                      spectra_link=None, ssim=None, baseline=None, distribution=None):
     """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
     metrics: {"test": {...}, "train": {...}} (either may be absent); measures: [(partition, {"mae": values, "mse": values})]
     in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}; maps_link: href of
@@ -221,7 +221,9 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
     [(partition, record)] of utils/ssim.summary: a "Structural similarity" section with the table of the mean ssim, ms_ssim
     and psnr and the histogram of the per-case ssim; baseline: [(partition, record)] of utils/baseline.summary: a "Skill
     against interpolation" section with the table of the pooled and per-case skill against the interpolated input and the
-    histogram of the per-case skill."""
+    histogram of the per-case skill; distribution: ([(partition, curves)] of utils/distribution.curves_from_counts, href of
+    the value distribution page): a "Value distribution" section with the table of the conditional slope, quantile bias,
+    distances and exceedance scores, and the link."""
     doc = Document("Model Evaluation")
     doc.head.add("style").text(STYLE)
     body = doc.body
@@ -266,6 +268,15 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
                                 f"{rec['n_cases']} cases")
             body.table(baseline_scores.section_rows(rec))
             body.add("img", {"src": svg_data_uri(svg_histogram(rec["case_skill"], "skill")), "alt": f"{partition} skill histogram"})
+    if distribution:
+        from . import distribution as distribution_curves
+        (records, link) = distribution
+        body.add("h2").text("Value distribution")
+        for (partition, rec) in records:
+            body.add("h3").text(f"{partition}: {rec['pairs']} pixel pairs, {rec['n_bin']} bins over [{rec['lo']:.6g}, {rec['hi']:.6g}]")
+            body.table(distribution_curves.section_rows(rec))
+        if link:
+            body.add("p").add("a", {"href": link}).text("Value distribution of prediction against target")
     if parameters or history:
         body.add("h2").text("Training Summary")
     if parameters:

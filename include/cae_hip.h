@@ -588,6 +588,50 @@ int cae_case_baseline(const void* low_dev, int low_kind, int64_t low_case_stride
                       double* sums_dev /* [n_case][6] */, double* field_dev /* NULL or [n_case][h_out][w_out] */,
                       void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- value distributions (stateless): joint histogram of prediction against target ------------- */
+
+/* One pass over channel 0 of prediction p and target a as stored, along value: the joint histogram of (a, p) over n_bin x
+ * n_bin coarse bins of [lo, hi], the two marginal histograms over n_fine = n_bin * sub fine bins, and per coarse bin of a and
+ * of p the sums of the error.  utils/distribution.py forms the scatter density, conditional bias, reliability, Q-Q curve and
+ * exceedance table from them.
+ * Operands as cae_case_baseline takes them: CAE_ELEM_* kinds read as stored, big-endian kinds included; channel 0 is the
+ * first `plane` elements of a case, case i starts at element i * case_stride, any stride >= plane, pointers aligned to their
+ * element size.
+ * A pixel is a pair when both values are finite; any other pixel is left out.
+ * Binning: scale = (double)n_fine / (hi - lo), one division, formed on the host.  For a value v, t = ((double)v - lo) * scale,
+ * the subtraction and the product each rounded on its own; the fine bin is f = 0 if t < 0, n_fine - 1 if t >= n_fine, else
+ * (long)t - the comparison is made in fp64 before any conversion, so 1e300 is safe.  The coarse bin is f / sub (integer
+ * division), so a coarse marginal is the sum of its fine bins by construction.  v == hi lands in the last bin and is not
+ * outside.  With d = (double)p - (double)a, over the pairs:
+ *   joint_dev[ia][ip]    += 1
+ *   marg_dev[0][fa]      += 1,   marg_dev[1][fp] += 1
+ *   cond_dev[0][ia][0..3] += {d, |d|, d*d, a - lo}      (the product rounded before it is added)
+ *   cond_dev[1][ip][0..3] += {d, |d|, d*d, p - lo}
+ *   outside_dev[0..3]    += {a < lo, a > hi, p < lo, p > hi}
+ * The call writes all four outputs whole.  n_case == 0 or plane == 0 looks at no operand, writes zeros to the outputs that
+ * are not NULL and succeeds.
+ * Limits: 1 <= n_bin <= 128, 1 <= sub <= 32, lo and hi finite with hi > lo and scale finite (and not zero: hi - lo finite),
+ * n_case * plane < 2^40.
+ * Counts are integers: 32-bit integer adds into LDS tables, 64-bit integer atomic adds of a workgroup's counts to the
+ * outputs, exact in any order.  No floating-point atomics: a wave loops over the distinct coarse pairs (ia, ip) among its 64
+ * pixels, sums the addends of a pair's lanes in a fixed full-wave tree and adds them plainly into its own LDS table; a
+ * workgroup adds its four waves' tables in wave order and stores the result plainly into workspace_dev, and a fold launch
+ * adds the workgroups' partials in workgroup order.  The cut of the pixels into workgroups and waves depends on (n_case,
+ * plane) alone - cae_case_measures' (case, 4096-element chunk) items, dealt in consecutive runs to the waves of at most 1024 workgroups of four - so the
+ * same arguments give the same bits of cond_dev from run to run.  workspace_dev (8-byte aligned) holds
+ * cae_joint_hist_workspace_bytes bytes = workgroups * 2 * n_bin * 4 doubles (0 only for an empty or a refused call).
+ * Bad kinds, sizes or range, negative strides, misaligned outputs, a stride shorter than the plane, an operand reaching 2^60
+ * elements from its pointer, NULL or misaligned pointers or too small a workspace: CAE_ERR_ARG, nothing written. */
+int64_t cae_joint_hist_workspace_bytes(int64_t n_case, int64_t plane, int n_bin, int sub);
+int cae_joint_hist(const void* pred_dev, int pred_kind, int64_t pred_case_stride,
+                   const void* actual_dev, int actual_kind, int64_t actual_case_stride,
+                   int64_t n_case, int64_t plane, double lo, double hi, int n_bin, int sub,
+                   int64_t* joint_dev   /* [n_bin][n_bin]      joint[ia][ip]            */,
+                   int64_t* marg_dev    /* [2][n_bin * sub]    fine counts of a, of p   */,
+                   double*  cond_dev    /* [2][n_bin][4]       keyed by a-bin, by p-bin */,
+                   int64_t* outside_dev /* [4] {a < lo, a > hi, p < lo, p > hi}         */,
+                   void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 /* ---- scene apply (stateless): a box model applied to a whole scene ----------------------------- */
 
 /* A model maps an input box (c, h, w) to an output box (c_out, H, W) with H = h * sy, W = w * sx.  A scene variable is
