@@ -1,0 +1,228 @@
+"""The optional outputs of ModelEvaluator.build_html, none of them a reference feature: ensemble verification, case pages,
+structural similarity, skill against interpolation, per-pixel skill maps, power spectra and value distributions.
+
+Each is one Analysis of functions over the evaluator `ev`:
+    enabled(ev)                                     whether its option is on
+    check(ev)                                       raises the option's refusal; called from the evaluator's constructor
+    partition(ev, partition, ds, values, report)    inside build_html's loop over the partitions, after the per-case measures
+                                                    `values`: returns {variable: per-case array} to add to the data set
+    after(ev, parts, report)                        once after that loop; parts = [(partition, ds)] in page order
+Both put what utils/report.evaluation_report shows of the analysis into `report` under that function's keyword.  The operands
+come from the evaluator's cache (ev.operand, ev.operands), so a partition's target, prediction and input go to the GPU once
+whatever is switched on.  ANALYSES holds them in the order build_html runs them.
+"""
+import os
+from collections import namedtuple
+
+import numpy as np
+
+from ..case_ops import case_baseline, case_range, case_spectra, case_ssim, device_operand, joint_histogram, pixel_sums, render_cases
+from ..utils import baseline as baseline_scores
+from ..utils import distribution as distribution_curves
+from ..utils import ensemble_scores, skill_maps
+from ..utils import spectra as spectra_curves
+from ..utils import ssim as ssim_scores
+
+Analysis = namedtuple("Analysis", "enabled check partition after", defaults=(None, None, None))
+
+
+def _keep(ev, module, kind, partition, record, records, *extra):
+    """the common end of an analysis of one partition: <kind>_<partition>.json in the output folder by the module's
+    write_json, its line printed where it has one, and the record kept for the report"""
+    os.makedirs(ev.output_html_folder, exist_ok=True)
+    module.write_json(os.path.join(ev.output_html_folder, f"{kind}_{partition}.json"), record, *extra)
+    if hasattr(module, "line"):
+        print(module.line(partition, record))
+    records.append((partition, record))
+
+
+# ---- ensemble verification -------------------------------------------------------------------
+
+def check_ensemble(ev):
+    if ev.ensemble_size is not None and (int(ev.ensemble_size) != ev.ensemble_size or not 2 <= int(ev.ensemble_size) <= 64):
+        raise ValueError(f"ensemble_size must be an integer from 2 to 64, got {ev.ensemble_size!r}")
+
+
+def check_ensemble_model(ev):
+    if ev.ensemble_size is not None and type(ev.model).__name__ != "VarAEModel":
+        raise ValueError(f"ensemble_size needs a VarAEModel (train_cae --method var): {ev.model_path} holds a "
+                         f"{type(ev.model).__name__}")
+
+
+def _ensemble(ev, partition, ds, values, report):
+    """ensemble_size=K (cli/verify_ensemble.py; a VarAEModel only) verifies the model's K-member ensemble against the target
+    per partition (VarAEModel.verify_ensemble, cae_ensemble_verify on the GPU): ensemble_<partition>.json with the scores,
+    rank counts, K and seed (strict JSON: a score that is not finite is null), a per-case crps variable beside mae / mse in
+    the data set, and the report's "Ensemble verification" section."""
+    scores = ev.model.verify_ensemble(ds, ev.model.get_input_variable_names(), ev.output_variable, int(ev.ensemble_size),
+                                      ev.ensemble_seed)
+    record = {k: v for (k, v) in scores.items() if k not in ("case_sums", "case_crps")}
+    record["mae"] = float(np.mean(values["mae"])) if len(values["mae"]) else float("nan")
+    _keep(ev, ensemble_scores, "ensemble", partition, {**record, "case_crps": scores["case_crps"]},
+          report.setdefault("ensemble", []))
+    return {"crps": scores["case_crps"]}
+
+
+# ---- case pages ------------------------------------------------------------------------------
+
+def _case_pages(ev, partition, ds, values, report):
+    """the case pages (--x-coordinate, --y-coordinate and --time-coordinate all given): ModelEvaluator.case_summary"""
+    if ev.case_summary(partition, ds):
+        report.setdefault("case_links", {})[partition] = partition + "/index.html"
+    return {}
+
+
+# ---- structural similarity -------------------------------------------------------------------
+
+def _ssim(ev, partition, ds, values, report):
+    """ssim=True (cli/ssim.py) adds the structural scores: per partition and case the SSIM, the MS-SSIM (five scales, where
+    min(h, w) > 160) and the PSNR of channel 0 against the model's output normalisation range, from one cae_case_ssim pass on
+    the GPU (fp64, the VAE loss's definition with a rule for missing data; utils/ssim.py) and the mse
+    already measured: ssim_<partition>.json, per-case ssim / ms_ssim / psnr variables beside mae / mse in the data set, and
+    the report's "Structural similarity" section."""
+    (vmin, vmax) = (float(ev.model.normalisation_parameters[2]), float(ev.model.normalisation_parameters[3]))
+    (p, a) = ev.operands(partition, ds)
+    (h, w) = (int(a.shape[2]), int(a.shape[3]))
+    scores = ssim_scores.scores_from_sums(case_ssim(p, a, vmin, vmax), h, w, mse=values["mse"], vmin=vmin, vmax=vmax)
+    _keep(ev, ssim_scores, "ssim", partition, ssim_scores.summary(scores, h, w, vmin, vmax), report.setdefault("ssim", []))
+    return {k: scores[k] for k in ("ssim", "ms_ssim", "psnr")}
+
+
+# ---- skill against interpolating the input ---------------------------------------------------
+
+def check_baseline(ev):
+    if ev.baseline and ev.baseline_mode not in baseline_scores.MODES:
+        raise ValueError(f"baseline_mode must be one of {', '.join(baseline_scores.MODES)}, got {ev.baseline_mode!r}")
+
+
+def _baseline(ev, partition, ds, values, report):
+    """baseline=True (cli/baseline.py) answers whether the model is better than interpolating its own input: channel 0 of
+    baseline_variable (default: the model's first input variable) is interpolated to the target's grid (baseline_mode
+    "nearest", "bilinear" or "bicubic", torch's align_corners=False formulas) inside the kernel that compares it, one
+    cae_case_baseline pass on the GPU (fp64; utils/baseline.py): baseline_<partition>.json with the
+    pooled and per-case skill 1 - model_mse / baseline_mse, per-case baseline_mse / skill variables beside mae / mse in the
+    data set, and the report's "Skill against interpolation" section."""
+    name = ev.baseline_variable
+    if name not in ds or len(ds[name].shape) != 4:
+        raise ValueError(f"baseline variable {name!r} is not a 4-dimensional variable of the {partition} data set")
+    (low, (p, a)) = (ev.operand(partition, ds, name), ev.operands(partition, ds))
+    record = baseline_scores.summary(case_baseline(low, p, a, mode=ev.baseline_mode), ev.baseline_mode, name, low.shape[2:],
+                                     a.shape[2:])
+    _keep(ev, baseline_scores, "baseline", partition, record, report.setdefault("baseline", []))
+    return {"baseline_mse": np.asarray(record["case_baseline_mse"], dtype=np.float64),
+            "skill": np.asarray(record["case_skill"], dtype=np.float64)}
+
+
+# ---- per-pixel skill maps --------------------------------------------------------------------
+
+def _skill_shift(ev):
+    """the midpoint of the model's output normalisation range, or 0.0 when that is not finite: the sums' second
+    moments are taken about it"""
+    try:
+        mid = 0.5 * (float(ev.model.normalisation_parameters[2]) + float(ev.model.normalisation_parameters[3]))
+    except (TypeError, ValueError, IndexError):
+        return 0.0
+    return mid if np.isfinite(mid) else 0.0
+
+
+def _skill_coordinates(ev, ds, dims):
+    """{name: (dimension, values, attrs)} of the y / x coordinate variables that are 1-D along the target's image
+    dimensions"""
+    found = {}
+    for (name, dim) in ((ev.y_coordinate, dims[0]), (ev.x_coordinate, dims[1])):
+        if name and name in ds and tuple(ds[name].dims) == (dim,):
+            found[name] = (dim, np.asarray(ds[name].values), dict(getattr(ds[name], "attrs", {})))
+    return found
+
+
+def _skill_maps(ev, parts, report):
+    """skill_maps=True (cli/skill_maps.py) adds the transposed reduction: per partition the per-pixel count, bias, mae, rmse,
+    correlation and sd_ratio of channel 0 over the cases, from two streaming passes over the operands on the GPU
+    (cae_pixel_sums about the midpoint of the output normalisation range, then cae_pixel_sums_about each pixel's means for
+    the variances; utils/skill_maps.py), written as skill_<partition>.nc beside index.html and drawn on maps/index.html,
+    which the report then links.  The six maps of a partition go to the GPU as six one-channel cases and are ranged and
+    drawn by the case pages' kernels; ranges go over both partitions (count over [0, largest number of cases], bias over
+    +-max|bias|)."""
+    target = ev.output_variable
+    shift = _skill_shift(ev)
+    drawn = []
+    for (partition, ds) in parts:
+        (p, a) = ev.operands(partition, ds)
+        sums = pixel_sums(p, a, shift)
+        # the second moments once more about each pixel's own means: variances without the cancellation
+        centred = pixel_sums(p, a, skill_maps.pixel_means(sums, shift))
+        maps = skill_maps.maps_from_sums(sums, centred)
+        dims = tuple(ds[target].dims[-2:])
+        skill_maps.write_netcdf(os.path.join(ev.output_html_folder, f"skill_{partition}.nc"), maps, dims,
+                                _skill_coordinates(ev, ds, dims))
+        flip = bool(ev.y_coordinate) and ev.flip_y(ds, target)
+        drawn.append((partition, int(ds[target].shape[0]), device_operand(skill_maps.stack_maps(maps)), flip))
+    n_case = max(d[1] for d in drawn)
+    ranges = {}
+    for (k, name) in enumerate(skill_maps.MAPS):
+        ranges[name] = skill_maps.map_range(name, [case_range(op.tensor[k:k + 1]) for (_, _, op, _) in drawn], n_case)
+    pages = [(partition, n, [(name, *ranges[name], render_cases(op, *ranges[name], cases=[k], flip_y=flip)[0])
+                             for (k, name) in enumerate(skill_maps.MAPS)]) for (partition, n, op, flip) in drawn]
+    skill_maps.write_maps_page(os.path.join(ev.output_html_folder, "maps"), pages)
+    report["maps_link"] = "maps/index.html"
+
+
+# ---- power spectra ---------------------------------------------------------------------------
+
+def _spectra(ev, parts, report):
+    """spectra=True (cli/spectra.py) adds the reduction along scale: per partition the radially binned power spectra of
+    prediction and target, their ratio, the spectral coherence and the error spectrum of channel 0 from one cae_case_spectra
+    pass on the GPU (a direct fp64 DFT of every case; utils/spectra.py), written as
+    spectra_<partition>.json and drawn on spectra/index.html, which the report then links.  Every rank would compute all
+    cases: the pass is not sharded."""
+    found = []
+    for (partition, ds) in parts:
+        (p, a) = ev.operands(partition, ds)
+        (h, w) = (int(a.shape[2]), int(a.shape[3]))
+        _keep(ev, spectra_curves, "spectra", partition, spectra_curves.curves_from_sums(*case_spectra(p, a), h, w), found, h, w)
+    spectra_curves.write_page(os.path.join(ev.output_html_folder, "spectra"), found)
+    report["spectra_link"] = "spectra/index.html"
+
+
+# ---- value distributions ---------------------------------------------------------------------
+
+DISTRIBUTION_SUB = 8        # fine bins of a coarse bin: 1024 fine bins at the default 128
+
+
+def check_distribution(ev):
+    if ev.distribution and (int(ev.distribution_bins) != ev.distribution_bins or not 1 <= int(ev.distribution_bins) <= 128):
+        raise ValueError(f"distribution_bins must be an integer from 1 to 128, got {ev.distribution_bins!r}")
+
+
+def _distribution(ev, parts, report):
+    """distribution=True (cli/distribution.py) adds the reduction along value: per partition the joint histogram of
+    prediction against target over distribution_bins (1 to 128) coarse bins, the two fine marginal histograms and the
+    per-bin error sums of channel 0 from one cae_joint_hist pass on the GPU (utils/distribution.py) over
+    the range of the finite values of target and prediction in the partitions present (cae_case_range; hi = lo + 1 where that
+    range is degenerate): distribution_<partition>.json with the conditional bias, reliability, quantiles, Wasserstein-1
+    distance, Perkins score and exceedance scores, distribution/index.html with the joint density and the curves, and the
+    report's "Value distribution" section."""
+    pairs = [(partition, *ev.operands(partition, ds)) for (partition, ds) in parts]
+    spans = [case_range(op) for (_, p, a) in pairs for op in (p, a)]
+    spans = [s for s in spans if s[2] > 0]
+    (lo, hi) = (min(s[0] for s in spans), max(s[1] for s in spans)) if spans else (0.0, 0.0)
+    if not (np.isfinite(hi - lo) and hi > lo and np.isfinite(ev.distribution_bins * DISTRIBUTION_SUB / (hi - lo))):
+        hi = lo + 1.0
+    found = []
+    for (partition, p, a) in pairs:
+        counts = joint_histogram(p, a, lo, hi, n_bin=int(ev.distribution_bins), sub=DISTRIBUTION_SUB)
+        curves = distribution_curves.curves_from_counts(*counts, lo, hi, n_pixels=int(a.shape[0]) * int(a.shape[2]) * int(a.shape[3]))
+        _keep(ev, distribution_curves, "distribution", partition, curves, found)
+    distribution_curves.write_page(os.path.join(ev.output_html_folder, "distribution"), found)
+    report["distribution"] = (found, "distribution/index.html")
+
+
+ENSEMBLE = Analysis(lambda ev: ev.ensemble_size is not None, check_ensemble, partition=_ensemble)
+CASE_PAGES = Analysis(lambda ev: ev.x_coordinate and ev.y_coordinate and ev.time_coordinate, partition=_case_pages)
+SSIM = Analysis(lambda ev: ev.ssim, partition=_ssim)
+BASELINE = Analysis(lambda ev: ev.baseline, check_baseline, partition=_baseline)
+SKILL_MAPS = Analysis(lambda ev: ev.skill_maps, after=_skill_maps)
+SPECTRA = Analysis(lambda ev: ev.spectra, after=_spectra)
+DISTRIBUTION = Analysis(lambda ev: ev.distribution, check_distribution, after=_distribution)
+# in the order build_html runs them: per partition ensemble, case pages, ssim, baseline; then skill maps, spectra, distribution
+ANALYSES = (ENSEMBLE, CASE_PAGES, SSIM, BASELINE, SKILL_MAPS, SPECTRA, DISTRIBUTION)

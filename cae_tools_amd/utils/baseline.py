@@ -6,19 +6,12 @@ DESIGN.md section 9 holds the definition of the interpolation and the counting r
 
 Host only: standard library and numpy.
 """
-import json
-import math
-
 import numpy as np
 
+from . import records
+from .records import ratio as _ratio, shown as _shown
+
 MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}        # CAE_INTERP_* of include/cae_hip.h
-
-
-def _ratio(num, den):
-    """num / den, NaN where den is 0"""
-    (num, den) = (np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64))
-    some = den != 0
-    return np.where(some, num / np.where(some, den, 1.0), np.nan)
 
 
 def scores_from_sums(sums):
@@ -37,13 +30,6 @@ def scores_from_sums(sums):
     scores["win_fraction"] = _ratio(sums[:, 5], n)
     scores["pixels"] = n.astype(np.int64)
     return scores
-
-
-def _stat(values, fn):
-    """fn over the values that are not NaN, NaN without one"""
-    v = np.asarray(values, dtype=np.float64)
-    v = v[~np.isnan(v)]
-    return float(fn(v)) if v.size else float("nan")
 
 
 def summary(sums, mode, variable, in_shape, out_shape):
@@ -65,7 +51,7 @@ def summary(sums, mode, variable, in_shape, out_shape):
             "pixels_counted": int(total[0]), "pixels_left_out": n_cases * plane - int(total[0]),
             "pooled_skill": float(pooled["skill"][0]), "baseline_mse": float(pooled["baseline_mse"][0]),
             "baseline_mae": float(pooled["baseline_mae"][0]), "model_mse": float(pooled["model_mse"][0]),
-            "mean_skill": _stat(skill, np.mean), "median_skill": _stat(skill, np.median),
+            "mean_skill": records.stat(skill, np.mean), "median_skill": records.stat(skill, np.median),
             "skill_positive": float(np.sum(skill[have] > 0)) / float(have.sum()) if have.any() else float("nan"),
             "win_fraction": float(pooled["win_fraction"][0]),
             "case_skill": skill.tolist(), "case_baseline_mse": scores["baseline_mse"].tolist(),
@@ -75,24 +61,12 @@ def summary(sums, mode, variable, in_shape, out_shape):
 
 def json_record(record):
     """the record as strict JSON values: a number that is not finite becomes null"""
-    def clean(v):
-        if isinstance(v, (list, tuple)):
-            return [clean(x) for x in v]
-        if isinstance(v, float) and not math.isfinite(v):
-            return None
-        return v
-    return {k: clean(v) for (k, v) in record.items()}
+    return records.json_record(record, (list, tuple))
 
 
 def write_json(path, record):
     """baseline_<partition>.json"""
-    with open(path, "w") as f:
-        json.dump(json_record(record), f, indent=1, allow_nan=False)
-    return path
-
-
-def _shown(v):
-    return format(v, ".6g") if math.isfinite(v) else ("inf" if v == math.inf else ("-inf" if v == -math.inf else "none"))
+    return records.write_json(path, json_record(record))
 
 
 def line(partition, record):

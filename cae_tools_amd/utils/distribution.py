@@ -9,24 +9,18 @@ distribution/index.html.  DESIGN.md section 9 holds the bin rule.
 Host only: standard library and numpy.
 """
 import base64
-import json
 import math
 import os
 
 import numpy as np
 
+from . import records
 from .case_pages import LEVELS, png_palette
+from .records import ratio as _ratio, shown as _shown
 from .report import STYLE, Document, svg_data_uri, svg_lines
 
 QUANTILES = (0.01, 0.05, 0.1, 0.25, 0.5, 0.75, 0.9, 0.95, 0.99)
 THRESHOLDS = ((0.05, "below"), (0.9, "above"), (0.95, "above"), (0.99, "above"))     # "above": at or above the edge
-
-
-def _ratio(num, den):
-    """num / den, NaN where den is 0"""
-    (num, den) = (np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64))
-    some = den != 0
-    return np.where(some, num / np.where(some, den, 1.0), np.nan)
 
 
 def _div(num, den):
@@ -156,29 +150,12 @@ def summary(curves):
 
 def json_record(curves):
     """the curves as strict JSON values: a number that is not finite becomes null"""
-    def clean(v):
-        if isinstance(v, dict):
-            return {k: clean(x) for (k, x) in v.items()}
-        if isinstance(v, (list, tuple)):
-            return [clean(x) for x in v]
-        if isinstance(v, float) and not math.isfinite(v):
-            return None
-        return v
-    return clean(dict(curves))
+    return records.json_record(curves, (dict, list, tuple))
 
 
 def write_json(path, curves):
     """distribution_<partition>.json: the curves and, under "summary", their scalars"""
-    with open(path, "w") as f:
-        json.dump(json_record({**curves, "summary": summary(curves)}), f, indent=1, allow_nan=False)
-    return path
-
-
-def _shown(v):
-    if v is None:
-        return "none"
-    v = float(v)
-    return format(v, ".6g") if math.isfinite(v) else ("inf" if v == math.inf else ("-inf" if v == -math.inf else "none"))
+    return records.write_json(path, json_record({**curves, "summary": summary(curves)}))
 
 
 def line(partition, curves):

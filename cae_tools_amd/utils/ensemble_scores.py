@@ -5,6 +5,8 @@ A = mean_k |m_k - a| and B = (1/K^2) S_{i<j} |m_i - m_j|; rank_counts is (K + 2,
 below = #{k: m_k < a} in bins 0 .. K (a tied pixel counted at its lowest rank) and the number of tied pixels in bin K + 1."""
 import numpy as np
 
+from . import records
+
 SUM_NAMES = ("n", "abs_error", "pair_distance", "squared_error_of_mean", "variance")
 
 
@@ -50,14 +52,9 @@ def json_record(scores, skip=()):
     """the scores as a dict that json.dump(..., allow_nan=False) takes: arrays become lists, numpy numbers Python's, and a
     value that is not finite (every score of a partition without a counted pixel, the crps of such a case) becomes None,
     JSON's null - strict JSON has no NaN token.  Keys in `skip` are left out."""
-    def plain(v):
-        if isinstance(v, np.ndarray):
-            return [plain(x) for x in v.tolist()]
-        if isinstance(v, (list, tuple)):
-            return [plain(x) for x in v]
-        if isinstance(v, (float, np.floating)):
-            return float(v) if np.isfinite(v) else None
-        if isinstance(v, np.integer):
-            return int(v)
-        return v
-    return {key: plain(v) for (key, v) in scores.items() if key not in skip}
+    return records.json_record({key: v for (key, v) in scores.items() if key not in skip}, (list, tuple, np.ndarray))
+
+
+def write_json(path, scores):
+    """ensemble_<partition>.json"""
+    return records.write_json(path, json_record(scores))

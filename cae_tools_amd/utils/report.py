@@ -209,6 +209,17 @@ ENSEMBLE_ROWS = (("crps", "crps"), ("fair crps", "fair_crps"), ("mean per-case m
                  ("rmse of the ensemble mean", "rmse_mean"), ("spread", "spread"), ("spread-skill ratio", "spread_skill"))
 
 
+def _section(body, title, records, heading, rows, plots=None):
+    """one optional analysis: the title, and per (partition, record) the heading "<partition>: <heading(record)>", the
+    table rows(record) and one image per plot, plots being {alt text after the partition: record -> SVG}"""
+    body.add("h2").text(title)
+    for (partition, rec) in records:
+        body.add("h3").text(f"{partition}: {heading(rec)}")
+        body.table(rows(rec))
+        for (alt, draw) in (plots or {}).items():
+            body.add("img", {"src": svg_data_uri(draw(rec)), "alt": f"{partition} {alt}"})
+
+
 def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None, ensemble=None,
                       spectra_link=None, ssim=None, baseline=None, distribution=None):
     """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
@@ -244,37 +255,29 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
     if spectra_link:
         body.add("p").add("a", {"href": spectra_link}).text("Power spectra of prediction against target")
     if ensemble:
-        body.add("h2").text("Ensemble verification")
-        for (partition, rec) in ensemble:
-            body.add("h3").text(f"{partition}: {rec['ensemble_size']} members, {rec['n']} pixels, {rec['tied']} tied")
-            body.table([["Score Name", "Score Value"]] + [[label, f"{float(rec[key]):0.6g}"] for (label, key) in ENSEMBLE_ROWS])
-            body.add("img", {"src": svg_data_uri(svg_rank_histogram(rec["rank_counts"], "rank histogram")),
-                             "alt": f"{partition} rank histogram"})
-            body.add("img", {"src": svg_data_uri(svg_histogram(rec["case_crps"], "crps")), "alt": f"{partition} crps histogram"})
+        _section(body, "Ensemble verification", ensemble,
+                 lambda rec: f"{rec['ensemble_size']} members, {rec['n']} pixels, {rec['tied']} tied",
+                 lambda rec: [["Score Name", "Score Value"]] + [[label, f"{float(rec[key]):0.6g}"] for (label, key) in ENSEMBLE_ROWS],
+                 {"rank histogram": lambda rec: svg_rank_histogram(rec["rank_counts"], "rank histogram"),
+                  "crps histogram": lambda rec: svg_histogram(rec["case_crps"], "crps")})
     if ssim:
         from . import ssim as ssim_scores
-        body.add("h2").text("Structural similarity")
-        for (partition, rec) in ssim:
-            body.add("h3").text(f"{partition}: {rec['n_counted']} of {rec['n_cases']} cases, {len(rec['scales'])} "
-                                f"scale{'s' if len(rec['scales']) != 1 else ''}")
-            body.table(ssim_scores.section_rows(rec))
-            body.add("img", {"src": svg_data_uri(svg_histogram(rec["case_ssim"], "ssim")), "alt": f"{partition} ssim histogram"})
+        _section(body, "Structural similarity", ssim,
+                 lambda rec: f"{rec['n_counted']} of {rec['n_cases']} cases, {len(rec['scales'])} "
+                             f"scale{'s' if len(rec['scales']) != 1 else ''}",
+                 ssim_scores.section_rows, {"ssim histogram": lambda rec: svg_histogram(rec["case_ssim"], "ssim")})
     if baseline:
         from . import baseline as baseline_scores
-        body.add("h2").text("Skill against interpolation")
-        for (partition, rec) in baseline:
-            body.add("h3").text(f"{partition}: {rec['mode']} interpolation of {rec['variable']}, {rec['in_shape'][0]} x "
-                                f"{rec['in_shape'][1]} to {rec['out_shape'][0]} x {rec['out_shape'][1]}, {rec['n_counted']} of "
-                                f"{rec['n_cases']} cases")
-            body.table(baseline_scores.section_rows(rec))
-            body.add("img", {"src": svg_data_uri(svg_histogram(rec["case_skill"], "skill")), "alt": f"{partition} skill histogram"})
+        _section(body, "Skill against interpolation", baseline,
+                 lambda rec: f"{rec['mode']} interpolation of {rec['variable']}, {rec['in_shape'][0]} x {rec['in_shape'][1]} to "
+                             f"{rec['out_shape'][0]} x {rec['out_shape'][1]}, {rec['n_counted']} of {rec['n_cases']} cases",
+                 baseline_scores.section_rows, {"skill histogram": lambda rec: svg_histogram(rec["case_skill"], "skill")})
     if distribution:
         from . import distribution as distribution_curves
         (records, link) = distribution
-        body.add("h2").text("Value distribution")
-        for (partition, rec) in records:
-            body.add("h3").text(f"{partition}: {rec['pairs']} pixel pairs, {rec['n_bin']} bins over [{rec['lo']:.6g}, {rec['hi']:.6g}]")
-            body.table(distribution_curves.section_rows(rec))
+        _section(body, "Value distribution", records,
+                 lambda rec: f"{rec['pairs']} pixel pairs, {rec['n_bin']} bins over [{rec['lo']:.6g}, {rec['hi']:.6g}]",
+                 distribution_curves.section_rows)
         if link:
             body.add("p").add("a", {"href": link}).text("Value distribution of prediction against target")
     if parameters or history:

@@ -6,12 +6,12 @@ page spectra/index.html.  DESIGN.md section 9 holds the definition.
 
 Host only: standard library and numpy; the table is made in Python integers, so no bin depends on a rounding.
 """
-import json
 import math
 import os
 
 import numpy as np
 
+from . import records
 from .report import Document, STYLE, svg_data_uri, svg_lines
 
 RATIO_THRESHOLD = 0.5        # effective resolution: the lowest bin whose power ratio falls below it
@@ -95,20 +95,18 @@ def curves_from_sums(sums, counted, h, w):
 
 def json_record(curves, h, w):
     """the curves as strict JSON values: a number that is not finite becomes null"""
-    def clean(v):
-        if isinstance(v, list):
-            return [clean(x) for x in v]
-        if isinstance(v, float) and not math.isfinite(v):
-            return None
-        return v
-    return {**{k: clean(v) for (k, v) in curves.items()}, "h": int(h), "w": int(w)}
+    return {**records.json_record(curves, (list,)), "h": int(h), "w": int(w)}
 
 
 def write_json(path, curves, h, w):
     """spectra_<partition>.json: the curves, n_cases, n_counted, h, w and effective_resolution"""
-    with open(path, "w") as f:
-        json.dump(json_record(curves, h, w), f, indent=1, allow_nan=False)
-    return path
+    return records.write_json(path, json_record(curves, h, w))
+
+
+def line(partition, curves):
+    """spectra <partition>: effective_resolution <x|none> pixels, <n_counted>/<n> cases"""
+    return (f"spectra {partition}: effective_resolution {records.shown(curves['effective_resolution'])} pixels, "
+            f"{curves['n_counted']}/{curves['n_cases']} cases")
 
 
 def _log10(values):

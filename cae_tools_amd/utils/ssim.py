@@ -6,10 +6,11 @@ so the MS-SSIM of a `--method var` model is the quantity it was trained on.
 
 Host only: standard library and numpy.
 """
-import json
-import math
+import functools
 
 import numpy as np
+
+from . import records
 
 WIN_SIZE = 11
 MAX_SCALES = 5
@@ -81,13 +82,6 @@ def scores_from_sums(sums, h, w, mse=None, vmin=0.0, vmax=1.0):
     return {"ssim": ssim, "ms_ssim": ms, "psnr": psnr, "windows": n.astype(np.int64)}
 
 
-def _mean(values):
-    """the mean of the values that are not NaN, NaN without one"""
-    v = np.asarray(values, dtype=np.float64)
-    v = v[~np.isnan(v)]
-    return float(np.mean(v)) if v.size else float("nan")
-
-
 def summary(scores, h, w, vmin, vmax):
     """one partition's record: n_cases, h, w, vmin, vmax, the scales' shapes, n_counted (cases with an ssim) and
     n_counted_ms (cases with an ms_ssim), the means of ssim, ms_ssim and psnr over the cases that have the score, and the
@@ -96,31 +90,22 @@ def summary(scores, h, w, vmin, vmax):
     return {"n_cases": int(scores["ssim"].shape[0]), "h": int(h), "w": int(w), "vmin": float(vmin), "vmax": float(vmax),
             "scales": [list(s) for s in scale_shapes(h, w, n_scale)],
             "n_counted": int(np.sum(~np.isnan(scores["ssim"]))), "n_counted_ms": int(np.sum(~np.isnan(scores["ms_ssim"]))),
-            "ssim": _mean(scores["ssim"]), "ms_ssim": _mean(scores["ms_ssim"]), "psnr": _mean(scores["psnr"]),
+            "ssim": records.stat(scores["ssim"]), "ms_ssim": records.stat(scores["ms_ssim"]), "psnr": records.stat(scores["psnr"]),
             "case_ssim": scores["ssim"].tolist(), "case_ms_ssim": scores["ms_ssim"].tolist(),
             "case_psnr": scores["psnr"].tolist(), "windows": scores["windows"].tolist()}
 
 
 def json_record(record):
     """the record as strict JSON values: a number that is not finite becomes null"""
-    def clean(v):
-        if isinstance(v, (list, tuple)):
-            return [clean(x) for x in v]
-        if isinstance(v, float) and not math.isfinite(v):
-            return None
-        return v
-    return {k: clean(v) for (k, v) in record.items()}
+    return records.json_record(record, (list, tuple))
 
 
 def write_json(path, record):
     """ssim_<partition>.json"""
-    with open(path, "w") as f:
-        json.dump(json_record(record), f, indent=1, allow_nan=False)
-    return path
+    return records.write_json(path, json_record(record))
 
 
-def _shown(v):
-    return format(v, ".6g") if math.isfinite(v) else ("inf" if v == math.inf else "none")
+_shown = functools.partial(records.shown, minus_inf="none")         # no score of this module is -inf
 
 
 def line(partition, record):

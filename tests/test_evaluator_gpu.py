@@ -174,6 +174,65 @@ def data(tmp_path_factory):
     return root, paths
 
 
+ANALYSES = {"skill_maps": {"skill_maps": True}, "spectra": {"spectra": True}, "ssim": {"ssim": True},
+            "baseline": {"baseline": True, "baseline_mode": "bilinear"}, "distribution": {"distribution": True, "distribution_bins": 32}}
+
+
+def test_analyses_together_equal_each_alone(tmp_path):
+    """The five analyses switched on together share their operands on the GPU; each alone uploads its own.  Every
+    <analysis>_test.json and skill_test.nc and every per-case variable is the same bytes either way, for a scored file and for
+    an unscored one whose prediction comes from apply_device."""
+    from cae_tools_amd.cli import apply_cae, train_cae
+    from cae_tools_amd.data import datagen
+    from cae_tools_amd.models.model_evaluator import ModelEvaluator
+    paths = {part: str(tmp_path / f"{part}.nc") for part in ("train", "test")}
+    for (part, seed) in (("train", 1234), ("test", 4321)):
+        datagen.generate("circle", 12, seed=seed).to_netcdf(paths[part])
+    (model, scored) = (str(tmp_path / "model"), str(tmp_path / "scored_test.nc"))
+    torch.manual_seed(0)
+    with redirect_stdout(io.StringIO()):
+        train_cae.main(["--train-inputs", paths["train"], "--test-inputs", paths["test"], "--model-folder", model,
+                        "--input-variables", "lowres", "--output-variable", "hires", "--method", "conv", "--nr-epochs", "2",
+                        "--batch-size", "6", "--latent-size", "4", "--fc-size", "16"])
+        apply_cae.main([paths["test"], scored, "--model-folder", model])
+
+    class Recording(ModelEvaluator):
+        def build_html(self, case_dimension, train_ds, test_ds, model_metrics):
+            before = set(test_ds.keys())
+            super().build_html(case_dimension, train_ds, test_ds, model_metrics)
+            self.added = {k: np.asarray(test_ds[k].values).tobytes() for k in test_ds.keys() if k not in before}
+
+    def run(name, source, options):
+        """(the files {name: bytes} an analysis writes per partition, the per-case variables {name: bytes})"""
+        out = str(tmp_path / f"report_{name}")
+        with redirect_stdout(io.StringIO()):
+            ev = Recording([], [source], output_html_folder=out, model_path=model, **options)
+            ev.run()
+        files = {}
+        for f in sorted(os.listdir(out)):
+            if f.endswith("_test.json") or f == "skill_test.nc":
+                with open(os.path.join(out, f), "rb") as fh:
+                    files[f] = fh.read()
+        return files, ev.added
+
+    sources = {"scored": scored, "unscored": paths["test"]}
+    together = {kind: run(f"all_{kind}", source, {k: v for o in ANALYSES.values() for (k, v) in o.items()})
+                for (kind, source) in sources.items()}
+    for (kind, (files, added)) in together.items():
+        assert sorted(files) == ["baseline_test.json", "distribution_test.json", "skill_test.nc", "spectra_test.json", "ssim_test.json"]
+        # the unscored data set also gets the prediction apply_device has made
+        assert sorted(added) == sorted(["baseline_mse", "mae", "ms_ssim", "mse", "psnr", "skill", "ssim"]
+                                       + ["model_output"] * (kind == "unscored"))
+    for (k, (name, options)) in enumerate(ANALYSES.items()):
+        kind = ("scored", "unscored")[k % 2]
+        (files, added) = run(f"{name}_{kind}", sources[kind], options)
+        assert len(files) == 1 and {"mae", "mse"} <= set(added)
+        for (f, data) in files.items():
+            assert data == together[kind][0][f], f"{f} of {name} alone ({kind})"
+        for (v, data) in added.items():
+            assert data == together[kind][1][v], f"{v} of {name} alone ({kind})"
+
+
 @pytest.mark.parametrize("method", ["conv", "unet", "var", "linear"])
 def test_train_apply_evaluate(data, method):
     from cae_tools_amd.cli import apply_cae, evaluate_cae, train_cae
