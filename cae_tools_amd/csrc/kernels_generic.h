@@ -543,6 +543,12 @@ __device__ __forceinline__ float consume_grad(const StepTail& tl, const ShardSeg
     return (float)g;
 }
 
+// exp_avg.lerp_(grad, w) with w = 1 - beta1, in the form ATen's lerp takes for each weight: from the old value below one half,
+// from the gradient above, where (g - m) * w added to m would round at the size of m (beta1 = 0 gives g itself)
+__device__ __forceinline__ float adam_lerp(float mi, float g, float w) {
+    return w < 0.5f ? mi + (g - mi) * w : g - (g - mi) * (1.f - w);
+}
+
 __device__ __forceinline__ void step_tail(const StepTail& tl, long long gid, long long nthreads) {
     for (long long j = gid; j < tl.zero_extra_n; j += nthreads) tl.zero_extra[j] = 0.0;
     if (gid == 0 && tl.st) {
@@ -653,7 +659,7 @@ __device__ __forceinline__ void adam_conv0_body(const AdamConv0& c0, float* __re
     if (tid == 0) {
         float gr = (float)(tot * c0.scale);
         if (h.wd != 0.0) gr = fmaf((float)h.wd, w, gr);
-        mi = mi + (gr - mi) * (float)(1.0 - h.beta1);
+        mi = adam_lerp(mi, gr, (float)(1.0 - h.beta1));
         vi = vi * (float)h.beta2 + ((float)(1.0 - h.beta2) * gr) * gr;
         const float denom = sqrtf(vi) / corr[1] + (float)h.eps;
         p[pi] = w - corr[0] * (mi / denom);
@@ -760,7 +766,7 @@ __global__ void __launch_bounds__(256) k_adam(long long n, float* __restrict__ p
             g = (float)gacc;
         }
         if (h.wd != 0.0) g = fmaf((float)h.wd, w, g);
-        mi = mi + (g - mi) * (float)(1.0 - h.beta1);
+        mi = adam_lerp(mi, g, (float)(1.0 - h.beta1));
         vi = vi * b2 + ((float)(1.0 - h.beta2) * g) * g;
         const float denom = sqrtf(vi) / bc2_sqrt + (float)h.eps;
         p[i] = w - step_size * (mi / denom);

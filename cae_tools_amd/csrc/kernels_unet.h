@@ -1073,13 +1073,20 @@ __device__ __forceinline__ bool f32_grad(const F32Ranges& fr, long long i, const
 
 // step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), decay = 1 - lr * wd: formed on the host in fp64 (the step number is
 // a host-side count here), so that no workgroup starts with two fp64 pow() calls in front of its loads
+// omb1, omb2 = 1 - beta in fp64, rounded once, as the reference's scalars are: 1.f - (float)0.999 is 1.3e-5 short of 0.001, which
+// put every exp_avg_sq 1.3e-5 of itself low and moved every update 6e-6 of its size, all weights the same way
 struct AdamwConsts {
-    float step_size, bc2_sqrt, decay, b1, b2, eps;
+    float step_size, bc2_sqrt, decay, omb1, omb2, b2, eps;
 };
+// exp_avg.lerp_(grad, w) with w = 1 - beta1, in the form ATen's lerp takes for each weight: from the old value below one half,
+// from the gradient above, where (g - m) * w added to m would round at the size of m (beta1 = 0 gives g itself)
+__device__ __forceinline__ float adam_lerp(float mi, float g, float w) {
+    return w < 0.5f ? mi + (g - mi) * w : g - (g - mi) * (1.f - w);
+}
 __device__ __forceinline__ void adamw_one(float g, float& w, float& mi, float& vi, const AdamwConsts& c) {
     w *= c.decay;
-    mi = mi + (g - mi) * (1.f - c.b1);              // exp_avg.lerp_(grad, 1 - beta1)
-    vi = fmaf(g * g, 1.f - c.b2, vi * c.b2);        // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
+    mi = adam_lerp(mi, g, c.omb1);                  // exp_avg.lerp_(grad, 1 - beta1)
+    vi = fmaf(g * g, c.omb2, vi * c.b2);            // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
     const float denom = sqrtf(vi) / c.bc2_sqrt + c.eps;
     w -= c.step_size * (mi / denom);
 }

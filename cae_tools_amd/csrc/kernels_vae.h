@@ -742,7 +742,7 @@ __global__ void __launch_bounds__(256) k_adam_l2(long long n, float* __restrict_
         const float w = p[i];
         const float g = fmaf(wd, w, (float)gacc[i]);      // grad = grad.add(param, alpha=weight_decay)
         gacc[i] = 0.0;
-        const float mi = m[i] + (g - m[i]) * omb1;
+        const float mi = unet::adam_lerp(m[i], g, omb1);
         const float vi = fmaf(g * g, omb2, v[i] * b2);
         p[i] = w - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
         m[i] = mi;

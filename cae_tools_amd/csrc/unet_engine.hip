@@ -737,7 +737,8 @@ int gather_x(unet_engine* e, int which, const int32_t* perm, int64_t start, int 
 AdamwConsts adamw_consts(const unet_engine* e) {
     const Hyper& h = e->hyper;
     const double bc1 = 1.0 - pow(h.beta1, (double)e->step), bc2 = 1.0 - pow(h.beta2, (double)e->step);
-    return AdamwConsts{(float)(h.lr / bc1), (float)sqrt(bc2), (float)(1.0 - h.lr * h.wd), (float)h.beta1, (float)h.beta2, (float)h.eps};
+    return AdamwConsts{(float)(h.lr / bc1), (float)sqrt(bc2), (float)(1.0 - h.lr * h.wd), (float)(1.0 - h.beta1), (float)(1.0 - h.beta2),
+                       (float)h.beta2, (float)h.eps};
 }
 int adamw_blocks(const unet_engine* e) { return blocks_for((e->tab.n_param + 3) / 4, 2048); }
 

@@ -92,6 +92,7 @@ def test_adam_steps_follow_the_definition():
     from oracle import vae_oracle as vo
     (fc, latent, B) = (12, 4, 4)
     (spec, enc, dec, x, t) = _setup((12, 12), (176, 176), fc, latent, B, seed=8)
+    init = {pre + k: v.detach().clone().numpy() for (pre, m) in (("enc/", enc), ("dec/", dec)) for k, v in m.state_dict().items()}
     o = vo.VaeOracle(spec.save(), enc.state_dict(), dec.state_dict(), lr=1e-3, weight_decay=1e-5, seed=2)
     eng = _engine(spec, enc, dec, fc, latent, B, lr=1e-3, weight_decay=1e-5, seed=2)
     eng.set_dataset(0, x, t)
@@ -102,12 +103,45 @@ def test_adam_steps_follow_the_definition():
     np.testing.assert_allclose(np.array(got)[:, :3], np.array(want), rtol=5e-3, atol=1e-6)
     (e_sd, d_sd) = eng.export_state()
     ref = o.state()
-    for (pre, sd) in (("enc/", e_sd), ("dec/", d_sd)):
+    # ... a bound an optimiser that does nothing meets as well.  So, as test_adam_steps_free_running (tests/test_hip_parity.py)
+    # asks of the ConvAE's free-running steps: 99 % of every parameter tensor within a tenth of that bound, which a tensor that
+    # did not move (every weight three rates from the definition's) misses five times over.  Not held to it: a bias in front
+    # of a BatchNorm, whose gradient is rounding noise that Adam turns into steps of +-lr.
+    # Why a quantile and no maximum.  Measured on an MI355X against the same three steps of the definition in fp64: 26 of the 27
+    # tensors lie within 3x the fp32 definition's own distance + 3e-6 (the per-step Adam criterion of tests/test_hip_parity.py,
+    # summed over three steps), most within 3x alone; dec/decoder_conv.0.weight has one element 1.48e-5 from fp64 where the fp32
+    # definition's worst is 1.9e-6 (bound 8.8e-6), of a movement of 3.0e-3.  Adam's update is lr m / (sqrt(v) + eps), and where
+    # a gradient of rounding size changes sign between steps |m| / sqrt(v) is decided by the rounding of the gradient: the
+    # error of such an element goes as 1 / |g|, the maximum over a tensor is that of a heavy-tailed sample, and two fp32
+    # evaluations differ in it by more than any fixed factor.  The lines below print both figures and the bias-corrected
+    # |m| / sqrt(v) of the fp64 definition at the worst element: 1 for a steady gradient, 0.13 at that element, 0.42 - 1 at the
+    # other tensors' worst.  The optimiser kernels' own arithmetic is held element by element in
+    # tests/test_optim_elementwise_gpu.py.
+    o64 = vo.VaeOracle(spec.save(), enc.state_dict(), dec.state_dict(), lr=1e-3, weight_decay=1e-5, seed=2, dtype=torch.float64)
+    for _ in range(3):
+        o64.train_step(x.double(), t.double())
+    ref64 = o64.state()
+    last_bias = "dec/decoder_conv.%d.bias" % (3 * (len(spec.get_output_layers()) - 1))
+    bound = 3 * 2.1e-3                                                           # 3 Adam steps of lr 1e-3
+    for (pre, sd, params64) in (("enc/", e_sd, o64.enc), ("dec/", d_sd, o64.dec)):
         for k, v in sd.items():
             if k.endswith("num_batches_tracked"):
                 assert int(v) == 3
-            else:
-                assert np.abs(v.numpy() - ref[pre + k].numpy()).max() <= 3 * 2.1e-3, k   # 3 Adam steps of lr 1e-3
+                continue
+            d = np.abs(v.numpy() - ref[pre + k].numpy()).reshape(-1)
+            assert d.max() <= bound, k
+            if "running_" in k or _feeds_batchnorm(pre + k, last_bias):
+                continue
+            start = init[pre + k].astype(np.float64)
+            (moved, want32, want64) = (a.numpy().astype(np.float64) - start for a in (v, ref[pre + k], ref64[pre + k]))
+            worst = int(np.abs(moved - want64).argmax())
+            st = o64.optim.state[params64[k]]
+            steady = float(st["exp_avg"].reshape(-1)[worst].abs() / st["exp_avg_sq"].reshape(-1)[worst].sqrt())
+            steady *= (1 - 0.999 ** 3) ** 0.5 / (1 - 0.9 ** 3)                   # the bias corrections of step 3
+            print(f"[vae adam] {pre + k}: movement {float(np.abs(want64).max()):.3e}, |hip - fp64| {float(np.abs(moved - want64).max()):.3e}, "
+                  f"the fp32 definition's own {float(np.abs(want32 - want64).max()):.3e}, |m| / sqrt(v) there {steady:.3f}, "
+                  f"99 % of |hip - fp32| below {float(np.quantile(d, 0.99)):.3e}")
+            assert np.quantile(d, 0.99) <= 0.1 * bound, pre + k
 
 
 def test_benchmark_geometry_cfg5():
