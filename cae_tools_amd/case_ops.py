@@ -1,5 +1,6 @@
 """The case kernels of libcae_hip (include/cae_hip.h) as functions, no engine needed: measures, per-pixel sums, spectra, SSIM,
-interpolation baseline, value distributions, ensemble verification, value range and rendered pages of channel 0 of (N, C, H, W) operands."""
+interpolation baseline, value distributions, skill by stratum, ensemble verification, value range and rendered pages of
+channel 0 of (N, C, H, W) operands."""
 import ctypes as C
 import math
 from contextlib import contextmanager
@@ -286,6 +287,56 @@ def joint_histogram(pred, actual, lo, hi, n_bin=128, sub=8, device=None):
         check(lib.cae_joint_hist(*p.args(), *a.args(), n, plane, lo, hi, n_bin, sub, joint.data_ptr(), marg.data_ptr(),
                                  cond.data_ptr(), outside.data_ptr(), ws.data_ptr(), need, stream))
         return joint.cpu().numpy(), marg.cpu().numpy(), cond.cpu().numpy(), outside.cpu().numpy()
+
+
+def strata_sums(pred, actual, strata, edges, shift=0.0, channel=0, device=None):
+    """The error sums of channel 0 conditioned on a third field (cae_strata_sums, include/cae_hip.h): (counts, sums) with
+    counts = {"members": (n_strata,) int64 pixels of the target grid per stratum, "pairs": (n_strata,) int64 of them with
+    prediction and target finite, "unclassified": int pixels whose stratifier is not finite} and sums (n_strata, 8) float64
+    {S d, S|d|, S d^2, S a', S p', S a'^2, S p'^2, S a'p'} over the pairs with d = p - a, a' = a - shift_a[k], p' = p -
+    shift_p[k].  strata: (N, C, sh, sw), whose plane `channel` covers the target's extent - the nearest source pixel is
+    taken by cae_case_baseline's "nearest" rule - or (N,) for one value per case.  edges: up to 63 finite, strictly
+    ascending numbers; the stratum of a value is the number of edges at or below it.  shift: one number, or a
+    (2, n_strata) array of per-stratum shifts for a and p.  Operands as case_baseline takes them.
+    utils/strata.scores_from_sums turns the sums into the scores per stratum."""
+    (device, p, a, n, h, w) = _pair("strata_sums", pred, actual, device)
+    s = device_operand(strata, device)
+    if len(s.shape) not in (1, 4) or s.shape[0] != n:
+        raise ValueError(f"strata_sums: a stratifier of (N, C, sh, sw) or (N,) with N = {n} expected, got {tuple(s.shape)}")
+    (c, sh, sw) = (int(s.shape[1]), int(s.shape[2]), int(s.shape[3])) if len(s.shape) == 4 else (1, 1, 1)
+    if int(channel) != channel or not 0 <= int(channel) < c:
+        raise ValueError(f"strata_sums: channel must be an integer from 0 to {c - 1}, got {channel!r}")
+    try:
+        edges = np.asarray(edges, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"strata_sums: edges must be numbers, got {edges!r}") from None
+    if edges.size > 63 or not np.isfinite(edges).all() or not (np.diff(edges) > 0).all():
+        raise ValueError(f"strata_sums: at most 63 finite, strictly ascending edges expected, got {edges.tolist()}")
+    n_strata = int(edges.size) + 1
+    if np.ndim(shift) != 0 and np.shape(shift) != (2, n_strata):
+        raise ValueError(f"strata_sums: per-stratum shifts of shape (2, {n_strata}) expected, got {np.shape(shift)}")
+    shifts = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, dtype=np.float64), (2, n_strata)))
+    if not np.isfinite(shifts).all():
+        raise ValueError("strata_sums: the shifts must be finite")
+    empty = {"members": np.zeros(n_strata, dtype=np.int64), "pairs": np.zeros(n_strata, dtype=np.int64), "unclassified": 0}
+    if n == 0 or h * w == 0:
+        return empty, np.zeros((n_strata, 8), dtype=np.float64)
+    if sh * sw == 0:
+        raise ValueError(f"strata_sums: a stratifier plane of at least one pixel expected, got {sh} x {sw}")
+    counts = torch.empty(2 * n_strata + 1, dtype=torch.int64, device=device)
+    sums = torch.empty((n_strata, 8), dtype=torch.float64, device=device)
+    lib = _lib.load()
+    (ws, need) = _workspace(device, lib.cae_strata_sums_workspace_bytes, n, h, w, n_strata)
+    (s_ptr, s_kind, s_stride) = s.args()
+    as_c = lambda v: v.ctypes.data_as(C.c_void_p)      # noqa: E731
+    with _stream(device) as stream:
+        check(lib.cae_strata_sums(*p.args(), *a.args(), s_ptr + int(channel) * sh * sw * s.elem_bytes, s_kind, s_stride, n, h, w,
+                                  sh, sw, as_c(edges) if edges.size else None, int(edges.size), as_c(shifts[0]), as_c(shifts[1]),
+                                  counts.data_ptr(), sums.data_ptr(), ws.data_ptr(), need, stream))
+        counts = counts.cpu().numpy()
+        sums = sums.cpu().numpy()
+    return {"members": counts[:n_strata].copy(), "pairs": counts[n_strata:2 * n_strata].copy(),
+            "unclassified": int(counts[2 * n_strata])}, sums
 
 
 def upsample(low, out_shape, mode="bicubic", device=None):

@@ -1,5 +1,6 @@
 """The optional outputs of ModelEvaluator.build_html, none of them a reference feature: ensemble verification, case pages,
-structural similarity, skill against interpolation, per-pixel skill maps, power spectra and value distributions.
+structural similarity, skill against interpolation, per-pixel skill maps, power spectra, value distributions and skill by
+stratum.
 
 Each is one Analysis of functions over the evaluator `ev`:
     enabled(ev)                                     whether its option is on
@@ -16,12 +17,15 @@ from collections import namedtuple
 
 import numpy as np
 
-from ..case_ops import case_baseline, case_range, case_spectra, case_ssim, device_operand, joint_histogram, pixel_sums, render_cases
+from ..case_ops import (case_baseline, case_range, case_spectra, case_ssim, device_operand, joint_histogram, pixel_sums, render_cases,
+                        strata_sums)
+from ..data.arrays import as_numpy
 from ..utils import baseline as baseline_scores
 from ..utils import distribution as distribution_curves
 from ..utils import ensemble_scores, skill_maps
 from ..utils import spectra as spectra_curves
 from ..utils import ssim as ssim_scores
+from ..utils import strata as strata_scores
 
 Analysis = namedtuple("Analysis", "enabled check partition after", defaults=(None, None, None))
 
@@ -217,6 +221,76 @@ def _distribution(ev, parts, report):
     report["distribution"] = (found, "distribution/index.html")
 
 
+# ---- skill by stratum ------------------------------------------------------------------------
+
+def check_strata(ev):
+    if not ev.strata:
+        return
+    if not ev.strata_variable:
+        raise ValueError("strata needs strata_variable, the name of the stratifier in the data set")
+    if ev.strata_edges is not None and ev.strata_classes is not None:
+        raise ValueError("strata_edges and strata_classes exclude each other")
+    if ev.strata_edges is not None:
+        strata_scores.check_edges(ev.strata_edges)
+    elif ev.strata_classes is not None:
+        if len(strata_scores.edges_from_classes(ev.strata_classes)[1]) > strata_scores.MAX_STRATA:
+            raise ValueError(f"at most {strata_scores.MAX_STRATA} strata expected, got {len(set(map(float, ev.strata_classes)))}")
+    elif int(ev.strata_count) != ev.strata_count or not 1 <= int(ev.strata_count) <= strata_scores.MAX_STRATA:
+        raise ValueError(f"strata_count must be an integer from 1 to {strata_scores.MAX_STRATA}, got {ev.strata_count!r}")
+
+
+def _strata_plane(op, ds, name, channel):
+    """what case_range, which reads channel 0 of (N, C, H, W), is given for the stratifier: the operand itself for channel 0
+    of a 4-D variable; else the one plane (a slice of the variable), or the values of a 1-D variable as (N, 1, 1, 1)"""
+    if len(op.shape) == 4 and channel == 0:
+        return op
+    values = as_numpy(ds[name])
+    return values.reshape(-1, 1, 1, 1) if values.ndim == 1 else values[:, channel:channel + 1]
+
+
+def _strata(ev, parts, report):
+    """strata=True (cli/strata.py) conditions the error on a variable that is neither target nor prediction: channel
+    strata_channel of strata_variable - 4-D with the case dimension first, on the target's grid or a coarser or finer one
+    over the same extent, or 1-D along the case dimension - cuts the pixels into strata by strata_edges, by strata_classes
+    (an edge midway between neighbouring classes) or into strata_count equal bins over the range of the stratifier's finite
+    values in the partitions present (cae_case_range).  Per partition two cae_strata_sums passes on the GPU (about the
+    midpoint of the output normalisation range, then about each stratum's own means for the variances; utils/strata.py,
+    DESIGN.md section 9): strata_<partition>.json with pixels, pairs, share, bias, mae, rmse, correlation, sd_ratio and the
+    share of the squared error per stratum and pooled, and the report's "Skill by stratum" section.  Every rank would
+    compute all cases: the pass is not sharded."""
+    (name, channel) = (ev.strata_variable, int(ev.strata_channel))
+    found = []
+    for (partition, ds) in parts:
+        if name not in ds or len(ds[name].shape) not in (1, 4) or ds[name].shape[0] != ds[ev.output_variable].shape[0]:
+            raise ValueError(f"strata variable {name!r} is not a variable of the {partition} data set with the case dimension "
+                             "first and 4 dimensions, or 1 along the cases")
+        if len(ds[name].shape) == 4 and not 0 <= channel < ds[name].shape[1]:
+            raise ValueError(f"strata_channel {channel} is not a channel of {name!r}, which has {ds[name].shape[1]}")
+        found.append((partition, ds, ev.operand(partition, ds, name), *ev.operands(partition, ds)))
+    names = None
+    if ev.strata_edges is not None:
+        edges = strata_scores.check_edges(ev.strata_edges)
+    elif ev.strata_classes is not None:
+        (edges, names) = strata_scores.edges_from_classes(ev.strata_classes)
+    else:
+        spans = [case_range(_strata_plane(s, ds, name, channel)) for (_, ds, s, _, _) in found]
+        spans = [sp for sp in spans if sp[2] > 0]
+        (lo, hi) = (min(sp[0] for sp in spans), max(sp[1] for sp in spans)) if spans else (0.0, 0.0)
+        edges = strata_scores.edges_from_count(lo, hi, int(ev.strata_count))
+    shift = _skill_shift(ev)
+    kept = []
+    for (partition, _, s, p, a) in found:
+        (counts, sums) = strata_sums(p, a, s, edges, shift, channel=channel)
+        # the second moments once more about each stratum's own means: variances without the cancellation
+        means = strata_scores.stratum_means(counts, sums, shift)
+        centred = strata_sums(p, a, s, edges, means, channel=channel)[1]
+        scores = strata_scores.scores_from_sums(counts, sums, centred, shift=shift, centred_shift=means)
+        in_shape = s.shape[2:] if len(s.shape) == 4 else (1, 1)
+        _keep(ev, strata_scores, "strata", partition,
+              strata_scores.summary(scores, name, channel, edges, names, in_shape, a.shape[2:]), kept)
+    report["strata"] = kept
+
+
 ENSEMBLE = Analysis(lambda ev: ev.ensemble_size is not None, check_ensemble, partition=_ensemble)
 CASE_PAGES = Analysis(lambda ev: ev.x_coordinate and ev.y_coordinate and ev.time_coordinate, partition=_case_pages)
 SSIM = Analysis(lambda ev: ev.ssim, partition=_ssim)
@@ -224,5 +298,7 @@ BASELINE = Analysis(lambda ev: ev.baseline, check_baseline, partition=_baseline)
 SKILL_MAPS = Analysis(lambda ev: ev.skill_maps, after=_skill_maps)
 SPECTRA = Analysis(lambda ev: ev.spectra, after=_spectra)
 DISTRIBUTION = Analysis(lambda ev: ev.distribution, check_distribution, after=_distribution)
-# in the order build_html runs them: per partition ensemble, case pages, ssim, baseline; then skill maps, spectra, distribution
-ANALYSES = (ENSEMBLE, CASE_PAGES, SSIM, BASELINE, SKILL_MAPS, SPECTRA, DISTRIBUTION)
+STRATA = Analysis(lambda ev: ev.strata, check_strata, after=_strata)
+# in the order build_html runs them: per partition ensemble, case pages, ssim, baseline; then skill maps, spectra, distribution,
+# strata
+ANALYSES = (ENSEMBLE, CASE_PAGES, SSIM, BASELINE, SKILL_MAPS, SPECTRA, DISTRIBUTION, STRATA)

@@ -18,9 +18,9 @@ index is 0 for NaN and 1 + round-half-up(254 * clamp((v - lo) / (hi - lo), 0, 1)
 (cae_render_cases) from the slabs as stored and from the prediction where it still lies in HBM.
 
 The optional analyses that are no reference feature - ensemble verification, structural similarity, skill against
-interpolation, per-pixel skill maps, power spectra and value distributions - are the units of evaluation_analyses.py,
-which build_html runs in their fixed order.  What they and the case pages read on the GPU comes from one operand cache
-(operand): a partition's variable is uploaded once per build_html, whatever is switched on.
+interpolation, per-pixel skill maps, power spectra, value distributions and skill by stratum - are the units of
+evaluation_analyses.py, which build_html runs in their fixed order.  What they and the case pages read on the GPU comes
+from one operand cache (operand): a partition's variable is uploaded once per build_html, whatever is switched on.
 """
 import json
 import os
@@ -45,7 +45,8 @@ class ModelEvaluator:
     def __init__(self, training_paths, testing_paths, output_html_folder="", model_output_variable="", model_path="",
                  database_path="", input_variables=[], sample_count=None, x_coordinate="", y_coordinate="",
                  time_coordinate="", skill_maps=False, ensemble_size=None, ensemble_seed=0, spectra=False, ssim=False,
-                 baseline=False, baseline_variable=None, baseline_mode="bicubic", distribution=False, distribution_bins=128):
+                 baseline=False, baseline_variable=None, baseline_mode="bicubic", distribution=False, distribution_bins=128,
+                 strata=False, strata_variable=None, strata_channel=0, strata_edges=None, strata_classes=None, strata_count=8):
         self.training_paths = list(training_paths) if training_paths else []
         self.testing_paths = list(testing_paths) if testing_paths else []
         self.output_html_folder = output_html_folder
@@ -65,8 +66,11 @@ class ModelEvaluator:
         (self.baseline, self.baseline_variable, self.baseline_mode) = (baseline, baseline_variable, baseline_mode)
         (self.distribution, self.distribution_bins) = (distribution, distribution_bins)
         (self.ensemble_size, self.ensemble_seed) = (ensemble_size, int(ensemble_seed))
-        for unit in (analyses.BASELINE, analyses.DISTRIBUTION, analyses.ENSEMBLE):      # the refusals come in this order,
-            unit.check(self)                                                            # all before the model is loaded
+        (self.strata, self.strata_variable, self.strata_channel) = (strata, strata_variable, strata_channel)
+        (self.strata_edges, self.strata_classes, self.strata_count) = (strata_edges, strata_classes, strata_count)
+        for unit in (analyses.BASELINE, analyses.DISTRIBUTION, analyses.ENSEMBLE,       # the refusals come in this order,
+                     analyses.STRATA):                                                  # all before the model is loaded
+            unit.check(self)
         self.model = load_model(self.model_path)
         analyses.check_ensemble_model(self)
         print(f"Evaluating model id={self.model.get_model_id()}")

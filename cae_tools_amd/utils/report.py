@@ -221,7 +221,7 @@ def _section(body, title, records, heading, rows, plots=None):
 
 
 def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None, ensemble=None,
-                      spectra_link=None, ssim=None, baseline=None, distribution=None):
+                      spectra_link=None, ssim=None, baseline=None, distribution=None, strata=None):
     """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
     metrics: {"test": {...}, "train": {...}} (either may be absent); measures: [(partition, {"mae": values, "mse": values})]
     in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}; maps_link: href of
@@ -234,7 +234,8 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
     against interpolation" section with the table of the pooled and per-case skill against the interpolated input and the
     histogram of the per-case skill; distribution: ([(partition, curves)] of utils/distribution.curves_from_counts, href of
     the value distribution page): a "Value distribution" section with the table of the conditional slope, quantile bias,
-    distances and exceedance scores, and the link."""
+    distances and exceedance scores, and the link; strata: [(partition, record)] of utils/strata.summary: a "Skill by stratum"
+    section with the table of the scores per stratum and pooled and the bar chart of bias +- rmse per stratum."""
     doc = Document("Model Evaluation")
     doc.head.add("style").text(STYLE)
     body = doc.body
@@ -280,6 +281,13 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
                  distribution_curves.section_rows)
         if link:
             body.add("p").add("a", {"href": link}).text("Value distribution of prediction against target")
+    if strata:
+        from . import strata as strata_scores
+        _section(body, "Skill by stratum", strata,
+                 lambda rec: f"{rec['n_strata']} strata of {rec['variable']}, {rec['pooled']['pairs']} pixel pairs, "
+                             f"{rec['unclassified']} pixels unclassified",
+                 strata_scores.section_rows,
+                 {"skill by stratum": lambda rec: strata_scores.svg_bars(rec, f"bias +- rmse by {rec['variable']}")})
     if parameters or history:
         body.add("h2").text("Training Summary")
     if parameters:

@@ -632,6 +632,52 @@ int cae_joint_hist(const void* pred_dev, int pred_kind, int64_t pred_case_stride
                    int64_t* outside_dev /* [4] {a < lo, a > hi, p < lo, p > hi}         */,
                    void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- skill by stratum (stateless): the error sums conditioned on a third field ------------------ */
+
+/* One pass over channel 0 of prediction p and target a, both (n_case, h, w) as stored, and a stratifier plane s of
+ * (n_case, sh, sw): the error sums of the pixels of every stratum of s.  utils/strata.py forms bias, mae, rmse, correlation
+ * and the shares per stratum from them.
+ * Operands as cae_case_baseline takes them: CAE_ELEM_* kinds read as stored, big-endian kinds included; case i starts at
+ * element i * case_stride, any stride >= the plane, pointers aligned to their element size.
+ * Mapping: the stratifier covers the target's extent and is pixel-centred.  For output row y the source row is
+ * i = min((long)floor((y + 0.5) * ((double)sh / (double)h)), sh - 1), columns likewise, in fp64 with every operation rounded
+ * on its own: the CAE_INTERP_NEAREST rule of cae_case_baseline.  sh == h, sw == w is the identity, sh == sw == 1 one value
+ * per case; the ratios need not be integers and the axes may differ.
+ * Stratum: edges[n_edge] (host) are finite and strictly ascending, 0 <= n_edge <= 63, n_strata = n_edge + 1.  The stratum of a
+ * finite value v is k = #{j : edges[j] <= v}, compared in fp64: stratum 0 lies below the first edge, the last at or above
+ * the last edge, -0.0 counts as 0.0; n_edge == 0 is one stratum that holds everything.
+ * For every pixel of the target grid: s not finite -> unclassified += 1; else members[k] += 1, and where p and a are both
+ * finite pairs[k] += 1 and, with d = p - a, a' = a - shift_a[k], p' = p - shift_p[k] (host arrays of n_strata finite shifts),
+ *   sums_dev[k][0..7] += {d, |d|, d*d, a', p', a'*a', p'*p', a'*p'}
+ * every subtraction and product rounded on its own, nothing contracted.  Sum members + unclassified == n_case * h * w.
+ *   counts_dev[0 .. n_strata)            members
+ *   counts_dev[n_strata .. 2 n_strata)   pairs
+ *   counts_dev[2 n_strata]               unclassified
+ * Both outputs are written whole.  n_case == 0, h == 0 or w == 0 looks at no operand, writes zeros to the outputs that are
+ * not NULL and succeeds.
+ * Counts are 64-bit integers, added to the outputs with integer atomics: exact in any order.  No floating-point atomics: a
+ * wave takes 64 consecutive target pixels, loops over the distinct strata among them, sums the addends of a stratum's lanes
+ * in a fixed full-wave tree and adds them plainly into its own LDS table; a workgroup adds its four waves' tables in wave
+ * order and stores the result plainly into workspace_dev, and a fold launch adds the workgroups' partials in workgroup
+ * order.  The cut of the pixels into workgroups and waves - items of (case, 4096 consecutive pixels), dealt in consecutive
+ * runs to the waves of at most 1024 workgroups of four - depends on (n_case, h, w) alone, so the same arguments give the same
+ * bits of sums_dev from run to run.  workspace_dev (8-byte aligned) holds cae_strata_sums_workspace_bytes bytes =
+ * workgroups * n_strata * 8 doubles (0 only for an empty or a refused call).
+ * Bad kinds, target sides outside 0 .. 2^30 or stratifier sides outside 1 .. 2^30, n_edge outside 0 .. 63, negative strides,
+ * misaligned outputs, NULL pointers, edges that are not finite or not strictly ascending, a shift that is not finite, a
+ * stride shorter than its plane, an operand reaching 2^60 elements from its pointer, misaligned pointers or too small a
+ * workspace: CAE_ERR_ARG, nothing written. */
+int64_t cae_strata_sums_workspace_bytes(int64_t n_case, int64_t h, int64_t w, int n_strata);
+int cae_strata_sums(const void* pred_dev, int pred_kind, int64_t pred_case_stride,
+                    const void* actual_dev, int actual_kind, int64_t actual_case_stride,
+                    const void* strata_dev, int strata_kind, int64_t strata_case_stride,
+                    int64_t n_case, int64_t h, int64_t w, int64_t sh, int64_t sw,
+                    const double* edges /* host [n_edge] */, int n_edge,
+                    const double* shift_a /* host [n_edge + 1] */, const double* shift_p /* host [n_edge + 1] */,
+                    int64_t* counts_dev /* [2 * (n_edge + 1) + 1] members, pairs, unclassified */,
+                    double*  sums_dev   /* [n_edge + 1][8] */,
+                    void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 /* ---- scene apply (stateless): a box model applied to a whole scene ----------------------------- */
 
 /* A model maps an input box (c, h, w) to an output box (c_out, H, W) with H = h * sy, W = w * sx.  A scene variable is
