@@ -160,6 +160,16 @@ class SpecPlan(EngineBase):
         self.in_shape = tuple(enc[0]["input_dimensions"])
         self.out_shape = tuple(dec[-1]["output_dimensions"])
 
+    def _plan_report(self, batch, train):
+        """PREFIX + debug_plan parsed, no GPU needed: {first word of a line: {key: value of its key=value fields}}"""
+        buf = C.create_string_buffer(1 << 16)
+        check(self._c("debug_plan")(self.handle, int(batch), 1 if train else 0, buf, len(buf)))
+        plan = {}
+        for line in buf.value.decode().splitlines():
+            (name, *fields) = line.split()
+            plan[name] = dict(f.split("=", 1) for f in fields)
+        return plan
+
     def view(self, name):
         """torch view (device) of a named tensor, e.g. 'dec/decoder_conv.0.weight'"""
         (arena, off, numel, shape) = self.tensors[name]

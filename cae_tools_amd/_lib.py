@@ -199,6 +199,8 @@ SIGNATURES = {
                                             ALLREDUCE_FN, _P]),
     "vae_eval_step_sync": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, ALLREDUCE_FN, _P]),
     "vae_debug_read": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
+    "vae_debug_plan": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p, C.c_int64]),
+    "vae_trunk_debug_read": (C.c_int64, [_P, C.c_char_p, C.c_int, _P, C.c_int64]),
     "vae_gauss_window": (None, [_P]),
     # ---- include/cae_linear.h ----
     "lin_engine_create": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),

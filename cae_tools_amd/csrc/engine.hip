@@ -770,6 +770,10 @@ int64_t cae_debug_read(cae_engine* e, const char* what, int index, void* host_ou
     } else if (w == "glast") {
         src = e->ws + e->off_glast;
         n = mb * e->dec.back().out_elems();
+    } else if (w == "vgz") {   // trunk mode: dL/dz as Linear 2's backward stored it, before the reparameterisation hook
+        if (!e->variational) return fail(CAE_ERR_ARG, "'vgz' is the variational trunk's");
+        src = e->ws + e->off_vgz;
+        n = mb * e->latent;
     } else if (w == "latent") {
         src = e->ws + e->fc[1].act_off;
         n = mb * e->fc[1].nout;

@@ -556,6 +556,15 @@ bool enc_conv0_in_adam_ok(const cae_engine* e, const StepArgs& a, const ConvLaye
     return a.adam_follows && e->x_published && enc_conv0_fits_adam(e, a, L);
 }
 
+// The input-gradient GEMM of Linear i's backward pair (linear_bwd_pair: gin[b][:] = gout[b][:] W, contraction over the layer's
+// nout outputs, gout rows nout floats apart) on the burst variant of k_gemm16_pair (kernels_gemm.h gemm16_burst_body): every
+// operand read issued at kernel start.  It needs 16-byte rows of gout (nout a multiple of 4), at most kBurstSteps k-steps per
+// wave, and pays from 128 outputs on; Linear 0's input gradient carries the BatchNorm mask epilogue, which it does not have.
+bool linear_bwd_burst(const cae_engine* e, int i) {
+    const int K = e->fc[i].nout;
+    return i > 0 && K % 4 == 0 && K >= 128 && (K / 4 + 3) / 4 <= kBurstSteps;
+}
+
 // how head_stage_inputs (kernels_head.h) brings the batch to LDS without a permutation: one contiguous block of 16-byte loads,
 // 16-byte loads through the sample table, or scalar loads (inputs per sample no multiple of 4)
 const char* head_staging(const HeadArgs& h) {
@@ -663,9 +672,10 @@ int cae_debug_plan(const cae_engine* e, int batch, int train, char* out, int64_t
         TailArgs t;
         size_t lds = 0;
         const char* why = "";
+        bool tail_fused = false;
         if (!tr) {
             snprintf(line, sizeof line, "tail bwd=-\n");
-        } else if (tail_plan(e, a, t, lds, &why)) {
+        } else if ((tail_fused = tail_plan(e, a, t, lds, &why))) {
             const int rows = (batch + 15) / 16;
             snprintf(line, sizeof line, "tail bwd=fused rows=%d sums=%s g1=%d:%d g0=%d:%d gx=%d:%d w2=%d:%d w1=%d:%d w0=%d:%d lds=%zu\n", rows,
                      rows <= kStatShards ? "stored" : "added", t.sp_d[0].lg, t.sp_d[0].per, t.sp_d[1].lg, t.sp_d[1].per, t.sp_d[2].lg,
@@ -674,6 +684,12 @@ int cae_debug_plan(const cae_engine* e, int batch, int train, char* out, int64_t
             snprintf(line, sizeof line, "tail bwd=layers why=%s\n", why);
         }
         s += line;
+        // the Linear backwards one by one (launch_backward): the GEMM pair and its input gradient's variant, or the generic kernels
+        for (int i = 3; tr && !tail_fused && i >= 0; i--) {
+            if (e->use_s2) snprintf(line, sizeof line, "fc%d bwd=pair burst=%d\n", i, (int)linear_bwd_burst(e, i));
+            else snprintf(line, sizeof line, "fc%d bwd=generic\n", i);
+            s += line;
+        }
     }
     if (tr) {
         // the encoder's backward (launch_backward): layer 0's weight gradient rides in the optimiser launch of a cae_train_step

@@ -510,8 +510,8 @@ int linear_bwd_pair(cae_engine* e, const StepArgs& a, int i, const ConvLayer& P)
         const int tiles_w = ((gw.M + 15) / 16) * ((gw.N + 15) / 16);
         ProfScope _p(e, "linear_bwd_pair_mfma", i, bytes_lin_bwd_pair(B, F));
         // the input gradient's contraction runs over nout: long for the last decoder Linear (576 at cfg2): burst variant
-        const bool burst = gd.epi != GE_BN_MASK && gd.sa_k == 1 && gd.sb_n == 1 && gd.K % 4 == 0 && gd.K >= 128 &&
-                           (gd.K / 4 + 3) / 4 <= kBurstSteps && gd.sa_m % 4 == 0;
+        // (gd as built above: unit strides along k in A and along n in B, A rows K floats apart, no BatchNorm mask but for i = 0)
+        const bool burst = linear_bwd_burst(e, i);
         if (burst && gemm16_burst_lds(gd.K) > lds) lds = gemm16_burst_lds(gd.K);
         hipLaunchKernelGGL(k_gemm16_pair, dim3(tiles_w + tiles_d), dim3(256), lds, e->stream, gw, gd, tiles_w, burst ? 1 : 0);
     }

@@ -390,5 +390,13 @@ int vae_debug_read(vae_engine* e, const char* what, float* out, int64_t count) {
     HIP_TRY(hipMemcpy(out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
     return CAE_OK;
 }
+int vae_debug_plan(const vae_engine* e, int batch, int train, char* out, int64_t out_bytes) {
+    if (!e) return fail(CAE_ERR_ARG, "vae_debug_plan: null engine");
+    return cae_debug_plan(e->trunk, batch, train, out, out_bytes);
+}
+int64_t vae_trunk_debug_read(vae_engine* e, const char* what, int index, void* out, int64_t capacity) {
+    if (!e) return fail(CAE_ERR_ARG, "vae_trunk_debug_read: null engine");
+    return cae_debug_read(e->trunk, what, index, out, capacity);
+}
 
 }  // extern "C"

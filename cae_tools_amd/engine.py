@@ -40,14 +40,9 @@ class EnginePlan(SpecPlan):
         lds; a fused tail rows, sums ("stored" | "added"), g1 / g0 / gx and w2 / w1 / w0 ("<lg>:<per>" of the chain and
         weight-gradient stages) and lds; a head or tail on "layers" has why, the first condition its planner refused.  A training
         step's plan ends with "enc": {"conv0": "adam" | "own", "inner": "pair" | "layers" | "-"} - whether train_step computes
-        the first encoder layer's weight gradient in the optimiser launch, and the inner encoder layers' backward"""
-        buf = C.create_string_buffer(1 << 16)
-        check(self.lib.cae_debug_plan(self.handle, int(batch), 1 if train else 0, buf, len(buf)))
-        plan = {}
-        for line in buf.value.decode().splitlines():
-            (name, *fields) = line.split()
-            plan[name] = dict(f.split("=", 1) for f in fields)
-        return plan
+        the first encoder layer's weight gradient in the optimiser launch, and the inner encoder layers' backward.  Behind a tail
+        on "layers", "fc3" .. "fc0": {"bwd": "pair", "burst": "0" | "1"} (or {"bwd": "generic"}) - each Linear backward's launch"""
+        return self._plan_report(batch, train)
 
 
 class HipEngine(EnginePlan):

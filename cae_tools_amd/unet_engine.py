@@ -2,8 +2,6 @@
 
 As in engine.py, torch is a container: flat CUDA tensors for the parameter / AdamW / running-statistics
 arenas and the workspace, and a stream.  Every FLOP runs in the HIP kernels."""
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -26,13 +24,7 @@ class UnetPlan(SpecPlan):
         ..., "dec0": {...}, "pack": {"entries": "7", "launches": "1"}}.  Beside the family every layer carries what its launch
         switches on below it, from the functions the launch calls: "down.rbn", "down.nsplit", "up.cl", "wgrad.tile", "fwd.rb",
         "fwd.slices", "outer_lds", ... (the list is in include/cae_unet.h)"""
-        buf = C.create_string_buffer(1 << 16)
-        check(self.lib.unet_debug_plan(self.handle, int(batch), 1 if train else 0, buf, len(buf)))
-        plan = {}
-        for line in buf.value.decode().splitlines():
-            (name, *fields) = line.split()
-            plan[name] = dict(f.split("=", 1) for f in fields)
-        return plan
+        return self._plan_report(batch, train)
 
 
 class UnetEngine(ShardedSteps, SteppedEngine, UnetPlan):

@@ -15,9 +15,20 @@ def check_noise_index(n_cases, latent_size):
                          "apply the model to the cases in several parts")
 
 
-class VaeEngine(ShardedSteps, SteppedEngine, SpecPlan):
+class VaePlan(SpecPlan):
+    """geometry-only view (no GPU needed): tensor table, arena and workspace sizes, the trunk's kernel plan"""
 
     PREFIX = "vae_"
+
+    def kernel_plan(self, batch, train):
+        """the kernels the trunk of a step at this batch runs (vae_debug_plan, include/cae_vae.h), no GPU needed: the dict of
+        EnginePlan.kernel_plan for the ConvAE engine in trunk mode - head and tail on "layers" with why "variational", the last
+        decoder layer with the raw epilogue and a backward of its own, "fc3" .. "fc0" for the four Linear backwards"""
+        return self._plan_report(batch, train)
+
+
+class VaeEngine(ShardedSteps, SteppedEngine, VaePlan):
+
     LOSSES_PER_BATCH = 4    # (mse, kl, 1 - ms_ssim, total)
 
     def __init__(self, spec, fc_size, latent_size, max_batch, device=None):
@@ -42,6 +53,15 @@ class VaeEngine(ShardedSteps, SteppedEngine, SpecPlan):
         out = np.empty(shape, dtype=np.float32)
         check(self.lib.vae_debug_read(self.handle, what.encode(), out.ctypes.data, out.size))
         return out
+
+    def trunk_read(self, what, index=0, count=None):
+        """what the last training-mode step left in the trunk's workspace (vae_trunk_debug_read: cae_debug_read of the trunk):
+        "act" / "grad" of conv layer `index` (encoder layers, then decoder layers but the last), "glast" = dL/d(raw output),
+        "fc" / "fcgrad" of Linear `index` (1: the heads' rows [mu | logvar]), "vgz" = dL/dz; `count` floats (default: all)"""
+        cap = int(count) if count is not None else (1 << 28)
+        buf = np.empty(cap, dtype=np.float32)
+        n = check(self.lib.vae_trunk_debug_read(self.handle, what.encode(), int(index), buf.ctypes.data, cap))
+        return buf[:n]
 
     # ---- the model as a generative one (vae_encode / vae_decode / vae_sample_latent, include/cae_vae.h) -------------------
     def _rows(self, t, row_shape, what):

@@ -232,7 +232,7 @@ int64_t cae_graph_captures(const cae_engine* e);
 /* Test hook (blocking): copy an internal tensor of the LAST train-mode step to host.
  * what: "act" raw conv output of layer `index` (encoder layers first, then decoder layers except
  * the last), "latent", "fc" (decoder FC output), "grad_acc" (fp64 gradient accumulator,
- * `index` ignored, count doubles).  Returns the number of elements copied or a negative status. */
+ * `index` ignored, count doubles), "vgz" (the variational trunk only: dL/dz, (batch, latent)).  Returns the number of elements copied or a negative status. */
 int64_t cae_debug_read(cae_engine* e, const char* what, int index, void* host_out, int64_t capacity_elems);
 
 /* Which kernels a step at `batch` runs (the choosers the launch code switches on), without a GPU: a NUL-terminated report
@@ -252,7 +252,9 @@ int64_t cae_debug_read(cae_engine* e, const char* what, int index, void* host_ou
  *    of head_plan that failed, in that order)
  *   "tail bwd=fused rows=<row groups> sums=stored|added (the BatchNorm sums of more than 8 row groups are added) g1= g0= gx=
  *    (chain stages) w2= w1= w0= (weight-gradient stages, <lg>:<per>) lds=<bytes>"
- *   "tail bwd=layers why=mode|syncing|variational|fc4|panel|weights|channels|lds"
+ *   "tail bwd=layers why=mode|syncing|variational|fc4|panel|weights|channels|lds", followed by one line per Linear layer,
+ *    last first: "fc3 bwd=pair burst=0|1" (k_gemm16_pair; burst: its input-gradient half reads every operand at kernel
+ *    start) or "fc3 bwd=generic"
  * A training step ends with "enc conv0=adam|own inner=pair|layers|-": whether a cae_train_step computes the first encoder
  * layer's weight gradient inside the optimiser launch (only behind a fused head), and whether the inner encoder layers take
  * k_conv_bwd_pair (-: there are none).

@@ -99,6 +99,13 @@ int vae_sync(vae_engine* e);
  * "z" ((batch, latent) rows); the sigmoid output "y" or "gssim" = d(lambda_ssim * (1 - MS-SSIM)) / dy ((batch * channels, H, W)
  * planes; "y" is also left by an eval step, "gssim" only by a step that computes gradients) */
 int vae_debug_read(vae_engine* e, const char* what, float* out_host, int64_t count);
+/* Test hooks on the trunk, the ConvAE engine in trunk mode that runs every layer of this model (cae_hip.h):
+ * vae_debug_plan: cae_debug_plan of the trunk, without a GPU - head and tail are "layers why=variational", the last decoder
+ *   layer hands out its raw output (epi=raw) and is never fused with a loss.
+ * vae_trunk_debug_read: cae_debug_read of the trunk ("act", "grad", "glast" = dL/d(raw output), "fc", "fcgrad", "latent" = the
+ *   heads' rows [mu | logvar], "vgz" = dL/dz); returns the number of elements copied or a negative status. */
+int vae_debug_plan(const vae_engine* e, int batch, int train, char* out_host, int64_t out_bytes);
+int64_t vae_trunk_debug_read(vae_engine* e, const char* what, int index, void* host_out, int64_t capacity_elems);
 /* the 11 window values of the MS-SSIM kernels (host only, no engine, no GPU): the fp32 values of the published definition */
 void vae_gauss_window(float* out11_host);
 

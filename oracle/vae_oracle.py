@@ -23,6 +23,11 @@ Precision: everything here follows the dtype of its inputs and state.  fp32 is t
 inputs (VaeOracle(..., dtype=torch.float64), ms_ssim(y.double(), t.double())) the same expressions give the 'exact' answer the
 parity tests anchor their bounds to.  The constants of the definition - the window, the scale weights, the noise - are the fp32
 values in either case, cast up: they are data of the definition, not results to be recomputed more accurately.
+
+Test hooks, as in cae_oracle.py: trace= records every ReLU's pre-activation ("z:" + name; names enc_conv{i}, enc_fc0, dec_fc0,
+dec_conv{i}) and the heads, relu_fix= overrides single ReLU derivatives (cae_oracle._relu), relu_inputs(x) returns the
+pre-activations without touching the running statistics: what tests/helpers.py relu_fix_for needs to give both precisions the
+HIP step's mask decisions (tests/test_vae_trunk_shapes_gpu.py).
 """
 import math
 from collections import OrderedDict
@@ -31,7 +36,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .cae_oracle import BN_EPS, BN_MOMENTUM, decoder_forward, is_param
+from .cae_oracle import BN_EPS, BN_MOMENTUM, _relu, decoder_forward, is_param
 from .unet_oracle import _pcg
 
 MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
@@ -116,7 +121,8 @@ def normal_noise(seed, step, shape):
     return (np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * math.pi * u2)).astype(np.float32).reshape(shape)
 
 
-def encoder_forward(spec, enc, x, train):
+def encoder_forward(spec, enc, x, train, trace=None, relu_fix=None):
+    """trace / relu_fix: the test hooks of cae_oracle._relu, under the ConvAE oracle's names (enc_conv{i}, enc_fc0)"""
     h = x
     for i, l in enumerate(spec["input_layers"]):
         c, b = f"encoder_cnn.{3 * i}", f"encoder_cnn.{3 * i + 1}"
@@ -125,8 +131,8 @@ def encoder_forward(spec, enc, x, train):
                          training=train, momentum=BN_MOMENTUM, eps=BN_EPS)
         if train:
             enc[b + ".num_batches_tracked"] += 1
-        h = F.relu(h)
-    h = F.relu(F.linear(h.flatten(1), enc["encoder_lin.0.weight"], enc["encoder_lin.0.bias"]))
+        h = _relu(h, f"enc_conv{i}", trace, relu_fix)
+    h = _relu(F.linear(h.flatten(1), enc["encoder_lin.0.weight"], enc["encoder_lin.0.bias"]), "enc_fc0", trace, relu_fix)
     return (F.linear(h, enc["encoder_mu.weight"], enc["encoder_mu.bias"]),
             F.linear(h, enc["encoder_logvar.weight"], enc["encoder_logvar.bias"]))
 
@@ -150,12 +156,32 @@ class VaeOracle:
                                        {"params": [v for k, v in self.dec.items() if is_param(k)]}], lr=lr,
                                       weight_decay=weight_decay)
 
-    def forward(self, x, train):
-        (mu, logvar) = encoder_forward(self.spec, self.enc, x, train)
+    def forward(self, x, train, trace=None, relu_fix=None):
+        (mu, logvar) = encoder_forward(self.spec, self.enc, x, train, trace, relu_fix)
         z = mu
         if train:
             z = mu + torch.from_numpy(normal_noise(self.seed, self.step_count, tuple(mu.shape))).to(mu.dtype) * torch.exp(0.5 * logvar)
-        return decoder_forward(self.spec, self.dec, z, train), mu, logvar
+        if trace is not None:
+            # the heads and the latent themselves: after loss_and_grads their .grad is dL/dmu, dL/dlogvar (KL term included), dL/dz
+            trace["heads"] = (mu, logvar, z)
+            if z.requires_grad:
+                for v in (mu, logvar, z):
+                    v.retain_grad()
+        return decoder_forward(self.spec, self.dec, z, train, trace, relu_fix), mu, logvar
+
+    def relu_inputs(self, x):
+        """{name: pre-activation of every ReLU} of a train-mode forward that leaves no trace on the model (running statistics
+        and batch counters put back; the noise is that of the current step_count): OracleModel.relu_inputs for this model,
+        what tests/helpers.py relu_fix_for compares the HIP path's mask decisions with"""
+        keep = {k: v.clone() for side in (self.enc, self.dec) for k, v in side.items() if not is_param(k)}
+        trace = {}
+        with torch.no_grad():
+            self.forward(x, train=True, trace=trace)
+        for side in (self.enc, self.dec):
+            for k in side:
+                if not is_param(k):
+                    side[k].copy_(keep[k])
+        return {k[2:]: v for k, v in trace.items() if k.startswith("z:")}
 
     def losses(self, y, t, mu, logvar):
         return loss_parts(y, t, mu, logvar)
@@ -172,8 +198,8 @@ class VaeOracle:
             (y, mu, logvar) = self.forward(x, train=False)
             return [float(v) for v in self.losses(y, t, mu, logvar)]
 
-    def loss_and_grads(self, x, t):
-        (y, mu, logvar) = self.forward(x, train=True)
+    def loss_and_grads(self, x, t, trace=None, relu_fix=None):
+        (y, mu, logvar) = self.forward(x, train=True, trace=trace, relu_fix=relu_fix)
         parts = self.losses(y, t, mu, logvar)
         self.optim.zero_grad()
         self.total(parts).backward()

@@ -110,6 +110,12 @@ int main() {
             }
             expect(mu && lv, "the heads are listed under the var model's names");
             expect(vae_train_step(v, 0, nullptr, 0, 16, 0) != 0, "a step on an unbound var engine is refused");
+            char plan[4096];
+            expect(vae_debug_plan(v, 16, 1, plan, sizeof plan) == 0 && strstr(plan, "head fwd=layers why=variational") &&
+                       strstr(plan, "tail bwd=layers why=variational") && strstr(plan, "fc2 bwd=pair burst=1"),
+                   "vae_debug_plan");
+            expect(vae_debug_plan(v, 17, 1, plan, sizeof plan) != 0, "var: a plan beyond max_batch is refused");
+            expect(vae_trunk_debug_read(v, "glast", 0, plan, 4) < 0, "var: a trunk read on an unbound engine is refused");
             float g[1];
             expect(vae_forward_backward_sync(v, 0, nullptr, 0, 3, 2, 4, 1, 0, g, no_allreduce, nullptr) == CAE_ERR_ARG,
                    "var: a shard past the global batch is refused");

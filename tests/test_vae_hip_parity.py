@@ -1,6 +1,12 @@
 """'var' path (include/cae_vae.h) against the build's own CPU definition (oracle/vae_oracle.py).  PARITY UNPINNED with
 respect to the reference: it has no source for this model (see the oracle's header); these tests pin the HIP kernels to
-the published definition only."""
+the published definition only.
+
+What this file is for: the loss parts at three sets of lambdas, three free-running Adam steps, the benchmark geometry, the
+geometry errors and the two MS-SSIM kernel modes against each other.  Its gradient bound (5e-3 of a tensor's L2 norm, 2e-2 of
+its maximum, against the fp32 definition, one geometry) is a smoke check: the gradients are held to the fp64 definition, at
+every branch the trunk's planners take, in tests/test_vae_trunk_shapes_gpu.py (tests/test_vae_trunk_criterion_cpu.py shows
+what passes the bound here and fails there), the MS-SSIM kernels per pixel in tests/test_vae_msssim_gpu.py."""
 import numpy as np
 import pytest
 import torch
