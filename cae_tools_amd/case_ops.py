@@ -1,6 +1,6 @@
 """The case kernels of libcae_hip (include/cae_hip.h) as functions, no engine needed: measures, per-pixel sums, spectra, SSIM,
-interpolation baseline, value distributions, skill by stratum, ensemble verification, value range and rendered pages of
-channel 0 of (N, C, H, W) operands."""
+interpolation baseline, value distributions, skill by stratum, neighbourhood skill, ensemble verification, value range and
+rendered pages of channel 0 of (N, C, H, W) operands."""
 import ctypes as C
 import math
 from contextlib import contextmanager
@@ -19,6 +19,7 @@ _TORCH_KINDS = {torch.float32: _lib.ELEM_F32, torch.float64: _lib.ELEM_F64}
 (_SPECTRA_CASES, _SSIM_CASES) = (512, 256)
 _BASELINE_FIELD_BYTES = 256 << 20       # of fp64 field per cae_case_baseline call when the field is asked for
 _RENDER_BYTES = 64 << 20                # of rendered pages per group of cae_render_cases calls
+_FSS_PLANE_BYTES = 256 << 20            # of bit-planes per cae_case_fss call (one case at least)
 
 
 @dataclass(frozen=True, eq=False)
@@ -337,6 +338,44 @@ def strata_sums(pred, actual, strata, edges, shift=0.0, channel=0, device=None):
         sums = sums.cpu().numpy()
     return {"members": counts[:n_strata].copy(), "pairs": counts[n_strata:2 * n_strata].copy(),
             "unclassified": int(counts[2 * n_strata])}, sums
+
+
+def fraction_skill(pred, actual, thresholds, widths=None, gaps="strict", device=None):
+    """The window sums of the Fractions Skill Score of channel 0 (cae_case_fss, include/cae_hip.h): an (N, T, S, 6) int64
+    numpy array {windows, S cM, S cO, S cM^2, S cO^2, S cM cO} per case, threshold and width over the counted n x n windows
+    that lie wholly inside the image, cM and cO being the window's numbers of prediction and target events among the pixels
+    where both are finite.  thresholds: 1 to 8 numbers (the event is v >= t) or (value, "above" | "below") pairs ("below":
+    v < t).  widths: up to 8 odd, ascending widths from 1 to 129; None: the DEFAULT widths of utils/fss.py at or below
+    min(H, W).  gaps "strict": a window over a pixel where a value is not finite is left out; "ignore": such a pixel is a
+    non-event in both fields and a window is left out only where it holds no pair at all.  Exact integers, the same from run
+    to run.  Operands as case_ssim takes them; the cases go in groups that bound the workspace, and a case's sums do not
+    depend on the cut.  utils/fss.scores_from_sums turns the sums into FSS, frequencies and the skilful width."""
+    from .utils import fss
+    (device, p, a, n, h, w) = _pair("fraction_skill", pred, actual, device)
+    if not (0 <= h <= 16384 and 0 <= w <= 16384):
+        raise ValueError(f"fraction_skill: planes of up to 16384 pixels a side expected, got {h} x {w}")
+    try:
+        (values, sides) = fss.check_thresholds(thresholds)
+        widths = fss.default_widths(h, w) if widths is None else fss.check_widths(widths)    # no default for a plane without a pixel
+        rule = fss.GAPS[gaps]
+    except (KeyError, TypeError):
+        raise ValueError(f"fraction_skill: gaps must be one of {', '.join(fss.GAPS)}, got {gaps!r}") from None
+    except ValueError as refused:
+        raise ValueError(f"fraction_skill: {refused}") from None
+    (n_thr, n_width) = (len(values), len(widths))
+    if n == 0 or h * w == 0 or n_width == 0:     # n_width 0: the default widths of a plane without a pixel
+        return np.zeros((n, n_thr, n_width, 6), dtype=np.int64)
+    lib = _lib.load()
+    group = max(1, min(n, _FSS_PLANE_BYTES // int(lib.cae_case_fss_workspace_bytes(1, h, w, n_thr))))
+    sums = torch.empty((n, n_thr, n_width, 6), dtype=torch.int64, device=device)
+    (ws, need) = _workspace(device, lib.cae_case_fss_workspace_bytes, group, h, w, n_thr)
+    (thr_c, side_c, width_c) = ((C.c_double * n_thr)(*values), (C.c_int * n_thr)(*sides), (C.c_int * n_width)(*widths))
+    with _stream(device) as stream:
+        for c0 in range(0, n, group):
+            g = min(n, c0 + group) - c0
+            check(lib.cae_case_fss(*p.args(c0), *a.args(c0), g, h, w, thr_c, side_c, n_thr, width_c, n_width, rule,
+                                   sums[c0:].data_ptr(), ws.data_ptr(), need, stream))
+        return sums.cpu().numpy()
 
 
 def upsample(low, out_shape, mode="bicubic", device=None):

@@ -1,6 +1,6 @@
 """The optional outputs of ModelEvaluator.build_html, none of them a reference feature: ensemble verification, case pages,
-structural similarity, skill against interpolation, per-pixel skill maps, power spectra, value distributions and skill by
-stratum.
+structural similarity, skill against interpolation, per-pixel skill maps, power spectra, value distributions, skill by
+stratum and neighbourhood skill.
 
 Each is one Analysis of functions over the evaluator `ev`:
     enabled(ev)                                     whether its option is on
@@ -17,12 +17,13 @@ from collections import namedtuple
 
 import numpy as np
 
-from ..case_ops import (case_baseline, case_range, case_spectra, case_ssim, device_operand, joint_histogram, pixel_sums, render_cases,
-                        strata_sums)
+from ..case_ops import (case_baseline, case_range, case_spectra, case_ssim, device_operand, fraction_skill, joint_histogram, pixel_sums,
+                        render_cases, strata_sums)
 from ..data.arrays import as_numpy
 from ..utils import baseline as baseline_scores
 from ..utils import distribution as distribution_curves
 from ..utils import ensemble_scores, skill_maps
+from ..utils import fss as fss_scores
 from ..utils import spectra as spectra_curves
 from ..utils import ssim as ssim_scores
 from ..utils import strata as strata_scores
@@ -198,6 +199,17 @@ def check_distribution(ev):
         raise ValueError(f"distribution_bins must be an integer from 1 to 128, got {ev.distribution_bins!r}")
 
 
+def _value_span(operands, n_bin):
+    """(lo, hi) of a joint_histogram pass of n_bin coarse bins: the range of the finite values of the operands, one
+    cae_case_range each in their order; hi = lo + 1 where that range is degenerate"""
+    spans = [case_range(op) for op in operands]
+    spans = [s for s in spans if s[2] > 0]
+    (lo, hi) = (min(s[0] for s in spans), max(s[1] for s in spans)) if spans else (0.0, 0.0)
+    if not (np.isfinite(hi - lo) and hi > lo and np.isfinite(n_bin * DISTRIBUTION_SUB / (hi - lo))):
+        hi = lo + 1.0
+    return lo, hi
+
+
 def _distribution(ev, parts, report):
     """distribution=True (cli/distribution.py) adds the reduction along value: per partition the joint histogram of
     prediction against target over distribution_bins (1 to 128) coarse bins, the two fine marginal histograms and the
@@ -207,11 +219,7 @@ def _distribution(ev, parts, report):
     distance, Perkins score and exceedance scores, distribution/index.html with the joint density and the curves, and the
     report's "Value distribution" section."""
     pairs = [(partition, *ev.operands(partition, ds)) for (partition, ds) in parts]
-    spans = [case_range(op) for (_, p, a) in pairs for op in (p, a)]
-    spans = [s for s in spans if s[2] > 0]
-    (lo, hi) = (min(s[0] for s in spans), max(s[1] for s in spans)) if spans else (0.0, 0.0)
-    if not (np.isfinite(hi - lo) and hi > lo and np.isfinite(ev.distribution_bins * DISTRIBUTION_SUB / (hi - lo))):
-        hi = lo + 1.0
+    (lo, hi) = _value_span([op for (_, p, a) in pairs for op in (p, a)], ev.distribution_bins)
     found = []
     for (partition, p, a) in pairs:
         counts = joint_histogram(p, a, lo, hi, n_bin=int(ev.distribution_bins), sub=DISTRIBUTION_SUB)
@@ -291,6 +299,74 @@ def _strata(ev, parts, report):
     report["strata"] = kept
 
 
+# ---- neighbourhood skill ---------------------------------------------------------------------
+
+FSS_BINS = 128              # coarse bins of the joint_histogram pass that turns percentiles into values: distribution's default
+
+
+def _fss_percentiles(ev):
+    """[(q, side)] of the percentile form: fss_percentiles as given, numbers ("above") or (q, side) pairs of percent values,
+    else utils/distribution.THRESHOLDS; q as a fraction"""
+    if ev.fss_percentiles is None:
+        return list(distribution_curves.THRESHOLDS)
+    (values, sides) = fss_scores.check_thresholds(ev.fss_percentiles)
+    if any(not 0.0 < v < 100.0 for v in values):
+        raise ValueError(f"fss_percentiles must lie between 0 and 100, got {values}")
+    return [(v / 100.0, "below" if s else "above") for (v, s) in zip(values, sides)]
+
+
+def check_fss(ev):
+    if not ev.fss:
+        return
+    if ev.fss_thresholds is not None and ev.fss_percentiles is not None:
+        raise ValueError("fss_thresholds and fss_percentiles exclude each other")
+    if ev.fss_thresholds is not None:
+        fss_scores.check_thresholds(ev.fss_thresholds)
+    else:
+        _fss_percentiles(ev)
+    if ev.fss_widths is not None:
+        fss_scores.check_widths(ev.fss_widths)
+    if ev.fss_gaps not in fss_scores.GAPS:
+        raise ValueError(f"fss_gaps must be one of {', '.join(fss_scores.GAPS)}, got {ev.fss_gaps!r}")
+
+
+def _fss(ev, parts, report):
+    """fss=True (cli/fss.py) adds the reduction along displacement: per partition the Fractions Skill Score of channel 0 for
+    up to 8 event thresholds over up to 8 neighbourhood widths (fss_widths, default 1, 3, 5, 9, 17, 33, 65 as far as the plane
+    allows), from one cae_case_fss pass on the GPU (exact integer window sums; utils/fss.py).  The
+    thresholds are fss_thresholds in data units, numbers ("above": v >= t) or (value, "above" | "below") pairs, or else the
+    fss_percentiles (percent values likewise; default the 5th below and the 90th, 95th and 99th above) of the target's
+    distribution in the partition: utils/distribution.quantile_from_counts on the target's fine marginal of one
+    joint_histogram pass of 128 x 8 bins over the range rule of the distribution analysis, so that a percentile threshold is
+    the quantile_target of distribution_<partition>.json.  fss_gaps "strict" leaves out a window over a value that is not
+    finite, "ignore" only a window without any pair.  fss_<partition>.json holds the threshold values used, the pooled sums,
+    the pooled and per-case FSS, the event frequencies, the uniform level and the skilful width; fss/index.html the curves;
+    the report gets the "Neighbourhood skill" section.  Every rank would compute all cases: the pass is not sharded."""
+    pairs = [(partition, *ev.operands(partition, ds)) for (partition, ds) in parts]
+    quantiles = None
+    if ev.fss_thresholds is None:
+        quantiles = _fss_percentiles(ev)
+        (lo, hi) = _value_span([op for (_, p, a) in pairs for op in (p, a)], FSS_BINS)
+    found = []
+    for (partition, p, a) in pairs:
+        (h, w) = (int(a.shape[2]), int(a.shape[3]))
+        if quantiles is None:
+            (thresholds, percentiles) = (list(ev.fss_thresholds), None)
+        else:
+            marg = joint_histogram(p, a, lo, hi, n_bin=FSS_BINS, sub=DISTRIBUTION_SUB)[1]
+            values = [distribution_curves.quantile_from_counts(marg[0], lo, hi, q) for (q, _) in quantiles]
+            if not all(np.isfinite(values)):
+                raise ValueError(f"fss: the {partition} partition has no pixel where target and prediction are finite, so no "
+                                 "percentile of the target")
+            (thresholds, percentiles) = ([(v, side) for (v, (_, side)) in zip(values, quantiles)], [q for (q, _) in quantiles])
+        widths = fss_scores.default_widths(h, w) if ev.fss_widths is None else fss_scores.check_widths(ev.fss_widths)
+        sums = fraction_skill(p, a, thresholds, widths=widths, gaps=ev.fss_gaps)
+        record = fss_scores.summary(fss_scores.scores_from_sums(sums, widths), thresholds, widths, ev.fss_gaps, h, w, percentiles)
+        _keep(ev, fss_scores, "fss", partition, record, found)
+    fss_scores.write_page(os.path.join(ev.output_html_folder, "fss"), found)
+    report["fss"] = (found, "fss/index.html")
+
+
 ENSEMBLE = Analysis(lambda ev: ev.ensemble_size is not None, check_ensemble, partition=_ensemble)
 CASE_PAGES = Analysis(lambda ev: ev.x_coordinate and ev.y_coordinate and ev.time_coordinate, partition=_case_pages)
 SSIM = Analysis(lambda ev: ev.ssim, partition=_ssim)
@@ -299,6 +375,7 @@ SKILL_MAPS = Analysis(lambda ev: ev.skill_maps, after=_skill_maps)
 SPECTRA = Analysis(lambda ev: ev.spectra, after=_spectra)
 DISTRIBUTION = Analysis(lambda ev: ev.distribution, check_distribution, after=_distribution)
 STRATA = Analysis(lambda ev: ev.strata, check_strata, after=_strata)
+FSS = Analysis(lambda ev: ev.fss, check_fss, after=_fss)
 # in the order build_html runs them: per partition ensemble, case pages, ssim, baseline; then skill maps, spectra, distribution,
-# strata
-ANALYSES = (ENSEMBLE, CASE_PAGES, SSIM, BASELINE, SKILL_MAPS, SPECTRA, DISTRIBUTION, STRATA)
+# strata, fss
+ANALYSES = (ENSEMBLE, CASE_PAGES, SSIM, BASELINE, SKILL_MAPS, SPECTRA, DISTRIBUTION, STRATA, FSS)

@@ -18,7 +18,7 @@ index is 0 for NaN and 1 + round-half-up(254 * clamp((v - lo) / (hi - lo), 0, 1)
 (cae_render_cases) from the slabs as stored and from the prediction where it still lies in HBM.
 
 The optional analyses that are no reference feature - ensemble verification, structural similarity, skill against
-interpolation, per-pixel skill maps, power spectra, value distributions and skill by stratum - are the units of
+interpolation, per-pixel skill maps, power spectra, value distributions, skill by stratum and neighbourhood skill - are the units of
 evaluation_analyses.py, which build_html runs in their fixed order.  What they and the case pages read on the GPU comes
 from one operand cache (operand): a partition's variable is uploaded once per build_html, whatever is switched on.
 """
@@ -46,7 +46,8 @@ class ModelEvaluator:
                  database_path="", input_variables=[], sample_count=None, x_coordinate="", y_coordinate="",
                  time_coordinate="", skill_maps=False, ensemble_size=None, ensemble_seed=0, spectra=False, ssim=False,
                  baseline=False, baseline_variable=None, baseline_mode="bicubic", distribution=False, distribution_bins=128,
-                 strata=False, strata_variable=None, strata_channel=0, strata_edges=None, strata_classes=None, strata_count=8):
+                 strata=False, strata_variable=None, strata_channel=0, strata_edges=None, strata_classes=None, strata_count=8,
+                 fss=False, fss_thresholds=None, fss_percentiles=None, fss_widths=None, fss_gaps="strict"):
         self.training_paths = list(training_paths) if training_paths else []
         self.testing_paths = list(testing_paths) if testing_paths else []
         self.output_html_folder = output_html_folder
@@ -68,8 +69,10 @@ class ModelEvaluator:
         (self.ensemble_size, self.ensemble_seed) = (ensemble_size, int(ensemble_seed))
         (self.strata, self.strata_variable, self.strata_channel) = (strata, strata_variable, strata_channel)
         (self.strata_edges, self.strata_classes, self.strata_count) = (strata_edges, strata_classes, strata_count)
+        (self.fss, self.fss_thresholds, self.fss_percentiles) = (fss, fss_thresholds, fss_percentiles)
+        (self.fss_widths, self.fss_gaps) = (fss_widths, fss_gaps)
         for unit in (analyses.BASELINE, analyses.DISTRIBUTION, analyses.ENSEMBLE,       # the refusals come in this order,
-                     analyses.STRATA):                                                  # all before the model is loaded
+                     analyses.STRATA, analyses.FSS):                                    # all before the model is loaded
             unit.check(self)
         self.model = load_model(self.model_path)
         analyses.check_ensemble_model(self)

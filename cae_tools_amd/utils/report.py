@@ -221,7 +221,7 @@ def _section(body, title, records, heading, rows, plots=None):
 
 
 def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None, ensemble=None,
-                      spectra_link=None, ssim=None, baseline=None, distribution=None, strata=None):
+                      spectra_link=None, ssim=None, baseline=None, distribution=None, strata=None, fss=None):
     """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
     metrics: {"test": {...}, "train": {...}} (either may be absent); measures: [(partition, {"mae": values, "mse": values})]
     in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}; maps_link: href of
@@ -235,7 +235,10 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
     histogram of the per-case skill; distribution: ([(partition, curves)] of utils/distribution.curves_from_counts, href of
     the value distribution page): a "Value distribution" section with the table of the conditional slope, quantile bias,
     distances and exceedance scores, and the link; strata: [(partition, record)] of utils/strata.summary: a "Skill by stratum"
-    section with the table of the scores per stratum and pooled and the bar chart of bias +- rmse per stratum."""
+    section with the table of the scores per stratum and pooled and the bar chart of bias +- rmse per stratum; fss:
+    ([(partition, record)] of utils/fss.summary, href of the neighbourhood skill page): a "Neighbourhood skill" section with
+    the table of the pooled Fractions Skill Score per threshold and width, the uniform level and the skilful width, and the
+    link."""
     doc = Document("Model Evaluation")
     doc.head.add("style").text(STYLE)
     body = doc.body
@@ -288,6 +291,15 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
                              f"{rec['unclassified']} pixels unclassified",
                  strata_scores.section_rows,
                  {"skill by stratum": lambda rec: strata_scores.svg_bars(rec, f"bias +- rmse by {rec['variable']}")})
+    if fss:
+        from . import fss as fss_scores
+        (records, link) = fss
+        _section(body, "Neighbourhood skill", records,
+                 lambda rec: f"{len(rec['thresholds'])} threshold{'s' if len(rec['thresholds']) != 1 else ''}, widths "
+                             f"{', '.join(str(n) for n in rec['widths']) or 'none'}, {rec['n_cases']} cases, gaps {rec['gaps']}",
+                 fss_scores.section_rows)
+        if link:
+            body.add("p").add("a", {"href": link}).text("Fractions Skill Score of prediction against target")
     if parameters or history:
         body.add("h2").text("Training Summary")
     if parameters:

@@ -680,6 +680,51 @@ int cae_strata_sums(const void* pred_dev, int pred_kind, int64_t pred_case_strid
                     double*  sums_dev   /* [n_edge + 1][8] */,
                     void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- neighbourhood skill (stateless): the window sums of the Fractions Skill Score --------------- */
+
+/* The Fractions Skill Score (Roberts & Lean 2008) compares the event fractions of prediction and target in n x n
+ * neighbourhoods, so that a feature predicted a few pixels beside its place is not counted as a miss and a false alarm at
+ * once.  This call forms, per case, threshold and width, the six integer sums utils/fss.py derives it from.
+ * Operands: channel 0 of prediction p and target a, both (n_case, h, w) as stored, as cae_strata_sums takes them: CAE_ELEM_*
+ * kinds, big-endian kinds included; case i starts at element i * case_stride, any stride >= the plane, pointers aligned to
+ * their element size.  Every value is widened to fp64 exactly before it is compared.
+ * Pair rule: a pixel is a pair when p and a are both finite there.
+ * Events: thresholds[n_thr] (host) are finite, sides[n_thr] (host) 0 or 1, 1 <= n_thr <= 8.  Side 0 ("above"): the event of
+ * a value v is v >= t; side 1 ("below"): v < t; compared in fp64, -0.0 as 0.0.  eP = pair && event(p), eA = pair && event(a),
+ * bad = !pair.
+ * Neighbourhoods: widths[n_width] (host) are odd, strictly ascending, 1 <= n <= 129, 1 <= n_width <= 8.  A window of width n
+ * has its top-left corner at (y0, x0), 0 <= y0 <= h - n, 0 <= x0 <= w - n: it lies wholly inside the image, nothing is
+ * padded, and a width larger than a side has no window.  cM, cO and cB are the numbers of its eP, eA and bad pixels.
+ * gap_rule 0 (strict): a window is counted iff cB == 0, the rule of cae_case_ssim.  gap_rule 1 (ignore): iff cB < n * n; a
+ * pixel that is no pair is then a non-event in both fields.
+ *   sums_dev[case][t][s][0..5] = {windows, S cM, S cO, S cM^2, S cO^2, S cM cO}     over the counted windows
+ * 64-bit integers, written whole.  cM <= 129^2 and a case of sides up to 16384 has at most 2^28 windows, so every sum stays
+ * below 2^28 * 16641^2 < 2^63; all additions are integer and therefore exact in any order: the same arguments give the same
+ * output from run to run, and a case's sums do not depend on the other cases of the call.  Sums over many cases can pass
+ * 2^63: pool them in wider integers.
+ * n_case == 0, h == 0 or w == 0 looks at no operand, writes zeros to sums_dev where it is not NULL and has elements, and
+ * succeeds.
+ * Two launches.  The first streams the operands once for all thresholds and stores, per 64 pixels of a row, the ballot words
+ * of bad, eP and eA into bit-planes in workspace_dev: planes[case][1 + 2 n_thr][h][ceil(w / 64)] 64-bit words, bit x & 63 of
+ * word x >> 6 is pixel x, bits at or beyond w are zero; every word is written.  The second walks the windows: a lane owns
+ * one x0 and walks y0 down a segment of rows, the row counts are popcounts of its n bits shifted out of at most three words,
+ * the window counts running sums (the row that enters added, the row that leaves subtracted), and the lane sums are folded
+ * over the wave and added to the zeroed output with 64-bit integer atomics.  No floating-point operation after the compare.
+ * workspace_dev (8-byte aligned) holds cae_case_fss_workspace_bytes bytes = n_case * (1 + 2 n_thr) * h * ceil(w / 64) * 8
+ * (0 only for an empty or a refused call).
+ * Bad kinds, sides outside 0 .. 16384, n_thr or n_width outside 1 .. 8, gap_rule other than 0 or 1, negative strides, a
+ * misaligned output, NULL pointers, a threshold that is not finite, a side other than 0 or 1, a width that is even, outside
+ * 1 .. 129 or not strictly ascending, a stride shorter than the plane, an operand reaching 2^60 elements from its pointer,
+ * misaligned pointers or too small a workspace: CAE_ERR_ARG, nothing written. */
+int64_t cae_case_fss_workspace_bytes(int64_t n_case, int64_t h, int64_t w, int n_thr);
+int cae_case_fss(const void* pred_dev, int pred_kind, int64_t pred_case_stride,
+                 const void* actual_dev, int actual_kind, int64_t actual_case_stride,
+                 int64_t n_case, int64_t h, int64_t w,
+                 const double* thresholds /* host [n_thr] */, const int* sides /* host [n_thr]: 0 above, 1 below */, int n_thr,
+                 const int* widths /* host [n_width] */, int n_width, int gap_rule,
+                 int64_t* sums_dev /* [n_case][n_thr][n_width][6] */,
+                 void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 /* ---- scene apply (stateless): a box model applied to a whole scene ----------------------------- */
 
 /* A model maps an input box (c, h, w) to an output box (c_out, H, W) with H = h * sy, W = w * sx.  A scene variable is
