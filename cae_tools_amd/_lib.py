@@ -85,6 +85,7 @@ SIGNATURES = {
     "cae_graph_captures": (C.c_int64, [_P]),
     "cae_debug_read": (C.c_int64, [_P, C.c_char_p, C.c_int, _P, C.c_int64]),
     "cae_debug_plan": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p, C.c_int64]),
+    "cae_debug_wgrad_slabs": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_int64]),
     "cae_profile_begin": (C.c_int, [_P]),
     "cae_debug_launch_floor": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     "cae_profile_end": (C.c_int, [_P, C.POINTER(ProfileRecC), C.c_int]),

@@ -277,6 +277,9 @@ static int engine_create_impl(const cae_layer_spec* enc, int n_enc, const cae_la
         e->off_vgz = carve(mb * latent_size * 4);
         e->off_zlast = carve(mb * e->dec.back().out_elems() * 4);
     }
+    // weight-gradient partial slabs, last: every offset above stays where it was
+    e->wslab_bytes = wgrad_slab_capacity(e);
+    e->off_wslab = carve(std::max<int64_t>(e->wslab_bytes, 256));
     e->ws_need = carve.top;
     for (auto& L : e->enc)
         if (L.cin > e->max_channels) e->max_channels = L.cin;
@@ -351,10 +354,13 @@ int cae_set_kernel_mode(cae_engine* e, int specialised) {
     if (!e) return fail(CAE_ERR_ARG, "null engine");
     const int ctb = (specialised & 2) ? 0x7fffffff : e->ctbwd_auto;   // bit 1: every eligible layer
     const bool gather = (specialised & 4) != 0;
-    if (e->use_s2 != ((specialised & 1) != 0) || ctb != e->ctbwd_mask || gather != e->gather_fwd) e->drop_graphs();
+    const bool atomics = (specialised & 8) != 0;
+    if (e->use_s2 != ((specialised & 1) != 0) || ctb != e->ctbwd_mask || gather != e->gather_fwd || atomics != e->wgrad_atomics)
+        e->drop_graphs();
     e->use_s2 = (specialised & 1) != 0;
     e->ctbwd_mask = ctb;
     e->gather_fwd = gather;
+    e->wgrad_atomics = atomics;
     return CAE_OK;
 }
 

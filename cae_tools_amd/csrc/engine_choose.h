@@ -539,6 +539,107 @@ DecBwdK choose_dec_bwd(const cae_engine* e, const ConvLayer& L, int l, int B, bo
     return DB_GENERIC;
 }
 
+// ---- weight-gradient partial slabs (folded by k_gemm16_pair: kernels_gemm.h wgrad_fold_body) -------------------------------
+// A decoder backward kernel stores its weight-gradient partials instead of adding them where the step has the launch that
+// folds them: launch_backward runs linear_bwd_pair(e, a, 3, P) behind the decoder whenever the specialised kernels are on,
+// in every kind of step (single device, data-parallel, SyncBN, trunk).  cae_set_kernel_mode bit 3 keeps the atomics.
+bool wgrad_slabs_on(const cae_engine* e) { return e->use_s2 && !e->wgrad_atomics; }
+
+// One slab: slab[nparts][nvals] at `off` bytes of the region, for the weight of decoder layer `layer`.
+//   k_ct_bwd_lds / k_ct_bwd_band (float: MFMA tiles): one partial per workgroup and chunk of kCtbKChunk positions.  Only the
+//     last band of an image / the last image group is short, so the partials are numbered without gaps - band kernel (grid x =
+//     image, z = band): x * ppg + z * kfull + chunk; whole images (grid x = image group): x * kfull + chunk
+//   k_s2_bwd_rows (double: the four-wave sums): one partial per workgroup
+// The weight-gradient half of k_ig_bwd_pair and k_s2_last_fused keep their atomics: as slab writers they were measured and
+// did not pay.
+struct WSlab { int layer; const char* writer; int nvals, nparts, f64, kfull, ppg; int64_t off; };
+
+void ct_bwd_slab(const ConvLayer& L, const CtBwdPlan& p, int B, WSlab& s) {
+    auto chunks = [](int positions) { return (positions + kCtbKChunk - 1) / kCtbKChunk; };
+    s.nvals = L.cin * L.cout * 9;
+    s.f64 = 0;
+    if (p.bands > 1) {
+        s.writer = "ct_bwd_band";
+        s.kfull = chunks(p.hb * L.win);
+        s.ppg = (p.bands - 1) * s.kfull + chunks((L.hin - (p.bands - 1) * p.hb) * L.win);
+        s.nparts = p.groups * s.ppg;
+    } else {
+        s.writer = "ct_bwd_lds";
+        s.kfull = s.ppg = chunks(p.imgs * L.hin * L.win);
+        s.nparts = (p.groups - 1) * s.kfull + chunks((B - (p.groups - 1) * p.imgs) * L.hin * L.win);
+    }
+}
+
+// the grid of rows_go (engine_launch.h)
+int rows_bwd_grid(const ConvLayer& L, int B) {
+    const RowsPick p = choose_rows_bwd(L);
+    const int qh = (L.hout + 1) / 2, hmax = L.hin > qh - 1 ? L.hin : qh - 1, nb = L.cin == 4 ? 4 : 1;
+    const int bands = (hmax + p.hb - 1) / p.hb, imgs = 64 / p.lw;
+    return ((B + imgs - 1) / imgs) * ((bands + nb - 1) / nb);
+}
+
+// The slabs of a training step at batch B in launch order (last decoder layer first): every layer whose backward kernel is a
+// slab writer, while the fold launch has room (kFoldMax slabs, `capacity` bytes; a layer beyond keeps its atomics).
+std::vector<WSlab> wgrad_slab_table(const cae_engine* e, int B, bool external_loss, int64_t capacity) {
+    std::vector<WSlab> t;
+    if (!wgrad_slabs_on(e)) return t;
+    int64_t used = 0;
+    for (int l = (int)e->dec.size() - 1; l >= 0; l--) {
+        const ConvLayer& L = e->dec[l];
+        WSlab s{l, "", L.cin * L.cout * L.kh * L.kw, 0, 1, 0, 0, 0};
+        switch (choose_dec_bwd(e, L, l, B, external_loss)) {
+            case DB_ROWS:
+                s.writer = "s2_bwd_rows"; s.nparts = rows_bwd_grid(L, B);
+                break;
+            case DB_CT_LDS: {
+                CtBwdPlan p;
+                (void)ct_bwd_plan(e, B, L, l, p);
+                ct_bwd_slab(L, p, B, s);
+                break;
+            }
+            default: continue;
+        }
+        const int64_t bytes = align_up((int64_t)s.nparts * s.nvals * (s.f64 ? 8 : 4), 256);
+        if ((int)t.size() >= kFoldMax || used + bytes > capacity) continue;
+        s.off = used;
+        used += bytes;
+        t.push_back(s);
+    }
+    return t;
+}
+
+// layer l's slab in the table of the step at hand (nparts == 0: none, the layer adds with atomics)
+WSlab wgrad_slab_of(const cae_engine* e, int B, bool external_loss, int l) {
+    for (const WSlab& s : wgrad_slab_table(e, B, external_loss, e->wslab_bytes))
+        if (s.layer == l) return s;
+    return WSlab{l, "", 0, 0, 0, 0, 0, 0};
+}
+
+// bytes of the slab region: the most a step of any batch up to max_batch stores, with every eligible layer on the
+// LDS-staged backward (cae_set_kernel_mode bit 1)
+int64_t wgrad_slab_capacity(cae_engine* e) {
+    const int mask = e->ctbwd_mask;
+    e->ctbwd_mask = 0x7fffffff;
+    int64_t cap = 0;
+    for (int B = 1; B <= e->max_batch; B++) {
+        const std::vector<WSlab> t = wgrad_slab_table(e, B, e->variational, INT64_MAX / 2);
+        if (!t.empty()) cap = std::max(cap, t.back().off + align_up((int64_t)t.back().nparts * t.back().nvals * (t.back().f64 ? 8 : 4), 256));
+    }
+    e->ctbwd_mask = mask;
+    return cap;
+}
+
+// the fold section of Linear 3's backward launch for that table
+WFold wgrad_fold_of(const cae_engine* e, const std::vector<WSlab>& t) {
+    WFold f = zeroed<WFold>();
+    for (const WSlab& s : t) {
+        const int vshift = fold_vshift(s.nparts);
+        f.s[f.nslab++] = WFoldSlab{e->ws + e->off_wslab + s.off, e->gradacc() + e->dec[s.layer].w_off, s.nvals, s.nparts, s.f64, vshift};
+        f.nwg += fold_wgs(s.nvals, vshift);
+    }
+    return f;
+}
+
 // The first encoder layer's weight gradient inside the optimiser launch (kernels_generic.h AdamConv0): a single-device training step
 // whose k_head_fwd left the batch's inputs behind, a layer small enough for k_adam's extra blocks, its BatchNorm table first in the swept range.
 // enc_conv0_fits_adam: what the engine and the layer decide (cae_debug_plan reports it for a step with a fused head);
@@ -701,6 +802,31 @@ int cae_debug_plan(const cae_engine* e, int batch, int train, char* out, int64_t
     }
     if ((int64_t)s.size() + 1 > out_bytes)
         return fail(CAE_ERR_ARG, "cae_debug_plan: the report needs %zu bytes, got %lld", s.size() + 1, (long long)out_bytes);
+    memcpy(out, s.c_str(), s.size() + 1);
+    return CAE_OK;
+}
+
+int cae_debug_wgrad_slabs(const cae_engine* e, int batch, char* out, int64_t out_bytes) {
+    if (!e || !out || out_bytes < 1) return fail(CAE_ERR_ARG, "cae_debug_wgrad_slabs: bad argument");
+    if (batch < 1 || batch > e->max_batch)
+        return fail(CAE_ERR_ARG, "cae_debug_wgrad_slabs: batch %d outside 1 .. %d", batch, e->max_batch);
+    const std::vector<WSlab> t = wgrad_slab_table(e, batch, e->variational, e->wslab_bytes);
+    const WFold f = wgrad_fold_of(e, t);
+    std::string s;
+    char line[256];
+    int64_t used = 0;
+    for (size_t k = 0; k < t.size(); k++) {
+        const WSlab& sl = t[k];
+        snprintf(line, sizeof line, "dec%d writer=%s type=%s param=%lld values=%d partials=%d offset=%lld fold_wgs=%d fold_values=%d\n", sl.layer,
+                 sl.writer, sl.f64 ? "f64" : "f32", (long long)e->dec[sl.layer].w_off, sl.nvals, sl.nparts, (long long)sl.off,
+                 fold_wgs(sl.nvals, f.s[k].vshift), 1 << f.s[k].vshift);
+        s += line;
+        used = sl.off + (int64_t)sl.nparts * sl.nvals * (sl.f64 ? 8 : 4);
+    }
+    snprintf(line, sizeof line, "fold slabs=%d wgs=%d bytes=%lld capacity=%lld\n", f.nslab, f.nwg, (long long)used, (long long)e->wslab_bytes);
+    s += line;
+    if ((int64_t)s.size() + 1 > out_bytes)
+        return fail(CAE_ERR_ARG, "cae_debug_wgrad_slabs: the report needs %zu bytes, got %lld", s.size() + 1, (long long)out_bytes);
     memcpy(out, s.c_str(), s.size() + 1);
     return CAE_OK;
 }

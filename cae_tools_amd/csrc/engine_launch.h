@@ -363,6 +363,8 @@ void bwd_rows(cae_engine* e, const StepArgs& a, const ConvBwd& c) {
     f.w = e->params + L.w_off; f.wacc = e->sgacc() + L.sh_w; f.wacc_stride = e->segs.n;
     f.gin = c.prod.gin; f.stats_in = c.prod.stats_in;
     f.bg = bn_grad_out(e, L, a);
+    const WSlab sl = wgrad_slab_of(e, a.batch, a.external_loss, c.l);
+    if (sl.nparts) f.wslab = reinterpret_cast<double*>(e->ws + e->off_wslab + sl.off);
     ProfScope _p(e, "s2_convt_bwd", c.l, bytes_bwd(a.batch, L, false, false));
     rows_bwd_launch(L, f, e->stream);
 }
@@ -395,6 +397,12 @@ int bwd_ct_lds(cae_engine* e, const StepArgs& a, const ConvBwd& c) {
     f.wacc_stride = L.sh_w >= 0 ? e->segs.n : 0;
     f.gin = c.prod.gin; f.stats_prev = c.prod.stats_in;
     f.bg = bn_grad_out(e, L, a);
+    const WSlab sl = wgrad_slab_of(e, a.batch, a.external_loss, c.l);
+    if (sl.nparts) {
+        // partial tiles stored; Linear 3's backward launch adds them up into the plain accumulator (the shards stay zero)
+        f.wslab = reinterpret_cast<float*>(e->ws + e->off_wslab + sl.off);
+        f.slab_kfull = sl.kfull; f.slab_ppg = sl.ppg;
+    }
     ProfScope _p(e, "ct_convt_bwd", c.l, bytes_bwd(a.batch, L, c.last, c.l == 0));
     if (cae_internal::ctbwd_launch(&f, sizeof f, (unsigned)cp.groups, (unsigned)(L.cin / 16), (unsigned)cp.parts, cp.lds_launch, e->stream))
         return fail(CAE_ERR_ARG, "k_ct_bwd_lds: argument layout mismatch");
@@ -513,7 +521,10 @@ int linear_bwd_pair(cae_engine* e, const StepArgs& a, int i, const ConvLayer& P)
         // (gd as built above: unit strides along k in A and along n in B, A rows K floats apart, no BatchNorm mask but for i = 0)
         const bool burst = linear_bwd_burst(e, i);
         if (burst && gemm16_burst_lds(gd.K) > lds) lds = gemm16_burst_lds(gd.K);
-        hipLaunchKernelGGL(k_gemm16_pair, dim3(tiles_w + tiles_d), dim3(256), lds, e->stream, gw, gd, tiles_w, burst ? 1 : 0);
+        // Linear 3's launch, the first behind the decoder's backward, also folds the weight-gradient slabs that wrote (the
+        // fold workgroups come first in the grid; the algorithmic bytes above stay the two GEMMs')
+        const WFold fold = i == 3 ? wgrad_fold_of(e, wgrad_slab_table(e, B, a.external_loss, e->wslab_bytes)) : zeroed<WFold>();
+        hipLaunchKernelGGL(k_gemm16_pair, dim3(fold.nwg + tiles_w + tiles_d), dim3(256), lds, e->stream, gw, gd, tiles_w, burst ? 1 : 0, fold);
     }
     if (i == 2 && e->variational) {
         if (!e->hooks.reparam_bwd) return fail(CAE_ERR_STATE, "trunk engine without a reparameterisation hook");

@@ -82,6 +82,10 @@ struct cae_engine {
     int64_t off_xbatch = 0;     // the current batch's inputs, contiguous (written by k_head_fwd, read by k_adam's fused conv-0 weight gradient)
     bool x_published = false;   // this step's k_head_fwd wrote them
     AdamConv0 c0_pending{};     // filled by launch_backward when the conv-0 weight gradient is left to k_adam
+    // weight-gradient partial slabs (engine_choose.h wgrad_slabs_on): a region outside the zeroed range, every slot is
+    // overwritten by the step that reads it
+    bool wgrad_atomics = false;   // cae_set_kernel_mode bit 3: weight-gradient partials by atomics, as before the slabs
+    int64_t off_wslab = 0, wslab_bytes = 0;
     // profiling (cae_profile_begin/end): every launch bracketed by an event pair, plain launches
     bool profiling = false;
     struct ProfRec { const char* name; int layer; double bytes; hipEvent_t e0, e1; };

@@ -13,7 +13,8 @@
 //        input gradient, one tile of 16 positions:  gin[p][ci] = sum_{co,tap} gy'[co][2y+ky][2x+kx] W[ci][co][tap]
 //            (K = Cout x 12: the nine taps of a channel padded to three k-steps; the pad slots multiply a zero weight);
 //        weight gradient, one tile of 16 (co,tap) columns:  dW[ci][(co,tap)] = sum_p act(a[ci][p]) gy'[co][2y+ky][2x+kx]
-//            (K = the workgroup's positions; fp64 atomics into the accumulator: B / imgs per address);
+//            (K = the workgroup's positions; the tile is stored to the layer's partial slab, which Linear 3's backward launch
+//            folds - or, without a slab, added by fp64 atomics into the accumulator: B / imgs per address);
 //   3. epilogue of the input gradient: ReLU mask of the producer, its BatchNorm-backward sums (per channel: lanes, then LDS,
 //      then one fp64 atomic per channel and workgroup), stores.
 // Only 3x3 kernels at stride 2 without padding (OH >= 2H + 1): everything else stays on k_ig_bwd_pair.
@@ -40,6 +41,11 @@ struct CtBwd {
     double* wacc;          // (Cin, Cout*9) fp64 accumulator, or its sharded side table (shard stride wacc_stride doubles)
     long long wacc_stride; // 0: not sharded
     BnGradOut bg;
+    // non-null: the weight-gradient tiles are stored, not added - wslab[partial][Cin * Cout*9], one partial per workgroup and
+    // chunk of positions (ct_bwd_slab, engine_choose.h); the Linear-3 backward launch folds them (kernels_gemm.h)
+    float* wslab;
+    int slab_kfull;        // chunks of a full band (bands > 1) / of a full image group
+    int slab_ppg;          // partials per grid x: the chunks of an image's bands / slab_kfull
 };
 
 constexpr int kCtbThreads = 512;
@@ -352,7 +358,13 @@ __device__ __forceinline__ void ct_bwd_body(const CtBwd& a) {
                 }
             }
             // register j of lane (r, q) is row (channel) 4q + j, column n
-            if (n_ok) {
+            if (n_ok && a.wslab) {
+                // this workgroup's chunk kc is partial (image group, band, kc) of the layer: 16 consecutive columns per row
+                const int part = (int)blockIdx.x * a.slab_ppg + (BAND ? (int)blockIdx.z * a.slab_kfull : 0) + kc;
+                float* sl = a.wslab + (size_t)part * a.Cin * N;
+#pragma unroll
+                for (int j = 0; j < 4; j++) sl[(size_t)(cb * 16 + 4 * q + j) * N + n] = acc[j] + acc1[j];
+            } else if (n_ok) {
 #pragma unroll
                 for (int j = 0; j < 4; j++) acc_add<ACC_GRAD>(&wacc_sh[(size_t)(cb * 16 + 4 * q + j) * N + n], (double)(acc[j] + acc1[j]));
             }

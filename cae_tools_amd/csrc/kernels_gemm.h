@@ -246,14 +246,99 @@ __global__ void __launch_bounds__(256) k_gemm16(GemmArgs g) {
     gemm16_body(g, blockIdx.x, lds_d);
 }
 
-// two independent GEMMs in one launch (a Linear layer's weight gradient beside its input gradient):
-// workgroups [0, na) run `a`, the rest run `b`
-__global__ void __launch_bounds__(256) k_gemm16_pair(GemmArgs a, GemmArgs b, int na, int b_burst) {
-    kernarg_warm<2 * sizeof(GemmArgs) + 8>();
+// ---- fold of the decoder's weight-gradient partial slabs (kernels_ctbwd.h CtBwd::wslab, kernels_rows.h S2Rows::wslab) ---------
+// The decoder's backward kernels used to end with one fp64 atomic per workgroup and weight; nothing reads those sums before
+// the optimiser, but each kernel had to drain them before its successor could start.  They now store their partial tiles
+// with plain stores, slab[partial][value], and the launch that always follows the decoder's backward - Linear 3's pair, a few
+// hundred small workgroups on an otherwise idle chip - adds them up: every partial rounded to the ACC_GRAD grid exactly as
+// acc_add rounded it, summed in fp64 (exact on that grid, hence the bits of the atomics in any order), stored to the plain
+// fp64 gradient accumulator (the optimiser adds the layer's shards, which then stay zero, to it).  The row kernels' slabs
+// (kernels_rows.h) hold the fp64 four-wave sums they handed to acc_add.
+constexpr int kFoldMax = 6;      // slabs (decoder layers) per launch
+constexpr int kFoldBurst = 16;   // partials a thread requests before it adds the first
+
+// A fold workgroup takes 2^vshift values of one slab: 256 >> vshift groups of lanes, group g adds partials g, g + groups, ...
+// in bursts of kFoldBurst, the groups meet in LDS.  fold_vshift: the fewest groups (most values per workgroup, 8 at least)
+// whose single burst covers the partials - more, shorter workgroups for the slabs with many partials, few for the slabs
+// with few.
+struct WFoldSlab {
+    const void* slab;    // [nparts][nvals] float (f64 == 0: MFMA tiles) or double (f64 == 1: the row kernels' four-wave sums)
+    double* acc;         // [nvals]
+    int nvals, nparts;
+    int f64, vshift;
+};
+struct WFold {
+    int nwg;             // fold workgroups, first in the grid: the sum over the slabs of fold_wgs; 0: none
+    int nslab;
+    WFoldSlab s[kFoldMax];
+};
+
+inline int fold_vshift(int nparts) {
+    int vshift = 8;
+    while (vshift > 3 && (256 >> vshift) * kFoldBurst < nparts) vshift--;
+    return vshift;
+}
+__host__ __device__ inline int fold_wgs(int nvals, int vshift) { return (nvals + (1 << vshift) - 1) >> vshift; }
+
+template <class T>
+__device__ __forceinline__ double wgrad_fold_column(const T* col, int first, int step, int nparts, int nvals) {
+    double sum = 0.0;
+    for (int p0 = first; p0 < nparts; p0 += step * kFoldBurst) {
+        // one burst of clamped, unconditional loads (see gemm16_burst_body), masked afterwards
+        T x[kFoldBurst];
+#pragma unroll
+        for (int u = 0; u < kFoldBurst; u++) x[u] = col[(size_t)min(p0 + step * u, nparts - 1) * nvals];
+#pragma unroll
+        for (int u = 0; u < kFoldBurst; u++) asm volatile("" : "+v"(x[u]));
+#pragma unroll
+        for (int u = 0; u < kFoldBurst; u++)
+            if (p0 + step * u < nparts) sum += acc_grid<ACC_GRAD>((double)x[u]);
+    }
+    return sum;
+}
+
+__device__ __forceinline__ void wgrad_fold_body(const WFold& f, const int bx, double* lds_d) {
+    // the slab of this workgroup and its tile of values (uniform selects: no indexed copy of the kernel arguments)
+    WFoldSlab s = f.s[0];
+    int t = bx;
+    bool found = false;
+#pragma unroll
+    for (int k = 0; k < kFoldMax; k++) {
+        const int tiles = k < f.nslab ? fold_wgs(f.s[k].nvals, f.s[k].vshift) : 0;
+        if (!found && t < tiles) {
+            s = f.s[k];
+            found = true;
+        } else if (!found) {
+            t -= tiles;
+        }
+    }
+    const int tid = threadIdx.x, vals = 1 << s.vshift, groups = 256 >> s.vshift;
+    const int v = tid & (vals - 1), pg = tid >> s.vshift;
+    const int val = (t << s.vshift) + v, vc = min(val, s.nvals - 1);
+    lds_d[tid] = s.f64 ? wgrad_fold_column(static_cast<const double*>(s.slab) + vc, pg, groups, s.nparts, s.nvals)
+                       : wgrad_fold_column(static_cast<const float*>(s.slab) + vc, pg, groups, s.nparts, s.nvals);
+    __syncthreads();
+    if (tid < vals && val < s.nvals) {
+        double sum = 0.0;
+        for (int g = 0; g < groups; g++) sum += lds_d[(g << s.vshift) + tid];
+        s.acc[val] = sum;
+    }
+}
+
+// two independent GEMMs in one launch (a Linear layer's weight gradient beside its input gradient): after the f.nwg fold
+// workgroups (dispatched first; none but in Linear 3's launch behind slab-writing decoder kernels), workgroups [0, na) run
+// `a`, the rest run `b`
+__global__ void __launch_bounds__(256) k_gemm16_pair(GemmArgs a, GemmArgs b, int na, int b_burst, WFold f) {
+    kernarg_warm<2 * sizeof(GemmArgs) + 8 + sizeof(WFold)>();
     extern __shared__ double lds_d[];
-    if ((int)blockIdx.x < na) gemm16_body(a, blockIdx.x, lds_d);
-    else if (b_burst) gemm16_burst_body(b, blockIdx.x - na, lds_d);
-    else gemm16_body(b, blockIdx.x - na, lds_d);
+    if ((int)blockIdx.x < f.nwg) {
+        wgrad_fold_body(f, blockIdx.x, lds_d);
+        return;
+    }
+    const int bx = (int)blockIdx.x - f.nwg;
+    if (bx < na) gemm16_body(a, bx, lds_d);
+    else if (b_burst) gemm16_burst_body(b, bx - na, lds_d);
+    else gemm16_body(b, bx - na, lds_d);
 }
 
 }  // namespace cae

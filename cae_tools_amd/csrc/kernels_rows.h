@@ -35,6 +35,8 @@ struct S2Rows {
     double* wacc;            // sharded [kStatShards][wacc_stride]
     int wacc_stride;
     BnGradOut bg;            // this layer's BatchNorm parameter gradients (published by workgroup 0)
+    double* wslab;           // non-null: the workgroup's weight-gradient sums are stored to wslab[workgroup][CIN*COUT*KH*KW], not
+                             // added to wacc; Linear 3's backward launch folds them (kernels_gemm.h wgrad_fold_body)
 };
 
 // CT input channels per wave (CS = CIN / CT channel groups = waves sharing a band), IMGS images side by side in a wave
@@ -341,7 +343,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
 #pragma unroll
         for (int q = 0; q < NB; q++) s += (double)redf[(q * CS + gsel) * NRED + j];
         if (j < NACC) {
-            acc_add<ACC_GRAD>(&a.wacc[(size_t)shard * a.wacc_stride + (size_t)gsel * NACC + j], s);
+            if (a.wslab) a.wslab[(size_t)blockIdx.x * (CS * NACC) + gsel * NACC + j] = s;
+            else acc_add<ACC_GRAD>(&a.wacc[(size_t)shard * a.wacc_stride + (size_t)gsel * NACC + j], s);
         } else {
             const int jj = j - NACC;
             acc_add<ACC_GRAD>(&a.stats_in[((size_t)shard * CIN + gsel * CT + (jj >> 1)) * 4 + 2 + (jj & 1)], s);

@@ -462,7 +462,8 @@ void lin_bwd(unet_engine* e, const Fc& L, int B, const float* in, const float* g
             gd.C = gin, gd.sc_m = L.nin, gd.sc_n = 1;
             gd.epi = ugemm::cae::GE_STORE;
             const int tiles_d = ((gd.M + 15) / 16) * ((gd.N + 15) / 16);
-            hipLaunchKernelGGL(ugemm::cae::k_gemm16_pair, dim3(tiles_w + tiles_d), dim3(256), gemm16_lds(), e->stream, gw, gd, tiles_w, 0);
+            hipLaunchKernelGGL(ugemm::cae::k_gemm16_pair, dim3(tiles_w + tiles_d), dim3(256), gemm16_lds(), e->stream, gw, gd, tiles_w, 0,
+                               ugemm::cae::WFold{});
             return;
         }
         case LIN_TILE: {

@@ -26,8 +26,21 @@ class EnginePlan(SpecPlan):
 
     def set_kernel_mode(self, mode):
         """cae_set_kernel_mode: 0 shape-generic kernels, 1 specialised (the default), bit 1 the LDS-staged backward on every
-        eligible layer, bit 2 the gather forward on the channel-rich decoder layers"""
+        eligible layer, bit 2 the gather forward on the channel-rich decoder layers, bit 3 (value 8) weight-gradient partials by
+        atomics as before the partial slabs (same gradients, bit for bit; see wgrad_slabs)"""
         check(self.lib.cae_set_kernel_mode(self.handle, int(mode)))
+
+    def wgrad_slabs(self, batch):
+        """the weight-gradient partial slabs of a training step at this batch (cae_debug_wgrad_slabs, include/cae_hip.h), no GPU
+        needed, parsed like kernel_plan: {"dec2": {"writer": "ct_bwd_band", "type": "f32", "param": .., "values": .., "partials": ..,
+        "offset": .., "fold_wgs": .., "fold_values": ..}, ..., "fold": {"slabs": .., "wgs": .., "bytes": .., "capacity": ..}} (all strings)"""
+        buf = C.create_string_buffer(1 << 14)
+        check(self.lib.cae_debug_wgrad_slabs(self.handle, int(batch), buf, len(buf)))
+        report = {}
+        for line in buf.value.decode().splitlines():
+            (name, *fields) = line.split()
+            report[name] = dict(f.split("=", 1) for f in fields)
+        return report
 
     def kernel_plan(self, batch, train):
         """the kernels a step at this batch runs (cae_debug_plan, include/cae_hip.h), no GPU needed:

@@ -108,7 +108,11 @@ int cae_set_capture_only(cae_engine* e, int enabled);
  * eligible channel-rich 3x3 stride-2 decoder layer runs the LDS-staged kernel (kernels_ctbwd.h) instead of the gather
  * pair; with 1 only the layers it is faster on do (one block of 16 input channels: DESIGN.md section 4).  Bit 2 (value 5):
  * the forward pass of those layers runs the gather kernel (k_ig_fwd_s2: what layers with Cin % 4 != 0 or 2-tap kernels
- * always run) instead of the LDS-staged one - kept selectable so that the full-size parity tests cover it. */
+ * always run) instead of the LDS-staged one - kept selectable so that the full-size parity tests cover it.  Bit 3 (value 9):
+ * weight-gradient partials by fp64 atomics, as before the partial slabs - without it the LDS-staged and the row-streaming
+ * backward kernels store their per-workgroup weight-gradient partials and Linear 3's backward launch adds them up
+ * (cae_debug_wgrad_slabs); the
+ * gradients are the same bits either way.  Every change of mode drops the captured graphs. */
 int cae_set_kernel_mode(cae_engine* e, int specialised);
 
 /* torch.optim.Adam(lr, betas, eps, weight_decay) with L2 decay added to the gradient
@@ -260,6 +264,17 @@ int64_t cae_debug_read(cae_engine* e, const char* what, int index, void* host_ou
  * k_conv_bwd_pair (-: there are none).
  * Fails for a batch outside 1 .. max_batch or too short a buffer. */
 int cae_debug_plan(const cae_engine* e, int batch, int train, char* out_host, int64_t out_bytes);
+
+/* The weight-gradient partial slabs of a training step at `batch`, without a GPU: which decoder backward kernels store
+ * their per-workgroup weight-gradient partials instead of adding them with atomics (the LDS-staged kernels k_ct_bwd_lds /
+ * k_ct_bwd_band and the row kernels k_s2_bwd_rows), and how the workgroups placed first in Linear 3's backward launch fold
+ * them.  One line per slab in launch order (last decoder layer first),
+ *   "dec2 writer=ct_bwd_band|ct_bwd_lds|s2_bwd_rows type=f32|f64 param=<offset of the weight in the parameter arena>
+ *    values=<weights> partials=<slab rows: one per workgroup, times the chunks of 64 positions for the ct_bwd kernels>
+ *    offset=<bytes before the slab in its region> fold_wgs=<fold workgroups> fold_values=<values each of them takes>"
+ * then "fold slabs=<n> wgs=<fold workgroups of the launch> bytes=<region in use> capacity=<bytes of the region>".
+ * Follows cae_set_kernel_mode (bit 3 or mode 0: no slabs).  Fails for a batch outside 1 .. max_batch or too short a buffer. */
+int cae_debug_wgrad_slabs(const cae_engine* e, int batch, char* out_host, int64_t out_bytes);
 
 /* ---- measurement ------------------------------------------------------------------------- */
 
