@@ -23,9 +23,11 @@ against the report and that the cases together reach (WANT):
 - k_ig_bwd_pair: ksplit 2 and 4; one and two tiles per wave; per = 32 and per > 32; chunks = 1, 2..8 and more than 8
   (w_n8 > 1); 3x3, 3x4, 4x3 and 4x4 taps; a ragged block of input channels (24 or 12).  ksplit = 1 needs Cout * KH * KW <= 48:
   those layers are all stride-2-specialised (kernels_s2.h), and test_sweep_reaches_no_ksplit_1_plan confirms that no sizer-made
-  decoder reaches it.
-Not built: a 3x3 layer with OH > 2H + 1 (the staging assumes nothing about the rows below 2H; a sizer-made decoder never pairs
-a 3x3 kernel with output padding, so only a hand-written spec could reach it).
+  decoder reaches it: the hand-written layer definitions of test_hand_specs_gpu.py do (ksplit = 1 at strides 1, 2 and 3, K no
+  multiple of 4, kernels of 1, 2, 6 and 7 taps).
+Not here: a 3x3 layer with OH > 2H + 1 (the staging assumes nothing about the rows below 2H; a sizer-made decoder never pairs
+a 3x3 kernel with output padding, so only a hand-written spec reaches it): test_hand_specs_gpu.py runs k_ct_bwd_lds and
+k_ct_bwd_band, 2 and 6 bands, at OH = 2H + 2.
 
 Per case, one training step in the case's mode and (small batches only) one on the shape-generic kernels (mode 0):
 - loss and every gradient no further from the fp64 oracle than 3x the fp32 oracle is (helpers.assert_close_as_reference),

@@ -19,13 +19,8 @@ import pytest
 import torch
 
 from helpers import assert_close_as_reference, bn_bias_keys, hip_relu_decisions, relu_fix_for
-
-ATOMICS = 8   # cae_set_kernel_mode bit 3
-kCtbKChunk = 64   # kernels_ctbwd.h: positions per weight-gradient task
-(kLastStripPx, kLastHB) = (127, 4)   # kernels_last.h / engine_choose.h: pixel columns of a strip, quad rows of a band
-# the slab writers: (writer, slab element type).  k_s2_last_fused and the weight-gradient half of k_ig_bwd_pair were tried as
-# writers and not kept; _writer and _expected_partials below still know their launches' partial counts
-KEPT_WRITERS = {("ct_bwd_band", "f32"), ("ct_bwd_lds", "f32"), ("s2_bwd_rows", "f64")}
+# the partial counts of the launches and the slab writers: one copy, shared with test_hand_specs_cpu.py
+from wgrad_slabs import ATOMICS, KEPT_WRITERS, expected_partials as _expected_partials, writer as _writer
 
 # ((output channels, height, width), batch, kernel mode, fc size, latent size)
 CASES = [((1, 80, 81), 2, 1, 16, 4), ((1, 80, 81), 3, 3, 16, 4), ((3, 82, 83), 8, 1, 16, 4), ((1, 256, 256), 13, 3, 128, 32)]
@@ -80,40 +75,6 @@ def test_cases_reach_what_they_name():
     want = {("ctb_kernel", "band"), ("ctb_kernel", "lds"), ("ctb_sharded", "0"), ("ctb_sharded", "1"),
             "lds: two images per workgroup, ragged last group", "ig_bwd_pair with chunks > 1", "s2_bwd_rows", "fused last layer"}
     assert want <= reached, sorted(map(str, want - reached))
-
-
-def _expected_partials(layer, rep, batch):
-    """workgroups (x chunks of positions) of the layer's backward launch, from the plan report and the layer's geometry"""
-    (ci, h, w) = layer["input_dimensions"]
-    (_, oh, ow) = layer["output_dimensions"]
-    (qh, qw) = ((oh + 1) // 2, (ow + 1) // 2)
-    if rep["bwd"] == "(fused)":            # k_s2_last_fused: four (image, strip, band of 4 quad rows) units per workgroup
-        strips = -(-max(w, qw - 1) // kLastStripPx)
-        return -(-batch * strips * -(-max(h, qh - 1) // kLastHB) // 4)
-    if rep["bwd"].startswith("s2_bwd_rows<"):   # k_s2_bwd_rows<CIN, CT, COUT, 3, 3, HB, IMGS, D>: 4 / (CIN / CT) bands per workgroup
-        (cin, ct, _, _, _, hb, imgs, _) = (int(v) for v in rep["bwd"][len("s2_bwd_rows<"):-1].split(","))
-        bands = -(-max(h, qh - 1) // hb)
-        return -(-batch // imgs) * -(-bands // (4 // (cin // ct)))
-    if rep["bwd"] == "ig_bwd_pair":        # the weight-gradient half: one slab row per K chunk
-        return int(rep["ig_chunks"])
-    chunks = lambda positions: -(-positions // kCtbKChunk)
-    (imgs, groups, bands, hb) = (int(rep[k]) for k in ("ctb_imgs", "ctb_groups", "ctb_bands", "ctb_hb"))
-    if rep["ctb_kernel"] == "band":
-        rows = [min(hb, h - z * hb) for z in range(bands)]          # grid z = band
-        return groups * sum(chunks(r * w) for r in rows)
-    return sum(chunks(min(imgs, batch - x * imgs) * h * w) for x in range(groups))   # grid x = image group
-
-
-def _writer(rep):
-    if rep["bwd"] == "ct_bwd_lds":
-        return ("ct_bwd_" + rep["ctb_kernel"], "f32")
-    if rep["bwd"] == "(fused)":
-        return ("s2_last_fused", "f64")
-    if rep["bwd"].startswith("s2_bwd_rows<"):
-        return ("s2_bwd_rows", "f64")
-    if rep["bwd"] == "ig_bwd_pair":
-        return ("ig_bwd_pair", "f32")
-    return None
 
 
 # the GPU cases, the benchmark geometry, and two of test_ct_bwd_shapes_gpu.py's: whole maps of one image in four chunks
