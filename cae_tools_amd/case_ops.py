@@ -1,6 +1,6 @@
 """The case kernels of libcae_hip (include/cae_hip.h) as functions, no engine needed: measures, per-pixel sums, spectra, SSIM,
-interpolation baseline, value distributions, skill by stratum, neighbourhood skill, ensemble verification, value range and
-rendered pages of channel 0 of (N, C, H, W) operands."""
+interpolation baseline, value distributions, skill by stratum, neighbourhood skill, permutation importance, ensemble
+verification, value range and rendered pages of channel 0 of (N, C, H, W) operands."""
 import ctypes as C
 import math
 from contextlib import contextmanager
@@ -375,6 +375,82 @@ def fraction_skill(pred, actual, thresholds, widths=None, gaps="strict", device=
             g = min(n, c0 + group) - c0
             check(lib.cae_case_fss(*p.args(c0), *a.args(c0), g, h, w, thr_c, side_c, n_thr, width_c, n_width, rule,
                                    sums[c0:].data_ptr(), ws.data_ptr(), need, stream))
+        return sums.cpu().numpy()
+
+
+def operand_cases(op, c0, c1):
+    """the cases c0 .. c1 - 1 of a device operand as an operand of its own: no copy, the tensor is a view of op's"""
+    (c0, c1) = (int(c0), int(c1))
+    if not 0 <= c0 <= c1 <= int(op.shape[0]):
+        raise IndexError(f"operand_cases: cases [{c0}, {c1}) are not within [0, {int(op.shape[0])})")
+    if op.tensor.dim() == 1 and op.tensor.dtype == torch.uint8:     # the raw bytes of a big-endian slab
+        per = op.stride * op.elem_bytes
+        view = op.tensor[c0 * per:c1 * per]
+    else:
+        view = op.tensor[c0:c1]
+    return DeviceOperand(view, op.kind, (c1 - c0,) + tuple(op.shape[1:]), op.stride)
+
+
+def pack_gather(raw, dst, c_off, rows, vmin, vmax, enable=True):
+    """dst[i, c_off:c_off + Cv] = normalise(raw[rows[i]]) on the device (cae_normalise_pack_gather, include/cae_hip.h): the
+    arithmetic of device_ops.normalise_pack bit for bit, the source row of every destination row read from rows, an int32
+    CUDA tensor of dst.shape[0] entries in any order, repeats allowed.  raw: (n_src, Cv, h, w) fp32 CUDA tensor; dst:
+    (n_dst, C, h, w) fp32 CUDA tensor, whose other channels are not touched.  A row index outside 0 .. n_src - 1 is not
+    followed: that row of dst gets NaN."""
+    for (name, t) in (("raw", raw), ("dst", dst)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 2 and t.is_contiguous()):
+            raise ValueError(f"pack_gather: {name} must be a contiguous float32 CUDA tensor of at least 2 dimensions")
+    if not (isinstance(rows, torch.Tensor) and rows.dtype == torch.int32 and rows.device == raw.device and rows.dim() == 1
+            and rows.is_contiguous() and rows.numel() == int(dst.shape[0])) or dst.device != raw.device:
+        raise ValueError("pack_gather: rows must be a contiguous int32 tensor of one entry per row of dst on the data's device")
+    (n_src, c_src) = (int(raw.shape[0]), int(raw.shape[1]))
+    hw = int(np.prod(raw.shape[2:]))
+    if int(np.prod(dst.shape[2:])) != hw:
+        raise ValueError(f"pack_gather: planes of raw {tuple(raw.shape)} and dst {tuple(dst.shape)} do not match")
+    rng = float(vmax) - float(vmin)
+    lib = _lib.load()
+    with _stream(raw.device) as stream:
+        check(lib.cae_normalise_pack_gather(raw.data_ptr(), n_src, c_src, hw, dst.data_ptr(), int(dst.shape[0]), int(dst.shape[1]),
+                                            int(c_off), C.c_float(float(np.float32(vmin))), C.c_float(float(np.float32(rng))),
+                                            1 if enable else 0, rows.data_ptr(), stream))
+
+
+def case_importance(base, pert, actual, vmin, vmax, maps=None, device=None):
+    """The eight sums of permutation importance per case (cae_case_importance, include/cae_hip.h): an (N, 8) float64 numpy
+    array {n, S e1^2, S e0^2, S|e1|, S|e0|, S (P1 - P0)^2, #(e1^2 > e0^2), #(e1^2 < e0^2)} of channel 0 with P = vmin +
+    (double)p * (vmax - vmin) for the unperturbed scores base and the perturbed scores pert - fp32 CUDA tensors (N, C, H, W)
+    as the model wrote them - and e = P - a against the target actual as stored, over the pixels where a, P0 and P1 are all
+    finite.  actual as case_measures takes it.  maps: None, or a (3, H, W) float64 CUDA tensor {count, S e1^2, S e0^2} per
+    pixel that is CARRIED: the call adds its cases to it in place, the caller clears it before the first call; the map after
+    a run of calls over consecutive cases is the same bits as after one call.  A case's sums do not depend on the other
+    cases of the call or on maps.  utils/importance.summary turns the sums into the scores."""
+    device = _case_device(device, base, pert, actual)
+    for (name, t) in (("base", base), ("pert", pert)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.device == device):
+            raise ValueError(f"case_importance: {name} must be a float32 CUDA tensor (N, C, H, W) on the device of the call")
+    if tuple(base.shape) != tuple(pert.shape):
+        raise ValueError(f"case_importance: base {tuple(base.shape)} and pert {tuple(pert.shape)} do not match")
+    (base, pert) = (base.contiguous(), pert if pert is base else pert.contiguous())
+    a = device_operand(actual, device)
+    if len(a.shape) != 4 or a.shape[0] != base.shape[0] or tuple(a.shape[2:]) != tuple(base.shape[2:]):
+        raise ValueError(f"case_importance: scores {tuple(base.shape)} and target {tuple(a.shape)} do not match")
+    (n, h, w) = (int(base.shape[0]), int(base.shape[2]), int(base.shape[3]))
+    plane = h * w
+    if maps is not None and not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.float64
+                                 and tuple(maps.shape) == (3, h, w) and maps.is_contiguous() and maps.device == device):
+        raise ValueError(f"case_importance: maps must be a contiguous float64 CUDA tensor (3, {h}, {w}) on the device of the call")
+    (vmin, rng) = (float(vmin), float(vmax) - float(vmin))
+    if not (math.isfinite(vmin) and math.isfinite(rng)):
+        raise ValueError(f"case_importance: vmin and vmax - vmin must be finite, got vmin {vmin!r} and vmax {vmax!r}")
+    if n == 0 or plane == 0:
+        return np.zeros((n, 8), dtype=np.float64)
+    lib = _lib.load()
+    sums = torch.empty((n, 8), dtype=torch.float64, device=device)
+    (ws, need) = _workspace(device, lib.cae_case_importance_workspace_bytes, n, plane, least=16)
+    with _stream(device) as stream:
+        check(lib.cae_case_importance(base.data_ptr(), int(base.stride(0)), pert.data_ptr(), int(pert.stride(0)), *a.args(), n, plane,
+                                      vmin, rng, sums.data_ptr(), maps.data_ptr() if maps is not None else None, ws.data_ptr(), need,
+                                      stream))
         return sums.cpu().numpy()
 
 

@@ -21,6 +21,9 @@ from .model_metric import DeviceModelMetric, ModelMetric  # noqa: F401
 from .model_sizer import ModelSpec, create_model_spec
 
 
+_IMPORTANCE_BYTES = 256 << 20       # of fp32 inputs and scores per piece of cases of importance()
+
+
 def _make_data_array(like_ds, data, dims):
     """DataArray of the same family as the dataset it is assigned into"""
     if type(like_ds).__module__.startswith("xarray"):
@@ -187,6 +190,71 @@ class BaseModel:
         scene_ds[prediction_variable] = _make_data_array(scene_ds, out.cpu().numpy(),
                                                          (time_dimension, channel_dimension, y_dimension, x_dimension))
         return out
+
+    def importance(self, ds, input_variables, output_variable, groups=None, repeats=5, seed=0, maps=False, case_chunk=None):
+        """Permutation importance of the input variables (build-only; DESIGN.md §9 'input importance'): every case is given
+        another case's values for one group of variables, the batch is scored again and the growth of the error against the
+        target is reported.  groups: lists of input-variable names (None: every variable on its own); repeats: 1 to 64
+        permutations, each a single cycle over the cases (utils/importance.permutations(n, repeats, seed)), the same for
+        every group.  Each input variable goes to the GPU once; for every group, repeat and piece of case_chunk cases
+        (None: a byte budget) the group's channels of the packed batch are re-packed from the permuted cases
+        (cae_normalise_pack_gather), the piece is scored through _score_all and reduced against the unperturbed scores and
+        the target as stored (cae_case_importance), and the channels are put back.  The result does not depend on
+        case_chunk.  maps=True also sums {count, S e1^2, S e0^2} per pixel over the cases and repeats of a group.  Returns
+        the record of utils/importance.summary (with "maps" (G, 3, H, W) when asked for).  Collective under a
+        torch.distributed.run launch, as _score_all is."""
+        from .. import dp as _dp
+        from ..case_ops import case_importance, device_operand, operand_cases, pack_gather
+        from ..data.arrays import as_numpy
+        from ..utils import importance as _imp
+        _dp.ensure_process_group()
+        names = list(input_variables)
+        groups = _imp.check_groups(groups, names)
+        repeats = _imp.check_repeats(repeats)
+        data = DSDataset(ds, names, output_variable, normalise_in=self.normalise_input, normalise_out=False)
+        data.set_normalisation_parameters(self.normalisation_parameters)
+        n = len(data)
+        if n < 2:
+            raise ValueError(f"importance: at least 2 cases expected, got {n}")
+        x = data.device_inputs()
+        device = x.device
+        target = device_operand(as_numpy(ds[output_variable]), device)
+        (vmin, vmax) = (data.min_output, data.max_output)
+        offsets = {}
+        off = 0
+        for (name, raw) in zip(names, data._raw_in):
+            offsets[name] = (off, raw)
+            off += int(raw.shape[1])
+        (h_out, w_out) = (int(target.shape[2]), int(target.shape[3]))
+        per_case = 4 * (int(np.prod(x.shape[1:])) + int(np.prod(target.shape[1:])))
+        chunk = max(1, min(n, _IMPORTANCE_BYTES // per_case)) if case_chunk is None else int(case_chunk)
+        if chunk < 1:
+            raise ValueError(f"importance: case_chunk must be at least 1, got {case_chunk!r}")
+        pieces = [(c0, min(n, c0 + chunk)) for c0 in range(0, n, chunk)]
+        base = [self._score_all(x[c0:c1]) for (c0, c1) in pieces]
+        perms = torch.from_numpy(_imp.permutations(n, repeats, seed)).to(device)
+        sums = np.zeros((len(groups), repeats, n, 8), dtype=np.float64)
+        fields = torch.zeros((len(groups), 3, h_out, w_out), dtype=torch.float64, device=device) if maps else None
+        batch = torch.empty((min(chunk, n),) + tuple(x.shape[1:]), dtype=torch.float32, device=device)
+        held = None             # the piece whose unperturbed rows `batch` holds
+        for (g, group) in enumerate(groups):
+            for r in range(repeats):
+                for (k, (c0, c1)) in enumerate(pieces):
+                    xb = batch[:c1 - c0]
+                    if held != k:
+                        xb.copy_(x[c0:c1])
+                        held = k
+                    rows = perms[r, c0:c1].contiguous()
+                    for name in group:
+                        (c_off, raw) = offsets[name]
+                        pack_gather(raw, xb, c_off, rows, data.min_inputs[name], data.max_inputs[name], enable=self.normalise_input)
+                    pert = self._score_all(xb)
+                    sums[g, r, c0:c1] = case_importance(base[k], pert, operand_cases(target, c0, c1), vmin, vmax,
+                                                        maps=fields[g] if maps else None, device=device)
+                    for name in group:
+                        (c_off, raw) = offsets[name]
+                        xb[:, c_off:c_off + int(raw.shape[1])] = x[c0:c1, c_off:c_off + int(raw.shape[1])]
+        return _imp.summary(groups, sums, seed=seed, maps=fields.cpu().numpy() if maps else None)
 
     def dump_metrics(self, title, metrics):
         print("\n" + title)

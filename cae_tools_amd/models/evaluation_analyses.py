@@ -1,6 +1,6 @@
 """The optional outputs of ModelEvaluator.build_html, none of them a reference feature: ensemble verification, case pages,
 structural similarity, skill against interpolation, per-pixel skill maps, power spectra, value distributions, skill by
-stratum and neighbourhood skill.
+stratum, neighbourhood skill and input importance.
 
 Each is one Analysis of functions over the evaluator `ev`:
     enabled(ev)                                     whether its option is on
@@ -24,6 +24,7 @@ from ..utils import baseline as baseline_scores
 from ..utils import distribution as distribution_curves
 from ..utils import ensemble_scores, skill_maps
 from ..utils import fss as fss_scores
+from ..utils import importance as importance_scores
 from ..utils import spectra as spectra_curves
 from ..utils import ssim as ssim_scores
 from ..utils import strata as strata_scores
@@ -367,6 +368,69 @@ def _fss(ev, parts, report):
     report["fss"] = (found, "fss/index.html")
 
 
+# ---- input importance ------------------------------------------------------------------------
+
+def check_importance(ev):
+    if not ev.importance:
+        return
+    importance_scores.check_repeats(ev.importance_repeats)
+    if int(ev.importance_seed) != ev.importance_seed or int(ev.importance_seed) < 0:
+        raise ValueError(f"importance_seed must be an integer, 0 or more, got {ev.importance_seed!r}")
+    importance_scores.check_groups(ev.importance_groups)
+
+
+def check_importance_model(ev):
+    """what check_importance cannot see before the model is loaded: the groups name input variables of the model, and every
+    partition holds those variables and at least 2 cases"""
+    if not ev.importance:
+        return
+    names = list(ev.model_input_variables)
+    importance_scores.check_groups(ev.importance_groups, names)
+    for (partition, paths) in (("test", ev.testing_paths), ("train", ev.training_paths)):
+        ds = ev._open(paths)
+        if ds is None:
+            continue
+        missing = [name for name in names if name not in ds]
+        if missing:
+            raise ValueError(f"importance needs the model's input variables in the {partition} data set: {', '.join(missing)} "
+                             f"of {ev.model_path} {'is' if len(missing) == 1 else 'are'} not there")
+        n = int(ds[names[0]].shape[0])
+        if n < 2:
+            raise ValueError(f"importance needs at least 2 cases to permute, the {partition} data set has {n}")
+
+
+def _importance(ev, parts, report):
+    """importance=True (cli/importance.py) asks which of its inputs the model uses: permutation importance.  Per partition
+    every case is given another case's values for one group of input variables (importance_groups; default every variable
+    on its own) by importance_repeats single-cycle permutations drawn from importance_seed, the batch is scored again
+    through the model and the growth of the error against the target is reduced on the GPU (BaseModel.importance:
+    cae_normalise_pack_gather and cae_case_importance; utils/importance.py): importance_<partition>.json
+    with, per group, the pooled mse and mae with and without the permutation per repeat, importance = their difference with
+    its standard deviation over the repeats, the ratio, the sensitivity of the prediction, the shares of cases and pixels
+    whose error grew, the rank and the per-case change of the mse; the report's "Input importance" section; and with
+    importance_maps importance/index.html, one map of the change of the mse per pixel and group, drawn the way the skill maps
+    are over one symmetric range."""
+    found = []
+    drawn = []
+    for (partition, ds) in parts:
+        record = ev.model.importance(ds, ev.model_input_variables, ev.output_variable, groups=ev.importance_groups,
+                                     repeats=int(ev.importance_repeats), seed=int(ev.importance_seed), maps=bool(ev.importance_maps))
+        _keep(ev, importance_scores, "importance", partition, record, found)
+        if ev.importance_maps:
+            flip = bool(ev.y_coordinate) and ev.flip_y(ds, ev.output_variable)
+            drawn.append((partition, record, device_operand(importance_scores.delta_maps(record)[:, None]), flip))
+    link = None
+    if drawn:
+        spans = [s for s in (case_range(op) for (_, _, op, _) in drawn) if s[2] > 0]
+        bound = max((max(abs(s[0]), abs(s[1])) for s in spans), default=0.0)
+        pages = [(partition, record, -bound, bound,
+                  [(g["name"], render_cases(op, -bound, bound, cases=[k], flip_y=flip)[0]) for (k, g) in enumerate(record["groups"])])
+                 for (partition, record, op, flip) in drawn]
+        importance_scores.write_maps_page(os.path.join(ev.output_html_folder, "importance"), pages)
+        link = "importance/index.html"
+    report["importance"] = (found, link)
+
+
 ENSEMBLE = Analysis(lambda ev: ev.ensemble_size is not None, check_ensemble, partition=_ensemble)
 CASE_PAGES = Analysis(lambda ev: ev.x_coordinate and ev.y_coordinate and ev.time_coordinate, partition=_case_pages)
 SSIM = Analysis(lambda ev: ev.ssim, partition=_ssim)
@@ -377,5 +441,6 @@ DISTRIBUTION = Analysis(lambda ev: ev.distribution, check_distribution, after=_d
 STRATA = Analysis(lambda ev: ev.strata, check_strata, after=_strata)
 FSS = Analysis(lambda ev: ev.fss, check_fss, after=_fss)
 # in the order build_html runs them: per partition ensemble, case pages, ssim, baseline; then skill maps, spectra, distribution,
-# strata, fss
-ANALYSES = (ENSEMBLE, CASE_PAGES, SSIM, BASELINE, SKILL_MAPS, SPECTRA, DISTRIBUTION, STRATA, FSS)
+# strata, fss, importance
+IMPORTANCE = Analysis(lambda ev: ev.importance, check_importance, after=_importance)
+ANALYSES = (ENSEMBLE, CASE_PAGES, SSIM, BASELINE, SKILL_MAPS, SPECTRA, DISTRIBUTION, STRATA, FSS, IMPORTANCE)

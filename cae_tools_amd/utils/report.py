@@ -221,7 +221,8 @@ def _section(body, title, records, heading, rows, plots=None):
 
 
 def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None, ensemble=None,
-                      spectra_link=None, ssim=None, baseline=None, distribution=None, strata=None, fss=None):
+                      spectra_link=None, ssim=None, baseline=None, distribution=None, strata=None, fss=None,
+                      importance=None):
     """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
     metrics: {"test": {...}, "train": {...}} (either may be absent); measures: [(partition, {"mae": values, "mse": values})]
     in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}; maps_link: href of
@@ -238,7 +239,9 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
     section with the table of the scores per stratum and pooled and the bar chart of bias +- rmse per stratum; fss:
     ([(partition, record)] of utils/fss.summary, href of the neighbourhood skill page): a "Neighbourhood skill" section with
     the table of the pooled Fractions Skill Score per threshold and width, the uniform level and the skilful width, and the
-    link."""
+    link; importance: ([(partition, record)] of utils/importance.summary, href of the page of per-pixel maps or None): an
+    "Input importance" section with the table of the groups of input variables by rank, the bar chart of importance +- sd,
+    and the link where there is one."""
     doc = Document("Model Evaluation")
     doc.head.add("style").text(STYLE)
     body = doc.body
@@ -300,6 +303,13 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
                  fss_scores.section_rows)
         if link:
             body.add("p").add("a", {"href": link}).text("Fractions Skill Score of prediction against target")
+    if importance:
+        from . import importance as importance_scores
+        (records, link) = importance
+        _section(body, "Input importance", records, importance_scores.heading, importance_scores.section_rows,
+                 {"input importance": lambda rec: importance_scores.svg_bars(rec, "importance +- sd")})
+        if link:
+            body.add("p").add("a", {"href": link}).text("Change of the mse per pixel by group of input variables")
     if parameters or history:
         body.add("h2").text("Training Summary")
     if parameters:

@@ -740,6 +740,47 @@ int cae_case_fss(const void* pred_dev, int pred_kind, int64_t pred_case_stride,
                  int64_t* sums_dev /* [n_case][n_thr][n_width][6] */,
                  void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- permutation importance of the input variables (stateless) --------------------------------- */
+
+/* A packed batch whose rows are drawn from chosen cases: dst[i, c_off + c, :] = norm(src[row[i], c, :]) for i < n_dst, with
+ * src_dev (n_src, c_src, hw) fp32, dst_dev (n_dst, c_dst, hw) fp32 and norm cae_normalise_pack's arithmetic bit for bit:
+ * (v - vmin) / range in two rounded fp32 operations, 0 where range == 0, v itself with enable == 0.  row_dev: n_dst int32 on
+ * the device, in any order, repeats allowed.  The host cannot see them, so the kernel checks each: an index outside
+ * 0 .. n_src - 1 is not dereferenced and row i of dst (its c_src channels) gets quiet NaNs, which takes the case out of every
+ * sum of cae_case_importance by its pair rule.  The other channels of dst are not touched.  One launch, no workspace.
+ * n_dst == 0 or hw == 0 succeeds and writes nothing.  Negative sizes, c_src < 1, c_off outside 0 .. c_dst - c_src, more than
+ * 2^31 - 1 rows, NULL or misaligned pointers, an operand reaching 2^60 elements: CAE_ERR_ARG, nothing written. */
+int cae_normalise_pack_gather(const float* src_dev, int64_t n_src, int c_src, int64_t hw, float* dst_dev, int64_t n_dst, int c_dst,
+                              int c_off, float vmin, float range, int enable, const int32_t* row_dev, void* hip_stream);
+
+/* Permutation importance compares, against the target, the scores of a batch with the scores of the same batch after one
+ * group of input variables was given another case's values.  base_dev and pert_dev: channel 0 of the unperturbed scores p0
+ * and the perturbed scores p1, fp32 as the model wrote them, case i at element i * case_stride.  actual_dev: the target a as
+ * stored, any CAE_ELEM_* kind, big-endian kinds included, as cae_case_measures takes it.  In fp64
+ *   P = vmin + (double)p * range            (cae_denormalise_f64's two rounded operations: P0 is what apply() stores)
+ * A pixel is a pair when a, P0 and P1 are all finite; every other pixel is left out.  e0 = P0 - a, e1 = P1 - a, each
+ * subtraction and product rounded on its own, nothing contracted.
+ *   sums_dev[case][0..7] = {n, S e1^2, S e0^2, S|e1|, S|e0|, S (P1 - P0)^2, #(e1^2 > e0^2), #(e1^2 < e0^2)}   over the pairs
+ *   map_dev[0..2][plane] += {count, S e1^2, S e0^2}                                          over the cases, per pixel
+ * sums_dev is written whole.  map_dev is NULL (no map) or CARRIED: the call adds its cases to what is there and the caller
+ * clears it before the first call.  Counts are exactly representable doubles (integers below 2^53).
+ * Fold order.  The plane is cut into tiles of 64 consecutive pixels, one pixel per lane.  A case's addends are summed over
+ * a tile in a fixed tree over the 64 lanes, the tiles by lane j taking tiles j, j + 64, ... in ascending order and the same
+ * tree over the lanes: the order depends on the plane alone, so a case's eight sums do not depend on the other cases of the
+ * call, on n_case, on the operands' alignment or on whether a map is asked for.  A pixel of the map belongs to one lane for
+ * the whole call; its running sums take the cases in ascending order with plain adds, so the map after cases 0 .. N - 1 is
+ * the same bits however the cases are cut into consecutive calls.  No floating-point atomics: the same arguments give the
+ * same bits from run to run.
+ * workspace_dev (16-byte aligned) holds cae_case_importance_workspace_bytes = n_case * ceil(plane / 64) * 64 bytes (0 for an
+ * empty call).  n_case == 0 or plane == 0 succeeds and writes nothing.  A bad kind, negative sizes or strides, vmin or range
+ * not finite, NULL pointers, a stride shorter than the plane, an operand reaching 2^60 elements from its pointer, misaligned
+ * pointers, too small or misaligned a workspace: CAE_ERR_ARG, nothing written. */
+int64_t cae_case_importance_workspace_bytes(int64_t n_case, int64_t plane);
+int cae_case_importance(const float* base_dev, int64_t base_case_stride, const float* pert_dev, int64_t pert_case_stride,
+                        const void* actual_dev, int actual_kind, int64_t actual_case_stride, int64_t n_case, int64_t plane,
+                        double vmin, double range, double* sums_dev /* [n_case][8] */, double* map_dev /* NULL or [3][plane] */,
+                        void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 /* ---- scene apply (stateless): a box model applied to a whole scene ----------------------------- */
 
 /* A model maps an input box (c, h, w) to an output box (c_out, H, W) with H = h * sy, W = w * sx.  A scene variable is
