@@ -142,6 +142,12 @@ SIGNATURES = {
     "cae_case_importance_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "cae_case_importance": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double,
                                       C.c_double, _P, _P, _P, C.c_int64, _P]),
+    "cae_score_quantiles_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "cae_score_quantiles": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                      C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_int64, _P]),
+    "cae_score_counts": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                   C.c_int, _P, C.c_int, _P, _P, _P]),
+    "cae_interval_bounds": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int, _P, _P, _P]),
     "cae_scene_gather": (C.c_int, [C.POINTER(SceneGeomC), _P, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                    _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P]),
     "cae_scene_blend": (C.c_int, [C.POINTER(SceneGeomC), _P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64,

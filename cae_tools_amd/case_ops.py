@@ -1,6 +1,6 @@
 """The case kernels of libcae_hip (include/cae_hip.h) as functions, no engine needed: measures, per-pixel sums, spectra, SSIM,
-interpolation baseline, value distributions, skill by stratum, neighbourhood skill, permutation importance, ensemble
-verification, value range and rendered pages of channel 0 of (N, C, H, W) operands."""
+interpolation baseline, value distributions, skill by stratum, neighbourhood skill, permutation importance, prediction
+intervals, ensemble verification, value range and rendered pages of channel 0 of (N, C, H, W) operands."""
 import ctypes as C
 import math
 from contextlib import contextmanager
@@ -452,6 +452,113 @@ def case_importance(base, pert, actual, vmin, vmax, maps=None, device=None):
                                       vmin, rng, sums.data_ptr(), maps.data_ptr() if maps is not None else None, ws.data_ptr(), need,
                                       stream))
         return sums.cpu().numpy()
+
+
+def _score_operands(name, pred, actual, scale, device):
+    """(device, p, a, s or None, N, H, W) of the three interval functions: _pair, and a scale shaped like the target's cases"""
+    (device, p, a, n, h, w) = _pair(name, pred, actual, device)
+    s = device_operand(scale, device) if scale is not None else None
+    if s is not None and (len(s.shape) != 4 or s.shape[0] != n or tuple(s.shape[2:]) != (h, w)):
+        raise ValueError(f"{name}: scale {tuple(s.shape)} and target {tuple(a.shape)} do not match")
+    if n >= 1 << 31 or n * h * w > 1 << 40:
+        raise ValueError(f"{name}: fewer than 2^31 cases and at most 2^40 scores a call expected, got {n} x {h * w}")
+    return device, p, a, s, n, h, w
+
+
+def _group_code(name, group):
+    from .utils import conformal
+    try:
+        return conformal.GROUPS[group]
+    except (KeyError, TypeError):
+        raise ValueError(f"{name}: group must be one of {', '.join(conformal.GROUPS)}, got {group!r}") from None
+
+
+def score_quantiles(pred, actual, levels, group="pooled", scale=None, device=None):
+    """Exact split-conformal quantiles of the absolute residual of channel 0 (cae_score_quantiles, include/cae_hip.h): (q, n)
+    with q (L, H, W) float64 for group "pixel" or (L,) for "pooled", and n (H, W) or () int64, the valid scores of the group.
+    The score is |p - a|, or |p - a| / s with a scale s, over the cases where p and a are finite (and s finite and > 0); for
+    a level num/den the rank is k = ceil((n + 1) num / den) and q the k-th smallest score of the group, +inf where k > n.
+    levels: 1 to 8 ascending coverage levels as utils/conformal.parse_levels takes them (decimal text or Fractions, never
+    floats).  All cases go in one call: a quantile cannot be folded over pieces.  Exact, the same bits from run to run.
+    Operands as case_measures takes them."""
+    from .utils import conformal
+    try:
+        levels = conformal.parse_levels(levels)
+    except ValueError as refused:
+        raise ValueError(f"score_quantiles: {refused}") from None
+    code = _group_code("score_quantiles", group)
+    (device, p, a, s, n, h, w) = _score_operands("score_quantiles", pred, actual, scale, device)
+    (plane, n_level) = (h * w, len(levels))
+    groups = 1 if code else plane
+    if groups == 0:     # a pixel group of a plane without a pixel
+        return np.zeros((n_level, h, w), dtype=np.float64), np.zeros((h, w), dtype=np.int64)
+    q = torch.empty((n_level, groups), dtype=torch.float64, device=device)
+    count = torch.empty(groups, dtype=torch.int64, device=device)
+    lib = _lib.load()
+    (ws, need) = _workspace(device, lib.cae_score_quantiles_workspace_bytes, n, plane, code, n_level)
+    num = (C.c_int64 * n_level)(*[v.numerator for v in levels])
+    den = (C.c_int64 * n_level)(*[v.denominator for v in levels])
+    with _stream(device) as stream:
+        check(lib.cae_score_quantiles(*p.args(), *a.args(), *_args(s), n, plane, code, num, den, n_level, q.data_ptr(),
+                                      count.data_ptr(), ws.data_ptr(), need, stream))
+        (q, count) = (q.cpu().numpy(), count.cpu().numpy())
+    return (q.reshape(n_level), count.reshape(())) if code else (q.reshape(n_level, h, w), count.reshape(h, w))
+
+
+def score_counts(pred, actual, q, group, scale=None, device=None):
+    """(count, n) of cae_score_counts (include/cae_hip.h): count (L, H, W) or (L,) int64, the valid scores <= q of the group
+    per level (a score of +inf is <= +inf), and n (H, W) or () int64, the valid scores.  q: (L, H, W) for group "pixel",
+    (L,) for "pooled", float64 as score_quantiles returns it, 1 <= L <= 8.  Operands and scores as score_quantiles.
+    Held-out coverage is count.sum() / n.sum() of a level."""
+    code = _group_code("score_counts", group)
+    (device, p, a, s, n, h, w) = _score_operands("score_counts", pred, actual, scale, device)
+    plane = h * w
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    if q.ndim != (1 if code else 3) or not 1 <= q.shape[0] <= 8 or (not code and q.shape[1:] != (h, w)):
+        raise ValueError(f"score_counts: q of shape {'(L,)' if code else f'(L, {h}, {w})'} with 1 <= L <= 8 expected, got {q.shape}")
+    n_level = int(q.shape[0])
+    groups = 1 if code else plane
+    if groups == 0:
+        return np.zeros((n_level, h, w), dtype=np.int64), np.zeros((h, w), dtype=np.int64)
+    count = torch.empty((n_level, groups), dtype=torch.int64, device=device)
+    total = torch.empty(groups, dtype=torch.int64, device=device)
+    lib = _lib.load()
+    with _stream(device) as stream:
+        q_dev = torch.from_numpy(q.reshape(n_level, groups)).to(device)
+        check(lib.cae_score_counts(*p.args(), *a.args(), *_args(s), n, plane, code, q_dev.data_ptr(), n_level,
+                                   count.data_ptr(), total.data_ptr(), stream))
+        (count, total) = (count.cpu().numpy(), total.cpu().numpy())
+    return (count.reshape(n_level), total.reshape(())) if code else (count.reshape(n_level, h, w), total.reshape(h, w))
+
+
+def interval_bounds(pred, q, group, scale=None, device=None):
+    """(lower, upper) of cae_interval_bounds (include/cae_hip.h): float64 CUDA tensors (N, H, W), lower = p - q * s and upper =
+    p + q * s of channel 0 of pred with the product and the sum rounded separately (p -+ q without a scale).  q: one number
+    for group "pooled", an (H, W) array for "pixel".  NaN where p is not finite or s is not finite or <= 0; q = +inf gives
+    -inf / +inf.  Operands as score_quantiles."""
+    code = _group_code("interval_bounds", group)
+    device = _case_device(device, pred, scale)
+    p = device_operand(pred, device)
+    if len(p.shape) != 4:
+        raise ValueError(f"interval_bounds: an (N, C, H, W) prediction expected, got {tuple(p.shape)}")
+    (n, h, w) = (int(p.shape[0]), int(p.shape[2]), int(p.shape[3]))
+    s = device_operand(scale, device) if scale is not None else None
+    if s is not None and (len(s.shape) != 4 or s.shape[0] != n or tuple(s.shape[2:]) != (h, w)):
+        raise ValueError(f"interval_bounds: scale {tuple(s.shape)} and prediction {tuple(p.shape)} do not match")
+    if n >= 1 << 31 or n * h * w > 1 << 40:
+        raise ValueError(f"interval_bounds: fewer than 2^31 cases and at most 2^40 pixels a call expected, got {n} x {h * w}")
+    q = np.asarray(q, dtype=np.float64)
+    if q.shape != (() if code else (h, w)):
+        raise ValueError(f"interval_bounds: q of shape {() if code else (h, w)} expected for group {group!r}, got {q.shape}")
+    lower = torch.empty((n, h, w), dtype=torch.float64, device=device)
+    upper = torch.empty((n, h, w), dtype=torch.float64, device=device)
+    if n * h * w == 0:
+        return lower, upper
+    lib = _lib.load()
+    with _stream(device) as stream:
+        q_dev = torch.from_numpy(np.ascontiguousarray(q).reshape(-1)).to(device)
+        check(lib.cae_interval_bounds(*p.args(), *_args(s), n, h * w, q_dev.data_ptr(), code, lower.data_ptr(), upper.data_ptr(), stream))
+    return lower, upper
 
 
 def upsample(low, out_shape, mode="bicubic", device=None):

@@ -28,7 +28,30 @@ def build_parser():
     p.add_argument("--ensemble-seed", type=int, default=0, metavar="S", help="seed of the ensemble's noise")
     p.add_argument("--latent-variable", default=None, metavar="NAME",
                    help="--method var models: also store the latent mean and log-variance as NAME_mu and NAME_logvar")
+    p.add_argument("--interval", default=None, metavar="L",
+                   help="build-only: also store the prediction interval of coverage L (a level the model folder was calibrated "
+                        "for: python -m cae_tools_amd.cli.calibrate) as two more variables")
+    p.add_argument("--interval-variables", nargs=2, default=None, metavar=("LO", "HI"),
+                   help="names of the two bounds (default: <prediction-variable>_lower and _upper)")
+    p.add_argument("--scale-variable", default=None, metavar="NAME",
+                   help="with --interval: the variable the calibration divided the residual by")
     return p
+
+
+def interval_keywords(args):
+    """the apply() keywords of --interval (empty: none asked for), checked against the folder's calibration.json here, before
+    any rank is spawned or the GPU touched"""
+    if args.interval is None:
+        if args.interval_variables is not None or args.scale_variable is not None:
+            raise SystemExit("--interval-variables and --scale-variable need --interval L")
+        return {}
+    from ..utils import conformal
+    try:
+        conformal.interval_request(args.model_folder, args.interval, args.scale_variable, args.interval_variables,
+                                   args.prediction_variable)
+    except (ValueError, FileNotFoundError) as refused:
+        raise SystemExit(f"--interval: {refused}") from None
+    return {"interval": args.interval, "interval_variables": args.interval_variables, "scale_variable": args.scale_variable}
 
 
 def ensemble_keywords(args):
@@ -54,6 +77,9 @@ def ensemble_keywords(args):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     ensemble = ensemble_keywords(args)
+    ensemble.update(interval_keywords(args))
+    if "interval" in ensemble and "ensemble_size" in ensemble:
+        raise SystemExit("--interval needs the plain prediction the model was calibrated with: leave --ensemble-size out")
     from ._launch import maybe_spawn_ranks
     rc = maybe_spawn_ranks("cae_tools_amd.cli.apply_cae", args.gpus, argv)   # before anything touches the GPU
     if rc is not None:

@@ -127,31 +127,116 @@ class BaseModel:
 
     def apply(self, score_ds, input_variables, prediction_variable="model_output",
               channel_dimension="model_output_channel", y_dimension="model_output_y",
-              x_dimension="model_output_x", mask_variable_name=None, **vae_only):
+              x_dimension="model_output_x", mask_variable_name=None, interval=None, interval_variables=None,
+              scale_variable=None, **vae_only):
         """Add `prediction_variable` (float64, denormalised, dims (case, channel, y, x)) to score_ds
-        in place (:102-152)."""
+        in place (:102-152).  interval=L (build-only; DESIGN.md §9 'prediction intervals'): a coverage level the model
+        folder was calibrated for (calibrate()), as its decimal text or a Fraction; channel 0 of the prediction then gets the
+        bounds prediction -+ q (times score_ds[scale_variable] where the calibration used a scale) as two more float64
+        variables (case, y, x), named interval_variables or <prediction_variable>_lower / _upper.  Without interval nothing
+        changes, bit for bit."""
         if vae_only:    # ensemble_size / spread_variable / ensemble_seed / latent_variable: VarAEModel.apply's own keywords
             raise TypeError(f"{type(self).__name__}.apply() got {sorted(vae_only)}: only VarAEModel (the VAE, --method var) has a "
                             "stochastic latent to draw an ensemble from")
-        self.apply_device(score_ds, input_variables, prediction_variable, channel_dimension, y_dimension, x_dimension,
-                          mask_variable_name)
+        request = self._interval_request(interval, interval_variables, scale_variable, prediction_variable)
+        out = self.apply_device(score_ds, input_variables, prediction_variable, channel_dimension, y_dimension, x_dimension,
+                                mask_variable_name)
+        self._store_interval(score_ds, out, request, score_ds[input_variables[0]].dims[0], y_dimension, x_dimension)
 
     def apply_device(self, score_ds, input_variables, prediction_variable="model_output",
                      channel_dimension="model_output_channel", y_dimension="model_output_y",
                      x_dimension="model_output_x", mask_variable_name=None):
         """apply(), returning the float64 CUDA tensor whose host copy it stored (the evaluator measures it in place)"""
+        n_dimension = score_ds[input_variables[0]].dims[0]
+        out = self._predict_device(score_ds, input_variables, mask_variable_name)
+        score_ds[prediction_variable] = _make_data_array(score_ds, out.cpu().numpy(),
+                                                         (n_dimension, channel_dimension, y_dimension, x_dimension))
+        return out
+
+    def _predict_device(self, score_ds, input_variables, mask_variable_name=None):
+        """the float64 CUDA tensor apply_device stores, and nothing stored: score_ds is not changed"""
         from .. import dp as _dp
         _dp.ensure_process_group()      # a rank's GPU is selected before the data set is uploaded
-        first = score_ds[input_variables[0]]
-        n_dimension = first.dims[0]
         ds = DSDataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input,
                        mask_variable_name=mask_variable_name)
         ds.set_normalisation_parameters(self.normalisation_parameters)
         y = self._score_all(ds.device_inputs())     # cases sharded over the GPUs of a torch.distributed.run launch
-        out = ds.denormalise_device(y)   # fp64 on the device: min + y*(max-min), then one D2H copy
-        score_ds[prediction_variable] = _make_data_array(score_ds, out.cpu().numpy(),
-                                                         (n_dimension, channel_dimension, y_dimension, x_dimension))
-        return out
+        return ds.denormalise_device(y)  # fp64 on the device: min + y*(max-min), then one D2H copy
+
+    # ---- prediction intervals ----------------------------------------------------------------
+    model_folder = None     # set by load() and by calibrate(model_path=...): where apply(interval=...) finds the calibration
+
+    def _interval_request(self, interval, interval_variables, scale_variable, prediction_variable):
+        """None without interval; else utils/conformal.interval_request against the model folder's calibration, before the
+        GPU is touched"""
+        if interval is None:
+            if interval_variables is not None or scale_variable is not None:
+                raise ValueError("interval_variables and scale_variable need interval=L, a calibrated coverage level")
+            return None
+        from ..utils import conformal
+        if self.model_folder is None:
+            raise ValueError("apply(interval=...) needs the model folder that holds the calibration: load() the model from it, "
+                             "or calibrate(model_path=...) first")
+        return conformal.interval_request(self.model_folder, interval, scale_variable, interval_variables, prediction_variable)
+
+    def _store_interval(self, score_ds, out, request, n_dimension, y_dimension, x_dimension):
+        """the two bounds of channel 0 of the prediction `out` (cae_interval_bounds) into score_ds; nothing without a request"""
+        if request is None:
+            return
+        from ..case_ops import interval_bounds
+        from ..data.arrays import as_numpy
+        (record, index, names) = request
+        if record["group"] == "pixel":
+            q = record["quantile"][index]
+            if tuple(q.shape) != tuple(out.shape[2:]):
+                raise ValueError(f"the calibration holds quantiles for a {q.shape[0]} x {q.shape[1]} plane, the prediction is "
+                                 f"{int(out.shape[2])} x {int(out.shape[3])}")
+        else:
+            q = np.float64(record["pooled_quantiles"][index])
+        scale = as_numpy(score_ds[record["scale_variable"]]) if record.get("scale_variable") else None
+        bounds = interval_bounds(out, q, record["group"], scale=scale, device=out.device)
+        for (name, t) in zip(names, bounds):
+            score_ds[name] = _make_data_array(score_ds, t.cpu().numpy(), (n_dimension, y_dimension, x_dimension))
+
+    def calibrate(self, ds, input_variables, output_variable, levels, group="pooled", scale_variable=None, model_path=None,
+                  test_ds=None, mask_variable_name=None):
+        """Split conformal calibration (build-only; DESIGN.md §9 'prediction intervals'): ds is scored exactly as apply_device
+        scores it, the absolute residual |p - a| of channel 0 against ds[output_variable] as stored - divided by
+        ds[scale_variable] as stored where one is named - is ranked per pixel (group "pixel") or over all pixels ("pooled"),
+        and for every coverage level the exact order statistic of rank ceil((n + 1) level) is kept (case_ops.score_quantiles;
+        +inf where the group has too few scores).  With exchangeable cases prediction -+ q covers the target with at least
+        that probability, whatever the model.  levels: 1 to 8 ascending levels as utils/conformal.parse_levels takes them.
+        test_ds: a held-out data set whose coverage sum count / sum n is recorded (case_ops.score_counts).  model_path: the
+        model folder, which receives calibration.json (and calibration.nc for the pixel group) and nothing else.  Returns
+        the record of utils/conformal.make_record with "q" and "n" as arrays.  Collective under a torch.distributed.run
+        launch, as _score_all is; the lead rank writes."""
+        from ..case_ops import device_operand, score_counts, score_quantiles
+        from ..data.arrays import as_numpy
+        from ..utils import conformal
+        levels = conformal.parse_levels(levels)
+        conformal.check_group(group)
+
+        def operands(data):
+            pred = self._predict_device(data, input_variables, mask_variable_name)
+            device = pred.device
+            target = device_operand(as_numpy(data[output_variable]), device)
+            scale = device_operand(as_numpy(data[scale_variable]), device) if scale_variable is not None else None
+            return device_operand(pred, device), target, scale, device
+
+        (pred, target, scale, device) = operands(ds)
+        (q, n) = score_quantiles(pred, target, levels, group=group, scale=scale, device=device)
+        pooled_q = q if group == "pooled" else score_quantiles(pred, target, levels, group="pooled", scale=scale, device=device)[0]
+        coverage = None
+        if test_ds is not None:
+            (t_pred, t_target, t_scale, _) = operands(test_ds)
+            (count, total) = score_counts(t_pred, t_target, q, group, scale=t_scale, device=device)
+            coverage = ([int(c.sum()) for c in count], int(total.sum()))
+        record = conformal.make_record(group, levels, output_variable, scale_variable, int(pred.shape[0]), q, n, pooled_q, coverage)
+        if model_path:
+            if int(os.environ.get("RANK", "0")) == 0:
+                conformal.write_record(model_path, record, q=q, n=n, shape=tuple(target.shape[2:]))
+            self.model_folder = model_path
+        return dict(record, q=q, n=n)
 
     def apply_scene(self, scene_ds, input_variables, prediction_variable="model_output", overlap=None,
                     y_dimension="model_output_y", x_dimension="model_output_x", channel_dimension="model_output_channel",
@@ -462,6 +547,7 @@ class EngineModel(BaseModel):
         for fname, module in self._weight_files().items():
             module.load_state_dict(self.torch_load(os.path.join(from_folder, fname)))
         self._engine = None
+        self.model_folder = from_folder
         super().load(from_folder)
 
     # ---- training --------------------------------------------------------------------------

@@ -148,19 +148,26 @@ class VarAEModel(EngineModel):
 
     def apply(self, score_ds, input_variables, prediction_variable="model_output", channel_dimension="model_output_channel",
               y_dimension="model_output_y", x_dimension="model_output_x", mask_variable_name=None, ensemble_size=None,
-              spread_variable=None, ensemble_seed=0, latent_variable=None):
+              spread_variable=None, ensemble_seed=0, latent_variable=None, interval=None, interval_variables=None,
+              scale_variable=None):
         """BaseModel.apply, and with ensemble_size=K the model's own spread: every case is encoded once, K latents
         z_k = mu + eps_k * exp(logvar / 2) are decoded (eps_k: the noise of (ensemble_seed, draw k, global case index)), and
         `prediction_variable` receives the per-pixel mean of the K fields, `spread_variable` (K >= 2) their sample standard
         deviation (same dimensions, float64, denormalised).  latent_variable=NAME stores NAME_mu and NAME_logvar, float32
-        (case, "model_latent").  With none of the four keywords this is BaseModel.apply (z = mu), bit for bit."""
+        (case, "model_latent").  With none of the four keywords this is BaseModel.apply (z = mu), bit for bit.  interval,
+        interval_variables and scale_variable as BaseModel.apply takes them; the calibrated scores are those of z = mu, so an
+        interval is refused beside ensemble_size."""
+        if interval is not None and ensemble_size is not None:
+            raise ValueError("interval needs the plain prediction (z = mu) the model was calibrated with: leave ensemble_size out")
         if ensemble_size is not None and (int(ensemble_size) != ensemble_size or int(ensemble_size) < 1):
             raise ValueError(f"ensemble_size must be a positive integer, got {ensemble_size!r}")
         if spread_variable is not None and (ensemble_size is None or int(ensemble_size) < 2):
             raise ValueError("spread_variable needs ensemble_size >= 2: one draw has no spread")
         if ensemble_size is None and latent_variable is None:
             return super().apply(score_ds, input_variables, prediction_variable, channel_dimension, y_dimension, x_dimension,
-                                 mask_variable_name)
+                                 mask_variable_name, interval=interval, interval_variables=interval_variables,
+                                 scale_variable=scale_variable)
+        request = self._interval_request(interval, interval_variables, scale_variable, prediction_variable)
         n = int(score_ds[input_variables[0]].shape[0])
         _ve.check_noise_index(n, self.encoded_dim_size)
         dist = _dp.ensure_process_group()      # a rank's GPU is selected before the data set is uploaded
@@ -192,6 +199,7 @@ class VarAEModel(EngineModel):
             std = None if std is None else self._gather_cases(std, n, dist)
         dims = (n_dimension, channel_dimension, y_dimension, x_dimension)
         score_ds[prediction_variable] = _make_data_array(score_ds, mean.cpu().numpy(), dims)
+        self._store_interval(score_ds, mean, request, n_dimension, y_dimension, x_dimension)
         if std is not None:
             score_ds[spread_variable] = _make_data_array(score_ds, std.cpu().numpy(), dims)
         if latent_variable is not None:

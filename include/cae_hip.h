@@ -781,6 +781,56 @@ int cae_case_importance(const float* base_dev, int64_t base_case_stride, const f
                         double vmin, double range, double* sums_dev /* [n_case][8] */, double* map_dev /* NULL or [3][plane] */,
                         void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- prediction intervals (stateless): exact quantiles of the absolute residual ----------------- */
+
+/* Split conformal prediction: score a held-out calibration set, take an exact order statistic of the scores, write
+ * prediction -+ q at apply time.  Operands: channel 0 of the prediction p, the target a and, optionally, a scale s
+ * (scale_dev NULL: none), each any CAE_ELEM_* kind as stored, case i at element i * case_stride, converted to fp64 exactly.
+ * A pixel of a case counts when p and a are finite and, with a scale, s is finite and s > 0.  Its score is
+ *   e = fabs(p - a)          or          e = fabs(p - a) / s
+ * each operation a correctly rounded fp64 operation.  e is never NaN and never -0; it may be +inf, which is a valid score
+ * above every finite one.  group 0 (pixel): one group per pixel of the plane, G = plane; group 1 (pooled): one group of all
+ * scores, G = 1.  Levels: 1 to 8 exact rationals num[l] / den[l] on the host, 0 < num < den <= 10^6, strictly ascending.
+ * For a group with n valid scores the rank is k = ((n + 1) * num + den - 1) / den in int64 = ceil((n + 1) num / den); with
+ * k <= n, q is the k-th smallest score of the group (1-based, an element of the group, no interpolation), else q = +inf.
+ *   q_dev[l][G], n_dev[G]
+ * The bits of a non-negative double order as an unsigned integer: q is found by a radix select on them, most significant
+ * digit first, and after the score is formed all work is integer work.  Pixel mode: a lane owns a pixel, counts 5-bit digits
+ * into its own counters in LDS, 13 passes over the operands in one launch.  Pooled mode: 8 passes of 8-bit digits, workgroup
+ * tables in LDS merged into a 64-bit table with integer atomics, one small scan launch per pass.  No floating-point atomics:
+ * the same arguments give the same bits.  ALL cases of a group go in one call: a quantile cannot be folded over consecutive
+ * calls as the sums of the other entry points can.
+ * workspace_dev (8-byte aligned) holds cae_score_quantiles_workspace_bytes: 0 for group 0 (workspace_dev may then be NULL),
+ * 16640 for group 1.  n_case == 0 or plane == 0 succeeds with q = +inf and n = 0 for every group that exists.  A bad kind,
+ * n_case above 2^31 - 1, more than 2^40 scores, negative sizes or strides, a stride shorter than the plane, NULL or
+ * misaligned pointers, a level outside the rule or levels not ascending, too small a workspace: CAE_ERR_ARG, nothing
+ * written. */
+int64_t cae_score_quantiles_workspace_bytes(int64_t n_case, int64_t plane, int group, int n_level);
+int cae_score_quantiles(const void* pred_dev, int pred_kind, int64_t pred_case_stride, const void* actual_dev, int actual_kind,
+                        int64_t actual_case_stride, const void* scale_dev /* NULL: none */, int scale_kind,
+                        int64_t scale_case_stride, int64_t n_case, int64_t plane, int group, const int64_t* num,
+                        const int64_t* den, int n_level, double* q_dev /* [n_level][G] */, int64_t* n_dev /* [G] */,
+                        void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
+/* The inner comparison of such a pass on its own: count_dev[l][G] = the number of valid scores e <= q_dev[l][G] of the group
+ * (a score of +inf is <= +inf; no score is <= NaN), n_dev[G] = the number of valid scores.  Operands, pair rule, score and
+ * groups as cae_score_quantiles; q_dev need not come from it.  Held-out coverage is sum count / sum n.  Both outputs are
+ * written whole; one pass, no workspace, integer atomics only.  An empty call zeroes the outputs of the groups that
+ * exist.  Refusals as cae_score_quantiles. */
+int cae_score_counts(const void* pred_dev, int pred_kind, int64_t pred_case_stride, const void* actual_dev, int actual_kind,
+                     int64_t actual_case_stride, const void* scale_dev /* NULL: none */, int scale_kind, int64_t scale_case_stride,
+                     int64_t n_case, int64_t plane, int group, const double* q_dev /* [n_level][G] */, int n_level,
+                     int64_t* count_dev /* [n_level][G] */, int64_t* n_dev /* [G] */, void* hip_stream);
+
+/* The bounds of one level: lower = p - q * s and upper = p + q * s in fp64, the product and the sum rounded separately
+ * (nothing is contracted into a fused multiply-add); without a scale lower = p - q, upper = p + q.  q_dev: one number
+ * (group 1) or one per pixel of the plane (group 0).  Where p is not finite, or s is not finite or <= 0, both bounds are NaN;
+ * q = +inf with a valid s gives -inf / +inf.  lower_dev and upper_dev: [n_case][plane] doubles, written whole.  An empty call
+ * writes nothing.  Refusals as cae_score_quantiles. */
+int cae_interval_bounds(const void* pred_dev, int pred_kind, int64_t pred_case_stride, const void* scale_dev /* NULL: none */,
+                        int scale_kind, int64_t scale_case_stride, int64_t n_case, int64_t plane, const double* q_dev, int group,
+                        double* lower_dev, double* upper_dev, void* hip_stream);
+
 /* ---- scene apply (stateless): a box model applied to a whole scene ----------------------------- */
 
 /* A model maps an input box (c, h, w) to an output box (c_out, H, W) with H = h * sy, W = w * sx.  A scene variable is
