@@ -148,6 +148,9 @@ SIGNATURES = {
     "cae_score_counts": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                    C.c_int, _P, C.c_int, _P, _P, _P]),
     "cae_interval_bounds": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int, _P, _P, _P]),
+    "cae_case_neighbours_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
+    "cae_case_neighbours": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64,
+                                      C.c_int, _P, _P, _P, _P, C.c_int64, _P]),
     "cae_scene_gather": (C.c_int, [C.POINTER(SceneGeomC), _P, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                    _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P]),
     "cae_scene_blend": (C.c_int, [C.POINTER(SceneGeomC), _P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64,

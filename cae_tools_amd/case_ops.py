@@ -1,6 +1,6 @@
 """The case kernels of libcae_hip (include/cae_hip.h) as functions, no engine needed: measures, per-pixel sums, spectra, SSIM,
 interpolation baseline, value distributions, skill by stratum, neighbourhood skill, permutation importance, prediction
-intervals, ensemble verification, value range and rendered pages of channel 0 of (N, C, H, W) operands."""
+intervals, novelty against a reference set, ensemble verification, value range and rendered pages of channel 0 of (N, C, H, W) operands."""
 import ctypes as C
 import math
 from contextlib import contextmanager
@@ -559,6 +559,65 @@ def interval_bounds(pred, q, group, scale=None, device=None):
         q_dev = torch.from_numpy(np.ascontiguousarray(q).reshape(-1)).to(device)
         check(lib.cae_interval_bounds(*p.args(), *_args(s), n, h * w, q_dev.data_ptr(), code, lower.data_ptr(), upper.data_ptr(), stream))
     return lower, upper
+
+
+def _rows(name, x, device):
+    """x (numpy array or CUDA tensor of shape (n, ...)) as a contiguous float32 CUDA tensor (n, D), one row per case"""
+    if isinstance(x, torch.Tensor):
+        t = x.to(device)
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(device)
+    if t.dim() < 1:
+        raise ValueError(f"case_neighbours: {name} must have a case axis, got shape {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"case_neighbours: {name} must be float32, got {t.dtype}")
+    n = int(t.shape[0])
+    return t.reshape(n, -1).contiguous() if n else t.reshape(0, int(np.prod(t.shape[1:])))
+
+
+def case_neighbours(query, reference, k, ref_base=0, self_offset=None, merge_into=None, device=None):
+    """The k nearest references of every query row, exact in fp64 (cae_case_neighbours, include/cae_hip.h): (dist2 (n_q, k)
+    float64 ascending, index (n_q, k) int32 global reference indices ref_base + j, count (n_q,) int32).  query and reference:
+    float32 CUDA tensors or numpy arrays of shape (n, ...), flattened per case, with the same number D of features.  d2 is
+    S_d (q_d - r_d)^2 in the difference form, d ascending; a row with a value that is not finite is invalid: such a reference
+    is never a neighbour, such a query has count -1, dist2 +inf and index -1.  Candidates are ordered by (d2, index), so ties
+    go to the smaller index.  Unused slots hold +inf / -1.  self_offset i0: query i never takes the reference with global
+    index i0 + i (leave-one-out).  merge_into: the (dist2, index, count) of earlier calls with the same queries and k over
+    other references; the result is the k smallest of the union, the same bits as one call over all references."""
+    device = _case_device(device, query, reference)
+    (q, r) = (_rows("query", query, device), _rows("reference", reference, device))
+    (n_q, n_r) = (int(q.shape[0]), int(r.shape[0]))
+    dim = int(q.shape[1]) if n_q else int(r.shape[1])
+    if n_q and n_r and int(r.shape[1]) != int(q.shape[1]):
+        raise ValueError(f"case_neighbours: queries of {int(q.shape[1])} and references of {int(r.shape[1])} features do not match")
+    if int(k) != k or not 1 <= int(k) <= 32:
+        raise ValueError(f"case_neighbours: k must be an integer from 1 to 32, got {k!r}")
+    k = int(k)
+    (ref_base, self_offset) = (int(ref_base), -1 if self_offset is None else int(self_offset))
+    if ref_base < 0 or ref_base + n_r > 0x7fffffff or self_offset < -1 or n_q > 0x7fffffff:
+        raise ValueError(f"case_neighbours: ref_base {ref_base} and self_offset {self_offset} must not be negative and indices must stay below 2^31")
+    if (n_q or n_r) and dim < 1:
+        raise ValueError("case_neighbours: rows of at least one feature expected")
+    if merge_into is None:
+        dist2 = torch.full((n_q, k), math.inf, dtype=torch.float64, device=device)
+        index = torch.full((n_q, k), -1, dtype=torch.int32, device=device)
+        count = torch.zeros(n_q, dtype=torch.int32, device=device)
+    else:
+        (d0, i0, c0) = merge_into
+        if np.shape(d0) != (n_q, k) or np.shape(i0) != (n_q, k) or np.shape(c0) != (n_q,):
+            raise ValueError(f"case_neighbours: merge_into must hold arrays of shape ({n_q}, {k}), ({n_q}, {k}) and ({n_q},)")
+        dist2 = torch.from_numpy(np.ascontiguousarray(d0, dtype=np.float64)).to(device)
+        index = torch.from_numpy(np.ascontiguousarray(i0, dtype=np.int32)).to(device)
+        count = torch.from_numpy(np.ascontiguousarray(c0, dtype=np.int32)).to(device)
+    if n_q == 0:
+        return np.zeros((0, k), dtype=np.float64), np.zeros((0, k), dtype=np.int32), np.zeros(0, dtype=np.int32)
+    lib = _lib.load()
+    (ws, need) = _workspace(device, lib.cae_case_neighbours_workspace_bytes, n_q, n_r, k)
+    with _stream(device) as stream:
+        check(lib.cae_case_neighbours(q.data_ptr(), n_q, dim, r.data_ptr() if n_r else None, n_r, dim, dim, k, ref_base, self_offset,
+                                      0 if merge_into is None else 1, dist2.data_ptr(), index.data_ptr(), count.data_ptr(),
+                                      ws.data_ptr(), need, stream))
+        return dist2.cpu().numpy(), index.cpu().numpy(), count.cpu().numpy()
 
 
 def upsample(low, out_shape, mode="bicubic", device=None):

@@ -35,7 +35,48 @@ def build_parser():
                    help="names of the two bounds (default: <prediction-variable>_lower and _upper)")
     p.add_argument("--scale-variable", default=None, metavar="NAME",
                    help="with --interval: the variable the calibration divided the residual by")
+    p.add_argument("--novelty-variable", default=None, metavar="NAME",
+                   help="build-only: also store the novelty of every scored case against --novelty-reference under NAME")
+    p.add_argument("--novelty-reference", nargs="+", default=None, metavar="F",
+                   help="with --novelty-variable: the file(s) of the reference set, usually the training data")
+    p.add_argument("--novelty-k", type=int, default=None, metavar="K",
+                   help="with --novelty-variable: the novelty is the distance to the K-th nearest reference case, 1 to 32 (default 5)")
     return p
+
+
+def novelty_keywords(args):
+    """the BaseModel.apply_novelty keywords of --novelty-variable (empty: none asked for), checked here, before any rank is
+    spawned or the GPU touched"""
+    if args.novelty_variable is None and args.novelty_reference is None:
+        if args.novelty_k is not None:
+            raise SystemExit("--novelty-k needs --novelty-variable NAME and --novelty-reference F ...")
+        return {}
+    if args.novelty_variable is None or args.novelty_reference is None:
+        raise SystemExit("--novelty-variable and --novelty-reference need each other")
+    from ..utils import novelty
+    try:
+        k = novelty.check_k(5 if args.novelty_k is None else args.novelty_k)
+    except ValueError as refused:
+        raise SystemExit(f"--novelty-k: {refused}") from None
+    if args.novelty_variable == args.prediction_variable:
+        raise SystemExit("--novelty-variable must differ from --prediction-variable")
+    missing = [path for path in args.novelty_reference if not os.path.exists(path)]
+    if missing:
+        raise SystemExit(f"--novelty-reference: {', '.join(missing)} not found")
+    return {"novelty_variable": args.novelty_variable, "k": k}
+
+
+def _open_cases(paths, names):
+    """the files concatenated along the case dimension, a per-case variable among `names` broadcast to a (case, 1, y, x) field"""
+    ds = open_mfdataset(paths, concat_dim="box", combine="nested")
+    case_dimension = ds[names[0]].dims[0]
+    for var in names:
+        if tuple(ds[var].dims) == (case_dimension,):
+            (y_dim, x_dim) = (ds.dims["y"], ds.dims["x"])
+            vals = np.asarray(ds[var].values)
+            ds[var] = DataArray(np.broadcast_to(vals[:, None, None, None], (vals.shape[0], 1, y_dim, x_dim)).copy(),
+                                dims=(case_dimension, "channel", "y", "x"))
+    return ds, case_dimension
 
 
 def interval_keywords(args):
@@ -78,6 +119,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     ensemble = ensemble_keywords(args)
     ensemble.update(interval_keywords(args))
+    novelty = novelty_keywords(args)
     if "interval" in ensemble and "ensemble_size" in ensemble:
         raise SystemExit("--interval needs the plain prediction the model was calibrated with: leave --ensemble-size out")
     from ._launch import maybe_spawn_ranks
@@ -100,16 +142,12 @@ def main(argv=None):
         raise Exception(f"input_variables [{','.join(input_variable_names)}] inconsistent with those used to train "
                         f"the model [{','.join(model_names)}]")
 
-    score_ds = open_mfdataset(args.data_paths, concat_dim="box", combine="nested")
-    case_dimension = score_ds[input_variable_names[0]].dims[0]
-    for var in (model_names or input_variable_names):
-        if tuple(score_ds[var].dims) == (case_dimension,):
-            (y_dim, x_dim) = (score_ds.dims["y"], score_ds.dims["x"])
-            vals = np.asarray(score_ds[var].values)
-            score_ds[var] = DataArray(np.broadcast_to(vals[:, None, None, None], (vals.shape[0], 1, y_dim, x_dim)).copy(),
-                                      dims=(case_dimension, "channel", "y", "x"))
+    (score_ds, case_dimension) = _open_cases(args.data_paths, model_names or input_variable_names)
     print("Applying model for %d cases" % score_ds[case_dimension].shape[0])
     mt.apply(score_ds, input_variable_names, args.prediction_variable, mask_variable_name=args.mask_variable, **ensemble)
+    if novelty:
+        (reference_ds, _) = _open_cases(args.novelty_reference, model_names or input_variable_names)
+        mt.apply_novelty(score_ds, reference_ds, input_variable_names, **novelty)
     if int(os.environ.get("RANK", "0")) == 0:       # every rank holds all predictions (all-gather); rank 0 writes
         score_ds.to_netcdf(args.output_path)
 

@@ -25,6 +25,7 @@
 #include "kernels_fss.h"         // likewise, after kernels_strata.h
 #include "kernels_importance.h"  // likewise, after kernels_fss.h
 #include "kernels_quantile.h"    // likewise, after kernels_importance.h
+#include "kernels_neighbours.h"  // likewise, after kernels_quantile.h
 #include "kernels_s2.h"
 #include "kernels_last.h"
 #include "kernels_rows.h"

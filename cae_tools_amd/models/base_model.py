@@ -22,6 +22,7 @@ from .model_sizer import ModelSpec, create_model_spec
 
 
 _IMPORTANCE_BYTES = 256 << 20       # of fp32 inputs and scores per piece of cases of importance()
+_NOVELTY_BYTES = 1 << 30            # of packed reference rows per cae_case_neighbours call of novelty()
 
 
 def _make_data_array(like_ds, data, dims):
@@ -340,6 +341,50 @@ class BaseModel:
                         (c_off, raw) = offsets[name]
                         xb[:, c_off:c_off + int(raw.shape[1])] = x[c0:c1, c_off:c_off + int(raw.shape[1])]
         return _imp.summary(groups, sums, seed=seed, maps=fields.cpu().numpy() if maps else None)
+
+    def _packed_inputs(self, ds, input_variables):
+        """the packed, normalised inputs of ds as _predict_device packs them: a float32 CUDA tensor (n, C, h, w)"""
+        data = DSDataset(ds, list(input_variables), input_variables[0], normalise_in=self.normalise_input)
+        data.set_normalisation_parameters(self.normalisation_parameters)
+        return data.device_inputs()
+
+    def novelty(self, ds, reference_ds, input_variables, k=5, same=False, reference_chunk=None):
+        """Novelty of the cases of ds against a reference set, usually the training set (build-only; DESIGN.md §9 'novelty'):
+        both sets are packed with the model's normalisation exactly as _predict_device packs them, and every case of ds gets
+        its k nearest reference cases in that space, exact in fp64 (case_ops.case_neighbours).  The references go through in
+        pieces of reference_chunk cases (None: a byte budget), merged; the result does not depend on the cut.  same=True:
+        reference_ds is ignored and ds is searched against itself, leave-one-out.  Returns a dict: "novelty" (n,) float64 =
+        sqrt(dist2[:, k - 1] / D), the rms difference per feature to the k-th nearest reference (+inf with fewer than k valid
+        references, NaN for a case with a value that is not finite), "nearest" likewise for dist2[:, 0], "nearest_case" (n,)
+        int32, "index" / "dist2" (n, k), "count" (n,), "features" D, "k", "reference_cases" and "valid_reference_cases".  Uses
+        the packing alone, never the forward pass; under a torch.distributed.run launch every rank computes the same."""
+        from .. import dp as _dp
+        from ..case_ops import case_neighbours
+        from ..utils import novelty as _nov
+        _dp.ensure_process_group()
+        k = _nov.check_k(k)
+        x = self._packed_inputs(ds, input_variables)
+        ref = x if same else self._packed_inputs(reference_ds, input_variables)
+        if tuple(ref.shape[1:]) != tuple(x.shape[1:]):
+            raise ValueError(f"novelty: cases of shape {tuple(x.shape[1:])} and reference cases of shape {tuple(ref.shape[1:])} do not match")
+        (n, n_ref, dim) = (int(x.shape[0]), int(ref.shape[0]), int(np.prod(x.shape[1:])))
+        chunk = max(1, _NOVELTY_BYTES // (4 * max(dim, 1))) if reference_chunk is None else int(reference_chunk)
+        if chunk < 1:
+            raise ValueError(f"novelty: reference_chunk must be at least 1, got {reference_chunk!r}")
+        result = None
+        for r0 in range(0, max(n_ref, 1), chunk):
+            result = case_neighbours(x, ref[r0:r0 + chunk], k, ref_base=r0, self_offset=0 if same else None, merge_into=result,
+                                     device=x.device)
+        # a row's validity as the kernel finds it: count -1 marks an invalid query, also against no reference at all
+        valid_ref = int((case_neighbours(ref, ref[:0], 1, device=x.device)[2] >= 0).sum()) if n_ref else 0
+        return _nov.case_record(*result, dim, n_ref, valid_ref)
+
+    def apply_novelty(self, score_ds, reference_ds, input_variables, novelty_variable, k=5):
+        """Add `novelty_variable` (float64, one value per case) to score_ds in place: novelty()'s "novelty" of every scored
+        case against reference_ds.  Returns novelty()'s record."""
+        found = self.novelty(score_ds, reference_ds, input_variables, k=k)
+        score_ds[novelty_variable] = _make_data_array(score_ds, found["novelty"], (score_ds[input_variables[0]].dims[0],))
+        return found
 
     def dump_metrics(self, title, metrics):
         print("\n" + title)

@@ -1,6 +1,6 @@
 """The optional outputs of ModelEvaluator.build_html, none of them a reference feature: ensemble verification, case pages,
 structural similarity, skill against interpolation, per-pixel skill maps, power spectra, value distributions, skill by
-stratum, neighbourhood skill and input importance.
+stratum, neighbourhood skill, input importance and novelty of the cases.
 
 Each is one Analysis of functions over the evaluator `ev`:
     enabled(ev)                                     whether its option is on
@@ -25,6 +25,7 @@ from ..utils import distribution as distribution_curves
 from ..utils import ensemble_scores, skill_maps
 from ..utils import fss as fss_scores
 from ..utils import importance as importance_scores
+from ..utils import novelty as novelty_scores
 from ..utils import spectra as spectra_curves
 from ..utils import ssim as ssim_scores
 from ..utils import strata as strata_scores
@@ -431,6 +432,46 @@ def _importance(ev, parts, report):
     report["importance"] = (found, link)
 
 
+# ---- novelty of the cases --------------------------------------------------------------------
+
+def check_novelty(ev):
+    if not ev.novelty:
+        return
+    novelty_scores.check_k(ev.novelty_k)
+    if not ev.novelty_reference and not ev.training_paths:
+        raise ValueError("novelty needs a reference set: the training files, or novelty_reference, the files of the reference set")
+
+
+def _novelty_reference(ev):
+    """(the reference data set, the record of that set searched against itself, leave-one-out): the train partition, or the
+    files of novelty_reference.  Computed once per build_html and kept beside the operands, which are dropped with them."""
+    key = ("novelty", "reference")
+    found = ev._operands.get(key)
+    if found is None:
+        ds = ev._open(list(ev.novelty_reference)) if ev.novelty_reference else dict(ev._run[1])["train"]
+        found = (ds, ev.model.novelty(ds, None, ev.model_input_variables, k=int(ev.novelty_k), same=True))
+        ev._operands[key] = found
+    return found
+
+
+def _novelty(ev, partition, ds, values, report):
+    """novelty=True (cli/novelty.py) asks whether a case is anything like what the model was trained on: every case of the
+    partition, packed and normalised as the model sees it, gets its novelty_k nearest cases of the reference set - the train
+    partition, or the files of novelty_reference - on the GPU, exact in fp64 (BaseModel.novelty: cae_case_neighbours;
+    utils/novelty.py).  The train partition against itself is leave-one-out, and that pass also gives
+    the reference's own distribution of novelty, so it runs once.  novelty_<partition>.json holds the min, median and max
+    of the novelty, the reference's 50th, 90th, 95th and 99th order statistics, the shares of the cases above the 95th and
+    99th, Spearman's rank correlation of novelty with the mse, the mse and mae per novelty quintile, the ten most novel cases
+    and the per-case values; the data set gets per-case novelty and nearest_case variables beside mae / mse, the report the
+    "Novelty of the cases" section."""
+    (ref_ds, loo) = _novelty_reference(ev)
+    own = partition == "train" and not ev.novelty_reference
+    case = loo if own else ev.model.novelty(ds, ref_ds, ev.model_input_variables, k=int(ev.novelty_k))
+    record = novelty_scores.summary(case, reference=loo, mse=values["mse"], mae=values["mae"])
+    _keep(ev, novelty_scores, "novelty", partition, record, report.setdefault("novelty", []))
+    return {"novelty": case["novelty"], "nearest_case": case["nearest_case"]}
+
+
 ENSEMBLE = Analysis(lambda ev: ev.ensemble_size is not None, check_ensemble, partition=_ensemble)
 CASE_PAGES = Analysis(lambda ev: ev.x_coordinate and ev.y_coordinate and ev.time_coordinate, partition=_case_pages)
 SSIM = Analysis(lambda ev: ev.ssim, partition=_ssim)
@@ -440,7 +481,8 @@ SPECTRA = Analysis(lambda ev: ev.spectra, after=_spectra)
 DISTRIBUTION = Analysis(lambda ev: ev.distribution, check_distribution, after=_distribution)
 STRATA = Analysis(lambda ev: ev.strata, check_strata, after=_strata)
 FSS = Analysis(lambda ev: ev.fss, check_fss, after=_fss)
-# in the order build_html runs them: per partition ensemble, case pages, ssim, baseline; then skill maps, spectra, distribution,
-# strata, fss, importance
+# in the order build_html runs them: per partition ensemble, case pages, ssim, baseline, novelty; then skill maps, spectra,
+# distribution, strata, fss, importance
 IMPORTANCE = Analysis(lambda ev: ev.importance, check_importance, after=_importance)
-ANALYSES = (ENSEMBLE, CASE_PAGES, SSIM, BASELINE, SKILL_MAPS, SPECTRA, DISTRIBUTION, STRATA, FSS, IMPORTANCE)
+NOVELTY = Analysis(lambda ev: ev.novelty, check_novelty, partition=_novelty)
+ANALYSES = (ENSEMBLE, CASE_PAGES, SSIM, BASELINE, NOVELTY, SKILL_MAPS, SPECTRA, DISTRIBUTION, STRATA, FSS, IMPORTANCE)

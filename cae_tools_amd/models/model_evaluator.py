@@ -18,7 +18,7 @@ index is 0 for NaN and 1 + round-half-up(254 * clamp((v - lo) / (hi - lo), 0, 1)
 (cae_render_cases) from the slabs as stored and from the prediction where it still lies in HBM.
 
 The optional analyses that are no reference feature - ensemble verification, structural similarity, skill against
-interpolation, per-pixel skill maps, power spectra, value distributions, skill by stratum, neighbourhood skill and input importance - are the units of
+interpolation, per-pixel skill maps, power spectra, value distributions, skill by stratum, neighbourhood skill, input importance and novelty of the cases - are the units of
 evaluation_analyses.py, which build_html runs in their fixed order.  What they and the case pages read on the GPU comes
 from one operand cache (operand): a partition's variable is uploaded once per build_html, whatever is switched on.
 """
@@ -48,7 +48,8 @@ class ModelEvaluator:
                  baseline=False, baseline_variable=None, baseline_mode="bicubic", distribution=False, distribution_bins=128,
                  strata=False, strata_variable=None, strata_channel=0, strata_edges=None, strata_classes=None, strata_count=8,
                  fss=False, fss_thresholds=None, fss_percentiles=None, fss_widths=None, fss_gaps="strict",
-                 importance=False, importance_repeats=5, importance_seed=0, importance_groups=None, importance_maps=False):
+                 importance=False, importance_repeats=5, importance_seed=0, importance_groups=None, importance_maps=False,
+                 novelty=False, novelty_k=5, novelty_reference=None):
         self.training_paths = list(training_paths) if training_paths else []
         self.testing_paths = list(testing_paths) if testing_paths else []
         self.output_html_folder = output_html_folder
@@ -74,8 +75,11 @@ class ModelEvaluator:
         (self.fss_widths, self.fss_gaps) = (fss_widths, fss_gaps)
         (self.importance, self.importance_repeats, self.importance_seed) = (importance, importance_repeats, importance_seed)
         (self.importance_groups, self.importance_maps) = (importance_groups, importance_maps)
+        (self.novelty, self.novelty_k) = (novelty, novelty_k)
+        self.novelty_reference = list(novelty_reference) if novelty_reference else None
         for unit in (analyses.BASELINE, analyses.DISTRIBUTION, analyses.ENSEMBLE,       # the refusals come in this order,
-                     analyses.STRATA, analyses.FSS, analyses.IMPORTANCE):               # all before the model is loaded
+                     analyses.STRATA, analyses.FSS, analyses.IMPORTANCE,                # all before the model is loaded
+                     analyses.NOVELTY):
             unit.check(self)
         self.model = load_model(self.model_path)
         analyses.check_ensemble_model(self)

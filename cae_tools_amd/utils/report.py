@@ -222,7 +222,7 @@ def _section(body, title, records, heading, rows, plots=None):
 
 def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None, ensemble=None,
                       spectra_link=None, ssim=None, baseline=None, distribution=None, strata=None, fss=None,
-                      importance=None):
+                      importance=None, novelty=None):
     """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
     metrics: {"test": {...}, "train": {...}} (either may be absent); measures: [(partition, {"mae": values, "mse": values})]
     in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}; maps_link: href of
@@ -241,7 +241,8 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
     the table of the pooled Fractions Skill Score per threshold and width, the uniform level and the skilful width, and the
     link; importance: ([(partition, record)] of utils/importance.summary, href of the page of per-pixel maps or None): an
     "Input importance" section with the table of the groups of input variables by rank, the bar chart of importance +- sd,
-    and the link where there is one."""
+    and the link where there is one; novelty: [(partition, record)] of utils/novelty.summary: a "Novelty of the cases"
+    section with the table of the scores and quintiles and the bar chart of the mse per novelty quintile."""
     doc = Document("Model Evaluation")
     doc.head.add("style").text(STYLE)
     body = doc.body
@@ -310,6 +311,10 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
                  {"input importance": lambda rec: importance_scores.svg_bars(rec, "importance +- sd")})
         if link:
             body.add("p").add("a", {"href": link}).text("Change of the mse per pixel by group of input variables")
+    if novelty:
+        from . import novelty as novelty_scores
+        _section(body, "Novelty of the cases", novelty, novelty_scores.heading, novelty_scores.section_rows,
+                 {"mse by novelty quintile": lambda rec: novelty_scores.svg_quintiles(rec, "mse by novelty quintile")})
     if parameters or history:
         body.add("h2").text("Training Summary")
     if parameters:

@@ -831,6 +831,38 @@ int cae_interval_bounds(const void* pred_dev, int pred_kind, int64_t pred_case_s
                         int scale_kind, int64_t scale_case_stride, int64_t n_case, int64_t plane, const double* q_dev, int group,
                         double* lower_dev, double* upper_dev, void* hip_stream);
 
+/* ---- novelty (stateless): K nearest neighbours between two sets of rows, exact in fp64 ---------- */
+
+/* Operands: queries Q (n_query rows) and references R (n_ref rows) of dim fp32 values each, row i at element i * stride,
+ * stride >= dim; the pointers need 4-byte alignment only.  A row is valid when all its dim values are finite; validity is
+ * found once per row and call.  The distance is the difference form
+ *   d2(i, j) = S_d ((double)q[i][d] - (double)r[j][d])^2
+ * with exact conversions, one correctly rounded fp64 subtraction and one fused multiply-add per d, d ascending from +0.0.
+ * Identical rows give exactly +0.0, d2 is finite for valid rows and never -0.0, and its bits depend on the two rows and dim
+ * alone: not on n_query, n_ref, k, the strides, the rows' places in the call, alignment or merge.
+ * Candidates of a query are the valid references, ordered by (d2, ref_base + j) ascending - a total order; the bits of a
+ * non-negative double order as an unsigned integer.  With self_offset >= 0 query i never takes the reference whose global
+ * index ref_base + j equals self_offset + i (leave-one-out, also when a set is searched against itself in pieces);
+ * self_offset -1: no exclusion.  Per query the k smallest candidates:
+ *   dist2_dev[n_query][k] ascending, index_dev[n_query][k] global indices, unused slots +inf / -1,
+ *   count_dev[n_query] in 0 .. k; an invalid query has count -1, every dist2 +inf and every index -1.
+ * merge 1: the three outputs hold the result of earlier calls with the same queries and k over references with other
+ * global indices, and the call leaves the k smallest of the union: the reference set cut into consecutive calls, in any
+ * order, gives the bits of one call.
+ * A workgroup owns a tile of 64 queries and walks a run of tiles of 64 references with 4 x 4 pairs per lane in registers;
+ * the reference axis is split over workgroups, whose partial lists a small second launch folds.  No atomics.
+ * workspace_dev (8-byte aligned) holds cae_case_neighbours_workspace_bytes (0 for n_query < 1, n_ref < 0 or k outside
+ * 1 .. 32).  n_query == 0 succeeds and writes nothing; n_ref == 0 succeeds with empty lists, or under merge with the
+ * lists left as they are.  k outside 1 .. 32, negative counts, dim < 1 while rows exist, a stride shorter than dim,
+ * n_query or ref_base + n_ref above 2^31 - 1, ref_base < 0, self_offset < -1, merge other than 0 or 1, NULL outputs,
+ * NULL operands with rows to read, an operand reaching 2^60 elements from its pointer, misaligned pointers, too small or
+ * misaligned a workspace: CAE_ERR_ARG, nothing written. */
+int64_t cae_case_neighbours_workspace_bytes(int64_t n_query, int64_t n_ref, int k);
+int cae_case_neighbours(const float* query_dev, int64_t n_query, int64_t query_stride, const float* ref_dev, int64_t n_ref,
+                        int64_t ref_stride, int64_t dim, int k, int64_t ref_base, int64_t self_offset, int merge,
+                        double* dist2_dev /* [n_query][k] */, int32_t* index_dev /* [n_query][k] */,
+                        int32_t* count_dev /* [n_query] */, void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 /* ---- scene apply (stateless): a box model applied to a whole scene ----------------------------- */
 
 /* A model maps an input box (c, h, w) to an output box (c_out, H, W) with H = h * sy, W = w * sx.  A scene variable is
