@@ -14,9 +14,10 @@
 //   k_baseline_fold        the partials of a case added in (band, strip) order by one lane per (case, sum)
 // No floating-point atomics; the cut into bands and strips depends on (h_out, w_out) alone.  Nothing is contracted into a
 // fused multiply-add: the coordinates src, i and t are the host restatement's bits (tests/baseline_ref.py).
-// Uses the element conversions of kernels_stateless.h (cm_word) and the helpers of kernels_ssim.h (ss_raw, ss_value,
-// ss_finite, ss_wave_sum), so it is included after them.
+// Uses the element conversions of case_elem.h (cm_word) and the helpers of kernels_ssim.h (ss_raw, ss_value,
+// ss_finite, ss_wave_sum), so it is included after that.
 #pragma once
+#include "case_elem.h"
 
 namespace cae {
 

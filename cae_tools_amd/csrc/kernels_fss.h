@@ -20,8 +20,9 @@
 //                       and added to the zeroed output with 64-bit integer atomics: exact in any order, so the cut into
 //                       items never shows.
 // No floating-point arithmetic after the compares of k_fss_bits, no LDS.
-// Uses cm_load1 of kernels_stateless.h and ss_finite of kernels_ssim.h, so it is included after them.
+// Uses cm_load1 of case_elem.h and ss_finite of kernels_ssim.h, so it is included after that.
 #pragma once
+#include "case_elem.h"
 
 namespace cae {
 

@@ -22,9 +22,10 @@
 // No floating-point atomics.  The cut into workgroups and waves depends on (n_case, plane) alone and the order of a wave's
 // rounds on the data alone, so the same arguments give the same bits from run to run.  Nothing is contracted into a fused
 // multiply-add: the bin of a value is the host restatement's (tests/distribution_ref.py).
-// Uses the element loads of kernels_stateless.h (cm_load1, cm_load4), ss_finite of kernels_ssim.h and wave_sum_lane63 of
+// Uses the element loads of case_elem.h (cm_load1, cm_load4), ss_finite of kernels_ssim.h and wave_sum_lane63 of
 // device_common.h, so it is included after them.
 #pragma once
+#include "case_elem.h"
 
 namespace cae {
 

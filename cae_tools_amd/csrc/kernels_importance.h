@@ -19,7 +19,7 @@
 // IM_RUN cases), so that a call without a map covers the device however few pixels a case has.  No LDS, no atomics; every
 // subtraction, product and sum is rounded on its own, nothing is contracted into a fused multiply-add.
 #pragma once
-#include "kernels_stateless.h"
+#include "case_elem.h"
 
 namespace cae {
 

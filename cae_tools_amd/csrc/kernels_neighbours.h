@@ -24,7 +24,7 @@
 // k_quantile_fill is, so that they are emitted where stateless_host.h instantiates them, at the end of the code object, and no
 // kernel of the training step moves.
 #pragma once
-#include "kernels_stateless.h"
+#include "device_common.h"
 
 namespace cae {
 

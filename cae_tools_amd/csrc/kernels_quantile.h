@@ -18,7 +18,6 @@
 // k_interval_bounds: p -+ q * s, the product and the sum rounded separately.
 // Integer atomics only, no scratch; the same arguments give the same bits.
 #pragma once
-#include "kernels_stateless.h"
 #include "kernels_importance.h"     // im_wave_sum_lane63
 
 namespace cae {

@@ -2,9 +2,10 @@
 // to a whole scene.  The scene (n_t, c, Y, X) is cut into overlapping h x w boxes whose origins along an axis are
 // min(k * stride, extent - box): every tile is a full box and the last one is shifted inward.  k_scene_gather cuts and
 // normalises the boxes of one variable into the packed batch the model scores; k_scene_blend folds the scored boxes back
-// into the float64 scene.  Both are pure traffic and neither touches an engine.  Included after kernels_stateless.h (the
-// element loads).
+// into the float64 scene.  Both are pure traffic and neither touches an engine.  Uses the element loads of
+// case_elem.h.
 #pragma once
+#include "case_elem.h"
 #include "device_common.h"
 
 namespace cae {

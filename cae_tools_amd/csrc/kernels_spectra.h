@@ -3,8 +3,9 @@
 // a direct two-dimensional DFT in fp64 - two small matrix products per band of kx columns, plain fp64 FMAs - and the four
 // products w|P|^2, w|A|^2, w Re(P conj A), w|D|^2 of every mode are added into the radial bin the caller's table names.
 // No floating-point atomics anywhere: a bin of a (case, band) is summed by one lane in a fixed order, the bands of a case
-// by the fold in band order.  Uses the element loads of kernels_stateless.h (cm_word), so it is included after it.
+// by the fold in band order.  Uses the element loads of case_elem.h (cm_load1).
 #pragma once
+#include "case_elem.h"
 
 namespace cae {
 

@@ -12,8 +12,9 @@
 // row (w) first, then along the column (h); taps in ascending order, each an fma onto a sum that starts at 0; the second
 // moments filter the rounded products x x, y y, x y.  Everything else is rounded operation by operation (no contraction):
 // with p bit-identical to a the three second moments are then the same bits, cs and ssim are exactly 1.
-// Uses the element conversions of kernels_stateless.h (cm_word), so it is included after it.
+// Uses the element conversions of case_elem.h (cm_word).
 #pragma once
+#include "case_elem.h"
 
 #include <utility>
 

@@ -1,8 +1,8 @@
-// kernels_stateless.h — the kernels behind the stateless entry points of include/cae_hip.h (at the end of engine.hip's
-// extern "C" block): the loader
+// kernels_stateless.h — the kernels behind the stateless entry points of include/cae_hip.h (stateless_host.h): the loader
 // (scan, normalise + pack, permutation inverse, denormalise, metric sums, byte swap), the evaluator's per-case measures, the
 // ensemble moments, the ensemble verification, the case pages and the per-pixel skill sums.  None of them touches an engine.
 #pragma once
+#include "case_elem.h"
 #include "device_common.h"
 
 namespace cae {
@@ -126,53 +126,8 @@ __global__ void __launch_bounds__(256) k_bswap32(unsigned* __restrict__ x, long 
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) x[(n4 << 2) + threadIdx.x] = __builtin_bswap32(x[(n4 << 2) + threadIdx.x]);
 }
 
-// ---- per-case error sums (model_evaluator.py:87-95): S|p - a| and S(p - a)^2 in fp64 over a case's first `plane` elements.
-// Element kinds of include/cae_hip.h (CAE_ELEM_*): 0 fp32, 1 fp32 big-endian, 2 fp64, 3 fp64 big-endian.  A big-endian
-// slab is the NetCDF-3 file's bytes copied to HBM as they are; the swap happens in registers.
-template <int K> struct CmElem;
-template <> struct CmElem<0> { static constexpr int bytes = 4; };
-template <> struct CmElem<1> { static constexpr int bytes = 4; };
-template <> struct CmElem<2> { static constexpr int bytes = 8; };
-template <> struct CmElem<3> { static constexpr int bytes = 8; };
-
-template <int K>
-__device__ __forceinline__ double cm_word(unsigned long long w) {
-    if constexpr (K == 0) return (double)__uint_as_float((unsigned)w);
-    else if constexpr (K == 1) return (double)__uint_as_float(__builtin_bswap32((unsigned)w));
-    else if constexpr (K == 2) return __longlong_as_double((long long)w);
-    else return __longlong_as_double((long long)__builtin_bswap64(w));
-}
-
-// element e of a case (element-aligned pointer)
-template <int K>
-__device__ __forceinline__ double cm_load1(const unsigned char* c, long long e) {
-    if constexpr (CmElem<K>::bytes == 4) return cm_word<K>(reinterpret_cast<const unsigned*>(c)[e]);
-    else return cm_word<K>(reinterpret_cast<const unsigned long long*>(c)[e]);
-}
-
-// elements e .. e+3: 16-byte loads when `vec` (the caller checked the alignment), else four scalar loads
-template <int K>
-__device__ __forceinline__ void cm_load4(const unsigned char* c, long long e, bool vec, double v[4]) {
-    if (vec) {
-        if constexpr (CmElem<K>::bytes == 4) {
-            const uint4 w = *reinterpret_cast<const uint4*>(c + e * 4);
-            v[0] = cm_word<K>(w.x);
-            v[1] = cm_word<K>(w.y);
-            v[2] = cm_word<K>(w.z);
-            v[3] = cm_word<K>(w.w);
-        } else {
-            const ulonglong2 w0 = *reinterpret_cast<const ulonglong2*>(c + e * 8);
-            const ulonglong2 w1 = *reinterpret_cast<const ulonglong2*>(c + e * 8 + 16);
-            v[0] = cm_word<K>(w0.x);
-            v[1] = cm_word<K>(w0.y);
-            v[2] = cm_word<K>(w1.x);
-            v[3] = cm_word<K>(w1.y);
-        }
-    } else {
-        for (int j = 0; j < 4; j++) v[j] = cm_load1<K>(c, e + j);
-    }
-}
-
+// ---- per-case error sums (model_evaluator.py:87-95): S|p - a| and S(p - a)^2 in fp64 over a case's first `plane` elements,
+// read with the element loads of case_elem.h.
 __device__ __forceinline__ void cm_acc(double p, double a, double& s1, double& s2) {
     const double d = p - a;     // fp64: numpy's promotion of the float64 prediction against the target
     s1 += fabs(d);

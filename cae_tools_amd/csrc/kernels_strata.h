@@ -22,9 +22,10 @@
 // No floating-point atomics.  The cut into workgroups and waves depends on (n_case, h, w) alone and the order of a wave's
 // rounds on the data alone, so the same arguments give the same bits from run to run.  Nothing is contracted into a fused
 // multiply-add: every addend is the host restatement's (tests/strata_ref.py).
-// Uses cm_load1 of kernels_stateless.h, ss_raw, ss_value and ss_finite of kernels_ssim.h, bl_axis of kernels_baseline.h and
+// Uses cm_load1 of case_elem.h, ss_raw, ss_value and ss_finite of kernels_ssim.h, bl_axis of kernels_baseline.h and
 // wave_sum_lane63 of device_common.h, so it is included after them.
 #pragma once
+#include "case_elem.h"
 
 namespace cae {
 
