@@ -1,5 +1,6 @@
 // case_elem.h - the element loads of the case kernels: an operand is channel 0 of the cases in one of the element kinds of
-// include/cae_hip.h.  Included by kernels_stateless.h where they have always stood, and by the kernel headers that use them.
+// include/cae_hip.h, and the denormalisation of a score that those kernels share (cm_denorm).  Included by
+// kernels_stateless.h where they have always stood, and by the kernel headers that use them.
 #pragma once
 #include "device_common.h"
 
@@ -49,6 +50,15 @@ __device__ __forceinline__ void cm_load4(const unsigned char* c, long long e, bo
     } else {
         for (int j = 0; j < 4; j++) v[j] = cm_load1<K>(c, e + j);
     }
+}
+
+// The denormalised score of ds_dataset.py:131-135, vmin + (y * range) in two rounded fp64 operations as numpy forms it.
+// Plain operators under the pragma: the bodies of __dadd_rn and __dmul_rn are a plain + and * that the compiler contracts
+// into one v_fma_f64 wherever they are inlined, which changes the last bit unless y * range happens to be exact.
+__device__ __forceinline__ double cm_denorm(double vmin, double y, double range) {
+#pragma clang fp contract(off)
+    const double prod = y * range;
+    return vmin + prod;
 }
 
 }  // namespace cae

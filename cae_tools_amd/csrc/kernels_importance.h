@@ -78,8 +78,8 @@ template <bool MAP>
 __device__ __forceinline__ void im_case(const ImArgs& s, bool inside, bool live, float yb, float yp, double av, long long cs,
                                         long long tile, int lane, double m[3]) {
 #pragma clang fp contract(off)
-    const double p0 = __dadd_rn(s.vmin, __dmul_rn((double)yb, s.range));
-    const double p1 = __dadd_rn(s.vmin, __dmul_rn((double)yp, s.range));
+    const double p0 = cm_denorm(s.vmin, (double)yb, s.range);
+    const double p1 = cm_denorm(s.vmin, (double)yp, s.range);
     const bool pair = inside && im_finite(av) && im_finite(p0) && im_finite(p1);
     double q1 = 0.0, q0 = 0.0, a1 = 0.0, a0 = 0.0, dd = 0.0;
     int cnt = 0;

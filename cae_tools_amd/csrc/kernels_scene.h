@@ -156,7 +156,7 @@ __device__ __forceinline__ unsigned sb_rows(const SbArgs& a, int tt, int c, int 
 #pragma unroll
     for (int j = 0; j < R; j++) {
         const bool hole = den[j] == 0;
-        const double v = __dadd_rn(a.vmin, __dmul_rn(__ddiv_rn(num[j], (double)(hole ? 1 : den[j])), a.range));
+        const double v = cm_denorm(a.vmin, __ddiv_rn(num[j], (double)(hole ? 1 : den[j])), a.range);
         holes += hole ? 1u : 0u;
         o[(long long)j * a.Xs] = hole ? __longlong_as_double(0x7ff8000000000000LL) : v;
     }

@@ -79,7 +79,7 @@ __global__ void __launch_bounds__(256) k_invert_perm(const int* __restrict__ per
 __global__ void __launch_bounds__(256) k_denorm_f64(const float* __restrict__ y, long long n, double vmin, double range,
                                                      double* __restrict__ out) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-        out[i] = __dadd_rn(vmin, __dmul_rn((double)y[i], range));
+        out[i] = cm_denorm(vmin, (double)y[i], range);
 }
 
 // model_metric.py:47-71 per instance: sums[inst][8] += {n, Σa', Σe', Σa'², Σe'², Σa'e', Σ|a-e|, Σ(a-e)²} over the
@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(256) k_metric_sums(const float* __restrict__ y
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < elems; i += (long long)gridDim.x * 256) {
         if (mask && mask[base + i] == 0.f) continue;
-        const double e = __dadd_rn(vmin, __dmul_rn((double)y[base + i], range));
+        const double e = cm_denorm(vmin, (double)y[base + i], range);
         const double av = (double)a[base + i];
         const double d = av - e, as = av - vmin, es = e - vmin;
         acc[0] += 1.0;

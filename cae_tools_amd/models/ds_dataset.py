@@ -3,7 +3,8 @@
 Public surface and semantics follow src/cae_tools/models/ds_dataset.py:
   __init__ :22-75    NaN check of every variable (ValueError with the reference's messages), global
                      min / max per input variable and of the output as python floats
-  normalisation :78-113,131-135   (x - min) / (max - min); 0.0 when an input's range is 0
+  normalisation :78-113,131-135   (x - min) / (max - min); 0.0 when a variable's range is 0 - the output's too, where the
+                     reference divides 0 by 0 ("The loader and metric-sum kernels")
   __getitem__ :137-159           (input (C,H,W) f32, output, mask of ones shaped like the input, label)
 The scans run in cae_scan_f32 and the normalise + channel-concat in cae_normalise_pack
 (include/cae_hip.h) on device copies of the variables; nothing is computed with numpy here.
