@@ -155,6 +155,13 @@ SIGNATURES = {
                                    _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P]),
     "cae_scene_blend": (C.c_int, [C.POINTER(SceneGeomC), _P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int64,
                                   C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_double, _P, C.c_int64, _P, _P]),
+    "cae_residual_scan_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "cae_residual_scan": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                    _P, C.c_int64, _P, C.POINTER(C.c_double)]),
+    "cae_residual_pack_rows": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                         C.c_double, C.c_double, C.c_int, _P, _P, _P]),
+    "cae_residual_restore_f64": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64,
+                                           C.c_int, C.c_double, C.c_double, C.c_int, _P, _P]),
     # ---- include/cae_unet.h ----
     "unet_engine_create": (C.c_int, [C.POINTER(LayerSpecC), C.c_int, C.POINTER(LayerSpecC), C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.POINTER(C.c_void_p)]),

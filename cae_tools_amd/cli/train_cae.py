@@ -4,7 +4,9 @@
 source is missing there - this build's own definition, PARITY UNPINNED) and linear (LinearModel) are
 implemented; the other method names are accepted by the parser, as in the reference, and rejected with a clear message
 (the reference itself constructs no model for vae/unet_res/srcnn_res/resunet_gan: SURVEY.md fact 3).
-Build-only flags: --gpus N (data-parallel ConvAE training over N GPUs of this node, one process per GPU) and --local-bn.
+Build-only flags: --gpus N (data-parallel ConvAE training over N GPUs of this node, one process per GPU) and --local-bn;
+--residual-variable NAME / --residual-mode MODE train any of the four on the residual over the interpolated input
+(DESIGN.md §9 'Residual target': the idea behind the reference's unet_res / srcnn_res names).
 """
 import argparse
 import json
@@ -15,6 +17,7 @@ import numpy as np
 
 from ..data.arrays import DataArray, open_mfdataset
 from ..lr_schedule import check_scheduler_type
+from ..utils.baseline import MODES as RESIDUAL_MODES
 from ..models.conv_ae_model import ConvAEModel
 from ..models.unet import UNET
 from ..models.linear_model import LinearModel
@@ -69,6 +72,36 @@ def build_parser():
     return p
 
 
+def build_cli_parser():
+    """build_parser() - the reference's flag table and the data-parallel flags - with the residual-target flags the command
+    line takes on top (build-only; DESIGN.md §9 'Residual target')"""
+    p = build_parser()
+    p.add_argument("--residual-variable", type=str, default=None, metavar="NAME",
+                   help="train on the output minus this low-resolution variable interpolated to the output grid, and add it back "
+                        "when the model is applied (default with --residual-mode alone: the first input variable)")
+    p.add_argument("--residual-mode", choices=list(RESIDUAL_MODES), default=None,
+                   help="interpolation of the residual variable (default: bicubic)")
+    return p
+
+
+def residual_settings(args, folder_parameters=None):
+    """(variable, mode) the run trains its residual target with, (None, "bicubic") without one.  folder_parameters: the
+    parameters.json of the folder --continue-training continues; its settings hold, and a flag that contradicts them ends
+    the run."""
+    asked = args.residual_variable is not None or args.residual_mode is not None
+    variable = (args.residual_variable or args.input_variables[0]) if asked else None
+    mode = args.residual_mode or "bicubic"
+    if folder_parameters is None:
+        return variable, mode
+    held = (folder_parameters.get("residual_variable"), folder_parameters.get("residual_mode") or "bicubic")
+    if asked and ((args.residual_variable is not None and args.residual_variable != held[0]) or
+                  (args.residual_mode is not None and args.residual_mode != held[1]) or held[0] is None):
+        was = f"the residual over '{held[0]}' ({held[1]})" if held[0] is not None else "no residual target"
+        raise SystemExit(f"--continue-training: the model folder was trained with {was}; --residual-variable / --residual-mode "
+                         "cannot change that")
+    return held
+
+
 def broadcast_case_variables(ds, variables, case_dimension):
     """a (case,) variable becomes (case, 1, y, x) by broadcasting (cli/train_cae.py:73-109)"""
     for var in variables:
@@ -81,12 +114,18 @@ def broadcast_case_variables(ds, variables, case_dimension):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_cli_parser().parse_args(argv)
     try:    # a misspelt scheduler ends the run here, before ranks are spawned and the GPU library is loaded
         check_scheduler_type(args.scheduler_type)
     except ValueError as ex:
         raise SystemExit(f"--scheduler-type: {ex}")
     schedule = dict(scheduler_type=args.scheduler_type, lr_step_size=args.lr_step_size, lr_gamma=args.lr_gamma)
+    folder_parameters = None
+    if args.continue_training:      # the folder's residual settings hold: a contradicting flag ends the run here
+        with open(os.path.join(args.model_folder, "parameters.json")) as f:
+            folder_parameters = json.loads(f.read())
+    (residual_variable, residual_mode) = residual_settings(args, folder_parameters)
+    residual = dict(residual_variable=residual_variable, residual_mode=residual_mode)
     from ._launch import maybe_spawn_ranks
     from .. import dp as _dp
     if max(int(args.gpus or 1), _dp.env_world()[2]) > 1:
@@ -123,19 +162,19 @@ def main(argv=None):
     else:
         if args.method == "conv":
             mt = ConvAEModel(fc_size=args.fc_size, encoded_dim_size=args.latent_size, nr_epochs=args.nr_epochs,
-                             batch_size=args.batch_size, lr=args.learning_rate, **schedule)
+                             batch_size=args.batch_size, lr=args.learning_rate, **schedule, **residual)
         elif args.method == "unet":     # cli/train_cae.py:131-135
             mt = UNET(fc_size=args.fc_size, encoded_dim_size=args.latent_size, nr_epochs=args.nr_epochs,
                       batch_size=args.batch_size, lr=args.learning_rate, lambda_l1=args.lambda_l1,
                       lambda_pearson=args.lambda_pearson, database_path=args.database_path,
-                      weight_decay=args.weight_decay, dropout_rate=args.dropout_rate, **schedule)
+                      weight_decay=args.weight_decay, dropout_rate=args.dropout_rate, **schedule, **residual)
         elif args.method == "var":      # the reference's default method; its model source is missing there
             mt = VarAEModel(fc_size=args.fc_size, encoded_dim_size=args.latent_size, nr_epochs=args.nr_epochs,
                             batch_size=args.batch_size, lr=args.learning_rate, lambda_mse=args.lambda_mse,
                             lambda_kl=args.lambda_kl, lambda_ssim=args.lambda_ssim, weight_decay=args.weight_decay,
-                            database_path=args.database_path, **schedule)
+                            database_path=args.database_path, **schedule, **residual)
         elif args.method == "linear":   # cli/train_cae.py:137-138
-            mt = LinearModel(batch_size=args.batch_size, nr_epochs=args.nr_epochs, lr=args.learning_rate, **schedule)
+            mt = LinearModel(batch_size=args.batch_size, nr_epochs=args.nr_epochs, lr=args.learning_rate, **schedule, **residual)
         else:
             raise SystemExit(f"--method {args.method}: cae_tools_amd implements 'conv' (ConvAEModel), 'unet' (UNET), 'var' "
                              "(VarAEModel) and 'linear' (LinearModel)")

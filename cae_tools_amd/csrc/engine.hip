@@ -878,6 +878,7 @@ int cae_profile_end(cae_engine* e, cae_profile_rec* out, int capacity) {
 }  // extern "C"
 
 #include "kernels_scene.h"   // the scene kernels, after every kernel of the step: those keep their places in the code object
+#include "kernels_residual.h"   // likewise: its fold is no template and is emitted here
 #include "stateless_host.h"
 
 // =================================================================================================

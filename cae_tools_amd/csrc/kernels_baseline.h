@@ -12,6 +12,7 @@
 //                          requested before the first is used.  {n, S|b-a|, S(b-a)^2, S|p-a|, S(p-a)^2, n_won} of the
 //                          wave are stored plainly as the partial of its (case, band, strip)
 //   k_baseline_fold        the partials of a case added in (band, strip) order by one lane per (case, sum)
+// The walk itself - taps, ring, vertical pass - is BlWalk<MODE>, which the residual kernels (kernels_residual.h) share.
 // No floating-point atomics; the cut into bands and strips depends on (h_out, w_out) alone.  Nothing is contracted into a
 // fused multiply-add: the coordinates src, i and t are the host restatement's bits (tests/baseline_ref.py).
 // Uses the element conversions of case_elem.h (cm_word) and the helpers of kernels_ssim.h (ss_raw, ss_value,
@@ -128,12 +129,64 @@ __device__ __forceinline__ double bl_row(const unsigned char* lc, int lk, long l
     return r;
 }
 
+// The ring walk of a lane's column down a band of at most BL_ROWS output rows: the column's horizontal taps, the vertical
+// taps of the band's row l in lane l, and the ring of horizontally interpolated low-resolution rows.  k_case_baseline and
+// the residual kernels (kernels_residual.h) walk with it, so that both form the same bits of b.
+template <int MODE>
+struct BlWalk {
+    static constexpr int T = BlMode<MODE>::taps;
+    const unsigned char* lc;                // the case's low-resolution plane
+    int lk, w_in;
+    int ix[T], iyl[T];
+    double wx[T], wyl[T];
+    int basel, cur;                         // floor(src_y) of the lane's row; the one the ring holds
+    double ring[T];                         // slot j: r(x) of the j-th vertical tap's row
+    bool ring_bad[T];
+
+    // column oxc; lane l takes the vertical taps of output row min(y0 + l, h_out - 1); the ring is filled for row y0
+    __device__ __forceinline__ void start(const unsigned char* plane, int kind, int oxc, int y0, int lane, int h_in, int w_in_,
+                                          int h_out, double sy, double sx) {
+        lc = plane, lk = kind, w_in = w_in_;
+        bl_axis<MODE>(oxc, sx, w_in, ix, wx);
+        basel = (int)bl_axis<MODE>(min(y0 + lane, h_out - 1), sy, h_in, iyl, wyl);
+        cur = bl_lane(basel, 0);
+#pragma unroll
+        for (int j = 0; j < T; j++) ring[j] = bl_row<T>(lc, lk, bl_lane(iyl[j], 0), w_in, ix, wx, ring_bad[j]);
+    }
+
+    // b of the band's row r (the same in every lane; the rows are asked for in ascending order): S_j wy_j r_j, every product
+    // and sum rounded; bad: a tap that is not finite, whatever its weight
+    __device__ __forceinline__ double row(int r, bool& bad) {
+#pragma clang fp contract(off)
+        const int base = bl_lane(basel, r);
+        if (base != cur) {
+            if (T > 1 && base == cur + 1) {             // one row on: slot j + 1's row is slot j's now
+#pragma unroll
+                for (int j = 0; j + 1 < T; j++) ring[j] = ring[j + 1], ring_bad[j] = ring_bad[j + 1];
+                ring[T - 1] = bl_row<T>(lc, lk, bl_lane(iyl[T - 1], r), w_in, ix, wx, ring_bad[T - 1]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < T; j++) ring[j] = bl_row<T>(lc, lk, bl_lane(iyl[j], r), w_in, ix, wx, ring_bad[j]);
+            }
+            cur = base;
+        }
+        double b = 0.0;
+        bad = false;
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            const double q = bl_lane(wyl[j], r) * ring[j];
+            b = j == 0 ? q : b + q;
+            bad = bad || ring_bad[j];
+        }
+        return b;
+    }
+};
+
 // One wave per item = (case, band, strip); four items per workgroup, no barrier, no LDS.  EA, EP: bytes of an element of a
 // and of p (without a prediction p is a again, read and not used).
 template <int MODE, int EA, int EP>
 __global__ void __launch_bounds__(256) k_case_baseline(const BlArgs a) {
 #pragma clang fp contract(off)
-    constexpr int T = BlMode<MODE>::taps;
     const int lane = threadIdx.x & 63;
     const long long item = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (item >= a.items) return;
@@ -153,20 +206,9 @@ __global__ void __launch_bounds__(256) k_case_baseline(const BlArgs a) {
     const unsigned char* pc = has_p ? a.p + c * a.p_stride * EP : ac;
     double* fc = a.field ? a.field + c * ((long long)a.h_out * W) : nullptr;
 
-    int ix[T];
-    double wx[T];
-    bl_axis<MODE>(oxc, a.sx, a.w_in, ix, wx);
-
     // the vertical taps of the band's rows, row y0 + l in lane l: computed once, handed to the wave row by row
-    int iyl[T];
-    double wyl[T];
-    const int basel = (int)bl_axis<MODE>(min(y0 + lane, a.h_out - 1), a.sy, a.h_in, iyl, wyl);
-
-    double ring[T];                         // slot j: r(x) of the j-th vertical tap's row
-    bool ring_bad[T];
-    int cur = bl_lane(basel, 0);            // the floor(src_y) the ring holds
-#pragma unroll
-    for (int j = 0; j < T; j++) ring[j] = bl_row<T>(lc, lk, bl_lane(iyl[j], 0), a.w_in, ix, wx, ring_bad[j]);
+    BlWalk<MODE> walk;
+    walk.start(lc, lk, oxc, y0, lane, a.h_in, a.w_in, a.h_out, a.sy, a.sx);
     double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
     int cnt = 0, won = 0;
 
@@ -182,27 +224,8 @@ __global__ void __launch_bounds__(256) k_case_baseline(const BlArgs a) {
         for (int d = 0; d < BL_AHEAD; d++) {
             const int oy = yb + d;
             if (oy < y1) {                  // the same in every lane
-                const int r = oy - y0;
-                const int base = bl_lane(basel, r);
-                if (base != cur) {
-                    if (T > 1 && base == cur + 1) {             // one row on: slot j + 1's row is slot j's now
-#pragma unroll
-                        for (int j = 0; j + 1 < T; j++) ring[j] = ring[j + 1], ring_bad[j] = ring_bad[j + 1];
-                        ring[T - 1] = bl_row<T>(lc, lk, bl_lane(iyl[T - 1], r), a.w_in, ix, wx, ring_bad[T - 1]);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < T; j++) ring[j] = bl_row<T>(lc, lk, bl_lane(iyl[j], r), a.w_in, ix, wx, ring_bad[j]);
-                    }
-                    cur = base;
-                }
-                double b = 0.0;
-                bool bad = false;
-#pragma unroll
-                for (int j = 0; j < T; j++) {
-                    const double q = bl_lane(wyl[j], r) * ring[j];
-                    b = j == 0 ? q : b + q;
-                    bad = bad || ring_bad[j];
-                }
+                bool bad;
+                const double b = walk.row(oy - y0, bad);
                 const double av = bl_value<EA>(aq[d], a_be);
                 const double pv = has_p ? bl_value<EP>(pq[d], p_be) : 0.0;
                 if (col_ok) {

@@ -1,5 +1,5 @@
 """The loader's kernels of libcae_hip (include/cae_hip.h) as functions on torch CUDA tensors, no engine needed: scan,
-normalise and pack, permutation, denormalise, metric sums, upload."""
+normalise and pack, permutation, denormalise, the residual target (scan, pack, restore), metric sums, upload."""
 import ctypes as C
 
 import numpy as np
@@ -61,6 +61,69 @@ def denormalise_f64(y, vmin, vmax):
     out = torch.empty(y.shape, dtype=torch.float64, device=y.device)
     check(lib.cae_denormalise_f64(y.data_ptr(), y.numel(), float(vmin), float(vmax) - float(vmin), out.data_ptr(),
                                   torch.cuda.current_stream(y.device).cuda_stream))
+    return out
+
+
+def _residual_operands(name, low, other, mode):
+    """(lib, low as a case operand, the fp32 tensor `other` contiguous, N, h, w, H, W, mode code) of a residual_* call:
+    low (N, C, h, w) in any form case_ops.device_operand takes, other a float32 CUDA tensor (N, 1, H, W) or (N, H, W)"""
+    from .case_ops import device_operand
+    from .utils.baseline import MODES
+    if mode not in MODES:
+        raise ValueError(f"{name}: mode must be one of {', '.join(MODES)}, got {mode!r}")
+    if not (isinstance(other, torch.Tensor) and other.is_cuda and other.dtype == torch.float32 and other.dim() in (3, 4)):
+        raise CaeError(f"{name}: a float32 CUDA tensor (N, 1, H, W) expected beside the low-resolution variable")
+    if other.dim() == 4 and int(other.shape[1]) != 1:
+        raise ValueError(f"{name}: the residual is defined for an output of one channel, got {int(other.shape[1])}")
+    lo = device_operand(low, other.device)
+    if len(lo.shape) != 4 or int(lo.shape[0]) != int(other.shape[0]):
+        raise ValueError(f"{name}: (N, C, h, w) beside (N, 1, H, W) expected, got {tuple(lo.shape)} and {tuple(other.shape)}")
+    (h_in, w_in, h, w) = (int(lo.shape[2]), int(lo.shape[3]), int(other.shape[-2]), int(other.shape[-1]))
+    if min(h_in, w_in, h, w) < 1:
+        raise ValueError(f"{name}: planes of at least one pixel expected, got {h_in} x {w_in} and {h} x {w}")
+    return _lib.load(), lo, other.contiguous(), int(other.shape[0]), h_in, w_in, h, w, MODES[mode]
+
+
+def residual_scan(low, target, mode="bicubic"):
+    """(k, rmin, rmax) of r = double(target) - b as python numbers (cae_residual_scan, include/cae_hip.h): b is channel 0 of
+    low interpolated to the target's grid, the field of case_ops.upsample, formed in registers; k counts the r that are not
+    finite, rmin and rmax are the exact fp64 minimum and maximum of the others (+inf, -inf without one)."""
+    (lib, lo, t, n, h_in, w_in, h, w, code) = _residual_operands("residual_scan", low, target, mode)
+    out = (C.c_double * 3)()
+    need = int(lib.cae_residual_scan_workspace_bytes(n, h, w))
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=t.device)
+    with torch.cuda.device(t.device):
+        check(lib.cae_residual_scan(*lo.args(), h_in, w_in, t.data_ptr(), n, h, w, code, ws.data_ptr(), need,
+                                    torch.cuda.current_stream(t.device).cuda_stream, out))
+    return int(out[0]), float(out[1]), float(out[2])
+
+
+def residual_pack(low, target, dst, rmin, rmax, mode="bicubic", enable=True, dst_rows=None):
+    """dst[row(i)] = float32((r - rmin) / (rmax - rmin)) on the device (cae_residual_pack_rows): the residual target a
+    model trains on, 0 at span 0, float32(r) when not enabled, NaN where r is not finite.  dst: a contiguous float32 CUDA
+    tensor shaped like target; dst_rows as normalise_pack takes it.  The span is formed in fp64 from python floats."""
+    (lib, lo, t, n, h_in, w_in, h, w, code) = _residual_operands("residual_pack", low, target, mode)
+    if dst.dtype != torch.float32 or dst.device != t.device or tuple(dst.shape) != tuple(target.shape) or not dst.is_contiguous():
+        raise CaeError("residual_pack: dst must be a contiguous float32 tensor shaped like the target on its device")
+    if dst_rows is not None:
+        if dst_rows.dtype != torch.int32 or dst_rows.device != t.device or dst_rows.numel() != n:
+            raise CaeError("residual_pack: dst_rows must be an int32 tensor of one entry per sample on the data's device")
+    with torch.cuda.device(t.device):      # (no case: a defined no-op of the entry point)
+        check(lib.cae_residual_pack_rows(*lo.args(), h_in, w_in, t.data_ptr(), n, h, w, code, float(rmin),
+                                         float(rmax) - float(rmin), 1 if enable else 0,
+                                         dst_rows.data_ptr() if dst_rows is not None else None, dst.data_ptr(),
+                                         torch.cuda.current_stream(t.device).cuda_stream))
+
+
+def residual_restore(low, y, rmin, rmax, mode="bicubic", enable=True):
+    """float64 CUDA tensor b + (rmin + double(y) * (rmax - rmin)), shaped like the scores y (cae_residual_restore_f64): the
+    prediction of a residual model, b + double(y) when not enabled, NaN where b or y is."""
+    (lib, lo, yc, n, h_in, w_in, h, w, code) = _residual_operands("residual_restore", low, y, mode)
+    out = torch.empty(yc.shape, dtype=torch.float64, device=yc.device)
+    with torch.cuda.device(yc.device):
+        check(lib.cae_residual_restore_f64(*lo.args(), h_in, w_in, yc.data_ptr(), n, h, w, code, float(rmin),
+                                           float(rmax) - float(rmin), 1 if enable else 0, out.data_ptr(),
+                                           torch.cuda.current_stream(yc.device).cuda_stream))
     return out
 
 

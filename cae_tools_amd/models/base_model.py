@@ -41,6 +41,12 @@ def _index_batches(n, batch_size):
     return torch.cat([b for b in loader]).to(torch.int32).numpy()
 
 
+def residual_refusal(path, variable):
+    """the one message of the paths that do not serve a residual model yet"""
+    return (f"{path}: this model predicts the residual over the interpolated variable '{variable}', and {path} denormalises "
+            "its scores without adding the interpolation back; use apply() for a residual model")
+
+
 def _mean_loss(losses, column=None):
     """a pass's loss: the mean over its batches of the engine's per-batch loss (entry `column` where that is a tuple)"""
     return float(np.mean(losses if column is None else [l[column] for l in losses]))
@@ -80,6 +86,60 @@ class BaseModel:
     def torch_load(self, from_path):
         return torch.load(from_path, map_location=torch.device("cpu"), weights_only=True)
 
+    # ---- residual target (build-only; DESIGN.md §9 'Residual target') ---------------------------
+    # residual_variable: the low-resolution variable whose channel 0, interpolated to the output grid (residual_mode), the
+    # model's target is taken over: it trains on target - b and apply() adds b back.  None: the target is the output itself.
+    # residual_min / residual_max: the training set's range of target - b, beside normalisation_parameters.
+    residual_variable = None
+    residual_mode = "bicubic"
+    residual_min = residual_max = None
+
+    def _init_residual(self, residual_variable=None, residual_mode="bicubic"):
+        """the two residual keywords of a model constructor (an unknown mode is an error here, before any GPU work)"""
+        from ..utils.baseline import MODES
+        if residual_mode not in MODES:
+            raise ValueError(f"residual_mode must be one of {', '.join(MODES)}, got {residual_mode!r}")
+        self.residual_variable = residual_variable
+        self.residual_mode = residual_mode
+        self.residual_min = self.residual_max = None
+
+    def _residual_parameters(self):
+        """what get_parameters() adds: nothing without a residual target (parameters.json is then what it always was)"""
+        if self.residual_variable is None:
+            return {}
+        return {"residual_variable": self.residual_variable, "residual_mode": self.residual_mode,
+                "residual_min": self.residual_min, "residual_max": self.residual_max}
+
+    def _refuse_residual(self, path):
+        """the paths that denormalise on their own do not add the interpolation back yet: one refusal, before the GPU is
+        touched"""
+        if self.residual_variable is not None:
+            raise NotImplementedError(residual_refusal(path, self.residual_variable))
+
+    def _model_dataset(self, ds, input_variables, output_variable, fit=False, **keywords):
+        """Every DSDataset built for this model.  fit=True (the training set): its scans become the model's normalisation and
+        residual range; otherwise the model's are applied to it.  A data set without the residual variable is refused before
+        the GPU is touched."""
+        residual = None
+        if self.residual_variable is not None:
+            if self.residual_variable not in ds:
+                raise ValueError(f"this model predicts the residual over the interpolated variable '{self.residual_variable}', "
+                                 f"which the data set does not hold")
+            residual = (self.residual_variable, self.residual_mode)
+            if not fit:
+                residual += ((self.residual_min, self.residual_max),)
+            data = DSDataset(ds, input_variables, output_variable, residual=residual, **keywords)
+            data.residual_normalise = bool(self.normalise_output)      # whatever normalise_out the caller asks the truth with
+        else:
+            data = DSDataset(ds, input_variables, output_variable, **keywords)
+        if fit:
+            self.normalisation_parameters = data.get_normalisation_parameters()
+            if residual is not None:
+                (self.residual_min, self.residual_max) = data.get_residual_parameters()
+        else:
+            data.set_normalisation_parameters(self.normalisation_parameters)
+        return data
+
     # ---- scoring helpers -------------------------------------------------------------------
     def _score_device(self, x):
         """eval-mode forward of an (N,C,H,W) fp32 CUDA tensor; implemented by the sub-class"""
@@ -116,9 +176,17 @@ class BaseModel:
         """score every case, denormalise, and pool the reference's metrics (:69-100).  Scores, truth and mask
         stay on the GPU; cae_metric_sums reduces each case to eight fp64 sums.  The mask is all ones unless the
         dataset carries a mask variable shaped like the output (the reference builds the default mask with the
-        INPUT's shape, which cannot index the output; the intended all-pixels mask is used - SURVEY.md headline 3)."""
+        INPUT's shape, which cannot index the output; the intended all-pixels mask is used - SURVEY.md headline 3).
+        With a residual target the scores are restored (the interpolation added back), rounded to fp32 and reduced against
+        the target as stored with (vmin, vmax) = (0, 1): the metrics are those of the prediction, not of the residual."""
         from .. import dp as _dp
         _dp.select_device()
+        if getattr(dataset, "residual", None) is not None:
+            scores = self._score_all(dataset.device_inputs())
+            restored = dataset.denormalise_device(scores).to(torch.float32)
+            mm = DeviceModelMetric()
+            mm.accumulate(dataset.device_target(), restored, dataset.device_mask(), 0.0, 1.0)
+            return mm.get_metrics()
         dataset.set_normalise_output(False)
         truth = dataset.device_outputs()
         scores = self._score_all(dataset.device_inputs())
@@ -158,11 +226,11 @@ class BaseModel:
         """the float64 CUDA tensor apply_device stores, and nothing stored: score_ds is not changed"""
         from .. import dp as _dp
         _dp.ensure_process_group()      # a rank's GPU is selected before the data set is uploaded
-        ds = DSDataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input,
-                       mask_variable_name=mask_variable_name)
-        ds.set_normalisation_parameters(self.normalisation_parameters)
+        ds = self._model_dataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input,
+                                 mask_variable_name=mask_variable_name)
         y = self._score_all(ds.device_inputs())     # cases sharded over the GPUs of a torch.distributed.run launch
-        return ds.denormalise_device(y)  # fp64 on the device: min + y*(max-min), then one D2H copy
+        # fp64 on the device: min + y*(max-min), or the restored residual b + (rmin + y*(rmax-rmin)); then one D2H copy
+        return ds.denormalise_device(y)
 
     # ---- prediction intervals ----------------------------------------------------------------
     model_folder = None     # set by load() and by calibrate(model_path=...): where apply(interval=...) finds the calibration
@@ -253,6 +321,7 @@ class BaseModel:
         from .. import dp as _dp
         from .. import scene as _scene
         from ..data.arrays import as_numpy
+        self._refuse_residual("apply_scene")
         _dp.ensure_process_group()
         (in_shape, out_shape) = (tuple(self.input_shape), tuple(self.output_shape))
         shaped = [as_numpy(scene_ds[name]) for name in input_variables]
@@ -293,12 +362,12 @@ class BaseModel:
         from ..case_ops import case_importance, device_operand, operand_cases, pack_gather
         from ..data.arrays import as_numpy
         from ..utils import importance as _imp
+        self._refuse_residual("importance")
         _dp.ensure_process_group()
         names = list(input_variables)
         groups = _imp.check_groups(groups, names)
         repeats = _imp.check_repeats(repeats)
-        data = DSDataset(ds, names, output_variable, normalise_in=self.normalise_input, normalise_out=False)
-        data.set_normalisation_parameters(self.normalisation_parameters)
+        data = self._model_dataset(ds, names, output_variable, normalise_in=self.normalise_input, normalise_out=False)
         n = len(data)
         if n < 2:
             raise ValueError(f"importance: at least 2 cases expected, got {n}")
@@ -344,9 +413,7 @@ class BaseModel:
 
     def _packed_inputs(self, ds, input_variables):
         """the packed, normalised inputs of ds as _predict_device packs them: a float32 CUDA tensor (n, C, h, w)"""
-        data = DSDataset(ds, list(input_variables), input_variables[0], normalise_in=self.normalise_input)
-        data.set_normalisation_parameters(self.normalisation_parameters)
-        return data.device_inputs()
+        return self._model_dataset(ds, list(input_variables), input_variables[0], normalise_in=self.normalise_input).device_inputs()
 
     def novelty(self, ds, reference_ds, input_variables, k=5, same=False, reference_chunk=None):
         """Novelty of the cases of ds against a reference set, usually the training set (build-only; DESIGN.md §9 'novelty'):
@@ -461,7 +528,8 @@ class EngineModel(BaseModel):
 
     MODEL_TYPE = None
     PARAM_KEYS = ()
-    OPTIONAL_PARAM_KEYS = ("conv_kernel_size", "conv_stride", "conv_input_layer_count", "conv_output_layer_count")
+    RESIDUAL_KEYS = ("residual_variable", "residual_mode", "residual_min", "residual_max")     # absent: no residual target
+    OPTIONAL_PARAM_KEYS = ("conv_kernel_size", "conv_stride", "conv_input_layer_count", "conv_output_layer_count") + RESIDUAL_KEYS
     SCHEDULE_KEYS = ("scheduler_type", "lr_step_size", "lr_gamma")     # in parameters.json only when a scheduler is set
 
     # ---- where train() differs between the model classes --------------------------------------
@@ -583,6 +651,8 @@ class EngineModel(BaseModel):
             setattr(self, key, p[key])
         for key in self.OPTIONAL_PARAM_KEYS:
             setattr(self, key, p.get(key, None))
+        if self.residual_mode is None:      # a folder from before the residual target, or without one
+            self.residual_mode = "bicubic"
         for key in self.SCHEDULE_KEYS:
             if key in p:
                 setattr(self, key, p[key])
@@ -616,15 +686,13 @@ class EngineModel(BaseModel):
         """both data sets (normalisation from the training set), specs, shapes, the model, and the frozen shuffles drawn
         in the reference's order (training loader first): (train_ds, test_ds, train_perm, test_perm)"""
         self._progress("initiating train method")
-        train_ds = DSDataset(training_ds, input_variables, output_variable, normalise_in=self.normalise_input,
-                             normalise_out=self.normalise_output, mask_variable_name=mask_variable_name)
+        train_ds = self._model_dataset(training_ds, input_variables, output_variable, fit=True, normalise_in=self.normalise_input,
+                                       normalise_out=self.normalise_output, mask_variable_name=mask_variable_name)
         self._progress("loaded train_ds to train method")
-        self.normalisation_parameters = train_ds.get_normalisation_parameters()
         self.set_input_spec(train_ds.get_input_spec())
         self.set_output_spec(train_ds.get_output_spec())
-        test_ds = DSDataset(testing_ds, input_variables, output_variable, normalise_in=self.normalise_input,
-                            normalise_out=self.normalise_output, mask_variable_name=mask_variable_name)
-        test_ds.set_normalisation_parameters(self.normalisation_parameters)
+        test_ds = self._model_dataset(testing_ds, input_variables, output_variable, normalise_in=self.normalise_input,
+                                      normalise_out=self.normalise_output, mask_variable_name=mask_variable_name)
         self.input_shape = tuple(train_ds.get_input_shape())
         self.output_shape = tuple(train_ds.get_output_shape())
         self._progress("finished loading train_ds and test_ds from DSDataset")

@@ -8,6 +8,11 @@ Public surface and semantics follow src/cae_tools/models/ds_dataset.py:
   __getitem__ :137-159           (input (C,H,W) f32, output, mask of ones shaped like the input, label)
 The scans run in cae_scan_f32 and the normalise + channel-concat in cae_normalise_pack
 (include/cae_hip.h) on device copies of the variables; nothing is computed with numpy here.
+
+Build-only: residual=(variable, mode) makes the target the residual over the interpolated input (DESIGN.md section 9,
+"Residual target"): device_outputs / device_batches pack (r - rmin) / (rmax - rmin) with r = target - upsample(variable) and
+denormalise_device adds the interpolation back (cae_residual_scan / _pack_rows / _restore_f64).  With residual=None every
+path is the one it always was.
 """
 import numpy as np
 import torch
@@ -26,7 +31,7 @@ def _device():
 class DSDataset(torch.utils.data.Dataset):
 
     def __init__(self, ds, input_variable_names, output_variable_name=None, normalise_in=True, normalise_out=True,
-                 mask_variable_name=None):
+                 mask_variable_name=None, residual=None):
         self.ds = ds
         self.input_variable_names = list(input_variable_names)
         self.output_variable_name = output_variable_name
@@ -71,6 +76,44 @@ class DSDataset(torch.utils.data.Dataset):
         self._x = None
         self._t = None
         self._t_norm_flag = None
+        self.residual = None
+        if residual is not None:
+            self._init_residual(residual, dev)
+
+    def _init_residual(self, residual, dev):
+        """residual = (variable, mode): the residual of the output over `variable` is scanned, and its range is this data
+        set's; (variable, mode, (rmin, rmax)): the range is given and nothing is scanned (a data set scored with a trained
+        model, whose output variable need not be the target)."""
+        from ..utils.baseline import MODES
+        (variable, mode) = (residual[0], residual[1])
+        if variable is None:
+            variable = self.input_variable_names[0]
+        if mode not in MODES:
+            raise ValueError(f"residual mode must be one of {', '.join(MODES)}, got {mode!r}")
+        if variable in self.input_variable_names:
+            raw = self._raw_in[self.input_variable_names.index(variable)]
+        else:
+            raw = self._upload(self.ds[variable], dev)
+        if int(raw.shape[0]) != self.n:
+            raise ValueError(f"residual variable {variable} holds {int(raw.shape[0])} cases, the inputs {self.n}")
+        self._raw_residual = raw
+        # whether the residual is normalised: fixed here (a model sets its own), since set_normalise_output(False) is how
+        # evaluate() asks for the truth and says nothing about the target the model was trained on
+        self.residual_normalise = bool(self.normalise_out)
+        if len(residual) > 2:
+            (self.min_residual, self.max_residual) = (float(residual[2][0]), float(residual[2][1]))
+            if variable not in self.input_variable_names:
+                (nans, _, _) = _ops.scan_f32(raw)
+                if nans > 0:
+                    raise ValueError(f"residual variable {variable} contains {nans} NaN values")
+        else:
+            if self.output_chan != 1:
+                raise ValueError(f"a residual target needs an output of one channel; {self.output_variable_name} has {self.output_chan}")
+            (k, rmin, rmax) = _ops.residual_scan(raw, self._raw_out, mode)
+            if k > 0:
+                raise ValueError(f"residual of {self.output_variable_name} over {variable} contains {k} values that are not finite")
+            (self.min_residual, self.max_residual) = (rmin, rmax)
+        self.residual = (variable, mode)
 
     @staticmethod
     def _upload(da, dev):
@@ -90,6 +133,17 @@ class DSDataset(torch.utils.data.Dataset):
         (self.min_inputs, self.max_inputs, self.min_output, self.max_output) = tuple(parameters)
         print(self.min_inputs, self.max_inputs, self.min_output, self.max_output)
         self._x = self._t = None
+
+    def get_residual_parameters(self):
+        """[rmin, rmax] of the residual target, None without one"""
+        return None if self.residual is None else [self.min_residual, self.max_residual]
+
+    def set_residual_parameters(self, parameters):
+        """the training set's [rmin, rmax], as set_normalisation_parameters hands on the normalisation"""
+        if self.residual is None:
+            raise ValueError("this data set has no residual target")
+        (self.min_residual, self.max_residual) = (float(parameters[0]), float(parameters[1]))
+        self._t = None
 
     def get_input_shape(self):
         return (self.input_chan, self.input_y, self.input_x)
@@ -111,7 +165,11 @@ class DSDataset(torch.utils.data.Dataset):
         return arr
 
     def denormalise_device(self, y):
-        """fp32 CUDA scores -> fp64 CUDA tensor (cae_denormalise_f64)"""
+        """fp32 CUDA scores -> fp64 CUDA tensor (cae_denormalise_f64); with a residual target the interpolation is added
+        back in the same pass (cae_residual_restore_f64)"""
+        if self.residual is not None:
+            return _ops.residual_restore(self._raw_residual, y, self.min_residual, self.max_residual, mode=self.residual[1],
+                                         enable=self.residual_normalise)
         return _ops.denormalise_f64(y, self.min_output, self.max_output)
 
     # -- device-resident normalised arrays (what the training loop consumes) ---------------------
@@ -130,6 +188,14 @@ class DSDataset(torch.utils.data.Dataset):
     def device_outputs(self):
         if self._raw_out is None:
             return None
+        if self.residual is not None:
+            if self._t is None or self._t_norm_flag != self.residual_normalise:
+                t = torch.empty_like(self._raw_out)
+                _ops.residual_pack(self._raw_residual, self._raw_out, t, self.min_residual, self.max_residual,
+                                   mode=self.residual[1], enable=self.residual_normalise)
+                torch.cuda.synchronize(t.device)
+                self._t, self._t_norm_flag = t, self.residual_normalise
+            return self._t
         if not self.normalise_out:
             return self._raw_out        # the un-normalised target IS the uploaded variable (one variable, no concat)
         if self._t is None or self._t_norm_flag != self.normalise_out:
@@ -156,10 +222,18 @@ class DSDataset(torch.utils.data.Dataset):
         t = None
         if self._raw_out is not None:
             t = torch.empty_like(self._raw_out)
-            _ops.normalise_pack(self._raw_out, t, 0, self.min_output, self.max_output, enable=self.normalise_out,
-                                dst_rows=rows)
+            if self.residual is not None:
+                _ops.residual_pack(self._raw_residual, self._raw_out, t, self.min_residual, self.max_residual,
+                                   mode=self.residual[1], enable=self.residual_normalise, dst_rows=rows)
+            else:
+                _ops.normalise_pack(self._raw_out, t, 0, self.min_output, self.max_output, enable=self.normalise_out,
+                                    dst_rows=rows)
         torch.cuda.synchronize(x.device)
         return x, t
+
+    def device_target(self):
+        """the output variable as uploaded (fp32 CUDA tensor), whatever the target the model trains on"""
+        return self._raw_out
 
     def device_mask(self):
         """mask variable as an fp32 CUDA tensor broadcastable to the output, or None (= every pixel)"""

@@ -18,13 +18,15 @@ class LinearModel(EngineModel):
 
     MODEL_TYPE = "Linear"
     PARAM_KEYS = ("batch_size", "test_interval", "lr", "weight_decay", "normalise_input", "normalise_output")
-    OPTIONAL_PARAM_KEYS = ()
+    OPTIONAL_PARAM_KEYS = EngineModel.RESIDUAL_KEYS
     DATA_PARALLEL = False
 
     def __init__(self, normalise_input=True, normalise_output=True, batch_size=10, nr_epochs=500, test_interval=10, lr=0.001,
-                 weight_decay=1e-5, use_gpu=True, database_path=None, scheduler_type=None, lr_step_size=500, lr_gamma=0.5):
+                 weight_decay=1e-5, use_gpu=True, database_path=None, scheduler_type=None, lr_step_size=500, lr_gamma=0.5,
+                 residual_variable=None, residual_mode="bicubic"):
         super().__init__()
         self._init_schedule(scheduler_type, lr_step_size, lr_gamma)
+        self._init_residual(residual_variable, residual_mode)
         self.normalise_input, self.normalise_output = normalise_input, normalise_output
         self.normalisation_parameters = None
         self.input_shape = self.output_shape = None
@@ -40,7 +42,7 @@ class LinearModel(EngineModel):
         return {"model_id": self.get_model_id(), "type": "LinearModel", "input_shape": list(self.input_shape),
                 "output_shape": list(self.output_shape), "batch_size": self.batch_size, "test_interval": self.test_interval,
                 "lr": self.lr, "weight_decay": self.weight_decay, "normalise_input": self.normalise_input,
-                "normalise_output": self.normalise_output, **self._schedule_parameters()}
+                "normalise_output": self.normalise_output, **self._schedule_parameters(), **self._residual_parameters()}
 
     def summary(self):
         if not self.input_shape:

@@ -34,7 +34,7 @@ from ..utils.model_database import ModelDatabase
 from ..utils.report import evaluation_report
 from .base_model import _make_data_array
 from . import evaluation_analyses as analyses
-from .ds_dataset import DSDataset
+from .ds_dataset import DSDataset  # noqa: F401  (this module's public name since before EngineModel built the data sets)
 from .model_loader import load_model
 
 MEASURES = ("mae", "mse")
@@ -123,10 +123,8 @@ class ModelEvaluator:
         return open_mfdataset(paths, concat_dim=first[self.output_variable].dims[0], combine="nested")
 
     def _dataset(self, ds):
-        dsdata = DSDataset(ds, self.model.get_input_variable_names(), self.model.get_output_variable_name(),
-                           normalise_in=self.model.normalise_input, normalise_out=False)
-        dsdata.set_normalisation_parameters(self.model.normalisation_parameters)
-        return dsdata
+        return self.model._model_dataset(ds, self.model.get_input_variable_names(), self.model.get_output_variable_name(),
+                                         normalise_in=self.model.normalise_input, normalise_out=False)
 
     def evaluate_model_metrics(self):
         train_ds = self._open(self.training_paths)

@@ -149,9 +149,10 @@ class UNET(EngineModel):
                  encoded_dim_size=32, fc_size=128, lr=0.001, weight_decay=1e-5, dropout_rate=0.1, use_gpu=True,
                  conv_kernel_size=3, conv_stride=2, conv_input_layer_count=None, conv_output_layer_count=None,
                  database_path=None, lambda_l1=0.001, lambda_pearson=1, dropout_seed=0, scheduler_type=None, lr_step_size=500,
-                 lr_gamma=0.5):
+                 lr_gamma=0.5, residual_variable=None, residual_mode="bicubic"):
         super().__init__()
         self._init_schedule(scheduler_type, lr_step_size, lr_gamma)
+        self._init_residual(residual_variable, residual_mode)
         self.normalise_input = normalise_input
         self.normalise_output = normalise_output
         self.normalisation_parameters = None
@@ -204,6 +205,7 @@ class UNET(EngineModel):
             "conv_output_layer_count": self.conv_output_layer_count,
             "model_id": self.get_model_id(),
             **self._schedule_parameters(),
+            **self._residual_parameters(),
         }
 
     def summary(self):

@@ -16,7 +16,7 @@ from ..utils.model_database import ModelDatabase
 from ._params import ParamBag, add_batchnorm, add_conv
 from .base_model import EngineModel, _make_data_array
 from .decoder import Decoder
-from .ds_dataset import DSDataset
+from .ds_dataset import DSDataset  # noqa: F401  (this module's public name since before EngineModel built the data sets)
 
 
 class VarEncoder(ParamBag):
@@ -63,9 +63,11 @@ class VarAEModel(EngineModel):
     def __init__(self, normalise_input=True, normalise_output=True, batch_size=10, nr_epochs=500, test_interval=10,
                  encoded_dim_size=32, fc_size=128, lr=0.001, weight_decay=1e-5, use_gpu=True, conv_kernel_size=3, conv_stride=2,
                  conv_input_layer_count=None, conv_output_layer_count=None, database_path=None, lambda_mse=1, lambda_kl=1,
-                 lambda_ssim=1, noise_seed=0, scheduler_type=None, lr_step_size=500, lr_gamma=0.5):
+                 lambda_ssim=1, noise_seed=0, scheduler_type=None, lr_step_size=500, lr_gamma=0.5, residual_variable=None,
+                 residual_mode="bicubic"):
         super().__init__()
         self._init_schedule(scheduler_type, lr_step_size, lr_gamma)
+        self._init_residual(residual_variable, residual_mode)
         self.normalise_input, self.normalise_output = normalise_input, normalise_output
         self.normalisation_parameters = None
         self.input_shape = self.output_shape = None
@@ -92,7 +94,7 @@ class VarAEModel(EngineModel):
                 "normalise_output": self.normalise_output, "conv_kernel_size": self.conv_kernel_size,
                 "conv_stride": self.conv_stride, "conv_input_layer_count": self.conv_input_layer_count,
                 "conv_output_layer_count": self.conv_output_layer_count, "model_id": self.get_model_id(),
-                **self._schedule_parameters()}
+                **self._schedule_parameters(), **self._residual_parameters()}
 
     def summary(self):
         if not self.spec:
@@ -128,20 +130,21 @@ class VarAEModel(EngineModel):
     def encode(self, score_ds, input_variables):
         """(mu, logvar) of every case of score_ds: float32 numpy arrays (N, encoded_dim_size); eval mode"""
         _dp.select_device()
-        ds = DSDataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input)
-        ds.set_normalisation_parameters(self.normalisation_parameters)
+        ds = self._model_dataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input)
         x = ds.device_inputs()
         (mu, logvar) = self._inference_engine(x.shape[0]).encode(x)
         return mu.cpu().numpy(), logvar.cpu().numpy()
 
     def decode(self, z):
         """z (N, encoded_dim_size) -> the denormalised float64 numpy array (N, C, H, W) the decoder makes of it; eval mode"""
+        self._refuse_residual("decode")
         _dp.select_device()
         z = torch.as_tensor(np.asarray(z), dtype=torch.float32).cuda()
         return self._denormalise(self._inference_engine(z.shape[0]).decode(z)).cpu().numpy()
 
     def generate(self, n, seed=0):
         """n fields decoded from the prior: the latents are normal_noise(seed, 0, (n, encoded_dim_size)) (oracle/vae_oracle.py)"""
+        self._refuse_residual("generate")
         _dp.select_device()
         eng = self._inference_engine(n)
         return self._denormalise(eng.decode(eng.sample_latent(None, None, draw=0, seed=seed, n=n))).cpu().numpy()
@@ -157,6 +160,8 @@ class VarAEModel(EngineModel):
         (case, "model_latent").  With none of the four keywords this is BaseModel.apply (z = mu), bit for bit.  interval,
         interval_variables and scale_variable as BaseModel.apply takes them; the calibrated scores are those of z = mu, so an
         interval is refused beside ensemble_size."""
+        if ensemble_size is not None:
+            self._refuse_residual("apply(ensemble_size=...)")
         if interval is not None and ensemble_size is not None:
             raise ValueError("interval needs the plain prediction (z = mu) the model was calibrated with: leave ensemble_size out")
         if ensemble_size is not None and (int(ensemble_size) != ensemble_size or int(ensemble_size) < 1):
@@ -172,9 +177,8 @@ class VarAEModel(EngineModel):
         _ve.check_noise_index(n, self.encoded_dim_size)
         dist = _dp.ensure_process_group()      # a rank's GPU is selected before the data set is uploaded
         n_dimension = score_ds[input_variables[0]].dims[0]
-        ds = DSDataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input,
-                       mask_variable_name=mask_variable_name)
-        ds.set_normalisation_parameters(self.normalisation_parameters)
+        ds = self._model_dataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input,
+                                 mask_variable_name=mask_variable_name)
         x = ds.device_inputs()
         # cases sharded over the GPUs of a torch.distributed.run launch as _score_all shards them; the noise counts in the
         # global case index (first_case), so the result does not depend on the number of ranks
@@ -214,14 +218,14 @@ class VarAEModel(EngineModel):
         "ensemble_seed".  2 <= K <= 64.  Under a process group every rank computes all cases."""
         from ..data.arrays import as_numpy
         from ..utils import ensemble_scores
+        self._refuse_residual("verify_ensemble")
         if int(ensemble_size) != ensemble_size or not 2 <= int(ensemble_size) <= 64:
             raise ValueError(f"ensemble_size must be an integer from 2 to 64 to be verified, got {ensemble_size!r}")
         k = int(ensemble_size)
         n = int(score_ds[input_variables[0]].shape[0])
         _ve.check_noise_index(n, self.encoded_dim_size)
         _dp.select_device()
-        ds = DSDataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input)
-        ds.set_normalisation_parameters(self.normalisation_parameters)
+        ds = self._model_dataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input)
         x = ds.device_inputs()
         eng = self._inference_engine(n)
         (mu, logvar) = eng.encode(x)

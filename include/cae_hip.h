@@ -906,6 +906,44 @@ int cae_scene_blend(const cae_scene_geom* geom, const float* pred_dev, const int
                     int64_t n_t_call, int c_out, int64_t row0, int64_t row1, double vmin, double range, double* out_dev,
                     int64_t out_t_stride, int64_t* nan_pixels_dev, void* hip_stream);
 
+/* ---- residual target over the interpolated input (stateless; DSDataset(residual=...)) ------------- */
+
+/* Global residual learning: a model trains on target - b and gets b back when it is applied, with b channel 0 of a
+ * low-resolution variable interpolated to the target's grid - exactly the field_dev of cae_case_baseline for the same low,
+ * sizes and mode (the same device functions form it: the same bits, NaN where a tap is not finite), never stored.
+ *   low     h_in x w_in per case, operand as cae_case_baseline takes it (CAE_ELEM_* kinds, big-endian as stored, any case
+ *           stride >= the plane)
+ *   target  (n_case, h_out, w_out) floats, the one-channel output variable as the loader holds it
+ *   r = (double)t - b, one rounding in fp64.
+ * cae_residual_scan (blocking): out3_host = {k, rmin, rmax}: k the number of pixels whose r is not finite, rmin and rmax the
+ * fp64 minimum and maximum of the others (+inf and -inf when there is none).  Per-wave partials are plain stores into
+ * workspace_dev (cae_residual_scan_workspace_bytes, 8-byte aligned) and one small launch folds them; a count, a minimum and a
+ * maximum do not depend on the order, so the result is exact and the same bits from run to run.
+ * cae_residual_pack_rows: row dst_row_dev[i] of dst (row i when NULL; the cae_normalise_pack_rows contract) receives
+ *   y = (float)((r - rmin) / span)   the subtraction and the division rounded in fp64, then one rounding to fp32;
+ *                                    0 when span == 0; (float)r when enable == 0; NaN where r is not finite.
+ * cae_residual_restore_f64: out = b + (rmin + (double)y * span), the product and both sums rounded in fp64, nothing
+ * contracted; b + (double)y when enable == 0; NaN where b or y is NaN.  y and out are (n_case, h_out, w_out).
+ * Pack and restore form the same bits of b, so |restore(pack(t)) - t| <= span * 2^-24 + 4 * 2^-53 * max(|t|, |b|, |rmin|,
+ * |rmax|) wherever r is finite.
+ * One launch each with cae_case_baseline's mapping: a wave owns 64 output columns of a band of 64 rows and keeps the ring of
+ * horizontally interpolated low-resolution rows; the rows of t or y stream past.  No floating-point atomics, no scratch.
+ * Limits and refusals as cae_case_baseline's: bad kind or mode, sizes below 1 or above 2^30, n_case * ceil(h_out / 64) *
+ * ceil(w_out / 64) above 2^31 - 1, a negative stride, a stride shorter than the plane, an operand reaching 2^60 elements,
+ * NULL or misaligned pointers, too small a workspace: CAE_ERR_ARG, nothing written.  n_case == 0 launches nothing and
+ * succeeds (the scan then returns {0, +inf, -inf}). */
+int64_t cae_residual_scan_workspace_bytes(int64_t n_case, int64_t h_out, int64_t w_out);
+int cae_residual_scan(const void* low_dev, int low_kind, int64_t low_case_stride, int64_t h_in, int64_t w_in,
+                      const float* target_dev, int64_t n_case, int64_t h_out, int64_t w_out, int mode,
+                      void* workspace_dev, int64_t workspace_bytes, void* hip_stream, double* out3_host);
+int cae_residual_pack_rows(const void* low_dev, int low_kind, int64_t low_case_stride, int64_t h_in, int64_t w_in,
+                           const float* target_dev, int64_t n_case, int64_t h_out, int64_t w_out, int mode,
+                           double rmin, double span, int enable, const int32_t* dst_row_dev /* NULL: row i */,
+                           float* dst_dev, void* hip_stream);
+int cae_residual_restore_f64(const void* low_dev, int low_kind, int64_t low_case_stride, int64_t h_in, int64_t w_in,
+                             const float* y_dev, int64_t n_case, int64_t h_out, int64_t w_out, int mode,
+                             double rmin, double span, int enable, double* out_dev, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
