@@ -1,6 +1,6 @@
 """The case kernels of libcae_hip (include/cae_hip.h) as functions, no engine needed: measures, per-pixel sums, spectra, SSIM,
 interpolation baseline, value distributions, skill by stratum, neighbourhood skill, permutation importance, prediction
-intervals, novelty against a reference set, ensemble verification, value range and rendered pages of channel 0 of (N, C, H, W) operands."""
+intervals, novelty against a reference set, model comparison and its bootstrap, ensemble verification, value range and rendered pages of channel 0 of (N, C, H, W) operands."""
 import ctypes as C
 import math
 from contextlib import contextmanager
@@ -20,6 +20,7 @@ _TORCH_KINDS = {torch.float32: _lib.ELEM_F32, torch.float64: _lib.ELEM_F64}
 _BASELINE_FIELD_BYTES = 256 << 20       # of fp64 field per cae_case_baseline call when the field is asked for
 _RENDER_BYTES = 64 << 20                # of rendered pages per group of cae_render_cases calls
 _FSS_PLANE_BYTES = 256 << 20            # of bit-planes per cae_case_fss call (one case at least)
+_COMPARE_BYTES = 256 << 20              # of per-tile partials per cae_case_compare call (one case at least)
 
 
 @dataclass(frozen=True, eq=False)
@@ -452,6 +453,84 @@ def case_importance(base, pert, actual, vmin, vmax, maps=None, device=None):
                                       vmin, rng, sums.data_ptr(), maps.data_ptr() if maps is not None else None, ws.data_ptr(), need,
                                       stream))
         return sums.cpu().numpy()
+
+
+def case_compare(preds, actual, device=None):
+    """Up to 8 predictions against one target on the same pixels (cae_case_compare, include/cae_hip.h): an (N, 2 + 4 M) float64
+    numpy array {n, tied, (S e_m, S|e_m|, S e_m^2, wins_m) for m = 0 .. M - 1} per case of channel 0, with e_m = P_m - a in
+    fp64 over the pixels where the target and every prediction are finite; candidate m wins a pixel when its squared error is
+    strictly the smallest, a pixel whose smallest squared error is shared counts as tied.  preds: a list of 1 to 8 (N, C, H,
+    W) operands as case_measures takes them (C may differ); they go to the kernel in one element kind, so where their kinds
+    differ those that are not native fp64 are converted to it on the device, which changes no value.  The cases go in chunks
+    that bound the workspace, and a case's sums do not depend on the cut.  utils/compare.summary turns the sums, and their
+    bootstrap resamples (bootstrap_sums), into the scores."""
+    preds = list(preds)
+    if not 1 <= len(preds) <= 8:
+        raise ValueError(f"case_compare: 1 to 8 predictions expected, got {len(preds)}")
+    (device, ops) = device_operands(preds + [actual], device)
+    (ps, a) = (ops[:-1], ops[-1])
+    for p in ps:
+        if len(p.shape) != 4 or len(a.shape) != 4:
+            raise ValueError(f"case_compare: (N, C, H, W) arrays expected, got {p.shape} and {a.shape}")
+        if p.shape[0] != a.shape[0] or p.shape[2:] != a.shape[2:]:
+            raise ValueError(f"case_compare: prediction {p.shape} and target {a.shape} do not match")
+    (n, h, w, m) = (int(a.shape[0]), int(a.shape[2]), int(a.shape[3]), len(ps))
+    (plane, width) = (h * w, 2 + 4 * len(ps))
+    if n == 0 or plane == 0:
+        return np.zeros((n, width), dtype=np.float64)
+    if len({p.kind for p in ps}) > 1:
+        ps = [p if p.kind == _lib.ELEM_F64 else _as_f64(p) for p in ps]
+    lib = _lib.load()
+    group = max(1, min(n, _COMPARE_BYTES // int(lib.cae_case_compare_workspace_bytes(1, plane, m))))
+    sums = torch.empty((n, width), dtype=torch.float64, device=device)
+    (ws, need) = _workspace(device, lib.cae_case_compare_workspace_bytes, group, plane, m, least=16)
+    strides = (C.c_int64 * m)(*[p.stride for p in ps])
+    with _stream(device) as stream:
+        for c0 in range(0, n, group):
+            g = min(n, c0 + group) - c0
+            ptrs = (C.c_void_p * m)(*[p.args(c0)[0] for p in ps])
+            check(lib.cae_case_compare(ptrs, ps[0].kind, strides, m, *a.args(c0), g, plane, sums[c0:].data_ptr(), ws.data_ptr(),
+                                       need, stream))
+        return sums.cpu().numpy()
+
+
+def _as_f64(op):
+    """channel 0 of a device operand as a native fp64 operand (N, 1, H, W), converted on the device: exact for every kind"""
+    if op.kind == _lib.ELEM_F32:
+        t = op.tensor[:, :1].to(torch.float64)
+    else:       # a big-endian slab: its raw bytes, swapped as integers
+        (n, per, wide) = (int(op.shape[0]), int(op.shape[2]) * int(op.shape[3]), op.elem_bytes)
+        raw = op.tensor.view(n, op.stride * wide)[:, :per * wide].reshape(n, per, wide).flip(2).contiguous()
+        t = raw.view(torch.float32 if wide == 4 else torch.float64).reshape(n, 1, int(op.shape[2]), int(op.shape[3])).to(torch.float64)
+    t = t.contiguous()
+    return DeviceOperand(t, _lib.ELEM_F64, tuple(t.shape), int(t.stride(0)))
+
+
+def bootstrap_sums(table, resamples, seed=0, first=0, device=None):
+    """The paired bootstrap of a table of per-unit sums on the device (cae_bootstrap_sums, include/cae_hip.h): table (n_unit,
+    n_col) float64 with 1 <= n_col <= 32 and 1 <= n_unit <= 2^20; returns the (resamples, n_col) float64 numpy array whose row k
+    is the sum of the n_unit rows drawn with replacement for resample first + k, added in draw order with plain fp64 adds.  The
+    draws are a counter-based function of (seed, resample, draw) alone: exact, the same bits from run to run, resamples cut
+    into consecutive calls give the bits of one call, and two tables of the same n_unit resampled with the same seed are
+    resampled alike.  tests/compare_ref.py restates it in numpy."""
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    if table.ndim != 2 or not 1 <= table.shape[0] <= 1 << 20 or not 1 <= table.shape[1] <= 32:
+        raise ValueError(f"bootstrap_sums: a table (n_unit, n_col) with 1 <= n_unit <= 2^20 and 1 <= n_col <= 32 expected, got {table.shape}")
+    (b, first, seed) = (int(resamples), int(first), int(seed))
+    if b < 0 or first < 0 or first + b > 1 << 32:
+        raise ValueError(f"bootstrap_sums: resamples [{first}, {first + b}) must lie within [0, 2^32)")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"bootstrap_sums: seed must be an integer from 0 to 2^64 - 1, got {seed}")
+    (n_unit, n_col) = table.shape
+    if b == 0:
+        return np.zeros((0, n_col), dtype=np.float64)
+    device = _case_device(device)
+    lib = _lib.load()
+    out = torch.empty((b, n_col), dtype=torch.float64, device=device)
+    with _stream(device) as stream:
+        t = torch.from_numpy(table).to(device)
+        check(lib.cae_bootstrap_sums(t.data_ptr(), n_unit, n_col, first, b, seed, out.data_ptr(), stream))
+        return out.cpu().numpy()
 
 
 def _score_operands(name, pred, actual, scale, device):

@@ -472,5 +472,5 @@ class HipEngine(EnginePlan):
 
 # the entry points that use no engine live beside this module; they keep the names they have always had here
 from .device_ops import denormalise_f64, inverse_permutation, metric_sums, normalise_pack, scan_f32, upload_f32  # noqa: E402,F401
-from .case_ops import (_SSIM_CASES, DeviceOperand, case_baseline, case_importance, case_measures, case_neighbours, case_range, case_spectra, case_ssim, device_operand, ensemble_verify, fraction_skill, interval_bounds, joint_histogram, operand_cases, pack_gather, pixel_sums, render_cases, score_counts, score_quantiles, strata_sums, upsample)  # noqa: E402,F401
+from .case_ops import (_SSIM_CASES, DeviceOperand, bootstrap_sums, case_baseline, case_compare, case_importance, case_measures, case_neighbours, case_range, case_spectra, case_ssim, device_operand, ensemble_verify, fraction_skill, interval_bounds, joint_histogram, operand_cases, pack_gather, pixel_sums, render_cases, score_counts, score_quantiles, strata_sums, upsample)  # noqa: E402,F401
 from .scene import ScenePlan, scene_apply, scene_blend, scene_chunks, scene_plan, scene_tiles  # noqa: E402,F401

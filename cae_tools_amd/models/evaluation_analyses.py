@@ -1,6 +1,6 @@
 """The optional outputs of ModelEvaluator.build_html, none of them a reference feature: ensemble verification, case pages,
 structural similarity, skill against interpolation, per-pixel skill maps, power spectra, value distributions, skill by
-stratum, neighbourhood skill, input importance and novelty of the cases.
+stratum, neighbourhood skill, input importance, novelty of the cases and the comparison of models.
 
 Each is one Analysis of functions over the evaluator `ev`:
     enabled(ev)                                     whether its option is on
@@ -17,10 +17,11 @@ from collections import namedtuple
 
 import numpy as np
 
-from ..case_ops import (case_baseline, case_range, case_spectra, case_ssim, device_operand, fraction_skill, joint_histogram, pixel_sums,
-                        render_cases, strata_sums)
-from ..data.arrays import as_numpy
+from ..case_ops import (bootstrap_sums, case_baseline, case_compare, case_range, case_spectra, case_ssim, device_operand, fraction_skill,
+                        joint_histogram, pixel_sums, render_cases, strata_sums)
+from ..data.arrays import as_numpy, open_mfdataset
 from ..utils import baseline as baseline_scores
+from ..utils import compare as compare_scores
 from ..utils import distribution as distribution_curves
 from ..utils import ensemble_scores, skill_maps
 from ..utils import fss as fss_scores
@@ -472,6 +473,109 @@ def _novelty(ev, partition, ds, values, report):
     return {"novelty": case["novelty"], "nearest_case": case["nearest_case"]}
 
 
+# ---- model comparison ------------------------------------------------------------------------
+
+def _compare_settings(ev):
+    """(variables, labels, resamples, seed, confidence) of the comparison, each refused where it is wrong"""
+    (variables, labels) = compare_scores.check_candidates(ev.model_output_variable, ev.compare_variables, ev.compare_labels)
+    return (variables, labels, compare_scores.check_resamples(ev.compare_resamples), compare_scores.check_seed(ev.compare_seed),
+            compare_scores.parse_confidence(ev.compare_confidence))
+
+
+def _compare_files(ev, partition, ds, variables, target=None):
+    """refuses a partition that does not hold the comparison's variables in the shapes it needs.  target None: before the
+    model is loaded its name is not known, so the candidates are held to the first of them that is there."""
+    found = [v for v in variables[1:] if v not in ds]
+    if found:
+        raise ValueError(f"compare needs the variable {found[0]!r} in the {partition} data set (apply_cae --prediction-variable "
+                         f"{found[0]} writes it)")
+    shapes = [(v, tuple(ds[v].shape)) for v in ([target] if target else []) + list(variables) if v in ds]
+    for (v, shape) in shapes:
+        if len(shape) != 4 or shape[0] != shapes[0][1][0] or shape[2:] != shapes[0][1][2:]:
+            raise ValueError(f"compare: {v!r} {shape} and {shapes[0][0]!r} {shapes[0][1]} of the {partition} data set do not match: "
+                             "(N, C, H, W) variables with N, H and W in common expected")
+    name = ev.compare_block_variable
+    if name:
+        if name not in ds or len(ds[name].shape) != 1 or (shapes and ds[name].shape[0] != shapes[0][1][0]):
+            raise ValueError(f"compare_block_variable {name!r} is not a variable of the {partition} data set with one value per case")
+    if shapes and not ev.compare_block_variable and shapes[0][1][0] > compare_scores.MAX_UNITS:
+        raise ValueError(f"compare: at most {compare_scores.MAX_UNITS} resampling units expected, the {partition} data set has "
+                         f"{shapes[0][1][0]} cases; name a compare_block_variable")
+
+
+def check_compare(ev):
+    """the refusals of the settings, and of the files as far as they can be seen before the model is loaded: no GPU yet"""
+    if not ev.compare:
+        return
+    variables = _compare_settings(ev)[0]
+    if ev.compare_baseline is not None and ev.compare_baseline not in baseline_scores.MODES:
+        raise ValueError(f"compare_baseline must be one of {', '.join(baseline_scores.MODES)}, got {ev.compare_baseline!r}")
+    for (partition, paths) in (("test", ev.testing_paths), ("train", ev.training_paths)):
+        if paths and (len(variables) > 1 or ev.compare_block_variable):
+            for path in paths:
+                _compare_files(ev, partition, open_mfdataset([path]), variables)
+
+
+def check_compare_model(ev):
+    """what check_compare cannot see before the model is loaded: the candidates have the target's cases and plane"""
+    if not ev.compare:
+        return
+    variables = _compare_settings(ev)[0]
+    for (partition, paths) in (("test", ev.testing_paths), ("train", ev.training_paths)):
+        ds = ev._open(paths)
+        if ds is not None:
+            _compare_files(ev, partition, ds, variables, target=ev.output_variable)
+            name = ev.model_input_variables[0]
+            if ev.compare_baseline is not None and (name not in ds or len(ds[name].shape) != 4):
+                raise ValueError(f"compare_baseline needs the model's first input variable {name!r} as a 4-dimensional variable "
+                                 f"of the {partition} data set")
+
+
+def _bootstrap(table, resamples, seed):
+    """cae_bootstrap_sums of a table of any width: column pieces of at most 32 with the same seed - the units of a resample
+    depend on (seed, resample, n_unit) alone, so the pieces are resampled alike - and resamples in consecutive pieces"""
+    pieces = []
+    for c0 in range(0, table.shape[1], compare_scores.MAX_COLUMNS):
+        part = np.ascontiguousarray(table[:, c0:c0 + compare_scores.MAX_COLUMNS])
+        pieces.append(np.concatenate([bootstrap_sums(part, min(_COMPARE_RESAMPLES, resamples - r0), seed=seed, first=r0)
+                                      for r0 in range(0, resamples, _COMPARE_RESAMPLES)]))
+    return np.concatenate(pieces, axis=1)
+
+
+_COMPARE_RESAMPLES = 1 << 18        # resamples per cae_bootstrap_sums call
+
+
+def _compare(ev, partition, ds, values, report):
+    """compare=True (cli/compare.py) asks whether a difference between models survives resampling the cases: the evaluator's
+    prediction and the compare_variables - other models' predictions in the same scored files (apply_cae
+    --prediction-variable) - are held against the target on the pixels where the target and all of them are finite, one
+    streaming cae_case_compare pass on the GPU; the per-case sums, or with compare_block_variable the sums of the cases of
+    equal value, are the units of a paired bootstrap on the GPU (cae_bootstrap_sums: compare_resamples resamples drawn from
+    compare_seed; utils/compare.py).  compare_<partition>.json holds per candidate mse, rmse, mae and
+    bias with their intervals at compare_confidence, per competitor delta_mse, skill, p_better, significant and the shares
+    of pixels won and tied; with compare_baseline the skill against interpolating the first input with its interval, from
+    cae_case_baseline's sums resampled with the same seed.  The report gets the "Model comparison" section."""
+    (variables, labels, resamples, seed, confidence) = _compare_settings(ev)
+    a = ev.operand(partition, ds, ev.output_variable)
+    rows = case_compare([ev.operand(partition, ds, v) for v in variables], a)
+    block = as_numpy(ds[ev.compare_block_variable]) if ev.compare_block_variable else None
+    table = compare_scores.units(rows, block)[0]
+    if not 1 <= table.shape[0] <= compare_scores.MAX_UNITS:
+        raise ValueError(f"compare: 1 to {compare_scores.MAX_UNITS} resampling units expected, the {partition} data set has {table.shape[0]}")
+    base = None
+    if ev.compare_baseline is not None:
+        name = ev.model_input_variables[0]
+        sums = case_baseline(ev.operand(partition, ds, name), ev.operand(partition, ds, ev.model_output_variable), a,
+                             mode=ev.compare_baseline)
+        units = compare_scores.units(sums, block)[0]
+        base = compare_scores.baseline_summary(units, _bootstrap(units, resamples, seed), confidence, ev.compare_baseline, name)
+    record = compare_scores.summary(table, _bootstrap(table, resamples, seed), variables, labels, confidence, resamples, seed,
+                                    n_cases=rows.shape[0], plane=int(a.shape[2]) * int(a.shape[3]),
+                                    block_variable=ev.compare_block_variable or None, baseline=base)
+    _keep(ev, compare_scores, "compare", partition, record, report.setdefault("compare", []))
+    return {}
+
+
 ENSEMBLE = Analysis(lambda ev: ev.ensemble_size is not None, check_ensemble, partition=_ensemble)
 CASE_PAGES = Analysis(lambda ev: ev.x_coordinate and ev.y_coordinate and ev.time_coordinate, partition=_case_pages)
 SSIM = Analysis(lambda ev: ev.ssim, partition=_ssim)
@@ -481,8 +585,9 @@ SPECTRA = Analysis(lambda ev: ev.spectra, after=_spectra)
 DISTRIBUTION = Analysis(lambda ev: ev.distribution, check_distribution, after=_distribution)
 STRATA = Analysis(lambda ev: ev.strata, check_strata, after=_strata)
 FSS = Analysis(lambda ev: ev.fss, check_fss, after=_fss)
-# in the order build_html runs them: per partition ensemble, case pages, ssim, baseline, novelty; then skill maps, spectra,
-# distribution, strata, fss, importance
+# in the order build_html runs them: per partition ensemble, case pages, ssim, baseline, novelty, compare; then skill maps,
+# spectra, distribution, strata, fss, importance
 IMPORTANCE = Analysis(lambda ev: ev.importance, check_importance, after=_importance)
 NOVELTY = Analysis(lambda ev: ev.novelty, check_novelty, partition=_novelty)
-ANALYSES = (ENSEMBLE, CASE_PAGES, SSIM, BASELINE, NOVELTY, SKILL_MAPS, SPECTRA, DISTRIBUTION, STRATA, FSS, IMPORTANCE)
+COMPARE = Analysis(lambda ev: ev.compare, check_compare, partition=_compare)
+ANALYSES = (ENSEMBLE, CASE_PAGES, SSIM, BASELINE, NOVELTY, COMPARE, SKILL_MAPS, SPECTRA, DISTRIBUTION, STRATA, FSS, IMPORTANCE)

@@ -18,7 +18,7 @@ index is 0 for NaN and 1 + round-half-up(254 * clamp((v - lo) / (hi - lo), 0, 1)
 (cae_render_cases) from the slabs as stored and from the prediction where it still lies in HBM.
 
 The optional analyses that are no reference feature - ensemble verification, structural similarity, skill against
-interpolation, per-pixel skill maps, power spectra, value distributions, skill by stratum, neighbourhood skill, input importance and novelty of the cases - are the units of
+interpolation, per-pixel skill maps, power spectra, value distributions, skill by stratum, neighbourhood skill, input importance, novelty of the cases and the comparison of models - are the units of
 evaluation_analyses.py, which build_html runs in their fixed order.  What they and the case pages read on the GPU comes
 from one operand cache (operand): a partition's variable is uploaded once per build_html, whatever is switched on.
 """
@@ -49,7 +49,9 @@ class ModelEvaluator:
                  strata=False, strata_variable=None, strata_channel=0, strata_edges=None, strata_classes=None, strata_count=8,
                  fss=False, fss_thresholds=None, fss_percentiles=None, fss_widths=None, fss_gaps="strict",
                  importance=False, importance_repeats=5, importance_seed=0, importance_groups=None, importance_maps=False,
-                 novelty=False, novelty_k=5, novelty_reference=None):
+                 novelty=False, novelty_k=5, novelty_reference=None, compare=False, compare_variables=None, compare_labels=None,
+                 compare_resamples=10000, compare_seed=0, compare_confidence="0.95", compare_block_variable=None,
+                 compare_baseline=None):
         self.training_paths = list(training_paths) if training_paths else []
         self.testing_paths = list(testing_paths) if testing_paths else []
         self.output_html_folder = output_html_folder
@@ -77,9 +79,13 @@ class ModelEvaluator:
         (self.importance_groups, self.importance_maps) = (importance_groups, importance_maps)
         (self.novelty, self.novelty_k) = (novelty, novelty_k)
         self.novelty_reference = list(novelty_reference) if novelty_reference else None
+        (self.compare, self.compare_variables) = (compare, list(compare_variables) if compare_variables else [])
+        self.compare_labels = list(compare_labels) if compare_labels else None
+        (self.compare_resamples, self.compare_seed, self.compare_confidence) = (compare_resamples, compare_seed, compare_confidence)
+        (self.compare_block_variable, self.compare_baseline) = (compare_block_variable, compare_baseline)
         for unit in (analyses.BASELINE, analyses.DISTRIBUTION, analyses.ENSEMBLE,       # the refusals come in this order,
                      analyses.STRATA, analyses.FSS, analyses.IMPORTANCE,                # all before the model is loaded
-                     analyses.NOVELTY):
+                     analyses.NOVELTY, analyses.COMPARE):
             unit.check(self)
         self.model = load_model(self.model_path)
         analyses.check_ensemble_model(self)
@@ -92,6 +98,7 @@ class ModelEvaluator:
         if self.baseline and not self.baseline_variable:
             self.baseline_variable = self.model_input_variables[0]
         analyses.check_importance_model(self)
+        analyses.check_compare_model(self)
         self._device_predictions = {}
         self._run = None             # inside build_html: (case dimension, [(partition, data set)] in page order)
         self._operands = None        # inside build_html: {(partition, variable): device operand}

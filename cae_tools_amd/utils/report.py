@@ -222,7 +222,7 @@ def _section(body, title, records, heading, rows, plots=None):
 
 def evaluation_report(metrics, measures, parameters=None, history=None, case_links=None, maps_link=None, ensemble=None,
                       spectra_link=None, ssim=None, baseline=None, distribution=None, strata=None, fss=None,
-                      importance=None, novelty=None):
+                      importance=None, novelty=None, compare=None):
     """index.html of evaluate_cae, its sections in the reference's order (model_evaluator.py:162-314).
     metrics: {"test": {...}, "train": {...}} (either may be absent); measures: [(partition, {"mae": values, "mse": values})]
     in page order; parameters: parameters.json; history: history.json; case_links: {partition: href}; maps_link: href of
@@ -242,7 +242,10 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
     link; importance: ([(partition, record)] of utils/importance.summary, href of the page of per-pixel maps or None): an
     "Input importance" section with the table of the groups of input variables by rank, the bar chart of importance +- sd,
     and the link where there is one; novelty: [(partition, record)] of utils/novelty.summary: a "Novelty of the cases"
-    section with the table of the scores and quintiles and the bar chart of the mse per novelty quintile."""
+    section with the table of the scores and quintiles and the bar chart of the mse per novelty quintile; compare: [(partition,
+    record)] of utils/compare.summary: a "Model comparison" section with the table of the candidates - mse, rmse, mae and bias,
+    and against the first of them delta mse, skill, p better and significance - and the bar chart of the mse with the
+    interval as whiskers."""
     doc = Document("Model Evaluation")
     doc.head.add("style").text(STYLE)
     body = doc.body
@@ -315,6 +318,10 @@ def evaluation_report(metrics, measures, parameters=None, history=None, case_lin
         from . import novelty as novelty_scores
         _section(body, "Novelty of the cases", novelty, novelty_scores.heading, novelty_scores.section_rows,
                  {"mse by novelty quintile": lambda rec: novelty_scores.svg_quintiles(rec, "mse by novelty quintile")})
+    if compare:
+        from . import compare as compare_scores
+        _section(body, "Model comparison", compare, compare_scores.heading, compare_scores.section_rows,
+                 {"mse by candidate": lambda rec: compare_scores.svg_bars(rec, "mse with bootstrap interval")})
     if parameters or history:
         body.add("h2").text("Training Summary")
     if parameters:

@@ -944,6 +944,48 @@ int cae_residual_restore_f64(const void* low_dev, int low_kind, int64_t low_case
                              const float* y_dev, int64_t n_case, int64_t h_out, int64_t w_out, int mode,
                              double rmin, double span, int enable, double* out_dev, void* hip_stream);
 
+/* ---- models compared on the same pixels, with bootstrap intervals (stateless) ------------------- */
+
+/* Candidates.  n_pred predictions P_0 .. P_{M-1} (1 <= M <= 8) and the target a, channel 0 of (n_case, plane) operands as
+ * stored, as cae_case_measures takes them: case i at element i * case_stride, any alignment of the element size, big-endian
+ * kinds included.  pred_ptrs and pred_case_strides are HOST arrays of n_pred device pointers and strides; the predictions of
+ * one call share one element kind.
+ * Pair rule.  A pixel counts for a case only if a and all M predictions are finite: common pixels.  In fp64
+ *   e_m = P_m - a,   q_m = e_m * e_m        each rounded on its own, nothing contracted into a fused multiply-add
+ *   sums_dev[case] = {n, tied, (S e_m, S|e_m|, S e_m^2, wins_m) for m = 0 .. M-1}        2 + 4 M doubles, over the pairs
+ * Candidate m wins a pixel when q_m < q_j for every j != m; a pixel whose smallest q is attained more than once adds 1 to
+ * tied and to nobody's wins (M == 1: wins_0 = n, tied = 0).  n, tied and the wins are exact integers.  A case without a
+ * pair gets +0.0 everywhere.  The row is written whole.
+ * Fold order: cae_case_importance's without the map.  Tiles of 64 consecutive pixels, one pixel per lane, a fixed tree over
+ * the 64 lanes, the partials per (case, tile) stored plainly to the workspace, then the tiles of a case by lane j taking tiles
+ * j, j + 64, ... in ascending order and the same tree.  A case's sums do not depend on the other cases of the call, on n_case
+ * or on the operands' alignment.  No atomics: the same arguments give the same bits from run to run.
+ * workspace_dev (16-byte aligned) holds cae_case_compare_workspace_bytes = n_case * ceil(plane / 64) * (2 + 4 M) * 8 bytes (0
+ * for an empty or refused shape).  n_case == 0 or plane == 0 succeeds and writes nothing.  A bad kind, n_pred outside 1 .. 8,
+ * negative sizes or strides, NULL pointers, a stride shorter than the plane, an operand reaching 2^60 elements from its
+ * pointer, misaligned pointers, too small or misaligned a workspace: CAE_ERR_ARG, nothing written. */
+int64_t cae_case_compare_workspace_bytes(int64_t n_case, int64_t plane, int n_pred);
+int cae_case_compare(const void* const* pred_ptrs /* host array of n_pred device pointers */, int pred_kind,
+                     const int64_t* pred_case_strides /* host array */, int n_pred, const void* actual_dev, int actual_kind,
+                     int64_t actual_case_stride, int64_t n_case, int64_t plane, double* sums_dev /* [n_case][2 + 4 n_pred] */,
+                     void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
+/* The paired bootstrap of a table of per-unit sums S[n_unit][n_col] (fp64, 1 <= n_col <= 32, 1 <= n_unit <= 2^20).  Resample
+ * k of the call has the absolute index r = first_resample + k < 2^32.  Draw i of resample r takes unit j(r, i):
+ *   x = (uint64(r) << 32) | i
+ *   z = mix64(seed + (x + 1) * 0x9E3779B97F4A7C15)     wrapping 64-bit arithmetic: output x + 1 of splitmix64 seeded with seed
+ *   mix64(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   u = z >> 32,   j = (u * n_unit) >> 32             a unit's probability is within n_unit / 2^32 relative of 1 / n_unit
+ *   out_dev[k][c] = S[j(r, 0)][c] + S[j(r, 1)][c] + ... + S[j(r, n_unit - 1)][c]      from +0.0, in that order, plain rounded adds
+ * so the bits depend on (S, seed, r) alone, resamples cut into consecutive calls give the bits of one call, and NaN, +-inf
+ * and -0.0 propagate as IEEE adds.  The same (seed, r) takes the same units from every table of the same n_unit: paired.
+ * A table of up to 160 KiB is staged in LDS by every workgroup, a larger one is read through L2; a lane owns a resample and 1
+ * column, or 4 from 2^17 such lanes on - the result is the same by definition.  No workspace.  n_resample == 0 succeeds and
+ * writes nothing.  n_unit or n_col outside their ranges, negative counts, first_resample + n_resample > 2^32, NULL or
+ * misaligned pointers: CAE_ERR_ARG, nothing written. */
+int cae_bootstrap_sums(const double* table_dev, int64_t n_unit, int n_col, int64_t first_resample, int64_t n_resample,
+                       uint64_t seed, double* out_dev /* [n_resample][n_col] */, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
