@@ -165,6 +165,7 @@ SIGNATURES = {
     "cae_case_compare_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
     "cae_case_compare": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
     "cae_bootstrap_sums": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_uint64, _P, _P]),
+    "cae_dihedral_rows": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P, C.c_int, _P]),
     # ---- include/cae_unet.h ----
     "unet_engine_create": (C.c_int, [C.POINTER(LayerSpecC), C.c_int, C.POINTER(LayerSpecC), C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.POINTER(C.c_void_p)]),

@@ -416,6 +416,57 @@ def pack_gather(raw, dst, c_off, rows, vmin, vmax, enable=True):
                                             1 if enable else 0, rows.data_ptr(), stream))
 
 
+def dihedral_rows(src, dst, codes, rows=None, group=8):
+    """dst[i] = g(codes[i]) applied to src[rows[i]] on the device, every channel, as 32-bit words (cae_dihedral_rows,
+    include/cae_hip.h; utils/augment.apply is the numpy definition of a code).  src: (n_src, C, h, w) and dst: (n_dst, C, h, w)
+    contiguous float32 CUDA tensors that do not overlap; codes: an int32 CUDA tensor of n_dst entries; rows: likewise, in any
+    order, repeats allowed, or None for row i.  group 4 takes the codes 0 .. 3 on any plane, group 8 all eight on square
+    planes.  A row index outside 0 .. n_src - 1 or a code outside the group is not followed: that row of dst gets NaN."""
+    for (name, t) in (("src", src), ("dst", dst)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()):
+            raise ValueError(f"dihedral_rows: {name} must be a contiguous float32 CUDA tensor (N, C, h, w)")
+    if dst.device != src.device or tuple(dst.shape[1:]) != tuple(src.shape[1:]):
+        raise ValueError(f"dihedral_rows: rows of src {tuple(src.shape)} and dst {tuple(dst.shape)} do not match, or their devices")
+    if group not in (4, 8):
+        raise ValueError(f"dihedral_rows: group must be 4 or 8, got {group!r}")
+    (n_src, n_dst, c, h, w) = (int(src.shape[0]), int(dst.shape[0]), int(src.shape[1]), int(src.shape[2]), int(src.shape[3]))
+    if group == 8 and h != w:
+        raise ValueError(f"dihedral_rows: group 8 transposes, which needs square planes, got {h} x {w}")
+    for (name, t) in (("codes", codes),) + ((("rows", rows),) if rows is not None else ()):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == src.device and t.dim() == 1
+                and t.is_contiguous() and t.numel() == n_dst):
+            raise ValueError(f"dihedral_rows: {name} must be a contiguous int32 tensor of one entry per row of dst on the data's device")
+    if c < 1:
+        raise ValueError("dihedral_rows: at least one channel expected")
+    lib = _lib.load()
+    with _stream(src.device) as stream:
+        check(lib.cae_dihedral_rows(src.data_ptr(), n_src, c, h, w, dst.data_ptr(), n_dst, rows.data_ptr() if rows is not None else None,
+                                    codes.data_ptr(), int(group), stream))
+
+
+def ensemble_moments(draws, vmin, vmax, want_std=True):
+    """The per-pixel mean and sample standard deviation of K >= 2 members (cae_ensemble_moments, include/cae_hip.h, all draws in
+    one call): draws is a contiguous float32 CUDA tensor (K, N, ...) - [draw][case], normalised scores - and the result (mean,
+    std) float64 CUDA tensors (N, ...), mean = vmin + (y_0 + S (y_k - y_0) / K) (vmax - vmin) and std (None unless want_std)
+    the ddof = 1 deviation times |vmax - vmin|.  A pixel is summed by one lane in draw order: a case's result does not depend
+    on the other cases of the call."""
+    if not (isinstance(draws, torch.Tensor) and draws.is_cuda and draws.dtype == torch.float32 and draws.dim() >= 3
+            and draws.is_contiguous()):
+        raise ValueError("ensemble_moments: draws must be a contiguous float32 CUDA tensor (K, N, ...)")
+    (k, n) = (int(draws.shape[0]), int(draws.shape[1]))
+    if k < 2:
+        raise ValueError(f"ensemble_moments: at least 2 draws expected, got {k}")
+    plane = int(np.prod(draws.shape[2:]))
+    mean = torch.empty(tuple(draws.shape[1:]), dtype=torch.float64, device=draws.device)
+    std = torch.empty_like(mean) if want_std else None
+    if n and plane:
+        lib = _lib.load()
+        with _stream(draws.device) as stream:
+            check(lib.cae_ensemble_moments(draws.data_ptr(), plane, n * plane, n, plane, k, 0, k, float(vmin), float(vmax) - float(vmin),
+                                           mean.data_ptr(), std.data_ptr() if want_std else None, None, 0, stream))
+    return mean, std
+
+
 def case_importance(base, pert, actual, vmin, vmax, maps=None, device=None):
     """The eight sums of permutation importance per case (cae_case_importance, include/cae_hip.h): an (N, 8) float64 numpy
     array {n, S e1^2, S e0^2, S|e1|, S|e0|, S (P1 - P0)^2, #(e1^2 > e0^2), #(e1^2 < e0^2)} of channel 0 with P = vmin +

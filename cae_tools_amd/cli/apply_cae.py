@@ -9,6 +9,7 @@ import numpy as np
 
 from ..data.arrays import DataArray, open_mfdataset
 from ..models.model_loader import load_model
+from ..utils.augment import GROUPS as AUGMENT_GROUPS
 
 
 def build_parser():
@@ -35,6 +36,11 @@ def build_parser():
                    help="names of the two bounds (default: <prediction-variable>_lower and _upper)")
     p.add_argument("--scale-variable", default=None, metavar="NAME",
                    help="with --interval: the variable the calibration divided the residual by")
+    p.add_argument("--self-ensemble", choices=list(AUGMENT_GROUPS), default=None,
+                   help="build-only: score every case in the 4 (flips) or 8 (dihedral: square planes only) orientations of the "
+                        "group, turn the outputs back and store their per-pixel mean")
+    p.add_argument("--self-ensemble-spread", default=None, metavar="NAME",
+                   help="with --self-ensemble: also store the per-pixel standard deviation of the orientations under NAME")
     p.add_argument("--novelty-variable", default=None, metavar="NAME",
                    help="build-only: also store the novelty of every scored case against --novelty-reference under NAME")
     p.add_argument("--novelty-reference", nargs="+", default=None, metavar="F",
@@ -95,6 +101,32 @@ def interval_keywords(args):
     return {"interval": args.interval, "interval_variables": args.interval_variables, "scale_variable": args.scale_variable}
 
 
+def self_ensemble_keywords(args):
+    """the apply() keywords of --self-ensemble (empty: none asked for), checked against the folder's parameters.json here, before
+    any rank is spawned or the GPU touched"""
+    if args.self_ensemble is None:
+        if args.self_ensemble_spread is not None:
+            raise SystemExit("--self-ensemble-spread needs --self-ensemble {flips,dihedral}")
+        return {}
+    if args.interval is not None:
+        raise SystemExit("--interval needs the plain prediction the model was calibrated with: leave --self-ensemble out")
+    if args.ensemble_size is not None:
+        raise SystemExit("--self-ensemble and --ensemble-size are two ensembles: ask for one of them")
+    if args.self_ensemble_spread is not None and args.self_ensemble_spread == args.prediction_variable:
+        raise SystemExit("--self-ensemble-spread must differ from --prediction-variable")
+    from ..models.base_model import residual_refusal
+    from ..utils import augment
+    with open(os.path.join(args.model_folder, "parameters.json")) as f:
+        parameters = json.load(f)
+    if parameters.get("residual_variable") is not None:
+        raise SystemExit("--self-ensemble: " + residual_refusal("apply(self_ensemble=...)", parameters["residual_variable"]))
+    try:
+        augment.check_square(args.self_ensemble, [parameters["input_shape"], parameters["output_shape"]], "self_ensemble")
+    except ValueError as refused:
+        raise SystemExit(f"--self-ensemble: {refused}") from None
+    return {"self_ensemble": args.self_ensemble, "self_ensemble_spread": args.self_ensemble_spread}
+
+
 def ensemble_keywords(args):
     """the VarAEModel.apply keywords the command line asks for (empty: the plain apply).  They need a VarAEModel folder:
     parameters.json is read here, before any rank is spawned or the GPU touched, and anything else is refused."""
@@ -119,6 +151,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     ensemble = ensemble_keywords(args)
     ensemble.update(interval_keywords(args))
+    ensemble.update(self_ensemble_keywords(args))
     novelty = novelty_keywords(args)
     if "interval" in ensemble and "ensemble_size" in ensemble:
         raise SystemExit("--interval needs the plain prediction the model was calibrated with: leave --ensemble-size out")

@@ -6,7 +6,8 @@ implemented; the other method names are accepted by the parser, as in the refere
 (the reference itself constructs no model for vae/unet_res/srcnn_res/resunet_gan: SURVEY.md fact 3).
 Build-only flags: --gpus N (data-parallel ConvAE training over N GPUs of this node, one process per GPU) and --local-bn;
 --residual-variable NAME / --residual-mode MODE train any of the four on the residual over the interpolated input
-(DESIGN.md §9 'Residual target': the idea behind the reference's unet_res / srcnn_res names).
+(DESIGN.md §9 'Residual target': the idea behind the reference's unet_res / srcnn_res names); --augment {flips,dihedral} /
+--augment-seed S turn every training case by a symmetry of the square before every epoch (DESIGN.md §9 'Dihedral augmentation').
 """
 import argparse
 import json
@@ -17,6 +18,7 @@ import numpy as np
 
 from ..data.arrays import DataArray, open_mfdataset
 from ..lr_schedule import check_scheduler_type
+from ..utils.augment import GROUPS as AUGMENT_GROUPS
 from ..utils.baseline import MODES as RESIDUAL_MODES
 from ..models.conv_ae_model import ConvAEModel
 from ..models.unet import UNET
@@ -81,7 +83,31 @@ def build_cli_parser():
                         "when the model is applied (default with --residual-mode alone: the first input variable)")
     p.add_argument("--residual-mode", choices=list(RESIDUAL_MODES), default=None,
                    help="interpolation of the residual variable (default: bicubic)")
+    p.add_argument("--augment", choices=list(AUGMENT_GROUPS), default=None,
+                   help="turn every training case before every epoch: by the two flips and the half turn (flips), or by all eight "
+                        "symmetries of the square (dihedral: square planes only).  Default: off; with --continue-training, what the "
+                        "model folder was trained with")
+    p.add_argument("--augment-seed", type=_augment_seed, default=None, metavar="S",
+                   help="seed of the augmentation's codes (default: 0; with --continue-training, the model folder's)")
     return p
+
+
+def _augment_seed(text):
+    value = int(text)
+    if not 0 <= value < 1 << 64:
+        raise argparse.ArgumentTypeError("a seed from 0 to 2^64 - 1 expected")
+    return value
+
+
+def augment_keywords(args):
+    """the train() keywords of --augment / --augment-seed: a flag that was not given is left out, so that a continued model
+    keeps its folder's value and a fresh one its default (off, seed 0)"""
+    keywords = {}
+    if args.augment is not None:
+        keywords["augment"] = args.augment
+    if args.augment_seed is not None:
+        keywords["augment_seed"] = args.augment_seed
+    return keywords
 
 
 def residual_settings(args, folder_parameters=None):
@@ -192,7 +218,7 @@ def main(argv=None):
     print("Ready for training process")
     mt.train(args.input_variables, args.output_variable, training_ds=train_ds, testing_ds=test_ds,
              model_path=args.model_folder, training_paths=training_paths, testing_paths=test_paths,
-             mask_variable_name=args.mask_variable)
+             mask_variable_name=args.mask_variable, **augment_keywords(args))
     print(f"Time taken to train: {time.time() - start_time:.2f} seconds")
 
 

@@ -27,6 +27,7 @@
 #include "kernels_quantile.h"    // likewise, after kernels_importance.h
 #include "kernels_neighbours.h"  // likewise, after kernels_quantile.h
 #include "kernels_compare.h"     // likewise, after kernels_neighbours.h
+#include "kernels_dihedral.h"    // likewise, after kernels_compare.h
 #include "kernels_s2.h"
 #include "kernels_last.h"
 #include "kernels_rows.h"
@@ -1039,5 +1040,6 @@ int trunk_adam_from(cae_engine* e, const float* grads) {
 
 // Where .text starts in this code object decides the training step's time (model comparison, "cost to the
 // training step"): the tables in front of it grew with the comparison's kernels and moved it from 0x300 to 0xf00 past a 4 KiB
-// boundary, which cost the step 0.8 us of 160.4; these 1 KiB of constants put it back at 0x300.
-namespace cae { __device__ __attribute__((used)) const unsigned char k_layout_pad[0x400] = {1}; }
+// boundary, which cost the step 0.8 us of 160.4; 1 KiB of constants put it back at 0x300.  k_dihedral_rows' descriptor and
+// metadata moved it on by 0x500, to 0x800 past the boundary: 0xb00 more bytes of constants, and it stands at 0x300 again.
+namespace cae { __device__ __attribute__((used)) const unsigned char k_layout_pad[0xf00] = {1}; }

@@ -23,6 +23,17 @@ from .model_sizer import ModelSpec, create_model_spec
 
 _IMPORTANCE_BYTES = 256 << 20       # of fp32 inputs and scores per piece of cases of importance()
 _NOVELTY_BYTES = 1 << 30            # of packed reference rows per cae_case_neighbours call of novelty()
+_SELF_ENSEMBLE_BYTES = 256 << 20    # of fp32 turned inputs and scores per piece of cases of apply(self_ensemble=...)
+
+
+class _Keep:
+    """the default of train()'s augment keywords: the model's own value stays"""
+
+    def __repr__(self):
+        return "KEEP"
+
+
+KEEP = _Keep()
 
 
 def _make_data_array(like_ds, data, dims):
@@ -197,20 +208,86 @@ class BaseModel:
     def apply(self, score_ds, input_variables, prediction_variable="model_output",
               channel_dimension="model_output_channel", y_dimension="model_output_y",
               x_dimension="model_output_x", mask_variable_name=None, interval=None, interval_variables=None,
-              scale_variable=None, **vae_only):
+              scale_variable=None, self_ensemble=None, self_ensemble_spread=None, case_chunk=None, **vae_only):
         """Add `prediction_variable` (float64, denormalised, dims (case, channel, y, x)) to score_ds
-        in place (:102-152).  interval=L (build-only; DESIGN.md §9 'prediction intervals'): a coverage level the model
+        in place (:102-152).  self_ensemble="flips" | "dihedral" (build-only; DESIGN.md §9 'Dihedral augmentation'): the
+        geometric self-ensemble - every case is scored in the 4 or 8 orientations of the group, the scores are turned back
+        and `prediction_variable` receives their per-pixel mean, `self_ensemble_spread` (a variable name) their sample
+        standard deviation (same dimensions, float64, denormalised: cae_ensemble_moments).  The cases go through in pieces of
+        case_chunk (None: a byte budget); the result does not depend on it.  Refused for a residual model, beside interval
+        (the calibration holds for the plain prediction) and beside ensemble_size.  interval=L (build-only; DESIGN.md §9 'prediction intervals'): a coverage level the model
         folder was calibrated for (calibrate()), as its decimal text or a Fraction; channel 0 of the prediction then gets the
         bounds prediction -+ q (times score_ds[scale_variable] where the calibration used a scale) as two more float64
         variables (case, y, x), named interval_variables or <prediction_variable>_lower / _upper.  Without interval nothing
         changes, bit for bit."""
+        self._check_self_ensemble(self_ensemble, self_ensemble_spread, case_chunk, interval, vae_only.get("ensemble_size"))
         if vae_only:    # ensemble_size / spread_variable / ensemble_seed / latent_variable: VarAEModel.apply's own keywords
             raise TypeError(f"{type(self).__name__}.apply() got {sorted(vae_only)}: only VarAEModel (the VAE, --method var) has a "
                             "stochastic latent to draw an ensemble from")
         request = self._interval_request(interval, interval_variables, scale_variable, prediction_variable)
+        if self_ensemble is not None:
+            (mean, std) = self._self_ensemble_device(score_ds, input_variables, self_ensemble, self_ensemble_spread is not None,
+                                                     case_chunk, mask_variable_name)
+            dims = (score_ds[input_variables[0]].dims[0], channel_dimension, y_dimension, x_dimension)
+            score_ds[prediction_variable] = _make_data_array(score_ds, mean.cpu().numpy(), dims)
+            if std is not None:
+                score_ds[self_ensemble_spread] = _make_data_array(score_ds, std.cpu().numpy(), dims)
+            return
         out = self.apply_device(score_ds, input_variables, prediction_variable, channel_dimension, y_dimension, x_dimension,
                                 mask_variable_name)
         self._store_interval(score_ds, out, request, score_ds[input_variables[0]].dims[0], y_dimension, x_dimension)
+
+    def _check_self_ensemble(self, self_ensemble, spread, case_chunk, interval, ensemble_size):
+        """the refusals of apply(self_ensemble=...), all before the GPU is touched"""
+        from ..utils import augment as _aug
+        if self_ensemble is None:
+            if spread is not None:
+                raise ValueError("self_ensemble_spread needs self_ensemble='flips' or 'dihedral'")
+            return
+        _aug.check_group(self_ensemble, "self_ensemble")
+        self._refuse_residual("apply(self_ensemble=...)")
+        if interval is not None:
+            raise ValueError("interval needs the plain prediction the model was calibrated with: leave self_ensemble out")
+        if ensemble_size is not None:
+            raise ValueError("self_ensemble and ensemble_size are two ensembles: ask for one of them")
+        _aug.check_square(self_ensemble, [s for s in (self.input_shape, self.output_shape) if s is not None], "self_ensemble")
+        if case_chunk is not None and (int(case_chunk) != case_chunk or int(case_chunk) < 1):
+            raise ValueError(f"case_chunk must be an integer of at least 1, got {case_chunk!r}")
+
+    def _self_ensemble_device(self, score_ds, input_variables, self_ensemble, want_std, case_chunk=None, mask_variable_name=None):
+        """(mean, std or None) of the geometric self-ensemble: float64 CUDA tensors (N, C, H, W).  A piece of g cases becomes
+        K x g rows [draw][case], draw k the piece turned by code k (case_ops.dihedral_rows gathers and turns in one pass), is
+        scored through _score_all, turned back by the inverse codes and reduced per pixel by cae_ensemble_moments."""
+        from .. import dp as _dp
+        from ..case_ops import dihedral_rows, ensemble_moments
+        from ..utils import augment as _aug
+        _dp.ensure_process_group()
+        ds = self._model_dataset(score_ds, input_variables, input_variables[0], normalise_in=self.normalise_input,
+                                 mask_variable_name=mask_variable_name)
+        x = ds.device_inputs()
+        (n, device) = (int(x.shape[0]), x.device)
+        k = _aug.GROUPS[self_ensemble]
+        out_shape = tuple(int(v) for v in self.output_shape)
+        per_case = 4 * k * (int(np.prod(x.shape[1:])) + 2 * int(np.prod(out_shape)))
+        chunk = max(1, min(max(n, 1), _SELF_ENSEMBLE_BYTES // per_case)) if case_chunk is None else int(case_chunk)
+        mean = torch.empty((n,) + out_shape, dtype=torch.float64, device=device)
+        std = torch.empty_like(mean) if want_std else None
+        forward = np.arange(k, dtype=np.int32)
+        for c0 in range(0, n, chunk):
+            g = min(n, c0 + chunk) - c0
+            rows = torch.from_numpy(np.tile(np.arange(c0, c0 + g, dtype=np.int32), k)).to(device)
+            turn = torch.from_numpy(np.repeat(forward, g)).to(device)
+            back = torch.from_numpy(np.repeat(_aug.inverse_code(forward), g)).to(device)
+            xk = torch.empty((k * g,) + tuple(x.shape[1:]), dtype=torch.float32, device=device)
+            dihedral_rows(x, xk, turn, rows=rows, group=k)
+            y = self._score_all(xk).contiguous()
+            yb = torch.empty_like(y)
+            dihedral_rows(y, yb, back, group=k)
+            (m, s) = ensemble_moments(yb.view((k, g) + out_shape), ds.min_output, ds.max_output, want_std=want_std)
+            mean[c0:c0 + g] = m
+            if want_std:
+                std[c0:c0 + g] = s
+        return mean, std
 
     def apply_device(self, score_ds, input_variables, prediction_variable="model_output",
                      channel_dimension="model_output_channel", y_dimension="model_output_y",
@@ -531,6 +608,7 @@ class EngineModel(BaseModel):
     RESIDUAL_KEYS = ("residual_variable", "residual_mode", "residual_min", "residual_max")     # absent: no residual target
     OPTIONAL_PARAM_KEYS = ("conv_kernel_size", "conv_stride", "conv_input_layer_count", "conv_output_layer_count") + RESIDUAL_KEYS
     SCHEDULE_KEYS = ("scheduler_type", "lr_step_size", "lr_gamma")     # in parameters.json only when a scheduler is set
+    AUGMENT_KEYS = ("augment", "augment_seed")      # in parameters.json only when the model was trained with augmentation
 
     # ---- where train() differs between the model classes --------------------------------------
     DATA_PARALLEL = True        # trains one rank per GPU under a torch.distributed.run launch (LinearModel: no such path)
@@ -541,6 +619,12 @@ class EngineModel(BaseModel):
     INTERRUPTIBLE = False       # Ctrl-C ends the epoch loop and the model is still saved (UNET, as the reference's)
 
     timing = None       # set by train(): seconds and images of the epoch loop, and the world size (build-only attribute)
+    # ---- augmentation (build-only; DESIGN.md §9 'Dihedral augmentation') ------------------------
+    # augment: None, "flips" or "dihedral": what the last train() turned the training cases with, which a model folder
+    # keeps and the next train() on the loaded model takes as its default.  augment_seed: the seed of the codes.
+    augment = None
+    augment_seed = 0
+    _augmenter = None   # the TrainAugmenter of the last train() with augmentation (its buffers are what the engine reads)
     _lead = True        # this process prints (rank 0 of a data-parallel run)
 
     # ---- learning-rate schedule ------------------------------------------------------------
@@ -560,6 +644,26 @@ class EngineModel(BaseModel):
         """a fresh schedule starting at self.lr, as the optimiser is fresh on every train()"""
         schedule = _lrs.make_schedule(self.scheduler_type, self.lr, self.lr_step_size, self.lr_gamma)
         return _ScheduledRate(schedule, eng, self.history, par)
+
+    def _augment_parameters(self):
+        """what get_parameters() adds: nothing without augmentation (parameters.json is then what it always was)"""
+        if self.augment is None:
+            return {}
+        return {"augment": self.augment, "augment_seed": self.augment_seed}
+
+    def _set_augment(self, augment, augment_seed, shapes):
+        """train()'s two keywords onto the model, checked before the GPU is touched: a keyword left at KEEP keeps the model's
+        own value (a fresh model: off, seed 0; a loaded one: its folder's).  shapes: those of the input and output planes, or a
+        function that returns them, called only with augmentation on: without it the data sets are not looked at here."""
+        from ..utils import augment as _aug
+        if augment is not KEEP:
+            if augment is not None:
+                _aug.check_group(augment)
+            self.augment = augment
+        if augment_seed is not KEEP:
+            self.augment_seed = _aug.check_seed(augment_seed)
+        if self.augment is not None:
+            _aug.check_square(self.augment, shapes() if callable(shapes) else shapes)
 
     def _modules(self):
         """fresh host weight containers for the current spec / shapes"""
@@ -656,6 +760,7 @@ class EngineModel(BaseModel):
         for key in self.SCHEDULE_KEYS:
             if key in p:
                 setattr(self, key, p[key])
+        (self.augment, self.augment_seed) = (p.get("augment"), p.get("augment_seed", 0))
         with open(os.path.join(from_folder, "history.json")) as f:
             self.history = json.loads(f.read())
         self._load_modules(from_folder)
@@ -706,9 +811,11 @@ class EngineModel(BaseModel):
         """the keywords of the engine's set_hyper"""
         return {"lr": self.lr, "weight_decay": self.weight_decay}
 
-    def _bind_data(self, eng, train_ds, test_ds, train_perm, test_perm):
-        """both data sets bound to the engine: the device index of each frozen shuffle, (train, test)"""
-        eng.set_dataset(TRAIN, train_ds.device_inputs(), train_ds.device_outputs())
+    def _bind_data(self, eng, train_ds, test_ds, train_perm, test_perm, augmenter=None):
+        """both data sets bound to the engine: the device index of each frozen shuffle, (train, test).  augmenter: the
+        training set's packed arrays stay pristine and the engine is bound to the augmenter's buffers instead."""
+        train = (train_ds.device_inputs(), train_ds.device_outputs())
+        eng.set_dataset(TRAIN, *(train if augmenter is None else augmenter.bind(train)))
         eng.set_dataset(TEST, test_ds.device_inputs(), test_ds.device_outputs())
         return eng.upload_perm(train_perm), eng.upload_perm(test_perm)
 
@@ -718,16 +825,30 @@ class EngineModel(BaseModel):
         print("%5d %.6f %.6f" % (epoch, _mean_loss(train_losses, column), _mean_loss(test_losses, column)))
 
     def train(self, input_variables, output_variable, training_ds, testing_ds, model_path="", training_paths="",
-              testing_paths="", mask_variable_name=None):
+              testing_paths="", mask_variable_name=None, augment=KEEP, augment_seed=KEEP):
         """Train (or continue training): see the reference docstring (conv_ae_model.py:241-252).  Data flow: both data sets
         are scanned / normalised / packed on the GPU once, the shuffle is frozen once (:315-325), and every epoch is one
         run_batches per pass plus one loss read-back.
+
+        augment="flips" | "dihedral" (build-only; DESIGN.md §9 'Dihedral augmentation'): before every training pass each
+        training case - input, target and loss mask alike - is turned by one of the 4 or 8 symmetries of the square, the code
+        of case j in epoch e being utils/augment.codes(augment_seed, e, n, group)[j] with e counted over all train() calls of
+        the model (history["nr_epochs"] + epoch).  The packed training set stays pristine and the engine reads buffers that
+        one kernel rewrites between epochs (cae_dihedral_rows), at the cost of one device synchronisation per epoch.  The
+        test set is never turned.  "dihedral" needs square input and output planes.  None: off, and nothing changes, bit for
+        bit.  Left out, both keywords keep the model's own values: off for a fresh model, the folder's for a loaded one.
 
         Data parallel (build-only; the reference selects ONE device at :294-297): under a torch.distributed.run launch every
         rank holds the model and both data sets and takes its rows of each frozen GLOBAL batch (dp.shard_bounds); gradients,
         and with sync_bn the BatchNorm and loss tables, are summed over the ranks, so that a step is the single-device step
         at batch_size.  Rank 0 prints and saves."""
         from .. import dp as _dp
+        self._set_augment(augment, augment_seed, lambda: [training_ds[input_variables[0]].shape, training_ds[output_variable].shape])
+        self._augmenter = None
+        if self.augment is not None:
+            from ._augmenter import TrainAugmenter
+            self._augmenter = TrainAugmenter(self.augment, self.augment_seed)
+        augmenter = self._augmenter
         # a rank works on ITS GPU from the first allocation on (the data sets below are uploaded to the current device, the
         # engine is created on it)
         dist = _dp.ensure_process_group() if self.DATA_PARALLEL else None
@@ -746,7 +867,10 @@ class EngineModel(BaseModel):
         eng = self._get_engine(-(-int(self.batch_size) // world))   # a rank's share of a global batch
         eng.set_hyper(**self._hyper())
         eng.reset_optimizer()       # the reference re-creates its optimiser on every train() (:310)
-        (train_idx, test_idx) = self._bind_data(eng, train_ds, test_ds, train_perm, test_perm)
+        if augmenter is None:
+            (train_idx, test_idx) = self._bind_data(eng, train_ds, test_ds, train_perm, test_perm)
+        else:
+            (train_idx, test_idx) = self._bind_data(eng, train_ds, test_ds, train_perm, test_perm, augmenter=augmenter)
         par = None
         if dist is not None:
             par = _dp.data_parallel(eng, dist, sync_bn=self.sync_bn)
@@ -771,6 +895,8 @@ class EngineModel(BaseModel):
             for epoch in range(self.nr_epochs):
                 epoch_start = time.time()
                 epoch_lr = rate.current
+                if augmenter is not None:       # the epoch counts over all train() calls: a continued model continues the stream
+                    augmenter.rewrite(self.history["nr_epochs"] + epoch)
                 train_losses = one_pass(TRAIN, train_idx, train_ds, True)
                 rate.after_train_pass()     # where the reference steps its scheduler (unet.py:485-487); one tiny launch
                 self._progress(f"time used for training one epoch: {time.time() - epoch_start:.2f}")

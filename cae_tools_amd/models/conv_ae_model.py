@@ -81,6 +81,7 @@ class ConvAEModel(EngineModel):
             "model_id": self.get_model_id(),
             **self._schedule_parameters(),
             **self._residual_parameters(),
+            **self._augment_parameters(),
         }
 
     def _modules(self):
@@ -97,13 +98,18 @@ class ConvAEModel(EngineModel):
         return _eng.HipEngine(self.spec, self.fc_size, self.encoded_dim_size, max_batch=max_batch)
 
     # ---- training --------------------------------------------------------------------------
-    def _bind_data(self, eng, train_ds, test_ds, train_perm, test_perm):
+    def _bind_data(self, eng, train_ds, test_ds, train_perm, test_perm, augmenter=None):
         # The reference stacks its shuffled batches ONCE and reuses that list every epoch (:315-325).  The same here: both data
         # sets are laid out in batch order once - by the normalisation kernel itself, which writes every sample to its row of
         # the frozen order (DSDataset.device_batches -> cae_normalise_pack_rows) - so a batch is a contiguous run of rows and
         # the kernels need no permutation look-up in front of their first load (one dependent memory round trip less per
         # gathering kernel: the encoder's head, the last layer's targets, the first conv's weight gradient).
-        eng.set_dataset(_eng.TRAIN, *train_ds.device_batches(train_perm))
+        # With augmentation the rows are gathered in that order from the packed arrays instead, turned on the way
+        # (TrainAugmenter: row i of its buffers is case train_perm[i]), before every training pass.
+        if augmenter is None:
+            eng.set_dataset(_eng.TRAIN, *train_ds.device_batches(train_perm))
+        else:
+            eng.set_dataset(_eng.TRAIN, *augmenter.bind((train_ds.device_inputs(), train_ds.device_outputs()), order=train_perm))
         eng.set_dataset(_eng.TEST, *test_ds.device_batches(test_perm))
         return None, None
 

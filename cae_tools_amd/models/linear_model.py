@@ -42,7 +42,8 @@ class LinearModel(EngineModel):
         return {"model_id": self.get_model_id(), "type": "LinearModel", "input_shape": list(self.input_shape),
                 "output_shape": list(self.output_shape), "batch_size": self.batch_size, "test_interval": self.test_interval,
                 "lr": self.lr, "weight_decay": self.weight_decay, "normalise_input": self.normalise_input,
-                "normalise_output": self.normalise_output, **self._schedule_parameters(), **self._residual_parameters()}
+                "normalise_output": self.normalise_output, **self._schedule_parameters(), **self._residual_parameters(),
+                **self._augment_parameters()}
 
     def summary(self):
         if not self.input_shape:

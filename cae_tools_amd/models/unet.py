@@ -206,6 +206,7 @@ class UNET(EngineModel):
             "model_id": self.get_model_id(),
             **self._schedule_parameters(),
             **self._residual_parameters(),
+            **self._augment_parameters(),
         }
 
     def summary(self):
@@ -233,11 +234,14 @@ class UNET(EngineModel):
         return {"lr": self.lr, "weight_decay": self.weight_decay, "dropout_rate": self.dropout_rate,
                 "lambda_pearson": self.lambda_pearson, "seed": self.dropout_seed}
 
-    def _bind_data(self, eng, train_ds, test_ds, train_perm, test_perm):
+    def _bind_data(self, eng, train_ds, test_ds, train_perm, test_perm, augmenter=None):
         eng.set_step(0)
         t0 = time.time()
         for (which, ds) in ((_ue.TRAIN, train_ds), (_ue.TEST, test_ds)):
-            eng.set_dataset(which, ds.device_inputs(), ds.device_outputs(), self._loss_mask(ds))
+            arrays = (ds.device_inputs(), ds.device_outputs(), self._loss_mask(ds))
+            if augmenter is not None and which == _ue.TRAIN:    # the loss mask of a case is turned with its input and target
+                arrays = augmenter.bind(arrays)
+            eng.set_dataset(which, *arrays)
         idx = (eng.upload_perm(train_perm), eng.upload_perm(test_perm))
         self._progress(f"finished batching in {time.time() - t0:.2f} seconds")
         return idx

@@ -94,7 +94,7 @@ class VarAEModel(EngineModel):
                 "normalise_output": self.normalise_output, "conv_kernel_size": self.conv_kernel_size,
                 "conv_stride": self.conv_stride, "conv_input_layer_count": self.conv_input_layer_count,
                 "conv_output_layer_count": self.conv_output_layer_count, "model_id": self.get_model_id(),
-                **self._schedule_parameters(), **self._residual_parameters()}
+                **self._schedule_parameters(), **self._residual_parameters(), **self._augment_parameters()}
 
     def summary(self):
         if not self.spec:
@@ -152,14 +152,22 @@ class VarAEModel(EngineModel):
     def apply(self, score_ds, input_variables, prediction_variable="model_output", channel_dimension="model_output_channel",
               y_dimension="model_output_y", x_dimension="model_output_x", mask_variable_name=None, ensemble_size=None,
               spread_variable=None, ensemble_seed=0, latent_variable=None, interval=None, interval_variables=None,
-              scale_variable=None):
-        """BaseModel.apply, and with ensemble_size=K the model's own spread: every case is encoded once, K latents
+              scale_variable=None, self_ensemble=None, self_ensemble_spread=None, case_chunk=None):
+        """BaseModel.apply (self_ensemble, self_ensemble_spread and case_chunk as it takes them: the geometric self-ensemble of
+        the z = mu prediction, refused beside ensemble_size), and with ensemble_size=K the model's own spread: every case is encoded once, K latents
         z_k = mu + eps_k * exp(logvar / 2) are decoded (eps_k: the noise of (ensemble_seed, draw k, global case index)), and
         `prediction_variable` receives the per-pixel mean of the K fields, `spread_variable` (K >= 2) their sample standard
         deviation (same dimensions, float64, denormalised).  latent_variable=NAME stores NAME_mu and NAME_logvar, float32
         (case, "model_latent").  With none of the four keywords this is BaseModel.apply (z = mu), bit for bit.  interval,
         interval_variables and scale_variable as BaseModel.apply takes them; the calibrated scores are those of z = mu, so an
         interval is refused beside ensemble_size."""
+        self._check_self_ensemble(self_ensemble, self_ensemble_spread, case_chunk, interval, ensemble_size)
+        if self_ensemble is not None:
+            if spread_variable is not None or latent_variable is not None:
+                raise ValueError("spread_variable and latent_variable belong to the latent ensemble: leave self_ensemble out")
+            return super().apply(score_ds, input_variables, prediction_variable, channel_dimension, y_dimension, x_dimension,
+                                 mask_variable_name, self_ensemble=self_ensemble, self_ensemble_spread=self_ensemble_spread,
+                                 case_chunk=case_chunk)
         if ensemble_size is not None:
             self._refuse_residual("apply(ensemble_size=...)")
         if interval is not None and ensemble_size is not None:

@@ -986,6 +986,24 @@ int cae_case_compare(const void* const* pred_ptrs /* host array of n_pred device
 int cae_bootstrap_sums(const double* table_dev, int64_t n_unit, int n_col, int64_t first_resample, int64_t n_resample,
                        uint64_t seed, double* out_dev /* [n_resample][n_col] */, void* hip_stream);
 
+/* ---- the symmetries of the square on packed rows (stateless): augmentation, self-ensemble ------ */
+
+/* dst[i] = g(code[i]) applied to src[row[i]] for i < n_dst and every channel: src_dev (n_src, c, h, w) and dst_dev (n_dst, c, h,
+ * w), moved as 32-bit words.  No arithmetic touches a value: NaN payloads and -0 arrive as they were.  A code is three bits,
+ *   bit 2: transpose          bit 1: reverse the rows          bit 0: reverse the columns
+ * applied in that order; in numpy, on the last two axes: swapaxes(-1, -2) if bit 2, then [..., ::-1, :] if bit 1, then
+ * [..., ::-1] if bit 0.  Codes 0 .. 3 are the identity, the two flips and the half turn; 4 .. 7 the two transposes and the two
+ * quarter turns.  The inverse of a code keeps bit 2 and swaps bits 0 and 1 where bit 2 is set: 5 and 6 undo each other, every
+ * other code undoes itself.  group is 4 (codes 0 .. 3, any plane) or 8 (all codes, h == w).  row_dev: n_dst int32 on the
+ * device in any order, repeats allowed, or NULL for row i; code_dev: n_dst int32 on the device.  The host cannot see either,
+ * so the kernel checks each: a row index outside 0 .. n_src - 1 is not followed and a code outside 0 .. group - 1 is not
+ * applied, and that row of dst gets quiet NaNs (0x7fc00000).  One launch, no workspace, no atomics.
+ * n_dst == 0, h == 0 or w == 0 succeeds and writes nothing.  Negative sizes, c < 1, a group other than 4 or 8, group 8 with
+ * h != w, more than 2^31 - 1 rows, NULL or misaligned pointers, an operand reaching 2^60 elements, dst overlapping src:
+ * CAE_ERR_ARG, nothing written. */
+int cae_dihedral_rows(const float* src_dev, int64_t n_src, int c, int h, int w, float* dst_dev, int64_t n_dst,
+                      const int32_t* row_dev /* NULL: row i */, const int32_t* code_dev, int group /* 4 or 8 */, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
