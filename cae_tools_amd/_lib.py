@@ -166,6 +166,9 @@ SIGNATURES = {
     "cae_case_compare": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
     "cae_bootstrap_sums": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_uint64, _P, _P]),
     "cae_dihedral_rows": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P, C.c_int, _P]),
+    "cae_case_error_moments_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
+    "cae_case_error_moments": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
+    "cae_blend_predictions": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_double, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
     # ---- include/cae_unet.h ----
     "unet_engine_create": (C.c_int, [C.POINTER(LayerSpecC), C.c_int, C.POINTER(LayerSpecC), C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.POINTER(C.c_void_p)]),

@@ -1,6 +1,7 @@
 """The case kernels of libcae_hip (include/cae_hip.h) as functions, no engine needed: measures, per-pixel sums, spectra, SSIM,
 interpolation baseline, value distributions, skill by stratum, neighbourhood skill, permutation importance, prediction
-intervals, novelty against a reference set, model comparison and its bootstrap, ensemble verification, value range and rendered pages of channel 0 of (N, C, H, W) operands."""
+intervals, novelty against a reference set, model comparison and its bootstrap, the error moments of a blend of models, ensemble
+verification, value range and rendered pages of channel 0 of (N, C, H, W) operands; and the blended field over all channels."""
 import ctypes as C
 import math
 from contextlib import contextmanager
@@ -557,6 +558,97 @@ def _as_f64(op):
     return DeviceOperand(t, _lib.ELEM_F64, tuple(t.shape), int(t.stride(0)))
 
 
+def _all_as_f64(op):
+    """every channel of a device operand as a native fp64 operand of the same shape, converted on the device: exact for every kind"""
+    if op.kind == _lib.ELEM_F64:
+        return op
+    if op.kind == _lib.ELEM_F32:
+        t = op.tensor.to(torch.float64)
+    else:       # a big-endian slab: its raw bytes, swapped as integers
+        wide = op.elem_bytes
+        raw = op.tensor.view(-1, wide).flip(1).contiguous()
+        t = raw.view(torch.float32 if wide == 4 else torch.float64).reshape(op.shape).to(torch.float64)
+    t = t.contiguous()
+    return DeviceOperand(t, _lib.ELEM_F64, tuple(t.shape), int(np.prod(t.shape[1:])))
+
+
+def moments_width(m):
+    """the width of a row of case_error_moments for m candidates: n, m sums of errors, m (m + 1) / 2 sums of products"""
+    return 1 + m + m * (m + 1) // 2
+
+
+def case_error_moments(preds, actual, device=None):
+    """The error moments a blend of up to 8 predictions is fitted from (cae_case_error_moments, include/cae_hip.h): an (N, 1 + M +
+    M (M + 1) / 2) float64 numpy array {n, S e_0 .. S e_{M-1}, S e_i e_j for i <= j in row-major order} per case of channel 0,
+    with e_m = P_m - a in fp64 over the pixels where the target and every prediction are finite.  n, S e_m and S e_m^2 carry the
+    bits of case_compare's columns 0, 2 + 4 m and 4 + 4 m.  preds and actual as case_compare takes them: predictions of mixed
+    kinds are converted to native fp64 on the device, which changes no value; the cases go in chunks that bound the workspace,
+    and a case's row does not depend on the cut.  utils/blend.fit turns the sums into weights."""
+    preds = list(preds)
+    if not 1 <= len(preds) <= 8:
+        raise ValueError(f"case_error_moments: 1 to 8 predictions expected, got {len(preds)}")
+    (device, ops) = device_operands(preds + [actual], device)
+    (ps, a) = (ops[:-1], ops[-1])
+    for p in ps:
+        if len(p.shape) != 4 or len(a.shape) != 4:
+            raise ValueError(f"case_error_moments: (N, C, H, W) arrays expected, got {p.shape} and {a.shape}")
+        if p.shape[0] != a.shape[0] or p.shape[2:] != a.shape[2:]:
+            raise ValueError(f"case_error_moments: prediction {p.shape} and target {a.shape} do not match")
+    (n, h, w, m) = (int(a.shape[0]), int(a.shape[2]), int(a.shape[3]), len(ps))
+    (plane, width) = (h * w, moments_width(m))
+    if n == 0 or plane == 0:
+        return np.zeros((n, width), dtype=np.float64)
+    if len({p.kind for p in ps}) > 1:
+        ps = [p if p.kind == _lib.ELEM_F64 else _as_f64(p) for p in ps]
+    lib = _lib.load()
+    group = max(1, min(n, _COMPARE_BYTES // int(lib.cae_case_error_moments_workspace_bytes(1, plane, m))))
+    sums = torch.empty((n, width), dtype=torch.float64, device=device)
+    (ws, need) = _workspace(device, lib.cae_case_error_moments_workspace_bytes, group, plane, m, least=16)
+    strides = (C.c_int64 * m)(*[p.stride for p in ps])
+    with _stream(device) as stream:
+        for c0 in range(0, n, group):
+            g = min(n, c0 + group) - c0
+            ptrs = (C.c_void_p * m)(*[p.args(c0)[0] for p in ps])
+            check(lib.cae_case_error_moments(ptrs, ps[0].kind, strides, m, *a.args(c0), g, plane, sums[c0:].data_ptr(), ws.data_ptr(),
+                                             need, stream))
+        return sums.cpu().numpy()
+
+
+def blend_predictions(preds, weights, intercept=0.0, device=None):
+    """The blended field of up to 8 predictions (cae_blend_predictions, include/cae_hip.h): the (N, C, H, W) float64 numpy array
+    y = intercept, then y = y + weights[m] * preds[m] for m ascending over the weights that are not 0, product and sum rounded
+    separately in fp64; NaN where a prediction with a weight other than 0 is not finite.  A prediction whose weight is exactly 0
+    is not read.  preds: (N, C, H, W) operands of one shape as case_compare takes them; where their kinds differ those that
+    are not native fp64 are converted to it on the device, which changes no value.  One streaming launch."""
+    preds = list(preds)
+    if not 1 <= len(preds) <= 8:
+        raise ValueError(f"blend_predictions: 1 to 8 predictions expected, got {len(preds)}")
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape[0] != len(preds):
+        raise ValueError(f"blend_predictions: one weight per prediction expected, got {w.shape[0]} for {len(preds)}")
+    intercept = float(intercept)
+    if not (np.isfinite(w).all() and math.isfinite(intercept)):
+        raise ValueError("blend_predictions: the weights and the intercept must be finite")
+    (device, ps) = device_operands(preds, device)
+    for p in ps:
+        if len(p.shape) != 4 or tuple(p.shape) != tuple(ps[0].shape):
+            raise ValueError(f"blend_predictions: (N, C, H, W) predictions of one shape expected, got {ps[0].shape} and {p.shape}")
+    shape = tuple(int(v) for v in ps[0].shape)
+    (n, per, m) = (shape[0], shape[1] * shape[2] * shape[3], len(ps))
+    if n == 0 or per == 0:
+        return np.zeros(shape, dtype=np.float64)
+    if len({p.kind for p in ps}) > 1:
+        ps = [_all_as_f64(p) for p in ps]
+    lib = _lib.load()
+    out = torch.empty(shape, dtype=torch.float64, device=device)
+    strides = (C.c_int64 * m)(*[p.stride for p in ps])
+    ptrs = (C.c_void_p * m)(*[p.args()[0] for p in ps])
+    with _stream(device) as stream:
+        check(lib.cae_blend_predictions(ptrs, ps[0].kind, strides, m, (C.c_double * m)(*w.tolist()), intercept, n, per,
+                                        out.data_ptr(), per, stream))
+        return out.cpu().numpy()
+
+
 def bootstrap_sums(table, resamples, seed=0, first=0, device=None):
     """The paired bootstrap of a table of per-unit sums on the device (cae_bootstrap_sums, include/cae_hip.h): table (n_unit,
     n_col) float64 with 1 <= n_col <= 32 and 1 <= n_unit <= 2^20; returns the (resamples, n_col) float64 numpy array whose row k
@@ -582,6 +674,21 @@ def bootstrap_sums(table, resamples, seed=0, first=0, device=None):
         t = torch.from_numpy(table).to(device)
         check(lib.cae_bootstrap_sums(t.data_ptr(), n_unit, n_col, first, b, seed, out.data_ptr(), stream))
         return out.cpu().numpy()
+
+
+_BOOTSTRAP_COLUMNS = 32             # of a table cae_bootstrap_sums takes
+_BOOTSTRAP_RESAMPLES = 1 << 18      # resamples per cae_bootstrap_sums call
+
+
+def bootstrap_table(table, resamples, seed, device=None):
+    """cae_bootstrap_sums of a table of any width: column pieces of at most 32 with the same seed - the units of a resample
+    depend on (seed, resample, n_unit) alone, so the pieces are resampled alike - and resamples in consecutive pieces"""
+    pieces = []
+    for c0 in range(0, table.shape[1], _BOOTSTRAP_COLUMNS):
+        part = np.ascontiguousarray(table[:, c0:c0 + _BOOTSTRAP_COLUMNS])
+        pieces.append(np.concatenate([bootstrap_sums(part, min(_BOOTSTRAP_RESAMPLES, resamples - r0), seed=seed, first=r0, device=device)
+                                      for r0 in range(0, resamples, _BOOTSTRAP_RESAMPLES)]))
+    return np.concatenate(pieces, axis=1)
 
 
 def _score_operands(name, pred, actual, scale, device):

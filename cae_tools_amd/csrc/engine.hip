@@ -28,6 +28,7 @@
 #include "kernels_neighbours.h"  // likewise, after kernels_quantile.h
 #include "kernels_compare.h"     // likewise, after kernels_neighbours.h
 #include "kernels_dihedral.h"    // likewise, after kernels_compare.h
+#include "kernels_blend.h"       // likewise, after kernels_dihedral.h: it uses kernels_compare.h's tiles
 #include "kernels_s2.h"
 #include "kernels_last.h"
 #include "kernels_rows.h"

@@ -139,3 +139,4 @@ static void launch_with_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, co
 #include "host_residual.h"
 #include "host_compare.h"
 #include "host_dihedral.h"
+#include "host_blend.h"

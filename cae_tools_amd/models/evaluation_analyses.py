@@ -17,7 +17,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from ..case_ops import (bootstrap_sums, case_baseline, case_compare, case_range, case_spectra, case_ssim, device_operand, fraction_skill,
+from ..case_ops import (bootstrap_table, case_baseline, case_compare, case_range, case_spectra, case_ssim, device_operand, fraction_skill,
                         joint_histogram, pixel_sums, render_cases, strata_sums)
 from ..data.arrays import as_numpy, open_mfdataset
 from ..utils import baseline as baseline_scores
@@ -531,20 +531,6 @@ def check_compare_model(ev):
                                  f"of the {partition} data set")
 
 
-def _bootstrap(table, resamples, seed):
-    """cae_bootstrap_sums of a table of any width: column pieces of at most 32 with the same seed - the units of a resample
-    depend on (seed, resample, n_unit) alone, so the pieces are resampled alike - and resamples in consecutive pieces"""
-    pieces = []
-    for c0 in range(0, table.shape[1], compare_scores.MAX_COLUMNS):
-        part = np.ascontiguousarray(table[:, c0:c0 + compare_scores.MAX_COLUMNS])
-        pieces.append(np.concatenate([bootstrap_sums(part, min(_COMPARE_RESAMPLES, resamples - r0), seed=seed, first=r0)
-                                      for r0 in range(0, resamples, _COMPARE_RESAMPLES)]))
-    return np.concatenate(pieces, axis=1)
-
-
-_COMPARE_RESAMPLES = 1 << 18        # resamples per cae_bootstrap_sums call
-
-
 def _compare(ev, partition, ds, values, report):
     """compare=True (cli/compare.py) asks whether a difference between models survives resampling the cases: the evaluator's
     prediction and the compare_variables - other models' predictions in the same scored files (apply_cae
@@ -568,8 +554,8 @@ def _compare(ev, partition, ds, values, report):
         sums = case_baseline(ev.operand(partition, ds, name), ev.operand(partition, ds, ev.model_output_variable), a,
                              mode=ev.compare_baseline)
         units = compare_scores.units(sums, block)[0]
-        base = compare_scores.baseline_summary(units, _bootstrap(units, resamples, seed), confidence, ev.compare_baseline, name)
-    record = compare_scores.summary(table, _bootstrap(table, resamples, seed), variables, labels, confidence, resamples, seed,
+        base = compare_scores.baseline_summary(units, bootstrap_table(units, resamples, seed), confidence, ev.compare_baseline, name)
+    record = compare_scores.summary(table, bootstrap_table(table, resamples, seed), variables, labels, confidence, resamples, seed,
                                     n_cases=rows.shape[0], plane=int(a.shape[2]) * int(a.shape[3]),
                                     block_variable=ev.compare_block_variable or None, baseline=base)
     _keep(ev, compare_scores, "compare", partition, record, report.setdefault("compare", []))

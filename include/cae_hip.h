@@ -1004,6 +1004,48 @@ int cae_bootstrap_sums(const double* table_dev, int64_t n_unit, int n_col, int64
 int cae_dihedral_rows(const float* src_dev, int64_t n_src, int c, int h, int w, float* dst_dev, int64_t n_dst,
                       const int32_t* row_dev /* NULL: row i */, const int32_t* code_dev, int group /* 4 or 8 */, void* hip_stream);
 
+/* ---- models blended with fitted weights (stateless) ---------------------------------------------- */
+
+/* The error moments a blend is fitted from.  Candidates, target and pair rule are cae_case_compare's: n_pred predictions
+ * P_0 .. P_{M-1} (1 <= M <= 8) in one element kind and the target a, channel 0 of (n_case, plane) operands as stored; a pixel
+ * counts for a case only if a and all M predictions are finite.  In fp64
+ *   e_m = P_m - a,   every product e_i * e_j rounded on its own, nothing contracted into a fused multiply-add
+ *   sums_dev[case] = {n, S e_0 .. S e_{M-1}, S e_i e_j for i <= j in row-major order: (0,0), (0,1), .., (0,M-1), (1,1), ..}
+ * 1 + M + M (M + 1) / 2 doubles over the pairs; n is an exact integer; a case without a pair gets +0.0 everywhere.  The row
+ * is written whole.  With Sw = 1 the blend's error is S w_m e_m, so its mse is w' E w with E_ij = S e_i e_j / n.
+ * Fold order: cae_case_compare's.  Tiles of 64 consecutive pixels, one pixel per lane, a fixed tree over the 64 lanes per
+ * addend, the partials per (case, tile) stored plainly to the workspace, then the tiles of a case by lane j taking tiles j,
+ * j + 64, ... in ascending order and the same tree.  n, S e_m and S e_m e_m therefore carry the bits of cae_case_compare's
+ * columns 0, 2 + 4 m and 4 + 4 m on the same operands, and a case's row does not depend on the other cases of the call, on
+ * n_case or on the operands' alignment.  No atomics: the same arguments give the same bits from run to run.
+ * workspace_dev (16-byte aligned) holds cae_case_error_moments_workspace_bytes = n_case * ceil(plane / 64) * pitch * 8 bytes,
+ * pitch the row's width rounded up to even (0 for an empty or refused shape).  n_case == 0 or plane == 0 succeeds and writes
+ * nothing.  A bad kind, n_pred outside 1 .. 8, negative sizes or strides, NULL pointers, a stride shorter than the plane, an
+ * operand reaching 2^60 elements from its pointer, misaligned pointers, too small or misaligned a workspace: CAE_ERR_ARG,
+ * nothing written. */
+int64_t cae_case_error_moments_workspace_bytes(int64_t n_case, int64_t plane, int n_pred);
+int cae_case_error_moments(const void* const* pred_ptrs /* host array of n_pred device pointers */, int pred_kind,
+                           const int64_t* pred_case_strides /* host array */, int n_pred, const void* actual_dev, int actual_kind,
+                           int64_t actual_case_stride, int64_t n_case, int64_t plane,
+                           double* sums_dev /* [n_case][1 + n_pred + n_pred (n_pred + 1) / 2] */, void* workspace_dev,
+                           int64_t workspace_bytes, void* hip_stream);
+
+/* The blended field: over the case_elems elements (all channels) of every case, in fp64,
+ *   y = intercept;   for m ascending over the candidates with weights[m] != 0:   y = y + weights[m] * P_m
+ * the product and the sum rounded separately, nothing contracted; y is NaN (0x7ff8000000000000) where a candidate with a
+ * weight other than 0 is not finite.  A candidate whose weight is exactly 0 (or -0) is not read and its gaps do not count.  A
+ * numpy loop with the same statement order gives the same bits.  pred_ptrs, pred_case_strides and weights are HOST arrays of
+ * n_pred entries; the candidates share one element kind; out_dev is native fp64, case i at element i * out_case_stride.  One
+ * streaming launch, no workspace, no atomics; 16-byte loads and stores where every operand's cases start on 16-byte boundaries,
+ * element accesses otherwise - the result is the same.  n_case == 0 or case_elems == 0 succeeds and writes nothing.  A bad
+ * kind, n_pred outside 1 .. 8, negative sizes or strides, NULL lists or pointers, a weight or an intercept that is not finite,
+ * a stride shorter than the case, an operand reaching 2^60 elements from its pointer, misaligned pointers: CAE_ERR_ARG, nothing
+ * written. */
+int cae_blend_predictions(const void* const* pred_ptrs /* host array of n_pred device pointers */, int pred_kind,
+                          const int64_t* pred_case_strides /* host array */, int n_pred, const double* weights /* host array */,
+                          double intercept, int64_t n_case, int64_t case_elems, double* out_dev, int64_t out_case_stride,
+                          void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
